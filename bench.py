@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Newton steps/s of the batched interior-point hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no RANK in the environment launches its own N ranks (the parent, before it has
@@ -172,6 +172,37 @@ def cpu_baseline(sample_n):
     return out
 
 
+DUMP_MAX_PROBLEMS = 1 << 20      # problems whose iters, status, vel1, duration0, duration1 are written, over all ranks: 40 MB
+DUMP_STATE_SAMPLE = 1 << 16      # problems whose whole state is written as well, over all ranks: 8.9 MB with the index (F3)
+
+
+def dump_outputs(batch, summary, out_dir, rank=0, world=1):
+    """What a pass of the timed path computed, as a caller of rp_batch_solve reads it back (problem order), into
+    out_dir/<name>.npy (one rank) or out_dir/<name>.rank<r>.npy (rank r of world), float64: each problem's iteration count,
+    status and (vel1, duration0, duration1) -- a seeded sample of DUMP_MAX_PROBLEMS / world of the rank's problems on a
+    larger shard, `problem_index` says which (indices into the shard) -- the whole state of a seeded sample of
+    DUMP_STATE_SAMPLE / world of them (`state_sample_index`), and, from rank 0 only, the summary reduction of the whole run
+    (summary.npy).  The budget is split between the ranks: under 60 MB in all for any number of ranks."""
+    os.makedirs(out_dir, exist_ok=True)
+    state = batch.get_state()
+    iters, status = batch.get_iters()
+    n = len(iters)
+    max_rows, max_sample = max(1, DUMP_MAX_PROBLEMS // world), max(1, DUMP_STATE_SAMPLE // world)
+    rows = np.arange(n) if n <= max_rows else np.sort(np.random.RandomState(SEED + rank).choice(n, max_rows, replace=False))
+    sample = np.sort(np.random.RandomState(SEED + world + rank).choice(n, min(n, max_sample), replace=False))
+    arrays = {"iters": iters[rows], "status": status[rows], "solution": state[rows, :3],
+              "state_sample": state[sample], "state_sample_index": sample}
+    if n > max_rows:
+        arrays["problem_index"] = rows
+    suffix = "" if world == 1 else ".rank%d" % rank
+    files = {name + suffix + ".npy": a for name, a in arrays.items()}
+    if rank == 0:
+        files["summary.npy"] = summary
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(files)
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -232,18 +263,17 @@ def main():
                     help="extra, after the timed region: keep solving batches back to back for at least this many seconds and report the "
                          "steady-state rate with clock / power samples (the device's hwmon files) -- the thermal-steady figure the 4 ms timed region cannot show.  "
                          "Default: 1.5 s on a single-GPU run with extras (it is also what lets an outside sampler see the GPU busy), 0 otherwise")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last pass computed (the arrays a caller of the solve reads back, problem "
+                         "order) as DIR/<name>.npy, float64; the inputs are seeded, so two builds compare output for output.  With N > 1 ranks "
+                         "each writes a seeded sample of its own shard as DIR/<name>.rank<r>.npy: under 60 MB in all for any N")
     args = ap.parse_args()
+
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, rehearsal=args.rehearse_on_one_gpu))
-
-    # The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues, 4 unless the environment says otherwise, and two
-    # streams that land on one queue serialise.  This process owns more than that (the timed batches' stream, the pipeline's two, the
-    # two-stream extras', torch's): with 4 queues the two streams of `end_to_end`'s rp_pipeline can end up sharing one (measured on one box with
-    # four user streams alive: 73 G steps/s against 91 G with 8 queues, profiles/r6_hw_queues.log).  An application's setting, made here by the
-    # application before anything initialises HIP -- the library itself neither reads nor writes the environment; the headline (one stream) is
-    # not affected either way.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
     import torch
     import torch.distributed as dist
@@ -384,6 +414,8 @@ def main():
     else:
         steps_all, conv_all = steps_local, conv_local
     g = sharding.summary_dict(summary)
+    # before anything below solves these batches again
+    dumped = dump_outputs(last, summary.cpu().numpy(), args.dump_outputs, rank, world) if args.dump_outputs else None
     # per rank: launch time from its HIP events, the three host-clock pieces of the timed region, the device it really sat on
     mine = [kernel_ms * K, sustained_ms, (t_kernels - t0) * 1e3, (t_coll - t_kernels) * 1e3, (t_end - t_coll) * 1e3, steps_local]
     my_dev = rp.device_id(local_rank)
@@ -431,9 +463,10 @@ def main():
         "ranks_in_process_group": dist.get_world_size() if grouped else 1,      # what RCCL (torch.distributed "nccl") saw
         "process_group_backend": (dist.get_backend() if grouped else None),    # "nccl" = RCCL; None: no group was created (N = 1 without --force-process-group)
         "self_launched": bool(os.environ.get("RP_BENCH_SELF_LAUNCHED")),
-        "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),      # set to 8 by this program unless the caller's environment had a value (see main)
+        "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),      # as the caller's environment has it; this program does not set it
         "steps": K,
         "warmup": W,
+        "dumped_outputs": dumped,      # rank 0's files under --dump-outputs DIR (None without it)
         # everything launched between the last idle moment and the timed region: the conditioning solves + the W warmup passes the driver asked for
         "untimed_launches_before_timed_region": cond_launches + W,
         "ms_per_step": elapsed / max(K, 1) * 1e3,

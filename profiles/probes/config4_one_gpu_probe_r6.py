@@ -5,7 +5,6 @@ for >= 60 ms before its clock starts and then timed over several passes: the 8 s
 the other on one stream; the same 8 shards as 8 jobs of an rp_pipeline on two streams; ONE batch of 8,388,608.  From bare positions, with
 the summary reduction of every shard; the summaries of the three forms must agree."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # before HIP initialises: streams that share one of the default 4 hardware queues serialise (profiles/r6_hw_queues.log)
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

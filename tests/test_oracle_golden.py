@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_api
+import ref_cases
 from oracle_api import Oracle
 
 
@@ -16,6 +17,12 @@ def _scale_err(a, b):
 @pytest.fixture(scope="module")
 def batch(golden_dir):
     return np.load(os.path.join(golden_dir, "f3_batch.npz"))
+
+
+@pytest.fixture(scope="module")
+def recorded(golden_dir):
+    """The reference's Eigen QR's answers on the systems of tests/ref_cases.py, or their digests (oracle/gen_ref_golden.py)."""
+    return np.load(os.path.join(golden_dir, "ref_outputs.npz"))
 
 
 def test_fixture_inputs_are_the_seeded_generator(batch, oracle):
@@ -105,96 +112,76 @@ def test_f4_single_steps(golden_dir, oracle):
     assert worst < 1e-9
 
 
-@pytest.mark.skipif(not oracle_api.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
-def test_own_qr_against_reference_eigen_qr(batch):
-    orc = Oracle(eigen=True)
-    rng = np.random.RandomState(3)
+def test_own_qr_against_reference_eigen_qr(batch, oracle, recorded):
+    """The oracle's own QR against the reference's Eigen QR, whose answers are recorded in tests/golden/ref_outputs.npz
+    (oracle/gen_ref_golden.py) and recomputed wherever oracle/_ref is built."""
+    kkt, generic, residuals = ref_cases.qr_cases(oracle, batch["init"])
+    orc_e = Oracle(eigen=True) if oracle_api.have_ref() else None
     # KKT systems along real trajectories
-    for i in rng.choice(len(batch["init"]), 40, replace=False):
-        v = batch["init"][i].copy()
-        for s in range(12):
-            M, r, _ = orc.kkt(3, v)
-            x_own, nz_own = orc.qr_solve(M, -r)
-            x_ref, nz_ref = orc.ref_qr_solve(M, -r)
-            assert nz_own == nz_ref == 11
-            assert np.max(np.abs(x_own - x_ref) / np.maximum(np.abs(x_ref), 1e-3 * np.max(np.abs(x_ref)))) < 1e-6
-            # both are backward stable: compare residuals of the linear system
-            assert np.linalg.norm(M @ x_own + r) <= 1e-9 * (np.linalg.norm(M) * np.linalg.norm(x_own) + np.linalg.norm(r))
-            orc.step(3, v)
+    assert len(kkt) == len(recorded["kkt_x"]) == len(recorded["kkt_nonzero_pivots"])
+    for (M, b), x_ref, nz_ref in zip(kkt, recorded["kkt_x"], recorded["kkt_nonzero_pivots"]):
+        if orc_e is not None:
+            x_live, nz_live = orc_e.ref_qr_solve(M, b)
+            assert nz_live == nz_ref and np.array_equal(x_live, x_ref)
+        x_own, nz_own = oracle.qr_solve(M, b)
+        assert nz_own == nz_ref == 11
+        assert np.max(np.abs(x_own - x_ref) / np.maximum(np.abs(x_ref), 1e-3 * np.max(np.abs(x_ref)))) < 1e-6
+        # both are backward stable: compare residuals of the linear system
+        assert np.linalg.norm(M @ x_own - b) <= 1e-9 * (np.linalg.norm(M) * np.linalg.norm(x_own) + np.linalg.norm(b))
     # generic random systems, fixed- and dynamic-size code paths
-    for n in (3, 4, 7, 8, 11):
-        A = rng.randn(n, n)
-        b = rng.randn(n)
-        x_own, _ = orc.qr_solve(A, b)
-        x_ref, _ = orc.ref_qr_solve(A, b)
-        x_dyn, _ = orc.ref_qr_solve(A, b, force_dynamic=True)
+    at = 0
+    for A, b in generic:
+        n = len(b)
+        x_ref, x_dyn = recorded["generic_x"][at:at + n], recorded["generic_x_dynamic"][at:at + n]
+        at += n
+        if orc_e is not None:
+            assert np.array_equal(orc_e.ref_qr_solve(A, b)[0], x_ref)
+            assert np.array_equal(orc_e.ref_qr_solve(A, b, force_dynamic=True)[0], x_dyn)
+        x_own, _ = oracle.qr_solve(A, b)
         assert np.allclose(x_own, x_ref, rtol=1e-9, atol=1e-11)
         assert np.allclose(x_dyn, x_ref, rtol=1e-9, atol=1e-11)
+    assert at == len(recorded["generic_x"])
     # the squared-norm emulation used by the Armijo test is Eigen's, bit for bit: compare
     # residualNorm (emulated reduction order) with Eigen's squaredNorm of the same residual
-    import ctypes
-    res = orc.lib.orc_residual
-    res.argtypes = [ctypes.c_int, oracle_api._dp, ctypes.c_double, oracle_api._dp]
-    for i in rng.choice(len(batch["init"]), 60, replace=False):
-        v = batch["init"][i].copy()
-        for s in range(10):
-            p = orc.gap(3, v) / 80.0
-            r = np.zeros(11)
-            res(3, v.ctypes.data_as(oracle_api._dp), p, r.ctypes.data_as(oracle_api._dp))
-            assert orc.ref.ref_squared_norm(11, r.ctypes.data_as(oracle_api._dp)) == orc.residual_norm(3, v, p)
-            orc.step(3, v)
+    assert len(residuals) == len(recorded["residual_squared_norm"])
+    for (v, p, r), sq in zip(residuals, recorded["residual_squared_norm"]):
+        if orc_e is not None:
+            assert orc_e.ref.ref_squared_norm(11, r.ctypes.data_as(oracle_api._dp)) == sq
+        assert oracle.residual_norm(3, v, p) == sq
 
 
-@pytest.mark.skipif(not oracle_api.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
-def test_own_qr_against_reference_eigen_on_feasibility_gram_systems():
+def test_own_qr_against_reference_eigen_on_feasibility_gram_systems(oracle, recorded):
     """moveTowardFeasibility solves a = G G^T by the DYNAMIC-size Eigen QR (onedpath_ip.cpp:676-693).  The oracle's QR in
     its dynamic form (orc_colpiv_qr_solve_dynamic: Eigen's run-time-sized reduction orders) reproduces the reference's
     Eigen bit for bit on Gram systems of 1, 2, 3 AND 4 violated rows.  Four rows of three-variable gradients give a
     matrix that is singular in exact arithmetic: its last pivot is rounding noise, and only the same sequence of
     roundings gives the same answer -- round 2's fixed-size ordering agreed on half of such systems, which is what
-    this test used to record.  (The whole move against the reference's own function: tests/test_oracle_reference.py.)"""
-    import rocket_path_amd as rp
-    orc = Oracle(eigen=True)
-    rng = np.random.RandomState(5)
+    this test used to record.  (The whole move against the reference's own function: tests/test_oracle_reference.py.)
+    Eigen's answers: tests/golden/ref_outputs.npz, recomputed wherever oracle/_ref is built."""
+    orc_e = Oracle(eigen=True) if oracle_api.have_ref() else None
+    counts = {v: {1: 0, 2: 0, 3: 0, 4: 0} for v in (3, 4)}
+    fixed_form_equal = {3: [], 4: []}
+    xs, nzs = [], []
+    for variant, A, e in ref_cases.gram_systems(oracle):
+        n = len(e)
+        x_own, nz_own = oracle.qr_solve(A, e, dynamic=True)
+        assert np.all(np.isfinite(x_own))
+        if orc_e is not None:
+            x_ref, nz_ref = orc_e.ref_qr_solve(A, e, force_dynamic=True)
+            assert nz_own == nz_ref and np.array_equal(x_own, x_ref), (variant, n)
+        counts[variant][n] += 1
+        if n == 4:
+            x_fix, nz_fix = oracle.qr_solve(A, e)
+            fixed_form_equal[variant].append(np.array_equal(x_fix, x_own) and nz_fix == nz_own)
+        xs.append(x_own)
+        nzs.append(nz_own)
+    # every answer and pivot count is Eigen's, bit for bit
+    assert ref_cases.digest(np.concatenate(xs), np.array(nzs, dtype=np.int32)) == str(recorded["gram_sha256"])
     for variant in (3, 4):
-        m = orc.num_constraints(variant)
-        n_prob = 3600
-        p0, p1, p2 = rp.problems.generate(36, 0, n_prob, 0)
-        aos = orc.batch_init_feasible(variant, p0, p1, p2)
-        short = rng.uniform(0.3, 1.2, (n_prob, 2))
-        aos[:, 1] *= short[:, 0]
-        aos[:, 2] *= short[:, 1]
-        aos[:, 0] = rng.uniform(-50, 250, n_prob)
-        aos[::2, 0] = rng.uniform(-5, 5, len(aos[::2]))
-        aos[::2, 1:3] *= 0.6
-        equal = {1: [], 2: [], 3: [], 4: []}
-        fixed_form_equal = []
-        for row in aos:
-            rows = [orc.constraint(variant, i, row) for i in range(m)]
-            viol = [(e, g) for e, g in rows if e > 0]
-            if not viol:
-                continue
-            G = np.array([g for _, g in viol])
-            e = np.array([x for x, _ in viol])
-            n = len(e)
-            A = np.zeros((n, n))
-            for i in range(n):
-                for j in range(n):
-                    acc = 0.0
-                    for k in range(3):
-                        acc += G[i, k] * G[j, k]
-                    A[i, j] = acc
-            x_own, nz_own = orc.qr_solve(A, e, dynamic=True)
-            x_ref, nz_ref = orc.ref_qr_solve(A, e, force_dynamic=True)
-            assert np.all(np.isfinite(x_own)) and np.all(np.isfinite(x_ref))
-            equal[n].append(np.array_equal(x_own, x_ref) and nz_own == nz_ref)
-            if n == 4:
-                x_fix, nz_fix = orc.qr_solve(A, e)
-                fixed_form_equal.append(np.array_equal(x_fix, x_ref) and nz_fix == nz_ref)
         for n in (1, 2, 3):
-            assert len(equal[n]) > 20 and all(equal[n]), (variant, n)
-        assert len(equal[4]) >= 2000 and all(equal[4]), (variant, len(equal[4]), np.mean(equal[4]))
-        assert np.mean(fixed_form_equal) < 0.9      # the order matters: the fixed-size form is NOT the reference here
+            assert counts[variant][n] > 20, (variant, n)
+        assert counts[variant][4] >= 2000, (variant, counts[variant][4])
+        assert np.mean(fixed_form_equal[variant]) < 0.9      # the order matters: the fixed-size form is NOT the reference here
 
 
 def test_multipliers_at_the_gate_are_pinned_where_they_are_well_conditioned(batch, oracle):
