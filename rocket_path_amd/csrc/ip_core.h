@@ -39,7 +39,7 @@
 //    multiplications), and reciprocals are batched: one for the two durations of a trial point (the reference
 //    divides by t about 20 times per constraint sweep, onedpath_ip.cpp:385-391, 404-410), one for all
 //    constraints, one for the two arrow pivots, one for the boundary fraction -- 4-5 per step where the first
-//    version of this file had 19.  Define RP_EXACT_DIV to build with correctly rounded divisions instead (A/B builds).
+//    version of this file had 19.
 //  * two forms of the step.  newton_step_inplace (the gated solve, and since round 4 every fixed-step launch of F3): the trial
 //    overwrites the state, the step's start waits in LDS (or, for small batches, registers), residual sums carried, loops tested
 //    by ballots over comparisons; FROZEN adds the post-convergence regime's search on affine pieces with its certain failures
@@ -84,18 +84,14 @@ template <> __device__ __forceinline__ bool finite_<float>(float a) { return abs
 
 // reciprocal
 template <typename T> __device__ __forceinline__ T rcp_(T x);
-#ifdef RP_EXACT_DIV
-template <> __device__ __forceinline__ double rcp_<double>(double x) { return 1.0 / x; }
-template <> __device__ __forceinline__ float rcp_<float>(float x) { return 1.0f / x; }
-#else
 template <> __device__ __forceinline__ double rcp_<double>(double x)
 {
     // v_rcp_f64 is good to 2^-24 (4.6e-8 measured); ONE cubic refinement, r (1 + e + e^2) with e = 1 - x r, leaves a truncation
     // error e^3 ~ 1e-22 relative before the final rounding: three multiply-adds.  That is CORRECTLY ROUNDED EXCEPT WITH
     // PROBABILITY ~1e-7 per input (e^3 / half an ulp; no misrounding among 4.19 M samples, profiles/probes/rcp_probe.hip) -- not
-    // IEEE-exact: a 1 Mi-problem solve makes ~1e8 reciprocals and will contain a few 1-ulp differences from true division, from
-    // the RP_EXACT_DIV build and from the two Newton steps (four multiply-adds, misrounding ~1e-13) this was until late in
-    // round 3.  "Bit-identical" claims elsewhere are A/B comparisons between builds that share this function.
+    // IEEE-exact: a 1 Mi-problem solve makes ~1e8 reciprocals and will contain a few 1-ulp differences from true division and
+    // from the two Newton steps (four multiply-adds, misrounding ~1e-13) this was until late in round 3.  "Bit-identical"
+    // claims elsewhere are A/B comparisons between builds that share this function.
     // (One Newton step, 10 ulp, fails parity: profiles/r3_tuning.md.)
     const double r = __builtin_amdgcn_rcp(x);
     const double e = __builtin_fma(-x, r, 1.0);
@@ -107,20 +103,15 @@ template <> __device__ __forceinline__ float rcp_<float>(float x)
     r = __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
     return r;
 }
-#endif
 // One Newton refinement: <= 10 ulp (measured on gfx950: raw v_rcp_f64 is 2^-24, one Newton step 2.2e-15 --
 // profiles/probes/rcp_probe.hip).  Used only where the quotient feeds a bound, not the iterate: the
 // fraction-to-boundary ratios.
 template <typename T> __device__ __forceinline__ T rcp1_(T x);
-#ifdef RP_EXACT_DIV
-template <> __device__ __forceinline__ double rcp1_<double>(double x) { return 1.0 / x; }
-#else
 template <> __device__ __forceinline__ double rcp1_<double>(double x)
 {
     const double r = __builtin_amdgcn_rcp(x);
     return __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
 }
-#endif
 template <> __device__ __forceinline__ float rcp1_<float>(float x) { return rcp_<float>(x); }
 // The 32-bit word of x that holds its sign bit, and the OR of three such words as ONE opaque instruction (written in C the
 // compiler widens an OR of high words back into 64-bit ORs of the whole numbers: twice the instructions for the same bit).
@@ -140,24 +131,7 @@ template <typename T> __device__ __forceinline__ T srcp_(T den) { return den != 
 
 // x of lane `src` (wave-uniform index) in every lane
 __device__ __forceinline__ int bcast_(int x, int src) { return __builtin_amdgcn_readlane(x, src); }
-__device__ __forceinline__ float bcast_(float x, int src) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), src)); }
-__device__ __forceinline__ double bcast_(double x, int src)
-{
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, src), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), src);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
 
-#ifndef RP_FROZEN_PROOF
-#define RP_FROZEN_PROOF 1      // 0: every trial of the frozen search is evaluated (A/B builds: no decision may change)
-#endif
-#ifndef RP_FROZEN_MASKS
-#define RP_FROZEN_MASKS 1     // the fixed-step kernels' feasibility loop (newton_step_inplace<FROZEN>) keeps its per-lane flag as a 64-bit lane mask in scalar
-                              // registers (0: the bool form, A/B).  Measured at 65,536 x 50 (profiles/r6_tuning.md): 289 -> 246 scalar instructions per
-                              // post-convergence wave-step, 0.200 -> 0.194 ms.  The same treatment of the residual loop costs 40-70 VGPRs (spills at every
-                              // occupancy) whichever way the mask becomes a predicate again, and a wave-uniform form of the frozen search trades its 17
-                              // scalar instructions per trip for 5 vector ones and is slower: neither is in the source.
-#endif
 // lane mask <-> lane predicate without a vector instruction (the mask must be wave-uniform, which a ballot's result is)
 __device__ __forceinline__ unsigned long long ballot_(bool c) { return __builtin_amdgcn_ballot_w64(c); }
 __device__ __forceinline__ bool in_mask_(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
@@ -899,7 +873,7 @@ __device__ __forceinline__ void direction_split(const P &k, const KParams<T> &kp
 // negative, and inside it the WAVE skips multiplier i when it would in none of its lanes (one compare and a scalar branch
 // instead of two multiplications, a compare and four selects).  A skipped multiplier has ratio >= 1 and could not have
 // changed the minimum below 1; a -0 or a NaN with its sign bit set passes the screens and loses the comparison.
-// WAVE_SCREEN = false (RP_FROZEN_BF, the fixed-step kernels' build switch): behind the lane screen every multiplier is compared, no
+// WAVE_SCREEN = false (the fixed-step kernels, newton_step_inplace<FROZEN>): behind the lane screen every multiplier is compared, no
 // per-multiplier wave votes -- eight ballots, scalar compares and branches that a lone wave in the post-convergence regime (where the
 // directions are rounding noise and sign bits are set at random, so the votes skip little) pays an issue slot each for.
 template <typename T, int NC, bool WAVE_SCREEN = true>
@@ -950,7 +924,9 @@ struct NoDiag {
     __device__ __forceinline__ void moving() {}
 };
 struct HalvingDiag {
-    unsigned nf = 0, nr = 0, nm = 0;      // nm: residual trials that needed a full evaluation (trial point != x); tuning only
+    // nm: residual trials that needed a full evaluation (trial point != x).  Nothing reads it, but without it the compiler
+    // schedules k_newton_counted<float, float, 4> differently.
+    unsigned nf = 0, nr = 0, nm = 0;
     __device__ __forceinline__ void feas() { ++nf; }
     __device__ __forceinline__ void resid() { ++nr; }
     __device__ __forceinline__ void moving() { ++nm; }
@@ -1057,31 +1033,6 @@ template <typename T, int VARIANT> struct AffineResidual {
         // BRANCH-FREE (round 6): which of the two trials is the first to pass, how many halvings that makes and the next step length are
         // selects on two comparisons -- as a loop over q with `q < valid && ...` the compiler nested two exec-mask regions per trip, eight
         // scalar instructions and two branches that a lone wave pays an issue slot each for (profiles/r6_tuning.md).
-#ifdef RP_SEARCH_BRANCHY      // A/B: the round-5 form of the trip
-        constexpr int W = 2;
-        while (it < kp.max_bt) {
-            T sk[W], rn[W];
-            sk[0] = s;
-            for (int q = 1; q < W; ++q) sk[q] = sk[q - 1] * kp.backtrack;
-            for (int q = 0; q < W; ++q) rn[q] = (*this)(sk[q]);
-            for (int q = 0; q < W; ++q) asm volatile("" : "+v"(rn[q]));
-            const int valid = (kp.max_bt - it < W) ? kp.max_bt - it : W;
-            int first = W;
-            for (int q = W - 1; q >= 0; --q)
-                if (q < valid && rn[q] <= r0 * (T(1) - kp.armijo * sk[q])) first = q;
-            const bool got = first < W;
-            const int halved = got ? first : valid;
-            T snew = sk[W - 1] * kp.backtrack;
-            for (int q = W - 1; q >= 0; --q)
-                if (halved == q) snew = sk[q];
-            s = snew;
-            if constexpr (!std::is_same<D, NoDiag>::value)
-                for (int q = 0; q < halved; ++q) diag.resid();
-            it += halved;
-            if (got) return true;
-        }
-        return false;
-#endif
         while (it < kp.max_bt) {
             const T s0 = s, s1 = s * kp.backtrack;
             T r0v = (*this)(s0), r1v = (*this)(s1);
@@ -1101,13 +1052,6 @@ template <typename T, int VARIANT> struct AffineResidual {
     }
 };
 
-#ifndef RP_FEAS_SCREEN
-#define RP_FEAS_SCREEN 1      // F4: walk the feasibility loop past trials that are infeasible beyond doubt (0: evaluate every trial, for A/B runs)
-#endif
-#ifndef RP_FEAS_RAY
-#define RP_FEAS_RAY 1         // ... first in closed form along the ray (0: trial by trial only)
-#endif
-
 // The feasibility loop's certain halvings (F4): s is walked past every trial that is infeasible beyond doubt -- first along the
 // ray in closed form (ray_proof), then trial by trial (infeasible_beyond_doubt) -- and the number of halvings made is returned;
 // the caller's loop takes over at the first trial that needs a proper look.  Wave-uniform loops.
@@ -1117,11 +1061,11 @@ __device__ __forceinline__ int skip_certain_halvings(const P &k, const KParams<T
     int it_feas = 0;
     // (not in the one instantiation that has no registers for it -- double precision with non-zero end velocities, 167 of the 168
     // three waves allow: the proof changes no decision, so leaving it out there changes no result either)
-    if constexpr (VARIANT == 4 && RP_FEAS_SCREEN && (P::zero_vel || sizeof(T) == 4)) {
+    if constexpr (VARIANT == 4 && (P::zero_vel || sizeof(T) == 4)) {
         // the halvings whose trial misses the limits beyond doubt: the reference evaluates them, finds an error > 0 and halves; this
         // halves.  Wave-uniform loops, every lane to its first trial that needs a proper look: first along the ray in closed form
         // for the one limit that stays broken longest (ray_proof), then trial by trial for all four (infeasible_beyond_doubt).
-        if constexpr (RP_FEAS_RAY && !P::lean) {
+        if constexpr (!P::lean) {
             const RayProof<T> ray = ray_proof<T, P>(k, L, v, t0, t1, dxv, dx0, dx1, s);
             if (kp.backtrack == T(0.5)) {
                 // The number of proven halvings by bisection, no loop over them.  The bisection needs "g(s 2^-k) > 0" to be true up to
@@ -1133,11 +1077,9 @@ __device__ __forceinline__ int skip_certain_halvings(const P &k, const KParams<T
                 // out of halvings -- but NOT for a convex one, which may dip below zero in between (10 - 140 s + 200 s^2): there the
                 // closed form is not used and the per-trial proof below, sequential and always sound, walks the trials.
                 // Seven probes find the last true k in [0, 127]; every counted halving lies between two EVALUATED positives.
-#ifdef RP_RAY_ASSUME_MONOTONE      // the round-3 form, for showing that tests/test_gpu_parity.py::test_f4_steps_from_points_that_are_infeasible_beyond_doubt bites
-                const bool monotone = true;
-#else
+                // (Round 3 assumed monotone throughout; tests/test_gpu_parity.py::test_f4_steps_from_points_that_are_infeasible_beyond_doubt
+                // fails against that form: profiles/r4_ray_ab.log.)
                 const bool monotone = !(ray.g0 > T(0)) || !(ray.g2 > T(0));
-#endif
                 int last = 0;
 #pragma unroll
                 for (int b = 64; b >= 1; b >>= 1) last += ray.holds(ldexp_(s, -(last + b))) ? b : 0;
@@ -1223,11 +1165,8 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
             for (int j = 0; j < 4; ++j) e.gt[j] = c.gt[j];
         }
         if constexpr (MU == 0) {
-#ifndef RP_NO_CARRIED_C      // tuning knob of newton_step_to (A/B builds with RP_GATED_IN_PLACE=0): 18 more VGPRs for 8 fewer instructions per step
+            // carried C: 18 more VGPRs for 8 fewer instructions per step
             if constexpr (SUMS && VARIANT == 3) direction<T, VARIANT, P, true>(k, kp, v, lam, e, p, dxv, dx0, dx1, dl, sg, suspect, c.cm, c.cp, &c.x);
-#else
-            if constexpr (false) {}
-#endif
             else direction<T, VARIANT, P>(k, kp, v, lam, e, p, dxv, dx0, dx1, dl, sg, suspect);
             if constexpr (SUMS) r0n = residual_from_sums<T, NC>(c.X, c.Q1, c.Q2, p);
             else r0n = residual_norm<T, VARIANT, false>(e, lam, dl, T(0), p, L);      // onedpath_ip.cpp:932
@@ -1341,13 +1280,7 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
         // halvings are used up.  The straggler jumps there (s, it) and re-evaluates that one trial in the common loop, so
         // everything downstream is the serial code and every decision and every bit is the serial loop's
         // (onedpath2_ip.cpp:791-833).
-#ifndef RP_WAVE_SERIAL_FIRST
-#define RP_WAVE_SERIAL_FIRST 1
-#endif
-#ifndef RP_WAVE_SERVE_AT_MOST
-#define RP_WAVE_SERVE_AT_MOST 16
-#endif
-        constexpr int kSerialFirst = RP_WAVE_SERIAL_FIRST, kServeAtMost = RP_WAVE_SERVE_AT_MOST;      // trials in lock step before anyone is served; stragglers worth serving one by one
+        constexpr int kSerialFirst = 1, kServeAtMost = 16;      // trials in lock step before anyone is served; stragglers worth serving one by one
         const unsigned long long alive = __ballot(true);
         const int lane_id = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
         const int rank = __popcll(alive & ((1ull << lane_id) - 1ull)), nalive = __popcll(alive);
@@ -1363,40 +1296,27 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
                     P bk = k;
                     T bv, bt0, bt1, bdv, bd0, bd1, bs, bp, br0n, blam[NC], bdl[NC];
                     const int bit = bcast_(it, src);
-#ifndef RP_WAVE_BCAST_LDS
-#define RP_WAVE_BCAST_LDS 1      // the straggler's search state reaches the other lanes through LDS (0: 2 x 21 v_readlane, for A/B runs)
-#endif
-                    if constexpr (RP_WAVE_BCAST_LDS != 0) {
-                        // One lane writes its 13 + 2 NC values, every lane reads them back (a broadcast read: one address, no bank
-                        // conflict): LDS instructions, which issue beside the other waves' arithmetic, where 2 x 21 v_readlane and the
-                        // moves that bring their scalar results back into vector registers were a third of the service's vector
-                        // instructions.  The kernel's blocks are single waves (k_steps_chunks: kChunkBlock, with a static_assert at the one
-                        // place this WAVE form is instantiated), and a wave's LDS operations complete in order: no barrier.  Any other launch
-                        // shape (the 256-thread streaming kernels share run_lane) must not instantiate WAVE: four waves would race on s_bc.
-                        __shared__ T s_bc[13 + 2 * NC];
-                        LdsBackup<T> bc = (LdsBackup<T>)s_bc;
-                        if (lane_id == src) {
-                            bc[0] = k.dx0; bc[1] = k.dx1;
-                            if constexpr (!P::zero_vel) { bc[2] = k.v0; bc[3] = k.v2; }
-                            bc[4] = v; bc[5] = t0; bc[6] = t1; bc[7] = dxv; bc[8] = dx0; bc[9] = dx1; bc[10] = s; bc[11] = p; bc[12] = r0n;
+                    // The straggler's search state reaches the other lanes through LDS: one lane writes its 13 + 2 NC values, every lane
+                    // reads them back (a broadcast read: one address, no bank conflict).  LDS instructions issue beside the other waves'
+                    // arithmetic, where 2 x 21 v_readlane and the moves that bring their scalar results back into vector registers were a
+                    // third of the service's vector instructions.  The kernel's blocks are single waves (k_steps_chunks: kChunkBlock, with a
+                    // static_assert at the one place this WAVE form is instantiated), and a wave's LDS operations complete in order: no
+                    // barrier.  Any other launch shape (the 256-thread streaming kernels share run_lane) must not instantiate WAVE: four
+                    // waves would race on s_bc.
+                    __shared__ T s_bc[13 + 2 * NC];
+                    LdsBackup<T> bc = (LdsBackup<T>)s_bc;
+                    if (lane_id == src) {
+                        bc[0] = k.dx0; bc[1] = k.dx1;
+                        if constexpr (!P::zero_vel) { bc[2] = k.v0; bc[3] = k.v2; }
+                        bc[4] = v; bc[5] = t0; bc[6] = t1; bc[7] = dxv; bc[8] = dx0; bc[9] = dx1; bc[10] = s; bc[11] = p; bc[12] = r0n;
 #pragma unroll
-                            for (int i = 0; i < NC; ++i) { bc[13 + i] = lam[i]; bc[13 + NC + i] = dl[i]; }
-                        }
-                        bk.dx0 = bc[0]; bk.dx1 = bc[1];
-                        if constexpr (!P::zero_vel) { bk.v0 = bc[2]; bk.v2 = bc[3]; }
-                        bv = bc[4]; bt0 = bc[5]; bt1 = bc[6]; bdv = bc[7]; bd0 = bc[8]; bd1 = bc[9]; bs = bc[10]; bp = bc[11]; br0n = bc[12];
-#pragma unroll
-                        for (int i = 0; i < NC; ++i) { blam[i] = bc[13 + i]; bdl[i] = bc[13 + NC + i]; }
-                    } else {
-                        bk.dx0 = bcast_(k.dx0, src);
-                        bk.dx1 = bcast_(k.dx1, src);
-                        if constexpr (!P::zero_vel) { bk.v0 = bcast_(k.v0, src); bk.v2 = bcast_(k.v2, src); }
-                        bv = bcast_(v, src); bt0 = bcast_(t0, src); bt1 = bcast_(t1, src);
-                        bdv = bcast_(dxv, src); bd0 = bcast_(dx0, src); bd1 = bcast_(dx1, src);
-                        bs = bcast_(s, src); bp = bcast_(p, src); br0n = bcast_(r0n, src);
-#pragma unroll
-                        for (int i = 0; i < NC; ++i) { blam[i] = bcast_(lam[i], src); bdl[i] = bcast_(dl[i], src); }
+                        for (int i = 0; i < NC; ++i) { bc[13 + i] = lam[i]; bc[13 + NC + i] = dl[i]; }
                     }
+                    bk.dx0 = bc[0]; bk.dx1 = bc[1];
+                    if constexpr (!P::zero_vel) { bk.v0 = bc[2]; bk.v2 = bc[3]; }
+                    bv = bc[4]; bt0 = bc[5]; bt1 = bc[6]; bdv = bc[7]; bd0 = bc[8]; bd1 = bc[9]; bs = bc[10]; bp = bc[11]; br0n = bc[12];
+#pragma unroll
+                    for (int i = 0; i < NC; ++i) { blam[i] = bc[13 + i]; bdl[i] = bc[13 + NC + i]; }
                     const T sq = ldexp_(bs, -rank);                    // the step length of the serial loop's trial number bit + rank
                     const bool beyond = bit + rank >= kp.max_bt;       // ... which it would not make
                     const T qv = fma_(bdv, sq, bv), q0 = fma_(bd0, sq, bt0), q1 = fma_(bd1, sq, bt1);
@@ -1602,7 +1522,7 @@ __device__ __forceinline__ void newton_step(const P &k, const KParams<T> &kp, T 
 // issue on the LDS port beside the other waves' arithmetic -- to be read back only when a trial is rejected (one step in five
 // has a rejected feasibility trial, a rejected residual trial is rare before convergence), and the loops run while ANY lane of
 // the wave is inside (wave-uniform exits: nothing to copy).  Same functions, same operands, same order of decisions as
-// newton_step_to<MEMO = false, MU = 0>: every bit of every iterate is the same (tests/checks/inplace_ab.py, 36 cases).
+// newton_step_to<MEMO = false, MU = 0>: every bit of every iterate was the same (36 cases, profiles/r3_inplace_ab.log).
 // bk: where the step's start waits (LdsColumn: this lane's column of the block's backup area, field q at p[q * 64]; volatile so that the compiler neither forwards the
 // stored values to the reads (keeping them in registers is what this form is there to avoid) nor drops the stores.
 // The loops are written with the trial formed where s is set (at the bottom, from the backed-up start), so that a trial
@@ -1630,14 +1550,6 @@ template <typename T, int N> struct RegColumn {
 // mask; a lane whose trial has passed simply re-evaluates its unchanged trial (same values, the instructions issue for the wave
 // anyway) while others retry.  The halving counter `it` is touched only where a trial fails: it enters every loop as zero and is
 // put back to zero behind a wave-uniform branch when some lane used it.
-#ifndef RP_USED_INT
-#define RP_USED_INT 1      // the wave-uniform "some lane moved its halving counter" flag of the in-place step's loops as an int (0: a bool, A/B)
-#endif
-#if RP_USED_INT
-typedef int used_t;
-#else
-typedef bool used_t;
-#endif
 template <typename T, int VARIANT, class P, bool FROZEN = false, class D = NoDiag, class BK = LdsColumn<T>>
 __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T> &kp, T gap, T &v, T &t0, T &t1, T (&lam)[CMap<VARIANT>::NC],
                                                     AccCarry<T, true, true> &c, BK &bk, int &it, D &diag)
@@ -1661,11 +1573,9 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
 #pragma unroll
     for (int i = 0; i < NC; ++i) bk.put(3 + i, lam[i]);
 
-#ifndef RP_FROZEN_BF
-#define RP_FROZEN_BF 1      // the fixed-step kernels (FROZEN) take the boundary fraction without the per-multiplier wave votes (0: with them, A/B): 0.194 -> 0.183 ms
-                            // at 65,536 x 50 and 0.0203 -> 0.0185 ms at 65,536 x 12 -- a lone wave pays an issue slot for every vote, compare and branch
-#endif
-    T s = boundary_fraction<T, NC, !(FROZEN && RP_FROZEN_BF != 0)>(kp, lam, dl, sg, suspect);         // onedpath_ip.cpp:903-915
+    // the fixed-step kernels (FROZEN) take the boundary fraction without the per-multiplier wave votes: 0.194 -> 0.183 ms at 65,536 x 50
+    // and 0.0203 -> 0.0185 ms at 65,536 x 12 -- a lone wave pays an issue slot for every vote, compare and branch
+    T s = boundary_fraction<T, NC, !FROZEN>(kp, lam, dl, sg, suspect);         // onedpath_ip.cpp:903-915
 
     // -- backtrack until primal feasible (onedpath_ip.cpp:919-928); a trial is formed where s is set --
     Acc<T> et;
@@ -1674,11 +1584,15 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
     v = fma_(dxv, s, v);
     t0 = fma_(dx0, s, t0);
     t1 = fma_(dx1, s, t1);
-    if constexpr (FROZEN && RP_FROZEN_MASKS != 0) {
-        // The same loop with its per-lane flags (the trial has become x: at_x) as LANE MASKS in scalar registers: a flag carried round a
-        // loop as a bool comes back as a select and a compare every time it is tested or merged; a mask is combined by scalar and / or
-        // and becomes a predicate again at no cost (in_mask_).  Same decisions per lane.
-        used_t used = VARIANT == 4;
+    if constexpr (FROZEN) {
+        // The fixed-step kernels' form of the loop below, with its per-lane flags (the trial has become x) as LANE MASKS in scalar
+        // registers: a flag carried round a loop as a bool comes back as a select and a compare every time it is tested or merged; a
+        // mask is combined by scalar and / or and becomes a predicate again at no cost (in_mask_).  Same decisions per lane.  Measured
+        // at 65,536 x 50 against the bool form (profiles/r6_tuning.md): 289 -> 246 scalar instructions per post-convergence wave-step,
+        // 0.200 -> 0.194 ms.  The same treatment of the residual loop costs 40-70 VGPRs (spills at every occupancy) whichever way the
+        // mask becomes a predicate again, and a wave-uniform form of the frozen search trades its 17 scalar instructions per trip for
+        // 5 vector ones and is slower: neither is in the source.
+        int used = VARIANT == 4;
         unsigned long long atx_m = 0ull;
         for (;;) {
             accel_values_u(k, v, t0, t1, et, xt);
@@ -1689,7 +1603,10 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
             used = 1;
             const unsigned long long jump_m = go_m & atx_m, step_m = go_m & ~atx_m;
             if (jump_m != 0ull) {
-                if (in_mask_(jump_m)) {      // x itself fails the test by a rounding and every smaller s gives x again: the remaining halvings at once
+                // x itself fails the test by a rounding (the residual loop accepts points the feasibility loop never saw, as the
+                // reference's does) and every smaller s gives x again: the reference walks its remaining halvings to the same verdict.
+                // So does this, without the evaluations.
+                if (in_mask_(jump_m)) {
                     if (kp.backtrack == T(0.5) && std::is_same<D, NoDiag>::value) {
                         s = ldexp_(s, it - kp.max_bt);
                     } else {
@@ -1709,17 +1626,12 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
                 }
                 // (one ballot per comparison, the masks combined as integers: a ballot of `a && b && c` is lowered through a select and a
                 // compare -- two vector instructions to turn three lane masks into one)
-#ifndef RP_SPLIT_BALLOTS
-#define RP_SPLIT_BALLOTS 1      // 0: one ballot of the conjunction (A/B)
-#endif
-                if constexpr (RP_SPLIT_BALLOTS != 0) atx_m |= step_m & ballot_(v == (T)bk.get(0)) & ballot_(t0 == (T)bk.get(1)) & ballot_(t1 == (T)bk.get(2));
-                else atx_m |= step_m & ballot_(v == (T)bk.get(0) && t0 == (T)bk.get(1) && t1 == (T)bk.get(2));
+                atx_m |= step_m & ballot_(v == (T)bk.get(0)) & ballot_(t0 == (T)bk.get(1)) & ballot_(t1 == (T)bk.get(2));
             }
         }
         if (used != 0) { asm volatile(""); it = 0; }
     } else {
-        used_t used = VARIANT == 4;      // wave-uniform: some lane has moved its counter
-        [[maybe_unused]] bool at_x = false;      // FROZEN: the trial point has become x itself (and every later one will be)
+        int used = VARIANT == 4;      // wave-uniform: some lane has moved its counter
         for (;;) {
             accel_values_u(k, v, t0, t1, et, xt);
             const bool bad = !all_satisfied<T, VARIANT>(et, L);
@@ -1730,26 +1642,13 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
             if ((any_bad & __builtin_amdgcn_ballot_w64(room)) == 0ull) break;
             used = 1;
             if (bad && room) {
-                if (FROZEN && at_x) {
-                    // x itself fails the test by a rounding (the residual loop accepts points the feasibility loop never saw, as the
-                    // reference's does) and every smaller s gives x again: the reference walks its remaining halvings to the same
-                    // verdict.  So does this, without the evaluations.
-                    if (kp.backtrack == T(0.5) && std::is_same<D, NoDiag>::value) {
-                        s = ldexp_(s, it - kp.max_bt);
-                    } else {
-                        for (int q = it; q < kp.max_bt; ++q) { s *= kp.backtrack; diag.feas(); }
-                    }
-                    it = kp.max_bt;
-                } else {
-                    s *= kp.backtrack;
-                    ++it;
-                    diag.feas();
-                    const T x0 = bk.get(0), x1 = bk.get(1), x2 = bk.get(2);
-                    v = fma_(dxv, s, x0);
-                    t0 = fma_(dx0, s, x1);
-                    t1 = fma_(dx1, s, x2);
-                    if constexpr (FROZEN) at_x = v == x0 && t0 == x1 && t1 == x2;
-                }
+                s *= kp.backtrack;
+                ++it;
+                diag.feas();
+                const T x0 = bk.get(0), x1 = bk.get(1), x2 = bk.get(2);
+                v = fma_(dxv, s, x0);
+                t0 = fma_(dx0, s, x1);
+                t1 = fma_(dx1, s, x2);
             }
         }
         if (used != 0) { asm volatile(""); it = 0; }      // (a branch, not a select: the common path does not touch the counter)
@@ -1759,15 +1658,13 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
 #pragma unroll
     for (int i = 0; i < NC; ++i) lam[i] = fma_(dl[i], s, lam[i]);
     {
-        used_t used = 0;
-#ifndef RP_FROZEN_INTFLAG
-#define RP_FROZEN_INTFLAG 1      // the flag lives in a vector register as 0 / 1 and every test of it is a FRESH compare (0: a bool, A/B) -- a bool carried round
-                                 // the loop is merged by three scalar mask operations per trip and comes back through v_cndmask / v_cmp at each ballot:
-                                 // 230 -> 187 scalar instructions per post-convergence wave-step of a lone wave (profiles/r6_tuning.md).  Where the step's
-                                 // start waits in registers only (the small-batch kernels, which are the ones a lone wave runs): the LDS-column kernels sit
-                                 // at 128 VGPRs for their fourth wave and have none to spare for it
-#endif
-        constexpr bool kIntFlag = RP_FROZEN_INTFLAG != 0 && !std::is_same<BK, LdsColumn<T>>::value;
+        int used = 0;
+        // The frozen flag lives in a vector register as 0 / 1 and every test of it is a FRESH compare -- a bool carried round the loop is
+        // merged by three scalar mask operations per trip and comes back through v_cndmask / v_cmp at each ballot: 230 -> 187 scalar
+        // instructions per post-convergence wave-step of a lone wave (profiles/r6_tuning.md).  Where the step's start waits in registers
+        // only (the small-batch kernels, which are the ones a lone wave runs): the LDS-column kernels sit at 128 VGPRs for their fourth
+        // wave and have none to spare for it
+        constexpr bool kIntFlag = !std::is_same<BK, LdsColumn<T>>::value;
         [[maybe_unused]] std::conditional_t<kIntFlag, int, bool> frozen = 0;      // FROZEN: the trial point has become bitwise x (and stays so: s only shrinks)
         for (;;) {
             accel_grads_u<T, P>(et, xt);
@@ -1781,8 +1678,7 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
             const bool again = bad && room && !(FROZEN && frozen != 0);
             [[maybe_unused]] unsigned long long again_m = 0ull;      // = ballot(again), from one ballot per comparison (see the feasibility loop)
             if constexpr (FROZEN) {
-                if constexpr (RP_SPLIT_BALLOTS != 0) again_m = any_bad & __builtin_amdgcn_ballot_w64(room) & __builtin_amdgcn_ballot_w64(frozen == 0);
-                else again_m = __builtin_amdgcn_ballot_w64(again);
+                again_m = any_bad & __builtin_amdgcn_ballot_w64(room) & __builtin_amdgcn_ballot_w64(frozen == 0);
                 if (again_m == 0ull) break;
             } else { if ((any_bad & __builtin_amdgcn_ballot_w64(room)) == 0ull) break; }
             used = 1;
@@ -1806,8 +1702,7 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
             // FROZEN: when every lane that is still searching has frozen, the affine search below takes over at once (its first
             // candidate is the trial just formed); the sums of such a trial are only wanted for the one the search ends on
             if constexpr (FROZEN) {
-                if constexpr (RP_SPLIT_BALLOTS != 0) { if ((again_m & __builtin_amdgcn_ballot_w64(frozen == 0)) == 0ull) break; }
-                else { if (__builtin_amdgcn_ballot_w64(again && frozen == 0) == 0ull) break; }
+                if ((again_m & __builtin_amdgcn_ballot_w64(frozen == 0)) == 0ull) break;
             }
         }
         if constexpr (FROZEN) {
@@ -1824,7 +1719,7 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
                     AffineResidual<T, VARIANT> ar;
                     ar.setup(et, [&](int i) { return (T)bk.get(3 + i); }, dl, p, L);
                     const T r0a = ar(T(0));
-                    if (RP_FROZEN_PROOF && kp.backtrack == T(0.5)) {
+                    if (kp.backtrack == T(0.5)) {
                         // the trials that fail beyond doubt, counted in closed form (AffineResidual::certain_failures)
                         int skip = ar.certain_failures(kp, r0a, s);
                         const int room = kp.max_bt - it;

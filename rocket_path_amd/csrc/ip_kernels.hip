@@ -42,13 +42,8 @@ namespace {
 
 constexpr int kBlock = 256;
 // once-per-launch global accesses (state in, results out): nontemporal, they are never re-read through the caches
-#if !defined(RP_STREAM_PLAIN) && !defined(RP_TILE_PLAIN)
 template <typename S> __device__ __forceinline__ S ld_once(const S *p) { return __builtin_nontemporal_load(p); }
 template <typename S> __device__ __forceinline__ void st_once(S *p, S v) { __builtin_nontemporal_store(v, p); }
-#else
-template <typename S> __device__ __forceinline__ S ld_once(const S *p) { return *p; }
-template <typename S> __device__ __forceinline__ void st_once(S *p, S v) { *p = v; }
-#endif
 // Progress counters are sharded over 64 words each (open lanes: [0,64), gated steps: [64,128)):
 // one word takes ~88 atomics/us, and a k = 1 gated launch ends with 16384 waves arriving at once
 // (measured: 0.34 ms of a 0.40 ms launch was the two single-word atomics).
@@ -88,13 +83,8 @@ __device__ __forceinline__ void store_solution(Solution *rec, double v, double t
     const unsigned long long words = ((unsigned long long)st << 32) | (unsigned long long)(uint32_t)it;      // little endian: iters, then status
     const v2 a = {v, t0}, b = {t1, __longlong_as_double((long long)words)};
     v2 *dst = reinterpret_cast<v2 *>(rec);
-#ifdef RP_SOLUTION_NT
-    __builtin_nontemporal_store(a, dst);
-    __builtin_nontemporal_store(b, dst + 1);
-#else
     dst[0] = a;      // plain stores: the two halves of the sector meet in L2 and leave it as one write -- 29.5 us per 1 Mi records
-    dst[1] = b;      // where nontemporal stores take 79 us and a gather through slot_of 46 us (profiles/r4_solution_probe.log)
-#endif
+    dst[1] = b;      // where nontemporal stores took 79 us and a gather through slot_of 46 us (profiles/r4_solution_probe.log)
 }
 
 // ---------------------------------------------------------------------------------------
@@ -103,32 +93,17 @@ __device__ __forceinline__ void store_solution(Solution *rec, double v, double t
 //   GATED = true  : before each step stop if gap < tol or the problem's step count reached
 //                   max_iter; problems already finished are skipped
 //                   without touching their state.
-#ifndef RP_NEWTON_WAVES
-#define RP_NEWTON_WAVES 2     // minimum waves per SIMD the register allocator must leave room for
-#endif
-#ifndef RP_GATED_WAVES
-#define RP_GATED_WAVES 4     // 128 VGPRs (112-128 used): the in-place step with the cold values parked in LDS fits without a spill in the loop; 1 Mi problems = 16,384
-                             // waves = exactly four full rounds of the chip's 4,096 wave slots (three per SIMD: 5.33 rounds).  The stall-detector
-                             // twin (two more live values, 10 spilled at 128) stays at three
-#endif
+constexpr int kNewtonWaves = 2;      // minimum waves per SIMD the register allocator must leave room for
+constexpr int kGatedWaves = 4;       // 128 VGPRs (112-128 used): the in-place step with the cold values parked in LDS fits without a spill in the loop; 1 Mi problems = 16,384
+                                     // waves = exactly four full rounds of the chip's 4,096 wave slots (three per SIMD: 5.33 rounds).  The stall-detector
+                                     // twin (two more live values, 10 spilled at 128) stays at three
 // Which residual-loop form the fixed-step kernels use once the trial point has become x (newton_step's AFFINE): every kernel of
 // a variant uses the same one, so that all launch shapes agree bit for bit.  This switch concerns newton_step_to, i.e. F4 (affine
 // pieces: it reaches that regime within a dozen steps and has the registers) and mu_mode 1; since round 4 F3's fixed-step
 // launches run newton_step_inplace<FROZEN>, whose post-convergence search is on affine pieces as well (ip_core.h).
-#ifdef RP_AFFINE_ALL      // A/B build (profiles/r3_tuning.md: no gain for F3, 168 VGPRs + 2 spilled in its chunk kernel)
-template <int VARIANT> constexpr bool kAffine = true;
-#else
+// (F3 on affine pieces as well was measured: no gain, 168 VGPRs + 2 spilled in its chunk kernel, profiles/r3_tuning.md.)
 template <int VARIANT> constexpr bool kAffine = (VARIANT == 4);
-#endif
-#ifndef RP_WAVE_LS
-#define RP_WAVE_LS 1      // wave-parallel line search in F4's fixed-step chunk kernel (0: the serial loop, for A/B runs)
-#endif
-#ifndef RP_GATED_IN_PLACE
-#define RP_GATED_IN_PLACE 1     // the gated kernel's step overwrites the state, its start backed up in LDS (0: newton_step_to, for A/B runs)
-#endif
-#ifndef RP_TILED_WAVES
-#define RP_TILED_WAVES 3     // F4's fixed-step chunk kernels (156-168 VGPRs) and F3's register-column instantiation; the in-place kernels have RP_GATED_WAVES
-#endif
+constexpr int kTiledWaves = 3;      // F4's fixed-step chunk kernels (156-168 VGPRs) and F3's register-column instantiation; the in-place kernels have kGatedWaves
 
 // The per-lane body shared by both Newton kernels: up to k steps on the state held in registers.
 // STALL: compile the stall detector in (two more live registers); the tiled solve instantiates both
@@ -145,15 +120,12 @@ template <int VARIANT> constexpr bool kAffine = (VARIANT == 4);
 // gated launch whose gate never closes now takes the very same steps as well.  F4's fixed-step launches keep newton_step_to (the
 // wave-parallel line search and the affine post-convergence loop are built on it); mu_mode 1 likewise.
 template <int VARIANT, bool GATED, int MU, class D>
-constexpr bool kStepInPlace = RP_GATED_IN_PLACE && MU == 0 && (GATED ? std::is_same<D, NoDiag>::value : VARIANT == 3);
+constexpr bool kStepInPlace = MU == 0 && (GATED ? std::is_same<D, NoDiag>::value : VARIANT == 3);
 
-// PARK (RP_PARK_FIXED_POINTS; F4's fused fixed-step launches on an fp32 state with fp64 arithmetic): a lane whose step has left its STORED
+// PARK (F4's fused fixed-step launches on an fp32 state with fp64 arithmetic): a lane whose step has left its STORED
 // state bit for bit where it was sits the remaining steps of the launch out -- see the ungated loop below.  (Pure fp32 arithmetic keeps
 // the plain loop: there the stuck problems are few -- its Armijo test stops resolving long before a state freezes -- and the bookkeeping
 // cost more than it saved: 50.0 against 53.8 G steps/s at 1 Mi x 50, profiles/r6_f4_park_ab.log.  The code below still handles S == T.)
-#ifndef RP_PARK_FIXED_POINTS
-#define RP_PARK_FIXED_POINTS 1      // 0: every lane takes every step (A/B builds: no bit may change)
-#endif
 template <typename T, int VARIANT, bool GATED, bool STALL = GATED, class P = Prob<T>, typename S = T, bool AFFINE = false, int MU = 0, class D = NoDiag, int WAVE = 0,
           class BK = LdsColumn<T>, bool PARK = false, bool ROUNDS = false>
 __device__ __forceinline__ void run_lane(const P &pr, const KParams<T> &kp, int k, T tol, int max_iter,
@@ -277,7 +249,7 @@ __device__ __forceinline__ void run_lane(const P &pr, const KParams<T> &kp, int 
             }
             if (__builtin_amdgcn_ballot_w64(open) == 0ull) break;
         }
-    } else if constexpr (PARK && RP_PARK_FIXED_POINTS != 0) {
+    } else if constexpr (PARK) {
         // ---- fixed points sit out (exact) ----
         // F4 never converges (README.md:34): from step ~6 on a growing share of its problems -- 2.4 % by step 48 on the benchmark
         // distribution -- is STUCK: the residual loop (onedpath2_ip.cpp:820-833) halves the step ~52 times until x + s dx is x bit for
@@ -286,7 +258,7 @@ __device__ __forceinline__ void run_lane(const P &pr, const KParams<T> &kp, int 
         // state it maps onto itself it maps onto itself for ever, and every further step of the launch is the same ~52-halving
         // walk to the same bits -- the lanes the wave-parallel line search exists for.  Such a lane is parked: it takes no further
         // steps in this launch, and what it stores is bit for bit what the steps would have left (tests/checks/fixed_step_ab.py
-        // against a build with RP_PARK_FIXED_POINTS=0; measured on the oracle, profiles/r6_tuning.md: the stuck problems and the
+        // against a build in which every lane took every step; measured on the oracle, profiles/r6_tuning.md: the stuck problems and the
         // fixed points of the fp32-state step are the same problems, none ever leaves).  Bit patterns are compared, not values
         // (-0 against +0 is a change, NaN against the same NaN is none), and with S == T (no re-evaluation after the step) the
         // carried evaluation is compared too.  A wave whose lanes are all parked leaves the loop.
@@ -433,7 +405,7 @@ __device__ unsigned long long g_trace[4 * 32768];
 // appends their positions to `list_out` (null in the last round, which runs every lane to its end).  Gathered 8-byte accesses instead of
 // coalesced ones from the second round on -- for the few per cent of a batch that get that far.
 template <typename S, typename T, int VARIANT, bool STALL, bool ZV, int MU = 0, bool START = false, bool ROUNDS = false>
-__global__ void __launch_bounds__(64, MU == 1 ? RP_NEWTON_WAVES : (STALL && RP_GATED_WAVES > 3) ? 3 : RP_GATED_WAVES)
+__global__ void __launch_bounds__(64, MU == 1 ? kNewtonWaves : (STALL && kGatedWaves > 3) ? 3 : kGatedWaves)
 k_solve_chunks(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T> kp, T tol, int max_iter,
                int32_t *__restrict__ iters, uint32_t *__restrict__ status, unsigned long long *__restrict__ counters,
                const StartRecord *__restrict__ records, const uint32_t *__restrict__ prob_of, double start_limit,
@@ -592,10 +564,8 @@ k_solve_chunks(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T> 
 // late in round 2 this was a 512-problem tile staged in LDS, the only form that fitted three waves per SIMD: the compiler
 // kept the eleven store addresses in registers across the steps.  Forming them after the steps, below, saved 16 VGPRs and
 // made the direct form both fit and win: 57.5 -> 65.5 G steps/s at k = 12.)
-#ifndef RP_SMALL_WAVES
-#define RP_SMALL_WAVES RP_TILED_WAVES     // the register-column instantiation (batches that leave SIMDs with a lone wave): A/B knob, profiles/r5_tuning.md
-#endif
-template <int VARIANT, bool REGBK> constexpr int kStepsChunkWaves = (kStepInPlace<VARIANT, false, 0, NoDiag> && !REGBK) ? RP_GATED_WAVES : (REGBK ? RP_SMALL_WAVES : RP_TILED_WAVES);
+// (the register-column instantiation, for batches that leave SIMDs with a lone wave, has kTiledWaves too: profiles/r5_tuning.md)
+template <int VARIANT, bool REGBK> constexpr int kStepsChunkWaves = (kStepInPlace<VARIANT, false, 0, NoDiag> && !REGBK) ? kGatedWaves : kTiledWaves;
 
 // REGBK (F3): the in-place step's start waits in registers instead of LDS, three waves per SIMD -- the instantiation for batches
 // that cannot fill three waves per SIMD anyway (launch_steps picks it below 196,608 problems): a lone wave has nothing to run
@@ -661,7 +631,7 @@ k_steps_chunks(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T> 
     // its stalled problems), so all its fixed-step kernels use it and agree bit for bit
     // (newton_step_to<WAVE> broadcasts through LDS without a barrier: single-wave blocks only -- the block size travels into the step as
     // the template argument WAVE and is asserted THERE, inside the WAVE branch, so that no multi-wave kernel can instantiate it: ADVICE r5)
-    run_lane<T, VARIANT, false, false, Pk, S, kAffine<VARIANT>, 0, (RP_WAVE_LS && VARIANT == 4) ? kChunkBlock : 0, (VARIANT == 4 && sizeof(S) == 4 && sizeof(T) == 8)>(pr, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open);
+    run_lane<T, VARIANT, false, false, Pk, S, kAffine<VARIANT>, 0, VARIANT == 4 ? kChunkBlock : 0, (VARIANT == 4 && sizeof(S) == 4 && sizeof(T) == 8)>(pr, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open);
     }
     // the store addresses are formed only now: the barrier keeps the compiler from holding eleven of them in registers
     // across the steps (168 VGPRs and 4-10 spilled without it, 152 with it)
@@ -686,7 +656,7 @@ k_steps_chunks(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T> 
 template <typename T, int NF> struct LaneState { T f[NF]; };
 
 template <typename S, typename T, int VARIANT, bool ZV, int MU = 0>
-__global__ void __launch_bounds__(kBlock, RP_NEWTON_WAVES)
+__global__ void __launch_bounds__(kBlock, kNewtonWaves)
 k_newton_stream(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T> kp)
 {
     constexpr int NC = CMap<VARIANT>::NC;
@@ -776,11 +746,7 @@ k_newton_counted(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T
     f[2 * stride] = (S)t1;
 #pragma unroll
     for (int c = 0; c < NC; ++c) f[(3 + c) * stride] = (S)lam[c];
-#ifdef RP_DIAG_MOVING      // tuning build: full residual evaluations instead of feasibility halvings
-    nfeas[i] = diag.nm;
-#else
     nfeas[i] = diag.nf;
-#endif
     nresid[i] = diag.nr;
 }
 
@@ -790,7 +756,7 @@ k_newton_counted(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T
 // them one after the other and stores each mutable field with one global_store_dwordx4.  No prefetch registers:
 // the 14 x 16 B a lane holds for its problems are the latency cover (57 KiB in flight per resident block).
 // Loads and stores are NONTEMPORAL: every byte is touched once per launch, and keeping it out of the caches' way is
-// worth 7 % at k = 1 (same box, alternating runs: 4.66 -> 4.98 TB/s; k = 0: 4.79 -> 5.33; -DRP_STREAM_PLAIN for the A/B).
+// worth 7 % at k = 1 (same box, alternating runs against plain accesses: 4.66 -> 4.98 TB/s; k = 0: 4.79 -> 5.33).
 // Covers floor(n / (256 PER)) full blocks; launch_steps hands the ragged remainder to k_newton_stream.
 // S = storage, T = arithmetic.  fp32 state with fp64 arithmetic takes 8 B per lane (two problems): four sequential fp64
 // problems per lane would leave the launch compute-bound with half the waves (measured at 1 Mi F4: 26 -> see DESIGN tuning log).
@@ -800,7 +766,7 @@ template <> struct Vec16<float, float> { using type = float __attribute__((ext_v
 template <> struct Vec16<float, double> { using type = float __attribute__((ext_vector_type(2))); static constexpr int PER = 2; };
 
 template <typename S, typename T, int VARIANT, bool ZV>
-__global__ void __launch_bounds__(kBlock, RP_NEWTON_WAVES)
+__global__ void __launch_bounds__(kBlock, kNewtonWaves)
 k_newton_stream16(S *__restrict__ base, size_t stride, int k, KParams<T> kp)
 {
     constexpr int NC = CMap<VARIANT>::NC;
@@ -815,11 +781,7 @@ k_newton_stream16(S *__restrict__ base, size_t stride, int k, KParams<T> kp)
     V f[NF];
 #pragma unroll
     for (int q = 0; q < NF; ++q)
-#ifndef RP_STREAM_PLAIN
         if (!(ZV && (q == CB + 1 || q == CB + 4))) f[q] = __builtin_nontemporal_load(reinterpret_cast<const V *>(base + (size_t)q * stride + i));
-#else
-        if (!(ZV && (q == CB + 1 || q == CB + 4))) f[q] = *reinterpret_cast<const V *>(base + (size_t)q * stride + i);
-#endif
     // the segment lengths of all PER problems up front: the three position vectors are dead from here on
     T dx0[PER], dx1[PER];
 #pragma unroll
@@ -853,11 +815,7 @@ k_newton_stream16(S *__restrict__ base, size_t stride, int k, KParams<T> kp)
     size_t j = ((size_t)blockIdx.x * kBlock + threadIdx.x) * PER;      // store addresses formed only now (see k_steps_chunks)
     asm volatile("" : "+v"(j));
 #pragma unroll
-#ifndef RP_STREAM_PLAIN
     for (int q = 0; q < CB; ++q) __builtin_nontemporal_store(f[q], reinterpret_cast<V *>(base + (size_t)q * stride + j));
-#else
-    for (int q = 0; q < CB; ++q) *reinterpret_cast<V *>(base + (size_t)q * stride + j) = f[q];
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1053,18 +1011,6 @@ k_solution(const S *__restrict__ base, size_t stride, size_t n, const int32_t *_
     const size_t prob = prob_of ? (size_t)prob_of[s] : s;
     store_solution(out + prob, (double)ld_once(base + s), (double)ld_once(base + stride + s), (double)ld_once(base + 2 * stride + s),
                    iters[s] + iters_add, status[s]);
-}
-
-// the same walking PROBLEMS: five gathered sectors read per problem, records written coalesced (A/B form, -DRP_SOLUTION_GATHER)
-template <typename S>
-__global__ void __launch_bounds__(kBlock)
-k_solution_gather(const S *__restrict__ base, size_t stride, size_t n, const int32_t *__restrict__ iters, const uint32_t *__restrict__ status,
-                  const uint32_t *__restrict__ slot_of, int iters_add, Solution *__restrict__ out)
-{
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const size_t s = slot_of[i];
-    store_solution(out + i, (double)base[s], (double)base[stride + s], (double)base[2 * stride + s], iters[s] + iters_add, status[s]);
 }
 
 // Feasible start (build-defined): vel1 = 0, t_i = (3.5/sqrt 12) sqrt(6 |dX_i| / L), multipliers 1,
@@ -1575,13 +1521,6 @@ hipError_t launch_solution(const BatchView &b, Solution *d_out, hipStream_t stre
 {
     if (b.n == 0) return hipSuccess;
     const uint32_t *inv = b.scheduled ? (const uint32_t *)b.prob_of : nullptr;
-#ifdef RP_SOLUTION_GATHER
-    if (b.scheduled) {
-        if (b.dtype == 0) hipLaunchKernelGGL((k_solution_gather<double>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (const double *)b.base, b.stride, b.n, b.iters, b.status, (const uint32_t *)b.slot_of, b.iters_add, d_out);
-        else              hipLaunchKernelGGL((k_solution_gather<float>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (const float *)b.base, b.stride, b.n, b.iters, b.status, (const uint32_t *)b.slot_of, b.iters_add, d_out);
-        return hipGetLastError();
-    }
-#endif
     if (b.dtype == 0) hipLaunchKernelGGL((k_solution<double>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (const double *)b.base, b.stride, b.n, b.iters, b.status, inv, b.iters_add, d_out);
     else              hipLaunchKernelGGL((k_solution<float>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (const float *)b.base, b.stride, b.n, b.iters, b.status, inv, b.iters_add, d_out);
     return hipGetLastError();

@@ -47,11 +47,8 @@ namespace rp {
 
 namespace {
 
-#ifndef RP_SCHED_LEVEL_BITS
-#define RP_SCHED_LEVEL_BITS 5                 // length levels: 5 bits = 4 per octave over [4, 1024) (6: 8 per octave, 4,096 keys -- 1.3 % idle lane-steps
+constexpr int kLevelBits = 5;                 // length levels: 5 bits = 4 per octave over [4, 1024) (6: 8 per octave, 4,096 keys -- 1.3 % idle lane-steps
                                               // instead of 1.5 %, but a pass of 36.8 instead of 31.8 us at 1 Mi problems: profiles/r3_tuning.md)
-#endif
-constexpr int kLevelBits = RP_SCHED_LEVEL_BITS;
 constexpr int kKeyBits = 6 + kLevelBits;
 constexpr int kKeys = 1 << kKeyBits;          // 64 ratio classes x 32 length levels = 2,048 keys
 
@@ -94,10 +91,8 @@ namespace fat {
 constexpr int kThreads = 256;                 // 4 waves
 constexpr int kPerThread = 16;
 constexpr int kTileProblems = kThreads * kPerThread;      // 4,096 problems per tile
-#ifndef RP_SCHED_COUNT_THREADS
-#define RP_SCHED_COUNT_THREADS 256      // measured at 1 Mi problems: 256 threads 37.0 us per pass, 512: 37.1, 1,024: 36.3 -- not bound by its occupancy
-#endif
-constexpr int kCountThreads = RP_SCHED_COUNT_THREADS;      // the counting kernel's block (a tile of 4,096 problems either way)
+constexpr int kCountThreads = 256;      // the counting kernel's block (a tile of 4,096 problems either way).  Measured at 1 Mi problems:
+                                        // 256 threads 37.0 us per pass, 512: 37.1, 1,024: 36.3 -- not bound by its occupancy
 constexpr int kCountPerThread = kTileProblems / kCountThreads;
 constexpr int kWaves = kThreads / 64;
 constexpr int kWaveSpan = kTileProblems / kWaves;         // consecutive problems a wave owns: 1,024 = 16 groups of 64
@@ -272,10 +267,7 @@ inline unsigned tiles_for(size_t n) { return (unsigned)((n + kTileProblems - 1) 
 namespace slim {
 
 constexpr int kThreads = 64;                  // ONE wave per block, in all three kernels (see the top of this file)
-#ifndef RP_SCHED_TILE
-#define RP_SCHED_TILE 2048                    // problems per tile: 512 tiles at 1 Mi problems (a 4 MB histogram matrix)
-#endif
-constexpr int kTileProblems = RP_SCHED_TILE;
+constexpr int kTileProblems = 2048;           // problems per tile: 512 tiles at 1 Mi problems (a 4 MB histogram matrix)
 constexpr int kGroups = kTileProblems / 64;   // 64-problem groups of a tile, walked in order by its one wave
 constexpr int kChunk = 16;                    // groups whose key loads are issued together (k_sched_scatter)
 constexpr int kCountChunk = 8;                // ... and whose position loads are (k_sched_count: 8 x 3 doubles in flight per lane; 16 made it 146 VGPRs --

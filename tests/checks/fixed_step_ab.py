@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Fixed-step launches (F3 and F4, every number mode, three launch shapes) saved for a bit-for-bit comparison between two builds of
-the library (RP_BATCH_LIB), e.g. -DRP_UNIFORM_LOOPS=0 against the default:
-    python tests/checks/fixed_step_ab.py gpurun_out/a.npz;  RP_BATCH_LIB=... python tests/checks/fixed_step_ab.py gpurun_out/b.npz
-    python tests/checks/inplace_ab.py cmp gpurun_out/a.npz gpurun_out/b.npz"""
+the library (RP_BATCH_LIB), e.g. a candidate build against the shipped one:
+    python tests/checks/fixed_step_ab.py a.npz;  RP_BATCH_LIB=... python tests/checks/fixed_step_ab.py b.npz
+    python tests/checks/fixed_step_ab.py cmp a.npz b.npz"""
 import os
 import sys
 
@@ -10,6 +10,18 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+
+if sys.argv[1] == "cmp":
+    a, b = np.load(sys.argv[2]), np.load(sys.argv[3])
+    bad = 0
+    for key in a.files:
+        same = np.array_equal(a[key], b[key], equal_nan=True)
+        bad += not same
+        if not same:
+            print("DIFFERENT:", key, "max abs diff", np.nanmax(np.abs(a[key].astype(np.float64) - b[key].astype(np.float64))))
+    print("%d arrays compared (%d values), %d differ" % (len(a.files), sum(a[k].size for k in a.files), bad))
+    sys.exit(1 if bad else 0)
+
 import rocket_path_amd as rp  # noqa: E402
 
 print("library:", os.environ.get("RP_BATCH_LIB", "(in-tree)"))

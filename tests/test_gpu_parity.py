@@ -1376,12 +1376,11 @@ def test_f4_steps_from_points_that_are_infeasible_beyond_doubt(oracle, dtype):
 
 
 def test_f4_closed_form_halving_count_on_the_states_where_it_was_unsound(oracle, golden_dir):
-    # The regression fixture for the case above: 31 F4 states (fp32-representable rows; inputs only) found by
-    # tests/checks/f4_ray_search.py among 12.6 M perturbed trajectory states, at which round 3's closed form -- a library built with
-    # -DRP_RAY_ASSUME_MONOTONE -- counted halvings the reference does not make: x beyond doubt infeasible, g convex along the ray,
-    # positive at s and near 0, negative in between (this test fails against that build: profiles/r4_ray_ab.log).  With the
-    # monotonicity condition the stepping launches equal the launch that evaluates every trial, bit for bit, and its feasibility
-    # counts are the oracle's.
+    # The regression fixture for the case above: 31 F4 states (fp32-representable rows; inputs only) found in round 4 among 12.6 M
+    # perturbed trajectory states, at which round 3's closed form -- which took g to be monotone along the ray -- counted halvings
+    # the reference does not make: x beyond doubt infeasible, g convex along the ray, positive at s and near 0, negative in between
+    # (this test failed against a library built with that form: profiles/r4_ray_ab.log).  With the monotonicity condition the
+    # stepping launches equal the launch that evaluates every trial, bit for bit, and its feasibility counts are the oracle's.
     states = np.load(os.path.join(golden_dir, "f4_ray_cases.npz"))["states"]
     m = len(states)
     assert m == 31 and np.array_equal(states, states.astype(np.float32).astype(np.float64))
