@@ -48,8 +48,9 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      environment switch; the library reads nothing from the environment; rp_batch_sample_device checks its alignment
  *   5  round 5: rp_device_id; a bound solution buffer is seeded before a gated launch that skips finished problems
  *   6  round 6: rp_pipeline_* (positions in -> solutions out over several streams); rp_params + handoff_rounds / handoff_lanes (the gated
- *      solve in rounds); a raw pointer to a mutable field keeps the seeding pass on for every later gated launch */
-#define RP_ABI_VERSION 6
+ *      solve in rounds); a raw pointer to a mutable field keeps the seeding pass on for every later gated launch
+ *   7  rp_batch_solution_vjp (gradients of the solution with respect to the positions) */
+#define RP_ABI_VERSION 7
 
 typedef enum {
     RP_OK = 0,
@@ -225,6 +226,20 @@ RP_API int rp_batch_solution_device(rp_batch *b, rp_solution *d_out);
  * than gated solves (rp_batch_step, nudges, set_state ...) do not update the buffer -- use rp_batch_solution_device for the
  * state they leave.  The buffer must outlive the binding. */
 RP_API int rp_batch_bind_solution(rp_batch *b, rp_solution *d_out);
+/* Vector-Jacobian product of the solution with respect to the positions, at the batch's current state (the
+ * Newton matrix of onedpath_ip.cpp:814-861 transposed).  All arrays: n doubles, device memory, PROBLEM order; a NULL upstream
+ * gradient counts as zeros.  Asynchronous on the batch stream.  F3, RP_DTYPE_F64 only (RP_ERR_UNSUPPORTED otherwise).
+ * Definition: z = (x, lam), x = (vel1, duration0, duration1) with the 8 multipliers, theta = (pos0, pos1, pos2); r(z; theta, p) is
+ * the reference's residual (onedpath_ip.cpp:753-783) with the perturbation p = gap / (m mu_divisor) of the state held fixed, and
+ * M = dr/dz.  Given upstream gradients g on x: solve M^T w = [g; 0_8], theta_bar = -w^T dr/dtheta -- the implicit-function derivative
+ * of the central-path point at this p, which tends to the derivative of the optimum as the gap goes to 0 wherever that exists.
+ * r depends on theta only through pos1 - pos0 and pos2 - pos1, so pos0_bar + pos1_bar + pos2_bar = 0.  A problem whose state is
+ * not finite or outside the feasible set (some c_i > 0, constraintsSatisfied of onedpath_ip.cpp:738-751: the states RP_ST_NONFINITE
+ * and RP_ST_INFEASIBLE describe, judged from the state itself at the time of the call) gets NaN in all three outputs; every other
+ * problem gets the formula, RP_ST_MAXITER ones included (|c_i| floored at L eps / 256 where rounding leaves an active c_i at 0).  Works on any state: after solves, steps, nudges, set_state, and on a
+ * batch from rp_pipeline_batch. */
+RP_API int rp_batch_solution_vjp(rp_batch *b, const double *d_g_vel1, const double *d_g_dur0, const double *d_g_dur1,
+                                 double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar);
 RP_API int rp_batch_reduce(rp_batch *b, rp_reduction *out);                   /* synchronous */
 /* Writes the 4 doubles of rp_reduction to device memory the caller owns, asynchronously on
  * the batch stream: the buffer a multi-GPU caller hands to its RCCL all-reduce. */

@@ -8,3 +8,11 @@ from . import capi, problems  # noqa: F401
 from .batch import Batch, Pipeline  # noqa: F401
 from .capi import (DTYPE_F32, DTYPE_F32_STATE, DTYPE_F64, ST_CONVERGED, ST_INFEASIBLE, ST_MAXITER, ST_NONFINITE, ST_STALLED, ST_WRONG_WAY,  # noqa: F401
                    VARIANT_F3, VARIANT_F4, RpError, device_count, device_id, load_library)
+
+
+def __getattr__(name):
+    # the torch layer (autograd.py) is imported on first use: everything else here works without importing torch
+    if name == "min_time_solve":
+        from .autograd import min_time_solve
+        return min_time_solve
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -141,6 +141,13 @@ class Batch:
         """Every problem's 32-byte rp_solution record, in problem order, into device memory (address of n records)."""
         capi.check(self._lib.rp_batch_solution_device(self._h, ctypes.c_void_p(d_out)))
 
+    def solution_vjp(self, d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar):
+        """Gradients with respect to (pos0, pos1, pos2) of a loss whose gradients on (vel1, duration0, duration1) are the three
+        upstream arrays, at the current state (rp_batch_solution_vjp): device addresses of n doubles each, problem order; an upstream
+        address of None / 0 counts as zeros.  Asynchronous on the batch stream.  F3 with DTYPE_F64 only."""
+        capi.check(self._lib.rp_batch_solution_vjp(self._h, *[ctypes.c_void_p(p) if p else None for p in
+                                                              (d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar)]))
+
     def bind_solution(self, d_out):
         """Gated solves write each problem's rp_solution record to d_out (device address of n records; None / 0 unbinds)."""
         capi.check(self._lib.rp_batch_bind_solution(self._h, ctypes.c_void_p(d_out) if d_out else None))

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librp_batch.so")
 
 RP_OK = 0
-ABI_VERSION = 6      # RP_ABI_VERSION of include/rp_batch.h this binding was written against
+ABI_VERSION = 7      # RP_ABI_VERSION of include/rp_batch.h this binding was written against
 RP_ERR_INVALID, RP_ERR_DEVICE, RP_ERR_NOMEM, RP_ERR_UNSUPPORTED, RP_ERR_NO_DEVICE = 1, 2, 3, 4, 5
 VARIANT_F3, VARIANT_F4 = 3, 4
 DTYPE_F64, DTYPE_F32, DTYPE_F32_STATE = 0, 1, 2      # 2: fp32 state in HBM, fp64 arithmetic (include/rp_batch.h)
@@ -83,6 +83,7 @@ SIGNATURES = {
     "rp_batch_get_iters": (ctypes.c_int, [_vp, _vp, _vp]),
     "rp_batch_solution_device": (ctypes.c_int, [_vp, _vp]),
     "rp_batch_bind_solution": (ctypes.c_int, [_vp, _vp]),
+    "rp_batch_solution_vjp": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_batch_traffic_probe": (ctypes.c_int, [_vp]),
     "rp_batch_reduce": (ctypes.c_int, [_vp, ctypes.POINTER(Reduction)]),
     "rp_batch_reduce_device": (ctypes.c_int, [_vp, _vp]),

@@ -81,6 +81,10 @@ hipError_t launch_reduce(const BatchView &b, const HostParams &hp, double host_s
 
 // every problem's 32-byte solution record in problem order (walks positions, scatters whole sectors)
 hipError_t launch_solution(const BatchView &b, Solution *d_out, hipStream_t stream);
+// d(vel1, duration0, duration1) / d(pos0, pos1, pos2) transposed, applied to upstream gradients (null: zeros), problem order in and
+// out, at the batch's current state (sensitivity.hip; F3, double storage only)
+hipError_t launch_solution_vjp(const BatchView &b, const HostParams &hp, const double *d_g_vel1, const double *d_g_dur0,
+                               const double *d_g_dur1, double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar, hipStream_t stream);
 
 // state movement / initialisation
 hipError_t launch_aos_to_soa(const BatchView &b, const double *d_aos, hipStream_t stream);

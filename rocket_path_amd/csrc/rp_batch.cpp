@@ -727,6 +727,18 @@ int rp_batch_solution_device(rp_batch *b, rp_solution *d_out)
     return RP_OK;
 }
 
+int rp_batch_solution_vjp(rp_batch *b, const double *d_g_vel1, const double *d_g_dur0, const double *d_g_dur1,
+                          double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar)
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
+        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_vjp: F3 with RP_DTYPE_F64 only");
+    if (!d_pos0_bar || !d_pos1_bar || !d_pos2_bar) return fail(RP_ERR_INVALID, "null output");
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_solution_vjp(b->view, b->params, d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar, b->stream));
+    return RP_OK;
+}
+
 int rp_batch_bind_solution(rp_batch *b, rp_solution *d_out)
 {
     if (!b) return fail(RP_ERR_INVALID, "null batch handle");
