@@ -49,7 +49,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *   5  round 5: rp_device_id; a bound solution buffer is seeded before a gated launch that skips finished problems
  *   6  round 6: rp_pipeline_* (positions in -> solutions out over several streams); rp_params + handoff_rounds / handoff_lanes (the gated
  *      solve in rounds); a raw pointer to a mutable field keeps the seeding pass on for every later gated launch
- *   7  rp_batch_solution_vjp (gradients of the solution with respect to the positions) */
+ *   7  rp_batch_solution_vjp (gradients of the solution with respect to the positions); rp_batch_solution_jvp and
+ *      rp_batch_solution_jacobian (the forward-mode derivative and the per-problem 3 x 3 Jacobian; new entries only) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -240,6 +241,21 @@ RP_API int rp_batch_bind_solution(rp_batch *b, rp_solution *d_out);
  * batch from rp_pipeline_batch. */
 RP_API int rp_batch_solution_vjp(rp_batch *b, const double *d_g_vel1, const double *d_g_dur0, const double *d_g_dur1,
                                  double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar);
+/* Jacobian-vector product of the solution with respect to the positions, at the batch's current state: the
+ * forward-mode counterpart of rp_batch_solution_vjp, with the same z, x, theta, r and M.  Given position tangents theta_dot =
+ * (pos0_dot, pos1_dot, pos2_dot): solve M z_dot = -(dr/dtheta) theta_dot and write the x part (vel1_dot, duration0_dot,
+ * duration1_dot).  All arrays: n doubles, device memory, PROBLEM order; a NULL tangent counts as zeros.  Equal tangents on the
+ * three positions give exactly 0.  Asynchronous on the batch stream.  F3, RP_DTYPE_F64 only (RP_ERR_UNSUPPORTED otherwise).  The
+ * NaN rule, the c_i floor and the states it works on are rp_batch_solution_vjp's. */
+RP_API int rp_batch_solution_jvp(rp_batch *b, const double *d_t_pos0, const double *d_t_pos1, const double *d_t_pos2,
+                                 double *d_t_vel1, double *d_t_dur0, double *d_t_dur1);
+/* Every problem's Jacobian J = d(vel1, duration0, duration1) / d(pos0, pos1, pos2) at the batch's current state: 9 doubles per
+ * problem, row-major (J[a][b] = dx_a / dpos_b at d_jac[9 i + 3 a + b]), n x 9 doubles of device memory in PROBLEM order.  The
+ * derivative of rp_batch_solution_jvp / rp_batch_solution_vjp (J theta_dot and J^T g), formed by one elimination on the two
+ * position-delta directions; each row sums to 0 up to rounding.  Asynchronous on the batch stream.  F3, RP_DTYPE_F64 only
+ * (RP_ERR_UNSUPPORTED otherwise); a problem whose state is not finite or outside the feasible set gets NaN in all nine entries;
+ * works on the states rp_batch_solution_vjp does. */
+RP_API int rp_batch_solution_jacobian(rp_batch *b, double *d_jac);
 RP_API int rp_batch_reduce(rp_batch *b, rp_reduction *out);                   /* synchronous */
 /* Writes the 4 doubles of rp_reduction to device memory the caller owns, asynchronously on
  * the batch stream: the buffer a multi-GPU caller hands to its RCCL all-reduce. */

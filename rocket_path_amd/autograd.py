@@ -2,11 +2,12 @@
 
     vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2)
     (duration0 + duration1).sum().backward()      # -> pos0.grad, pos1.grad, pos2.grad
+    vel1, duration0, duration1, iters, status, jac = min_time_jacobian(pos0, pos1, pos2)      # jac: (n, 3, 3)
 
 The forward is Batch.set_problems_device + the fused gated solve + Batch.solution_device into a torch buffer, enqueued without
-synchronising the host.  The backward is one rp_batch_solution_vjp launch at the state the forward left (include/rp_batch.h,
-DESIGN.md section 12): the implicit-function derivative of the central-path point the solve stopped at.  F3, float64 only; no
-double backward.
+synchronising the host.  The backward is one rp_batch_solution_vjp launch at the state the forward left, the forward-mode rule
+(torch.autograd.forward_ad, torch.func.jvp) one rp_batch_solution_jvp launch (include/rp_batch.h): the
+implicit-function derivative of the central-path point the solve stopped at.  F3, float64 only; no double backward, no vmap rule.
 """
 import ctypes
 import threading
@@ -67,22 +68,29 @@ def _stream_handle(stream):
     return stream.cuda_stream
 
 
-def _check_positions(pos0, pos1, pos2):
+def _check_positions(pos0, pos1, pos2, who="min_time_solve"):
     for name, t in (("pos0", pos0), ("pos1", pos1), ("pos2", pos2)):
         if not isinstance(t, torch.Tensor):
-            raise TypeError("min_time_solve: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+            raise TypeError(who + ": %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
         if t.device.type != "cuda":
-            raise TypeError("min_time_solve: %s is on %s; the solve runs on a ROCm device only (move it with .cuda())" % (name, t.device))
+            raise TypeError(who + ": %s is on %s; the solve runs on a ROCm device only (move it with .cuda())" % (name, t.device))
         if t.dtype != torch.float64:
-            raise TypeError("min_time_solve: %s has dtype %s; float64 is required" % (name, t.dtype))
+            raise TypeError(who + ": %s has dtype %s; float64 is required" % (name, t.dtype))
         if t.dim() != 1:
-            raise ValueError("min_time_solve: %s must be 1-D, got shape %s" % (name, tuple(t.shape)))
+            raise ValueError(who + ": %s must be 1-D, got shape %s" % (name, tuple(t.shape)))
     if not (pos0.shape == pos1.shape == pos2.shape):
-        raise ValueError("min_time_solve: lengths differ (%d, %d, %d)" % (pos0.shape[0], pos1.shape[0], pos2.shape[0]))
+        raise ValueError(who + ": lengths differ (%d, %d, %d)" % (pos0.shape[0], pos1.shape[0], pos2.shape[0]))
     if not (pos0.device == pos1.device == pos2.device):
-        raise ValueError("min_time_solve: positions on different devices (%s, %s, %s)" % (pos0.device, pos1.device, pos2.device))
+        raise ValueError(who + ": positions on different devices (%s, %s, %s)" % (pos0.device, pos1.device, pos2.device))
     if pos0.shape[0] == 0:
-        raise ValueError("min_time_solve: empty batch")
+        raise ValueError(who + ": empty batch")
+
+
+def _check_params(params, who):
+    if params is not None:
+        unknown = set(params) - _PARAM_FIELDS
+        if unknown:
+            raise ValueError("%s: unknown rp_params field(s) %s" % (who, sorted(unknown)))
 
 
 def _run_on(batch_stream, cur):
@@ -99,45 +107,76 @@ def _run_on(batch_stream, cur):
     return _Order()
 
 
+def _solve(pos0, pos1, pos2, gap_tol, max_iter, params, jacobian=False):
+    """Enqueue the solve on the current stream with a batch taken from the pool: (key, batch, (vel1, dur0, dur1, iters, status)),
+    and the (n, 3, 3) Jacobian at the end when `jacobian`.  The caller gives the batch back or leases it."""
+    device = pos0.device.index if pos0.device.index is not None else torch.cuda.current_device()
+    n = pos0.shape[0]
+    cur = torch.cuda.current_stream(device)
+    handle = _stream_handle(cur)
+    key = (device, n, handle)
+    batch = _pool.take(key)
+    # the null stream cannot be handed to a batch (NULL = "create your own"): then the batch's own stream is ordered by events
+    ext = None if handle else torch.cuda.ExternalStream(batch.stream(), device=pos0.device)
+    p0, p1, p2 = (t.contiguous() for t in (pos0, pos1, pos2))
+    out = torch.empty((n, 4), dtype=torch.float64, device=pos0.device)      # n rp_solution records (torch's blocks: 512-byte aligned)
+    jac = torch.empty((n, 3, 3), dtype=torch.float64, device=pos0.device) if jacobian else None
+    try:
+        p = capi.Params()
+        batch._lib.rp_params_default(ctypes.byref(p))
+        for k, v in (params or {}).items():
+            setattr(p, k, v)
+        capi.check(batch._lib.rp_batch_set_params(batch._h, ctypes.byref(p)))
+        with _run_on(ext, cur):
+            batch.set_problems_device(p0.data_ptr(), p1.data_ptr(), p2.data_ptr())
+            batch.solve(gap_tol, max_iter, 0)
+            batch.solution_device(out.data_ptr())
+            if jac is not None:
+                batch.solution_jacobian(jac.data_ptr())
+        if ext is not None:
+            for t in (p0, p1, p2, out, jac):
+                if t is not None:
+                    t.record_stream(ext)
+    except Exception:
+        _pool.give(key, batch)
+        raise
+    vel1, dur0, dur1 = out[:, 0].clone(), out[:, 1].clone(), out[:, 2].clone()
+    words = out.view(torch.int32).view(n, 8)
+    iters, status = words[:, 6].clone(), words[:, 7].clone()
+    return key, batch, (vel1, dur0, dur1, iters, status) + ((jac,) if jac is not None else ())
+
+
+def _plain(t):
+    """The tensor under torch.func's wrappers: inside a transform the jvp rule receives its tangents, and creates its buffers, as
+    wrapped tensors, which have no storage of their own; the kernel reads and writes the one they wrap."""
+    while torch._C._functorch.is_functorch_wrapped_tensor(t):
+        t = torch._C._functorch.get_unwrapped(t)
+    return t
+
+
+class _Holder:
+    """How forward's batch reaches setup_context (in the setup_context form forward has no ctx): a non-tensor argument of apply."""
+    __slots__ = ("lease",)
+
+    def __init__(self):
+        self.lease = None
+
+
 class _MinTimeSolve(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pos0, pos1, pos2, gap_tol, max_iter, params, keep):
-        device = pos0.device.index if pos0.device.index is not None else torch.cuda.current_device()
-        n = pos0.shape[0]
-        cur = torch.cuda.current_stream(device)
-        handle = _stream_handle(cur)
-        key = (device, n, handle)
-        batch = _pool.take(key)
-        # the null stream cannot be handed to a batch (NULL = "create your own"): then the batch's own stream is ordered by events
-        ext = None if handle else torch.cuda.ExternalStream(batch.stream(), device=pos0.device)
-        p0, p1, p2 = (t.contiguous() for t in (pos0, pos1, pos2))
-        out = torch.empty((n, 4), dtype=torch.float64, device=pos0.device)      # n rp_solution records (torch's blocks: 512-byte aligned)
-        try:
-            p = capi.Params()
-            batch._lib.rp_params_default(ctypes.byref(p))
-            for k, v in (params or {}).items():
-                setattr(p, k, v)
-            capi.check(batch._lib.rp_batch_set_params(batch._h, ctypes.byref(p)))
-            with _run_on(ext, cur):
-                batch.set_problems_device(p0.data_ptr(), p1.data_ptr(), p2.data_ptr())
-                batch.solve(gap_tol, max_iter, 0)
-                batch.solution_device(out.data_ptr())
-            if ext is not None:
-                for t in (p0, p1, p2, out):
-                    t.record_stream(ext)
-        except Exception:
-            _pool.give(key, batch)
-            raise
-        vel1, dur0, dur1 = out[:, 0].clone(), out[:, 1].clone(), out[:, 2].clone()
-        words = out.view(torch.int32).view(n, 8)
-        iters, status = words[:, 6].clone(), words[:, 7].clone()
-        ctx.mark_non_differentiable(iters, status)
-        if keep:
-            ctx.lease = _Lease(key, batch)      # held by the graph until it is freed: its state is what the backward differentiates
-            ctx.device = pos0.device
-        else:
-            _pool.give(key, batch)      # the read-back is enqueued; the next user of this key works on the same stream
-        return vel1, dur0, dur1, iters, status
+    def forward(pos0, pos1, pos2, gap_tol, max_iter, params, holder):
+        key, batch, outs = _solve(pos0, pos1, pos2, gap_tol, max_iter, params)
+        holder.lease = _Lease(key, batch)
+        return outs
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        # ctx keeps the lease, and with it the batch whose state backward and jvp differentiate, out of the pool: for as long as an
+        # autograd graph holds ctx, or only until apply returns when none does (no_grad, or no input requiring grad).  The holder
+        # goes when min_time_solve returns, so a batch nothing holds is back in the pool once its read-back is enqueued.
+        ctx.lease = inputs[-1].lease
+        ctx.device = inputs[0].device
+        ctx.mark_non_differentiable(output[3], output[4])
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -158,21 +197,50 @@ class _MinTimeSolve(torch.autograd.Function):
                     t.record_stream(bstream)
         return bars[0], bars[1], bars[2], None, None, None, None
 
+    @staticmethod
+    def jvp(ctx, t_pos0, t_pos1, t_pos2, _t_gap, _t_iter, _t_params, _t_holder):
+        batch = ctx.lease.batch
+        device = ctx.device
+        cur = torch.cuda.current_stream(device)
+        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
+        ts = [_plain(t.contiguous()) if t is not None else None for t in (t_pos0, t_pos1, t_pos2)]
+        n = batch.n
+        outs = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(3)]
+        dots = [_plain(t) for t in outs]
+        same = bstream.cuda_stream == cur.cuda_stream
+        with _run_on(None if same else bstream, cur):
+            batch.solution_jvp(*[t.data_ptr() if t is not None else 0 for t in ts], *[d.data_ptr() for d in dots])
+        if not same:
+            for t in ts + dots:
+                if t is not None:
+                    t.record_stream(bstream)
+        return outs[0], outs[1], outs[2], None, None
+
 
 def min_time_solve(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None):
     """Solve the F3 problems (pos0[i], pos1[i], pos2[i]) -- 1-D float64 tensors on one ROCm device -- on the current stream.
 
-    Returns (vel1, duration0, duration1, iters, status): float64 tensors, differentiable with respect to the positions, and the
-    int32 step counts and RP_ST_* status words (not differentiable).  `params`: rp_params fields to override (a dict).
-    Gradients are the implicit-function derivative at the state the solve returns (include/rp_batch.h, rp_batch_solution_vjp):
-    NaN for problems whose state is not finite or not strictly feasible.  Does not synchronise the host."""
+    Returns (vel1, duration0, duration1, iters, status): float64 tensors, differentiable with respect to the positions in reverse
+    mode (backward) and forward mode (torch.autograd.forward_ad, torch.func.jvp), and the int32 step counts and RP_ST_* status words
+    (not differentiable).  `params`: rp_params fields to override (a dict).  Derivatives are the implicit-function derivative at the
+    state the solve returns (include/rp_batch.h, rp_batch_solution_vjp / rp_batch_solution_jvp): NaN for problems whose state is not
+    finite or not strictly feasible.  Does not synchronise the host."""
     _check_positions(pos0, pos1, pos2)
-    if params is not None:
-        unknown = set(params) - _PARAM_FIELDS
-        if unknown:
-            raise ValueError("min_time_solve: unknown rp_params field(s) %s" % sorted(unknown))
-    keep = torch.is_grad_enabled() and any(t.requires_grad for t in (pos0, pos1, pos2))      # (forward itself runs with grad off)
-    return _MinTimeSolve.apply(pos0, pos1, pos2, float(gap_tol), int(max_iter), params, keep)
+    _check_params(params, "min_time_solve")
+    return _MinTimeSolve.apply(pos0, pos1, pos2, float(gap_tol), int(max_iter), params, _Holder())
+
+
+def min_time_jacobian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve's solve, and every problem's Jacobian at the state it returns, on the current stream.
+
+    Returns (vel1, duration0, duration1, iters, status, jac) with jac (n, 3, 3) float64, jac[i, a, b] = d x_a / d pos_b of problem i
+    for x = (vel1, duration0, duration1) (rp_batch_solution_jacobian; NaN rows as for min_time_solve's derivatives).  One solve and
+    one Jacobian launch; nothing returned is differentiable.  Does not synchronise the host."""
+    _check_positions(pos0, pos1, pos2, "min_time_jacobian")
+    _check_params(params, "min_time_jacobian")
+    key, batch, outs = _solve(pos0.detach(), pos1.detach(), pos2.detach(), float(gap_tol), int(max_iter), params, jacobian=True)
+    _pool.give(key, batch)      # the read-backs are enqueued; the next user of this key works on the same stream
+    return outs
 
 
 def clear_pool():

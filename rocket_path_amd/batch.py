@@ -148,6 +148,19 @@ class Batch:
         capi.check(self._lib.rp_batch_solution_vjp(self._h, *[ctypes.c_void_p(p) if p else None for p in
                                                               (d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar)]))
 
+    def solution_jvp(self, d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel1, d_t_dur0, d_t_dur1):
+        """Tangents of (vel1, duration0, duration1) along the position tangents (pos0, pos1, pos2), at the current state
+        (rp_batch_solution_jvp): device addresses of n doubles each, problem order; a tangent address of None / 0 counts as zeros.
+        Asynchronous on the batch stream.  F3 with DTYPE_F64 only."""
+        capi.check(self._lib.rp_batch_solution_jvp(self._h, *[ctypes.c_void_p(p) if p else None for p in
+                                                              (d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel1, d_t_dur0, d_t_dur1)]))
+
+    def solution_jacobian(self, d_jac):
+        """Every problem's 3 x 3 Jacobian d(vel1, duration0, duration1) / d(pos0, pos1, pos2), row-major, at the current state
+        (rp_batch_solution_jacobian): device address of n x 9 doubles, problem order.  Asynchronous on the batch stream.  F3 with
+        DTYPE_F64 only."""
+        capi.check(self._lib.rp_batch_solution_jacobian(self._h, ctypes.c_void_p(d_jac) if d_jac else None))
+
     def bind_solution(self, d_out):
         """Gated solves write each problem's rp_solution record to d_out (device address of n records; None / 0 unbinds)."""
         capi.check(self._lib.rp_batch_bind_solution(self._h, ctypes.c_void_p(d_out) if d_out else None))

@@ -85,6 +85,11 @@ hipError_t launch_solution(const BatchView &b, Solution *d_out, hipStream_t stre
 // out, at the batch's current state (sensitivity.hip; F3, double storage only)
 hipError_t launch_solution_vjp(const BatchView &b, const HostParams &hp, const double *d_g_vel1, const double *d_g_dur0,
                                const double *d_g_dur1, double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar, hipStream_t stream);
+// d(vel1, duration0, duration1) / d(pos0, pos1, pos2) applied to position tangents (null: zeros), and the whole 3 x 3 Jacobian
+// (9 doubles per problem, row-major), problem order in and out, at the batch's current state (sensitivity.hip; F3, double storage only)
+hipError_t launch_solution_jvp(const BatchView &b, const HostParams &hp, const double *d_t_pos0, const double *d_t_pos1,
+                               const double *d_t_pos2, double *d_t_vel1, double *d_t_dur0, double *d_t_dur1, hipStream_t stream);
+hipError_t launch_solution_jacobian(const BatchView &b, const HostParams &hp, double *d_jac, hipStream_t stream);
 
 // state movement / initialisation
 hipError_t launch_aos_to_soa(const BatchView &b, const double *d_aos, hipStream_t stream);

@@ -739,6 +739,29 @@ int rp_batch_solution_vjp(rp_batch *b, const double *d_g_vel1, const double *d_g
     return RP_OK;
 }
 
+int rp_batch_solution_jvp(rp_batch *b, const double *d_t_pos0, const double *d_t_pos1, const double *d_t_pos2,
+                          double *d_t_vel1, double *d_t_dur0, double *d_t_dur1)
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
+        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_jvp: F3 with RP_DTYPE_F64 only");
+    if (!d_t_vel1 || !d_t_dur0 || !d_t_dur1) return fail(RP_ERR_INVALID, "null output");
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_solution_jvp(b->view, b->params, d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel1, d_t_dur0, d_t_dur1, b->stream));
+    return RP_OK;
+}
+
+int rp_batch_solution_jacobian(rp_batch *b, double *d_jac)
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
+        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_jacobian: F3 with RP_DTYPE_F64 only");
+    if (!d_jac) return fail(RP_ERR_INVALID, "null output");
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_solution_jacobian(b->view, b->params, d_jac, b->stream));
+    return RP_OK;
+}
+
 int rp_batch_bind_solution(rp_batch *b, rp_solution *d_out)
 {
     if (!b) return fail(RP_ERR_INVALID, "null batch handle");

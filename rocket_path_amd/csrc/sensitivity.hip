@@ -1,25 +1,36 @@
-// sensitivity.hip -- vector-Jacobian product of an F3 solution with respect to the positions (rp_batch_solution_vjp), gfx950.
+// sensitivity.hip -- derivatives of an F3 solution with respect to the positions, gfx950: the vector-Jacobian product
+// (rp_batch_solution_vjp), the Jacobian-vector product (rp_batch_solution_jvp) and the per-problem 3 x 3 Jacobian
+// (rp_batch_solution_jacobian).
 //
 // For the state z = (x, lam), x = (vel1, duration0, duration1), the reference's residual r(z; theta, p) (onedpath_ip.cpp:753-783,
 // p held fixed) and M = dr/dz, the Newton matrix moveInteriorPoint assembles (onedpath_ip.cpp:814-861):
-//     M^T w = [g; 0_8],    theta_bar = -w^T dr/dtheta,    theta = (pos0, pos1, pos2)
-// -- the implicit-function derivative of the central-path point at this p.  M^T = [[W, G^T Lam], [G, C]]
-// condenses as the forward system does:
+//     reverse:  M^T w = [g; 0_8],    theta_bar = -w^T dr/dtheta,    theta = (pos0, pos1, pos2)
+//     forward:  M z_dot = -(dr/dtheta) theta_dot,    x_dot = the x part of z_dot
+// -- the implicit-function derivative of the central-path point at this p.  M = [[W, G^T], [Lam G, C]]
+// condenses as the Newton step does, in both directions with the same symmetric matrix:
 //     w_lam = -C^-1 G w_x,    K w_x = g,    K = W - G^T Lam C^-1 G = W + S_j D_j h_j h_j^T
 // with h_j = grad a_j and D_j = lam_p / (-c_p) + lam_m / (-c_m) of the constraint pair on acceleration j; K is solved by Gaussian
 // elimination with partial pivoting, every quotient an IEEE division.  The theta-derivative then needs only
 //     s_j = lam_p w_lam_p - lam_m w_lam_m = D_j h_j . w_x     (the multiplier-weighted dual step of pair j)
 // because r depends on theta only through dX0 = pos1 - pos0, dX1 = pos2 - pos1, affinely:
 //     d a / d dX = +-6 / t^2,   d (d a / d t) / d dX = -+12 / t^3,   d (d a / d v) / d dX = 0.
+// Forward, with b = (dr/dtheta) theta_dot: the complementarity rows give lam_dot_i = -(b_i + lam_i grad c_i . x_dot) / c_i, and
+//     K x_dot = -b_x + S_i grad c_i b_i / c_i = -b_x - S_j D_j alpha_j h_j
+// where alpha_j = (d a_j / d dX) dX_dot is the tangent of acceleration j (b_i = +-lam_i alpha_j on the pair, so a pair's two terms
+// sum to D_j: the large factors appear once, in the VJP's D_j h_j shape) and b_x = S_j mu_j beta_j, mu_j = lam_p - lam_m,
+// beta_j = (d (d a_j / d t) / d dX) dX_dot, sits in the duration rows only.
 // Why this form is accurate although D_j reaches ~1e8 relative on active rows: on the states a solve returns, lam_i c_i ~ -p for
 // every constraint, so D_j is either huge (active: lam^2 / p) or tiny (inactive: p / c^2) -- no pair sits in between.  The huge
 // part of K is H_A^T D_A H_A, and the product that matters, s_A = D_A H_A K^-1 g, has the large factors cancel analytically
 // (s_A -> H_A^-T g): an elimination error of eps relative to K itself reaches s as eps times cond(H_A)-sized factors, not times D.
-// Measured against a longdouble elimination of the full 11 x 11 system (tests/test_sensitivity_cpu.py): ~1e-14 normwise on the
-// monotone and reference-like distributions, ~1e-11 on the degenerate non-monotone one.
+// The forward product is the transpose of the same operator: K^-1 H_A^T D_A alpha_A -> H_A^-1 alpha_A (active accelerations keep
+// their values along the tangent), with the same cancellation.
+// Measured against a longdouble elimination of the full 11 x 11 system (tests/test_sensitivity_cpu.py,
+// tests/test_sensitivity_jvp_cpu.py): ~1e-14 normwise on the monotone and reference-like distributions, ~1e-11 on the degenerate
+// non-monotone one.
 //
-// One lane per problem, walking batch positions like k_solution: 16 fields read coalesced, the upstream gradient gathered at
-// prob_of[s], theta_bar scattered there -- problem order in and out.
+// One lane per problem, walking batch positions like k_solution: 16 fields read coalesced, the per-problem inputs gathered at
+// prob_of[s], the results scattered there -- problem order in and out.
 #include "ip_kernels.h"
 
 #include "../../include/rp_batch.h"
@@ -61,6 +72,44 @@ __device__ __forceinline__ void solve3_pivoted(double (&A)[3][3], double (&b)[3]
     x[2] = b[2] / A[2][2];
     x[1] = (b[1] - A[1][2] * x[2]) / A[1][1];
     x[0] = (b[0] - A[0][1] * x[1] - A[0][2] * x[2]) / A[0][0];
+}
+
+// solve3_pivoted on two right-hand sides: one pivot sequence and one set of multipliers, applied to both columns
+__device__ __forceinline__ void solve3_pivoted2(double (&A)[3][3], double (&b)[2][3], double (&x)[2][3])
+{
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+#pragma unroll
+        for (int r = k + 1; r < 3; ++r) {
+            const bool sw = __builtin_fabs(A[r][k]) > __builtin_fabs(A[k][k]);
+#pragma unroll
+            for (int c = k; c < 3; ++c) {
+                const double a = A[k][c], o = A[r][c];
+                A[k][c] = sw ? o : a;
+                A[r][c] = sw ? a : o;
+            }
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const double a = b[q][k], o = b[q][r];
+                b[q][k] = sw ? o : a;
+                b[q][r] = sw ? a : o;
+            }
+        }
+#pragma unroll
+        for (int r = k + 1; r < 3; ++r) {
+            const double f = A[r][k] / A[k][k];
+#pragma unroll
+            for (int c = k + 1; c < 3; ++c) A[r][c] -= f * A[k][c];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) b[q][r] -= f * b[q][k];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        x[q][2] = b[q][2] / A[2][2];
+        x[q][1] = (b[q][1] - A[1][2] * x[q][2]) / A[1][1];
+        x[q][0] = (b[q][0] - A[0][1] * x[q][1] - A[0][2] * x[q][2]) / A[0][0];
+    }
 }
 
 __global__ void __launch_bounds__(kVjpBlock)
@@ -135,6 +184,136 @@ k_solution_vjp(const double *__restrict__ base, size_t stride, size_t n, const u
     pos2_bar[prob] = ok ? dx1_bar : nan;
 }
 
+// The condensed system at one state (the 16 fields of a lane) for the forward kernels: K, the pair weights D_j and mu_j,
+// h_j = (gv_j, e.gt_j); returns whether the state gets the formula or NaN.  The same arithmetic as k_solution_vjp, which keeps
+// its own inline copy: moved into this helper, its device code would change.
+struct Condensed {
+    Acc<double> e;
+    double D[4], mu[4], gv[4];
+    double K[3][3];
+};
+
+__device__ __forceinline__ bool condense(const double (&f)[16], double limit, Condensed &c)
+{
+    const double v = f[0], t0 = f[1], t1 = f[2];
+    const double *lam = f + 3;
+    Prob<double> k;
+    k.v0 = f[12];
+    k.v2 = f[15];
+    k.dx0 = f[13] - f[11];
+    k.dx1 = f[14] - f[13];
+    Acc<double> &e = c.e;
+    accel_values(k, v, t0, t1, e);
+    accel_grads(k, v, e);
+    double htt[4], htv[4];
+    accel_hess(k, v, e, htt, htv);
+
+    // NaN for the states RP_ST_NONFINITE / RP_ST_INFEASIBLE describe: not finite, or some c_i > 0 (constraintsSatisfied,
+    // onedpath_ip.cpp:738-751).  Below gaps of ~1e-12 an active constraint's value is under the rounding of a - L and can come out
+    // as exactly 0: |c| is floored at the forward step's c_floor (L eps / 256).  D of that pair is then huge either way, and the
+    // result does not depend on it (s_A -> H_A^-T g).
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) ok = ok && finite_(f[i]);
+    const double c_floor = limit * 8.673617379884035e-19;
+    double (&D)[4] = c.D, (&mu)[4] = c.mu;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const double cm = c_value<double, 3>(2 * j, e, limit), cp = c_value<double, 3>(2 * j + 1, e, limit);
+        const double lm = lam[2 * j], lp = lam[2 * j + 1];
+        ok = ok && !(cm > 0.0) && !(cp > 0.0);
+        D[j] = lp / max_(-cp, c_floor) + lm / max_(-cm, c_floor);
+        mu[j] = lp - lm;      // S lam_i g_i = (lp - lm) grad a_j: the pair's weight in W = S lam_i H_i
+    }
+
+    // K = W + S_j D_j h_j h_j^T in (vel1, duration0, duration1); K(t0, t1) = 0 (no constraint touches both durations)
+    double (&gv)[4] = c.gv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gv[j] = acc_gv(e, j);
+    double (&K)[3][3] = c.K;
+    K[0][0] = D[0] * gv[0] * gv[0] + D[1] * gv[1] * gv[1] + D[2] * gv[2] * gv[2] + D[3] * gv[3] * gv[3];
+    K[0][1] = mu[0] * htv[0] + mu[1] * htv[1] + D[0] * gv[0] * e.gt[0] + D[1] * gv[1] * e.gt[1];
+    K[0][2] = mu[2] * htv[2] + mu[3] * htv[3] + D[2] * gv[2] * e.gt[2] + D[3] * gv[3] * e.gt[3];
+    K[1][1] = mu[0] * htt[0] + mu[1] * htt[1] + D[0] * e.gt[0] * e.gt[0] + D[1] * e.gt[1] * e.gt[1];
+    K[2][2] = mu[2] * htt[2] + mu[3] * htt[3] + D[2] * e.gt[2] * e.gt[2] + D[3] * e.gt[3] * e.gt[3];
+    K[1][0] = K[0][1];
+    K[2][0] = K[0][2];
+    K[1][2] = K[2][1] = 0.0;
+    return ok;
+}
+
+__device__ __forceinline__ void load_fields(const double *__restrict__ base, size_t stride, size_t s, double (&f)[16])
+{
+#pragma unroll
+    for (int i = 0; i < 16; ++i) f[i] = __builtin_nontemporal_load(base + (size_t)i * stride + s);
+}
+
+// The condensed forward right-hand side -b_x - S_j D_j alpha_j h_j for position-delta tangents (dd0, dd1) = (dX0_dot, dX1_dot):
+// alpha_j = +-6 dd / t^2 (the tangent of a_j), and b_x = S_j mu_j beta_j with beta_j = -+12 dd / t^3 in the durations' rows.
+__device__ __forceinline__ void forward_rhs(const Condensed &c, double dd0, double dd1, double (&rhs)[3])
+{
+    const Acc<double> &e = c.e;
+    const double q0 = e.r0 * e.r0, q1 = e.r1 * e.r1;
+    const double al0 = 6.0 * q0 * dd0, al1 = 6.0 * q1 * dd1;
+    double pa[4];      // D_j alpha_j: the pair's two complementarity terms, summed before they meet h_j
+    pa[0] = c.D[0] * al0;
+    pa[1] = -(c.D[1] * al0);
+    pa[2] = c.D[2] * al1;
+    pa[3] = -(c.D[3] * al1);
+    rhs[0] = -(pa[0] * c.gv[0] + pa[1] * c.gv[1] + pa[2] * c.gv[2] + pa[3] * c.gv[3]);
+    rhs[1] = -(12.0 * q0 * e.r0 * dd0 * (c.mu[1] - c.mu[0]) + pa[0] * e.gt[0] + pa[1] * e.gt[1]);
+    rhs[2] = -(12.0 * q1 * e.r1 * dd1 * (c.mu[3] - c.mu[2]) + pa[2] * e.gt[2] + pa[3] * e.gt[3]);
+}
+
+__global__ void __launch_bounds__(kVjpBlock)
+k_solution_jvp(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
+               const double *__restrict__ t_pos0, const double *__restrict__ t_pos1, const double *__restrict__ t_pos2,
+               double *__restrict__ t_vel1, double *__restrict__ t_dur0, double *__restrict__ t_dur1)
+{
+    const size_t s = (size_t)blockIdx.x * kVjpBlock + threadIdx.x;
+    if (s >= n) return;
+    double f[16];
+    load_fields(base, stride, s, f);
+    const size_t prob = prob_of ? (size_t)prob_of[s] : s;
+    const double tp0 = t_pos0 ? t_pos0[prob] : 0.0, tp1 = t_pos1 ? t_pos1[prob] : 0.0, tp2 = t_pos2 ? t_pos2[prob] : 0.0;
+
+    Condensed c;
+    const bool ok = condense(f, limit, c);
+    double rhs[3], xd[3];
+    forward_rhs(c, tp1 - tp0, tp2 - tp1, rhs);      // equal tangents: dX tangents of exactly 0
+    solve3_pivoted(c.K, rhs, xd);
+    const double nan = __builtin_nan("");
+    t_vel1[prob] = ok ? xd[0] : nan;
+    t_dur0[prob] = ok ? xd[1] : nan;
+    t_dur1[prob] = ok ? xd[2] : nan;
+}
+
+__global__ void __launch_bounds__(kVjpBlock)
+k_solution_jacobian(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
+                    double *__restrict__ jac)
+{
+    const size_t s = (size_t)blockIdx.x * kVjpBlock + threadIdx.x;
+    if (s >= n) return;
+    double f[16];
+    load_fields(base, stride, s, f);
+    const size_t prob = prob_of ? (size_t)prob_of[s] : s;
+
+    Condensed c;
+    const bool ok = condense(f, limit, c);
+    double rhs[2][3], d[2][3];      // d[0] = dx / d dX0, d[1] = dx / d dX1
+    forward_rhs(c, 1.0, 0.0, rhs[0]);
+    forward_rhs(c, 0.0, 1.0, rhs[1]);
+    solve3_pivoted2(c.K, rhs, d);
+    const double nan = __builtin_nan("");
+    double *out = jac + prob * 9;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {      // row a = x_a; columns pos0, pos1, pos2 through dX0 = pos1 - pos0, dX1 = pos2 - pos1
+        out[3 * a + 0] = ok ? -d[0][a] : nan;
+        out[3 * a + 1] = ok ? d[0][a] - d[1][a] : nan;
+        out[3 * a + 2] = ok ? d[1][a] : nan;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_solution_vjp(const BatchView &b, const HostParams &hp, const double *d_g_vel1, const double *d_g_dur0,
@@ -145,6 +324,26 @@ hipError_t launch_solution_vjp(const BatchView &b, const HostParams &hp, const d
     hipLaunchKernelGGL(k_solution_vjp, dim3(blocks), dim3(kVjpBlock), 0, stream, (const double *)b.base, b.stride, b.n,
                        b.scheduled ? (const uint32_t *)b.prob_of : nullptr, hp.accel_limit, d_g_vel1, d_g_dur0, d_g_dur1,
                        d_pos0_bar, d_pos1_bar, d_pos2_bar);
+    return hipGetLastError();
+}
+
+hipError_t launch_solution_jvp(const BatchView &b, const HostParams &hp, const double *d_t_pos0, const double *d_t_pos1,
+                               const double *d_t_pos2, double *d_t_vel1, double *d_t_dur0, double *d_t_dur1, hipStream_t stream)
+{
+    if (b.n == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((b.n + kVjpBlock - 1) / kVjpBlock);
+    hipLaunchKernelGGL(k_solution_jvp, dim3(blocks), dim3(kVjpBlock), 0, stream, (const double *)b.base, b.stride, b.n,
+                       b.scheduled ? (const uint32_t *)b.prob_of : nullptr, hp.accel_limit, d_t_pos0, d_t_pos1, d_t_pos2,
+                       d_t_vel1, d_t_dur0, d_t_dur1);
+    return hipGetLastError();
+}
+
+hipError_t launch_solution_jacobian(const BatchView &b, const HostParams &hp, double *d_jac, hipStream_t stream)
+{
+    if (b.n == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((b.n + kVjpBlock - 1) / kVjpBlock);
+    hipLaunchKernelGGL(k_solution_jacobian, dim3(blocks), dim3(kVjpBlock), 0, stream, (const double *)b.base, b.stride, b.n,
+                       b.scheduled ? (const uint32_t *)b.prob_of : nullptr, hp.accel_limit, d_jac);
     return hipGetLastError();
 }
 
