@@ -50,7 +50,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *   6  round 6: rp_pipeline_* (positions in -> solutions out over several streams); rp_params + handoff_rounds / handoff_lanes (the gated
  *      solve in rounds); a raw pointer to a mutable field keeps the seeding pass on for every later gated launch
  *   7  rp_batch_solution_vjp (gradients of the solution with respect to the positions); rp_batch_solution_jvp and
- *      rp_batch_solution_jacobian (the forward-mode derivative and the per-problem 3 x 3 Jacobian; new entries only) */
+ *      rp_batch_solution_jacobian (the forward-mode derivative and the per-problem 3 x 3 Jacobian; new entries only);
+ *      rp_batch_solution_hessian (the per-problem second derivatives; new entries only) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -256,6 +257,15 @@ RP_API int rp_batch_solution_jvp(rp_batch *b, const double *d_t_pos0, const doub
  * (RP_ERR_UNSUPPORTED otherwise); a problem whose state is not finite or outside the feasible set gets NaN in all nine entries;
  * works on the states rp_batch_solution_vjp does. */
 RP_API int rp_batch_solution_jacobian(rp_batch *b, double *d_jac);
+/* Every problem's second derivatives H[a][b][c] = d^2 x_a / dpos_b dpos_c of x = (vel1, duration0, duration1) at the batch's current
+ * state: the second derivative of the implicit function z(theta) that r(z; theta, p) = 0 defines, with the
+ * z, x, theta, r and M of rp_batch_solution_vjp -- for tangents u, w, M z_uw = -R_uw, R_uw the second total derivative of r along
+ * (z_u, u), (z_w, w) without the z_uw terms.  27 doubles per problem at d_hess[27 i + 9 a + 3 b + c], n x 27 doubles of device
+ * memory in PROBLEM order, symmetric in (b, c); every row and column of each H[a] sums to 0 up to rounding.  d_jac may be NULL;
+ * when given, it receives the Jacobian from the same first-order solves in rp_batch_solution_jacobian's layout (n x 9 doubles).
+ * Asynchronous on the batch stream.  F3, RP_DTYPE_F64 only (RP_ERR_UNSUPPORTED otherwise); a problem whose state is not finite or
+ * outside the feasible set gets NaN in all 27 (and 9) entries; works on the states rp_batch_solution_vjp does. */
+RP_API int rp_batch_solution_hessian(rp_batch *b, double *d_jac, double *d_hess);
 RP_API int rp_batch_reduce(rp_batch *b, rp_reduction *out);                   /* synchronous */
 /* Writes the 4 doubles of rp_reduction to device memory the caller owns, asynchronously on
  * the batch stream: the buffer a multi-GPU caller hands to its RCCL all-reduce. */

@@ -3,11 +3,14 @@
     vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2)
     (duration0 + duration1).sum().backward()      # -> pos0.grad, pos1.grad, pos2.grad
     vel1, duration0, duration1, iters, status, jac = min_time_jacobian(pos0, pos1, pos2)      # jac: (n, 3, 3)
+    vel1, duration0, duration1, iters, status, jac, hess = min_time_hessian(pos0, pos1, pos2)      # hess: (n, 3, 3, 3)
 
 The forward is Batch.set_problems_device + the fused gated solve + Batch.solution_device into a torch buffer, enqueued without
 synchronising the host.  The backward is one rp_batch_solution_vjp launch at the state the forward left, the forward-mode rule
 (torch.autograd.forward_ad, torch.func.jvp) one rp_batch_solution_jvp launch (include/rp_batch.h): the
-implicit-function derivative of the central-path point the solve stopped at.  F3, float64 only; no double backward, no vmap rule.
+implicit-function derivative of the central-path point the solve stopped at.  The backward is itself differentiable once more
+(double backward: torch.autograd.grad(..., create_graph=True), torch.autograd.functional.hessian), through one
+rp_batch_solution_jvp and one rp_batch_solution_hessian launch.  F3, float64 only; no vmap rule.
 """
 import ctypes
 import threading
@@ -107,9 +110,10 @@ def _run_on(batch_stream, cur):
     return _Order()
 
 
-def _solve(pos0, pos1, pos2, gap_tol, max_iter, params, jacobian=False):
+def _solve(pos0, pos1, pos2, gap_tol, max_iter, params, jacobian=False, hessian=False):
     """Enqueue the solve on the current stream with a batch taken from the pool: (key, batch, (vel1, dur0, dur1, iters, status)),
-    and the (n, 3, 3) Jacobian at the end when `jacobian`.  The caller gives the batch back or leases it."""
+    and the (n, 3, 3) Jacobian at the end when `jacobian`, the Jacobian and the (n, 3, 3, 3) Hessian (one launch) when `hessian`.
+    The caller gives the batch back or leases it."""
     device = pos0.device.index if pos0.device.index is not None else torch.cuda.current_device()
     n = pos0.shape[0]
     cur = torch.cuda.current_stream(device)
@@ -120,7 +124,8 @@ def _solve(pos0, pos1, pos2, gap_tol, max_iter, params, jacobian=False):
     ext = None if handle else torch.cuda.ExternalStream(batch.stream(), device=pos0.device)
     p0, p1, p2 = (t.contiguous() for t in (pos0, pos1, pos2))
     out = torch.empty((n, 4), dtype=torch.float64, device=pos0.device)      # n rp_solution records (torch's blocks: 512-byte aligned)
-    jac = torch.empty((n, 3, 3), dtype=torch.float64, device=pos0.device) if jacobian else None
+    jac = torch.empty((n, 3, 3), dtype=torch.float64, device=pos0.device) if jacobian or hessian else None
+    hess = torch.empty((n, 3, 3, 3), dtype=torch.float64, device=pos0.device) if hessian else None
     try:
         p = capi.Params()
         batch._lib.rp_params_default(ctypes.byref(p))
@@ -131,10 +136,12 @@ def _solve(pos0, pos1, pos2, gap_tol, max_iter, params, jacobian=False):
             batch.set_problems_device(p0.data_ptr(), p1.data_ptr(), p2.data_ptr())
             batch.solve(gap_tol, max_iter, 0)
             batch.solution_device(out.data_ptr())
-            if jac is not None:
+            if hess is not None:
+                batch.solution_hessian(jac.data_ptr(), hess.data_ptr())
+            elif jac is not None:
                 batch.solution_jacobian(jac.data_ptr())
         if ext is not None:
-            for t in (p0, p1, p2, out, jac):
+            for t in (p0, p1, p2, out, jac, hess):
                 if t is not None:
                     t.record_stream(ext)
     except Exception:
@@ -143,7 +150,7 @@ def _solve(pos0, pos1, pos2, gap_tol, max_iter, params, jacobian=False):
     vel1, dur0, dur1 = out[:, 0].clone(), out[:, 1].clone(), out[:, 2].clone()
     words = out.view(torch.int32).view(n, 8)
     iters, status = words[:, 6].clone(), words[:, 7].clone()
-    return key, batch, (vel1, dur0, dur1, iters, status) + ((jac,) if jac is not None else ())
+    return key, batch, (vel1, dur0, dur1, iters, status) + tuple(t for t in (jac, hess) if t is not None)
 
 
 def _plain(t):
@@ -176,25 +183,15 @@ class _MinTimeSolve(torch.autograd.Function):
         # goes when min_time_solve returns, so a batch nothing holds is back in the pool once its read-back is enqueued.
         ctx.lease = inputs[-1].lease
         ctx.device = inputs[0].device
+        # the positions themselves, for the graph a create_graph backward builds (_SolutionVJP takes them as inputs); kept as
+        # attributes, not saved tensors, so first-order use keeps its rules (no version check on the positions)
+        ctx.pos = inputs[:3]
         ctx.mark_non_differentiable(output[3], output[4])
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
     def backward(ctx, g_vel1, g_dur0, g_dur1, _g_iters, _g_status):
-        batch = ctx.lease.batch
-        device = ctx.device
-        cur = torch.cuda.current_stream(device)
-        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
-        gs = [g.contiguous() if g is not None else None for g in (g_vel1, g_dur0, g_dur1)]
-        n = batch.n
-        bars = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(3)]
-        same = bstream.cuda_stream == cur.cuda_stream
-        with _run_on(None if same else bstream, cur):
-            batch.solution_vjp(*[g.data_ptr() if g is not None else 0 for g in gs], *[b.data_ptr() for b in bars])
-        if not same:
-            for t in gs + bars:
-                if t is not None:
-                    t.record_stream(bstream)
+        # one rp_batch_solution_vjp launch; differentiable once more (double backward) through _SolutionVJP
+        bars = _SolutionVJP.apply(g_vel1, g_dur0, g_dur1, *ctx.pos, ctx.lease, ctx.device)
         return bars[0], bars[1], bars[2], None, None, None, None
 
     @staticmethod
@@ -217,12 +214,78 @@ class _MinTimeSolve(torch.autograd.Function):
         return outs[0], outs[1], outs[2], None, None
 
 
+class _SolutionVJP(torch.autograd.Function):
+    """theta_bar = J^T g at the state of the leased batch (rp_batch_solution_vjp), as a function of the upstream gradients g and the
+    positions theta, so that a backward run with create_graph=True can be differentiated again.  For cotangents h on theta_bar:
+        g_bar = J h                      one rp_batch_solution_jvp launch
+        pos_bar = S_a g_a H_a h          one rp_batch_solution_hessian launch and a contraction on the current stream
+    ctx holds the lease: a graph built through this function keeps the batch out of the pool until the graph is freed."""
+
+    @staticmethod
+    def forward(ctx, g_vel1, g_dur0, g_dur1, pos0, pos1, pos2, lease, device):
+        batch = lease.batch
+        cur = torch.cuda.current_stream(device)
+        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
+        gs = [g.contiguous() if g is not None else None for g in (g_vel1, g_dur0, g_dur1)]
+        n = batch.n
+        bars = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(3)]
+        same = bstream.cuda_stream == cur.cuda_stream
+        with _run_on(None if same else bstream, cur):
+            batch.solution_vjp(*[g.data_ptr() if g is not None else 0 for g in gs], *[b.data_ptr() for b in bars])
+        if not same:
+            for t in gs + bars:
+                if t is not None:
+                    t.record_stream(bstream)
+        ctx.lease = lease
+        ctx.device = device
+        ctx.save_for_backward(g_vel1, g_dur0, g_dur1)
+        return bars[0], bars[1], bars[2]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, h_pos0, h_pos1, h_pos2):
+        batch = ctx.lease.batch
+        device = ctx.device
+        gs = ctx.saved_tensors
+        need_g, need_pos = any(ctx.needs_input_grad[:3]), any(ctx.needs_input_grad[3:6])
+        hs = [h.contiguous() if h is not None else None for h in (h_pos0, h_pos1, h_pos2)]
+        n = batch.n
+        g_bar = pos_bar = (None, None, None)
+        if all(h is None for h in hs):
+            return g_bar + pos_bar + (None, None)
+        cur = torch.cuda.current_stream(device)
+        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
+        same = bstream.cuda_stream == cur.cuda_stream
+        outs = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(3)] if need_g else []
+        hess = None
+        if need_pos and any(g is not None for g in gs):
+            hess = torch.empty((n, 3, 3, 3), dtype=torch.float64, device=device)
+        with _run_on(None if same else bstream, cur):
+            if outs:
+                batch.solution_jvp(*[h.data_ptr() if h is not None else 0 for h in hs], *[o.data_ptr() for o in outs])
+            if hess is not None:
+                batch.solution_hessian(0, hess.data_ptr())
+        if not same:
+            for t in hs + outs + [hess]:
+                if t is not None:
+                    t.record_stream(bstream)
+        if outs:
+            g_bar = tuple(outs)
+        if hess is not None:
+            zero = torch.zeros(n, dtype=torch.float64, device=device)
+            gv = torch.stack([g if g is not None else zero for g in gs], dim=1)
+            hv = torch.stack([h if h is not None else zero for h in hs], dim=1)
+            pb = torch.einsum("na,nabc,nc->bn", gv, hess, hv).contiguous()
+            pos_bar = (pb[0], pb[1], pb[2])
+        return g_bar + pos_bar + (None, None)
+
+
 def min_time_solve(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None):
     """Solve the F3 problems (pos0[i], pos1[i], pos2[i]) -- 1-D float64 tensors on one ROCm device -- on the current stream.
 
     Returns (vel1, duration0, duration1, iters, status): float64 tensors, differentiable with respect to the positions in reverse
-    mode (backward) and forward mode (torch.autograd.forward_ad, torch.func.jvp), and the int32 step counts and RP_ST_* status words
-    (not differentiable).  `params`: rp_params fields to override (a dict).  Derivatives are the implicit-function derivative at the
+    mode (backward, twice: create_graph=True gives a differentiable gradient) and forward mode (torch.autograd.forward_ad,
+    torch.func.jvp), and the int32 step counts and RP_ST_* status words (not differentiable).  `params`: rp_params fields to override (a dict).  Derivatives are the implicit-function derivative at the
     state the solve returns (include/rp_batch.h, rp_batch_solution_vjp / rp_batch_solution_jvp): NaN for problems whose state is not
     finite or not strictly feasible.  Does not synchronise the host."""
     _check_positions(pos0, pos1, pos2)
@@ -239,6 +302,20 @@ def min_time_jacobian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=No
     _check_positions(pos0, pos1, pos2, "min_time_jacobian")
     _check_params(params, "min_time_jacobian")
     key, batch, outs = _solve(pos0.detach(), pos1.detach(), pos2.detach(), float(gap_tol), int(max_iter), params, jacobian=True)
+    _pool.give(key, batch)      # the read-backs are enqueued; the next user of this key works on the same stream
+    return outs
+
+
+def min_time_hessian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve's solve, and every problem's Jacobian and second derivatives at the state it returns, on the current stream.
+
+    Returns (vel1, duration0, duration1, iters, status, jac, hess) with jac (n, 3, 3) as min_time_jacobian's and hess (n, 3, 3, 3)
+    float64, hess[i, a, b, c] = d^2 x_a / dpos_b dpos_c of problem i (rp_batch_solution_hessian; symmetric in b, c; NaN for the
+    problems min_time_solve's derivatives are NaN for).  One solve and one Hessian launch; nothing returned is differentiable.  Does
+    not synchronise the host."""
+    _check_positions(pos0, pos1, pos2, "min_time_hessian")
+    _check_params(params, "min_time_hessian")
+    key, batch, outs = _solve(pos0.detach(), pos1.detach(), pos2.detach(), float(gap_tol), int(max_iter), params, hessian=True)
     _pool.give(key, batch)      # the read-backs are enqueued; the next user of this key works on the same stream
     return outs
 

@@ -161,6 +161,14 @@ class Batch:
         DTYPE_F64 only."""
         capi.check(self._lib.rp_batch_solution_jacobian(self._h, ctypes.c_void_p(d_jac) if d_jac else None))
 
+    def solution_hessian(self, d_jac, d_hess):
+        """Every problem's second derivatives H[a][b][c] = d^2 x_a / dpos_b dpos_c, x = (vel1, duration0, duration1), at the current
+        state (rp_batch_solution_hessian): d_hess the device address of n x 27 doubles, problem order, symmetric in (b, c); d_jac
+        None / 0, or n x 9 doubles for the Jacobian in solution_jacobian's layout.  Asynchronous on the batch stream.  F3 with
+        DTYPE_F64 only."""
+        capi.check(self._lib.rp_batch_solution_hessian(self._h, ctypes.c_void_p(d_jac) if d_jac else None,
+                                                       ctypes.c_void_p(d_hess) if d_hess else None))
+
     def bind_solution(self, d_out):
         """Gated solves write each problem's rp_solution record to d_out (device address of n records; None / 0 unbinds)."""
         capi.check(self._lib.rp_batch_bind_solution(self._h, ctypes.c_void_p(d_out) if d_out else None))

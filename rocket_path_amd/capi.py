@@ -86,6 +86,7 @@ SIGNATURES = {
     "rp_batch_solution_vjp": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_batch_solution_jvp": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_batch_solution_jacobian": (ctypes.c_int, [_vp, _vp]),
+    "rp_batch_solution_hessian": (ctypes.c_int, [_vp, _vp, _vp]),
     "rp_batch_traffic_probe": (ctypes.c_int, [_vp]),
     "rp_batch_reduce": (ctypes.c_int, [_vp, ctypes.POINTER(Reduction)]),
     "rp_batch_reduce_device": (ctypes.c_int, [_vp, _vp]),

@@ -90,6 +90,9 @@ hipError_t launch_solution_vjp(const BatchView &b, const HostParams &hp, const d
 hipError_t launch_solution_jvp(const BatchView &b, const HostParams &hp, const double *d_t_pos0, const double *d_t_pos1,
                                const double *d_t_pos2, double *d_t_vel1, double *d_t_dur0, double *d_t_dur1, hipStream_t stream);
 hipError_t launch_solution_jacobian(const BatchView &b, const HostParams &hp, double *d_jac, hipStream_t stream);
+// d^2(vel1, duration0, duration1) / d(pos0, pos1, pos2)^2 (27 doubles per problem) and, unless d_jac is null, the Jacobian from the
+// same first-order solves, problem order, at the batch's current state (sensitivity.hip; F3, double storage only)
+hipError_t launch_solution_hessian(const BatchView &b, const HostParams &hp, double *d_jac, double *d_hess, hipStream_t stream);
 
 // state movement / initialisation
 hipError_t launch_aos_to_soa(const BatchView &b, const double *d_aos, hipStream_t stream);

@@ -762,6 +762,17 @@ int rp_batch_solution_jacobian(rp_batch *b, double *d_jac)
     return RP_OK;
 }
 
+int rp_batch_solution_hessian(rp_batch *b, double *d_jac, double *d_hess)
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
+        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_hessian: F3 with RP_DTYPE_F64 only");
+    if (!d_hess) return fail(RP_ERR_INVALID, "null output");
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_solution_hessian(b->view, b->params, d_jac, d_hess, b->stream));
+    return RP_OK;
+}
+
 int rp_batch_bind_solution(rp_batch *b, rp_solution *d_out)
 {
     if (!b) return fail(RP_ERR_INVALID, "null batch handle");

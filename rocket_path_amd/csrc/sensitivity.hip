@@ -1,6 +1,6 @@
 // sensitivity.hip -- derivatives of an F3 solution with respect to the positions, gfx950: the vector-Jacobian product
-// (rp_batch_solution_vjp), the Jacobian-vector product (rp_batch_solution_jvp) and the per-problem 3 x 3 Jacobian
-// (rp_batch_solution_jacobian).
+// (rp_batch_solution_vjp), the Jacobian-vector product (rp_batch_solution_jvp), the per-problem 3 x 3 Jacobian
+// (rp_batch_solution_jacobian) and the per-problem 3 x 3 x 3 Hessian (rp_batch_solution_hessian, see k_solution_hessian).
 //
 // For the state z = (x, lam), x = (vel1, duration0, duration1), the reference's residual r(z; theta, p) (onedpath_ip.cpp:753-783,
 // p held fixed) and M = dr/dz, the Newton matrix moveInteriorPoint assembles (onedpath_ip.cpp:814-861):
@@ -314,6 +314,190 @@ k_solution_jacobian(const double *__restrict__ base, size_t stride, size_t n, co
     }
 }
 
+// X = A^-1 B for an N x N system and R right-hand sides: solve3_pivoted's elimination at any size (the second-order kernel's
+// 7 x 7 and 3 x 3 solves).  Each row below k is compared with row k in turn and swapped in when larger, so row k ends with the
+// column's largest magnitude; the swaps are selects on registers.
+template <int N, int R>
+__device__ __forceinline__ void solve_pivoted(double (&A)[N][N], double (&B)[R][N], double (&X)[R][N])
+{
+#pragma unroll
+    for (int k = 0; k < N - 1; ++k) {
+#pragma unroll
+        for (int r = k + 1; r < N; ++r) {
+            const bool sw = __builtin_fabs(A[r][k]) > __builtin_fabs(A[k][k]);
+#pragma unroll
+            for (int c = k; c < N; ++c) {
+                const double a = A[k][c], o = A[r][c];
+                A[k][c] = sw ? o : a;
+                A[r][c] = sw ? a : o;
+            }
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const double a = B[q][k], o = B[q][r];
+                B[q][k] = sw ? o : a;
+                B[q][r] = sw ? a : o;
+            }
+        }
+#pragma unroll
+        for (int r = k + 1; r < N; ++r) {
+            const double f = A[r][k] / A[k][k];
+#pragma unroll
+            for (int c = k + 1; c < N; ++c) A[r][c] -= f * A[k][c];
+#pragma unroll
+            for (int q = 0; q < R; ++q) B[q][r] -= f * B[q][k];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+#pragma unroll
+        for (int k = N - 1; k >= 0; --k) {
+            double acc = B[q][k];
+#pragma unroll
+            for (int c = k + 1; c < N; ++c) acc -= A[k][c] * X[q][c];
+            X[q][k] = acc / A[k][k];
+        }
+    }
+}
+
+// Second derivatives (rp_batch_solution_hessian).  For position-delta tangents u, w (the unit dX0 and dX1
+// directions): M z_uw = -R_uw, R_uw the second total derivative of r along (z_u, u), (z_w, w) without the z_uw terms.  With the
+// multipliers eliminated as in the VJP, on the same K:
+//     K x_uw = -T_uw - S_j h_j (D_j Q_j,uw + 2 (E_j / D_j^2) mu_j,u mu_j,w)
+//     T_uw = S_j [mu_j,u h_j,w + mu_j,w h_j,u + mu_j a3_j(u, w)],    E_j = lam_p / c_p^2 - lam_m / c_m^2
+// where a_j is differentiated in (v, t, dX) of its segment: Q_j,uw = y_u^T (grad^2 a_j) y_w with y_u = (v_u, t_u, dX_u), h_j,w the
+// derivative of h_j along y_w, a3_j(u, w) = grad_x (grad^2 a_j)[y_u, y_w] (the non-zero third derivatives: a_ttt, a_vtt, a_Xtt).
+// The pair's first-order dual step mu_j,u = D_j A_j,u is O(1), but A_j,u (the total derivative of a_j) cancels to O(p) on an
+// active pair: formed from the condensed x_u, eps-level errors come back multiplied by D_j.  So the first-order steps are the
+// unknowns of the 7 x 7 symmetric system [[W, H^T], [H, -diag(1 / D)]] [x_u; mu_u] = [-b_x; -alpha_u] (row j: h_j . x_u -
+// mu_j,u / D_j = -alpha_j,u, well scaled whether the pair is active or not), and E_j / D_j^2 -> 1 / lam on an active pair: no large
+// factor is formed outside K.  a_j = 6 sg_j dX r^2 + w_j r (r = 1 / t, w_j the velocity combination, dw_j / dv = cv_j).
+__global__ void __launch_bounds__(kVjpBlock)
+k_solution_hessian(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
+                   double *__restrict__ jac, double *__restrict__ hess)
+{
+    const size_t s = (size_t)blockIdx.x * kVjpBlock + threadIdx.x;
+    if (s >= n) return;
+    double f[16];
+    load_fields(base, stride, s, f);
+    const size_t prob = prob_of ? (size_t)prob_of[s] : s;
+
+    Condensed c;
+    const bool ok = condense(f, limit, c);
+    const Acc<double> &e = c.e;
+    const double v = f[0], v0 = f[12], v2 = f[15];
+    const double dx[2] = {f[13] - f[11], f[14] - f[13]};
+    const double wj[4] = {-4.0 * v0 - 2.0 * v, 2.0 * v0 + 4.0 * v, -4.0 * v - 2.0 * v2, 2.0 * v + 4.0 * v2};
+    constexpr double sg[4] = {1.0, -1.0, 1.0, -1.0}, cv[4] = {-2.0, 4.0, -4.0, 2.0};
+    double ed2[4];
+    const double c_floor = limit * 8.673617379884035e-19;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {      // E_j / D_j^2 with the constraint values floored as D_j's are
+        const double cm = max_(-c_value<double, 3>(2 * j, e, limit), c_floor), cp = max_(-c_value<double, 3>(2 * j + 1, e, limit), c_floor);
+        ed2[j] = (f[4 + 2 * j] / (cp * cp) - f[3 + 2 * j] / (cm * cm)) / (c.D[j] * c.D[j]);
+    }
+
+    // first order: [[W, H^T], [H, -diag(1 / D)]] [x_u; mu_u] = [-b_x; -alpha_u] for u = dX0, dX1
+    double A[7][7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i)
+#pragma unroll
+        for (int k = 0; k < 7; ++k) A[i][k] = 0.0;
+    {
+        Prob<double> k;
+        k.v0 = v0;
+        k.v2 = v2;
+        k.dx0 = dx[0];
+        k.dx1 = dx[1];
+        double htt[4], htv[4];
+        accel_hess(k, v, e, htt, htv);
+        A[0][1] = A[1][0] = c.mu[0] * htv[0] + c.mu[1] * htv[1];      // W: K's second-derivative part
+        A[0][2] = A[2][0] = c.mu[2] * htv[2] + c.mu[3] * htv[3];
+        A[1][1] = c.mu[0] * htt[0] + c.mu[1] * htt[1];
+        A[2][2] = c.mu[2] * htt[2] + c.mu[3] * htt[3];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int seg = 1 + (j >> 1);
+        A[0][3 + j] = A[3 + j][0] = c.gv[j];
+        A[seg][3 + j] = A[3 + j][seg] = e.gt[j];
+        A[3 + j][3 + j] = -1.0 / max_(c.D[j], 2.2250738585072014e-308);
+    }
+    double B[2][7], Z[2][7];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int i = 0; i < 7; ++i) B[u][i] = 0.0;
+    const double q0 = e.r0 * e.r0, q1 = e.r1 * e.r1;
+    B[0][1] = -(12.0 * q0 * e.r0 * (c.mu[1] - c.mu[0]));
+    B[1][2] = -(12.0 * q1 * e.r1 * (c.mu[3] - c.mu[2]));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) B[j >> 1][3 + j] = -(6.0 * sg[j] * (j < 2 ? q0 : q1));
+    solve_pivoted<7, 2>(A, B, Z);      // Z[u] = (x_u, mu_u)
+
+    // second order: three right-hand sides (u, w) = (0, 0), (0, 1), (1, 1) on K, from a_j's derivatives in (v, t, dX)
+    double att[4], avt[4], axt[4], attt[4], avtt[4], axtt[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const double r = j < 2 ? e.r0 : e.r1;
+        const double r2 = r * r, r3 = r2 * r, r4 = r2 * r2, u = dx[j >> 1] * r;
+        att[j] = (36.0 * sg[j] * u + 2.0 * wj[j]) * r3;
+        avt[j] = -cv[j] * r2;
+        axt[j] = -12.0 * sg[j] * r3;
+        attt[j] = -(144.0 * sg[j] * u + 6.0 * wj[j]) * r4;
+        avtt[j] = 2.0 * cv[j] * r3;
+        axtt[j] = 36.0 * sg[j] * r4;
+    }
+    double S[3][3], xw[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int u = k == 2 ? 1 : 0, w = k == 0 ? 0 : 1;
+        S[k][0] = S[k][1] = S[k][2] = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int seg = j >> 1;
+            const double vu = Z[u][0], tu = Z[u][1 + seg], Xu = seg == u ? 1.0 : 0.0;
+            const double vw = Z[w][0], tw = Z[w][1 + seg], Xw = seg == w ? 1.0 : 0.0;
+            const double mu_u = Z[u][3 + j], mu_w = Z[w][3 + j];
+            const double tt = tu * tw, vt = vu * tw + vw * tu, Xt = Xu * tw + Xw * tu;
+            const double Q = att[j] * tt + avt[j] * vt + axt[j] * Xt;
+            const double a3v = c.mu[j] * (avtt[j] * tt);
+            const double a3t = c.mu[j] * (attt[j] * tt + avtt[j] * vt + axtt[j] * Xt);
+            const double hv_u = avt[j] * tu, hv_w = avt[j] * tw;
+            const double ht_u = att[j] * tu + avt[j] * vu + axt[j] * Xu, ht_w = att[j] * tw + avt[j] * vw + axt[j] * Xw;
+            const double sj = c.D[j] * Q + 2.0 * ed2[j] * mu_u * mu_w;
+            S[k][0] -= mu_u * hv_w + mu_w * hv_u + a3v + sj * c.gv[j];
+            S[k][1 + seg] -= mu_u * ht_w + mu_w * ht_u + a3t + sj * e.gt[j];
+        }
+    }
+    solve_pivoted<3, 3>(c.K, S, xw);
+
+    const double nan = __builtin_nan("");
+    if (jac) {
+        double *out = jac + prob * 9;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {      // rp_batch_solution_jacobian's layout
+            out[3 * a + 0] = ok ? -Z[0][a] : nan;
+            out[3 * a + 1] = ok ? Z[0][a] - Z[1][a] : nan;
+            out[3 * a + 2] = ok ? Z[1][a] : nan;
+        }
+    }
+    // H[a] = P^T [[x00, x01], [x01, x11]] P, P = d(dX0, dX1) / d(pos0, pos1, pos2) = [[-1, 1, 0], [0, -1, 1]]
+    double *out = hess + prob * 27;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double h00 = xw[0][a], h02 = -xw[1][a], h22 = xw[2][a];
+        const double h01 = xw[1][a] - xw[0][a], h12 = xw[1][a] - xw[2][a];
+        const double h11 = -h01 - h12;
+        const double H[6] = {h00, h01, h02, h11, h12, h22};      // (b, c) = 00, 01, 02, 11, 12, 22
+        out[9 * a + 0] = ok ? H[0] : nan;
+        out[9 * a + 1] = out[9 * a + 3] = ok ? H[1] : nan;
+        out[9 * a + 2] = out[9 * a + 6] = ok ? H[2] : nan;
+        out[9 * a + 4] = ok ? H[3] : nan;
+        out[9 * a + 5] = out[9 * a + 7] = ok ? H[4] : nan;
+        out[9 * a + 8] = ok ? H[5] : nan;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_solution_vjp(const BatchView &b, const HostParams &hp, const double *d_g_vel1, const double *d_g_dur0,
@@ -344,6 +528,15 @@ hipError_t launch_solution_jacobian(const BatchView &b, const HostParams &hp, do
     const unsigned blocks = (unsigned)((b.n + kVjpBlock - 1) / kVjpBlock);
     hipLaunchKernelGGL(k_solution_jacobian, dim3(blocks), dim3(kVjpBlock), 0, stream, (const double *)b.base, b.stride, b.n,
                        b.scheduled ? (const uint32_t *)b.prob_of : nullptr, hp.accel_limit, d_jac);
+    return hipGetLastError();
+}
+
+hipError_t launch_solution_hessian(const BatchView &b, const HostParams &hp, double *d_jac, double *d_hess, hipStream_t stream)
+{
+    if (b.n == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((b.n + kVjpBlock - 1) / kVjpBlock);
+    hipLaunchKernelGGL(k_solution_hessian, dim3(blocks), dim3(kVjpBlock), 0, stream, (const double *)b.base, b.stride, b.n,
+                       b.scheduled ? (const uint32_t *)b.prob_of : nullptr, hp.accel_limit, d_jac, d_hess);
     return hipGetLastError();
 }
 
