@@ -9,8 +9,8 @@
 // -- the implicit-function derivative of the central-path point at this p.  M = [[W, G^T], [Lam G, C]]
 // condenses as the Newton step does, in both directions with the same symmetric matrix:
 //     w_lam = -C^-1 G w_x,    K w_x = g,    K = W - G^T Lam C^-1 G = W + S_j D_j h_j h_j^T
-// with h_j = grad a_j and D_j = lam_p / (-c_p) + lam_m / (-c_m) of the constraint pair on acceleration j; K is solved by Gaussian
-// elimination with partial pivoting, every quotient an IEEE division.  The theta-derivative then needs only
+// with h_j = grad a_j and D_j = lam_p / (-c_p) + lam_m / (-c_m) of the constraint pair on acceleration j; K is formed and solved by
+// Gaussian elimination with partial pivoting in double-double (see below).  The theta-derivative then needs only
 //     s_j = lam_p w_lam_p - lam_m w_lam_m = D_j h_j . w_x     (the multiplier-weighted dual step of pair j)
 // because r depends on theta only through dX0 = pos1 - pos0, dX1 = pos2 - pos1, affinely:
 //     d a / d dX = +-6 / t^2,   d (d a / d t) / d dX = -+12 / t^3,   d (d a / d v) / d dX = 0.
@@ -19,15 +19,15 @@
 // where alpha_j = (d a_j / d dX) dX_dot is the tangent of acceleration j (b_i = +-lam_i alpha_j on the pair, so a pair's two terms
 // sum to D_j: the large factors appear once, in the VJP's D_j h_j shape) and b_x = S_j mu_j beta_j, mu_j = lam_p - lam_m,
 // beta_j = (d (d a_j / d t) / d dX) dX_dot, sits in the duration rows only.
-// Why this form is accurate although D_j reaches ~1e8 relative on active rows: on the states a solve returns, lam_i c_i ~ -p for
-// every constraint, so D_j is either huge (active: lam^2 / p) or tiny (inactive: p / c^2) -- no pair sits in between.  The huge
-// part of K is H_A^T D_A H_A, and the product that matters, s_A = D_A H_A K^-1 g, has the large factors cancel analytically
-// (s_A -> H_A^-T g): an elimination error of eps relative to K itself reaches s as eps times cond(H_A)-sized factors, not times D.
-// The forward product is the transpose of the same operator: K^-1 H_A^T D_A alpha_A -> H_A^-1 alpha_A (active accelerations keep
-// their values along the tangent), with the same cancellation.
-// Measured against a longdouble elimination of the full 11 x 11 system (tests/test_sensitivity_cpu.py,
-// tests/test_sensitivity_jvp_cpu.py): ~1e-14 normwise on the monotone and reference-like distributions, ~1e-11 on the degenerate
-// non-monotone one.
+// Why double-double: D_j reaches lam^2 / p on an active pair (~1e8 at gap 1e-8, ~1e12 at 1e-13, ~1e17 where |c| is floored).  Where
+// the active rows H_A leave a null space (two active constraints, some with three), the solution's component in it is set by W
+// alone, which sits that far below D_A h h^T in K: a K rounded to float64 loses it (errors up to 1e2 relative).  With every product
+// D_j h_j exact and K, the forward right-hand side and the elimination in ~106 bits, the result is the exact solution of the
+// condensed system for the float64 inputs W, h_j, D_j -- that is, of the well-conditioned system [[W, H^T], [H, -diag(1 / D)]]
+// (eliminating its last four unknowns gives K), whose inputs' rounding moves the answer by its own condition number times eps.
+// That 7 x 7 system solved in float64 would do the same but does not fit the register budget.  Measured
+// against a longdouble elimination of the full 11 x 11 system (tests/test_sensitivity_edges_cpu.py and the first-order CPU tests):
+// ~1e-14 normwise on the generators' problems, <= 5e-12 with non-zero end velocities.
 //
 // One lane per problem, walking batch positions like k_solution: 16 fields read coalesced, the per-problem inputs gathered at
 // prob_of[s], the results scattered there -- problem order in and out.
@@ -42,155 +42,116 @@ namespace {
 
 constexpr int kVjpBlock = 256;
 
-// x = A^-1 b for a 3 x 3 system: Gaussian elimination with partial pivoting.  The row swaps are selects on registers
-// (a dynamically indexed row would go to scratch).
-__device__ __forceinline__ void solve3_pivoted(double (&A)[3][3], double (&b)[3], double (&x)[3])
+// Double-double arithmetic: a value is hi + lo, the pair's sum exact, ~106 significant bits -- for the condensed K, whose
+// D_j h_j h_j^T part reaches ~1e12 (gap 1e-8) to ~1e17 (gap 1e-13, |c| floored) times W; in float64 the component of the solution
+// in the null space of the active rows, which W alone determines, would be lost in the rounding of K (see the block comment
+// further down).  two_sum, quick_two_sum and two_prod are the error-free transformations; the sums are the accurate (not the
+// sloppy) double-double addition, since the elimination cancels.
+struct ddv {
+    double hi, lo;
+};
+
+__device__ __forceinline__ ddv two_sum(double a, double b)
+{
+    const double s = a + b, bb = s - a;
+    return {s, (a - (s - bb)) + (b - bb)};
+}
+
+__device__ __forceinline__ ddv quick_two_sum(double a, double b)
+{
+    const double s = a + b;
+    return {s, b - (s - a)};
+}
+
+__device__ __forceinline__ ddv two_prod(double a, double b)      // a * b exactly
+{
+    const double p = a * b;
+    return {p, __builtin_fma(a, b, -p)};
+}
+
+__device__ __forceinline__ ddv dd_add(ddv x, ddv y)
+{
+    const ddv s = two_sum(x.hi, y.hi), t = two_sum(x.lo, y.lo);
+    const ddv u = quick_two_sum(s.hi, s.lo + t.hi);
+    return quick_two_sum(u.hi, u.lo + t.lo);
+}
+
+__device__ __forceinline__ ddv dd_neg(ddv x) { return {-x.hi, -x.lo}; }
+__device__ __forceinline__ ddv dd_sub(ddv x, ddv y) { return dd_add(x, dd_neg(y)); }
+__device__ __forceinline__ ddv dd_of(double a) { return {a, 0.0}; }
+
+__device__ __forceinline__ ddv dd_mul_d(ddv x, double c)
+{
+    const ddv p = two_prod(x.hi, c);
+    return quick_two_sum(p.hi, p.lo + x.lo * c);
+}
+
+__device__ __forceinline__ ddv dd_mul(ddv x, ddv y)
+{
+    const ddv p = two_prod(x.hi, y.hi);
+    return quick_two_sum(p.hi, p.lo + (x.hi * y.lo + x.lo * y.hi));
+}
+
+__device__ __forceinline__ ddv dd_div(ddv x, ddv y)
+{
+    const double q1 = x.hi / y.hi;
+    const ddv r = dd_sub(x, dd_mul_d(y, q1));
+    return quick_two_sum(q1, r.hi / y.hi);
+}
+
+// X = K^-1 B for the 3 x 3 double-double K and R right-hand sides: Gaussian elimination with partial pivoting (on the high
+// parts), every operation in double-double.  Each row below k is compared with row k in turn and swapped in when larger, so row k
+// ends with the column's largest magnitude; the swaps are selects on registers (a dynamically indexed row would go to scratch).
+template <int R>
+__device__ __forceinline__ void solve3_dd(ddv (&A)[3][3], ddv (&B)[R][3], ddv (&X)[R][3])
 {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
 #pragma unroll
         for (int r = k + 1; r < 3; ++r) {
-            const bool sw = __builtin_fabs(A[r][k]) > __builtin_fabs(A[k][k]);
+            const bool sw = __builtin_fabs(A[r][k].hi) > __builtin_fabs(A[k][k].hi);
 #pragma unroll
             for (int c = k; c < 3; ++c) {
-                const double a = A[k][c], o = A[r][c];
-                A[k][c] = sw ? o : a;
-                A[r][c] = sw ? a : o;
-            }
-            const double a = b[k], o = b[r];
-            b[k] = sw ? o : a;
-            b[r] = sw ? a : o;
-        }
-#pragma unroll
-        for (int r = k + 1; r < 3; ++r) {
-            const double f = A[r][k] / A[k][k];
-#pragma unroll
-            for (int c = k + 1; c < 3; ++c) A[r][c] -= f * A[k][c];
-            b[r] -= f * b[k];
-        }
-    }
-    x[2] = b[2] / A[2][2];
-    x[1] = (b[1] - A[1][2] * x[2]) / A[1][1];
-    x[0] = (b[0] - A[0][1] * x[1] - A[0][2] * x[2]) / A[0][0];
-}
-
-// solve3_pivoted on two right-hand sides: one pivot sequence and one set of multipliers, applied to both columns
-__device__ __forceinline__ void solve3_pivoted2(double (&A)[3][3], double (&b)[2][3], double (&x)[2][3])
-{
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-#pragma unroll
-        for (int r = k + 1; r < 3; ++r) {
-            const bool sw = __builtin_fabs(A[r][k]) > __builtin_fabs(A[k][k]);
-#pragma unroll
-            for (int c = k; c < 3; ++c) {
-                const double a = A[k][c], o = A[r][c];
+                const ddv a = A[k][c], o = A[r][c];
                 A[k][c] = sw ? o : a;
                 A[r][c] = sw ? a : o;
             }
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const double a = b[q][k], o = b[q][r];
-                b[q][k] = sw ? o : a;
-                b[q][r] = sw ? a : o;
+            for (int q = 0; q < R; ++q) {
+                const ddv a = B[q][k], o = B[q][r];
+                B[q][k] = sw ? o : a;
+                B[q][r] = sw ? a : o;
             }
         }
 #pragma unroll
         for (int r = k + 1; r < 3; ++r) {
-            const double f = A[r][k] / A[k][k];
+            const ddv f = dd_div(A[r][k], A[k][k]);
 #pragma unroll
-            for (int c = k + 1; c < 3; ++c) A[r][c] -= f * A[k][c];
+            for (int c = k + 1; c < 3; ++c) A[r][c] = dd_sub(A[r][c], dd_mul(f, A[k][c]));
 #pragma unroll
-            for (int q = 0; q < 2; ++q) b[q][r] -= f * b[q][k];
+            for (int q = 0; q < R; ++q) B[q][r] = dd_sub(B[q][r], dd_mul(f, B[q][k]));
         }
     }
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        x[q][2] = b[q][2] / A[2][2];
-        x[q][1] = (b[q][1] - A[1][2] * x[q][2]) / A[1][1];
-        x[q][0] = (b[q][0] - A[0][1] * x[q][1] - A[0][2] * x[q][2]) / A[0][0];
+    for (int q = 0; q < R; ++q) {
+#pragma unroll
+        for (int k = 2; k >= 0; --k) {
+            ddv acc = B[q][k];
+#pragma unroll
+            for (int c = k + 1; c < 3; ++c) acc = dd_sub(acc, dd_mul(A[k][c], X[q][c]));
+            X[q][k] = dd_div(acc, A[k][k]);
+        }
     }
 }
 
-__global__ void __launch_bounds__(kVjpBlock)
-k_solution_vjp(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
-               const double *__restrict__ g_vel1, const double *__restrict__ g_dur0, const double *__restrict__ g_dur1,
-               double *__restrict__ pos0_bar, double *__restrict__ pos1_bar, double *__restrict__ pos2_bar)
-{
-    const size_t s = (size_t)blockIdx.x * kVjpBlock + threadIdx.x;
-    if (s >= n) return;
-    double f[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) f[i] = __builtin_nontemporal_load(base + (size_t)i * stride + s);
-    const size_t prob = prob_of ? (size_t)prob_of[s] : s;
-    const double g[3] = {g_vel1 ? g_vel1[prob] : 0.0, g_dur0 ? g_dur0[prob] : 0.0, g_dur1 ? g_dur1[prob] : 0.0};
-
-    const double v = f[0], t0 = f[1], t1 = f[2];
-    const double *lam = f + 3;
-    Prob<double> k;
-    k.v0 = f[12];
-    k.v2 = f[15];
-    k.dx0 = f[13] - f[11];
-    k.dx1 = f[14] - f[13];
-    Acc<double> e;
-    accel_values(k, v, t0, t1, e);
-    accel_grads(k, v, e);
-    double htt[4], htv[4];
-    accel_hess(k, v, e, htt, htv);
-
-    // NaN for the states RP_ST_NONFINITE / RP_ST_INFEASIBLE describe: not finite, or some c_i > 0 (constraintsSatisfied,
-    // onedpath_ip.cpp:738-751).  Below gaps of ~1e-12 an active constraint's value is under the rounding of a - L and can come out
-    // as exactly 0: |c| is floored at the forward step's c_floor (L eps / 256).  D of that pair is then huge either way, and the
-    // result does not depend on it (s_A -> H_A^-T g).
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) ok = ok && finite_(f[i]);
-    const double c_floor = limit * 8.673617379884035e-19;
-    double D[4], mu[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const double cm = c_value<double, 3>(2 * j, e, limit), cp = c_value<double, 3>(2 * j + 1, e, limit);
-        const double lm = lam[2 * j], lp = lam[2 * j + 1];
-        ok = ok && !(cm > 0.0) && !(cp > 0.0);
-        D[j] = lp / max_(-cp, c_floor) + lm / max_(-cm, c_floor);
-        mu[j] = lp - lm;      // S lam_i g_i = (lp - lm) grad a_j: the pair's weight in W = S lam_i H_i
-    }
-
-    // K = W + S_j D_j h_j h_j^T in (vel1, duration0, duration1); K(t0, t1) = 0 (no constraint touches both durations)
-    double gv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) gv[j] = acc_gv(e, j);
-    double K[3][3];
-    K[0][0] = D[0] * gv[0] * gv[0] + D[1] * gv[1] * gv[1] + D[2] * gv[2] * gv[2] + D[3] * gv[3] * gv[3];
-    K[0][1] = mu[0] * htv[0] + mu[1] * htv[1] + D[0] * gv[0] * e.gt[0] + D[1] * gv[1] * e.gt[1];
-    K[0][2] = mu[2] * htv[2] + mu[3] * htv[3] + D[2] * gv[2] * e.gt[2] + D[3] * gv[3] * e.gt[3];
-    K[1][1] = mu[0] * htt[0] + mu[1] * htt[1] + D[0] * e.gt[0] * e.gt[0] + D[1] * e.gt[1] * e.gt[1];
-    K[2][2] = mu[2] * htt[2] + mu[3] * htt[3] + D[2] * e.gt[2] * e.gt[2] + D[3] * e.gt[3] * e.gt[3];
-    K[1][0] = K[0][1];
-    K[2][0] = K[0][2];
-    K[1][2] = K[2][1] = 0.0;
-    double rhs[3] = {g[0], g[1], g[2]}, w[3];
-    solve3_pivoted(K, rhs, w);
-
-    double sj[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sj[j] = D[j] * (gv[j] * w[0] + e.gt[j] * w[1 + (j >> 1)]);
-    const double q0 = e.r0 * e.r0, q1 = e.r1 * e.r1;
-    const double dx0_bar = -(12.0 * q0 * e.r0 * w[1] * (mu[1] - mu[0]) + 6.0 * q0 * (sj[0] - sj[1]));
-    const double dx1_bar = -(12.0 * q1 * e.r1 * w[2] * (mu[3] - mu[2]) + 6.0 * q1 * (sj[2] - sj[3]));
-    const double nan = __builtin_nan("");
-    pos0_bar[prob] = ok ? -dx0_bar : nan;
-    pos1_bar[prob] = ok ? dx0_bar - dx1_bar : nan;
-    pos2_bar[prob] = ok ? dx1_bar : nan;
-}
-
-// The condensed system at one state (the 16 fields of a lane) for the forward kernels: K, the pair weights D_j and mu_j,
-// h_j = (gv_j, e.gt_j); returns whether the state gets the formula or NaN.  The same arithmetic as k_solution_vjp, which keeps
-// its own inline copy: moved into this helper, its device code would change.
+// The condensed system at one state (the 16 fields of a lane): the pair weights D_j and mu_j, h_j = (gv_j, e.gt_j), the exact
+// products D_j h_j and K = W + S_j D_j h_j h_j^T in double-double (condense_K); returns whether the state gets the formula or NaN.
 struct Condensed {
     Acc<double> e;
     double D[4], mu[4], gv[4];
-    double K[3][3];
+    double W01, W02, W11, W22;      // W = S_j mu_j grad^2 a_j: W(v, v) = W(t0, t1) = 0
+    ddv Dgv[4], Dgt[4];             // D_j gv_j, D_j gt_j
+    ddv K[3][3];
 };
 
 __device__ __forceinline__ bool condense(const double (&f)[16], double limit, Condensed &c)
@@ -216,7 +177,7 @@ __device__ __forceinline__ bool condense(const double (&f)[16], double limit, Co
 #pragma unroll
     for (int i = 0; i < 16; ++i) ok = ok && finite_(f[i]);
     const double c_floor = limit * 8.673617379884035e-19;
-    double (&D)[4] = c.D, (&mu)[4] = c.mu;
+    double (&D)[4] = c.D, (&mu)[4] = c.mu, (&gv)[4] = c.gv;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const double cm = c_value<double, 3>(2 * j, e, limit), cp = c_value<double, 3>(2 * j + 1, e, limit);
@@ -224,22 +185,38 @@ __device__ __forceinline__ bool condense(const double (&f)[16], double limit, Co
         ok = ok && !(cm > 0.0) && !(cp > 0.0);
         D[j] = lp / max_(-cp, c_floor) + lm / max_(-cm, c_floor);
         mu[j] = lp - lm;      // S lam_i g_i = (lp - lm) grad a_j: the pair's weight in W = S lam_i H_i
+        gv[j] = acc_gv(e, j);
+    }
+    c.W01 = mu[0] * htv[0] + mu[1] * htv[1];
+    c.W02 = mu[2] * htv[2] + mu[3] * htv[3];
+    c.W11 = mu[0] * htt[0] + mu[1] * htt[1];
+    c.W22 = mu[2] * htt[2] + mu[3] * htt[3];
+    return ok;
+}
+
+// K = W + S_j D_j h_j h_j^T in (vel1, duration0, duration1) and the products D_j h_j, in double-double
+__device__ __forceinline__ void condense_K(Condensed &c)
+{
+    const Acc<double> &e = c.e;
+    const double (&gv)[4] = c.gv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        c.Dgv[j] = two_prod(c.D[j], gv[j]);
+        c.Dgt[j] = two_prod(c.D[j], e.gt[j]);
     }
 
     // K = W + S_j D_j h_j h_j^T in (vel1, duration0, duration1); K(t0, t1) = 0 (no constraint touches both durations)
-    double (&gv)[4] = c.gv;
+    ddv (&K)[3][3] = c.K;
+    K[0][0] = dd_mul_d(c.Dgv[0], gv[0]);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) gv[j] = acc_gv(e, j);
-    double (&K)[3][3] = c.K;
-    K[0][0] = D[0] * gv[0] * gv[0] + D[1] * gv[1] * gv[1] + D[2] * gv[2] * gv[2] + D[3] * gv[3] * gv[3];
-    K[0][1] = mu[0] * htv[0] + mu[1] * htv[1] + D[0] * gv[0] * e.gt[0] + D[1] * gv[1] * e.gt[1];
-    K[0][2] = mu[2] * htv[2] + mu[3] * htv[3] + D[2] * gv[2] * e.gt[2] + D[3] * gv[3] * e.gt[3];
-    K[1][1] = mu[0] * htt[0] + mu[1] * htt[1] + D[0] * e.gt[0] * e.gt[0] + D[1] * e.gt[1] * e.gt[1];
-    K[2][2] = mu[2] * htt[2] + mu[3] * htt[3] + D[2] * e.gt[2] * e.gt[2] + D[3] * e.gt[3] * e.gt[3];
+    for (int j = 1; j < 4; ++j) K[0][0] = dd_add(K[0][0], dd_mul_d(c.Dgv[j], gv[j]));
+    K[0][1] = dd_add(dd_of(c.W01), dd_add(dd_mul_d(c.Dgv[0], e.gt[0]), dd_mul_d(c.Dgv[1], e.gt[1])));
+    K[0][2] = dd_add(dd_of(c.W02), dd_add(dd_mul_d(c.Dgv[2], e.gt[2]), dd_mul_d(c.Dgv[3], e.gt[3])));
+    K[1][1] = dd_add(dd_of(c.W11), dd_add(dd_mul_d(c.Dgt[0], e.gt[0]), dd_mul_d(c.Dgt[1], e.gt[1])));
+    K[2][2] = dd_add(dd_of(c.W22), dd_add(dd_mul_d(c.Dgt[2], e.gt[2]), dd_mul_d(c.Dgt[3], e.gt[3])));
     K[1][0] = K[0][1];
     K[2][0] = K[0][2];
-    K[1][2] = K[2][1] = 0.0;
-    return ok;
+    K[1][2] = K[2][1] = dd_of(0.0);
 }
 
 __device__ __forceinline__ void load_fields(const double *__restrict__ base, size_t stride, size_t s, double (&f)[16])
@@ -248,21 +225,51 @@ __device__ __forceinline__ void load_fields(const double *__restrict__ base, siz
     for (int i = 0; i < 16; ++i) f[i] = __builtin_nontemporal_load(base + (size_t)i * stride + s);
 }
 
-// The condensed forward right-hand side -b_x - S_j D_j alpha_j h_j for position-delta tangents (dd0, dd1) = (dX0_dot, dX1_dot):
-// alpha_j = +-6 dd / t^2 (the tangent of a_j), and b_x = S_j mu_j beta_j with beta_j = -+12 dd / t^3 in the durations' rows.
-__device__ __forceinline__ void forward_rhs(const Condensed &c, double dd0, double dd1, double (&rhs)[3])
+__global__ void __launch_bounds__(kVjpBlock)
+k_solution_vjp(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
+               const double *__restrict__ g_vel1, const double *__restrict__ g_dur0, const double *__restrict__ g_dur1,
+               double *__restrict__ pos0_bar, double *__restrict__ pos1_bar, double *__restrict__ pos2_bar)
+{
+    const size_t s = (size_t)blockIdx.x * kVjpBlock + threadIdx.x;
+    if (s >= n) return;
+    double f[16];
+    load_fields(base, stride, s, f);
+    const size_t prob = prob_of ? (size_t)prob_of[s] : s;
+
+    Condensed c;
+    const bool ok = condense(f, limit, c);
+    condense_K(c);
+    ddv rhs[1][3] = {{dd_of(g_vel1 ? g_vel1[prob] : 0.0), dd_of(g_dur0 ? g_dur0[prob] : 0.0), dd_of(g_dur1 ? g_dur1[prob] : 0.0)}};
+    ddv w[1][3];
+    solve3_dd<1>(c.K, rhs, w);
+
+    double sj[4];      // s_j = D_j h_j . w: the pair's multiplier-weighted dual step, from the exact D_j h_j and the double-double w
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sj[j] = dd_add(dd_mul(c.Dgv[j], w[0][0]), dd_mul(c.Dgt[j], w[0][1 + (j >> 1)])).hi;
+    const Acc<double> &e = c.e;
+    const double q0 = e.r0 * e.r0, q1 = e.r1 * e.r1;
+    const double dx0_bar = -(12.0 * q0 * e.r0 * w[0][1].hi * (c.mu[1] - c.mu[0]) + 6.0 * q0 * (sj[0] - sj[1]));
+    const double dx1_bar = -(12.0 * q1 * e.r1 * w[0][2].hi * (c.mu[3] - c.mu[2]) + 6.0 * q1 * (sj[2] - sj[3]));
+    const double nan = __builtin_nan("");
+    pos0_bar[prob] = ok ? -dx0_bar : nan;
+    pos1_bar[prob] = ok ? dx0_bar - dx1_bar : nan;
+    pos2_bar[prob] = ok ? dx1_bar : nan;
+}
+
+// The condensed forward right-hand side -b_x - S_j D_j alpha_j h_j for position-delta tangents (dd0, dd1) = (dX0_dot, dX1_dot),
+// in double-double from the exact D_j h_j: alpha_j = +-6 dd / t^2 (the tangent of a_j), and b_x = S_j mu_j beta_j with
+// beta_j = -+12 dd / t^3 in the durations' rows.
+__device__ __forceinline__ void forward_rhs(const Condensed &c, double dd0, double dd1, ddv (&rhs)[3])
 {
     const Acc<double> &e = c.e;
     const double q0 = e.r0 * e.r0, q1 = e.r1 * e.r1;
-    const double al0 = 6.0 * q0 * dd0, al1 = 6.0 * q1 * dd1;
-    double pa[4];      // D_j alpha_j: the pair's two complementarity terms, summed before they meet h_j
-    pa[0] = c.D[0] * al0;
-    pa[1] = -(c.D[1] * al0);
-    pa[2] = c.D[2] * al1;
-    pa[3] = -(c.D[3] * al1);
-    rhs[0] = -(pa[0] * c.gv[0] + pa[1] * c.gv[1] + pa[2] * c.gv[2] + pa[3] * c.gv[3]);
-    rhs[1] = -(12.0 * q0 * e.r0 * dd0 * (c.mu[1] - c.mu[0]) + pa[0] * e.gt[0] + pa[1] * e.gt[1]);
-    rhs[2] = -(12.0 * q1 * e.r1 * dd1 * (c.mu[3] - c.mu[2]) + pa[2] * e.gt[2] + pa[3] * e.gt[3]);
+    const double al[4] = {6.0 * q0 * dd0, -(6.0 * q0 * dd0), 6.0 * q1 * dd1, -(6.0 * q1 * dd1)};
+    rhs[0] = dd_neg(dd_add(dd_add(dd_mul_d(c.Dgv[0], al[0]), dd_mul_d(c.Dgv[1], al[1])),
+                           dd_add(dd_mul_d(c.Dgv[2], al[2]), dd_mul_d(c.Dgv[3], al[3]))));
+    rhs[1] = dd_neg(dd_add(dd_of(12.0 * q0 * e.r0 * dd0 * (c.mu[1] - c.mu[0])),
+                           dd_add(dd_mul_d(c.Dgt[0], al[0]), dd_mul_d(c.Dgt[1], al[1]))));
+    rhs[2] = dd_neg(dd_add(dd_of(12.0 * q1 * e.r1 * dd1 * (c.mu[3] - c.mu[2])),
+                           dd_add(dd_mul_d(c.Dgt[2], al[2]), dd_mul_d(c.Dgt[3], al[3]))));
 }
 
 __global__ void __launch_bounds__(kVjpBlock)
@@ -279,13 +286,14 @@ k_solution_jvp(const double *__restrict__ base, size_t stride, size_t n, const u
 
     Condensed c;
     const bool ok = condense(f, limit, c);
-    double rhs[3], xd[3];
-    forward_rhs(c, tp1 - tp0, tp2 - tp1, rhs);      // equal tangents: dX tangents of exactly 0
-    solve3_pivoted(c.K, rhs, xd);
+    condense_K(c);
+    ddv rhs[1][3], xd[1][3];
+    forward_rhs(c, tp1 - tp0, tp2 - tp1, rhs[0]);      // equal tangents: dX tangents of exactly 0
+    solve3_dd<1>(c.K, rhs, xd);
     const double nan = __builtin_nan("");
-    t_vel1[prob] = ok ? xd[0] : nan;
-    t_dur0[prob] = ok ? xd[1] : nan;
-    t_dur1[prob] = ok ? xd[2] : nan;
+    t_vel1[prob] = ok ? xd[0][0].hi : nan;
+    t_dur0[prob] = ok ? xd[0][1].hi : nan;
+    t_dur1[prob] = ok ? xd[0][2].hi : nan;
 }
 
 __global__ void __launch_bounds__(kVjpBlock)
@@ -300,23 +308,22 @@ k_solution_jacobian(const double *__restrict__ base, size_t stride, size_t n, co
 
     Condensed c;
     const bool ok = condense(f, limit, c);
-    double rhs[2][3], d[2][3];      // d[0] = dx / d dX0, d[1] = dx / d dX1
+    condense_K(c);
+    ddv rhs[2][3], d[2][3];      // d[0] = dx / d dX0, d[1] = dx / d dX1
     forward_rhs(c, 1.0, 0.0, rhs[0]);
     forward_rhs(c, 0.0, 1.0, rhs[1]);
-    solve3_pivoted2(c.K, rhs, d);
+    solve3_dd<2>(c.K, rhs, d);
     const double nan = __builtin_nan("");
     double *out = jac + prob * 9;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {      // row a = x_a; columns pos0, pos1, pos2 through dX0 = pos1 - pos0, dX1 = pos2 - pos1
-        out[3 * a + 0] = ok ? -d[0][a] : nan;
-        out[3 * a + 1] = ok ? d[0][a] - d[1][a] : nan;
-        out[3 * a + 2] = ok ? d[1][a] : nan;
+        out[3 * a + 0] = ok ? -d[0][a].hi : nan;
+        out[3 * a + 1] = ok ? d[0][a].hi - d[1][a].hi : nan;
+        out[3 * a + 2] = ok ? d[1][a].hi : nan;
     }
 }
 
-// X = A^-1 B for an N x N system and R right-hand sides: solve3_pivoted's elimination at any size (the second-order kernel's
-// 7 x 7 and 3 x 3 solves).  Each row below k is compared with row k in turn and swapped in when larger, so row k ends with the
-// column's largest magnitude; the swaps are selects on registers.
+// X = A^-1 B for an N x N system and R right-hand sides in float64: solve3_dd's elimination (the second-order kernel's 7 x 7).
 template <int N, int R>
 __device__ __forceinline__ void solve_pivoted(double (&A)[N][N], double (&B)[R][N], double (&X)[R][N])
 {
@@ -361,16 +368,16 @@ __device__ __forceinline__ void solve_pivoted(double (&A)[N][N], double (&B)[R][
 
 // Second derivatives (rp_batch_solution_hessian).  For position-delta tangents u, w (the unit dX0 and dX1
 // directions): M z_uw = -R_uw, R_uw the second total derivative of r along (z_u, u), (z_w, w) without the z_uw terms.  With the
-// multipliers eliminated as in the VJP, on the same K:
+// multipliers eliminated as in the VJP, on the same (double-double) K:
 //     K x_uw = -T_uw - S_j h_j (D_j Q_j,uw + 2 (E_j / D_j^2) mu_j,u mu_j,w)
 //     T_uw = S_j [mu_j,u h_j,w + mu_j,w h_j,u + mu_j a3_j(u, w)],    E_j = lam_p / c_p^2 - lam_m / c_m^2
 // where a_j is differentiated in (v, t, dX) of its segment: Q_j,uw = y_u^T (grad^2 a_j) y_w with y_u = (v_u, t_u, dX_u), h_j,w the
 // derivative of h_j along y_w, a3_j(u, w) = grad_x (grad^2 a_j)[y_u, y_w] (the non-zero third derivatives: a_ttt, a_vtt, a_Xtt).
 // The pair's first-order dual step mu_j,u = D_j A_j,u is O(1), but A_j,u (the total derivative of a_j) cancels to O(p) on an
-// active pair: formed from the condensed x_u, eps-level errors come back multiplied by D_j.  So the first-order steps are the
+// active pair: formed from a float64 condensed x_u, eps-level errors come back multiplied by D_j.  So the first-order steps are the
 // unknowns of the 7 x 7 symmetric system [[W, H^T], [H, -diag(1 / D)]] [x_u; mu_u] = [-b_x; -alpha_u] (row j: h_j . x_u -
 // mu_j,u / D_j = -alpha_j,u, well scaled whether the pair is active or not), and E_j / D_j^2 -> 1 / lam on an active pair: no large
-// factor is formed outside K.  a_j = 6 sg_j dX r^2 + w_j r (r = 1 / t, w_j the velocity combination, dw_j / dv = cv_j).
+// factor is formed outside K.  The second-order right-hand sides (D_j Q_j,uw exact) go to the double-double K of the VJP.  a_j = 6 sg_j dX r^2 + w_j r (r = 1 / t, w_j the velocity combination, dw_j / dv = cv_j).
 __global__ void __launch_bounds__(kVjpBlock)
 k_solution_hessian(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
                    double *__restrict__ jac, double *__restrict__ hess)
@@ -393,7 +400,10 @@ k_solution_hessian(const double *__restrict__ base, size_t stride, size_t n, con
 #pragma unroll
     for (int j = 0; j < 4; ++j) {      // E_j / D_j^2 with the constraint values floored as D_j's are
         const double cm = max_(-c_value<double, 3>(2 * j, e, limit), c_floor), cp = max_(-c_value<double, 3>(2 * j + 1, e, limit), c_floor);
-        ed2[j] = (f[4 + 2 * j] / (cp * cp) - f[3 + 2 * j] / (cm * cm)) / (c.D[j] * c.D[j]);
+        const double d2 = c.D[j] * c.D[j];
+        // A pair whose multipliers are 0, or so small that D_j^2 is 0 or below the normal range, has E_j / D_j^2 ~ 1 / lam while
+        // mu_j,u mu_j,w ~ lam^2: the term is ~lam, 0 to working precision, where the quotient would be 0 / 0 or x / 0.
+        ed2[j] = d2 >= 2.2250738585072014e-308 ? (f[4 + 2 * j] / (cp * cp) - f[3 + 2 * j] / (cm * cm)) / d2 : 0.0;
     }
 
     // first order: [[W, H^T], [H, -diag(1 / D)]] [x_u; mu_u] = [-b_x; -alpha_u] for u = dX0, dX1
@@ -402,19 +412,10 @@ k_solution_hessian(const double *__restrict__ base, size_t stride, size_t n, con
     for (int i = 0; i < 7; ++i)
 #pragma unroll
         for (int k = 0; k < 7; ++k) A[i][k] = 0.0;
-    {
-        Prob<double> k;
-        k.v0 = v0;
-        k.v2 = v2;
-        k.dx0 = dx[0];
-        k.dx1 = dx[1];
-        double htt[4], htv[4];
-        accel_hess(k, v, e, htt, htv);
-        A[0][1] = A[1][0] = c.mu[0] * htv[0] + c.mu[1] * htv[1];      // W: K's second-derivative part
-        A[0][2] = A[2][0] = c.mu[2] * htv[2] + c.mu[3] * htv[3];
-        A[1][1] = c.mu[0] * htt[0] + c.mu[1] * htt[1];
-        A[2][2] = c.mu[2] * htt[2] + c.mu[3] * htt[3];
-    }
+    A[0][1] = A[1][0] = c.W01;      // W: K's second-derivative part
+    A[0][2] = A[2][0] = c.W02;
+    A[1][1] = c.W11;
+    A[2][2] = c.W22;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int seg = 1 + (j >> 1);
@@ -433,6 +434,7 @@ k_solution_hessian(const double *__restrict__ base, size_t stride, size_t n, con
 #pragma unroll
     for (int j = 0; j < 4; ++j) B[j >> 1][3 + j] = -(6.0 * sg[j] * (j < 2 ? q0 : q1));
     solve_pivoted<7, 2>(A, B, Z);      // Z[u] = (x_u, mu_u)
+    condense_K(c);
 
     // second order: three right-hand sides (u, w) = (0, 0), (0, 1), (1, 1) on K, from a_j's derivatives in (v, t, dX)
     double att[4], avt[4], axt[4], attt[4], avtt[4], axtt[4];
@@ -447,11 +449,11 @@ k_solution_hessian(const double *__restrict__ base, size_t stride, size_t n, con
         avtt[j] = 2.0 * cv[j] * r3;
         axtt[j] = 36.0 * sg[j] * r4;
     }
-    double S[3][3], xw[3][3];
+    double xw[3][3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int u = k == 2 ? 1 : 0, w = k == 0 ? 0 : 1;
-        S[k][0] = S[k][1] = S[k][2] = 0.0;
+    for (int k = 0; k < 3; ++k) {      // one right-hand side at a time, each on a copy of K: the same pivots and arithmetic as one
+        const int u = k == 2 ? 1 : 0, w = k == 0 ? 0 : 1;      // elimination on all three, in fewer registers
+        ddv S[1][3] = {{dd_of(0.0), dd_of(0.0), dd_of(0.0)}}, X[1][3];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int seg = j >> 1;
@@ -464,12 +466,19 @@ k_solution_hessian(const double *__restrict__ base, size_t stride, size_t n, con
             const double a3t = c.mu[j] * (attt[j] * tt + avtt[j] * vt + axtt[j] * Xt);
             const double hv_u = avt[j] * tu, hv_w = avt[j] * tw;
             const double ht_u = att[j] * tu + avt[j] * vu + axt[j] * Xu, ht_w = att[j] * tw + avt[j] * vw + axt[j] * Xw;
-            const double sj = c.D[j] * Q + 2.0 * ed2[j] * mu_u * mu_w;
-            S[k][0] -= mu_u * hv_w + mu_w * hv_u + a3v + sj * c.gv[j];
-            S[k][1 + seg] -= mu_u * ht_w + mu_w * ht_u + a3t + sj * e.gt[j];
+            const ddv sj = dd_add(two_prod(c.D[j], Q), dd_of(2.0 * ed2[j] * mu_u * mu_w));      // D_j Q_j exactly: the large term
+            S[0][0] = dd_sub(S[0][0], dd_add(dd_of(mu_u * hv_w + mu_w * hv_u + a3v), dd_mul_d(sj, c.gv[j])));
+            S[0][1 + seg] = dd_sub(S[0][1 + seg], dd_add(dd_of(mu_u * ht_w + mu_w * ht_u + a3t), dd_mul_d(sj, e.gt[j])));
         }
+        ddv K[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) K[a][b] = c.K[a][b];
+        solve3_dd<1>(K, S, X);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) xw[k][a] = X[0][a].hi;
     }
-    solve_pivoted<3, 3>(c.K, S, xw);
 
     const double nan = __builtin_nan("");
     if (jac) {

@@ -10,8 +10,8 @@ follows through P = d dX / d pos = [[-1, 1, 0], [0, -1, 1]].
 full_hessian solves both systems on the full 11 x 11 matrix in np.longdouble, with R_uw written from the residual's definition
 (every multiplier's own first-order step, no condensation) and the accelerations' derivative tables below.  condensed_hessian
 restates the kernel's arithmetic in float64: the first-order steps from the 7 x 7 active-set-aware system (each pair's dual step
-an unknown of the row h_j . x - mu_j / D_j = -alpha_j), the three second-order right-hand sides on the VJP's condensed 3 x 3 K,
-both eliminations with the kernel's pivot order.  naive_hessian is the rejected form: the first-order steps from K, and
+an unknown of the row h_j . x - mu_j / D_j = -alpha_j), the three second-order right-hand sides on the VJP's condensed 3 x 3 K in
+double-double, both eliminations with the kernel's pivot order.  naive_hessian is the rejected form: the first-order steps from K, and
 mu_j,u = D_j A_j,u formed from them.
 """
 import numpy as np
@@ -185,7 +185,7 @@ def gepp(A, B):
 
 def _pair_terms(states, limit):
     """The condensed system (sensitivity_jvp_ref.condensed) and float64 derivative tables, E_j / D_j^2 included."""
-    c = jr.condensed(states, limit)
+    c = jr.condensed_dd(states, limit)
     T = accel_tables(states, np.float64)
     s = np.asarray(states, dtype=np.float64)
     lam = s[:, 3:11]
@@ -194,7 +194,9 @@ def _pair_terms(states, limit):
         cm = np.maximum(-(-T["a"] - limit), floor)      # |c| of each pair's two constraints, floored as D is
         cp = np.maximum(-(T["a"] - limit), floor)
         E = lam[:, 1::2] / (cp * cp) - lam[:, 0::2] / (cm * cm)
-        c["ED2"] = E / (c["D"] * c["D"])
+        d2 = c["D"] * c["D"]
+        # 0 where D_j^2 is 0 or below the normal range (multipliers of 0 or ~1e-160): the term is ~lam there
+        c["ED2"] = np.where(d2 >= np.finfo(np.float64).tiny, E / d2, 0.0)
     c["T"] = T
     return c
 
@@ -226,26 +228,30 @@ def aware_first_order(c):
 
 
 def second_order_condensed(c, xu, muu):
-    """x_uw (n, 3, 3) float64 for (u, w) = (0, 0), (0, 1), (1, 1): K x_uw = -T_uw - S_j h_j (D_j Q_j + 2 (E_j / D_j^2) mu_u mu_w)."""
-    n = len(c["ok"])
+    """x_uw (n, 3, 3) float64 for (u, w) = (0, 0), (0, 1), (1, 1): K x_uw = -T_uw - S_j h_j (D_j Q_j + 2 (E_j / D_j^2) mu_u mu_w),
+    K and the right-hand sides in double-double (D_j Q_j exactly), as k_solution_hessian forms them."""
     T, D, mu, gv, gt, ED2 = c["T"], c["D"], c["mu"], c["gv"], c["gt"], c["ED2"]
-    B = np.zeros((n, 3, 3))
+    B = []
     with np.errstate(all="ignore"):
         for k, (u, w) in enumerate(((0, 0), (0, 1), (1, 1))):
+            S = [jr.dd(np.zeros(len(D))) for _ in range(3)]
             for j in range(4):
                 seg = j >> 1
                 vu, tu, Xu = xu[:, u, 0], xu[:, u, 1 + seg], float(seg == u)
                 vw, tw, Xw = xu[:, w, 0], xu[:, w, 1 + seg], float(seg == w)
-                Q = T["tt"][:, j] * tu * tw + T["vt"][:, j] * (vu * tw + vw * tu) + T["Xt"][:, j] * (Xu * tw + Xw * tu)
-                Tv = mu[:, j] * T["vtt"][:, j] * tu * tw
-                Tt = mu[:, j] * (T["ttt"][:, j] * tu * tw + T["vtt"][:, j] * (vu * tw + vw * tu) + T["Xtt"][:, j] * (Xu * tw + Xw * tu))
+                tt, vt, Xt = tu * tw, vu * tw + vw * tu, Xu * tw + Xw * tu
+                Q = T["tt"][:, j] * tt + T["vt"][:, j] * vt + T["Xt"][:, j] * Xt
+                Tv = mu[:, j] * (T["vtt"][:, j] * tt)
+                Tt = mu[:, j] * (T["ttt"][:, j] * tt + T["vtt"][:, j] * vt + T["Xtt"][:, j] * Xt)
                 hv_u, hv_w = T["vt"][:, j] * tu, T["vt"][:, j] * tw
                 ht_u = T["tt"][:, j] * tu + T["vt"][:, j] * vu + T["Xt"][:, j] * Xu
                 ht_w = T["tt"][:, j] * tw + T["vt"][:, j] * vw + T["Xt"][:, j] * Xw
-                s = D[:, j] * Q + 2 * ED2[:, j] * muu[:, u, j] * muu[:, w, j]
-                B[:, 0, k] -= muu[:, u, j] * hv_w + muu[:, w, j] * hv_u + Tv + s * gv[:, j]
-                B[:, 1 + seg, k] -= muu[:, u, j] * ht_w + muu[:, w, j] * ht_u + Tt + s * gt[:, j]
-    return np.transpose(gepp(c["K"], B), (0, 2, 1))
+                s = jr.dd_add(jr.dd_prod(D[:, j], Q), jr.dd(2 * ED2[:, j] * muu[:, u, j] * muu[:, w, j]))
+                S[0] = jr.dd_sub(S[0], jr.dd_add(jr.dd(muu[:, u, j] * hv_w + muu[:, w, j] * hv_u + Tv), jr.dd_mul_d(s, gv[:, j])))
+                S[1 + seg] = jr.dd_sub(S[1 + seg], jr.dd_add(jr.dd(muu[:, u, j] * ht_w + muu[:, w, j] * ht_u + Tt),
+                                                            jr.dd_mul_d(s, gt[:, j])))
+            B.append(S)
+    return jr._hi(jr.gepp_dd(c["Kdd"], B))
 
 
 def _assemble(c, xu, xuw):
