@@ -51,7 +51,9 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      solve in rounds); a raw pointer to a mutable field keeps the seeding pass on for every later gated launch
  *   7  rp_batch_solution_vjp (gradients of the solution with respect to the positions); rp_batch_solution_jvp and
  *      rp_batch_solution_jacobian (the forward-mode derivative and the per-problem 3 x 3 Jacobian; new entries only);
- *      rp_batch_solution_hessian (the per-problem second derivatives; new entries only) */
+ *      rp_batch_solution_hessian (the per-problem second derivatives; new entries only); rp_batch_set_problems_vel(_device),
+ *      rp_batch_solution_vjp_vel, rp_batch_solution_jvp_vel and rp_batch_solution_jacobian_vel (problems with end velocities and the
+ *      first derivatives in them; new entries only) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -175,8 +177,28 @@ RP_API int rp_batch_set_problems(rp_batch *b, const double *pos0, const double *
  * is the one of rp_params.accel_limit AS IT WAS when the problems were set (rp_batch_set_params writes the start out before
  * it changes the limit); raw pointers from rp_batch_field_ptr are undefined until the next state-touching call. */
 RP_API int rp_batch_set_problems_device(rp_batch *b, const double *d_pos0, const double *d_pos1, const double *d_pos2);
+/* Problems with non-zero end velocities (vel0X, vel2X of enum V): positions and velocities in PROBLEM order, device memory, n doubles
+ * each; a NULL velocity array counts as zeros.  Every variant and dtype.  The scheduling pass of rp_batch_set_problems_device runs on
+ * the positions, then one kernel writes the start -- not deferred -- with the velocities gathered into their fields (stored in the
+ * batch's type, the start computed from the stored values):
+ *     vel1 = 0, multipliers 1,  t_0 = (3.5/sqrt 12) sqrt(6 |dX_0| / L) + 8 |vel0| / L,  t_1 = (3.5/sqrt 12) sqrt(6 |dX_1| / L) + 8 |vel2| / L
+ * -- rp_batch_set_problems_device's start bit for bit where the velocities are 0, and strictly feasible for any velocities (every
+ * |a| <= 0.98 L).  The Newton kernels then run their general form (bit-identical to the zero-velocity form where the
+ * velocities are 0), and the fused gated solve its watched kernel (the scheduled order was fitted to rest-to-rest starts): for zero or
+ * NULL velocities iteration counts, status words and state are those of rp_batch_set_problems_device.  rp_batch_restart returns to this
+ * start with the velocities the batch holds; a later rp_batch_set_problems(_device) zeroes them again.
+ * The reference's F3 has no t > 0 constraint, and its backtracking can step over the t = 0 wall when the velocities are large: with
+ * velocities kappa U(-1, 1) sqrt(L |dX|), 100 % of problems converge at kappa = 0.1, 99 % at 0.3, 81 % at 0.5 and 50 % at 1; the others
+ * drift to negative or huge durations, and the status bits report them as for any problem (RP_ST_MAXITER, RP_ST_NONFINITE ...).  This
+ * is the reference model's behaviour, reproduced.  Asynchronous, with rp_batch_set_problems_device's rules for the input arrays. */
+RP_API int rp_batch_set_problems_vel_device(rp_batch *b, const double *d_pos0, const double *d_pos1, const double *d_pos2,
+                                            const double *d_vel0, const double *d_vel2);
+/* The same from host arrays.  Synchronous. */
+RP_API int rp_batch_set_problems_vel(rp_batch *b, const double *pos0, const double *pos1, const double *pos2, const double *vel0,
+                                     const double *vel2);
 /* Back to the feasible start of the positions the batch already holds (the `I` key for per-problem positions): nothing
- * crosses the boundary.  Asynchronous. */
+ * crosses the boundary.  Asynchronous.  A batch whose problems were set by rp_batch_set_problems_vel(_device) returns to that start,
+ * with the end velocities it holds; every other batch to rest-to-rest (velocities zeroed). */
 RP_API int rp_batch_restart(rp_batch *b);
 /* Whole state in the reference's AoS layout, n * 16 (F3) or n * 12 (F4) doubles.  Synchronous. */
 RP_API int rp_batch_set_state(rp_batch *b, const double *aos);
@@ -266,6 +288,20 @@ RP_API int rp_batch_solution_jacobian(rp_batch *b, double *d_jac);
  * Asynchronous on the batch stream.  F3, RP_DTYPE_F64 only (RP_ERR_UNSUPPORTED otherwise); a problem whose state is not finite or
  * outside the feasible set gets NaN in all 27 (and 9) entries; works on the states rp_batch_solution_vjp does. */
 RP_API int rp_batch_solution_hessian(rp_batch *b, double *d_jac, double *d_hess);
+/* The first derivatives in all five boundary inputs theta = (pos0, pos1, pos2, vel0, vel2) at the batch's current state (DESIGN.md
+ * section 12): the z, x, r, p and M of rp_batch_solution_vjp, the same double-double condensed K, c_i floor and NULL handling, with
+ * dr/dtheta widened by the two end velocities (each enters only its own segment's accelerations).  NaN as for rp_batch_solution_vjp,
+ * and also for a state with a duration <= 0.  They work on any state, rest-to-rest batches included (d / d vel at vel = 0).  The
+ * position outputs are those of rp_batch_solution_vjp / _jvp / _jacobian (the same device code).  All arrays device memory, PROBLEM
+ * order; asynchronous on the batch stream; F3, RP_DTYPE_F64 only (RP_ERR_UNSUPPORTED otherwise).
+ *   vjp_vel       theta_bar = J^T g for upstream gradients g on x (NULL: zeros), five arrays of n doubles
+ *   jvp_vel       x_dot = J theta_dot for the five tangents (NULL: zeros), three arrays of n doubles
+ *   jacobian_vel  J[a][b] = dx_a / dtheta_b at d_jac[15 i + 5 a + b], b over (pos0, pos1, pos2, vel0, vel2): n x 15 doubles */
+RP_API int rp_batch_solution_vjp_vel(rp_batch *b, const double *d_g_vel1, const double *d_g_dur0, const double *d_g_dur1,
+                                     double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar, double *d_vel0_bar, double *d_vel2_bar);
+RP_API int rp_batch_solution_jvp_vel(rp_batch *b, const double *d_t_pos0, const double *d_t_pos1, const double *d_t_pos2,
+                                     const double *d_t_vel0, const double *d_t_vel2, double *d_t_vel1, double *d_t_dur0, double *d_t_dur1);
+RP_API int rp_batch_solution_jacobian_vel(rp_batch *b, double *d_jac);
 RP_API int rp_batch_reduce(rp_batch *b, rp_reduction *out);                   /* synchronous */
 /* Writes the 4 doubles of rp_reduction to device memory the caller owns, asynchronously on
  * the batch stream: the buffer a multi-GPU caller hands to its RCCL all-reduce. */

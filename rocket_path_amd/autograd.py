@@ -4,6 +4,7 @@
     (duration0 + duration1).sum().backward()      # -> pos0.grad, pos1.grad, pos2.grad
     vel1, duration0, duration1, iters, status, jac = min_time_jacobian(pos0, pos1, pos2)      # jac: (n, 3, 3)
     vel1, duration0, duration1, iters, status, jac, hess = min_time_hessian(pos0, pos1, pos2)      # hess: (n, 3, 3, 3)
+    vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2, vel0=vel0, vel2=vel2)      # end velocities
 
 The forward is Batch.set_problems_device + the fused gated solve + Batch.solution_device into a torch buffer, enqueued without
 synchronising the host.  The backward is one rp_batch_solution_vjp launch at the state the forward left, the forward-mode rule
@@ -11,6 +12,10 @@ synchronising the host.  The backward is one rp_batch_solution_vjp launch at the
 implicit-function derivative of the central-path point the solve stopped at.  The backward is itself differentiable once more
 (double backward: torch.autograd.grad(..., create_graph=True), torch.autograd.functional.hessian), through one
 rp_batch_solution_jvp and one rp_batch_solution_hessian launch.  F3, float64 only; no vmap rule.
+
+With end velocities (vel0= / vel2=) the forward is Batch.set_problems_vel_device instead, and the derivatives
+in all five inputs come from rp_batch_solution_vjp_vel / rp_batch_solution_jvp_vel (first order only: a double backward raises
+torch's once_differentiable error).  Without them the code path is the rest-to-rest one above, unchanged.
 """
 import ctypes
 import threading
@@ -89,6 +94,24 @@ def _check_positions(pos0, pos1, pos2, who="min_time_solve"):
         raise ValueError(who + ": empty batch")
 
 
+def _check_velocities(pos0, vel0, vel2, who):
+    """Whether end velocities were given; each given one must be a 1-D float64 tensor on the positions' ROCm device, of their length."""
+    if vel0 is None and vel2 is None:
+        return False
+    for name, t in (("vel0", vel0), ("vel2", vel2)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(who + ": %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if t.device.type != "cuda" or t.device != pos0.device:
+            raise TypeError(who + ": %s is on %s; it must be on the positions' ROCm device %s" % (name, t.device, pos0.device))
+        if t.dtype != torch.float64:
+            raise TypeError(who + ": %s has dtype %s; float64 is required" % (name, t.dtype))
+        if t.shape != pos0.shape:
+            raise ValueError(who + ": %s has shape %s, the positions %s" % (name, tuple(t.shape), tuple(pos0.shape)))
+    return True
+
+
 def _check_params(params, who):
     if params is not None:
         unknown = set(params) - _PARAM_FIELDS
@@ -110,10 +133,11 @@ def _run_on(batch_stream, cur):
     return _Order()
 
 
-def _solve(pos0, pos1, pos2, gap_tol, max_iter, params, jacobian=False, hessian=False):
+def _solve(pos0, pos1, pos2, gap_tol, max_iter, params, jacobian=False, hessian=False, vel=None):
     """Enqueue the solve on the current stream with a batch taken from the pool: (key, batch, (vel1, dur0, dur1, iters, status)),
     and the (n, 3, 3) Jacobian at the end when `jacobian`, the Jacobian and the (n, 3, 3, 3) Hessian (one launch) when `hessian`.
-    The caller gives the batch back or leases it."""
+    vel = (vel0, vel2) (either may be None: zeros) poses the problems with end velocities: the Jacobian is then the (n, 3, 5) one in
+    (pos0, pos1, pos2, vel0, vel2), the Hessian still the positions' (its own launch).  The caller gives the batch back or leases it."""
     device = pos0.device.index if pos0.device.index is not None else torch.cuda.current_device()
     n = pos0.shape[0]
     cur = torch.cuda.current_stream(device)
@@ -123,8 +147,9 @@ def _solve(pos0, pos1, pos2, gap_tol, max_iter, params, jacobian=False, hessian=
     # the null stream cannot be handed to a batch (NULL = "create your own"): then the batch's own stream is ordered by events
     ext = None if handle else torch.cuda.ExternalStream(batch.stream(), device=pos0.device)
     p0, p1, p2 = (t.contiguous() for t in (pos0, pos1, pos2))
+    v0, v2 = (t.contiguous() if t is not None else None for t in (vel if vel is not None else (None, None)))
     out = torch.empty((n, 4), dtype=torch.float64, device=pos0.device)      # n rp_solution records (torch's blocks: 512-byte aligned)
-    jac = torch.empty((n, 3, 3), dtype=torch.float64, device=pos0.device) if jacobian or hessian else None
+    jac = torch.empty((n, 3, 5 if vel is not None else 3), dtype=torch.float64, device=pos0.device) if jacobian or hessian else None
     hess = torch.empty((n, 3, 3, 3), dtype=torch.float64, device=pos0.device) if hessian else None
     try:
         p = capi.Params()
@@ -133,15 +158,23 @@ def _solve(pos0, pos1, pos2, gap_tol, max_iter, params, jacobian=False, hessian=
             setattr(p, k, v)
         capi.check(batch._lib.rp_batch_set_params(batch._h, ctypes.byref(p)))
         with _run_on(ext, cur):
-            batch.set_problems_device(p0.data_ptr(), p1.data_ptr(), p2.data_ptr())
+            if vel is None:
+                batch.set_problems_device(p0.data_ptr(), p1.data_ptr(), p2.data_ptr())
+            else:
+                batch.set_problems_vel_device(p0.data_ptr(), p1.data_ptr(), p2.data_ptr(), *[t.data_ptr() if t is not None else 0 for t in (v0, v2)])
             batch.solve(gap_tol, max_iter, 0)
             batch.solution_device(out.data_ptr())
-            if hess is not None:
+            if vel is not None:
+                if hess is not None:
+                    batch.solution_hessian(0, hess.data_ptr())
+                if jac is not None:
+                    batch.solution_jacobian_vel(jac.data_ptr())
+            elif hess is not None:
                 batch.solution_hessian(jac.data_ptr(), hess.data_ptr())
             elif jac is not None:
                 batch.solution_jacobian(jac.data_ptr())
         if ext is not None:
-            for t in (p0, p1, p2, out, jac, hess):
+            for t in (p0, p1, p2, v0, v2, out, jac, hess):
                 if t is not None:
                     t.record_stream(ext)
     except Exception:
@@ -207,6 +240,63 @@ class _MinTimeSolve(torch.autograd.Function):
         same = bstream.cuda_stream == cur.cuda_stream
         with _run_on(None if same else bstream, cur):
             batch.solution_jvp(*[t.data_ptr() if t is not None else 0 for t in ts], *[d.data_ptr() for d in dots])
+        if not same:
+            for t in ts + dots:
+                if t is not None:
+                    t.record_stream(bstream)
+        return outs[0], outs[1], outs[2], None, None
+
+
+class _MinTimeSolveVel(torch.autograd.Function):
+    """min_time_solve with end velocities: differentiable in (pos0, pos1, pos2, vel0, vel2), first order, through
+    rp_batch_solution_vjp_vel (backward) and rp_batch_solution_jvp_vel (forward mode) at the state the solve left."""
+
+    @staticmethod
+    def forward(pos0, pos1, pos2, vel0, vel2, gap_tol, max_iter, params, holder):
+        key, batch, outs = _solve(pos0, pos1, pos2, gap_tol, max_iter, params, vel=(vel0, vel2))
+        holder.lease = _Lease(key, batch)
+        return outs
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.lease = inputs[-1].lease      # _MinTimeSolve's rule: the batch stays out of the pool while the graph holds ctx
+        ctx.device = inputs[0].device
+        ctx.has_vel = (inputs[3] is not None, inputs[4] is not None)
+        ctx.mark_non_differentiable(output[3], output[4])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_vel1, g_dur0, g_dur1, _g_iters, _g_status):
+        batch = ctx.lease.batch
+        device = ctx.device
+        cur = torch.cuda.current_stream(device)
+        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
+        gs = [g.contiguous() if g is not None else None for g in (g_vel1, g_dur0, g_dur1)]
+        n = batch.n
+        bars = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(5)]
+        same = bstream.cuda_stream == cur.cuda_stream
+        with _run_on(None if same else bstream, cur):
+            batch.solution_vjp_vel(*[g.data_ptr() if g is not None else 0 for g in gs], *[b.data_ptr() for b in bars])
+        if not same:
+            for t in gs + bars:
+                if t is not None:
+                    t.record_stream(bstream)
+        vel_bars = tuple(b if has else None for b, has in zip(bars[3:], ctx.has_vel))
+        return (bars[0], bars[1], bars[2]) + vel_bars + (None, None, None, None)
+
+    @staticmethod
+    def jvp(ctx, t_pos0, t_pos1, t_pos2, t_vel0, t_vel2, _t_gap, _t_iter, _t_params, _t_holder):
+        batch = ctx.lease.batch
+        device = ctx.device
+        cur = torch.cuda.current_stream(device)
+        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
+        ts = [_plain(t.contiguous()) if t is not None else None for t in (t_pos0, t_pos1, t_pos2, t_vel0, t_vel2)]
+        n = batch.n
+        outs = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(3)]
+        dots = [_plain(t) for t in outs]
+        same = bstream.cuda_stream == cur.cuda_stream
+        with _run_on(None if same else bstream, cur):
+            batch.solution_jvp_vel(*[t.data_ptr() if t is not None else 0 for t in ts], *[d.data_ptr() for d in dots])
         if not same:
             for t in ts + dots:
                 if t is not None:
@@ -280,42 +370,57 @@ class _SolutionVJP(torch.autograd.Function):
         return g_bar + pos_bar + (None, None)
 
 
-def min_time_solve(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None):
+def min_time_solve(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None, vel0=None, vel2=None):
     """Solve the F3 problems (pos0[i], pos1[i], pos2[i]) -- 1-D float64 tensors on one ROCm device -- on the current stream.
 
     Returns (vel1, duration0, duration1, iters, status): float64 tensors, differentiable with respect to the positions in reverse
     mode (backward, twice: create_graph=True gives a differentiable gradient) and forward mode (torch.autograd.forward_ad,
     torch.func.jvp), and the int32 step counts and RP_ST_* status words (not differentiable).  `params`: rp_params fields to override (a dict).  Derivatives are the implicit-function derivative at the
     state the solve returns (include/rp_batch.h, rp_batch_solution_vjp / rp_batch_solution_jvp): NaN for problems whose state is not
-    finite or not strictly feasible.  Does not synchronise the host."""
+    finite or not strictly feasible.  Does not synchronise the host.
+
+    vel0, vel2: end velocities (1-D float64 tensors on the positions' device; one given, the other counts as zeros) -- the problems are
+    posed with rp_batch_set_problems_vel_device, and the outputs are differentiable in all five inputs, first order, in reverse and
+    forward mode (rp_batch_solution_vjp_vel / _jvp_vel; NaN also where a duration is not positive); a double backward raises.  Large
+    velocities can make the reference's model ill-posed: check `status`."""
     _check_positions(pos0, pos1, pos2)
     _check_params(params, "min_time_solve")
+    if _check_velocities(pos0, vel0, vel2, "min_time_solve"):
+        return _MinTimeSolveVel.apply(pos0, pos1, pos2, vel0, vel2, float(gap_tol), int(max_iter), params, _Holder())
     return _MinTimeSolve.apply(pos0, pos1, pos2, float(gap_tol), int(max_iter), params, _Holder())
 
 
-def min_time_jacobian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None):
+def min_time_jacobian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None, vel0=None, vel2=None):
     """min_time_solve's solve, and every problem's Jacobian at the state it returns, on the current stream.
 
     Returns (vel1, duration0, duration1, iters, status, jac) with jac (n, 3, 3) float64, jac[i, a, b] = d x_a / d pos_b of problem i
     for x = (vel1, duration0, duration1) (rp_batch_solution_jacobian; NaN rows as for min_time_solve's derivatives).  One solve and
-    one Jacobian launch; nothing returned is differentiable.  Does not synchronise the host."""
+    one Jacobian launch; nothing returned is differentiable.  Does not synchronise the host.  With end velocities (vel0= / vel2=, as
+    min_time_solve's) jac is (n, 3, 5), columns (pos0, pos1, pos2, vel0, vel2) (rp_batch_solution_jacobian_vel)."""
     _check_positions(pos0, pos1, pos2, "min_time_jacobian")
     _check_params(params, "min_time_jacobian")
-    key, batch, outs = _solve(pos0.detach(), pos1.detach(), pos2.detach(), float(gap_tol), int(max_iter), params, jacobian=True)
+    vel = (vel0, vel2) if _check_velocities(pos0, vel0, vel2, "min_time_jacobian") else None
+    if vel is not None:
+        vel = tuple(t.detach() if t is not None else None for t in vel)
+    key, batch, outs = _solve(pos0.detach(), pos1.detach(), pos2.detach(), float(gap_tol), int(max_iter), params, jacobian=True, vel=vel)
     _pool.give(key, batch)      # the read-backs are enqueued; the next user of this key works on the same stream
     return outs
 
 
-def min_time_hessian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None):
+def min_time_hessian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None, vel0=None, vel2=None):
     """min_time_solve's solve, and every problem's Jacobian and second derivatives at the state it returns, on the current stream.
 
     Returns (vel1, duration0, duration1, iters, status, jac, hess) with jac (n, 3, 3) as min_time_jacobian's and hess (n, 3, 3, 3)
     float64, hess[i, a, b, c] = d^2 x_a / dpos_b dpos_c of problem i (rp_batch_solution_hessian; symmetric in b, c; NaN for the
     problems min_time_solve's derivatives are NaN for).  One solve and one Hessian launch; nothing returned is differentiable.  Does
-    not synchronise the host."""
+    not synchronise the host.  With end velocities (vel0= / vel2=, as min_time_solve's) jac is min_time_jacobian's (n, 3, 5) and hess
+    the second derivatives in the positions only, at that state (one Hessian and one Jacobian launch)."""
     _check_positions(pos0, pos1, pos2, "min_time_hessian")
     _check_params(params, "min_time_hessian")
-    key, batch, outs = _solve(pos0.detach(), pos1.detach(), pos2.detach(), float(gap_tol), int(max_iter), params, hessian=True)
+    vel = (vel0, vel2) if _check_velocities(pos0, vel0, vel2, "min_time_hessian") else None
+    if vel is not None:
+        vel = tuple(t.detach() if t is not None else None for t in vel)
+    key, batch, outs = _solve(pos0.detach(), pos1.detach(), pos2.detach(), float(gap_tol), int(max_iter), params, hessian=True, vel=vel)
     _pool.give(key, batch)      # the read-backs are enqueued; the next user of this key works on the same stream
     return outs
 

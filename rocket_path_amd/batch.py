@@ -86,6 +86,22 @@ class Batch:
         """Device pointers (ints) to n float64 each, e.g. torch tensors' data_ptr()."""
         capi.check(self._lib.rp_batch_set_problems_device(self._h, *[ctypes.c_void_p(p) for p in (d_pos0, d_pos1, d_pos2)]))
 
+    def set_problems_vel(self, pos0, pos1, pos2, vel0=None, vel2=None):
+        """Problems with end velocities from host arrays (rp_batch_set_problems_vel): n float64 each, problem order; a velocity of
+        None counts as zeros.  The start grows each duration by 8 |vel_end| / L (include/rp_batch.h).  Synchronous."""
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (pos0, pos1, pos2)]
+        vels = [np.ascontiguousarray(v, dtype=np.float64) if v is not None else None for v in (vel0, vel2)]
+        for a in arrs + [v for v in vels if v is not None]:
+            if a.shape != (self.n,):
+                raise ValueError("need %d values per array, got shape %s" % (self.n, a.shape))
+        capi.check(self._lib.rp_batch_set_problems_vel(self._h, *[_ptr(a) for a in arrs], *[_ptr(v) if v is not None else None for v in vels]))
+
+    def set_problems_vel_device(self, d_pos0, d_pos1, d_pos2, d_vel0=None, d_vel2=None):
+        """The same from device pointers (ints) to n float64 each (rp_batch_set_problems_vel_device); a velocity pointer of None / 0
+        counts as zeros.  Asynchronous."""
+        capi.check(self._lib.rp_batch_set_problems_vel_device(self._h, *[ctypes.c_void_p(p) for p in (d_pos0, d_pos1, d_pos2)],
+                                                              *[ctypes.c_void_p(p) if p else None for p in (d_vel0, d_vel2)]))
+
     def restart(self):
         """Feasible start again from the positions already in the batch (no input crosses the boundary)."""
         capi.check(self._lib.rp_batch_restart(self._h))
@@ -160,6 +176,28 @@ class Batch:
         (rp_batch_solution_jacobian): device address of n x 9 doubles, problem order.  Asynchronous on the batch stream.  F3 with
         DTYPE_F64 only."""
         capi.check(self._lib.rp_batch_solution_jacobian(self._h, ctypes.c_void_p(d_jac) if d_jac else None))
+
+    def solution_vjp_vel(self, d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar, d_vel0_bar, d_vel2_bar):
+        """Gradients with respect to (pos0, pos1, pos2, vel0, vel2) of a loss whose gradients on (vel1, duration0, duration1) are the
+        three upstream arrays, at the current state (rp_batch_solution_vjp_vel): device addresses of n doubles each, problem order; an
+        upstream address of None / 0 counts as zeros.  Asynchronous on the batch stream.  F3 with DTYPE_F64 only."""
+        capi.check(self._lib.rp_batch_solution_vjp_vel(self._h, *[ctypes.c_void_p(p) if p else None for p in
+                                                                  (d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar,
+                                                                   d_vel0_bar, d_vel2_bar)]))
+
+    def solution_jvp_vel(self, d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel0, d_t_vel2, d_t_vel1, d_t_dur0, d_t_dur1):
+        """Tangents of (vel1, duration0, duration1) along the tangents of (pos0, pos1, pos2, vel0, vel2), at the current state
+        (rp_batch_solution_jvp_vel): device addresses of n doubles each, problem order; a tangent address of None / 0 counts as zeros.
+        Asynchronous on the batch stream.  F3 with DTYPE_F64 only."""
+        capi.check(self._lib.rp_batch_solution_jvp_vel(self._h, *[ctypes.c_void_p(p) if p else None for p in
+                                                                  (d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel0, d_t_vel2, d_t_vel1, d_t_dur0,
+                                                                   d_t_dur1)]))
+
+    def solution_jacobian_vel(self, d_jac):
+        """Every problem's 3 x 5 Jacobian d(vel1, duration0, duration1) / d(pos0, pos1, pos2, vel0, vel2), row-major, at the current
+        state (rp_batch_solution_jacobian_vel): device address of n x 15 doubles, problem order.  Asynchronous on the batch stream.  F3
+        with DTYPE_F64 only."""
+        capi.check(self._lib.rp_batch_solution_jacobian_vel(self._h, ctypes.c_void_p(d_jac) if d_jac else None))
 
     def solution_hessian(self, d_jac, d_hess):
         """Every problem's second derivatives H[a][b][c] = d^2 x_a / dpos_b dpos_c, x = (vel1, duration0, duration1), at the current

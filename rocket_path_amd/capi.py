@@ -70,6 +70,8 @@ SIGNATURES = {
     "rp_batch_init_stuck": (ctypes.c_int, [_vp]),
     "rp_batch_set_problems": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "rp_batch_set_problems_device": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "rp_batch_set_problems_vel": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "rp_batch_set_problems_vel_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_batch_restart": (ctypes.c_int, [_vp]),
     "rp_batch_set_state": (ctypes.c_int, [_vp, _vp]),
     "rp_batch_get_state": (ctypes.c_int, [_vp, _vp]),
@@ -87,6 +89,9 @@ SIGNATURES = {
     "rp_batch_solution_jvp": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_batch_solution_jacobian": (ctypes.c_int, [_vp, _vp]),
     "rp_batch_solution_hessian": (ctypes.c_int, [_vp, _vp, _vp]),
+    "rp_batch_solution_vjp_vel": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rp_batch_solution_jvp_vel": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rp_batch_solution_jacobian_vel": (ctypes.c_int, [_vp, _vp]),
     "rp_batch_traffic_probe": (ctypes.c_int, [_vp]),
     "rp_batch_reduce": (ctypes.c_int, [_vp, ctypes.POINTER(Reduction)]),
     "rp_batch_reduce_device": (ctypes.c_int, [_vp, _vp]),

@@ -93,6 +93,16 @@ hipError_t launch_solution_jacobian(const BatchView &b, const HostParams &hp, do
 // d^2(vel1, duration0, duration1) / d(pos0, pos1, pos2)^2 (27 doubles per problem) and, unless d_jac is null, the Jacobian from the
 // same first-order solves, problem order, at the batch's current state (sensitivity.hip; F3, double storage only)
 hipError_t launch_solution_hessian(const BatchView &b, const HostParams &hp, double *d_jac, double *d_hess, hipStream_t stream);
+// the first derivatives in all five boundary inputs (pos0, pos1, pos2, vel0, vel2): VJP, JVP (null tangents / gradients: zeros) and
+// the 3 x 5 Jacobian (15 doubles per problem, row-major), problem order, at the batch's current state (sensitivity_vel.hip; F3,
+// double storage only)
+hipError_t launch_solution_vjp_vel(const BatchView &b, const HostParams &hp, const double *d_g_vel1, const double *d_g_dur0,
+                                   const double *d_g_dur1, double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar,
+                                   double *d_vel0_bar, double *d_vel2_bar, hipStream_t stream);
+hipError_t launch_solution_jvp_vel(const BatchView &b, const HostParams &hp, const double *d_t_pos0, const double *d_t_pos1,
+                                   const double *d_t_pos2, const double *d_t_vel0, const double *d_t_vel2, double *d_t_vel1,
+                                   double *d_t_dur0, double *d_t_dur1, hipStream_t stream);
+hipError_t launch_solution_jacobian_vel(const BatchView &b, const HostParams &hp, double *d_jac, hipStream_t stream);
 
 // state movement / initialisation
 hipError_t launch_aos_to_soa(const BatchView &b, const double *d_aos, hipStream_t stream);
@@ -101,6 +111,11 @@ hipError_t launch_restart_feasible(const BatchView &b, const HostParams &hp, hip
 // the same from b.records through b.prob_of (a batch that has just been scheduled): positions into the constant fields, the
 // feasible start, cleared progress words -- everything k_solve_chunks<START> forms in registers, written out
 hipError_t launch_start_from_records(const BatchView &b, const HostParams &hp, hipStream_t stream);
+// the start with end velocities (rp_batch_set_problems_vel_device): launch_start_from_records, and the end velocities gathered
+// from d_vel0 / d_vel2 (problem order; null: zeros) through b.prob_of into their fields; t_i grows by 8 |vel_end| / L
+hipError_t launch_start_vel_from_records(const BatchView &b, const HostParams &hp, const double *d_vel0, const double *d_vel2, hipStream_t stream);
+// the same start from the positions AND end velocities in the batch's constant fields (rp_batch_restart of such a batch)
+hipError_t launch_restart_vel(const BatchView &b, const HostParams &hp, hipStream_t stream);
 hipError_t launch_init_const(const BatchView &b, const double *host_state /* state_len values */, hipStream_t stream);
 hipError_t launch_nudge(const BatchView &b, int field, double delta, hipStream_t stream);
 hipError_t launch_clear_progress(const BatchView &b, hipStream_t stream);

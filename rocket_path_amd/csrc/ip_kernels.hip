@@ -1070,6 +1070,66 @@ k_start_from_records(S *__restrict__ base, size_t stride, size_t n, double limit
     status[i] = 0;
 }
 
+// Feasible start with end velocities (rp_batch_set_problems_vel_device, rp_batch_restart of such a batch): vel1 = 0, multipliers 1,
+//     t_0 = (3.5/sqrt 12) sqrt(6 |dX_0| / L) + 8 |vel0| / L,    t_1 = (3.5/sqrt 12) sqrt(6 |dX_1| / L) + 8 |vel2| / L,
+// from the STORED positions and velocities.  With zero velocities it is k_restart_feasible's start bit for bit (x + 0 = x, the same
+// operations in the same order); with any velocities it is strictly feasible: on a segment with t = t_pos + t_vel (t_pos the
+// rest-to-rest duration) every |a| <= L (0.98 rho^2 + (4/8)(1 - rho)) <= 0.98 L, rho = t_pos / t.
+template <typename S>
+__device__ __forceinline__ void store_vel_start(S *__restrict__ f, size_t stride, int nc, double limit, double p0, double p1, double p2,
+                                                double u0, double u2)
+{
+    const double scale = 3.5 / __builtin_sqrt(12.0);
+    f[0 * stride] = S(0);
+    f[1 * stride] = (S)(scale * __builtin_sqrt(6.0 * __builtin_fabs(p1 - p0) / limit) + 8.0 * __builtin_fabs(u0) / limit);
+    f[2 * stride] = (S)(scale * __builtin_sqrt(6.0 * __builtin_fabs(p2 - p1) / limit) + 8.0 * __builtin_fabs(u2) / limit);
+    for (int c = 0; c < nc; ++c) f[(3 + c) * stride] = S(1);
+}
+
+// rp_batch_set_problems_vel_device: k_start_from_records with the end velocities gathered from problem-order arrays (null: zeros)
+template <typename S, int VARIANT>
+__global__ void __launch_bounds__(kBlock)
+k_start_vel_from_records(S *__restrict__ base, size_t stride, size_t n, double limit, const StartRecord *__restrict__ records,
+                         const uint32_t *__restrict__ prob_of, const double *__restrict__ vel0, const double *__restrict__ vel2,
+                         int32_t *__restrict__ iters, uint32_t *__restrict__ status)
+{
+    constexpr int NC = CMap<VARIANT>::NC;
+    constexpr int CB = 3 + NC;
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const size_t prob = prob_of[i];
+    typedef double v2 __attribute__((ext_vector_type(2)));
+    const v2 *rec = reinterpret_cast<const v2 *>(records + prob);
+    const v2 ra = rec[0], rb = rec[1];
+    const S s0 = (S)ra[0], s1 = (S)ra[1], s2 = (S)rb[0];
+    // + 0.0: a velocity of -0 is stored as +0, the bits set_problems_device leaves (rest-to-rest bit for bit)
+    const S w0 = vel0 ? (S)(vel0[prob] + 0.0) : S(0), w2 = vel2 ? (S)(vel2[prob] + 0.0) : S(0);
+    S *f = base + i;
+    store_vel_start(f, stride, NC, limit, (double)s0, (double)s1, (double)s2, (double)w0, (double)w2);
+    f[(CB + 0) * stride] = s0;
+    f[(CB + 1) * stride] = w0;
+    f[(CB + 2) * stride] = s1;
+    f[(CB + 3) * stride] = s2;
+    f[(CB + 4) * stride] = w2;
+    iters[i] = 0;
+    status[i] = 0;
+}
+
+// rp_batch_restart of a batch given its problems with end velocities: the same start from the constant fields
+template <typename S, int VARIANT>
+__global__ void __launch_bounds__(kBlock)
+k_restart_vel(S *__restrict__ base, size_t stride, size_t n, double limit)
+{
+    constexpr int NC = CMap<VARIANT>::NC;
+    constexpr int CB = 3 + NC;
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    S *f = base + i;
+    const double p0 = (double)f[(CB + 0) * stride], p1 = (double)f[(CB + 2) * stride], p2 = (double)f[(CB + 3) * stride];
+    const double u0 = (double)f[(CB + 1) * stride], u2 = (double)f[(CB + 4) * stride];
+    store_vel_start(f, stride, NC, limit, p0, p1, p2, u0, u2);
+}
+
 // Every problem gets the same state (initDefault / initStuck broadcast).
 struct ConstState { double v[16]; };
 
@@ -1591,6 +1651,22 @@ hipError_t launch_start_from_records(const BatchView &b, const HostParams &hp, h
     if (!b.records) return hipErrorInvalidValue;
     RP_DISPATCH(b, hipLaunchKernelGGL((k_start_from_records<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
                                        (S *)b.base, b.stride, b.n, hp.accel_limit, (const StartRecord *)b.records, (const uint32_t *)b.prob_of, b.iters, b.status));
+    return hipGetLastError();
+}
+
+hipError_t launch_start_vel_from_records(const BatchView &b, const HostParams &hp, const double *d_vel0, const double *d_vel2, hipStream_t stream)
+{
+    if (!b.records || !b.scheduled) return hipErrorInvalidValue;
+    RP_DISPATCH(b, hipLaunchKernelGGL((k_start_vel_from_records<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                       (S *)b.base, b.stride, b.n, hp.accel_limit, (const StartRecord *)b.records, (const uint32_t *)b.prob_of,
+                                       d_vel0, d_vel2, b.iters, b.status));
+    return hipGetLastError();
+}
+
+hipError_t launch_restart_vel(const BatchView &b, const HostParams &hp, hipStream_t stream)
+{
+    RP_DISPATCH(b, hipLaunchKernelGGL((k_restart_vel<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                       (S *)b.base, b.stride, b.n, hp.accel_limit));
     return hipGetLastError();
 }
 

@@ -48,6 +48,9 @@ struct rp_batch {
     bool slim_schedule;       // the scheduling pass runs in its one-wave-per-block form (schedule.hip): set by rp_pipeline for its batches
     bool at_start;            // set_problems has run and nothing else since: the batch holds its scheduled order and its positions; the
                               // feasible start itself (mutable fields, progress words) is NOT materialised yet -- see materialize()
+    bool vel_start;           // the problems were set with end velocities (rp_batch_set_problems_vel(_device)): rp_batch_restart goes back to the
+                              // start with the velocities the batch holds, not to the rest-to-rest start; cleared by every other init / set_problems /
+                              // set_state
     double ungated_steps;     // per-problem count of ungated steps since the last init
     unsigned long long *h_pinned;   // 72 pinned host words: [0,64) counter shards, [64,68) reduction: read-backs without pageable staging
     hipEvent_t events[8];
@@ -433,6 +436,7 @@ int rp_batch_init_default(rp_batch *b)
     b->view.scheduled = false;         // identical problems: nothing to schedule
     b->at_start = false;
     b->records_current = false;
+    b->vel_start = false;
     return reset_progress(b);
 }
 
@@ -452,6 +456,7 @@ int rp_batch_init_stuck(rp_batch *b)
     b->view.scheduled = false;
     b->at_start = false;
     b->records_current = false;
+    b->vel_start = false;
     return reset_progress(b);
 }
 
@@ -476,6 +481,26 @@ int rp_batch_set_problems_device(rp_batch *b, const double *d_pos0, const double
     b->unpredicted = false;      // the feasible-start rule: what the scheduled order was fitted to
     b->at_start = true;
     b->records_current = true;
+    b->vel_start = false;
+    return RP_OK;
+}
+
+int rp_batch_set_problems_vel_device(rp_batch *b, const double *d_pos0, const double *d_pos1, const double *d_pos2,
+                                     const double *d_vel0, const double *d_vel2)
+{
+    RP_NEED(b);
+    if (!d_pos0 || !d_pos1 || !d_pos2) return fail(RP_ERR_INVALID, "null position array");
+    // the scheduling pass on the positions (set_problems_device), then the start with the velocities written out at once: the fused
+    // solve forms only the rest-to-rest start in registers
+    b->view.zero_end_vel = true;      // (skips set_problems_device's clearing of the velocity fields: the start below writes both)
+    int st = rp_batch_set_problems_device(b, d_pos0, d_pos1, d_pos2);
+    if (st != RP_OK) return st;
+    b->at_start = false;
+    RP_HIP(rp::launch_start_vel_from_records(b->view, b->params, d_vel0, d_vel2, b->stream));
+    b->view.zero_end_vel = false;      // the general Newton kernels (bit-identical to the zero-velocity ones where the velocities are 0)
+    b->unpredicted = true;             // the scheduled order was fitted to rest-to-rest starts
+    b->records_current = false;
+    b->vel_start = true;
     return RP_OK;
 }
 
@@ -485,8 +510,13 @@ int rp_batch_restart(rp_batch *b)
     b->sol_stale = true;
     if (!b->raw_positions_out) b->unpredicted = false;      // back on the feasible start of the positions the order was computed from
     if (b->at_start) return materialize(b);      // already at the start of its positions: write it out
-    RP_HIP(rp::launch_restart_feasible(b->view, b->params, b->stream));
-    b->view.zero_end_vel = true;
+    if (b->vel_start) {      // back to the start with the end velocities the batch holds
+        RP_HIP(rp::launch_restart_vel(b->view, b->params, b->stream));
+        b->unpredicted = true;
+    } else {
+        RP_HIP(rp::launch_restart_feasible(b->view, b->params, b->stream));
+        b->view.zero_end_vel = true;
+    }
     b->ungated_steps = 0.0;
     RP_HIP(rp::launch_clear_progress(b->view, b->stream));      // the positions have not changed: the scheduled order stays as it is
     return RP_OK;
@@ -504,6 +534,30 @@ int rp_batch_set_problems(rp_batch *b, const double *pos0, const double *pos1, c
     int st = rp_batch_set_problems_device(b, b->d_pos, b->d_pos + n, b->d_pos + 2 * n);
     if (st != RP_OK) return st;
     RP_HIP(hipStreamSynchronize(b->stream));   // the host arrays may be reused on return
+    return RP_OK;
+}
+
+int rp_batch_set_problems_vel(rp_batch *b, const double *pos0, const double *pos1, const double *pos2, const double *vel0, const double *vel2)
+{
+    RP_NEED(b);
+    if (!pos0 || !pos1 || !pos2) return fail(RP_ERR_INVALID, "null position array");
+    const size_t n = b->view.n;
+    if (!b->d_pos) RP_HIP(hipMalloc((void **)&b->d_pos, 3 * n * sizeof(double)));
+    RP_HIP(hipMemcpyAsync(b->d_pos, pos0, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    RP_HIP(hipMemcpyAsync(b->d_pos + n, pos1, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    RP_HIP(hipMemcpyAsync(b->d_pos + 2 * n, pos2, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    double *d_vel = nullptr;      // the two velocity arrays, staged for this call only
+    if (vel0 || vel2) RP_HIP(hipMalloc((void **)&d_vel, 2 * n * sizeof(double)));
+    hipError_t e = hipSuccess;
+    if (vel0) e = hipMemcpyAsync(d_vel, vel0, n * sizeof(double), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess && vel2) e = hipMemcpyAsync(d_vel + n, vel2, n * sizeof(double), hipMemcpyHostToDevice, b->stream);
+    int st = e == hipSuccess ? rp_batch_set_problems_vel_device(b, b->d_pos, b->d_pos + n, b->d_pos + 2 * n, vel0 ? d_vel : nullptr,
+                                                                vel2 ? d_vel + n : nullptr)
+                             : fail(RP_ERR_DEVICE, "rp_batch_set_problems_vel: %s", hipGetErrorString(e));
+    const hipError_t se = hipStreamSynchronize(b->stream);      // the host arrays may be reused on return, the staging freed
+    if (d_vel) (void)hipFree(d_vel);
+    if (st != RP_OK) return st;
+    RP_HIP(se);
     return RP_OK;
 }
 
@@ -530,6 +584,7 @@ int rp_batch_set_state(rp_batch *b, const double *aos)
         b->sol_stale = true;
         b->raw_state_out = false;
         b->unpredicted = true;      // any state: the order (computed from the positions in the rows) predicts nothing about it
+        b->vel_start = false;
     }
     RP_HIP(rp::launch_aos_to_soa(b->view, b->d_aos, b->stream));
     st = reset_progress(b);
@@ -770,6 +825,43 @@ int rp_batch_solution_hessian(rp_batch *b, double *d_jac, double *d_hess)
     if (!d_hess) return fail(RP_ERR_INVALID, "null output");
     RP_NEED_STATE(b);
     RP_HIP(rp::launch_solution_hessian(b->view, b->params, d_jac, d_hess, b->stream));
+    return RP_OK;
+}
+
+int rp_batch_solution_vjp_vel(rp_batch *b, const double *d_g_vel1, const double *d_g_dur0, const double *d_g_dur1, double *d_pos0_bar,
+                              double *d_pos1_bar, double *d_pos2_bar, double *d_vel0_bar, double *d_vel2_bar)
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
+        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_vjp_vel: F3 with RP_DTYPE_F64 only");
+    if (!d_pos0_bar || !d_pos1_bar || !d_pos2_bar || !d_vel0_bar || !d_vel2_bar) return fail(RP_ERR_INVALID, "null output");
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_solution_vjp_vel(b->view, b->params, d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar, d_vel0_bar,
+                                       d_vel2_bar, b->stream));
+    return RP_OK;
+}
+
+int rp_batch_solution_jvp_vel(rp_batch *b, const double *d_t_pos0, const double *d_t_pos1, const double *d_t_pos2, const double *d_t_vel0,
+                              const double *d_t_vel2, double *d_t_vel1, double *d_t_dur0, double *d_t_dur1)
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
+        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_jvp_vel: F3 with RP_DTYPE_F64 only");
+    if (!d_t_vel1 || !d_t_dur0 || !d_t_dur1) return fail(RP_ERR_INVALID, "null output");
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_solution_jvp_vel(b->view, b->params, d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel0, d_t_vel2, d_t_vel1, d_t_dur0, d_t_dur1,
+                                       b->stream));
+    return RP_OK;
+}
+
+int rp_batch_solution_jacobian_vel(rp_batch *b, double *d_jac)
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
+        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_jacobian_vel: F3 with RP_DTYPE_F64 only");
+    if (!d_jac) return fail(RP_ERR_INVALID, "null output");
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_solution_jacobian_vel(b->view, b->params, d_jac, b->stream));
     return RP_OK;
 }
 
