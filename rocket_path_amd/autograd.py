@@ -76,14 +76,22 @@ def _stream_handle(stream):
     return stream.cuda_stream
 
 
+def _check_is_tensor(name, t, who):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(who + ": %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+
+
+def _check_is_float64(name, t, who):
+    if t.dtype != torch.float64:
+        raise TypeError(who + ": %s has dtype %s; float64 is required" % (name, t.dtype))
+
+
 def _check_positions(pos0, pos1, pos2, who="min_time_solve"):
     for name, t in (("pos0", pos0), ("pos1", pos1), ("pos2", pos2)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(who + ": %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        _check_is_tensor(name, t, who)
         if t.device.type != "cuda":
             raise TypeError(who + ": %s is on %s; the solve runs on a ROCm device only (move it with .cuda())" % (name, t.device))
-        if t.dtype != torch.float64:
-            raise TypeError(who + ": %s has dtype %s; float64 is required" % (name, t.dtype))
+        _check_is_float64(name, t, who)
         if t.dim() != 1:
             raise ValueError(who + ": %s must be 1-D, got shape %s" % (name, tuple(t.shape)))
     if not (pos0.shape == pos1.shape == pos2.shape):
@@ -101,12 +109,10 @@ def _check_velocities(pos0, vel0, vel2, who):
     for name, t in (("vel0", vel0), ("vel2", vel2)):
         if t is None:
             continue
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(who + ": %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        _check_is_tensor(name, t, who)
         if t.device.type != "cuda" or t.device != pos0.device:
             raise TypeError(who + ": %s is on %s; it must be on the positions' ROCm device %s" % (name, t.device, pos0.device))
-        if t.dtype != torch.float64:
-            raise TypeError(who + ": %s has dtype %s; float64 is required" % (name, t.dtype))
+        _check_is_float64(name, t, who)
         if t.shape != pos0.shape:
             raise ValueError(who + ": %s has shape %s, the positions %s" % (name, tuple(t.shape), tuple(pos0.shape)))
     return True
@@ -202,24 +208,69 @@ class _Holder:
         self.lease = None
 
 
+def _launch(batch, device, launches, plain=False):
+    """Enqueue derivative kernels at the state of `batch` from the current stream, as one ordered region: the batch stream waits
+    for the current stream, runs them, and the current stream waits for it (_run_on; nothing is added when the two are the same
+    stream), and every tensor the kernels touch is recorded on the batch stream.  launches: (bound Batch method, input tensors --
+    None: a null address, which the kernels read as zeros --, number of outputs, their shape) each; the method gets the inputs'
+    addresses, then the outputs'.  Returns one list of new float64 tensors per launch.  plain: the caller is a jvp rule, whose
+    tensors the kernels read and write under torch.func's wrappers (_plain)."""
+    cur = torch.cuda.current_stream(device)
+    bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
+    same = bstream.cuda_stream == cur.cuda_stream
+    unwrap = _plain if plain else (lambda t: t)
+    jobs, results = [], []
+    for method, inputs, count, shape in launches:
+        ins = [unwrap(t.contiguous()) if t is not None else None for t in inputs]
+        outs = [torch.empty(shape, dtype=torch.float64, device=device) for _ in range(count)]
+        jobs.append((method, ins, [unwrap(t) for t in outs]))
+        results.append(outs)
+    with _run_on(None if same else bstream, cur):
+        for method, ins, raw in jobs:
+            method(*[t.data_ptr() if t is not None else 0 for t in ins], *[t.data_ptr() for t in raw])
+    if not same:
+        for _, ins, raw in jobs:
+            for t in ins + raw:
+                if t is not None:
+                    t.record_stream(bstream)
+    return results
+
+
+def _forward(holder, *solve_args, **solve_kw):
+    """forward of both solve Functions: the solve, its batch leased to the holder."""
+    key, batch, outs = _solve(*solve_args, **solve_kw)
+    holder.lease = _Lease(key, batch)
+    return outs
+
+
+def _setup_context(ctx, inputs, output):
+    """setup_context of both solve Functions.  ctx keeps the lease, and with it the batch whose state backward and jvp differentiate,
+    out of the pool: for as long as an autograd graph holds ctx, or only until apply returns when none does (no_grad, or no input
+    requiring grad).  The holder goes when min_time_solve returns, so a batch nothing holds is back in the pool once its read-back
+    is enqueued."""
+    ctx.lease = inputs[-1].lease
+    ctx.device = inputs[0].device
+    ctx.mark_non_differentiable(output[3], output[4])
+
+
+def _jvp(ctx, method, tangents):
+    """jvp of both solve Functions: one launch of `method` (Batch.solution_jvp / solution_jvp_vel) on the input tangents."""
+    batch = ctx.lease.batch
+    (dots,) = _launch(batch, ctx.device, [(getattr(batch, method), tangents, 3, batch.n)], plain=True)
+    return dots[0], dots[1], dots[2], None, None
+
+
 class _MinTimeSolve(torch.autograd.Function):
     @staticmethod
     def forward(pos0, pos1, pos2, gap_tol, max_iter, params, holder):
-        key, batch, outs = _solve(pos0, pos1, pos2, gap_tol, max_iter, params)
-        holder.lease = _Lease(key, batch)
-        return outs
+        return _forward(holder, pos0, pos1, pos2, gap_tol, max_iter, params)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        # ctx keeps the lease, and with it the batch whose state backward and jvp differentiate, out of the pool: for as long as an
-        # autograd graph holds ctx, or only until apply returns when none does (no_grad, or no input requiring grad).  The holder
-        # goes when min_time_solve returns, so a batch nothing holds is back in the pool once its read-back is enqueued.
-        ctx.lease = inputs[-1].lease
-        ctx.device = inputs[0].device
+        _setup_context(ctx, inputs, output)
         # the positions themselves, for the graph a create_graph backward builds (_SolutionVJP takes them as inputs); kept as
         # attributes, not saved tensors, so first-order use keeps its rules (no version check on the positions)
         ctx.pos = inputs[:3]
-        ctx.mark_non_differentiable(output[3], output[4])
 
     @staticmethod
     def backward(ctx, g_vel1, g_dur0, g_dur1, _g_iters, _g_status):
@@ -229,22 +280,7 @@ class _MinTimeSolve(torch.autograd.Function):
 
     @staticmethod
     def jvp(ctx, t_pos0, t_pos1, t_pos2, _t_gap, _t_iter, _t_params, _t_holder):
-        batch = ctx.lease.batch
-        device = ctx.device
-        cur = torch.cuda.current_stream(device)
-        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
-        ts = [_plain(t.contiguous()) if t is not None else None for t in (t_pos0, t_pos1, t_pos2)]
-        n = batch.n
-        outs = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(3)]
-        dots = [_plain(t) for t in outs]
-        same = bstream.cuda_stream == cur.cuda_stream
-        with _run_on(None if same else bstream, cur):
-            batch.solution_jvp(*[t.data_ptr() if t is not None else 0 for t in ts], *[d.data_ptr() for d in dots])
-        if not same:
-            for t in ts + dots:
-                if t is not None:
-                    t.record_stream(bstream)
-        return outs[0], outs[1], outs[2], None, None
+        return _jvp(ctx, "solution_jvp", [t_pos0, t_pos1, t_pos2])
 
 
 class _MinTimeSolveVel(torch.autograd.Function):
@@ -253,55 +289,24 @@ class _MinTimeSolveVel(torch.autograd.Function):
 
     @staticmethod
     def forward(pos0, pos1, pos2, vel0, vel2, gap_tol, max_iter, params, holder):
-        key, batch, outs = _solve(pos0, pos1, pos2, gap_tol, max_iter, params, vel=(vel0, vel2))
-        holder.lease = _Lease(key, batch)
-        return outs
+        return _forward(holder, pos0, pos1, pos2, gap_tol, max_iter, params, vel=(vel0, vel2))
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.lease = inputs[-1].lease      # _MinTimeSolve's rule: the batch stays out of the pool while the graph holds ctx
-        ctx.device = inputs[0].device
+        _setup_context(ctx, inputs, output)
         ctx.has_vel = (inputs[3] is not None, inputs[4] is not None)
-        ctx.mark_non_differentiable(output[3], output[4])
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_vel1, g_dur0, g_dur1, _g_iters, _g_status):
         batch = ctx.lease.batch
-        device = ctx.device
-        cur = torch.cuda.current_stream(device)
-        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
-        gs = [g.contiguous() if g is not None else None for g in (g_vel1, g_dur0, g_dur1)]
-        n = batch.n
-        bars = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(5)]
-        same = bstream.cuda_stream == cur.cuda_stream
-        with _run_on(None if same else bstream, cur):
-            batch.solution_vjp_vel(*[g.data_ptr() if g is not None else 0 for g in gs], *[b.data_ptr() for b in bars])
-        if not same:
-            for t in gs + bars:
-                if t is not None:
-                    t.record_stream(bstream)
+        (bars,) = _launch(batch, ctx.device, [(batch.solution_vjp_vel, [g_vel1, g_dur0, g_dur1], 5, batch.n)])
         vel_bars = tuple(b if has else None for b, has in zip(bars[3:], ctx.has_vel))
         return (bars[0], bars[1], bars[2]) + vel_bars + (None, None, None, None)
 
     @staticmethod
     def jvp(ctx, t_pos0, t_pos1, t_pos2, t_vel0, t_vel2, _t_gap, _t_iter, _t_params, _t_holder):
-        batch = ctx.lease.batch
-        device = ctx.device
-        cur = torch.cuda.current_stream(device)
-        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
-        ts = [_plain(t.contiguous()) if t is not None else None for t in (t_pos0, t_pos1, t_pos2, t_vel0, t_vel2)]
-        n = batch.n
-        outs = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(3)]
-        dots = [_plain(t) for t in outs]
-        same = bstream.cuda_stream == cur.cuda_stream
-        with _run_on(None if same else bstream, cur):
-            batch.solution_jvp_vel(*[t.data_ptr() if t is not None else 0 for t in ts], *[d.data_ptr() for d in dots])
-        if not same:
-            for t in ts + dots:
-                if t is not None:
-                    t.record_stream(bstream)
-        return outs[0], outs[1], outs[2], None, None
+        return _jvp(ctx, "solution_jvp_vel", [t_pos0, t_pos1, t_pos2, t_vel0, t_vel2])
 
 
 class _SolutionVJP(torch.autograd.Function):
@@ -314,18 +319,7 @@ class _SolutionVJP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g_vel1, g_dur0, g_dur1, pos0, pos1, pos2, lease, device):
         batch = lease.batch
-        cur = torch.cuda.current_stream(device)
-        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
-        gs = [g.contiguous() if g is not None else None for g in (g_vel1, g_dur0, g_dur1)]
-        n = batch.n
-        bars = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(3)]
-        same = bstream.cuda_stream == cur.cuda_stream
-        with _run_on(None if same else bstream, cur):
-            batch.solution_vjp(*[g.data_ptr() if g is not None else 0 for g in gs], *[b.data_ptr() for b in bars])
-        if not same:
-            for t in gs + bars:
-                if t is not None:
-                    t.record_stream(bstream)
+        (bars,) = _launch(batch, device, [(batch.solution_vjp, [g_vel1, g_dur0, g_dur1], 3, batch.n)])
         ctx.lease = lease
         ctx.device = device
         ctx.save_for_backward(g_vel1, g_dur0, g_dur1)
@@ -338,30 +332,22 @@ class _SolutionVJP(torch.autograd.Function):
         device = ctx.device
         gs = ctx.saved_tensors
         need_g, need_pos = any(ctx.needs_input_grad[:3]), any(ctx.needs_input_grad[3:6])
-        hs = [h.contiguous() if h is not None else None for h in (h_pos0, h_pos1, h_pos2)]
+        hs = [h_pos0, h_pos1, h_pos2]
         n = batch.n
         g_bar = pos_bar = (None, None, None)
         if all(h is None for h in hs):
             return g_bar + pos_bar + (None, None)
-        cur = torch.cuda.current_stream(device)
-        bstream = torch.cuda.ExternalStream(batch.stream(), device=device)
-        same = bstream.cuda_stream == cur.cuda_stream
-        outs = [torch.empty(n, dtype=torch.float64, device=device) for _ in range(3)] if need_g else []
-        hess = None
-        if need_pos and any(g is not None for g in gs):
-            hess = torch.empty((n, 3, 3, 3), dtype=torch.float64, device=device)
-        with _run_on(None if same else bstream, cur):
-            if outs:
-                batch.solution_jvp(*[h.data_ptr() if h is not None else 0 for h in hs], *[o.data_ptr() for o in outs])
-            if hess is not None:
-                batch.solution_hessian(0, hess.data_ptr())
-        if not same:
-            for t in hs + outs + [hess]:
-                if t is not None:
-                    t.record_stream(bstream)
-        if outs:
-            g_bar = tuple(outs)
-        if hess is not None:
+        need_hess = need_pos and any(g is not None for g in gs)
+        launches = []      # both in one ordered region
+        if need_g:
+            launches.append((batch.solution_jvp, hs, 3, n))
+        if need_hess:
+            launches.append((lambda d_hess: batch.solution_hessian(0, d_hess), [], 1, (n, 3, 3, 3)))
+        results = _launch(batch, device, launches)
+        if need_g:
+            g_bar = tuple(results[0])
+        if need_hess:
+            (hess,) = results[-1]
             zero = torch.zeros(n, dtype=torch.float64, device=device)
             gv = torch.stack([g if g is not None else zero for g in gs], dim=1)
             hv = torch.stack([h if h is not None else zero for h in hs], dim=1)
@@ -390,6 +376,19 @@ def min_time_solve(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None,
     return _MinTimeSolve.apply(pos0, pos1, pos2, float(gap_tol), int(max_iter), params, _Holder())
 
 
+def _solve_detached(who, pos0, pos1, pos2, gap_tol, max_iter, params, vel0, vel2, **which):
+    """min_time_jacobian and min_time_hessian: the checks in `who`'s name, the solve on detached inputs with the launch `which`
+    names (jacobian=True / hessian=True), the batch straight back to the pool."""
+    _check_positions(pos0, pos1, pos2, who)
+    _check_params(params, who)
+    vel = (vel0, vel2) if _check_velocities(pos0, vel0, vel2, who) else None
+    if vel is not None:
+        vel = tuple(t.detach() if t is not None else None for t in vel)
+    key, batch, outs = _solve(pos0.detach(), pos1.detach(), pos2.detach(), float(gap_tol), int(max_iter), params, vel=vel, **which)
+    _pool.give(key, batch)      # the read-backs are enqueued; the next user of this key works on the same stream
+    return outs
+
+
 def min_time_jacobian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None, vel0=None, vel2=None):
     """min_time_solve's solve, and every problem's Jacobian at the state it returns, on the current stream.
 
@@ -397,14 +396,7 @@ def min_time_jacobian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=No
     for x = (vel1, duration0, duration1) (rp_batch_solution_jacobian; NaN rows as for min_time_solve's derivatives).  One solve and
     one Jacobian launch; nothing returned is differentiable.  Does not synchronise the host.  With end velocities (vel0= / vel2=, as
     min_time_solve's) jac is (n, 3, 5), columns (pos0, pos1, pos2, vel0, vel2) (rp_batch_solution_jacobian_vel)."""
-    _check_positions(pos0, pos1, pos2, "min_time_jacobian")
-    _check_params(params, "min_time_jacobian")
-    vel = (vel0, vel2) if _check_velocities(pos0, vel0, vel2, "min_time_jacobian") else None
-    if vel is not None:
-        vel = tuple(t.detach() if t is not None else None for t in vel)
-    key, batch, outs = _solve(pos0.detach(), pos1.detach(), pos2.detach(), float(gap_tol), int(max_iter), params, jacobian=True, vel=vel)
-    _pool.give(key, batch)      # the read-backs are enqueued; the next user of this key works on the same stream
-    return outs
+    return _solve_detached("min_time_jacobian", pos0, pos1, pos2, gap_tol, max_iter, params, vel0, vel2, jacobian=True)
 
 
 def min_time_hessian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=None, vel0=None, vel2=None):
@@ -415,14 +407,7 @@ def min_time_hessian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=Non
     problems min_time_solve's derivatives are NaN for).  One solve and one Hessian launch; nothing returned is differentiable.  Does
     not synchronise the host.  With end velocities (vel0= / vel2=, as min_time_solve's) jac is min_time_jacobian's (n, 3, 5) and hess
     the second derivatives in the positions only, at that state (one Hessian and one Jacobian launch)."""
-    _check_positions(pos0, pos1, pos2, "min_time_hessian")
-    _check_params(params, "min_time_hessian")
-    vel = (vel0, vel2) if _check_velocities(pos0, vel0, vel2, "min_time_hessian") else None
-    if vel is not None:
-        vel = tuple(t.detach() if t is not None else None for t in vel)
-    key, batch, outs = _solve(pos0.detach(), pos1.detach(), pos2.detach(), float(gap_tol), int(max_iter), params, hessian=True, vel=vel)
-    _pool.give(key, batch)      # the read-backs are enqueued; the next user of this key works on the same stream
-    return outs
+    return _solve_detached("min_time_hessian", pos0, pos1, pos2, gap_tol, max_iter, params, vel0, vel2, hessian=True)
 
 
 def clear_pool():

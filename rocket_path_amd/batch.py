@@ -21,6 +21,11 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+def _addrs(*device_addresses):
+    """Device addresses as the C ABI's pointer arguments: None / 0 goes as NULL."""
+    return [ctypes.c_void_p(p) if p else None for p in device_addresses]
+
+
 class Batch:
     def __init__(self, n, variant=capi.VARIANT_F3, dtype=capi.DTYPE_F64, device=0, stream=None, _borrowed=None):
         self._lib = capi.load_library()
@@ -161,51 +166,46 @@ class Batch:
         """Gradients with respect to (pos0, pos1, pos2) of a loss whose gradients on (vel1, duration0, duration1) are the three
         upstream arrays, at the current state (rp_batch_solution_vjp): device addresses of n doubles each, problem order; an upstream
         address of None / 0 counts as zeros.  Asynchronous on the batch stream.  F3 with DTYPE_F64 only."""
-        capi.check(self._lib.rp_batch_solution_vjp(self._h, *[ctypes.c_void_p(p) if p else None for p in
-                                                              (d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar)]))
+        capi.check(self._lib.rp_batch_solution_vjp(self._h, *_addrs(d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar)))
 
     def solution_jvp(self, d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel1, d_t_dur0, d_t_dur1):
         """Tangents of (vel1, duration0, duration1) along the position tangents (pos0, pos1, pos2), at the current state
         (rp_batch_solution_jvp): device addresses of n doubles each, problem order; a tangent address of None / 0 counts as zeros.
         Asynchronous on the batch stream.  F3 with DTYPE_F64 only."""
-        capi.check(self._lib.rp_batch_solution_jvp(self._h, *[ctypes.c_void_p(p) if p else None for p in
-                                                              (d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel1, d_t_dur0, d_t_dur1)]))
+        capi.check(self._lib.rp_batch_solution_jvp(self._h, *_addrs(d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel1, d_t_dur0, d_t_dur1)))
 
     def solution_jacobian(self, d_jac):
         """Every problem's 3 x 3 Jacobian d(vel1, duration0, duration1) / d(pos0, pos1, pos2), row-major, at the current state
         (rp_batch_solution_jacobian): device address of n x 9 doubles, problem order.  Asynchronous on the batch stream.  F3 with
         DTYPE_F64 only."""
-        capi.check(self._lib.rp_batch_solution_jacobian(self._h, ctypes.c_void_p(d_jac) if d_jac else None))
+        capi.check(self._lib.rp_batch_solution_jacobian(self._h, *_addrs(d_jac)))
 
     def solution_vjp_vel(self, d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar, d_vel0_bar, d_vel2_bar):
         """Gradients with respect to (pos0, pos1, pos2, vel0, vel2) of a loss whose gradients on (vel1, duration0, duration1) are the
         three upstream arrays, at the current state (rp_batch_solution_vjp_vel): device addresses of n doubles each, problem order; an
         upstream address of None / 0 counts as zeros.  Asynchronous on the batch stream.  F3 with DTYPE_F64 only."""
-        capi.check(self._lib.rp_batch_solution_vjp_vel(self._h, *[ctypes.c_void_p(p) if p else None for p in
-                                                                  (d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar,
-                                                                   d_vel0_bar, d_vel2_bar)]))
+        capi.check(self._lib.rp_batch_solution_vjp_vel(self._h, *_addrs(d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar,
+                                                                        d_vel0_bar, d_vel2_bar)))
 
     def solution_jvp_vel(self, d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel0, d_t_vel2, d_t_vel1, d_t_dur0, d_t_dur1):
         """Tangents of (vel1, duration0, duration1) along the tangents of (pos0, pos1, pos2, vel0, vel2), at the current state
         (rp_batch_solution_jvp_vel): device addresses of n doubles each, problem order; a tangent address of None / 0 counts as zeros.
         Asynchronous on the batch stream.  F3 with DTYPE_F64 only."""
-        capi.check(self._lib.rp_batch_solution_jvp_vel(self._h, *[ctypes.c_void_p(p) if p else None for p in
-                                                                  (d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel0, d_t_vel2, d_t_vel1, d_t_dur0,
-                                                                   d_t_dur1)]))
+        capi.check(self._lib.rp_batch_solution_jvp_vel(self._h, *_addrs(d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel0, d_t_vel2, d_t_vel1, d_t_dur0,
+                                                                        d_t_dur1)))
 
     def solution_jacobian_vel(self, d_jac):
         """Every problem's 3 x 5 Jacobian d(vel1, duration0, duration1) / d(pos0, pos1, pos2, vel0, vel2), row-major, at the current
         state (rp_batch_solution_jacobian_vel): device address of n x 15 doubles, problem order.  Asynchronous on the batch stream.  F3
         with DTYPE_F64 only."""
-        capi.check(self._lib.rp_batch_solution_jacobian_vel(self._h, ctypes.c_void_p(d_jac) if d_jac else None))
+        capi.check(self._lib.rp_batch_solution_jacobian_vel(self._h, *_addrs(d_jac)))
 
     def solution_hessian(self, d_jac, d_hess):
         """Every problem's second derivatives H[a][b][c] = d^2 x_a / dpos_b dpos_c, x = (vel1, duration0, duration1), at the current
         state (rp_batch_solution_hessian): d_hess the device address of n x 27 doubles, problem order, symmetric in (b, c); d_jac
         None / 0, or n x 9 doubles for the Jacobian in solution_jacobian's layout.  Asynchronous on the batch stream.  F3 with
         DTYPE_F64 only."""
-        capi.check(self._lib.rp_batch_solution_hessian(self._h, ctypes.c_void_p(d_jac) if d_jac else None,
-                                                       ctypes.c_void_p(d_hess) if d_hess else None))
+        capi.check(self._lib.rp_batch_solution_hessian(self._h, *_addrs(d_jac, d_hess)))
 
     def bind_solution(self, d_out):
         """Gated solves write each problem's rp_solution record to d_out (device address of n records; None / 0 unbinds)."""

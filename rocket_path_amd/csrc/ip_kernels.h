@@ -94,7 +94,7 @@ hipError_t launch_solution_jacobian(const BatchView &b, const HostParams &hp, do
 // same first-order solves, problem order, at the batch's current state (sensitivity.hip; F3, double storage only)
 hipError_t launch_solution_hessian(const BatchView &b, const HostParams &hp, double *d_jac, double *d_hess, hipStream_t stream);
 // the first derivatives in all five boundary inputs (pos0, pos1, pos2, vel0, vel2): VJP, JVP (null tangents / gradients: zeros) and
-// the 3 x 5 Jacobian (15 doubles per problem, row-major), problem order, at the batch's current state (sensitivity_vel.hip; F3,
+// the 3 x 5 Jacobian (15 doubles per problem, row-major), problem order, at the batch's current state (sensitivity.hip, the k_endvel_* kernels; F3,
 // double storage only)
 hipError_t launch_solution_vjp_vel(const BatchView &b, const HostParams &hp, const double *d_g_vel1, const double *d_g_dur0,
                                    const double *d_g_dur1, double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar,

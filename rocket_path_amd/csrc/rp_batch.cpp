@@ -164,6 +164,17 @@ int seed_solution(rp_batch *b)
         if (ms_ != RP_OK) return ms_;        \
     } while (0)
 
+// What every derivative entry (rp_batch_solution_vjp ... rp_batch_solution_jacobian_vel) asks for, in the order it is tested: a
+// handle, an F3 batch in double storage (the message names the entry), every output (`outputs`: all of them given), the state
+#define RP_NEED_F3_STATE(b, outputs)                                                    \
+    do {                                                                                \
+        if (!(b)) return fail(RP_ERR_INVALID, "null batch handle");                     \
+        if ((b)->view.variant != RP_VARIANT_F3 || (b)->view.dtype != RP_DTYPE_F64)      \
+            return fail(RP_ERR_UNSUPPORTED, "%s: F3 with RP_DTYPE_F64 only", __func__); \
+        if (!(outputs)) return fail(RP_ERR_INVALID, "null output");                     \
+        RP_NEED_STATE(b);                                                               \
+    } while (0)
+
 int need_words(rp_batch *b)
 {
     if (!b->d_words) RP_HIP(hipMalloc((void **)&b->d_words, 2 * b->view.n * sizeof(uint32_t)));
@@ -785,11 +796,7 @@ int rp_batch_solution_device(rp_batch *b, rp_solution *d_out)
 int rp_batch_solution_vjp(rp_batch *b, const double *d_g_vel1, const double *d_g_dur0, const double *d_g_dur1,
                           double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar)
 {
-    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
-        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_vjp: F3 with RP_DTYPE_F64 only");
-    if (!d_pos0_bar || !d_pos1_bar || !d_pos2_bar) return fail(RP_ERR_INVALID, "null output");
-    RP_NEED_STATE(b);
+    RP_NEED_F3_STATE(b, d_pos0_bar && d_pos1_bar && d_pos2_bar);
     RP_HIP(rp::launch_solution_vjp(b->view, b->params, d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar, b->stream));
     return RP_OK;
 }
@@ -797,33 +804,21 @@ int rp_batch_solution_vjp(rp_batch *b, const double *d_g_vel1, const double *d_g
 int rp_batch_solution_jvp(rp_batch *b, const double *d_t_pos0, const double *d_t_pos1, const double *d_t_pos2,
                           double *d_t_vel1, double *d_t_dur0, double *d_t_dur1)
 {
-    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
-        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_jvp: F3 with RP_DTYPE_F64 only");
-    if (!d_t_vel1 || !d_t_dur0 || !d_t_dur1) return fail(RP_ERR_INVALID, "null output");
-    RP_NEED_STATE(b);
+    RP_NEED_F3_STATE(b, d_t_vel1 && d_t_dur0 && d_t_dur1);
     RP_HIP(rp::launch_solution_jvp(b->view, b->params, d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel1, d_t_dur0, d_t_dur1, b->stream));
     return RP_OK;
 }
 
 int rp_batch_solution_jacobian(rp_batch *b, double *d_jac)
 {
-    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
-        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_jacobian: F3 with RP_DTYPE_F64 only");
-    if (!d_jac) return fail(RP_ERR_INVALID, "null output");
-    RP_NEED_STATE(b);
+    RP_NEED_F3_STATE(b, d_jac);
     RP_HIP(rp::launch_solution_jacobian(b->view, b->params, d_jac, b->stream));
     return RP_OK;
 }
 
 int rp_batch_solution_hessian(rp_batch *b, double *d_jac, double *d_hess)
 {
-    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
-        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_hessian: F3 with RP_DTYPE_F64 only");
-    if (!d_hess) return fail(RP_ERR_INVALID, "null output");
-    RP_NEED_STATE(b);
+    RP_NEED_F3_STATE(b, d_hess);
     RP_HIP(rp::launch_solution_hessian(b->view, b->params, d_jac, d_hess, b->stream));
     return RP_OK;
 }
@@ -831,11 +826,7 @@ int rp_batch_solution_hessian(rp_batch *b, double *d_jac, double *d_hess)
 int rp_batch_solution_vjp_vel(rp_batch *b, const double *d_g_vel1, const double *d_g_dur0, const double *d_g_dur1, double *d_pos0_bar,
                               double *d_pos1_bar, double *d_pos2_bar, double *d_vel0_bar, double *d_vel2_bar)
 {
-    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
-        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_vjp_vel: F3 with RP_DTYPE_F64 only");
-    if (!d_pos0_bar || !d_pos1_bar || !d_pos2_bar || !d_vel0_bar || !d_vel2_bar) return fail(RP_ERR_INVALID, "null output");
-    RP_NEED_STATE(b);
+    RP_NEED_F3_STATE(b, d_pos0_bar && d_pos1_bar && d_pos2_bar && d_vel0_bar && d_vel2_bar);
     RP_HIP(rp::launch_solution_vjp_vel(b->view, b->params, d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar, d_vel0_bar,
                                        d_vel2_bar, b->stream));
     return RP_OK;
@@ -844,11 +835,7 @@ int rp_batch_solution_vjp_vel(rp_batch *b, const double *d_g_vel1, const double 
 int rp_batch_solution_jvp_vel(rp_batch *b, const double *d_t_pos0, const double *d_t_pos1, const double *d_t_pos2, const double *d_t_vel0,
                               const double *d_t_vel2, double *d_t_vel1, double *d_t_dur0, double *d_t_dur1)
 {
-    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
-        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_jvp_vel: F3 with RP_DTYPE_F64 only");
-    if (!d_t_vel1 || !d_t_dur0 || !d_t_dur1) return fail(RP_ERR_INVALID, "null output");
-    RP_NEED_STATE(b);
+    RP_NEED_F3_STATE(b, d_t_vel1 && d_t_dur0 && d_t_dur1);
     RP_HIP(rp::launch_solution_jvp_vel(b->view, b->params, d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel0, d_t_vel2, d_t_vel1, d_t_dur0, d_t_dur1,
                                        b->stream));
     return RP_OK;
@@ -856,11 +843,7 @@ int rp_batch_solution_jvp_vel(rp_batch *b, const double *d_t_pos0, const double 
 
 int rp_batch_solution_jacobian_vel(rp_batch *b, double *d_jac)
 {
-    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    if (b->view.variant != RP_VARIANT_F3 || b->view.dtype != RP_DTYPE_F64)
-        return fail(RP_ERR_UNSUPPORTED, "rp_batch_solution_jacobian_vel: F3 with RP_DTYPE_F64 only");
-    if (!d_jac) return fail(RP_ERR_INVALID, "null output");
-    RP_NEED_STATE(b);
+    RP_NEED_F3_STATE(b, d_jac);
     RP_HIP(rp::launch_solution_jacobian_vel(b->view, b->params, d_jac, b->stream));
     return RP_OK;
 }

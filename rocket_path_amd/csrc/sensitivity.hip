@@ -1,6 +1,10 @@
-// sensitivity.hip -- derivatives of an F3 solution with respect to the positions, gfx950: the vector-Jacobian product
+// sensitivity.hip -- derivatives of an F3 solution, gfx950.  With respect to the positions: the vector-Jacobian product
 // (rp_batch_solution_vjp), the Jacobian-vector product (rp_batch_solution_jvp), the per-problem 3 x 3 Jacobian
-// (rp_batch_solution_jacobian) and the per-problem 3 x 3 x 3 Hessian (rp_batch_solution_hessian, see k_solution_hessian).
+// (rp_batch_solution_jacobian) and the per-problem 3 x 3 x 3 Hessian (rp_batch_solution_hessian, see k_solution_hessian).  First
+// derivatives in all five boundary inputs theta = (pos0, pos1, pos2, vel0, vel2): the vector-Jacobian product
+// (rp_batch_solution_vjp_vel), the Jacobian-vector product (rp_batch_solution_jvp_vel) and the per-problem 3 x 5 Jacobian
+// (rp_batch_solution_jacobian_vel).  Each first derivative is stated once, as a body templated on `Vel`; its two kernels
+// (k_solution_*, k_endvel_*) instantiate it, and what exists only with end velocities sits behind `if constexpr (Vel)`.
 //
 // For the state z = (x, lam), x = (vel1, duration0, duration1), the reference's residual r(z; theta, p) (onedpath_ip.cpp:753-783,
 // p held fixed) and M = dr/dz, the Newton matrix moveInteriorPoint assembles (onedpath_ip.cpp:814-861):
@@ -29,8 +33,19 @@
 // against a longdouble elimination of the full 11 x 11 system (tests/test_sensitivity_edges_cpu.py and the first-order CPU tests):
 // ~1e-14 normwise on the generators' problems, <= 5e-12 with non-zero end velocities.
 //
-// One lane per problem, walking batch positions like k_solution: 16 fields read coalesced, the per-problem inputs gathered at
-// prob_of[s], the results scattered there -- problem order in and out.
+// With end velocities (Vel): same z, r, p, M, condensed double-double K and NaN rule; the position parts run the arithmetic above
+// operation for operation.  The end velocities have the shape of the position deltas and enter only their
+// own segment's two accelerations, affinely (a_j = 6 sg_j dX / t^2 + w_j / t, w_j = -4 vel0 - 2 v, 2 vel0 + 4 v, -4 v - 2 vel2,
+// 2 v + 4 vel2; onedpath_ip.cpp:1025-1028):
+//     segment 0:  d a / d vel0 = (-4, +2) / t0,    d (d a / d t0) / d vel0 = (+4, -2) / t0^2
+//     segment 1:  d a / d vel2 = (-2, +4) / t1,    d (d a / d t1) / d vel2 = (+2, -4) / t1^2
+// and d (d a / d vel1) / d vel_end = 0, so a velocity direction adds to the durations' rows of b_x and to the pairs' alpha_j exactly
+// as a dX direction does, with these coefficients.  A state with a non-positive duration gets NaN besides those the position
+// derivatives give NaN for: with end velocities the reference's backtracking can step over t = 0, and there
+// the formula describes no trajectory.
+//
+// One lane per problem, walking batch positions like k_solution (load_lane): 16 fields read coalesced, the per-problem inputs
+// gathered at prob_of[s], the results scattered there -- problem order in and out.
 #include "ip_kernels.h"
 
 #include "../../include/rp_batch.h"
@@ -41,20 +56,18 @@ namespace rp {
 
 namespace {
 
-__global__ void __launch_bounds__(kVjpBlock)
-k_solution_vjp(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
-               const double *__restrict__ g_vel1, const double *__restrict__ g_dur0, const double *__restrict__ g_dur1,
-               double *__restrict__ pos0_bar, double *__restrict__ pos1_bar, double *__restrict__ pos2_bar)
+// theta_bar = J^T g.  Vel: also vel0_bar and vel2_bar (otherwise not read).
+template <bool Vel>
+__device__ __forceinline__ void solution_vjp(const double *base, size_t stride, size_t n, const uint32_t *prob_of, double limit,
+                                             const double *g_vel1, const double *g_dur0, const double *g_dur1, double *pos0_bar,
+                                             double *pos1_bar, double *pos2_bar, double *vel0_bar, double *vel2_bar)
 {
-    const size_t s = (size_t)blockIdx.x * kVjpBlock + threadIdx.x;
-    if (s >= n) return;
     double f[16];
-    load_fields(base, stride, s, f);
-    const size_t prob = prob_of ? (size_t)prob_of[s] : s;
+    size_t prob;
+    if (!load_lane(base, stride, n, prob_of, f, prob)) return;
 
     Condensed c;
-    const bool ok = condense(f, limit, c);
-    condense_K(c);
+    const bool ok = condense_with_K<Vel>(f, limit, c);
     ddv rhs[1][3] = {{dd_of(g_vel1 ? g_vel1[prob] : 0.0), dd_of(g_dur0 ? g_dur0[prob] : 0.0), dd_of(g_dur1 ? g_dur1[prob] : 0.0)}};
     ddv w[1][3];
     solve3_dd<1>(c.K, rhs, w);
@@ -67,28 +80,37 @@ k_solution_vjp(const double *__restrict__ base, size_t stride, size_t n, const u
     const double dx0_bar = -(12.0 * q0 * e.r0 * w[0][1].hi * (c.mu[1] - c.mu[0]) + 6.0 * q0 * (sj[0] - sj[1]));
     const double dx1_bar = -(12.0 * q1 * e.r1 * w[0][2].hi * (c.mu[3] - c.mu[2]) + 6.0 * q1 * (sj[2] - sj[3]));
     const double nan = __builtin_nan("");
+    double v0_bar, v2_bar;
+    if constexpr (Vel) {      // formed before the position outputs are stored, as k_endvel_vjp always has
+        v0_bar = -(q0 * w[0][1].hi * (4.0 * c.mu[0] - 2.0 * c.mu[1]) + e.r0 * (2.0 * sj[1] - 4.0 * sj[0]));
+        v2_bar = -(q1 * w[0][2].hi * (2.0 * c.mu[2] - 4.0 * c.mu[3]) + e.r1 * (4.0 * sj[3] - 2.0 * sj[2]));
+    }
     pos0_bar[prob] = ok ? -dx0_bar : nan;
     pos1_bar[prob] = ok ? dx0_bar - dx1_bar : nan;
     pos2_bar[prob] = ok ? dx1_bar : nan;
+    if constexpr (Vel) {
+        vel0_bar[prob] = ok ? v0_bar : nan;
+        vel2_bar[prob] = ok ? v2_bar : nan;
+    }
 }
 
-__global__ void __launch_bounds__(kVjpBlock)
-k_solution_jvp(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
-               const double *__restrict__ t_pos0, const double *__restrict__ t_pos1, const double *__restrict__ t_pos2,
-               double *__restrict__ t_vel1, double *__restrict__ t_dur0, double *__restrict__ t_dur1)
+// x_dot = J theta_dot.  Vel: with the tangents of vel0 and vel2 (otherwise not read).
+template <bool Vel>
+__device__ __forceinline__ void solution_jvp(const double *base, size_t stride, size_t n, const uint32_t *prob_of, double limit,
+                                             const double *t_pos0, const double *t_pos1, const double *t_pos2, const double *t_vel0,
+                                             const double *t_vel2, double *t_vel1, double *t_dur0, double *t_dur1)
 {
-    const size_t s = (size_t)blockIdx.x * kVjpBlock + threadIdx.x;
-    if (s >= n) return;
     double f[16];
-    load_fields(base, stride, s, f);
-    const size_t prob = prob_of ? (size_t)prob_of[s] : s;
+    size_t prob;
+    if (!load_lane(base, stride, n, prob_of, f, prob)) return;
     const double tp0 = t_pos0 ? t_pos0[prob] : 0.0, tp1 = t_pos1 ? t_pos1[prob] : 0.0, tp2 = t_pos2 ? t_pos2[prob] : 0.0;
+    const double tv0 = Vel && t_vel0 ? t_vel0[prob] : 0.0, tv2 = Vel && t_vel2 ? t_vel2[prob] : 0.0;
 
     Condensed c;
-    const bool ok = condense(f, limit, c);
-    condense_K(c);
+    const bool ok = condense_with_K<Vel>(f, limit, c);
     ddv rhs[1][3], xd[1][3];
-    forward_rhs(c, tp1 - tp0, tp2 - tp1, rhs[0]);      // equal tangents: dX tangents of exactly 0
+    // equal position tangents: dX tangents of exactly 0; zero velocity tangents: the right-hand side without Vel
+    forward_rhs<Vel>(c, tp1 - tp0, tp2 - tp1, tv0, tv2, rhs[0]);
     solve3_dd<1>(c.K, rhs, xd);
     const double nan = __builtin_nan("");
     t_vel1[prob] = ok ? xd[0][0].hi : nan;
@@ -96,30 +118,63 @@ k_solution_jvp(const double *__restrict__ base, size_t stride, size_t n, const u
     t_dur1[prob] = ok ? xd[0][2].hi : nan;
 }
 
-__global__ void __launch_bounds__(kVjpBlock)
-k_solution_jacobian(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
-                    double *__restrict__ jac)
+// Stores what direction k's solution x = dx / d(direction k) determines of a Jacobian whose rows are `ld` apart, NaN where the state
+// gets no formula.  Directions 0 and 1 are dX0 and dX1: columns pos0, pos1, pos2 through dX0 = pos1 - pos0, dX1 = pos2 - pos1, so x is
+// kept in d0 at k = 0 and column pos1 is stored at k = 1.  Directions 2 and 3 (vel0, vel2) are columns 3 and 4 as they are.
+template <int ld>
+__device__ __forceinline__ void store_direction(double *out, int k, const double (&x)[3], double (&d0)[3], bool ok)
 {
-    const size_t s = (size_t)blockIdx.x * kVjpBlock + threadIdx.x;
-    if (s >= n) return;
+    const double nan = __builtin_nan("");
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (k == 0) { d0[a] = x[a]; out[ld * a + 0] = ok ? -x[a] : nan; }
+        else if (k == 1) { out[ld * a + 1] = ok ? d0[a] - x[a] : nan; out[ld * a + 2] = ok ? x[a] : nan; }
+        else out[ld * a + k + 1] = ok ? x[a] : nan;
+    }
+}
+
+// J[a][b] = d x_a / d theta_b, row-major: 3 x 3 in the positions at jac[9 i + 3 a + b], or (Vel) 3 x 5 with b over (pos0, pos1, pos2,
+// vel0, vel2) at jac[15 i + 5 a + b].  The right-hand sides of the directions dX0, dX1 (and vel0, vel2) are formed first, so that
+// D_j h_j and mu_j are dead before the elimination.  The two eliminate K differently on purpose: two right-hand sides go through one
+// solve3_dd (96 VGPRs); for four, K is eliminated once (lu3_dd) and applied to them one at a time, the columns stored as soon as
+// they are known: 128 VGPRs (one solve3_dd on all four, or two pairs on copies of K: 134-140).
+template <bool Vel>
+__device__ __forceinline__ void solution_jacobian(const double *base, size_t stride, size_t n, const uint32_t *prob_of, double limit,
+                                                  double *jac)
+{
     double f[16];
-    load_fields(base, stride, s, f);
-    const size_t prob = prob_of ? (size_t)prob_of[s] : s;
+    size_t prob;
+    if (!load_lane(base, stride, n, prob_of, f, prob)) return;
 
     Condensed c;
-    const bool ok = condense(f, limit, c);
-    condense_K(c);
-    ddv rhs[2][3], d[2][3];      // d[0] = dx / d dX0, d[1] = dx / d dX1
-    forward_rhs(c, 1.0, 0.0, rhs[0]);
-    forward_rhs(c, 0.0, 1.0, rhs[1]);
-    solve3_dd<2>(c.K, rhs, d);
-    const double nan = __builtin_nan("");
-    double *out = jac + prob * 9;
+    const bool ok = condense_with_K<Vel>(f, limit, c);
+    constexpr int R = Vel ? 4 : 2, ld = Vel ? 5 : 3;
+    ddv rhs[R][3];      // rhs[0], rhs[1]: the directions dX0, dX1
+    forward_rhs<false>(c, 1.0, 0.0, 0.0, 0.0, rhs[0]);
+    forward_rhs<false>(c, 0.0, 1.0, 0.0, 0.0, rhs[1]);
+    double *out = jac + prob * (3 * ld);
+    double d0[3];      // dx / d dX0, until dx / d dX1 is known
+    if constexpr (Vel) {
+        forward_rhs<true>(c, 0.0, 0.0, 1.0, 0.0, rhs[2]);
+        forward_rhs<true>(c, 0.0, 0.0, 0.0, 1.0, rhs[3]);
+        rhs[2][2] = rhs[3][1] = dd_of(0.0);      // a velocity enters only its own segment's duration row (the kernel cannot know these are 0)
+        bool sw[3];
+        lu3_dd(c.K, sw);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {      // row a = x_a; columns pos0, pos1, pos2 through dX0 = pos1 - pos0, dX1 = pos2 - pos1
-        out[3 * a + 0] = ok ? -d[0][a].hi : nan;
-        out[3 * a + 1] = ok ? d[0][a].hi - d[1][a].hi : nan;
-        out[3 * a + 2] = ok ? d[1][a].hi : nan;
+        for (int k = 0; k < 4; ++k) {      // one right-hand side after the other; every column stored as soon as it is known
+            ddv X[3];
+            lu3_dd_solve(c.K, sw, rhs[k], X);
+            const double x[3] = {X[0].hi, X[1].hi, X[2].hi};
+            store_direction<ld>(out, k, x, d0, ok);
+        }
+    } else {
+        ddv d[2][3];      // d[0] = dx / d dX0, d[1] = dx / d dX1
+        solve3_dd<2>(c.K, rhs, d);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const double x[3] = {d[k][0].hi, d[k][1].hi, d[k][2].hi};
+            store_direction<ld>(out, k, x, d0, ok);
+        }
     }
 }
 
@@ -182,11 +237,9 @@ __global__ void __launch_bounds__(kVjpBlock)
 k_solution_hessian(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
                    double *__restrict__ jac, double *__restrict__ hess)
 {
-    const size_t s = (size_t)blockIdx.x * kVjpBlock + threadIdx.x;
-    if (s >= n) return;
     double f[16];
-    load_fields(base, stride, s, f);
-    const size_t prob = prob_of ? (size_t)prob_of[s] : s;
+    size_t prob;
+    if (!load_lane(base, stride, n, prob_of, f, prob)) return;
 
     Condensed c;
     const bool ok = condense(f, limit, c);
@@ -284,7 +337,7 @@ k_solution_hessian(const double *__restrict__ base, size_t stride, size_t n, con
     if (jac) {
         double *out = jac + prob * 9;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {      // rp_batch_solution_jacobian's layout
+        for (int a = 0; a < 3; ++a) {      // store_direction's columns, a row at a time (through it: one s_nop fewer, not the same code)
             out[3 * a + 0] = ok ? -Z[0][a] : nan;
             out[3 * a + 1] = ok ? Z[0][a] - Z[1][a] : nan;
             out[3 * a + 2] = ok ? Z[1][a] : nan;
@@ -307,46 +360,109 @@ k_solution_hessian(const double *__restrict__ base, size_t stride, size_t n, con
     }
 }
 
+// The first-order kernels: each body at its Vel, under the names and parameter lists the C ABI's entries launch.
+__global__ void __launch_bounds__(kVjpBlock)
+k_solution_vjp(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
+               const double *__restrict__ g_vel1, const double *__restrict__ g_dur0, const double *__restrict__ g_dur1,
+               double *__restrict__ pos0_bar, double *__restrict__ pos1_bar, double *__restrict__ pos2_bar)
+{
+    solution_vjp<false>(base, stride, n, prob_of, limit, g_vel1, g_dur0, g_dur1, pos0_bar, pos1_bar, pos2_bar, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(kVjpBlock)
+k_endvel_vjp(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
+             const double *__restrict__ g_vel1, const double *__restrict__ g_dur0, const double *__restrict__ g_dur1,
+             double *__restrict__ pos0_bar, double *__restrict__ pos1_bar, double *__restrict__ pos2_bar,
+             double *__restrict__ vel0_bar, double *__restrict__ vel2_bar)
+{
+    solution_vjp<true>(base, stride, n, prob_of, limit, g_vel1, g_dur0, g_dur1, pos0_bar, pos1_bar, pos2_bar, vel0_bar, vel2_bar);
+}
+
+__global__ void __launch_bounds__(kVjpBlock)
+k_solution_jvp(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
+               const double *__restrict__ t_pos0, const double *__restrict__ t_pos1, const double *__restrict__ t_pos2,
+               double *__restrict__ t_vel1, double *__restrict__ t_dur0, double *__restrict__ t_dur1)
+{
+    solution_jvp<false>(base, stride, n, prob_of, limit, t_pos0, t_pos1, t_pos2, nullptr, nullptr, t_vel1, t_dur0, t_dur1);
+}
+
+__global__ void __launch_bounds__(kVjpBlock)
+k_endvel_jvp(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
+             const double *__restrict__ t_pos0, const double *__restrict__ t_pos1, const double *__restrict__ t_pos2,
+             const double *__restrict__ t_vel0, const double *__restrict__ t_vel2,
+             double *__restrict__ t_vel1, double *__restrict__ t_dur0, double *__restrict__ t_dur1)
+{
+    solution_jvp<true>(base, stride, n, prob_of, limit, t_pos0, t_pos1, t_pos2, t_vel0, t_vel2, t_vel1, t_dur0, t_dur1);
+}
+
+__global__ void __launch_bounds__(kVjpBlock)
+k_solution_jacobian(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
+                    double *__restrict__ jac)
+{
+    solution_jacobian<false>(base, stride, n, prob_of, limit, jac);
+}
+
+__global__ void __launch_bounds__(kVjpBlock)
+k_endvel_jacobian(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of, double limit,
+                  double *__restrict__ jac)
+{
+    solution_jacobian<true>(base, stride, n, prob_of, limit, jac);
+}
+
+// One lane per batch position, on `stream`: the leading arguments every kernel here takes, then its own
+template <typename Kernel, typename... Args>
+hipError_t launch_per_problem(Kernel kernel, const BatchView &b, const HostParams &hp, hipStream_t stream, Args... args)
+{
+    if (b.n == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((b.n + kVjpBlock - 1) / kVjpBlock);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kVjpBlock), 0, stream, (const double *)b.base, b.stride, b.n,
+                       b.scheduled ? (const uint32_t *)b.prob_of : nullptr, hp.accel_limit, args...);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_solution_vjp(const BatchView &b, const HostParams &hp, const double *d_g_vel1, const double *d_g_dur0,
                                const double *d_g_dur1, double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar, hipStream_t stream)
 {
-    if (b.n == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((b.n + kVjpBlock - 1) / kVjpBlock);
-    hipLaunchKernelGGL(k_solution_vjp, dim3(blocks), dim3(kVjpBlock), 0, stream, (const double *)b.base, b.stride, b.n,
-                       b.scheduled ? (const uint32_t *)b.prob_of : nullptr, hp.accel_limit, d_g_vel1, d_g_dur0, d_g_dur1,
-                       d_pos0_bar, d_pos1_bar, d_pos2_bar);
-    return hipGetLastError();
+    return launch_per_problem(k_solution_vjp, b, hp, stream, d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar);
 }
 
 hipError_t launch_solution_jvp(const BatchView &b, const HostParams &hp, const double *d_t_pos0, const double *d_t_pos1,
                                const double *d_t_pos2, double *d_t_vel1, double *d_t_dur0, double *d_t_dur1, hipStream_t stream)
 {
-    if (b.n == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((b.n + kVjpBlock - 1) / kVjpBlock);
-    hipLaunchKernelGGL(k_solution_jvp, dim3(blocks), dim3(kVjpBlock), 0, stream, (const double *)b.base, b.stride, b.n,
-                       b.scheduled ? (const uint32_t *)b.prob_of : nullptr, hp.accel_limit, d_t_pos0, d_t_pos1, d_t_pos2,
-                       d_t_vel1, d_t_dur0, d_t_dur1);
-    return hipGetLastError();
+    return launch_per_problem(k_solution_jvp, b, hp, stream, d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel1, d_t_dur0, d_t_dur1);
 }
 
 hipError_t launch_solution_jacobian(const BatchView &b, const HostParams &hp, double *d_jac, hipStream_t stream)
 {
-    if (b.n == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((b.n + kVjpBlock - 1) / kVjpBlock);
-    hipLaunchKernelGGL(k_solution_jacobian, dim3(blocks), dim3(kVjpBlock), 0, stream, (const double *)b.base, b.stride, b.n,
-                       b.scheduled ? (const uint32_t *)b.prob_of : nullptr, hp.accel_limit, d_jac);
-    return hipGetLastError();
+    return launch_per_problem(k_solution_jacobian, b, hp, stream, d_jac);
 }
 
 hipError_t launch_solution_hessian(const BatchView &b, const HostParams &hp, double *d_jac, double *d_hess, hipStream_t stream)
 {
-    if (b.n == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((b.n + kVjpBlock - 1) / kVjpBlock);
-    hipLaunchKernelGGL(k_solution_hessian, dim3(blocks), dim3(kVjpBlock), 0, stream, (const double *)b.base, b.stride, b.n,
-                       b.scheduled ? (const uint32_t *)b.prob_of : nullptr, hp.accel_limit, d_jac, d_hess);
-    return hipGetLastError();
+    return launch_per_problem(k_solution_hessian, b, hp, stream, d_jac, d_hess);
+}
+
+hipError_t launch_solution_vjp_vel(const BatchView &b, const HostParams &hp, const double *d_g_vel1, const double *d_g_dur0,
+                                   const double *d_g_dur1, double *d_pos0_bar, double *d_pos1_bar, double *d_pos2_bar,
+                                   double *d_vel0_bar, double *d_vel2_bar, hipStream_t stream)
+{
+    return launch_per_problem(k_endvel_vjp, b, hp, stream, d_g_vel1, d_g_dur0, d_g_dur1, d_pos0_bar, d_pos1_bar, d_pos2_bar, d_vel0_bar,
+                              d_vel2_bar);
+}
+
+hipError_t launch_solution_jvp_vel(const BatchView &b, const HostParams &hp, const double *d_t_pos0, const double *d_t_pos1,
+                                   const double *d_t_pos2, const double *d_t_vel0, const double *d_t_vel2, double *d_t_vel1,
+                                   double *d_t_dur0, double *d_t_dur1, hipStream_t stream)
+{
+    return launch_per_problem(k_endvel_jvp, b, hp, stream, d_t_pos0, d_t_pos1, d_t_pos2, d_t_vel0, d_t_vel2, d_t_vel1, d_t_dur0,
+                              d_t_dur1);
+}
+
+hipError_t launch_solution_jacobian_vel(const BatchView &b, const HostParams &hp, double *d_jac, hipStream_t stream)
+{
+    return launch_per_problem(k_endvel_jacobian, b, hp, stream, d_jac);
 }
 
 }  // namespace rp

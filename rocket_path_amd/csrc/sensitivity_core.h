@@ -1,6 +1,6 @@
-// sensitivity_core.h -- the device code the F3 derivative kernels share (sensitivity.hip, sensitivity_vel.hip): double-double
-// arithmetic, the 3 x 3 double-double elimination, the condensed system at one state and the forward right-hand side of the
-// position directions.  The derivation is in sensitivity.hip's opening comment and DESIGN.md section 12.
+// sensitivity_core.h -- the building blocks of the F3 derivative kernels (sensitivity.hip): double-double arithmetic, the 3 x 3
+// double-double elimination (whole, and split into factor and apply), the condensed system at one state and the forward right-hand
+// side of the position and end-velocity directions.  The derivation is in sensitivity.hip's opening comment and DESIGN.md section 12.
 #pragma once
 
 #include "ip_core.h"
@@ -113,6 +113,58 @@ __device__ __forceinline__ void solve3_dd(ddv (&A)[3][3], ddv (&B)[R][3], ddv (&
     }
 }
 
+// solve3_dd split in two: lu3_dd runs its elimination on K once, keeping the row swaps and the multipliers f (in A's lower part), and
+// lu3_dd_solve applies them to one right-hand side -- the same swaps, updates and back substitution, operation for operation, as
+// solve3_dd gives that right-hand side (its updates of B read only B, the swaps and f), so the results are solve3_dd's bit for bit.  For
+// the Jacobian's four directions: one elimination of K, and one right-hand side live at a time.
+__device__ __forceinline__ void lu3_dd(ddv (&A)[3][3], bool (&sw)[3])
+{
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+#pragma unroll
+        for (int r = k + 1; r < 3; ++r) {
+            const bool w = __builtin_fabs(A[r][k].hi) > __builtin_fabs(A[k][k].hi);
+            sw[k + r - 1] = w;      // (k, r) = (0, 1), (0, 2), (1, 2) -> 0, 1, 2
+#pragma unroll
+            for (int c = k; c < 3; ++c) {
+                const ddv a = A[k][c], o = A[r][c];
+                A[k][c] = w ? o : a;
+                A[r][c] = w ? a : o;
+            }
+        }
+#pragma unroll
+        for (int r = k + 1; r < 3; ++r) {
+            const ddv f = dd_div(A[r][k], A[k][k]);
+#pragma unroll
+            for (int c = k + 1; c < 3; ++c) A[r][c] = dd_sub(A[r][c], dd_mul(f, A[k][c]));
+            A[r][k] = f;
+        }
+    }
+}
+
+__device__ __forceinline__ void lu3_dd_solve(const ddv (&A)[3][3], const bool (&sw)[3], ddv (&B)[3], ddv (&X)[3])
+{
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+#pragma unroll
+        for (int r = k + 1; r < 3; ++r) {
+            const bool w = sw[k + r - 1];
+            const ddv a = B[k], o = B[r];
+            B[k] = w ? o : a;
+            B[r] = w ? a : o;
+        }
+#pragma unroll
+        for (int r = k + 1; r < 3; ++r) B[r] = dd_sub(B[r], dd_mul(A[r][k], B[k]));
+    }
+#pragma unroll
+    for (int k = 2; k >= 0; --k) {
+        ddv acc = B[k];
+#pragma unroll
+        for (int c = k + 1; c < 3; ++c) acc = dd_sub(acc, dd_mul(A[k][c], X[c]));
+        X[k] = dd_div(acc, A[k][k]);
+    }
+}
+
 // The condensed system at one state (the 16 fields of a lane): the pair weights D_j and mu_j, h_j = (gv_j, e.gt_j), the exact
 // products D_j h_j and K = W + S_j D_j h_j h_j^T in double-double (condense_K); returns whether the state gets the formula or NaN.
 struct Condensed {
@@ -188,25 +240,50 @@ __device__ __forceinline__ void condense_K(Condensed &c)
     K[1][2] = K[2][1] = dd_of(0.0);
 }
 
-__device__ __forceinline__ void load_fields(const double *__restrict__ base, size_t stride, size_t s, double (&f)[16])
+// Both for a first-order kernel.  Vel: the derivatives with end velocities give NaN for a non-positive duration besides.
+template <bool Vel>
+__device__ __forceinline__ bool condense_with_K(const double (&f)[16], double limit, Condensed &c)
 {
+    bool ok = condense(f, limit, c);
+    if constexpr (Vel) ok = ok && f[1] > 0.0 && f[2] > 0.0;
+    condense_K(c);
+    return ok;
+}
+
+// One lane per problem, walking batch positions: the lane's 16 fields, read coalesced, and the problem at its position, where its
+// inputs are gathered and its results scattered.  False for the lanes past the end of the batch.
+__device__ __forceinline__ bool load_lane(const double *__restrict__ base, size_t stride, size_t n, const uint32_t *__restrict__ prob_of,
+                                          double (&f)[16], size_t &prob)
+{
+    const size_t s = (size_t)blockIdx.x * kVjpBlock + threadIdx.x;
+    if (s >= n) return false;
 #pragma unroll
     for (int i = 0; i < 16; ++i) f[i] = __builtin_nontemporal_load(base + (size_t)i * stride + s);
+    prob = prob_of ? (size_t)prob_of[s] : s;
+    return true;
 }
 
 // The condensed forward right-hand side -b_x - S_j D_j alpha_j h_j for position-delta tangents (dd0, dd1) = (dX0_dot, dX1_dot),
 // in double-double from the exact D_j h_j: alpha_j = +-6 dd / t^2 (the tangent of a_j), and b_x = S_j mu_j beta_j with
-// beta_j = -+12 dd / t^3 in the durations' rows.
-__device__ __forceinline__ void forward_rhs(const Condensed &c, double dd0, double dd1, ddv (&rhs)[3])
+// beta_j = -+12 dd / t^3 in the durations' rows.  Vel: of all five tangents, the end-velocity tangents (e0, e2) = (vel0_dot, vel2_dot)
+// added to alpha_j and b_x before the double-double products:
+//     alpha_j += (-4 e0, 2 e0) / t0, (-2 e2, 4 e2) / t1,    b_x += (0, (4 mu_0 - 2 mu_1) e0 / t0^2, (2 mu_2 - 4 mu_3) e2 / t1^2).
+// With e0 = e2 = 0 the additions are of zeros, the values those without Vel bit for bit; without Vel the terms are not formed at all.
+template <bool Vel>
+__device__ __forceinline__ void forward_rhs(const Condensed &c, double dd0, double dd1, double e0, double e2, ddv (&rhs)[3])
 {
     const Acc<double> &e = c.e;
     const double q0 = e.r0 * e.r0, q1 = e.r1 * e.r1;
-    const double al[4] = {6.0 * q0 * dd0, -(6.0 * q0 * dd0), 6.0 * q1 * dd1, -(6.0 * q1 * dd1)};
+    const double a0 = 6.0 * q0 * dd0, a1 = 6.0 * q1 * dd1;
+    const double al[4] = {Vel ? a0 + -4.0 * e.r0 * e0 : a0, Vel ? -a0 + 2.0 * e.r0 * e0 : -a0,
+                          Vel ? a1 + -2.0 * e.r1 * e2 : a1, Vel ? -a1 + 4.0 * e.r1 * e2 : -a1};
     rhs[0] = dd_neg(dd_add(dd_add(dd_mul_d(c.Dgv[0], al[0]), dd_mul_d(c.Dgv[1], al[1])),
                            dd_add(dd_mul_d(c.Dgv[2], al[2]), dd_mul_d(c.Dgv[3], al[3]))));
-    rhs[1] = dd_neg(dd_add(dd_of(12.0 * q0 * e.r0 * dd0 * (c.mu[1] - c.mu[0])),
+    const double b0 = 12.0 * q0 * e.r0 * dd0 * (c.mu[1] - c.mu[0]);
+    rhs[1] = dd_neg(dd_add(dd_of(Vel ? b0 + q0 * e0 * (4.0 * c.mu[0] - 2.0 * c.mu[1]) : b0),
                            dd_add(dd_mul_d(c.Dgt[0], al[0]), dd_mul_d(c.Dgt[1], al[1]))));
-    rhs[2] = dd_neg(dd_add(dd_of(12.0 * q1 * e.r1 * dd1 * (c.mu[3] - c.mu[2])),
+    const double b1 = 12.0 * q1 * e.r1 * dd1 * (c.mu[3] - c.mu[2]);
+    rhs[2] = dd_neg(dd_add(dd_of(Vel ? b1 + q1 * e2 * (2.0 * c.mu[2] - 4.0 * c.mu[3]) : b1),
                            dd_add(dd_mul_d(c.Dgt[2], al[2]), dd_mul_d(c.Dgt[3], al[3]))));
 }
 

@@ -6,7 +6,7 @@ start_state restates the start rule in numpy.  For theta = (pos0, pos1, pos2, ve
                     velocity columns (d a / d vel0 = (-4, 2) / t0, d (d a / d t0) / d vel0 = (4, -2) / t0^2; vel2: (-2, 4) / t1 and
                     (2, -4) / t1^2), checked against central differences of residual_ld by the CPU tests
     full_jacobian5  J = -M^-1 dr/dtheta (n, 3, 5) on the full 11 x 11 system in longdouble (M = kkt_ld)
-    condensed_*5    the kernels' condensed double-double arithmetic (csrc/sensitivity_vel.hip) restated with the helpers of
+    condensed_*5    the kernels' condensed double-double arithmetic (csrc/sensitivity.hip, the k_endvel_* kernels) restated with the helpers of
                     tests/sensitivity_jvp_ref.py
 """
 import numpy as np
@@ -78,7 +78,7 @@ def full_jacobian5(states, limit=L_DEFAULT):
 
 
 def _rhs5_dd(c, dd0, dd1, e0, e2):
-    """forward_rhs5 of csrc/sensitivity_vel.hip in double-double."""
+    """forward_rhs<true> of csrc/sensitivity_core.h in double-double."""
     r0, r1 = c["r0"], c["r1"]
     q0, q1 = r0 ** 2, r1 ** 2
     al = [6 * q0 * dd0 + -4.0 * r0 * e0, -(6 * q0 * dd0) + 2.0 * r0 * e0, 6 * q1 * dd1 + -2.0 * r1 * e2, -(6 * q1 * dd1) + 4.0 * r1 * e2]

@@ -1,34 +1,14 @@
 """Register / scratch budget of the forward-mode sensitivity kernels (k_solution_jvp, k_solution_jacobian in
 csrc/sensitivity.hip), checked at compile time like tests/test_sensitivity_resources.py: no scratch, no spills, 128 VGPRs or fewer."""
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import kernel_usage
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+@pytest.mark.skipif(not os.path.exists(kernel_usage.HIPCC), reason="no hipcc")
 def test_jvp_and_jacobian_kernels_have_no_scratch():
-    src = os.path.join(ROOT, "rocket_path_amd", "csrc", "sensitivity.hip")
-    r = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull, src],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
     for kernel in ("k_solution_jvp", "k_solution_jacobian"):
-        found = {k: v for k, v in usage.items() if kernel in k}
-        assert len(found) == 1, (kernel, sorted(usage))
-        for k, v in found.items():
-            assert v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["VGPRs"] <= 128, (k, v)
+        k, v = kernel_usage.only("sensitivity.hip", kernel)
+        assert v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["VGPRs"] <= 128, (k, v)
