@@ -51,7 +51,8 @@ struct HostParams {
     int stall_window;
     int mu_mode;                 // 0 = reference centring, 1 = centring by trial (ip_core.h, newton_step)
     double mu_sigma_try[2];      // the two candidates of mode 1
-    int handoff_rounds;          // rp_params.handoff_rounds: 0 = automatic, -1 = never, 2..8 = always that many rounds
+    int handoff_rounds;          // rp_params.handoff_rounds: 0 = a batch whose order predicts nothing runs the kernel that watches for fixed points, in ONE
+                                 // launch; -1 = the plain kernel always; 2..8 = the watching kernel in that many rounds
     int handoff_lanes;           // rp_params.handoff_lanes
 };
 

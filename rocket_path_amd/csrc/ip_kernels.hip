@@ -31,6 +31,7 @@
 #include "ip_kernels.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "../../include/rp_batch.h"
 #include "feas_core.h"
@@ -1364,52 +1365,52 @@ k_constraint_table(const S *__restrict__ base, size_t stride, size_t first, size
 
 inline unsigned grid_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
-// dispatch on (dtype, variant): S = storage type in HBM, T = arithmetic type in registers
-//   RP_DTYPE_F64        double / double
-//   RP_DTYPE_F32        float  / float
-//   RP_DTYPE_F32_STATE  float  / double   (fp32 state and traffic, fp64 arithmetic)
-#define RP_DISPATCH_V(b, ...)                                             \
-    do {                                                                  \
-        if ((b).variant == 3) { constexpr int V = 3; __VA_ARGS__; }       \
-        else                  { constexpr int V = 4; __VA_ARGS__; }       \
-    } while (0)
-#define RP_DISPATCH(b, ...)                                                                              \
-    do {                                                                                                 \
-        if ((b).dtype == 0)      { using S [[maybe_unused]] = double; using T [[maybe_unused]] = double; RP_DISPATCH_V(b, __VA_ARGS__); } \
-        else if ((b).dtype == 1) { using S [[maybe_unused]] = float;  using T [[maybe_unused]] = float;  RP_DISPATCH_V(b, __VA_ARGS__); } \
-        else                     { using S [[maybe_unused]] = float;  using T [[maybe_unused]] = double; RP_DISPATCH_V(b, __VA_ARGS__); } \
-    } while (0)
+// ---- the one dispatch: run-time properties of a batch -> compile-time constants of a kernel instantiation ----
+// A launcher names the AXES its kernel is instantiated on and gets, inside RP_DISPATCH's statement,
+//   S     storage type in HBM: double (RP_DTYPE_F64) or float (RP_DTYPE_F32, RP_DTYPE_F32_STATE)                       always
+//   T     arithmetic type in registers    kArith: double / float / double for the three dtypes
+//                                         kDoubleArith: double whatever the dtype (mu_mode 1; rp_batch_set_params refuses it for pure fp32)
+//                                         neither: S
+//   V, M  variant and its row length      kVariant: 3, 16 or 4, 12; otherwise 3, 16
+//   Z     BatchView::zero_end_vel         kZeroVel: as the batch says; otherwise true
+// An axis that is not named is not branched on: a kernel is instantiated for the combinations its launchers can reach and no others
+// (no MU = 1 in float arithmetic, the transposes on S and M only, k_solution / k_init_const / k_nudge / k_sample_records on S only).
+enum : unsigned { kStorage = 0, kArith = 1, kDoubleArith = 2, kVariant = 4, kZeroVel = 8 };
 
-// dispatch on the dtype alone (S, T)
-#define RP_DISPATCH_ST(b, ...)                                                                           \
-    do {                                                                                                 \
-        if ((b).dtype == 0)      { using S [[maybe_unused]] = double; using T [[maybe_unused]] = double; __VA_ARGS__; } \
-        else if ((b).dtype == 1) { using S [[maybe_unused]] = float;  using T [[maybe_unused]] = float;  __VA_ARGS__; } \
-        else                     { using S [[maybe_unused]] = float;  using T [[maybe_unused]] = double; __VA_ARGS__; } \
-    } while (0)
+template <typename S_, typename T_, int V_, bool Z_> struct Tag {
+    using S = S_;
+    using T = T_;
+    static constexpr int V = V_, M = V_ == 4 ? 12 : 16;      // M: state_len(V)
+    static constexpr bool Z = Z_;
+};
+
+template <unsigned AXES, typename F> void dispatch(const BatchView &b, F f)
+{
+    auto on_zero_vel = [&](auto s, auto t, auto v) {
+        constexpr int V = decltype(v)::value;
+        if constexpr ((AXES & kZeroVel) != 0) { if (!b.zero_end_vel) return f(Tag<decltype(s), decltype(t), V, false>{}); }
+        f(Tag<decltype(s), decltype(t), V, true>{});
+    };
+    auto on_variant = [&](auto s, auto t) {
+        if constexpr ((AXES & kVariant) != 0) { if (b.variant != 3) return on_zero_vel(s, t, std::integral_constant<int, 4>{}); }
+        on_zero_vel(s, t, std::integral_constant<int, 3>{});
+    };
+    if (b.dtype == 0) on_variant(double{}, double{});
+    else if constexpr ((AXES & kDoubleArith) != 0) on_variant(float{}, double{});
+    else if constexpr ((AXES & kArith) != 0) { if (b.dtype == 1) on_variant(float{}, float{}); else on_variant(float{}, double{}); }
+    else on_variant(float{}, float{});
+}
+
+#define RP_DISPATCH(AXES, b, ...)                                         \
+    dispatch<(AXES)>((b), [&](auto tag_) {                                \
+        using S [[maybe_unused]] = typename decltype(tag_)::S;            \
+        using T [[maybe_unused]] = typename decltype(tag_)::T;            \
+        [[maybe_unused]] constexpr int V = decltype(tag_)::V, M = decltype(tag_)::M; \
+        [[maybe_unused]] constexpr bool Z = decltype(tag_)::Z;            \
+        __VA_ARGS__;                                                      \
+    })
 
 }  // namespace
-
-// the three Newton kernels are also instantiated for "end velocities are zero" (BatchView::zero_end_vel)
-#define RP_DISPATCH_Z(b, ...)                                             \
-    do {                                                                  \
-        if ((b).zero_end_vel) { constexpr bool Z = true; RP_DISPATCH(b, __VA_ARGS__); }   \
-        else                  { constexpr bool Z = false; RP_DISPATCH(b, __VA_ARGS__); }  \
-    } while (0)
-
-// mu_mode 1 (centring by trial) exists for double arithmetic (dtypes f64 and f32-state) in the one-problem-per-lane
-// kernels; rp_batch_set_params refuses it for pure fp32.
-#define RP_DISPATCH_MU1(b, ...)                                                                          \
-    do {                                                                                                 \
-        using T [[maybe_unused]] = double;                                                               \
-        if ((b).dtype == 0) { using S [[maybe_unused]] = double; RP_DISPATCH_V(b, __VA_ARGS__); }          \
-        else                { using S [[maybe_unused]] = float;  RP_DISPATCH_V(b, __VA_ARGS__); }          \
-    } while (0)
-#define RP_DISPATCH_MU1_Z(b, ...)                                         \
-    do {                                                                  \
-        if ((b).zero_end_vel) { constexpr bool Z = true; RP_DISPATCH_MU1(b, __VA_ARGS__); }   \
-        else                  { constexpr bool Z = false; RP_DISPATCH_MU1(b, __VA_ARGS__); }  \
-    } while (0)
 
 hipError_t launch_steps(const BatchView &b, const HostParams &hp, int k, hipStream_t stream)
 {
@@ -1417,8 +1418,8 @@ hipError_t launch_steps(const BatchView &b, const HostParams &hp, int k, hipStre
     if (hp.mu_mode == 1) {
         unsigned grid = grid_for(b.n);
         if (grid > 2048u) grid = 2048u;
-        RP_DISPATCH_MU1_Z(b, hipLaunchKernelGGL((k_newton_stream<S, T, V, Z, 1>), dim3(grid), dim3(kBlock), 0, stream,
-                                                 (S *)b.base, b.stride, b.n, k, make_kparams<T>(hp, V)));
+        RP_DISPATCH(kDoubleArith | kVariant | kZeroVel, b, hipLaunchKernelGGL((k_newton_stream<S, T, V, Z, 1>), dim3(grid), dim3(kBlock), 0, stream,
+                                                                               (S *)b.base, b.stride, b.n, k, make_kparams<T>(hp, V)));
         return hipGetLastError();
     }
     // k = 1 is memory-bound (200 B per problem cross HBM for one step's arithmetic): the 16-byte streaming kernel.  From k = 2 on
@@ -1444,7 +1445,6 @@ hipError_t launch_steps(const BatchView &b, const HostParams &hp, int k, hipStre
         constexpr size_t reg_column_upto = (size_t)3 * 1024 * 64;
 #endif
         if (b.variant == 3 && b.n <= reg_column_upto) {
-            constexpr int V3 = 3;
 #ifdef RP_TUNING
             static const unsigned lanes_env = getenv("RP_LANES_PER_WAVE") ? (unsigned)atoi(getenv("RP_LANES_PER_WAVE")) : 64u;      // A/B: part-filled waves
             if (lanes_env < 1u || lanes_env > 64u) return hipErrorInvalidValue;      // (0 would divide by zero below, > 64 would leave problems unprocessed: ADVICE r5)
@@ -1453,12 +1453,12 @@ hipError_t launch_steps(const BatchView &b, const HostParams &hp, int k, hipStre
             constexpr unsigned lanes = 64u;
 #endif
             const dim3 grid((unsigned)((b.n + lanes - 1) / lanes));
-            if (b.zero_end_vel) { constexpr bool Z = true;  RP_DISPATCH_ST(b, hipLaunchKernelGGL((k_steps_chunks<S, T, V3, Z, true>), grid, dim3(kChunkBlock), 0, stream, (S *)b.base, b.stride, b.n, k, make_kparams<T>(hp, V3), lanes)); }
-            else                { constexpr bool Z = false; RP_DISPATCH_ST(b, hipLaunchKernelGGL((k_steps_chunks<S, T, V3, Z, true>), grid, dim3(kChunkBlock), 0, stream, (S *)b.base, b.stride, b.n, k, make_kparams<T>(hp, V3), lanes)); }
+            RP_DISPATCH(kArith | kZeroVel, b, hipLaunchKernelGGL((k_steps_chunks<S, T, V, Z, true>), grid, dim3(kChunkBlock), 0, stream,      // (V = 3: not an axis here)
+                                                                  (S *)b.base, b.stride, b.n, k, make_kparams<T>(hp, V), lanes));
             return hipGetLastError();
         }
-        RP_DISPATCH_Z(b, hipLaunchKernelGGL((k_steps_chunks<S, T, V, Z>), dim3((unsigned)((b.n + 63) / 64)), dim3(kChunkBlock), 0, stream,
-                                             (S *)b.base, b.stride, b.n, k, make_kparams<T>(hp, V), 64u));
+        RP_DISPATCH(kArith | kVariant | kZeroVel, b, hipLaunchKernelGGL((k_steps_chunks<S, T, V, Z>), dim3((unsigned)((b.n + 63) / 64)), dim3(kChunkBlock), 0, stream,
+                                                                         (S *)b.base, b.stride, b.n, k, make_kparams<T>(hp, V), 64u));
         return hipGetLastError();
     }
     // k = 1: memory-bound.  Full blocks of 256 lanes x 16 B go through k_newton_stream16; the ragged remainder (and, in a
@@ -1466,8 +1466,8 @@ hipError_t launch_steps(const BatchView &b, const HostParams &hp, int k, hipStre
     const size_t per_block = (size_t)kBlock * (b.dtype == 1 ? 4 : 2);      // problems per lane: Vec16<S, T>::PER
     const size_t nfull = (scalar_only || grid_env || k > 2) ? 0 : b.n / per_block * per_block;      // (k > 2 only under RP_STREAM_GRID)
     if (nfull > 0)
-        RP_DISPATCH_Z(b, hipLaunchKernelGGL((k_newton_stream16<S, T, V, Z>), dim3((unsigned)(nfull / per_block)), dim3(kBlock), 0, stream,
-                                             (S *)b.base, b.stride, k, make_kparams<T>(hp, V)));
+        RP_DISPATCH(kArith | kVariant | kZeroVel, b, hipLaunchKernelGGL((k_newton_stream16<S, T, V, Z>), dim3((unsigned)(nfull / per_block)), dim3(kBlock), 0, stream,
+                                                                         (S *)b.base, b.stride, k, make_kparams<T>(hp, V)));
     if (nfull < b.n) {
         BatchView w = b;
         w.base = (char *)b.base + nfull * storage_size(b.dtype);
@@ -1475,23 +1475,38 @@ hipError_t launch_steps(const BatchView &b, const HostParams &hp, int k, hipStre
         const unsigned cap = grid_env ? (unsigned)atoi(grid_env) : 512u;
         unsigned grid = grid_for(w.n);
         if (grid > cap) grid = cap;
-        RP_DISPATCH_Z(w, hipLaunchKernelGGL((k_newton_stream<S, T, V, Z>), dim3(grid), dim3(kBlock), 0, stream,
-                                             (S *)w.base, w.stride, w.n, k, make_kparams<T>(hp, V)));
+        RP_DISPATCH(kArith | kVariant | kZeroVel, w, hipLaunchKernelGGL((k_newton_stream<S, T, V, Z>), dim3(grid), dim3(kBlock), 0, stream,
+                                                                         (S *)w.base, w.stride, w.n, k, make_kparams<T>(hp, V)));
     }
     return hipGetLastError();
 }
 
 hipError_t launch_steps_counted(const BatchView &b, const HostParams &hp, int k, uint32_t *d_nfeas, uint32_t *d_nresid, hipStream_t stream)
 {
-    RP_DISPATCH(b, hipLaunchKernelGGL((k_newton_counted<S, T, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
-                                       (S *)b.base, b.stride, b.n, k, make_kparams<T>(hp, V), d_nfeas, d_nresid));
+    RP_DISPATCH(kArith | kVariant, b, hipLaunchKernelGGL((k_newton_counted<S, T, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                          (S *)b.base, b.stride, b.n, k, make_kparams<T>(hp, V), d_nfeas, d_nresid));
     return hipGetLastError();
+}
+
+// One launch of the gated kernel, one 64-problem chunk (or 64 list entries) per single-wave block: the argument list every form of it shares.
+// The hand-off parameters and the four lists belong to the ROUNDS form; the others leave them at the kernel's own defaults.
+template <typename S, typename T, int V, bool STALL, bool Z, int MU, bool START, bool ROUNDS>
+static void launch_gated(const BatchView &b, const HostParams &hp, unsigned waves, unsigned lds, int k, double gap_tol, int max_iter, hipStream_t stream,
+                         int handoff_lanes = 0, int handoff_patience = 0, const uint32_t *list_in = nullptr, const uint32_t *list_count = nullptr,
+                         uint32_t *list_out = nullptr, uint32_t *list_out_count = nullptr)
+{
+    KParams<T> kp = make_kparams<T>(hp, V);
+    kp.handoff_lanes = handoff_lanes;
+    kp.handoff_patience = handoff_patience;
+    hipLaunchKernelGGL((k_solve_chunks<S, T, V, STALL, Z, MU, START, ROUNDS>), dim3(waves), dim3(64), lds, stream, (S *)b.base, b.stride, b.n, k, kp,
+                       (T)gap_tol, max_iter, b.iters, b.status, b.counters, b.records, b.prob_of, hp.accel_limit, b.solution,
+                       b.scheduled ? (const uint32_t *)b.prob_of : nullptr, b.iters_add, list_in, list_count, list_out, list_out_count);
 }
 
 // the gated solve: up to k gated steps per problem, one 64-problem chunk of the scheduled order per single-wave block
 static hipError_t launch_chunks(const BatchView &b, const HostParams &hp, int k, double gap_tol, int max_iter, bool from_start, hipStream_t stream)
 {
-    const dim3 grid((unsigned)((b.n + 63) / 64)), block(64);
+    const unsigned waves = (unsigned)((b.n + 63) / 64);
 #ifdef RP_TUNING
     // tuning builds only: dynamic LDS per block, to cap the waves per SIMD -- passed to whichever instantiation the batch selects
     static const unsigned lds_pad = getenv("RP_GATED_LDS_PAD") ? (unsigned)atoi(getenv("RP_GATED_LDS_PAD")) : 0u;
@@ -1500,17 +1515,13 @@ static hipError_t launch_chunks(const BatchView &b, const HostParams &hp, int k,
 #endif
     if (from_start) {      // reference mode, no stall detector, zero end velocities: rp_batch.cpp only asks for this form then
         if (hp.mu_mode != 0 || hp.stall_window > 0 || !b.zero_end_vel || !b.records) return hipErrorInvalidValue;
-        RP_DISPATCH(b, hipLaunchKernelGGL((k_solve_chunks<S, T, V, false, true, 0, true>), grid, block, lds_pad, stream, (S *)b.base, b.stride, b.n, k,
-                                           make_kparams<T>(hp, V), (T)gap_tol, max_iter, b.iters, b.status, b.counters, b.records, b.prob_of, hp.accel_limit, b.solution, b.scheduled ? (const uint32_t *)b.prob_of : nullptr, b.iters_add));
+        RP_DISPATCH(kArith | kVariant, b, launch_gated<S, T, V, false, true, 0, true, false>(b, hp, waves, lds_pad, k, gap_tol, max_iter, stream));
     } else if (hp.mu_mode == 1)
-        RP_DISPATCH_MU1_Z(b, hipLaunchKernelGGL((k_solve_chunks<S, T, V, true, Z, 1>), grid, block, lds_pad, stream, (S *)b.base, b.stride, b.n, k,
-                                                 make_kparams<T>(hp, V), (T)gap_tol, max_iter, b.iters, b.status, b.counters, b.records, b.prob_of, hp.accel_limit, b.solution, b.scheduled ? (const uint32_t *)b.prob_of : nullptr, b.iters_add));
+        RP_DISPATCH(kDoubleArith | kVariant | kZeroVel, b, launch_gated<S, T, V, true, Z, 1, false, false>(b, hp, waves, lds_pad, k, gap_tol, max_iter, stream));
     else if (hp.stall_window > 0)
-        RP_DISPATCH_Z(b, hipLaunchKernelGGL((k_solve_chunks<S, T, V, true, Z>), grid, block, lds_pad, stream, (S *)b.base, b.stride, b.n, k,
-                                             make_kparams<T>(hp, V), (T)gap_tol, max_iter, b.iters, b.status, b.counters, b.records, b.prob_of, hp.accel_limit, b.solution, b.scheduled ? (const uint32_t *)b.prob_of : nullptr, b.iters_add));
+        RP_DISPATCH(kArith | kVariant | kZeroVel, b, launch_gated<S, T, V, true, Z, 0, false, false>(b, hp, waves, lds_pad, k, gap_tol, max_iter, stream));
     else
-        RP_DISPATCH_Z(b, hipLaunchKernelGGL((k_solve_chunks<S, T, V, false, Z>), grid, block, lds_pad, stream, (S *)b.base, b.stride, b.n, k,
-                                             make_kparams<T>(hp, V), (T)gap_tol, max_iter, b.iters, b.status, b.counters, b.records, b.prob_of, hp.accel_limit, b.solution, b.scheduled ? (const uint32_t *)b.prob_of : nullptr, b.iters_add));
+        RP_DISPATCH(kArith | kVariant | kZeroVel, b, launch_gated<S, T, V, false, Z, 0, false, false>(b, hp, waves, lds_pad, k, gap_tol, max_iter, stream));
     return hipGetLastError();
 }
 
@@ -1534,14 +1545,8 @@ hipError_t launch_solve_rounds(const BatchView &b, const HostParams &hp, double 
         const unsigned waves = (unsigned)((bound + 63) / 64);
         const uint32_t *in = r == 0 ? nullptr : list[(r - 1) & 1], *in_count = r == 0 ? nullptr : counts + (r - 1);
         uint32_t *out = last ? nullptr : list[r & 1], *out_count = last ? nullptr : counts + r;
-        RP_DISPATCH_Z(b, {
-            KParams<T> kp = make_kparams<T>(hp, V);
-            kp.handoff_lanes = last ? 0 : lanes;
-            kp.handoff_patience = patience;
-            hipLaunchKernelGGL((k_solve_chunks<S, T, V, false, Z, 0, false, true>), dim3(waves), dim3(64), 0, stream, (S *)b.base, b.stride, b.n, max_iter,
-                               kp, (T)gap_tol, max_iter, b.iters, b.status, b.counters, b.records, b.prob_of, hp.accel_limit, b.solution,
-                               b.scheduled ? (const uint32_t *)b.prob_of : nullptr, b.iters_add, in, in_count, out, out_count);
-        });
+        RP_DISPATCH(kArith | kVariant | kZeroVel, b, launch_gated<S, T, V, false, Z, 0, false, true>(b, hp, waves, 0, max_iter, gap_tol, max_iter, stream,
+                                                                                                     last ? 0 : lanes, patience, in, in_count, out, out_count));
         e = hipGetLastError();
         if (e != hipSuccess) return e;
         bound = (size_t)waves * (size_t)lanes;      // every wave hands off at most `lanes` of its lanes
@@ -1569,104 +1574,79 @@ hipError_t launch_reduce(const BatchView &b, const HostParams &hp, double host_s
 {
     unsigned blocks = grid_for(b.n);
     if (blocks > 1024) blocks = 1024;
-    RP_DISPATCH(b, hipLaunchKernelGGL((k_reduce_partial<S, T, V>), dim3(blocks), dim3(kBlock), 0, stream,
-                                       (const S *)b.base, b.stride, b.n, make_kparams<T>(hp, V), b.status, d_partials));
+    RP_DISPATCH(kArith | kVariant, b, hipLaunchKernelGGL((k_reduce_partial<S, T, V>), dim3(blocks), dim3(kBlock), 0, stream,
+                                                          (const S *)b.base, b.stride, b.n, make_kparams<T>(hp, V), b.status, d_partials));
     hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(64), 0, stream, d_partials, (int)blocks, b.counters, host_steps, d_out4);
     return hipGetLastError();
 }
 
+// where the problems lie, for the kernels that walk problems (slots) and those that walk positions (problems); null: in problem order
 static const uint32_t *slots(const BatchView &b) { return b.scheduled ? b.slot_of : nullptr; }
+static const uint32_t *problems(const BatchView &b) { return b.scheduled ? b.prob_of : nullptr; }
 
 hipError_t launch_solution(const BatchView &b, Solution *d_out, hipStream_t stream)
 {
     if (b.n == 0) return hipSuccess;
-    const uint32_t *inv = b.scheduled ? (const uint32_t *)b.prob_of : nullptr;
-    if (b.dtype == 0) hipLaunchKernelGGL((k_solution<double>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (const double *)b.base, b.stride, b.n, b.iters, b.status, inv, b.iters_add, d_out);
-    else              hipLaunchKernelGGL((k_solution<float>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (const float *)b.base, b.stride, b.n, b.iters, b.status, inv, b.iters_add, d_out);
+    RP_DISPATCH(kStorage, b, hipLaunchKernelGGL((k_solution<S>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                (const S *)b.base, b.stride, b.n, b.iters, b.status, problems(b), b.iters_add, d_out));
     return hipGetLastError();
 }
 
+// the state transposes: on the storage type (dtype 1 and 2 both keep floats) and the row length
 hipError_t launch_aos_to_soa(const BatchView &b, const double *d_aos, hipStream_t stream)
 {
     const dim3 g(grid_for(b.n)), t(kBlock);
-    if (b.scheduled) {      // whole rows in, walking positions
-        const uint32_t *inv = (const uint32_t *)b.prob_of;
-        if (b.dtype == 0) {
-            if (b.variant == 3) hipLaunchKernelGGL((k_aos_rows_to_soa<double, 16>), g, t, 0, stream, d_aos, (double *)b.base, b.stride, b.n, inv);
-            else                hipLaunchKernelGGL((k_aos_rows_to_soa<double, 12>), g, t, 0, stream, d_aos, (double *)b.base, b.stride, b.n, inv);
-        } else {
-            if (b.variant == 3) hipLaunchKernelGGL((k_aos_rows_to_soa<float, 16>), g, t, 0, stream, d_aos, (float *)b.base, b.stride, b.n, inv);
-            else                hipLaunchKernelGGL((k_aos_rows_to_soa<float, 12>), g, t, 0, stream, d_aos, (float *)b.base, b.stride, b.n, inv);
-        }
-        return hipGetLastError();
-    }
-    if (b.dtype == 0) {      // storage type only: dtype 1 and 2 both keep floats
-        if (b.variant == 3) hipLaunchKernelGGL((k_aos_to_soa<double, 16>), g, t, 0, stream, d_aos, (double *)b.base, b.stride, b.n, slots(b));
-        else                hipLaunchKernelGGL((k_aos_to_soa<double, 12>), g, t, 0, stream, d_aos, (double *)b.base, b.stride, b.n, slots(b));
-    } else {
-        if (b.variant == 3) hipLaunchKernelGGL((k_aos_to_soa<float, 16>), g, t, 0, stream, d_aos, (float *)b.base, b.stride, b.n, slots(b));
-        else                hipLaunchKernelGGL((k_aos_to_soa<float, 12>), g, t, 0, stream, d_aos, (float *)b.base, b.stride, b.n, slots(b));
-    }
+    if (b.scheduled)      // whole rows in, walking positions
+        RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_aos_rows_to_soa<S, M>), g, t, 0, stream, d_aos, (S *)b.base, b.stride, b.n, problems(b)));
+    else
+        RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_aos_to_soa<S, M>), g, t, 0, stream, d_aos, (S *)b.base, b.stride, b.n, slots(b)));
     return hipGetLastError();
 }
 
 hipError_t launch_soa_to_aos_range(const BatchView &b, size_t first, size_t count, double *d_aos, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    const dim3 g(grid_for(count)), t(kBlock);
-    if (b.dtype == 0) {
-        if (b.variant == 3) hipLaunchKernelGGL((k_soa_to_aos<double, 16>), g, t, 0, stream, (const double *)b.base, b.stride, first, count, slots(b), d_aos);
-        else                hipLaunchKernelGGL((k_soa_to_aos<double, 12>), g, t, 0, stream, (const double *)b.base, b.stride, first, count, slots(b), d_aos);
-    } else {
-        if (b.variant == 3) hipLaunchKernelGGL((k_soa_to_aos<float, 16>), g, t, 0, stream, (const float *)b.base, b.stride, first, count, slots(b), d_aos);
-        else                hipLaunchKernelGGL((k_soa_to_aos<float, 12>), g, t, 0, stream, (const float *)b.base, b.stride, first, count, slots(b), d_aos);
-    }
+    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_soa_to_aos<S, M>), dim3(grid_for(count)), dim3(kBlock), 0, stream,
+                                                (const S *)b.base, b.stride, first, count, slots(b), d_aos));
     return hipGetLastError();
 }
 
 hipError_t launch_soa_to_aos(const BatchView &b, double *d_aos, hipStream_t stream)
 {
     if (!b.scheduled || b.n == 0) return launch_soa_to_aos_range(b, 0, b.n, d_aos, stream);
-    const dim3 g(grid_for(b.n)), t(kBlock);      // whole rows out, walking positions
-    const uint32_t *inv = (const uint32_t *)b.prob_of;
-    if (b.dtype == 0) {
-        if (b.variant == 3) hipLaunchKernelGGL((k_soa_to_aos_rows<double, 16>), g, t, 0, stream, (const double *)b.base, b.stride, b.n, inv, d_aos);
-        else                hipLaunchKernelGGL((k_soa_to_aos_rows<double, 12>), g, t, 0, stream, (const double *)b.base, b.stride, b.n, inv, d_aos);
-    } else {
-        if (b.variant == 3) hipLaunchKernelGGL((k_soa_to_aos_rows<float, 16>), g, t, 0, stream, (const float *)b.base, b.stride, b.n, inv, d_aos);
-        else                hipLaunchKernelGGL((k_soa_to_aos_rows<float, 12>), g, t, 0, stream, (const float *)b.base, b.stride, b.n, inv, d_aos);
-    }
+    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_soa_to_aos_rows<S, M>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,      // whole rows out, walking positions
+                                                (const S *)b.base, b.stride, b.n, problems(b), d_aos));
     return hipGetLastError();
 }
 
 hipError_t launch_restart_feasible(const BatchView &b, const HostParams &hp, hipStream_t stream)
 {
-    RP_DISPATCH(b, hipLaunchKernelGGL((k_restart_feasible<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
-                                       (S *)b.base, b.stride, b.n, hp.accel_limit));
+    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_restart_feasible<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                (S *)b.base, b.stride, b.n, hp.accel_limit));
     return hipGetLastError();
 }
 
 hipError_t launch_start_from_records(const BatchView &b, const HostParams &hp, hipStream_t stream)
 {
     if (!b.records) return hipErrorInvalidValue;
-    RP_DISPATCH(b, hipLaunchKernelGGL((k_start_from_records<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
-                                       (S *)b.base, b.stride, b.n, hp.accel_limit, (const StartRecord *)b.records, (const uint32_t *)b.prob_of, b.iters, b.status));
+    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_start_from_records<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                (S *)b.base, b.stride, b.n, hp.accel_limit, (const StartRecord *)b.records, (const uint32_t *)b.prob_of, b.iters, b.status));
     return hipGetLastError();
 }
 
 hipError_t launch_start_vel_from_records(const BatchView &b, const HostParams &hp, const double *d_vel0, const double *d_vel2, hipStream_t stream)
 {
     if (!b.records || !b.scheduled) return hipErrorInvalidValue;
-    RP_DISPATCH(b, hipLaunchKernelGGL((k_start_vel_from_records<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
-                                       (S *)b.base, b.stride, b.n, hp.accel_limit, (const StartRecord *)b.records, (const uint32_t *)b.prob_of,
-                                       d_vel0, d_vel2, b.iters, b.status));
+    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_start_vel_from_records<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                (S *)b.base, b.stride, b.n, hp.accel_limit, (const StartRecord *)b.records, (const uint32_t *)b.prob_of,
+                                                d_vel0, d_vel2, b.iters, b.status));
     return hipGetLastError();
 }
 
 hipError_t launch_restart_vel(const BatchView &b, const HostParams &hp, hipStream_t stream)
 {
-    RP_DISPATCH(b, hipLaunchKernelGGL((k_restart_vel<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
-                                       (S *)b.base, b.stride, b.n, hp.accel_limit));
+    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_restart_vel<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                (S *)b.base, b.stride, b.n, hp.accel_limit));
     return hipGetLastError();
 }
 
@@ -1675,15 +1655,13 @@ hipError_t launch_init_const(const BatchView &b, const double *host_state, hipSt
     ConstState cs;
     const int m = state_len(b.variant);
     for (int f = 0; f < 16; ++f) cs.v[f] = f < m ? host_state[f] : 0.0;
-    if (b.dtype == 0) hipLaunchKernelGGL((k_init_const<double>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (double *)b.base, b.stride, b.n, m, cs);
-    else              hipLaunchKernelGGL((k_init_const<float>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (float *)b.base, b.stride, b.n, m, cs);
+    RP_DISPATCH(kStorage, b, hipLaunchKernelGGL((k_init_const<S>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (S *)b.base, b.stride, b.n, m, cs));
     return hipGetLastError();
 }
 
 hipError_t launch_nudge(const BatchView &b, int field, double delta, hipStream_t stream)
 {
-    if (b.dtype == 0) hipLaunchKernelGGL((k_nudge<double>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (double *)b.base + (size_t)field * b.stride, b.n, delta);
-    else              hipLaunchKernelGGL((k_nudge<float>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (float *)b.base + (size_t)field * b.stride, b.n, (float)delta);
+    RP_DISPATCH(kStorage, b, hipLaunchKernelGGL((k_nudge<S>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream, (S *)b.base + (size_t)field * b.stride, b.n, (S)delta));
     return hipGetLastError();
 }
 
@@ -1698,8 +1676,8 @@ hipError_t launch_move_toward_feasibility(const BatchView &b, const HostParams &
     // Always in double, whatever the batch's arithmetic type: the move squares the conditioning of the constraint
     // gradients (Gram matrix), which single precision cannot carry (measured: 10 % of fp32 moves off by > 6e-3), and
     // it is a one-off between solves, not the hot path.  An fp32 state gets the fp64 move rounded to fp32.
-    RP_DISPATCH(b, hipLaunchKernelGGL((k_move_toward_feasibility<S, double, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
-                                       (S *)b.base, b.stride, b.n, make_kparams<double>(hp, V)));
+    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_move_toward_feasibility<S, double, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                (S *)b.base, b.stride, b.n, make_kparams<double>(hp, V)));
     return hipGetLastError();
 }
 
@@ -1708,13 +1686,8 @@ hipError_t launch_sample_range(const BatchView &b, size_t first, size_t count, d
 {
     if (count == 0) return hipSuccess;
     const dim3 grid((unsigned)((count + kSampleProblems - 1) / kSampleProblems));
-    if (b.zero_end_vel) {
-        RP_DISPATCH(b, hipLaunchKernelGGL((k_sample<S, V, true>), grid, dim3(kBlock), 0, stream,
-                                           (const S *)b.base, b.stride, first, count, slots(b), d_pos66, d_acc4));
-    } else {
-        RP_DISPATCH(b, hipLaunchKernelGGL((k_sample<S, V, false>), grid, dim3(kBlock), 0, stream,
-                                           (const S *)b.base, b.stride, first, count, slots(b), d_pos66, d_acc4));
-    }
+    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_sample<S, V, Z>), grid, dim3(kBlock), 0, stream,
+                                                           (const S *)b.base, b.stride, first, count, slots(b), d_pos66, d_acc4));
     return hipGetLastError();
 }
 
@@ -1727,16 +1700,16 @@ hipError_t launch_sample_from_records(const BatchView &b, Solution *d_solution_s
     hipError_t e = launch_solution(b, d_solution_scratch, stream);      // every problem's (vel1, duration0, duration1) in problem order
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((b.n + kSampleProblems - 1) / kSampleProblems));
-    if (b.dtype == 0) hipLaunchKernelGGL((k_sample_records<double>), grid, dim3(kBlock), 0, stream, (const StartRecord *)b.records, (const Solution *)d_solution_scratch, b.n, d_pos66, d_acc4);
-    else              hipLaunchKernelGGL((k_sample_records<float>), grid, dim3(kBlock), 0, stream, (const StartRecord *)b.records, (const Solution *)d_solution_scratch, b.n, d_pos66, d_acc4);
+    RP_DISPATCH(kStorage, b, hipLaunchKernelGGL((k_sample_records<S>), grid, dim3(kBlock), 0, stream,
+                                                (const StartRecord *)b.records, (const Solution *)d_solution_scratch, b.n, d_pos66, d_acc4));
     return hipGetLastError();
 }
 
 hipError_t launch_constraint_table(const BatchView &b, const HostParams &hp, size_t first, size_t count, double *d_rows, hipStream_t stream)
 {
     if (count == 0) return hipSuccess;
-    RP_DISPATCH(b, hipLaunchKernelGGL((k_constraint_table<S, T, V>), dim3(grid_for(count)), dim3(kBlock), 0, stream,
-                                       (const S *)b.base, b.stride, first, count, slots(b), make_kparams<T>(hp, V), d_rows));
+    RP_DISPATCH(kArith | kVariant, b, hipLaunchKernelGGL((k_constraint_table<S, T, V>), dim3(grid_for(count)), dim3(kBlock), 0, stream,
+                                                          (const S *)b.base, b.stride, first, count, slots(b), make_kparams<T>(hp, V), d_rows));
     return hipGetLastError();
 }
 

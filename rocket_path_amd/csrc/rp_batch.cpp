@@ -18,6 +18,41 @@
 
 #include "ip_kernels.h"
 
+// ---- what a batch remembers about its own state, and the only events that change it ----
+// The flags below decide what a gated solve does next (start formed in registers / plain / watching for fixed points / in rounds), whether a
+// bound solution buffer is seeded first and whether the plot data may go through the records.  They are assigned by the transition functions
+// under the struct and nowhere else: an entry point says what happened by calling one; the questions have one predicate each, below those.
+//   view.scheduled     the problems lie in the scheduled order (slot_of / prob_of), not in problem order
+//   view.zero_end_vel  every end velocity is zero: the Newton kernels' zero-velocity instantiations
+//   at_start           lazy: the batch holds its order and records, the feasible start itself (mutable fields, progress words) is not written:
+//                      the fused solve forms it in registers, everything else goes through materialize() first (left_lazy_start, both)
+//   records_current    view.records hold the positions the batch's constant fields hold
+//   vel_start          the problems were given with end velocities: a restart keeps them
+//   unpredicted        the order no longer predicts step counts: the fused solve runs the kernel that watches for fixed points, in ONE
+//                      launch (rp_params.handoff_rounds = 0; rounds only on request, 2..8; -1: the plain kernel always)
+//   sol_stale          a bound buffer's records of problems the next gated launch does NOT work on are not current: it is seeded first
+//   raw_state_out      a raw pointer to a MUTABLE field is out and the caller may write at any later time: a bound buffer is seeded before EVERY
+//                      gated launch that may skip problems, until the batch is given a new state (not a restart)
+//   raw_positions_out  a raw pointer to a CONSTANT field (a position, an end velocity) is out: the records may miss positions written at any
+//                      later time.  Never cleared: the records path of the plot data stays off for the life of the batch
+//   ungated_steps      ungated steps per problem since the last init; with the device's progress words "the progress"
+// event (transition): entry points -> what it leaves
+//   created: create -> the zeroed struct: not scheduled, zero_end_vel, everything else false
+//   identical_problems: init_default, init_stuck -> not scheduled, zero_end_vel, predicted, not lazy, records not current, no raw state out,
+//       no velocity start, stale; progress reset
+//   problems_given: set_problems(_device), rp_pipeline_submit -> scheduled, zero_end_vel (the velocity fields cleared first if they might be
+//       non-zero), predicted, LAZY, records current, no raw state out, no velocity start, stale, no ungated steps
+//   problems_vel_given: set_problems_vel(_device) -> scheduled, NOT zero_end_vel, unpredicted, start written out, records not current, no raw
+//       state out, velocity start, stale, no ungated steps
+//   rows_given: set_state -> scheduled by the rows' positions, zero_end_vel as scanned on the host, unpredicted, not lazy, records not current,
+//       no raw state out, no velocity start, stale; progress reset
+//   restarted: restart -> stale; predicted again unless a raw position pointer is out; a lazy batch is only written out and resets nothing,
+//       any other goes back to its velocity start (unpredicted) or its rest-to-rest start (zero_end_vel), progress reset; raw_state_out stays
+//   stepped / moved / nudged: step, step_counted / move_toward_feasibility / nudge -> stale; steps add to ungated_steps; a move or a nudge:
+//       unpredicted; a nudged constant: records not current; an end velocity nudged by a non-zero delta: not zero_end_vel
+//   raw_pointer_out: field_ptr (start written out first) -> records not current, stale, unpredicted, raw_positions_out or raw_state_out,
+//       an end-velocity field: not zero_end_vel
+//   solution_bound: bind_solution -> stale.     solution_current: solve, solve_launch -> not stale, only behind a launch that succeeded
 struct rp_batch {
     rp::BatchView view;
     rp::HostParams params;
@@ -32,26 +67,9 @@ struct rp_batch {
     void *d_sched;            // lazily allocated scratch of the scheduling pass (schedule.hip), sched_bytes bytes
     size_t sched_bytes;
     rp::Solution *d_solscratch;   // lazily allocated n solution records: the plot data of a whole batch reads its state through them
-    bool records_current;     // view.records hold the positions the batch's constant fields hold (set_problems; until a set_state, an init,
-                              // a nudge of a position or a raw field pointer handed out)
-    bool raw_positions_out;   // a raw pointer to a CONSTANT field (a position, an end velocity) has been handed out (rp_batch_field_ptr): the caller may
-                              // write positions the records never see, at any later time -- the records path of rp_batch_sample_device stays off
-                              // for the life of the batch
-    bool sol_stale;           // a solution buffer is bound and something other than a gated solve has touched the state (or the buffer is new): the
-                              // records of problems the next gated launch does NOT work on are not current -- that launch seeds the buffer first
-    bool raw_state_out;       // a raw pointer to a MUTABLE field (vel1, a duration, a multiplier) has been handed out (rp_batch_field_ptr): the caller
-                              // may write state the batch never sees, at any later time -- sticky until the next init / set_problems / set_state
-                              // (which invalidate such pointers' meaning): while it is set, a bound solution buffer is seeded before EVERY gated
-                              // launch that may skip problems, not only the first one after the hand-out
-    bool unpredicted;         // the state has been set, nudged, moved or handed out raw since the last set_problems / init: the batch's internal order
-                              // no longer predicts step counts, and the fused gated solve runs in rounds (rp_params.handoff_rounds = 0: automatic)
-    bool slim_schedule;       // the scheduling pass runs in its one-wave-per-block form (schedule.hip): set by rp_pipeline for its batches
-    bool at_start;            // set_problems has run and nothing else since: the batch holds its scheduled order and its positions; the
-                              // feasible start itself (mutable fields, progress words) is NOT materialised yet -- see materialize()
-    bool vel_start;           // the problems were set with end velocities (rp_batch_set_problems_vel(_device)): rp_batch_restart goes back to the
-                              // start with the velocities the batch holds, not to the rest-to-rest start; cleared by every other init / set_problems /
-                              // set_state
-    double ungated_steps;     // per-problem count of ungated steps since the last init
+    bool slim_schedule;       // configuration: the scheduling pass runs in its one-wave-per-block form (schedule.hip): set by rp_pipeline for its batches
+    bool at_start, records_current, vel_start, unpredicted, sol_stale, raw_state_out, raw_positions_out;      // see above
+    double ungated_steps;
     unsigned long long *h_pinned;   // 72 pinned host words: [0,64) counter shards, [64,68) reduction: read-backs without pageable staging
     hipEvent_t events[8];
     bool event_live[8];
@@ -83,78 +101,109 @@ int fail(int status, const char *fmt, ...)
         RP_HIP(hipSetDevice((b)->device));                          \
     } while (0)
 
-size_t elem_size(int dtype) { return rp::storage_size(dtype); }
+// ---- the transitions (the table above the struct) ----
+int first_constant(const rp_batch *b) { return 3 + rp::num_constraints(b->view.variant); }      // fields from here on are constants: pos0, vel0, pos1, pos2, vel2
+bool is_end_velocity(const rp_batch *b, int field) { return field == first_constant(b) + 1 || field == first_constant(b) + 4; }
 
-// The *_range calls (a watched problem, a page of a table) go through one small device buffer that lives as long as
-// the batch: kRangeChunk problems x the widest row (the F3 constraint table, 1 + 14 * 8 doubles) = 0.9 MB.
-constexpr size_t kRangeChunk = 1024, kRangeRow = 113;
-
-void default_params(rp::HostParams &hp)
+// the four events that give the batch a new state differ in five answers; raw pointers to the old state lose their meaning in all of them
+void new_state(rp_batch *b, bool scheduled, bool zero_end_vel, bool unpredicted, bool lazy, bool vel_start)
 {
-    hp.accel_limit = 100.0;
-    hp.mu_divisor = 10.0;
-    hp.boundary_fraction = 0.99;
-    hp.backtrack = 0.5;
-    hp.armijo = 0.01;
-    hp.max_backtracks = 100;
-    hp.stall_window = 0;
-    hp.mu_mode = 0;
-    hp.mu_sigma_try[0] = 0.01;
-    hp.mu_sigma_try[1] = 0.03;
-    hp.handoff_rounds = 0;
-    hp.handoff_lanes = 24;
+    b->view.scheduled = scheduled;
+    b->view.zero_end_vel = zero_end_vel;
+    b->unpredicted = unpredicted;
+    b->at_start = lazy;
+    b->records_current = lazy;      // the records are the batch's positions exactly as long as nothing but set_problems has written any
+    b->vel_start = vel_start;
+    b->raw_state_out = false;
+    b->sol_stale = true;
 }
+void created(rp_batch *b) { b->view.scheduled = false; b->view.zero_end_vel = true; }      // (the struct is zeroed) the state starts all-zero, in problem order
+void identical_problems(rp_batch *b) { new_state(b, false, true, false, false, false); }      // nothing to schedule; identical step counts
+// the feasible-start rule (vel0 = vel2 = 0): what the order was fitted to
+void problems_given(rp_batch *b) { new_state(b, true, true, false, true, false); b->ungated_steps = 0.0; }
+// the order was fitted to rest-to-rest starts; the general Newton kernels (bit-identical to the zero-velocity ones where the velocities are 0)
+void problems_vel_given(rp_batch *b) { new_state(b, true, false, true, false, true); b->ungated_steps = 0.0; }
+void rows_given(rp_batch *b, bool zero_end_vel) { new_state(b, true, zero_end_vel, true, false, false); }      // any state: the order predicts nothing about it
 
-int reset_progress(rp_batch *b)
+void restarted(rp_batch *b)
 {
+    b->sol_stale = true;
+    if (!b->raw_positions_out) b->unpredicted = false;      // back on the feasible start of the positions the order was computed from
+    if (b->at_start) return;                                // still lazy: the start is only written out
+    if (b->vel_start) b->unpredicted = true;                // back to the start with the end velocities the batch holds
+    else b->view.zero_end_vel = true;
     b->ungated_steps = 0.0;
-    RP_HIP(rp::launch_clear_progress(b->view, b->stream));
-    return RP_OK;
 }
 
-// the scheduled order from positions given as three strided double arrays in problem order (device memory), on the batch's
-// own stream (three small kernels of ours, schedule.hip; round 2's library sort needed a queue of its own)
-int schedule(rp_batch *b, const double *d_pos0, const double *d_pos1, const double *d_pos2, size_t pstride, bool write_positions)
+void stepped(rp_batch *b, int k) { b->ungated_steps += (double)k; b->sol_stale = true; }
+void moved(rp_batch *b) { b->sol_stale = true; b->unpredicted = true; }
+void nudged(rp_batch *b, int field, double delta)
 {
-    if (!b->d_sched) {
-        size_t bytes = 0;
-        RP_HIP(rp::schedule_scratch_bytes(b->view.n, &bytes));
-        void *p = nullptr;
-        RP_HIP(hipMalloc(&p, bytes));
-        b->d_sched = p;
-        b->sched_bytes = bytes;
-    }
-    if (write_positions && !b->view.records) {      // 32 B per problem: what the scheduling pass keeps for the feasible start / the fused solve
-        void *p = nullptr;
-        RP_HIP(hipMalloc(&p, b->view.n * sizeof(rp::StartRecord)));
-        b->view.records = (rp::StartRecord *)p;
-    }
-    RP_HIP(rp::launch_schedule(b->view, d_pos0, d_pos1, d_pos2, pstride, write_positions, b->d_sched, b->sched_bytes, b->stream, b->slim_schedule));
-    b->view.scheduled = true;
-    return RP_OK;
+    moved(b);
+    if (field >= first_constant(b)) b->records_current = false;      // a constant moved: the records no longer are the batch's positions
+    if (is_end_velocity(b, field) && delta != 0.0) b->view.zero_end_vel = false;
 }
 
-// set_problems leaves the batch "at its start" without writing the start: the fused gated solve forms it in registers
-// (k_solve_chunks<START>).  Every other consumer of the state goes through here first: positions from the records into the
+void raw_pointer_out(rp_batch *b, int field)
+{
+    moved(b);
+    b->records_current = false;      // the caller may write through the pointer, now or at any later time
+    if (field >= first_constant(b)) b->raw_positions_out = true;
+    else b->raw_state_out = true;
+    if (is_end_velocity(b, field)) b->view.zero_end_vel = false;      // ... non-zero end velocities the batch never sees: the Newton kernels read vel0X and vel2X
+}
+
+void left_lazy_start(rp_batch *b) { b->at_start = false; }     // the start is written out (materialize), or a START launch forms it in registers
+void solution_bound(rp_batch *b) { b->sol_stale = true; }        // nothing in the new buffer is current
+void solution_current(rp_batch *b) { b->sol_stale = false; }     // a gated launch has been enqueued: it writes the record of every problem it works on
+
+// A batch that has just been given its problems is "at its start" without the start being written: the fused gated solve forms it in
+// registers (k_solve_chunks<START>).  Every other consumer of the state goes through here first: positions from the records into the
 // constant fields, their feasible start, cleared progress words -- bit for bit what the fused solve starts from.
 int materialize(rp_batch *b)
 {
     if (!b->at_start) return RP_OK;
-    b->at_start = false;
+    left_lazy_start(b);
     RP_HIP(rp::launch_start_from_records(b->view, b->params, b->stream));      // (the progress counters were zeroed by the scheduling pass)
     return RP_OK;
 }
 
+// ---- the questions asked of that state ----
+// may this fused solve form its start in registers?  (reference mode only; it then consumes the lazy start)
+bool starts_in_registers(const rp_batch *b, int max_iter)
+{
+    return b->at_start && b->params.mu_mode == 0 && b->params.stall_window == 0 && b->view.zero_end_vel && max_iter > 0;
+}
+
+// which form of the fused gated kernel: 0 = plain, 1 = the one that watches for fixed points (a batch whose state has been set, nudged, moved
+// or handed out raw: starts outside the feasible set use their budget up at once instead of walking a hundred halvings two hundred times:
+// exact), 2..8 = that one in so many rounds (on request: rp_params.handoff_rounds; a batch big enough for a second wave).  Reference mode only.
+int gated_rounds(const rp_batch *b, bool from_start, int max_iter)
+{
+    if (from_start || b->params.mu_mode != 0 || b->params.stall_window > 0 || max_iter <= 0 || b->params.handoff_rounds == -1) return 0;
+    const int rounds = b->params.handoff_rounds >= 2 && b->view.n > 64 ? b->params.handoff_rounds : 1;
+    return b->unpredicted || rounds > 1 ? rounds : 0;
+}
+
 // A gated launch writes the bound solution record of every problem it WORKS ON (k_solve_chunks); problems that finished in an
 // earlier launch are skipped without touching their state.  Their records are current only if nothing but gated solves has run
-// since they were written: otherwise (a new buffer, steps, a nudge, a set_state ... in between) the launch is preceded by one pass
-// that writes every record from the state as it is (k_solution, 68 B per problem).  Not on the fresh-batch path: a START launch
-// stores every record itself.
-int seed_solution(rp_batch *b)
+// since they were written: otherwise (a new buffer, steps, a nudge, a set_state ... in between, or a raw pointer to the state out)
+// the launch is preceded by one pass that writes every record from the state as it is (k_solution, 68 B per problem).
+bool needs_seed(const rp_batch *b) { return b->view.solution && (b->sol_stale || b->raw_state_out); }
+
+// may the plot data of the whole batch go through problem-order records instead of the per-field gather?
+bool samples_through_records(const rp_batch *b)
 {
-    if (!b->view.solution || !(b->sol_stale || b->raw_state_out)) return RP_OK;
-    RP_HIP(rp::launch_solution(b->view, b->view.solution, b->stream));
-    return RP_OK;      // (sol_stale is cleared by the caller once its gated launch has been enqueued: a failed launch leaves the buffer stale)
+    return b->view.scheduled && b->view.zero_end_vel && b->records_current && !b->raw_positions_out && b->view.records;
+}
+
+// The protocol around every gated launch: the ungated steps that the records' counts include, the seed (not before a START launch, which
+// stores every record itself), the launch, and -- only behind a launch that succeeded, a failed one has written no record -- solution_current().
+int before_gated_launch(rp_batch *b, bool seed)
+{
+    b->view.iters_add = (int)b->ungated_steps;
+    if (seed && needs_seed(b)) RP_HIP(rp::launch_solution(b->view, b->view.solution, b->stream));
+    return RP_OK;
 }
 
 #define RP_NEED_STATE(b)                     \
@@ -175,15 +224,88 @@ int seed_solution(rp_batch *b)
         RP_NEED_STATE(b);                                                               \
     } while (0)
 
+// The *_range calls (a watched problem, a page of a table) go through one small device buffer that lives as long as
+// the batch: kRangeChunk problems x the widest row (the F3 constraint table, 1 + 14 * 8 doubles) = 0.9 MB.
+constexpr size_t kRangeChunk = 1024, kRangeRow = 113;
+
+// The solver constants: the one list of the fields that rp_params and rp::HostParams share (the same names on both sides), each with its
+// default, the reference's compile-time value (include/rp_batch.h).  A new constant is added here, and to the two structs.
+#define RP_PARAMS(X)                                                                                                                  \
+    X(accel_limit, 100.0) X(mu_divisor, 10.0) X(boundary_fraction, 0.99) X(backtrack, 0.5) X(armijo, 0.01) X(max_backtracks, 100)     \
+    X(stall_window, 0) X(mu_mode, 0) X(mu_sigma_try[0], 0.01) X(mu_sigma_try[1], 0.03) X(handoff_rounds, 0) X(handoff_lanes, 24)
+
+template <typename To, typename From> void copy_params(To &to, const From &from)
+{
+#define X(field, value) to.field = from.field;
+    RP_PARAMS(X)
+#undef X
+}
+
+rp::HostParams default_params()
+{
+    rp::HostParams hp;
+#define X(field, value) hp.field = value;
+    RP_PARAMS(X)
+#undef X
+    return hp;
+}
+
+int reset_progress(rp_batch *b)
+{
+    b->ungated_steps = 0.0;
+    RP_HIP(rp::launch_clear_progress(b->view, b->stream));
+    return RP_OK;
+}
+
+// the scheduled order from positions given as three strided double arrays in problem order (device memory), on the batch's
+// own stream (three small kernels of ours, schedule.hip; round 2's library sort needed a queue of its own).
+// The caller applies its transition once this has succeeded.
+int schedule(rp_batch *b, const double *d_pos0, const double *d_pos1, const double *d_pos2, size_t pstride, bool write_positions)
+{
+    if (!b->d_sched) {
+        RP_HIP(rp::schedule_scratch_bytes(b->view.n, &b->sched_bytes));
+        RP_HIP(hipMalloc(&b->d_sched, b->sched_bytes));
+    }
+    // 32 B per problem: what the scheduling pass keeps for the feasible start / the fused solve
+    if (write_positions && !b->view.records) RP_HIP(hipMalloc((void **)&b->view.records, b->view.n * sizeof(rp::StartRecord)));
+    RP_HIP(rp::launch_schedule(b->view, d_pos0, d_pos1, d_pos2, pstride, write_positions, b->d_sched, b->sched_bytes, b->stream, b->slim_schedule));
+    return RP_OK;
+}
+
+// host position arrays into d_pos (3 n doubles: pos0, pos1, pos2), in stream order
+int stage_positions(rp_batch *b, const double *pos0, const double *pos1, const double *pos2)
+{
+    if (!pos0 || !pos1 || !pos2) return fail(RP_ERR_INVALID, "null position array");
+    const size_t n = b->view.n;
+    if (!b->d_pos) RP_HIP(hipMalloc((void **)&b->d_pos, 3 * n * sizeof(double)));
+    RP_HIP(hipMemcpyAsync(b->d_pos, pos0, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    RP_HIP(hipMemcpyAsync(b->d_pos + n, pos1, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    RP_HIP(hipMemcpyAsync(b->d_pos + 2 * n, pos2, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    return RP_OK;
+}
+
+// the four doubles of the last rp_batch_reduce_device into d_scratch + 4096, read back through pinned memory
+int read_summary(rp_batch *b, rp_reduction *out)
+{
+    double *h = reinterpret_cast<double *>(b->h_pinned + 64);
+    RP_HIP(hipMemcpyAsync(h, b->d_scratch + 4096, 4 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    RP_HIP(hipStreamSynchronize(b->stream));
+    out->max_residual_sq = h[0];
+    out->max_gap = h[1];
+    out->n_converged = h[2];
+    out->total_steps = h[3];
+    return RP_OK;
+}
+
 int need_words(rp_batch *b)
 {
     if (!b->d_words) RP_HIP(hipMalloc((void **)&b->d_words, 2 * b->view.n * sizeof(uint32_t)));
     return RP_OK;
 }
 
-int need_range(rp_batch *b)
+int need_aos(rp_batch *b)
 {
-    if (!b->d_range) RP_HIP(hipMalloc((void **)&b->d_range, kRangeChunk * kRangeRow * sizeof(double)));
+    if (!b->d_aos) RP_HIP(hipMalloc((void **)&b->d_aos, b->view.n * rp::state_len(b->view.variant) * sizeof(double)));
     return RP_OK;
 }
 
@@ -194,11 +316,23 @@ int check_range(const rp_batch *b, size_t first, size_t count, const void *out)
     return RP_OK;
 }
 
-int need_aos(rp_batch *b)
+// A *_range read-back: problems [first, first + count) in chunks of kRangeChunk through d_range.  produce(first, count) enqueues the
+// kernel that fills the staging buffer, copy_out(done, count) the copies of that chunk to the caller's arrays.
+template <typename Produce, typename CopyOut> int read_range(rp_batch *b, size_t first, size_t count, Produce produce, CopyOut copy_out)
 {
-    if (!b->d_aos) RP_HIP(hipMalloc((void **)&b->d_aos, b->view.n * rp::state_len(b->view.variant) * sizeof(double)));
+    if (!b->d_range) RP_HIP(hipMalloc((void **)&b->d_range, kRangeChunk * kRangeRow * sizeof(double)));
+    for (size_t done = 0; done < count; done += kRangeChunk) {
+        const size_t c = count - done < kRangeChunk ? count - done : kRangeChunk;
+        RP_HIP(produce(first + done, c));
+        RP_HIP(copy_out(done, c));
+        RP_HIP(hipStreamSynchronize(b->stream));      // the staging buffer is reused by the next chunk
+    }
     return RP_OK;
 }
+
+int check_steps(int k) { return k < 0 || k > 1000000 ? fail(RP_ERR_INVALID, "step count %d out of range (0..1000000)", k) : RP_OK; }
+int check_max_iter(int max_iter) { return max_iter < 0 || max_iter > 1000000 ? fail(RP_ERR_INVALID, "max_iter %d out of range (0..1000000)", max_iter) : RP_OK; }
+int check_gap_tol(double gap_tol) { return gap_tol == gap_tol ? RP_OK : fail(RP_ERR_INVALID, "gap_tol is NaN"); }
 
 }  // namespace
 
@@ -254,21 +388,7 @@ int rp_device_id(int device, char *out, size_t len)
 
 void rp_params_default(rp_params *p)
 {
-    if (!p) return;
-    rp::HostParams hp;
-    default_params(hp);
-    p->accel_limit = hp.accel_limit;
-    p->mu_divisor = hp.mu_divisor;
-    p->boundary_fraction = hp.boundary_fraction;
-    p->backtrack = hp.backtrack;
-    p->armijo = hp.armijo;
-    p->max_backtracks = hp.max_backtracks;
-    p->stall_window = hp.stall_window;
-    p->mu_mode = hp.mu_mode;
-    p->mu_sigma_try[0] = hp.mu_sigma_try[0];
-    p->mu_sigma_try[1] = hp.mu_sigma_try[1];
-    p->handoff_rounds = hp.handoff_rounds;
-    p->handoff_lanes = hp.handoff_lanes;
+    if (p) copy_params(*p, default_params());
 }
 
 int rp_batch_create(rp_batch **out, int variant, int dtype, size_t n, int device, void *stream)
@@ -290,7 +410,7 @@ int rp_batch_create(rp_batch **out, int variant, int dtype, size_t n, int device
     if (!b) return fail(RP_ERR_NOMEM, "host allocation failed");
     std::memset(b, 0, sizeof *b);
     b->device = device;
-    default_params(b->params);
+    b->params = default_params();
     b->view.n = n;
     b->view.variant = variant;
     b->view.dtype = dtype;
@@ -303,14 +423,13 @@ int rp_batch_create(rp_batch **out, int variant, int dtype, size_t n, int device
 #ifdef RP_TUNING      // tuning builds only (profiles/probes/stride_probe.py): the shipped library reads nothing from the environment
     if (const char *pad = getenv("RP_STRIDE_PAD")) b->view.stride += (size_t)atoi(pad) / 16 * 16;
 #endif
-    b->view.zero_end_vel = true;       // the state starts all-zero
-    b->view.scheduled = false;         // ... and identical problems lie in problem order
+    created(b);
     const size_t fields = (size_t)rp::state_len(variant);
 
     hipError_t e = hipSuccess;
     if (stream) { b->stream = (hipStream_t)stream; b->own_stream = false; }
     else { e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking); b->own_stream = (e == hipSuccess); }
-    if (e == hipSuccess) e = hipMalloc(&b->view.base, fields * b->view.stride * elem_size(dtype));
+    if (e == hipSuccess) e = hipMalloc(&b->view.base, fields * b->view.stride * rp::storage_size(dtype));
     if (e == hipSuccess) e = hipMalloc((void **)&b->view.iters, n * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&b->view.status, n * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&b->view.slot_of, n * sizeof(uint32_t));
@@ -318,7 +437,7 @@ int rp_batch_create(rp_batch **out, int variant, int dtype, size_t n, int device
     if (e == hipSuccess) e = hipMalloc((void **)&b->view.counters, 128 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_scratch, (4096 + 4) * sizeof(double));
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_pinned, 72 * sizeof(unsigned long long), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMemsetAsync(b->view.base, 0, fields * b->view.stride * elem_size(dtype), b->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b->view.base, 0, fields * b->view.stride * rp::storage_size(dtype), b->stream);
     if (e == hipSuccess) e = rp::launch_clear_progress(b->view, b->stream);
     if (e != hipSuccess) {
         const int code = fail(e == hipErrorOutOfMemory ? RP_ERR_NOMEM : RP_ERR_DEVICE, "rp_batch_create: %s", hipGetErrorString(e));
@@ -376,40 +495,16 @@ int rp_batch_set_params(rp_batch *b, const rp_params *p)
         // the feasible start of a batch that has just been given its problems is formed lazily, from the limit of the moment the
         // problems were set: write it out before the limit changes (set_problems, set_params, solve = the start of the OLD limit,
         // as if set_problems had written it)
-        RP_HIP(hipSetDevice(b->device));
-        const int ms = materialize(b);
-        if (ms != RP_OK) return ms;
+        RP_NEED_STATE(b);
     }
-    b->params.accel_limit = p->accel_limit;
-    b->params.mu_divisor = p->mu_divisor;
-    b->params.boundary_fraction = p->boundary_fraction;
-    b->params.backtrack = p->backtrack;
-    b->params.armijo = p->armijo;
-    b->params.max_backtracks = p->max_backtracks;
-    b->params.stall_window = p->stall_window;
-    b->params.mu_mode = p->mu_mode;
-    b->params.mu_sigma_try[0] = p->mu_sigma_try[0];
-    b->params.mu_sigma_try[1] = p->mu_sigma_try[1];
-    b->params.handoff_rounds = p->handoff_rounds;
-    b->params.handoff_lanes = p->handoff_lanes;
+    copy_params(b->params, *p);
     return RP_OK;
 }
 
 int rp_batch_get_params(const rp_batch *b, rp_params *p)
 {
     if (!b || !p) return fail(RP_ERR_INVALID, "null argument");
-    p->accel_limit = b->params.accel_limit;
-    p->mu_divisor = b->params.mu_divisor;
-    p->boundary_fraction = b->params.boundary_fraction;
-    p->backtrack = b->params.backtrack;
-    p->armijo = b->params.armijo;
-    p->max_backtracks = b->params.max_backtracks;
-    p->stall_window = b->params.stall_window;
-    p->mu_mode = b->params.mu_mode;
-    p->mu_sigma_try[0] = b->params.mu_sigma_try[0];
-    p->mu_sigma_try[1] = b->params.mu_sigma_try[1];
-    p->handoff_rounds = b->params.handoff_rounds;
-    p->handoff_lanes = b->params.handoff_lanes;
+    copy_params(*p, b->params);
     return RP_OK;
 }
 
@@ -429,6 +524,14 @@ int rp_batch_info(const rp_batch *b, int *variant, int *dtype, int *device)
     return RP_OK;
 }
 
+// every problem of the batch in the one state `s` (state_len values)
+static int init_identical(rp_batch *b, const double *s)
+{
+    RP_HIP(rp::launch_init_const(b->view, s, b->stream));
+    identical_problems(b);
+    return reset_progress(b);
+}
+
 // initDefault: pos (0, 200, 400), zero velocities, durations 3.5, multipliers 1
 // (onedpath_ip.cpp:201-228, onedpath2_ip.cpp:164-193).
 int rp_batch_init_default(rp_batch *b)
@@ -439,16 +542,7 @@ int rp_batch_init_default(rp_batch *b)
     s[0] = 0.0; s[1] = 3.5; s[2] = 3.5;
     for (int i = 0; i < m; ++i) s[3 + i] = 1.0;
     s[3 + m + 0] = 0.0; s[3 + m + 1] = 0.0; s[3 + m + 2] = 200.0; s[3 + m + 3] = 400.0; s[3 + m + 4] = 0.0;
-    RP_HIP(rp::launch_init_const(b->view, s, b->stream));
-    b->sol_stale = true;
-    b->raw_state_out = false;
-    b->unpredicted = false;      // identical problems: identical step counts
-    b->view.zero_end_vel = true;
-    b->view.scheduled = false;         // identical problems: nothing to schedule
-    b->at_start = false;
-    b->records_current = false;
-    b->vel_start = false;
-    return reset_progress(b);
+    return init_identical(b, s);
 }
 
 // initStuck, onedpath_ip.cpp:177-199.
@@ -459,76 +553,49 @@ int rp_batch_init_stuck(rp_batch *b)
     const double s[16] = {-9.66825, 4.78149, 4.38968,
                           5.45948e-07, 0.00310769, 3.49109e-08, 0.00281523, 8.39344e-07, 1.76937e-06, 0.0187559, 8.42414e-07,
                           0.0, 0.0, 350.0, 400.0, 0.0};
-    RP_HIP(rp::launch_init_const(b->view, s, b->stream));
-    b->sol_stale = true;
-    b->raw_state_out = false;
-    b->unpredicted = false;      // identical problems: identical step counts
-    b->view.zero_end_vel = true;
-    b->view.scheduled = false;
-    b->at_start = false;
-    b->records_current = false;
-    b->vel_start = false;
-    return reset_progress(b);
+    return init_identical(b, s);
 }
 
+// Where each problem goes (scheduled order), its positions copied into its record, progress counters zeroed: three
+// kernels (schedule.hip).  The feasible start itself is not written: a fused gated solve that follows forms it in registers,
+// anything else materialises it first (materialize above).  The position arrays are consumed in stream order, here.
 int rp_batch_set_problems_device(rp_batch *b, const double *d_pos0, const double *d_pos1, const double *d_pos2)
 {
     RP_NEED(b);
     if (!d_pos0 || !d_pos1 || !d_pos2) return fail(RP_ERR_INVALID, "null position array");
-    // Where each problem goes (scheduled order), its positions copied into its record, progress counters zeroed: three
-    // kernels (schedule.hip).  The feasible start itself is not written: a fused gated solve that follows forms it in registers,
-    // anything else materialises it first (materialize above).  The position arrays are consumed in stream order, here.
     if (!b->view.zero_end_vel) {       // a set_state / nudge / field_ptr may have left non-zero end velocities: the start rule zeroes them
-        const size_t es = elem_size(b->view.dtype), cb = 3 + (size_t)rp::num_constraints(b->view.variant);
+        const size_t es = rp::storage_size(b->view.dtype), cb = (size_t)first_constant(b);
         RP_HIP(hipMemsetAsync((char *)b->view.base + (cb + 1) * b->view.stride * es, 0, b->view.n * es, b->stream));
         RP_HIP(hipMemsetAsync((char *)b->view.base + (cb + 4) * b->view.stride * es, 0, b->view.n * es, b->stream));
     }
     int st = schedule(b, d_pos0, d_pos1, d_pos2, 1, true);
     if (st != RP_OK) return st;
-    b->view.zero_end_vel = true;       // the feasible-start rule sets vel0 = vel2 = 0
-    b->ungated_steps = 0.0;
-    b->sol_stale = true;
-    b->raw_state_out = false;
-    b->unpredicted = false;      // the feasible-start rule: what the scheduled order was fitted to
-    b->at_start = true;
-    b->records_current = true;
-    b->vel_start = false;
+    problems_given(b);
     return RP_OK;
 }
 
+// The same scheduling pass on the positions, then the start with the velocities written out at once (it writes both velocity fields):
+// the fused solve forms only the rest-to-rest start in registers.
 int rp_batch_set_problems_vel_device(rp_batch *b, const double *d_pos0, const double *d_pos1, const double *d_pos2,
                                      const double *d_vel0, const double *d_vel2)
 {
     RP_NEED(b);
     if (!d_pos0 || !d_pos1 || !d_pos2) return fail(RP_ERR_INVALID, "null position array");
-    // the scheduling pass on the positions (set_problems_device), then the start with the velocities written out at once: the fused
-    // solve forms only the rest-to-rest start in registers
-    b->view.zero_end_vel = true;      // (skips set_problems_device's clearing of the velocity fields: the start below writes both)
-    int st = rp_batch_set_problems_device(b, d_pos0, d_pos1, d_pos2);
+    int st = schedule(b, d_pos0, d_pos1, d_pos2, 1, true);
     if (st != RP_OK) return st;
-    b->at_start = false;
+    problems_vel_given(b);
     RP_HIP(rp::launch_start_vel_from_records(b->view, b->params, d_vel0, d_vel2, b->stream));
-    b->view.zero_end_vel = false;      // the general Newton kernels (bit-identical to the zero-velocity ones where the velocities are 0)
-    b->unpredicted = true;             // the scheduled order was fitted to rest-to-rest starts
-    b->records_current = false;
-    b->vel_start = true;
     return RP_OK;
 }
 
 int rp_batch_restart(rp_batch *b)
 {
     RP_NEED(b);
-    b->sol_stale = true;
-    if (!b->raw_positions_out) b->unpredicted = false;      // back on the feasible start of the positions the order was computed from
-    if (b->at_start) return materialize(b);      // already at the start of its positions: write it out
-    if (b->vel_start) {      // back to the start with the end velocities the batch holds
-        RP_HIP(rp::launch_restart_vel(b->view, b->params, b->stream));
-        b->unpredicted = true;
-    } else {
-        RP_HIP(rp::launch_restart_feasible(b->view, b->params, b->stream));
-        b->view.zero_end_vel = true;
-    }
-    b->ungated_steps = 0.0;
+    const bool lazy = b->at_start, vel = b->vel_start;
+    restarted(b);
+    if (lazy) return materialize(b);      // already at the start of its positions: write it out
+    if (vel) RP_HIP(rp::launch_restart_vel(b->view, b->params, b->stream));      // back to the start with the end velocities the batch holds
+    else RP_HIP(rp::launch_restart_feasible(b->view, b->params, b->stream));
     RP_HIP(rp::launch_clear_progress(b->view, b->stream));      // the positions have not changed: the scheduled order stays as it is
     return RP_OK;
 }
@@ -536,13 +603,8 @@ int rp_batch_restart(rp_batch *b)
 int rp_batch_set_problems(rp_batch *b, const double *pos0, const double *pos1, const double *pos2)
 {
     RP_NEED(b);
-    if (!pos0 || !pos1 || !pos2) return fail(RP_ERR_INVALID, "null position array");
-    const size_t n = b->view.n;
-    if (!b->d_pos) RP_HIP(hipMalloc((void **)&b->d_pos, 3 * n * sizeof(double)));
-    RP_HIP(hipMemcpyAsync(b->d_pos, pos0, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    RP_HIP(hipMemcpyAsync(b->d_pos + n, pos1, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    RP_HIP(hipMemcpyAsync(b->d_pos + 2 * n, pos2, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    int st = rp_batch_set_problems_device(b, b->d_pos, b->d_pos + n, b->d_pos + 2 * n);
+    int st = stage_positions(b, pos0, pos1, pos2);
+    if (st == RP_OK) st = rp_batch_set_problems_device(b, b->d_pos, b->d_pos + b->view.n, b->d_pos + 2 * b->view.n);
     if (st != RP_OK) return st;
     RP_HIP(hipStreamSynchronize(b->stream));   // the host arrays may be reused on return
     return RP_OK;
@@ -551,20 +613,17 @@ int rp_batch_set_problems(rp_batch *b, const double *pos0, const double *pos1, c
 int rp_batch_set_problems_vel(rp_batch *b, const double *pos0, const double *pos1, const double *pos2, const double *vel0, const double *vel2)
 {
     RP_NEED(b);
-    if (!pos0 || !pos1 || !pos2) return fail(RP_ERR_INVALID, "null position array");
+    int st = stage_positions(b, pos0, pos1, pos2);
+    if (st != RP_OK) return st;
     const size_t n = b->view.n;
-    if (!b->d_pos) RP_HIP(hipMalloc((void **)&b->d_pos, 3 * n * sizeof(double)));
-    RP_HIP(hipMemcpyAsync(b->d_pos, pos0, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    RP_HIP(hipMemcpyAsync(b->d_pos + n, pos1, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    RP_HIP(hipMemcpyAsync(b->d_pos + 2 * n, pos2, n * sizeof(double), hipMemcpyHostToDevice, b->stream));
     double *d_vel = nullptr;      // the two velocity arrays, staged for this call only
     if (vel0 || vel2) RP_HIP(hipMalloc((void **)&d_vel, 2 * n * sizeof(double)));
     hipError_t e = hipSuccess;
     if (vel0) e = hipMemcpyAsync(d_vel, vel0, n * sizeof(double), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess && vel2) e = hipMemcpyAsync(d_vel + n, vel2, n * sizeof(double), hipMemcpyHostToDevice, b->stream);
-    int st = e == hipSuccess ? rp_batch_set_problems_vel_device(b, b->d_pos, b->d_pos + n, b->d_pos + 2 * n, vel0 ? d_vel : nullptr,
-                                                                vel2 ? d_vel + n : nullptr)
-                             : fail(RP_ERR_DEVICE, "rp_batch_set_problems_vel: %s", hipGetErrorString(e));
+    st = e == hipSuccess ? rp_batch_set_problems_vel_device(b, b->d_pos, b->d_pos + n, b->d_pos + 2 * n, vel0 ? d_vel : nullptr,
+                                                            vel2 ? d_vel + n : nullptr)
+                         : fail(RP_ERR_DEVICE, "rp_batch_set_problems_vel: %s", hipGetErrorString(e));
     const hipError_t se = hipStreamSynchronize(b->stream);      // the host arrays may be reused on return, the staging freed
     if (d_vel) (void)hipFree(d_vel);
     if (st != RP_OK) return st;
@@ -578,25 +637,14 @@ int rp_batch_set_state(rp_batch *b, const double *aos)
     if (!aos) return fail(RP_ERR_INVALID, "null state array");
     int st = need_aos(b);
     if (st != RP_OK) return st;
-    const size_t M = (size_t)rp::state_len(b->view.variant), bytes = b->view.n * M * sizeof(double);
-    {   // which instantiation the Newton kernels may use: are all end velocities zero?  (NaN counts as non-zero)
-        const size_t iv0 = 3 + rp::num_constraints(b->view.variant) + 1, iv2 = iv0 + 3;
-        bool zero = true;
-        for (size_t i = 0; i < b->view.n && zero; ++i) zero = (aos[i * M + iv0] == 0.0) && (aos[i * M + iv2] == 0.0);
-        b->view.zero_end_vel = zero;
-    }
+    const size_t M = (size_t)rp::state_len(b->view.variant), bytes = b->view.n * M * sizeof(double), cb = (size_t)first_constant(b);
+    bool zero = true;      // which instantiation the Newton kernels may use: are all end velocities zero?  (NaN counts as non-zero)
+    for (size_t i = 0; i < b->view.n && zero; ++i) zero = (aos[i * M + cb + 1] == 0.0) && (aos[i * M + cb + 4] == 0.0);
     RP_HIP(hipMemcpyAsync(b->d_aos, aos, bytes, hipMemcpyHostToDevice, b->stream));
-    {   // schedule by the positions in the rows (columns pos0, pos1, pos2 of the reference's enum), then scatter the rows
-        const size_t cb = 3 + (size_t)rp::num_constraints(b->view.variant);
-        st = schedule(b, b->d_aos + cb + 0, b->d_aos + cb + 2, b->d_aos + cb + 3, M, false);
-        if (st != RP_OK) return st;
-        b->at_start = false;      // the rows below are the state
-        b->records_current = false;
-        b->sol_stale = true;
-        b->raw_state_out = false;
-        b->unpredicted = true;      // any state: the order (computed from the positions in the rows) predicts nothing about it
-        b->vel_start = false;
-    }
+    // schedule by the positions in the rows (columns pos0, pos1, pos2 of the reference's enum), then scatter the rows: they are the state
+    st = schedule(b, b->d_aos + cb + 0, b->d_aos + cb + 2, b->d_aos + cb + 3, M, false);
+    if (st != RP_OK) return st;
+    rows_given(b, zero);
     RP_HIP(rp::launch_aos_to_soa(b->view, b->d_aos, b->stream));
     st = reset_progress(b);
     if (st != RP_OK) return st;
@@ -620,17 +668,12 @@ int rp_batch_get_state(rp_batch *b, double *aos)
 int rp_batch_get_state_range(rp_batch *b, size_t first, size_t count, double *aos)
 {
     RP_NEED_STATE(b);
-    int st = check_range(b, first, count, aos);
-    if (st == RP_OK) st = need_range(b);
+    const int st = check_range(b, first, count, aos);
     if (st != RP_OK) return st;
     const size_t M = (size_t)rp::state_len(b->view.variant);
-    for (size_t done = 0; done < count; done += kRangeChunk) {
-        const size_t c = count - done < kRangeChunk ? count - done : kRangeChunk;
-        RP_HIP(rp::launch_soa_to_aos_range(b->view, first + done, c, b->d_range, b->stream));
-        RP_HIP(hipMemcpyAsync(aos + done * M, b->d_range, c * M * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        RP_HIP(hipStreamSynchronize(b->stream));      // the staging buffer is reused by the next chunk
-    }
-    return RP_OK;
+    return read_range(b, first, count,
+                      [&](size_t f, size_t c) { return rp::launch_soa_to_aos_range(b->view, f, c, b->d_range, b->stream); },
+                      [&](size_t done, size_t c) { return hipMemcpyAsync(aos + done * M, b->d_range, c * M * sizeof(double), hipMemcpyDeviceToHost, b->stream); });
 }
 
 int rp_batch_nudge(rp_batch *b, int var_index, double delta)
@@ -638,24 +681,17 @@ int rp_batch_nudge(rp_batch *b, int var_index, double delta)
     RP_NEED_STATE(b);
     if (var_index < 0 || var_index >= rp::state_len(b->view.variant)) return fail(RP_ERR_INVALID, "variable index %d out of range", var_index);
     RP_HIP(rp::launch_nudge(b->view, var_index, delta, b->stream));
-    b->sol_stale = true;
-    b->unpredicted = true;
-    if (var_index >= 3 + rp::num_constraints(b->view.variant)) b->records_current = false;      // a constant moved: the records no longer are the batch's positions
-    {
-        const int iv0 = 3 + rp::num_constraints(b->view.variant) + 1, iv2 = iv0 + 3;
-        if ((var_index == iv0 || var_index == iv2) && delta != 0.0) b->view.zero_end_vel = false;
-    }
+    nudged(b, var_index, delta);
     return RP_OK;
 }
 
 int rp_batch_step(rp_batch *b, int k)
 {
     RP_NEED_STATE(b);
-    if (k < 0 || k > 1000000) return fail(RP_ERR_INVALID, "step count %d out of range (0..1000000)", k);
-    if (k == 0) return RP_OK;
+    const int st = check_steps(k);
+    if (st != RP_OK || k == 0) return st;
     RP_HIP(rp::launch_steps(b->view, b->params, k, b->stream));
-    b->ungated_steps += (double)k;
-    b->sol_stale = true;
+    stepped(b, k);
     return RP_OK;
 }
 
@@ -669,7 +705,8 @@ int rp_batch_traffic_probe(rp_batch *b)
 int rp_batch_step_counted(rp_batch *b, int k, uint32_t *feas_halvings, uint32_t *resid_halvings)
 {
     RP_NEED_STATE(b);
-    if (k < 0 || k > 1000000) return fail(RP_ERR_INVALID, "step count %d out of range (0..1000000)", k);
+    const int st = check_steps(k);
+    if (st != RP_OK) return st;
     if (!feas_halvings || !resid_halvings) return fail(RP_ERR_INVALID, "null output");
     if (b->params.mu_mode != 0) return fail(RP_ERR_UNSUPPORTED, "the counted step exists for the reference's mu mode only");
     const size_t n = b->view.n;
@@ -688,47 +725,37 @@ int rp_batch_step_counted(rp_batch *b, int k, uint32_t *feas_halvings, uint32_t 
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     (void)hipFree(d);
     if (e != hipSuccess) return fail(RP_ERR_DEVICE, "rp_batch_step_counted: %s", hipGetErrorString(e));
-    b->ungated_steps += (double)k;
-    b->sol_stale = true;
+    stepped(b, k);
     return RP_OK;
 }
 
 int rp_batch_solve(rp_batch *b, double gap_tol, int max_iter, int steps_per_launch)
 {
     RP_NEED(b);
-    if (max_iter < 0 || max_iter > 1000000) return fail(RP_ERR_INVALID, "max_iter %d out of range (0..1000000)", max_iter);
-    if (!(gap_tol == gap_tol)) return fail(RP_ERR_INVALID, "gap_tol is NaN");
-    if (steps_per_launch <= 0) {
-        // a batch that has just been given its problems starts from the feasible start formed in registers (reference mode only)
-        const bool from_start = b->at_start && b->params.mu_mode == 0 && b->params.stall_window == 0 && b->view.zero_end_vel && max_iter > 0;
-        if (from_start) b->at_start = false;
-        else { const int ms = materialize(b); if (ms != RP_OK) return ms; }
-        b->view.iters_add = (int)b->ungated_steps;
-        if (!from_start) { const int ss = seed_solution(b); if (ss != RP_OK) return ss; }      // (the START launch stores every record itself)
-        // in rounds (rp_params.handoff_rounds): states the batch's order says nothing about -- reference mode only, and a batch big enough for a second wave
-        // A batch whose state has been set, nudged, moved or handed out raw runs the kernel that watches for fixed points (starts outside the
-        // feasible set use their budget up at once instead of walking a hundred halvings two hundred times: exact); rounds on request
-        const bool plain = from_start || b->params.mu_mode != 0 || b->params.stall_window > 0 || max_iter <= 0;
-        int rounds = b->params.handoff_rounds >= 2 ? b->params.handoff_rounds : 1;
-        if (b->view.n <= 64) rounds = 1;
-        const bool watched = !plain && b->params.handoff_rounds != -1 && (b->unpredicted || rounds > 1);
-        if (watched) {
+    int st = check_max_iter(max_iter);
+    if (st == RP_OK) st = check_gap_tol(gap_tol);
+    if (st != RP_OK) return st;
+    const bool fused = steps_per_launch <= 0, from_start = fused && starts_in_registers(b, max_iter);
+    if (from_start) left_lazy_start(b);
+    else st = materialize(b);
+    if (st == RP_OK) st = before_gated_launch(b, !from_start);
+    if (st != RP_OK) return st;
+    if (fused) {      // every problem to its gate in one launch (or one per round)
+        const int rounds = gated_rounds(b, from_start, max_iter);
+        if (rounds > 0) {
             if (rounds > 1 && !b->view.lists) RP_HIP(hipMalloc((void **)&b->view.lists, (2 * b->view.n + 16) * sizeof(uint32_t)));
             RP_HIP(rp::launch_solve_rounds(b->view, b->params, gap_tol, max_iter, rounds, b->params.handoff_lanes, 1, b->stream));
         } else {
             RP_HIP(rp::launch_solve_fused(b->view, b->params, gap_tol, max_iter, from_start, b->stream));
         }
-        b->sol_stale = false;      // only now: a launch that failed has written no record
+        solution_current(b);
         return RP_OK;
     }
-    { const int ms = materialize(b); if (ms != RP_OK) return ms; }
-    b->view.iters_add = (int)b->ungated_steps;
-    { const int ss = seed_solution(b); if (ss != RP_OK) return ss; }
     // bounded host loop: every launch either finishes a problem or advances it by >= 1 step
     const int max_launches = max_iter / steps_per_launch + 2;
     for (int l = 0; l < max_launches; ++l) {
         RP_HIP(rp::launch_solve(b->view, b->params, steps_per_launch, gap_tol, max_iter, b->stream));
-        b->sol_stale = false;
+        solution_current(b);
         RP_HIP(hipMemcpyAsync(b->h_pinned, b->view.counters, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
         RP_HIP(hipStreamSynchronize(b->stream));
         unsigned long long open = 0;
@@ -741,13 +768,13 @@ int rp_batch_solve(rp_batch *b, double gap_tol, int max_iter, int steps_per_laun
 int rp_batch_solve_launch(rp_batch *b, double gap_tol, int max_iter, int k)
 {
     RP_NEED_STATE(b);
-    if (max_iter < 0 || max_iter > 1000000) return fail(RP_ERR_INVALID, "max_iter %d out of range (0..1000000)", max_iter);
-    if (k < 1 || k > 1000000) return fail(RP_ERR_INVALID, "steps per launch %d out of range (1..1000000)", k);
-    if (!(gap_tol == gap_tol)) return fail(RP_ERR_INVALID, "gap_tol is NaN");
-    b->view.iters_add = (int)b->ungated_steps;
-    { const int ss = seed_solution(b); if (ss != RP_OK) return ss; }
+    int st = check_max_iter(max_iter);
+    if (st == RP_OK && (k < 1 || k > 1000000)) st = fail(RP_ERR_INVALID, "steps per launch %d out of range (1..1000000)", k);
+    if (st == RP_OK) st = check_gap_tol(gap_tol);
+    if (st == RP_OK) st = before_gated_launch(b, true);
+    if (st != RP_OK) return st;
     RP_HIP(rp::launch_solve(b->view, b->params, k, gap_tol, max_iter, b->stream));
-    b->sol_stale = false;
+    solution_current(b);
     return RP_OK;
 }
 
@@ -755,8 +782,7 @@ int rp_batch_move_toward_feasibility(rp_batch *b)
 {
     RP_NEED_STATE(b);
     RP_HIP(rp::launch_move_toward_feasibility(b->view, b->params, b->stream));
-    b->sol_stale = true;
-    b->unpredicted = true;
+    moved(b);
     return RP_OK;
 }
 
@@ -853,7 +879,7 @@ int rp_batch_bind_solution(rp_batch *b, rp_solution *d_out)
     if (!b) return fail(RP_ERR_INVALID, "null batch handle");
     if (((uintptr_t)d_out & 31u) != 0) return fail(RP_ERR_INVALID, "solution records must be 32-byte aligned");
     b->view.solution = reinterpret_cast<rp::Solution *>(d_out);
-    b->sol_stale = true;      // nothing in the new buffer is current: the next gated launch that skips finished problems seeds it first
+    solution_bound(b);      // the next gated launch that skips finished problems seeds it first
     return RP_OK;
 }
 
@@ -869,16 +895,8 @@ int rp_batch_reduce(rp_batch *b, rp_reduction *out)
 {
     RP_NEED(b);
     if (!out) return fail(RP_ERR_INVALID, "null output");
-    int st = rp_batch_reduce_device(b, b->d_scratch + 4096);
-    if (st != RP_OK) return st;
-    double *h = reinterpret_cast<double *>(b->h_pinned + 64);
-    RP_HIP(hipMemcpyAsync(h, b->d_scratch + 4096, 4 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    RP_HIP(hipStreamSynchronize(b->stream));
-    out->max_residual_sq = h[0];
-    out->max_gap = h[1];
-    out->n_converged = h[2];
-    out->total_steps = h[3];
-    return RP_OK;
+    const int st = rp_batch_reduce_device(b, b->d_scratch + 4096);
+    return st == RP_OK ? read_summary(b, out) : st;
 }
 
 int rp_batch_summary_device(rp_batch *b, double **d_out4)
@@ -895,14 +913,7 @@ int rp_batch_summary_read(rp_batch *b, rp_reduction *out)
 {
     RP_NEED(b);
     if (!out) return fail(RP_ERR_INVALID, "null output");
-    double *h = reinterpret_cast<double *>(b->h_pinned + 64);
-    RP_HIP(hipMemcpyAsync(h, b->d_scratch + 4096, 4 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    RP_HIP(hipStreamSynchronize(b->stream));
-    out->max_residual_sq = h[0];
-    out->max_gap = h[1];
-    out->n_converged = h[2];
-    out->total_steps = h[3];
-    return RP_OK;
+    return read_summary(b, out);
 }
 
 int rp_batch_sample(rp_batch *b, double *pos66, double *acc4)
@@ -926,7 +937,7 @@ int rp_batch_sample_device(rp_batch *b, double *d_pos66, double *d_acc4)
     RP_NEED_STATE(b);
     if (!d_pos66 || !d_acc4) return fail(RP_ERR_INVALID, "null output");
     if (((uintptr_t)d_pos66 & 15u) != 0) return fail(RP_ERR_INVALID, "d_pos66 must be 16-byte aligned (the positions are written as 16-byte vectors)");
-    if (b->view.scheduled && b->view.zero_end_vel && b->records_current && !b->raw_positions_out && b->view.records) {
+    if (samples_through_records(b)) {
         // a whole scheduled batch whose positions are still the ones it was given: through problem-order records (two coalesced
         // sectors per problem) instead of the per-field gather; same arithmetic, same bits
         if (!b->d_solscratch) RP_HIP(hipMalloc((void **)&b->d_solscratch, b->view.n * sizeof(rp::Solution)));
@@ -943,33 +954,25 @@ int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66
     RP_NEED_STATE(b);
     int st = check_range(b, first, count, pos66);
     if (st == RP_OK && !acc4) st = fail(RP_ERR_INVALID, "null output");
-    if (st == RP_OK) st = need_range(b);
     if (st != RP_OK) return st;
-    for (size_t done = 0; done < count; done += kRangeChunk) {
-        const size_t c = count - done < kRangeChunk ? count - done : kRangeChunk;
-        double *d_pos = b->d_range, *d_acc = b->d_range + kRangeChunk * 66;
-        RP_HIP(rp::launch_sample_range(b->view, first + done, c, d_pos, d_acc, b->stream));
-        RP_HIP(hipMemcpyAsync(pos66 + done * 66, d_pos, c * 66 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        RP_HIP(hipMemcpyAsync(acc4 + done * 4, d_acc, c * 4 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        RP_HIP(hipStreamSynchronize(b->stream));
-    }
-    return RP_OK;
+    const size_t acc_at = kRangeChunk * 66;      // the staging buffer holds a chunk's positions, then its accelerations
+    return read_range(b, first, count,
+                      [&](size_t f, size_t c) { return rp::launch_sample_range(b->view, f, c, b->d_range, b->d_range + acc_at, b->stream); },
+                      [&](size_t done, size_t c) {
+                          const hipError_t e = hipMemcpyAsync(pos66 + done * 66, b->d_range, c * 66 * sizeof(double), hipMemcpyDeviceToHost, b->stream);
+                          return e != hipSuccess ? e : hipMemcpyAsync(acc4 + done * 4, b->d_range + acc_at, c * 4 * sizeof(double), hipMemcpyDeviceToHost, b->stream);
+                      });
 }
 
 int rp_batch_constraints_range(rp_batch *b, size_t first, size_t count, double *rows)
 {
     RP_NEED_STATE(b);
-    int st = check_range(b, first, count, rows);
-    if (st == RP_OK) st = need_range(b);
+    const int st = check_range(b, first, count, rows);
     if (st != RP_OK) return st;
     const size_t row = 1 + 14 * (size_t)rp::num_constraints(b->view.variant);
-    for (size_t done = 0; done < count; done += kRangeChunk) {
-        const size_t c = count - done < kRangeChunk ? count - done : kRangeChunk;
-        RP_HIP(rp::launch_constraint_table(b->view, b->params, first + done, c, b->d_range, b->stream));
-        RP_HIP(hipMemcpyAsync(rows + done * row, b->d_range, c * row * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        RP_HIP(hipStreamSynchronize(b->stream));
-    }
-    return RP_OK;
+    return read_range(b, first, count,
+                      [&](size_t f, size_t c) { return rp::launch_constraint_table(b->view, b->params, f, c, b->d_range, b->stream); },
+                      [&](size_t done, size_t c) { return hipMemcpyAsync(rows + done * row, b->d_range, c * row * sizeof(double), hipMemcpyDeviceToHost, b->stream); });
 }
 
 int rp_batch_sync(rp_batch *b)
@@ -1012,22 +1015,9 @@ int rp_batch_field_ptr(rp_batch *b, int field, void **d_ptr)
 {
     if (!b || !d_ptr) return fail(RP_ERR_INVALID, "null argument");
     if (field < 0 || field >= rp::state_len(b->view.variant)) return fail(RP_ERR_INVALID, "field %d out of range", field);
-    {   // the caller is about to look at (or write) raw state: it has to exist
-        RP_HIP(hipSetDevice(b->device));
-        const int ms = materialize(b);
-        if (ms != RP_OK) return ms;
-    }
-    *d_ptr = (char *)b->view.base + (size_t)field * b->view.stride * elem_size(b->view.dtype);
-    b->records_current = false;      // the caller may write through the pointer
-    b->sol_stale = true;
-    if (field >= 3 + rp::num_constraints(b->view.variant)) b->raw_positions_out = true;      // ... now or at any later time: sticky (see the struct)
-    else b->raw_state_out = true;                                                            // ... and so may the state: every later gated launch seeds a bound buffer first
-    b->unpredicted = true;
-    {   // a caller holding a raw pointer to an end-velocity field may write non-zero values the batch never sees: from
-        // here on (until the next init / set_problems / set_state) the Newton kernels read vel0X and vel2X
-        const int iv0 = 3 + rp::num_constraints(b->view.variant) + 1, iv2 = iv0 + 3;
-        if (field == iv0 || field == iv2) b->view.zero_end_vel = false;
-    }
+    RP_NEED_STATE(b);      // the caller is about to look at (or write) raw state: it has to exist
+    *d_ptr = (char *)b->view.base + (size_t)field * b->view.stride * rp::storage_size(b->view.dtype);
+    raw_pointer_out(b, field);
     return RP_OK;
 }
 

@@ -1029,9 +1029,10 @@ def _unpredicted_states(oracle, n, seed, family):
 @pytest.mark.parametrize("family", ["multipliers", "vel1", "durations"])
 def test_gated_solve_in_rounds_gives_every_problem_the_steps_of_the_single_launch(oracle, family):
     # states entered through set_state (multipliers != 1, a nudged velocity, nudged durations) have step counts the
-    # scheduled order does not predict -- a few problems need 60 or 200 steps and hold their wave's other 63 lanes.  The fused solve then
-    # runs in rounds (rp_params.handoff_rounds, automatic after set_state): waves hand their last stragglers off, later launches pack
-    # them densely.  Which lane runs a problem changes nothing: states, multipliers, iteration counts, status words and the bound
+    # scheduled order does not predict -- a few problems need 60 or 200 steps and hold their wave's other 63 lanes.  On request the fused
+    # solve runs in rounds (rp_params.handoff_rounds = 2..8; 0, the default, watches for fixed points in one launch after a set_state):
+    # waves hand their last stragglers off, later launches pack them densely.
+    # Which lane runs a problem changes nothing: states, multipliers, iteration counts, status words and the bound
     # solution records must be bit for bit those of ONE launch (handoff_rounds = -1), for every round count, a small lane threshold,
     # a step budget that ends mid-solve, and a resumed solve.  The oracle checks the answers themselves.
     from hip_util import DeviceBuffer
