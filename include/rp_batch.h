@@ -53,7 +53,9 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      rp_batch_solution_jacobian (the forward-mode derivative and the per-problem 3 x 3 Jacobian; new entries only);
  *      rp_batch_solution_hessian (the per-problem second derivatives; new entries only); rp_batch_set_problems_vel(_device),
  *      rp_batch_solution_vjp_vel, rp_batch_solution_jvp_vel and rp_batch_solution_jacobian_vel (problems with end velocities and the
- *      first derivatives in them; new entries only) */
+ *      first derivatives in them; new entries only); rp_trajectory_eval, rp_trajectory_eval_vjp, rp_trajectory_eval_jvp and
+ *      rp_batch_trajectory_device (a solved spline at the caller's own times, and the first derivatives of that evaluation; new entries
+ *      only) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -320,7 +322,48 @@ RP_API int rp_batch_sample(rp_batch *b, double *pos66, double *acc4);
 /* d_pos66 must be 16-byte aligned (positions are written as 16-byte vectors): RP_ERR_INVALID otherwise. */
 RP_API int rp_batch_sample_device(rp_batch *b, double *d_pos66, double *d_acc4);
 
-/* The same for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
+/* ---- a solved spline at the caller's own times (new: the reference only draws it, drawSegment, onedpath_ip.cpp:1065-1088) ----
+ * Position, velocity and acceleration of the two-segment spline at k times per problem, and the first derivatives of that evaluation
+ * (DESIGN.md section 13).  Stateless: any spline, not only a batch's.  The spline comes as a table of eight pointers to n doubles of
+ * device memory each, in this order wherever such a table appears:
+ *     (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)
+ * -- d_spline[3] and [4] (the end velocities) may be NULL: zeros.  d_tau holds the k query times of every problem, n x k doubles,
+ * row-major, counted from the start of segment 0; every per-query array has that shape.
+ * Segment rule: a query with tau < duration0 lies in segment 0, (pos0, vel0) -> (pos1, vel1) over h = duration0 at s = tau; every other
+ * one in segment 1, (pos1, vel1) -> (pos2, vel2) over h = duration1 at s = tau - duration0.  With (x0, va) -> (x1, vb) the segment's ends:
+ *     acc0 = 6 (x1 - x0) / h^2 - (4 va + 2 vb) / h        jrk0 = 2 (vb - va) / h^2 - 2 acc0 / h
+ *     pos = x0 + (va + (acc0 + jrk0 s / 3) s / 2) s       vel = va + (acc0 + jrk0 s / 2) s       acc = acc0 + jrk0 s
+ * (the cubic of onedpath_ip.cpp:1065-1088; divisions as refined reciprocals, the arithmetic of rp_batch_sample_device).  acc jumps at
+ * the knot as the model's does; derivatives there are the selected segment's.
+ * Extrapolation rule: no clamping -- outside [0, duration0 + duration1] the end segments' cubics continue.
+ * NaN rule: a problem with a duration that is not finite or not > 0 gets NaN in all its outputs (rp_batch_solution_vjp_vel's rule); a
+ * NaN tau gives NaN for that query only (in the VJP, the sums of its problem are NaN with it).
+ * A NULL output is not wanted and costs no traffic; at least one must be given.  Every n x k array must be 16-byte aligned (the queries
+ * move as 16-byte vectors), n and k positive, k < 2^31: RP_ERR_INVALID otherwise, as for a NULL required pointer, before any device
+ * call.  `stream` is a hipStream_t of `device`, NULL the device's null stream.  Asynchronous; never throws. */
+RP_API int rp_trajectory_eval(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau,
+                              double *d_pos, double *d_vel, double *d_acc);
+/* Reverse mode: upstream gradients on pos, vel, acc (n x k each; NULL: zeros, not read -- the same bits as explicit zeros) in, the
+ * gradients of the eight spline inputs (n doubles each, the table's order; any entry, or the table, NULL: not wanted) and of tau
+ * (n x k; NULL: not wanted) out.  Per query tau_bar = g_pos vel + g_vel acc + g_acc jrk0; per problem the k queries reduce to nine
+ * sums in an order that depends on k alone -- no atomics: a problem's gradient is the same bits in a batch of 1 and of 2^20, and from
+ * run to run -- and the chain rule through (acc0, jrk0) runs once.  pos1_bar and vel1_bar collect both segments;
+ * duration0_bar also -(the sum of tau_bar over segment 1's queries). */
+RP_API int rp_trajectory_eval_vjp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau,
+                                  const double *d_g_pos, const double *d_g_vel, const double *d_g_acc,
+                                  double *const d_spline_bar[8], double *d_tau_bar);
+/* Forward mode, the transpose, pointwise: tangents on the eight spline inputs (any entry, or the table, NULL: zeros) and on tau
+ * (NULL: zeros) in, tangents of pos, vel, acc out (NULL: not wanted; at least one). */
+RP_API int rp_trajectory_eval_jvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau,
+                                  const double *const d_spline_dot[8], const double *d_tau_dot,
+                                  double *d_pos_dot, double *d_vel_dot, double *d_acc_dot);
+/* The arbitrary-time sibling of rp_batch_sample_device: rp_trajectory_eval of the batch's current state, PROBLEM order, every variant
+ * and dtype (the state read in the batch's storage type, evaluated in double: bit for bit rp_trajectory_eval on what
+ * rp_batch_get_state returns).  d_tau and the outputs: n x k doubles, 16-byte aligned, with rp_trajectory_eval's segment, extrapolation,
+ * NaN and NULL rules.  Asynchronous on the batch stream; works on any state. */
+RP_API int rp_batch_trajectory_device(rp_batch *b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc);
+
+/* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);
 /* The rest of printState for problems [first, first + count): `Surrogate gap` and the `Constraints:` table
  * (printConstraints, onedpath_ip.cpp:955-995, 1008-1010).  Per problem 1 + 14 m doubles (m = 8 for F3, 4 for F4):

@@ -5,6 +5,8 @@
     vel1, duration0, duration1, iters, status, jac = min_time_jacobian(pos0, pos1, pos2)      # jac: (n, 3, 3)
     vel1, duration0, duration1, iters, status, jac, hess = min_time_hessian(pos0, pos1, pos2)      # hess: (n, 3, 3, 3)
     vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2, vel0=vel0, vel2=vel2)      # end velocities
+    pos, vel, acc = trajectory_eval(pos0, pos1, pos2, vel1, duration0, duration1, tau)      # the spline at the caller's times, (n, k) each
+    pos, vel, acc, vel1, duration0, duration1, iters, status = min_time_trajectory(pos0, pos1, pos2, tau)      # solve, then evaluate
 
 The forward is Batch.set_problems_device + the fused gated solve + Batch.solution_device into a torch buffer, enqueued without
 synchronising the host.  The backward is one rp_batch_solution_vjp launch at the state the forward left, the forward-mode rule
@@ -16,6 +18,10 @@ rp_batch_solution_jvp and one rp_batch_solution_hessian launch.  F3, float64 onl
 With end velocities (vel0= / vel2=) the forward is Batch.set_problems_vel_device instead, and the derivatives
 in all five inputs come from rp_batch_solution_vjp_vel / rp_batch_solution_jvp_vel (first order only: a double backward raises
 torch's once_differentiable error).  Without them the code path is the rest-to-rest one above, unchanged.
+
+trajectory_eval is stateless: one rp_trajectory_eval launch on the current stream, differentiable to first order
+in all eight spline inputs and in tau through one rp_trajectory_eval_vjp (backward) or rp_trajectory_eval_jvp (forward mode) launch.
+min_time_trajectory composes it with min_time_solve, whose derivatives supply the rest of the chain.
 """
 import ctypes
 import threading
@@ -408,6 +414,126 @@ def min_time_hessian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=Non
     not synchronise the host.  With end velocities (vel0= / vel2=, as min_time_solve's) jac is min_time_jacobian's (n, 3, 5) and hess
     the second derivatives in the positions only, at that state (one Hessian and one Jacobian launch)."""
     return _solve_detached("min_time_hessian", pos0, pos1, pos2, gap_tol, max_iter, params, vel0, vel2, hessian=True)
+
+
+# ---- the solved spline at the caller's own times ----
+# (tables of eight tensors are in the C ABI's order: pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)
+def _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0, vel2, who):
+    """The evaluator's arguments in the style of _check_positions; returns tau as (n, k) (a (k,) tau is broadcast)."""
+    _check_positions(pos0, pos1, pos2, who)
+    for name, t in (("vel1", vel1), ("duration0", duration0), ("duration1", duration1)):
+        _check_is_tensor(name, t, who)
+        if t.device.type != "cuda" or t.device != pos0.device:
+            raise TypeError(who + ": %s is on %s; it must be on the positions' ROCm device %s" % (name, t.device, pos0.device))
+        _check_is_float64(name, t, who)
+        if t.shape != pos0.shape:
+            raise ValueError(who + ": %s has shape %s, the positions %s" % (name, tuple(t.shape), tuple(pos0.shape)))
+    _check_velocities(pos0, vel0, vel2, who)
+    return _check_tau(pos0, tau, who)
+
+
+def _check_tau(pos0, tau, who):
+    """tau against the (checked) positions; returns it as (n, k) (a (k,) tau is broadcast)."""
+    _check_is_tensor("tau", tau, who)
+    if tau.device.type != "cuda" or tau.device != pos0.device:
+        raise TypeError(who + ": tau is on %s; it must be on the positions' ROCm device %s" % (tau.device, pos0.device))
+    _check_is_float64("tau", tau, who)
+    n = pos0.shape[0]
+    if tau.dim() == 1 and tau.shape[0] > 0:
+        return tau.unsqueeze(0).expand(n, tau.shape[0])
+    if tau.dim() != 2 or tau.shape[0] != n or tau.shape[1] == 0:
+        raise ValueError(who + ": tau must have shape (%d, k) or (k,) with k >= 1, got %s" % (n, tuple(tau.shape)))
+    return tau
+
+
+def _trajectory_launch(entry, device, spline, tau, *rest):
+    """One rp_trajectory_* launch on the current stream of `device`, no host synchronisation.  spline: the eight tensors (None: NULL);
+    rest: the entry's remaining arguments, tensors, None or lists of eight of them (tables)."""
+    addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+    n, k = tau.shape
+    with torch.cuda.device(device):      # the entry selects the device for its thread: put torch's choice back afterwards
+        stream = torch.cuda.current_stream(device).cuda_stream
+        entry(device.index, stream, n, k, [addr(t) for t in spline], addr(tau),
+              *[[addr(t) for t in a] if isinstance(a, (list, tuple)) else addr(a) for a in rest])
+
+
+def _dense(t):
+    return t.contiguous() if t is not None else None
+
+
+class _TrajectoryEval(torch.autograd.Function):
+    """(pos, vel, acc) of the spline at tau: differentiable to first order in the eight spline inputs (the table's order) and in tau."""
+
+    @staticmethod
+    def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, tau):
+        spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
+        tau = tau.contiguous()
+        outs = [torch.empty(tau.shape, dtype=torch.float64, device=tau.device) for _ in range(3)]
+        _trajectory_launch(capi.trajectory_eval, tau.device, spline, tau, *outs)
+        return tuple(outs)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None and goes to the kernel as NULL: not read
+        ctx.given = [t is not None for t in inputs]
+        kept = [t for t in inputs if t is not None]
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _inputs(ctx):
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        return [_dense(t) for t in inputs[:8]], inputs[8].contiguous()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_pos, g_vel, g_acc):
+        if g_pos is None and g_vel is None and g_acc is None:
+            return (None,) * 9
+        spline, tau = _TrajectoryEval._inputs(ctx)
+        n = tau.shape[0]
+        bars = [torch.empty(n, dtype=torch.float64, device=tau.device) if need else None for need in ctx.needs_input_grad[:8]]
+        tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if ctx.needs_input_grad[8] else None
+        _trajectory_launch(capi.trajectory_eval_vjp, tau.device, spline, tau, _dense(g_pos), _dense(g_vel), _dense(g_acc), bars, tau_bar)
+        return tuple(bars) + (tau_bar,)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        spline, tau = _TrajectoryEval._inputs(ctx)
+        dots = [_dense(t) for t in tangents]
+        outs = [torch.empty(tau.shape, dtype=torch.float64, device=tau.device) for _ in range(3)]
+        _trajectory_launch(capi.trajectory_eval_jvp, tau.device, spline, tau, dots[:8], dots[8], *outs)
+        return tuple(outs)
+
+
+def trajectory_eval(pos0, pos1, pos2, vel1, duration0, duration1, tau, *, vel0=None, vel2=None):
+    """Position, velocity and acceleration of the two-segment spline (pos0, vel0) -> (pos1, vel1) -> (pos2, vel2) with the durations
+    duration0, duration1 -- 1-D float64 tensors on one ROCm device; vel0 / vel2 of None count as zeros -- at the times tau, (n, k) or
+    (k,) (the same times for every problem), counted from the start of segment 0.  Returns (pos, vel, acc), (n, k) each.
+
+    One rp_trajectory_eval launch on the current stream (include/rp_batch.h: tau < duration0 selects segment 0; no clamping, outside
+    [0, duration0 + duration1] the end segments' cubics continue; a problem with a duration that is not finite or not > 0 is NaN).
+    Differentiable to first order in all eight spline inputs and in tau: reverse mode is one rp_trajectory_eval_vjp launch (tau's
+    gradient is formed only when tau requires it; a double backward raises torch's once_differentiable error), forward mode
+    (torch.autograd.forward_ad, torch.func.jvp) one rp_trajectory_eval_jvp launch.  Does not synchronise the host."""
+    tau = _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0, vel2, "trajectory_eval")
+    return _TrajectoryEval.apply(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, tau)
+
+
+def min_time_trajectory(pos0, pos1, pos2, tau, *, normalized=False, vel0=None, vel2=None, gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve, then trajectory_eval of its solution at tau ((n, k) or (k,)): returns (pos, vel, acc, vel1, duration0, duration1,
+    iters, status).  normalized=True: tau is a fraction of each problem's total time (0: the start, 1: the end), multiplied by
+    duration0 + duration1 in torch, so that its dependence on the solution is differentiated too.  Plain composition: pos, vel and acc
+    are differentiable in the positions, the end velocities and tau through the solve's derivatives and the evaluator's."""
+    _check_positions(pos0, pos1, pos2, "min_time_trajectory")
+    tau = _check_tau(pos0, tau, "min_time_trajectory")      # before the solve: a bad tau costs none
+    vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2, gap_tol=gap_tol, max_iter=max_iter, params=params,
+                                                                vel0=vel0, vel2=vel2)
+    if normalized:
+        tau = tau * (duration0 + duration1).unsqueeze(1)
+    pos, vel, acc = trajectory_eval(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0=vel0, vel2=vel2)
+    return pos, vel, acc, vel1, duration0, duration1, iters, status
 
 
 def clear_pool():

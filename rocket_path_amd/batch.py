@@ -234,6 +234,12 @@ class Batch:
         """The same into device memory (addresses of n x 66 and n x 4 doubles), asynchronously on the batch stream."""
         capi.check(self._lib.rp_batch_sample_device(self._h, ctypes.c_void_p(d_pos66), ctypes.c_void_p(d_acc4)))
 
+    def trajectory_device(self, d_tau, k, d_pos=None, d_vel=None, d_acc=None):
+        """Position, velocity and acceleration of the batch's current state at k times per problem (rp_batch_trajectory_device):
+        addresses of (n, k) float64 arrays in device memory, 16-byte aligned, problem order; d_tau counts from the start of segment 0;
+        an output of None / 0 is not wanted.  Asynchronous on the batch stream."""
+        capi.check(self._lib.rp_batch_trajectory_device(self._h, ctypes.c_void_p(d_tau) if d_tau else None, int(k), *_addrs(d_pos, d_vel, d_acc)))
+
     def sample_range(self, first, count):
         pos = np.empty((count, 66), dtype=np.float64)
         acc = np.empty((count, 4), dtype=np.float64)

@@ -99,6 +99,12 @@ SIGNATURES = {
     "rp_batch_summary_read": (ctypes.c_int, [_vp, ctypes.POINTER(Reduction)]),
     "rp_batch_sample": (ctypes.c_int, [_vp, _vp, _vp]),
     "rp_batch_sample_device": (ctypes.c_int, [_vp, _vp, _vp]),
+    "rp_trajectory_eval": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, _vp, _vp]),
+    "rp_trajectory_eval_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, _vp, _vp,
+                                              ctypes.POINTER(_vp), _vp]),
+    "rp_trajectory_eval_jvp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp),
+                                              _vp, _vp, _vp, _vp]),
+    "rp_batch_trajectory_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "rp_batch_sample_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
     "rp_batch_constraints_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rp_batch_sync": (ctypes.c_int, [_vp]),
@@ -151,6 +157,41 @@ def check(status):
     if status != RP_OK:
         lib = load_library()
         raise RpError(status, (lib.rp_last_error() or b"").decode() or lib.rp_status_string(status).decode())
+
+
+def pointer_table(addresses):
+    """Eight device addresses (ints; None / 0: NULL) as the `double *const [8]` tables of the rp_trajectory_* entries, in the order
+    (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1); None gives a NULL table."""
+    if addresses is None:
+        return None
+    addresses = list(addresses)
+    if len(addresses) != 8:
+        raise ValueError("a spline table has eight entries, got %d" % len(addresses))
+    return (_vp * 8)(*[a if a else None for a in addresses])
+
+
+def _trajectory(entry, device, stream, n, k, spline, d_tau, *rest):
+    args = [pointer_table(a) if isinstance(a, (list, tuple)) else (ctypes.c_void_p(a) if a else None) for a in rest]
+    check(getattr(load_library(), entry)(int(device), ctypes.c_void_p(stream) if stream else None, int(n), int(k), pointer_table(spline),
+                                        ctypes.c_void_p(d_tau) if d_tau else None, *args))
+
+
+def trajectory_eval(device, stream, n, k, spline, d_tau, d_pos=None, d_vel=None, d_acc=None):
+    """rp_trajectory_eval on device addresses (ints; None / 0: NULL): `spline` the eight addresses of (pos0, pos1, pos2, vel0, vel2, vel1,
+    duration0, duration1), d_tau and the outputs (n, k) float64.  Asynchronous on `stream` (None: the null stream)."""
+    _trajectory("rp_trajectory_eval", device, stream, n, k, spline, d_tau, d_pos, d_vel, d_acc)
+
+
+def trajectory_eval_vjp(device, stream, n, k, spline, d_tau, d_g_pos=None, d_g_vel=None, d_g_acc=None, spline_bar=None, d_tau_bar=None):
+    """rp_trajectory_eval_vjp: upstream gradients in (None: zeros), `spline_bar` the eight output addresses (None entries: not wanted)."""
+    _trajectory("rp_trajectory_eval_vjp", device, stream, n, k, spline, d_tau, d_g_pos, d_g_vel, d_g_acc,
+                list(spline_bar) if spline_bar is not None else None, d_tau_bar)
+
+
+def trajectory_eval_jvp(device, stream, n, k, spline, d_tau, spline_dot=None, d_tau_dot=None, d_pos_dot=None, d_vel_dot=None, d_acc_dot=None):
+    """rp_trajectory_eval_jvp: `spline_dot` the eight tangent addresses (None entries: zeros), tangents of pos, vel, acc out."""
+    _trajectory("rp_trajectory_eval_jvp", device, stream, n, k, spline, d_tau, list(spline_dot) if spline_dot is not None else None,
+                d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot)
 
 
 def device_count():

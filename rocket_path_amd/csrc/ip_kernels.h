@@ -143,4 +143,17 @@ hipError_t launch_soa_to_aos_range(const BatchView &b, size_t first, size_t coun
 hipError_t launch_sample_range(const BatchView &b, size_t first, size_t count, double *d_pos66, double *d_acc4, hipStream_t stream);
 hipError_t launch_constraint_table(const BatchView &b, const HostParams &hp, size_t first, size_t count, double *d_rows, hipStream_t stream);
 
+
+// a spline evaluated at the caller's times, and the evaluation's first derivatives (trajectory.hip).  Tables of eight pointers are
+// (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1), n doubles each in problem order; d_tau and everything per query
+// n x k doubles, row-major, 16-byte aligned; k < 2^31.  Null pointers as include/rp_batch.h says.
+hipError_t launch_trajectory_eval(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, double *d_pos, double *d_vel,
+                                  double *d_acc, hipStream_t stream);
+hipError_t launch_trajectory_vjp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *d_g_pos,
+                                 const double *d_g_vel, const double *d_g_acc, double *const d_spline_bar[8], double *d_tau_bar, hipStream_t stream);
+hipError_t launch_trajectory_jvp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *const d_spline_dot[8],
+                                 const double *d_tau_dot, double *d_pos_dot, double *d_vel_dot, double *d_acc_dot, hipStream_t stream);
+// the same evaluation of the batch's current state, problem order, every variant and dtype (the staging of launch_sample_range)
+hipError_t launch_trajectory_batch(const BatchView &b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc, hipStream_t stream);
+
 }  // namespace rp

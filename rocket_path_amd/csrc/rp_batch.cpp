@@ -949,6 +949,93 @@ int rp_batch_sample_device(rp_batch *b, double *d_pos66, double *d_acc4)
     return RP_OK;
 }
 
+// ---- a spline at the caller's own times (trajectory.hip) ----
+namespace {
+
+bool misaligned16(const void *p) { return ((uintptr_t)p & 15u) != 0; }
+
+// what the four trajectory entries check before any device call: the sizes, the times, and the 16-byte alignment of everything that
+// is read or written per query (null: not given)
+int check_queries(const char *who, size_t n, size_t k, const double *d_tau, const void *const per_query[], int count)
+{
+    if (n == 0 || k == 0) return fail(RP_ERR_INVALID, "%s: n and k must be positive", who);
+    if (k >= ((size_t)1 << 31)) return fail(RP_ERR_INVALID, "%s: k must be below 2^31", who);
+    if (n > SIZE_MAX / sizeof(double) / k) return fail(RP_ERR_INVALID, "%s: n x k does not fit", who);
+    if (!d_tau) return fail(RP_ERR_INVALID, "%s: d_tau is null", who);
+    if (misaligned16(d_tau)) return fail(RP_ERR_INVALID, "%s: d_tau must be 16-byte aligned (the queries move as 16-byte vectors)", who);
+    for (int i = 0; i < count; ++i)
+        if (misaligned16(per_query[i])) return fail(RP_ERR_INVALID, "%s: every n x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
+    return RP_OK;
+}
+
+int check_spline(const char *who, int device, const double *const d_spline[8])
+{
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", who, device);
+    if (!d_spline) return fail(RP_ERR_INVALID, "%s: d_spline is null", who);
+    for (int f = 0; f < 8; ++f)
+        if (!d_spline[f] && f != 3 && f != 4) return fail(RP_ERR_INVALID, "%s: d_spline[%d] is null (only the end velocities, [3] and [4], may be)", who, f);
+    return RP_OK;
+}
+
+}  // namespace
+
+int rp_trajectory_eval(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau, double *d_pos,
+                       double *d_vel, double *d_acc)
+{
+    const void *const per_query[] = {d_pos, d_vel, d_acc};
+    int st = check_spline(__func__, device, d_spline);
+    if (st == RP_OK) st = check_queries(__func__, n, k, d_tau, per_query, 3);
+    if (st != RP_OK) return st;
+    if (!d_pos && !d_vel && !d_acc) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_trajectory_eval(n, k, d_spline, d_tau, d_pos, d_vel, d_acc, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_trajectory_eval_vjp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau,
+                           const double *d_g_pos, const double *d_g_vel, const double *d_g_acc, double *const d_spline_bar[8], double *d_tau_bar)
+{
+    const void *const per_query[] = {d_g_pos, d_g_vel, d_g_acc, d_tau_bar};
+    int st = check_spline(__func__, device, d_spline);
+    if (st == RP_OK) st = check_queries(__func__, n, k, d_tau, per_query, 4);
+    if (st != RP_OK) return st;
+    double *const none[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double *const *bars = d_spline_bar ? d_spline_bar : none;
+    bool any = d_tau_bar != nullptr;
+    for (int f = 0; f < 8; ++f) any = any || bars[f];
+    if (!any) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_trajectory_vjp(n, k, d_spline, d_tau, d_g_pos, d_g_vel, d_g_acc, bars, d_tau_bar, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_trajectory_eval_jvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau,
+                           const double *const d_spline_dot[8], const double *d_tau_dot, double *d_pos_dot, double *d_vel_dot, double *d_acc_dot)
+{
+    const void *const per_query[] = {d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot};
+    int st = check_spline(__func__, device, d_spline);
+    if (st == RP_OK) st = check_queries(__func__, n, k, d_tau, per_query, 4);
+    if (st != RP_OK) return st;
+    if (!d_pos_dot && !d_vel_dot && !d_acc_dot) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
+    const double *const none[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_trajectory_jvp(n, k, d_spline, d_tau, d_spline_dot ? d_spline_dot : none, d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot,
+                                     (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_batch_trajectory_device(rp_batch *b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc)
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    const void *const per_query[] = {d_pos, d_vel, d_acc};
+    const int st = check_queries(__func__, b->view.n, k, d_tau, per_query, 3);
+    if (st != RP_OK) return st;
+    if (!d_pos && !d_vel && !d_acc) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_trajectory_batch(b->view, d_tau, k, d_pos, d_vel, d_acc, b->stream));
+    return RP_OK;
+}
+
 int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4)
 {
     RP_NEED_STATE(b);

@@ -1,0 +1,498 @@
+// trajectory.hip -- a solved two-segment spline evaluated at the caller's own times, and the first derivatives of that
+// evaluation, gfx950: rp_trajectory_eval, rp_trajectory_eval_vjp, rp_trajectory_eval_jvp and rp_batch_trajectory_device
+// (include/rp_batch.h).
+//
+// Per problem the spline is (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1) -- this order wherever eight pointers travel
+// together -- and the k query times tau[i, j] (row-major n x k) count from the start of segment 0.  A query with tau < duration0
+// lies in segment 0, (pos0, vel0) -> (pos1, vel1) over h = duration0 at s = tau; every other one in segment 1, (pos1, vel1) ->
+// (pos2, vel2) over h = duration1 at s = tau - duration0.  The cubic is the one the reference draws (drawSegment,
+// onedpath_ip.cpp:1065-1088) and k_sample restates (ip_kernels.hip), with k_sample's arithmetic:
+//     acc0 = 6 (x1 - x0) / h^2 - (4 va + 2 vb) / h        jrk0 = 2 (vb - va) / h^2 - 2 acc0 / h
+//     pos = x0 + (va + (acc0 + jrk0 s / 3) s / 2) s       vel = va + (acc0 + jrk0 s / 2) s       acc = acc0 + jrk0 s
+// No clamping: outside [0, duration0 + duration1] the end segments' cubics continue.  A problem with a duration that is not finite
+// or not > 0 gets NaN everywhere (its constants are NaN); a NaN tau gives NaN for that query.
+//
+// All three kernels move 8-32 B per query and ~128 B per problem and do ~20 flops per query: streaming kernels, built the way k_sample
+// was rebuilt.  A block takes P consecutive problems per trip (P a function of k alone, P k ~ 4096 queries); its first P threads
+// read one problem's eight parameters each, do the two reciprocals (rcp_, as k_sample) and leave the per-segment constants and
+// duration0 in LDS; then the block streams.  The grid is capped and strides over the trips.
+//   k_trajectory_eval / k_trajectory_jvp / k_batch_trajectory: pointwise.  The block's P k queries are consecutive elements of
+//     tau (P is even, so a trip starts on a 16-byte boundary): each thread takes two at a time -- one 16-byte load, one 16-byte
+//     nontemporal store per wanted output -- and finds each query's problem by carrying (problem, column) along, without a division.
+//   k_trajectory_vjp: a problem's k queries reduce to nine sums (four per segment, and the sum of tau_bar over segment 1).  A group
+//     of G lanes (a power of two <= 64, from k alone) owns one problem at a time: lane l adds queries l, l + G, l + 2 G, ... (pairs
+//     2 l, 2 l + 1, ... as 16-byte vectors when k is even -- every row then starts on a 16-byte boundary; single elements when k is
+//     odd) in that order into its own nine sums, the lanes combine by an xor butterfly (a + b == b + a bit for bit: every lane holds
+//     the same sums), and lane 0 runs the chain rule once.  The order of every addition is a function of k: a problem's gradient is
+//     the same bits in any batch, in any block, in every run.  No atomics.
+// A null output is not written, a null gradient or tangent is not read and counts as zeros -- as the VALUE zero in the same
+// expression, so that null and explicit zeros give the same bits.
+#include "ip_kernels.h"
+
+#include "../../include/rp_batch.h"
+#include "ip_core.h"
+
+namespace rp {
+
+namespace {
+
+constexpr int kTrajBlock = 256;
+constexpr int kTrajProblems = 128;       // the most problems a block stages per trip
+constexpr unsigned kTrajGridCap = 2048;  // 256 CUs x 8 blocks: the blocks stride over the rest
+constexpr size_t kTrajTrip = 4096;       // queries per trip a block aims at
+
+typedef double v2 __attribute__((ext_vector_type(2)));
+
+struct Spline8 { const double *p[8]; };      // pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1
+struct SplineBar8 { double *p[8]; };
+
+__device__ __forceinline__ double quiet_nan() { return __builtin_nan(""); }
+
+// one problem's eight numbers in the order the segments use them
+struct Knots {
+    double p0, p1, p2, v0, v2, v1, t0, t1;
+    // the NaN rule: a duration that is not finite or not > 0 poisons both (then every constant of the problem, then every output)
+    __device__ __forceinline__ void check()
+    {
+        if (!(finite_(t0) && t0 > 0.0 && finite_(t1) && t1 > 0.0)) t0 = t1 = quiet_nan();
+    }
+};
+
+// where a problem's eight numbers come from: eight arrays in problem order (the stateless entries) ...
+struct FromArrays {
+    Spline8 s;
+    __device__ __forceinline__ Knots load(size_t i) const
+    {
+        Knots k;
+        k.p0 = s.p[0][i]; k.p1 = s.p[1][i]; k.p2 = s.p[2][i];
+        k.v0 = s.p[3] ? s.p[3][i] : 0.0; k.v2 = s.p[4] ? s.p[4][i] : 0.0;
+        k.v1 = s.p[5][i]; k.t0 = s.p[6][i]; k.t1 = s.p[7][i];
+        return k;
+    }
+};
+
+// ... or a batch's fields, gathered through the slot map in the batch's storage type (k_sample's reads)
+template <typename S, int VARIANT, bool ZV> struct FromBatch {
+    const S *base;
+    size_t stride;
+    const uint32_t *slot_of;
+    __device__ __forceinline__ Knots load(size_t i) const
+    {
+        constexpr int CB = 3 + CMap<VARIANT>::NC;
+        const S *f = base + (slot_of ? (size_t)slot_of[i] : i);
+        Knots k;
+        k.v1 = (double)f[0]; k.t0 = (double)f[1 * stride]; k.t1 = (double)f[2 * stride];
+        k.p0 = (double)f[(CB + 0) * stride]; k.p1 = (double)f[(CB + 2) * stride]; k.p2 = (double)f[(CB + 3) * stride];
+        k.v0 = ZV ? 0.0 : (double)f[(CB + 1) * stride]; k.v2 = ZV ? 0.0 : (double)f[(CB + 4) * stride];
+        return k;
+    }
+};
+
+// the constants of one segment, k_sample's arithmetic: ih = 1 / h (rcp_)
+__device__ __forceinline__ void segment_constants(double x0, double x1, double va, double vb, double ih, double &acc0, double &jrk0)
+{
+    const double ih2 = ih * ih;
+    acc0 = (x1 - x0) * (6.0 * ih2) - (va * 4.0 + vb * 2.0) * ih;
+    jrk0 = (vb - va) * (2.0 * ih2) - acc0 * (2.0 * ih);
+}
+
+__device__ __forceinline__ int problems_here(size_t n, size_t p_first, int P)
+{
+    return (int)(n - p_first < (size_t)P ? n - p_first : (size_t)P);
+}
+
+// The streaming loop of the pointwise kernels: the block's `here` x k queries, consecutive from element p_first * k (even), two per
+// thread and trip; f(element, problem within the block, second?) handles one query, g(pair) moves a pair's 16 bytes.
+// (problem, column) of a thread's first query of the pair come from one division per trip and are carried from pair to pair.
+template <class Pair> __device__ __forceinline__ void stream_pairs(int here, size_t k, Pair pair)
+{
+    const size_t count = (size_t)here * k;
+    const uint32_t step = 2 * kTrajBlock, k32 = (uint32_t)k;      // k < 2^31 (the entries refuse more): 32-bit problem and column
+    const uint32_t dq = step / k32, dr = step - dq * k32;          // uniform
+    size_t e = 2 * (size_t)threadIdx.x;
+    uint32_t q = (uint32_t)e / k32, r = (uint32_t)e - q * k32;
+    for (; e + 1 < count; e += step) {
+        pair(e, (int)q, (int)(r + 1 == k32 ? q + 1 : q), true);
+        q += dq;
+        r += dr;
+        if (r >= k32) { r -= k32; ++q; }
+    }
+    if (e < count) pair(e, (int)q, (int)q, false);      // the last query of an odd total (the last trip of the launch only)
+}
+
+// ---- forward ----
+struct EvalLds {
+    double c[2][4][kTrajProblems];      // per segment: x0, va, acc0, jrk0
+    double d0[kTrajProblems];
+};
+
+__device__ __forceinline__ void stage_eval(EvalLds &L, int q, Knots kn)
+{
+    kn.check();
+    const double ih0 = rcp_<double>(kn.t0), ih1 = rcp_<double>(kn.t1);
+    double acc0, jrk0;
+    segment_constants(kn.p0, kn.p1, kn.v0, kn.v1, ih0, acc0, jrk0);
+    L.c[0][0][q] = kn.p0; L.c[0][1][q] = kn.v0; L.c[0][2][q] = acc0; L.c[0][3][q] = jrk0;
+    segment_constants(kn.p1, kn.p2, kn.v1, kn.v2, ih1, acc0, jrk0);
+    L.c[1][0][q] = kn.p1; L.c[1][1][q] = kn.v1; L.c[1][2][q] = acc0; L.c[1][3][q] = jrk0;
+    L.d0[q] = kn.t0;
+}
+
+__device__ __forceinline__ void eval_query(const EvalLds &L, int q, double tau, double &pos, double &vel, double &acc)
+{
+    const double d0 = L.d0[q];
+    const int seg = !(tau < d0);
+    const double s = seg ? tau - d0 : tau;
+    const double x0 = L.c[seg][0][q], va = L.c[seg][1][q], acc0 = L.c[seg][2][q], jrk0 = L.c[seg][3][q];
+    pos = x0 + (va + (acc0 + jrk0 * (s * (1.0 / 3.0))) * (s * 0.5)) * s;
+    vel = va + (acc0 + jrk0 * (s * 0.5)) * s;
+    acc = acc0 + jrk0 * s;
+}
+
+__device__ __forceinline__ void store_pair(double *out, size_t at, double a, double b, bool two)
+{
+    if (two) {
+        const v2 both = {a, b};
+        __builtin_nontemporal_store(both, reinterpret_cast<v2 *>(out + at));
+    } else {
+        out[at] = a;
+    }
+}
+
+__device__ __forceinline__ void load_pair(const double *in, size_t at, bool two, double &a, double &b)
+{
+    if (two) {
+        const v2 both = __builtin_nontemporal_load(reinterpret_cast<const v2 *>(in + at));
+        a = both[0];
+        b = both[1];
+    } else {
+        a = in[at];
+        b = a;
+    }
+}
+
+template <class Stage>
+__device__ __forceinline__ void eval_trips(const Stage &stage, size_t n, size_t k, int P, const double *__restrict__ tau,
+                                           double *__restrict__ pos, double *__restrict__ vel, double *__restrict__ acc)
+{
+    __shared__ EvalLds L;
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        const size_t p_first = trip * (size_t)P;
+        const int here = problems_here(n, p_first, P);
+        if ((int)threadIdx.x < here) stage_eval(L, threadIdx.x, stage.load(p_first + threadIdx.x));
+        __syncthreads();
+        const size_t e_first = p_first * k;
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double ta, tb, pa, va, aa, pb, vb, ab;
+            load_pair(tau, e_first + e, two, ta, tb);
+            eval_query(L, qa, ta, pa, va, aa);
+            eval_query(L, qb, tb, pb, vb, ab);
+            if (pos) store_pair(pos, e_first + e, pa, pb, two);
+            if (vel) store_pair(vel, e_first + e, va, vb, two);
+            if (acc) store_pair(acc, e_first + e, aa, ab, two);
+        });
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_trajectory_eval(FromArrays stage, size_t n, size_t k, int P, const double *__restrict__ tau, double *__restrict__ pos,
+                  double *__restrict__ vel, double *__restrict__ acc)
+{
+    eval_trips(stage, n, k, P, tau, pos, vel, acc);
+}
+
+// the batch's current state, PROBLEM order: only the staging differs
+template <typename S, int VARIANT, bool ZV>
+__global__ void __launch_bounds__(kTrajBlock)
+k_batch_trajectory(FromBatch<S, VARIANT, ZV> stage, size_t n, size_t k, int P, const double *__restrict__ tau, double *__restrict__ pos,
+                   double *__restrict__ vel, double *__restrict__ acc)
+{
+    eval_trips(stage, n, k, P, tau, pos, vel, acc);
+}
+
+// ---- forward mode: tangents on the eight parameters and on tau in, tangents of pos, vel, acc out ----
+struct JvpLds {
+    double c[2][4][kTrajProblems];      // per segment: x0, va, acc0, jrk0 ...
+    double t[2][4][kTrajProblems];      // ... and their tangents
+    double d0[kTrajProblems], d0_dot[kTrajProblems];
+};
+
+// tangents of (acc0, jrk0): d(1/h) = -hd / h^2, d(1/h^2) = -2 hd / h^3
+__device__ __forceinline__ void segment_tangents(double dx, double va, double vb, double acc0, double ih, double dxd, double vad, double vbd,
+                                                 double hd, double &acc0d, double &jrk0d)
+{
+    const double ih2 = ih * ih, ih3 = ih2 * ih;
+    acc0d = dxd * (6.0 * ih2) - dx * (12.0 * ih3) * hd - (vad * 4.0 + vbd * 2.0) * ih + (va * 4.0 + vb * 2.0) * ih2 * hd;
+    jrk0d = (vbd - vad) * (2.0 * ih2) - (vb - va) * (4.0 * ih3) * hd - acc0d * (2.0 * ih) + acc0 * (2.0 * ih2) * hd;
+}
+
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(8)))      // 64 VGPRs: without the hint the allocator stops at 65
+k_trajectory_jvp(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const double *__restrict__ tau, const double *__restrict__ tau_dot,
+                 double *__restrict__ pos_dot, double *__restrict__ vel_dot, double *__restrict__ acc_dot)
+{
+    __shared__ JvpLds L;
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        const size_t p_first = trip * (size_t)P;
+        const int here = problems_here(n, p_first, P);
+        if ((int)threadIdx.x < here) {
+            // one segment at a time (a loop the compiler is told to keep): the sixteen loads of a problem and its tangents, taken at
+            // once, cost the registers of two waves per SIMD.  pos1, vel1 and their tangents are asked for in both passes (same thread,
+            // same address: the second is a cache hit)
+            const int q = threadIdx.x;
+            const size_t i = p_first + q;
+            const Spline8 &s = stage.s;
+            double t0 = s.p[6][i], t1 = s.p[7][i];
+            if (!(finite_(t0) && t0 > 0.0 && finite_(t1) && t1 > 0.0)) t0 = t1 = quiet_nan();
+            const double t0d = dot.p[6] ? dot.p[6][i] : 0.0, t1d = dot.p[7] ? dot.p[7][i] : 0.0;
+            L.d0[q] = t0;
+            L.d0_dot[q] = t0d;
+#pragma nounroll
+            for (int seg = 0; seg < 2; ++seg) {
+                const double *pva = seg ? s.p[5] : s.p[3], *pvb = seg ? s.p[4] : s.p[5];      // vel0, vel1 | vel1, vel2
+                const double *pvad = seg ? dot.p[5] : dot.p[3], *pvbd = seg ? dot.p[4] : dot.p[5];
+                const double *px0 = seg ? s.p[1] : s.p[0], *px1 = seg ? s.p[2] : s.p[1];
+                const double *px0d = seg ? dot.p[1] : dot.p[0], *px1d = seg ? dot.p[2] : dot.p[1];
+                const double x0 = px0[i], x1 = px1[i], va = pva ? pva[i] : 0.0, vb = pvb ? pvb[i] : 0.0;
+                const double x0d = px0d ? px0d[i] : 0.0, x1d = px1d ? px1d[i] : 0.0, vad = pvad ? pvad[i] : 0.0, vbd = pvbd ? pvbd[i] : 0.0;
+                const double ih = rcp_<double>(seg ? t1 : t0);
+                double acc0, jrk0, acc0d, jrk0d;
+                segment_constants(x0, x1, va, vb, ih, acc0, jrk0);
+                segment_tangents(x1 - x0, va, vb, acc0, ih, x1d - x0d, vad, vbd, seg ? t1d : t0d, acc0d, jrk0d);
+                L.c[seg][0][q] = x0; L.c[seg][1][q] = va; L.c[seg][2][q] = acc0; L.c[seg][3][q] = jrk0;
+                L.t[seg][0][q] = x0d; L.t[seg][1][q] = vad; L.t[seg][2][q] = acc0d; L.t[seg][3][q] = jrk0d;
+            }
+        }
+        __syncthreads();
+        const size_t e_first = p_first * k;
+        auto query = [&](int q, double ta, double td, double &pd, double &vd, double &ad) {
+            const double d0 = L.d0[q];
+            const int seg = !(ta < d0);
+            const double s = seg ? ta - d0 : ta, sd = seg ? td - L.d0_dot[q] : td;
+            const double va = L.c[seg][1][q], acc0 = L.c[seg][2][q], jrk0 = L.c[seg][3][q];
+            const double x0d = L.t[seg][0][q], vad = L.t[seg][1][q], acc0d = L.t[seg][2][q], jrk0d = L.t[seg][3][q];
+            const double vel = va + (acc0 + jrk0 * (s * 0.5)) * s, acc = acc0 + jrk0 * s;
+            pd = x0d + (vad + (acc0d + jrk0d * (s * (1.0 / 3.0))) * (s * 0.5)) * s + vel * sd;
+            vd = vad + (acc0d + jrk0d * (s * 0.5)) * s + acc * sd;
+            ad = acc0d + jrk0d * s + jrk0 * sd;
+        };
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double ta, tb, da = 0.0, db = 0.0, pa, va, aa, pb, vb, ab;
+            load_pair(tau, e_first + e, two, ta, tb);
+            if (tau_dot) load_pair(tau_dot, e_first + e, two, da, db);
+            query(qa, ta, da, pa, va, aa);
+            query(qb, tb, db, pb, vb, ab);
+            if (pos_dot) store_pair(pos_dot, e_first + e, pa, pb, two);
+            if (vel_dot) store_pair(vel_dot, e_first + e, va, vb, two);
+            if (acc_dot) store_pair(acc_dot, e_first + e, aa, ab, two);
+        });
+        __syncthreads();
+    }
+}
+
+// ---- reverse mode ----
+// With upstream gradients gp, gv, ga on pos, vel, acc and the sums restricted to the queries of a segment:
+//     tau_bar = gp vel + gv acc + ga jrk0                                               (per query)
+//     S_x = S gp    S_v = S (gp s + gv)    S_a = S (gp s^2 / 2 + gv s + ga)    S_j = S (gp s^3 / 6 + gv s^2 / 2 + ga s)
+//     A = S_a - (2 / h) S_j
+//     x0_bar = S_x - 6 A / h^2      x1_bar = 6 A / h^2
+//     va_bar = S_v - 4 A / h - 2 S_j / h^2      vb_bar = -2 A / h + 2 S_j / h^2
+//     h_bar = A (-12 (x1 - x0) / h^3 + (4 va + 2 vb) / h^2) + S_j (-4 (vb - va) / h^3 + 2 acc0 / h^2)
+// Segment 0 sends them to (pos0, pos1, vel0, vel1, duration0), segment 1 to (pos1, pos2, vel1, vel2, duration1) and takes the sum
+// of its queries' tau_bar off duration0_bar (s = tau - duration0 there).
+struct VjpLds {
+    double c[2][6][kTrajProblems];      // per segment: va, vb, x1 - x0, acc0, jrk0, 1 / h
+    double d0[kTrajProblems];
+    double bar[8][kTrajProblems];       // the problem's eight results, in the pointer table's order
+};
+
+struct SegmentBar { double x0, x1, va, vb, h; };
+
+__device__ __forceinline__ SegmentBar segment_chain(const VjpLds &L, int seg, int q, double Sx, double Sv, double Sa, double Sj)
+{
+    const double va = L.c[seg][0][q], vb = L.c[seg][1][q], dx = L.c[seg][2][q], acc0 = L.c[seg][3][q], ih = L.c[seg][5][q];
+    const double ih2 = ih * ih, ih3 = ih2 * ih;
+    const double A = Sa - (2.0 * ih) * Sj;
+    SegmentBar b;
+    b.x1 = (6.0 * ih2) * A;
+    b.x0 = Sx - b.x1;
+    b.va = Sv - (4.0 * ih) * A - (2.0 * ih2) * Sj;
+    b.vb = (2.0 * ih2) * Sj - (2.0 * ih) * A;
+    b.h = A * ((va * 4.0 + vb * 2.0) * ih2 - dx * (12.0 * ih3)) + Sj * (acc0 * (2.0 * ih2) - (vb - va) * (4.0 * ih3));
+    return b;
+}
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_trajectory_vjp(FromArrays stage, size_t n, size_t k, int P, int G, const double *__restrict__ tau, const double *__restrict__ g_pos,
+                 const double *__restrict__ g_vel, const double *__restrict__ g_acc, SplineBar8 bar, double *__restrict__ tau_bar)
+{
+    __shared__ VjpLds L;
+    const int groups = kTrajBlock / G, group = (int)threadIdx.x / G, lane = (int)threadIdx.x & (G - 1);
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        const size_t p_first = trip * (size_t)P;
+        const int here = problems_here(n, p_first, P);
+        if ((int)threadIdx.x < here) {
+            const int q = threadIdx.x;
+            Knots kn = stage.load(p_first + q);
+            kn.check();
+            const double ih0 = rcp_<double>(kn.t0), ih1 = rcp_<double>(kn.t1);
+            double acc0, jrk0;
+            segment_constants(kn.p0, kn.p1, kn.v0, kn.v1, ih0, acc0, jrk0);
+            L.c[0][0][q] = kn.v0; L.c[0][1][q] = kn.v1; L.c[0][2][q] = kn.p1 - kn.p0; L.c[0][3][q] = acc0; L.c[0][4][q] = jrk0; L.c[0][5][q] = ih0;
+            segment_constants(kn.p1, kn.p2, kn.v1, kn.v2, ih1, acc0, jrk0);
+            L.c[1][0][q] = kn.v1; L.c[1][1][q] = kn.v2; L.c[1][2][q] = kn.p2 - kn.p1; L.c[1][3][q] = acc0; L.c[1][4][q] = jrk0; L.c[1][5][q] = ih1;
+            L.d0[q] = kn.t0;
+        }
+        __syncthreads();
+        for (int q = group; q < here; q += groups) {
+            const size_t row = (p_first + (size_t)q) * k;
+            const double d0 = L.d0[q];
+            double S[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, T1 = 0.0;      // this lane's nine sums
+            auto query = [&](double ta, double gp, double gv, double ga) -> double {
+                const bool seg = !(ta < d0);
+                const double s = seg ? ta - d0 : ta;
+                const double va = L.c[seg][0][q], acc0 = L.c[seg][3][q], jrk0 = L.c[seg][4][q];
+                const double vel = va + (acc0 + jrk0 * (s * 0.5)) * s, acc = acc0 + jrk0 * s;
+                const double tb = gp * vel + gv * acc + ga * jrk0;
+                const double h2 = s * (s * 0.5), h3 = h2 * (s * (1.0 / 3.0));
+                const double w0 = gp, w1 = gp * s + gv, w2 = gp * h2 + gv * s + ga, w3 = gp * h3 + gv * h2 + ga * s;
+                S[0][0] += seg ? 0.0 : w0; S[0][1] += seg ? 0.0 : w1; S[0][2] += seg ? 0.0 : w2; S[0][3] += seg ? 0.0 : w3;
+                S[1][0] += seg ? w0 : 0.0; S[1][1] += seg ? w1 : 0.0; S[1][2] += seg ? w2 : 0.0; S[1][3] += seg ? w3 : 0.0;
+                T1 += seg ? tb : 0.0;
+                return tb;
+            };
+            if ((k & 1) == 0) {      // k even: the row starts on a 16-byte boundary
+                const size_t units = k >> 1;
+                for (size_t u = lane; u < units; u += G) {
+                    const size_t at = row + 2 * u;
+                    double ta, tb, pa = 0.0, pb = 0.0, va = 0.0, vb = 0.0, aa = 0.0, ab = 0.0;
+                    load_pair(tau, at, true, ta, tb);
+                    if (g_pos) load_pair(g_pos, at, true, pa, pb);
+                    if (g_vel) load_pair(g_vel, at, true, va, vb);
+                    if (g_acc) load_pair(g_acc, at, true, aa, ab);
+                    const double ba = query(ta, pa, va, aa);
+                    const double bb = query(tb, pb, vb, ab);
+                    if (tau_bar) store_pair(tau_bar, at, ba, bb, true);
+                }
+            } else {
+                for (size_t u = lane; u < k; u += G) {
+                    const size_t at = row + u;
+                    const double b = query(tau[at], g_pos ? g_pos[at] : 0.0, g_vel ? g_vel[at] : 0.0, g_acc ? g_acc[at] : 0.0);
+                    if (tau_bar) tau_bar[at] = b;
+                }
+            }
+            // the group's lanes combine: after the butterfly every lane holds the same nine sums
+            for (int m = 1; m < G; m <<= 1) {
+#pragma unroll
+                for (int seg = 0; seg < 2; ++seg)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) S[seg][c] += __shfl_xor(S[seg][c], m, 64);
+                T1 += __shfl_xor(T1, m, 64);
+            }
+            if (lane == 0) {
+                const SegmentBar a = segment_chain(L, 0, q, S[0][0], S[0][1], S[0][2], S[0][3]);
+                const SegmentBar b = segment_chain(L, 1, q, S[1][0], S[1][1], S[1][2], S[1][3]);
+                L.bar[0][q] = a.x0; L.bar[1][q] = a.x1 + b.x0; L.bar[2][q] = b.x1;
+                L.bar[3][q] = a.va; L.bar[4][q] = b.vb; L.bar[5][q] = a.vb + b.va;
+                L.bar[6][q] = a.h - T1; L.bar[7][q] = b.h;
+            }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < here) {
+#pragma unroll
+            for (int f = 0; f < 8; ++f)
+                if (bar.p[f]) bar.p[f][p_first + threadIdx.x] = L.bar[f][threadIdx.x];
+        }
+        __syncthreads();
+    }
+}
+
+// problems per trip: a function of k alone; even where the pointwise kernels need a trip to start on a 16-byte boundary
+int problems_per_trip(size_t k, bool even)
+{
+    size_t P = kTrajTrip / k;
+    if (P > (size_t)kTrajProblems) P = kTrajProblems;
+    if (even) P &= ~(size_t)1;
+    const size_t least = even ? 2 : 1;
+    return (int)(P < least ? least : P);
+}
+
+unsigned trajectory_grid(size_t n, int P)
+{
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    return (unsigned)(trips < kTrajGridCap ? trips : kTrajGridCap);
+}
+
+Spline8 spline_of(const double *const s[8])
+{
+    Spline8 t;
+    for (int f = 0; f < 8; ++f) t.p[f] = s[f];
+    return t;
+}
+
+}  // namespace
+
+hipError_t launch_trajectory_eval(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, double *d_pos, double *d_vel,
+                                  double *d_acc, hipStream_t stream)
+{
+    const int P = problems_per_trip(k, true);
+    hipLaunchKernelGGL(k_trajectory_eval, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)}, n, k, P,
+                       d_tau, d_pos, d_vel, d_acc);
+    return hipGetLastError();
+}
+
+hipError_t launch_trajectory_jvp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *const d_spline_dot[8],
+                                 const double *d_tau_dot, double *d_pos_dot, double *d_vel_dot, double *d_acc_dot, hipStream_t stream)
+{
+    const int P = problems_per_trip(k, true);
+    hipLaunchKernelGGL(k_trajectory_jvp, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)},
+                       spline_of(d_spline_dot), n, k, P, d_tau, d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot);
+    return hipGetLastError();
+}
+
+hipError_t launch_trajectory_vjp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *d_g_pos,
+                                 const double *d_g_vel, const double *d_g_acc, double *const d_spline_bar[8], double *d_tau_bar, hipStream_t stream)
+{
+    const bool vec = (k & 1) == 0;
+    const size_t units = vec ? k >> 1 : k;      // what a lane takes at a time
+    int G = 1;
+    while (G < 64 && (size_t)G < units) G <<= 1;
+    const int P = problems_per_trip(k, false);
+    SplineBar8 bar;
+    for (int f = 0; f < 8; ++f) bar.p[f] = d_spline_bar[f];
+    const dim3 grid(trajectory_grid(n, P)), block(kTrajBlock);
+    hipLaunchKernelGGL(k_trajectory_vjp, grid, block, 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, G, d_tau, d_g_pos, d_g_vel, d_g_acc,
+                       bar, d_tau_bar);
+    return hipGetLastError();
+}
+
+// the batch's state through its slot map, over variant, storage type and zero-velocity form as launch_sample_range (ip_kernels.hip)
+hipError_t launch_trajectory_batch(const BatchView &b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc, hipStream_t stream)
+{
+    if (b.n == 0) return hipSuccess;
+    const int P = problems_per_trip(k, true);
+    const dim3 grid(trajectory_grid(b.n, P)), block(kTrajBlock);
+    const uint32_t *slot_of = b.scheduled ? b.slot_of : nullptr;
+    auto on_zero_vel = [&](auto s, auto v) {
+        using S = decltype(s);
+        constexpr int V = decltype(v)::value;
+        if (b.zero_end_vel)
+            hipLaunchKernelGGL((k_batch_trajectory<S, V, true>), grid, block, 0, stream, FromBatch<S, V, true>{(const S *)b.base, b.stride, slot_of},
+                               b.n, k, P, d_tau, d_pos, d_vel, d_acc);
+        else
+            hipLaunchKernelGGL((k_batch_trajectory<S, V, false>), grid, block, 0, stream, FromBatch<S, V, false>{(const S *)b.base, b.stride, slot_of},
+                               b.n, k, P, d_tau, d_pos, d_vel, d_acc);
+    };
+    auto on_variant = [&](auto s) {
+        if (b.variant != 3) on_zero_vel(s, std::integral_constant<int, 4>{});
+        else on_zero_vel(s, std::integral_constant<int, 3>{});
+    };
+    if (b.dtype == 0) on_variant(double{});
+    else on_variant(float{});
+    return hipGetLastError();
+}
+
+}  // namespace rp
