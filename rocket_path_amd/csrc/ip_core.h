@@ -152,6 +152,19 @@ template <typename T> struct KParams {
                                               // handoff_lanes for more than handoff_patience steps stops and leaves them open (0 lanes: never)
 };
 
+// Feasible start (build-defined), the one rule: vel1 = 0, multipliers 1 and, per segment in double,
+//     t = (3.5/sqrt 12) sqrt(6 |dX| / L) [+ 8 |u| / L]
+// from the STORED positions (dX their difference) and -- Vel -- the segment's STORED end velocity u (not looked at otherwise).  With
+// zero velocities the Vel form gives the other's bits (x + 0 = x, the same operations in the same order); with any velocities it is
+// strictly feasible: on a segment with t = t_pos + t_vel (t_pos the rest-to-rest duration) every |a| <= L (0.98 rho^2 +
+// (4/8)(1 - rho)) <= 0.98 L, rho = t_pos / t.
+template <bool Vel> __device__ __forceinline__ double start_duration(double limit, double dx, double u)
+{
+    const double t = 3.5 / __builtin_sqrt(12.0) * __builtin_sqrt(6.0 * __builtin_fabs(dx) / limit);
+    if constexpr (Vel) return t + 8.0 * __builtin_fabs(u) / limit;
+    else return t;
+}
+
 // The per-problem constants the step needs (enum V 11..15 reduced to velocities and deltas).
 // ZV = "vel0X and vel2X are zero for every problem of the batch".  Every start state the reference has
 // leaves them at zero (initDefault / initStuck, onedpath_ip.cpp:179-186, 203-210) and no key changes them, so

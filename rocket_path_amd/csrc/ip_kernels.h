@@ -108,15 +108,14 @@ hipError_t launch_solution_jacobian_vel(const BatchView &b, const HostParams &hp
 // state movement / initialisation
 hipError_t launch_aos_to_soa(const BatchView &b, const double *d_aos, hipStream_t stream);
 hipError_t launch_soa_to_aos(const BatchView &b, double *d_aos, hipStream_t stream);
-hipError_t launch_restart_feasible(const BatchView &b, const HostParams &hp, hipStream_t stream);      // the feasible start of the positions in the batch's constant fields
+// the feasible start of the positions in the batch's constant fields (rp_batch_restart; the start rule: start_duration, ip_core.h).
+// vel: of the positions AND end velocities there, which stay (t_i grows by 8 |vel_end| / L); otherwise the end velocities are zeroed
+hipError_t launch_restart(const BatchView &b, const HostParams &hp, bool vel, hipStream_t stream);
 // the same from b.records through b.prob_of (a batch that has just been scheduled): positions into the constant fields, the
-// feasible start, cleared progress words -- everything k_solve_chunks<START> forms in registers, written out
-hipError_t launch_start_from_records(const BatchView &b, const HostParams &hp, hipStream_t stream);
-// the start with end velocities (rp_batch_set_problems_vel_device): launch_start_from_records, and the end velocities gathered
-// from d_vel0 / d_vel2 (problem order; null: zeros) through b.prob_of into their fields; t_i grows by 8 |vel_end| / L
-hipError_t launch_start_vel_from_records(const BatchView &b, const HostParams &hp, const double *d_vel0, const double *d_vel2, hipStream_t stream);
-// the same start from the positions AND end velocities in the batch's constant fields (rp_batch_restart of such a batch)
-hipError_t launch_restart_vel(const BatchView &b, const HostParams &hp, hipStream_t stream);
+// feasible start, cleared progress words -- everything k_solve_chunks<START> forms in registers, written out.  vel
+// (rp_batch_set_problems_vel_device; b.scheduled): the end velocities are gathered from d_vel0 / d_vel2 (problem order; null: zeros)
+// through b.prob_of into their fields; otherwise those fields are zeroed and the two arrays are not looked at
+hipError_t launch_start_from_records(const BatchView &b, const HostParams &hp, const double *d_vel0, const double *d_vel2, bool vel, hipStream_t stream);
 hipError_t launch_init_const(const BatchView &b, const double *host_state /* state_len values */, hipStream_t stream);
 hipError_t launch_nudge(const BatchView &b, int field, double delta, hipStream_t stream);
 hipError_t launch_clear_progress(const BatchView &b, hipStream_t stream);
@@ -144,7 +143,7 @@ hipError_t launch_sample_range(const BatchView &b, size_t first, size_t count, d
 hipError_t launch_constraint_table(const BatchView &b, const HostParams &hp, size_t first, size_t count, double *d_rows, hipStream_t stream);
 
 
-// a spline evaluated at the caller's times, and the evaluation's first derivatives (trajectory.hip).  Tables of eight pointers are
+// a spline evaluated at the caller's times, and the evaluation's first derivatives (trajectory.hip, where the plot data above live too).  Tables of eight pointers are
 // (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1), n doubles each in problem order; d_tau and everything per query
 // n x k doubles, row-major, 16-byte aligned; k < 2^31.  Null pointers as include/rp_batch.h says.
 hipError_t launch_trajectory_eval(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, double *d_pos, double *d_vel,
@@ -153,7 +152,7 @@ hipError_t launch_trajectory_vjp(size_t n, size_t k, const double *const d_splin
                                  const double *d_g_vel, const double *d_g_acc, double *const d_spline_bar[8], double *d_tau_bar, hipStream_t stream);
 hipError_t launch_trajectory_jvp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *const d_spline_dot[8],
                                  const double *d_tau_dot, double *d_pos_dot, double *d_vel_dot, double *d_acc_dot, hipStream_t stream);
-// the same evaluation of the batch's current state, problem order, every variant and dtype (the staging of launch_sample_range)
+// the same evaluation of the batch's current state, problem order, every variant and dtype (launch_sample_range's loader: spline_core.h, FromBatch)
 hipError_t launch_trajectory_batch(const BatchView &b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc, hipStream_t stream);
 
 }  // namespace rp

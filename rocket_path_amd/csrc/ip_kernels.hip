@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "../../include/rp_batch.h"
+#include "batch_dispatch.h"
 #include "feas_core.h"
 #include "ip_core.h"
 
@@ -396,8 +397,8 @@ __device__ unsigned long long g_trace[4 * 32768];
 // START: the batch has just been given its problems (rp_batch_set_problems_device: scheduled order computed, each problem's
 // three positions in its 32-byte record, nothing else materialised) and this launch is its first: every lane loads the
 // record of the problem that lies at its position (a gather through prob_of, hidden under the other waves' arithmetic),
-// stores the positions into the constant fields, forms the feasible start (k_restart_feasible's rule, same
-// arithmetic, so the same bits) in registers instead of loading it, takes iteration count and status as zero, and stores
+// stores the positions into the constant fields, forms the feasible start (start_duration, the rule the start kernels
+// write out) in registers instead of loading it, takes iteration count and status as zero, and stores
 // unconditionally.  That spares a fresh batch the 128 B per problem the feasible start would write, the 88 B of them this
 // kernel would read back, and the progress words' clearing pass.
 // (mu_mode 1 carries the split direction: ~210 VGPRs, two waves per SIMD)
@@ -458,10 +459,9 @@ k_solve_chunks(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T> 
             f[(CB + 0) * stride] = s0;
             f[(CB + 2) * stride] = s1;
             f[(CB + 3) * stride] = s2;
-            const double scale = 3.5 / __builtin_sqrt(12.0);      // k_restart_feasible, operation for operation
-            v = T(0);
-            t0 = (T)(S)(scale * __builtin_sqrt(6.0 * __builtin_fabs((double)s1 - (double)s0) / start_limit));
-            t1 = (T)(S)(scale * __builtin_sqrt(6.0 * __builtin_fabs((double)s2 - (double)s1) / start_limit));
+            v = T(0);      // the one start rule, from the stored positions and rounded as a store would round it
+            t0 = (T)(S)start_duration<false>(start_limit, (double)s1 - (double)s0, 0.0);
+            t1 = (T)(S)start_duration<false>(start_limit, (double)s2 - (double)s1, 0.0);
 #pragma unroll
             for (int c = 0; c < NC; ++c) lam[c] = T(1);
             pr.dx0 = (T)s1 - (T)s0;
@@ -1014,11 +1014,21 @@ k_solution(const S *__restrict__ base, size_t stride, size_t n, const int32_t *_
                    iters[s] + iters_add, status[s]);
 }
 
-// Feasible start (build-defined): vel1 = 0, t_i = (3.5/sqrt 12) sqrt(6 |dX_i| / L), multipliers 1,
-// vel0 = vel2 = 0, computed in double from the positions the batch holds in its own constant fields (put there, at each
-// problem's position in the scheduled order, by schedule.hip) and stored in the batch's storage type.  This is what
-// materialises a batch that has been given its problems, and what rp_batch_restart runs.
-template <typename S, int VARIANT>
+// The feasible start (start_duration, ip_core.h) written into a problem's mutable fields in the batch's storage type
+template <typename S, int NC, bool Vel>
+__device__ __forceinline__ void store_start(S *__restrict__ f, size_t stride, double limit, double p0, double p1, double p2, double u0, double u2)
+{
+    f[0 * stride] = S(0);
+    f[1 * stride] = (S)start_duration<Vel>(limit, p1 - p0, u0);
+    f[2 * stride] = (S)start_duration<Vel>(limit, p2 - p1, u2);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) f[(3 + c) * stride] = S(1);
+}
+
+// rp_batch_restart: the start of the positions the batch holds in its own constant fields (put there, at each problem's position in
+// the scheduled order, by schedule.hip).  Without Vel the end velocities are ZEROED (whatever a nudge or a set_state left there);
+// with Vel -- a batch given its problems with end velocities -- they are read and kept.
+template <typename S, int VARIANT, bool Vel>
 __global__ void __launch_bounds__(kBlock)
 k_restart_feasible(S *__restrict__ base, size_t stride, size_t n, double limit)
 {
@@ -1028,71 +1038,27 @@ k_restart_feasible(S *__restrict__ base, size_t stride, size_t n, double limit)
     if (i >= n) return;
     S *f = base + i;
     const double p0 = (double)f[(CB + 0) * stride], p1 = (double)f[(CB + 2) * stride], p2 = (double)f[(CB + 3) * stride];
-    const double scale = 3.5 / __builtin_sqrt(12.0);
-    f[0 * stride] = S(0);
-    f[1 * stride] = (S)(scale * __builtin_sqrt(6.0 * __builtin_fabs(p1 - p0) / limit));
-    f[2 * stride] = (S)(scale * __builtin_sqrt(6.0 * __builtin_fabs(p2 - p1) / limit));
-#pragma unroll
-    for (int c = 0; c < NC; ++c) f[(3 + c) * stride] = S(1);
-    f[(CB + 1) * stride] = S(0);
-    f[(CB + 4) * stride] = S(0);
+    double u0 = 0.0, u2 = 0.0;
+    if constexpr (Vel) {
+        u0 = (double)f[(CB + 1) * stride];
+        u2 = (double)f[(CB + 4) * stride];
+    }
+    store_start<S, NC, Vel>(f, stride, limit, p0, p1, p2, u0, u2);
+    if constexpr (!Vel) {
+        f[(CB + 1) * stride] = S(0);
+        f[(CB + 4) * stride] = S(0);
+    }
 }
 
 // The same start for a batch that has just been scheduled: positions from the 32-byte records the scheduling pass kept per
-// problem (schedule.hip), found through prob_of, into the constant fields, the start computed from the STORED positions exactly as above, progress
-// words cleared -- what k_solve_chunks<START> forms in registers, written out for every other consumer of the state.
-template <typename S, int VARIANT>
+// problem (schedule.hip), found through prob_of, into the constant fields, the start computed from the STORED values, progress
+// words cleared -- what k_solve_chunks<START> forms in registers, written out for every other consumer of the state.  Vel
+// (rp_batch_set_problems_vel_device): the end velocities are gathered from problem-order arrays (null: zeros); otherwise they are zero.
+template <typename S, int VARIANT, bool Vel>
 __global__ void __launch_bounds__(kBlock)
 k_start_from_records(S *__restrict__ base, size_t stride, size_t n, double limit, const StartRecord *__restrict__ records,
-                     const uint32_t *__restrict__ prob_of, int32_t *__restrict__ iters, uint32_t *__restrict__ status)
-{
-    constexpr int NC = CMap<VARIANT>::NC;
-    constexpr int CB = 3 + NC;
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    typedef double v2 __attribute__((ext_vector_type(2)));
-    const v2 *rec = reinterpret_cast<const v2 *>(records + prob_of[i]);
-    const v2 ra = rec[0], rb = rec[1];
-    const S s0 = (S)ra[0], s1 = (S)ra[1], s2 = (S)rb[0];
-    const double p0 = (double)s0, p1 = (double)s1, p2 = (double)s2;
-    const double scale = 3.5 / __builtin_sqrt(12.0);
-    S *f = base + i;
-    f[0 * stride] = S(0);
-    f[1 * stride] = (S)(scale * __builtin_sqrt(6.0 * __builtin_fabs(p1 - p0) / limit));
-    f[2 * stride] = (S)(scale * __builtin_sqrt(6.0 * __builtin_fabs(p2 - p1) / limit));
-#pragma unroll
-    for (int c = 0; c < NC; ++c) f[(3 + c) * stride] = S(1);
-    f[(CB + 0) * stride] = s0;
-    f[(CB + 1) * stride] = S(0);
-    f[(CB + 2) * stride] = s1;
-    f[(CB + 3) * stride] = s2;
-    f[(CB + 4) * stride] = S(0);
-    iters[i] = 0;
-    status[i] = 0;
-}
-
-// Feasible start with end velocities (rp_batch_set_problems_vel_device, rp_batch_restart of such a batch): vel1 = 0, multipliers 1,
-//     t_0 = (3.5/sqrt 12) sqrt(6 |dX_0| / L) + 8 |vel0| / L,    t_1 = (3.5/sqrt 12) sqrt(6 |dX_1| / L) + 8 |vel2| / L,
-// from the STORED positions and velocities.  With zero velocities it is k_restart_feasible's start bit for bit (x + 0 = x, the same
-// operations in the same order); with any velocities it is strictly feasible: on a segment with t = t_pos + t_vel (t_pos the
-// rest-to-rest duration) every |a| <= L (0.98 rho^2 + (4/8)(1 - rho)) <= 0.98 L, rho = t_pos / t.
-template <typename S>
-__device__ __forceinline__ void store_vel_start(S *__restrict__ f, size_t stride, int nc, double limit, double p0, double p1, double p2,
-                                                double u0, double u2)
-{
-    const double scale = 3.5 / __builtin_sqrt(12.0);
-    f[0 * stride] = S(0);
-    f[1 * stride] = (S)(scale * __builtin_sqrt(6.0 * __builtin_fabs(p1 - p0) / limit) + 8.0 * __builtin_fabs(u0) / limit);
-    f[2 * stride] = (S)(scale * __builtin_sqrt(6.0 * __builtin_fabs(p2 - p1) / limit) + 8.0 * __builtin_fabs(u2) / limit);
-    for (int c = 0; c < nc; ++c) f[(3 + c) * stride] = S(1);
-}
-
-// rp_batch_set_problems_vel_device: k_start_from_records with the end velocities gathered from problem-order arrays (null: zeros)
-template <typename S, int VARIANT>
-__global__ void __launch_bounds__(kBlock)
-k_start_vel_from_records(S *__restrict__ base, size_t stride, size_t n, double limit, const StartRecord *__restrict__ records,
-                         const uint32_t *__restrict__ prob_of, const double *__restrict__ vel0, const double *__restrict__ vel2,
-                         int32_t *__restrict__ iters, uint32_t *__restrict__ status)
+                     const uint32_t *__restrict__ prob_of, int32_t *__restrict__ iters, uint32_t *__restrict__ status,
+                     const double *__restrict__ vel0, const double *__restrict__ vel2)
 {
     constexpr int NC = CMap<VARIANT>::NC;
     constexpr int CB = 3 + NC;
@@ -1103,10 +1069,13 @@ k_start_vel_from_records(S *__restrict__ base, size_t stride, size_t n, double l
     const v2 *rec = reinterpret_cast<const v2 *>(records + prob);
     const v2 ra = rec[0], rb = rec[1];
     const S s0 = (S)ra[0], s1 = (S)ra[1], s2 = (S)rb[0];
-    // + 0.0: a velocity of -0 is stored as +0, the bits set_problems_device leaves (rest-to-rest bit for bit)
-    const S w0 = vel0 ? (S)(vel0[prob] + 0.0) : S(0), w2 = vel2 ? (S)(vel2[prob] + 0.0) : S(0);
+    S w0 = S(0), w2 = S(0);
+    if constexpr (Vel) {      // + 0.0: a velocity of -0 is stored as +0, the bits the other form leaves
+        w0 = vel0 ? (S)(vel0[prob] + 0.0) : S(0);
+        w2 = vel2 ? (S)(vel2[prob] + 0.0) : S(0);
+    }
     S *f = base + i;
-    store_vel_start(f, stride, NC, limit, (double)s0, (double)s1, (double)s2, (double)w0, (double)w2);
+    store_start<S, NC, Vel>(f, stride, limit, (double)s0, (double)s1, (double)s2, (double)w0, (double)w2);
     f[(CB + 0) * stride] = s0;
     f[(CB + 1) * stride] = w0;
     f[(CB + 2) * stride] = s1;
@@ -1114,21 +1083,6 @@ k_start_vel_from_records(S *__restrict__ base, size_t stride, size_t n, double l
     f[(CB + 4) * stride] = w2;
     iters[i] = 0;
     status[i] = 0;
-}
-
-// rp_batch_restart of a batch given its problems with end velocities: the same start from the constant fields
-template <typename S, int VARIANT>
-__global__ void __launch_bounds__(kBlock)
-k_restart_vel(S *__restrict__ base, size_t stride, size_t n, double limit)
-{
-    constexpr int NC = CMap<VARIANT>::NC;
-    constexpr int CB = 3 + NC;
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    S *f = base + i;
-    const double p0 = (double)f[(CB + 0) * stride], p1 = (double)f[(CB + 2) * stride], p2 = (double)f[(CB + 3) * stride];
-    const double u0 = (double)f[(CB + 1) * stride], u2 = (double)f[(CB + 4) * stride];
-    store_vel_start(f, stride, NC, limit, p0, p1, p2, u0, u2);
 }
 
 // Every problem gets the same state (initDefault / initStuck broadcast).
@@ -1185,120 +1139,6 @@ k_move_toward_feasibility(S *__restrict__ base, size_t stride, size_t n, KParams
         f[1 * stride] = (S)(t0 + dx0);
         f[2 * stride] = (S)(t1 + dx1);
     }
-}
-
-// Plot data: per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
-// (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
-// kernel.  A 256-thread block takes 128 problems: its first 128 threads read one problem each (eight fields through the slot
-// map) and leave, per segment, the six numbers a sample is made of in LDS; then all threads write the block's 8,448 positions
-// and 512 accelerations as consecutive elements (full coalesced segments), each from the constants of its problem.  The
-// reference's divisions are multiplications by a refined reciprocal (rcp_: IEEE 1/x), one per segment instead of nine per
-// sample; the parity test allows 1e-13.  (The first form -- one thread per output element, every thread reading the eight
-// fields and dividing for itself -- ran at 0.17 of the HBM peak: it was bound by its 9 broadcast loads per wave.)
-// (Walking POSITIONS instead -- coalesced field reads, each problem's 528-byte row scattered to where prob_of says -- was measured
-// and is slower, 0.227 against 0.194 ms at 1 Mi problems: rows start on alternating 16-byte offsets, so every row ends in two
-// partial sectors.  The gather through slot_of costs eight -- with zero end velocities, which are then not read, six --
-// 32-byte sectors per problem on top of the 560 B written; that traffic is what the launch time is made of.)
-constexpr int kSampleProblems = 128;
-template <typename T, int VARIANT, bool ZV>
-__global__ void __launch_bounds__(kBlock)
-k_sample(const T *__restrict__ base, size_t stride, size_t first, size_t count, const uint32_t *__restrict__ slot_of,
-         double *__restrict__ pos66, double *__restrict__ acc4)
-{
-    constexpr int CB = 3 + CMap<VARIANT>::NC;
-    __shared__ double s_seg[2][6][kSampleProblems];      // per segment: x0, x1, va, acc0, jrk0, h / 32
-    __shared__ double s_acc[4][kSampleProblems];
-    const size_t p_first = (size_t)blockIdx.x * kSampleProblems;      // output row of the block's first problem
-    const int here = (int)(count - p_first < (size_t)kSampleProblems ? count - p_first : (size_t)kSampleProblems);
-    if (threadIdx.x < here) {
-        const int q = threadIdx.x;
-        const T *f = base + (slot_of ? (size_t)slot_of[first + p_first + q] : first + p_first + q);
-        const double v1 = (double)f[0], t0 = (double)f[1 * stride], t1 = (double)f[2 * stride];
-        const double p0 = (double)f[(CB + 0) * stride], p1 = (double)f[(CB + 2) * stride], p2 = (double)f[(CB + 3) * stride];
-        const double v0 = ZV ? 0.0 : (double)f[(CB + 1) * stride], v2 = ZV ? 0.0 : (double)f[(CB + 4) * stride];
-#pragma unroll
-        for (int seg = 0; seg < 2; ++seg) {
-            const double x0 = seg ? p1 : p0, x1 = seg ? p2 : p1, va = seg ? v1 : v0, vb = seg ? v2 : v1, h = seg ? t1 : t0;
-            const double ih = rcp_<double>(h), ih2 = ih * ih;
-            const double acc0 = (x1 - x0) * (6.0 * ih2) - (va * 4.0 + vb * 2.0) * ih;
-            const double jrk0 = (vb - va) * (2.0 * ih2) - acc0 * (2.0 * ih);
-            s_seg[seg][0][q] = x0; s_seg[seg][1][q] = x1; s_seg[seg][2][q] = va;
-            s_seg[seg][3][q] = acc0; s_seg[seg][4][q] = jrk0; s_seg[seg][5][q] = h * 0.03125;
-            // end accelerations of the segment (evalAccelInit / evalAccelFinal's formulas)
-            s_acc[2 * seg][q] = ((x1 - x0) * 6.0 * ih + va * -4.0 + vb * -2.0) * ih;
-            s_acc[2 * seg + 1][q] = ((x1 - x0) * -6.0 * ih + va * 2.0 + vb * 4.0) * ih;
-        }
-    }
-    __syncthreads();
-    // two consecutive positions per thread and trip (a problem's 66 are 33 pairs): 16-byte nontemporal stores, 1 KiB per wave
-    typedef double v2 __attribute__((ext_vector_type(2)));
-    auto position = [&](int q, int slot) -> double {
-        const int seg = slot >= 33, j = slot - 33 * seg;
-        if (j == 0) return s_seg[seg][0][q];
-        if (j == 32) return s_seg[seg][1][q];
-        const double t = s_seg[seg][5][q] * (double)j;      // h j / 32
-        return s_seg[seg][0][q] + (s_seg[seg][2][q] + (s_seg[seg][3][q] + s_seg[seg][4][q] * (t * (1.0 / 3.0))) * (t * 0.5)) * t;
-    };
-    v2 *out_pos = reinterpret_cast<v2 *>(pos66 + p_first * 66);      // 16-byte aligned: 66 doubles per problem, 128 problems per block
-    for (int pr = threadIdx.x; pr < here * 33; pr += kBlock) {
-        const int q = pr / 33, pair = pr - q * 33;
-        const v2 both = {position(q, 2 * pair), position(q, 2 * pair + 1)};
-        __builtin_nontemporal_store(both, out_pos + pr);
-    }
-    double *out_acc = acc4 + p_first * 4;
-    for (int o = threadIdx.x; o < here * 4; o += kBlock) out_acc[o] = s_acc[o & 3][o >> 2];
-}
-
-// The same plot data for a WHOLE scheduled batch from two problem-order records per problem (round 4): the positions the batch
-// was given (StartRecord, kept by the scheduling pass) and the problem's solution record (k_solution writes them into a scratch
-// first: 68 B per problem).  Both reads are coalesced whole sectors -- 64 B per problem where the gather through slot_of touches
-// six 32-byte sectors for 48 B -- and the arithmetic and the stores are k_sample's (same bits).  Zero end velocities only, and
-// only while the records are the batch's positions (rp_batch.cpp keeps the flag).
-template <typename S>
-__global__ void __launch_bounds__(kBlock)
-k_sample_records(const StartRecord *__restrict__ records, const Solution *__restrict__ sol, size_t count,
-                 double *__restrict__ pos66, double *__restrict__ acc4)
-{
-    __shared__ double s_seg[2][6][kSampleProblems];      // per segment: x0, x1, va, acc0, jrk0, h / 32
-    __shared__ double s_acc[4][kSampleProblems];
-    const size_t p_first = (size_t)blockIdx.x * kSampleProblems;
-    const int here = (int)(count - p_first < (size_t)kSampleProblems ? count - p_first : (size_t)kSampleProblems);
-    if (threadIdx.x < here) {
-        const int q = threadIdx.x;
-        typedef double v2 __attribute__((ext_vector_type(2)));
-        const v2 *rec = reinterpret_cast<const v2 *>(records + p_first + q), *so = reinterpret_cast<const v2 *>(sol + p_first + q);
-        const v2 ra = rec[0], rb = rec[1], sa = so[0], sb = so[1];
-        const double p0 = (double)(S)ra[0], p1 = (double)(S)ra[1], p2 = (double)(S)rb[0];      // what the constant fields hold
-        const double v1 = sa[0], t0 = sa[1], t1 = sb[0];
-#pragma unroll
-        for (int seg = 0; seg < 2; ++seg) {
-            const double x0 = seg ? p1 : p0, x1 = seg ? p2 : p1, va = seg ? v1 : 0.0, vb = seg ? 0.0 : v1, h = seg ? t1 : t0;
-            const double ih = rcp_<double>(h), ih2 = ih * ih;
-            const double acc0 = (x1 - x0) * (6.0 * ih2) - (va * 4.0 + vb * 2.0) * ih;
-            const double jrk0 = (vb - va) * (2.0 * ih2) - acc0 * (2.0 * ih);
-            s_seg[seg][0][q] = x0; s_seg[seg][1][q] = x1; s_seg[seg][2][q] = va;
-            s_seg[seg][3][q] = acc0; s_seg[seg][4][q] = jrk0; s_seg[seg][5][q] = h * 0.03125;
-            s_acc[2 * seg][q] = ((x1 - x0) * 6.0 * ih + va * -4.0 + vb * -2.0) * ih;
-            s_acc[2 * seg + 1][q] = ((x1 - x0) * -6.0 * ih + va * 2.0 + vb * 4.0) * ih;
-        }
-    }
-    __syncthreads();
-    typedef double v2 __attribute__((ext_vector_type(2)));
-    auto position = [&](int q, int slot) -> double {
-        const int seg = slot >= 33, j = slot - 33 * seg;
-        if (j == 0) return s_seg[seg][0][q];
-        if (j == 32) return s_seg[seg][1][q];
-        const double t = s_seg[seg][5][q] * (double)j;      // h j / 32
-        return s_seg[seg][0][q] + (s_seg[seg][2][q] + (s_seg[seg][3][q] + s_seg[seg][4][q] * (t * (1.0 / 3.0))) * (t * 0.5)) * t;
-    };
-    v2 *out_pos = reinterpret_cast<v2 *>(pos66 + p_first * 66);
-    for (int pr = threadIdx.x; pr < here * 33; pr += kBlock) {
-        const int q = pr / 33, pair = pr - q * 33;
-        const v2 both = {position(q, 2 * pair), position(q, 2 * pair + 1)};
-        __builtin_nontemporal_store(both, out_pos + pr);
-    }
-    double *out_acc = acc4 + p_first * 4;
-    for (int o = threadIdx.x; o < here * 4; o += kBlock) out_acc[o] = s_acc[o & 3][o >> 2];
 }
 
 // printState's per-problem part for a (small) range of problems: the surrogate gap and, per constraint, what
@@ -1364,51 +1204,6 @@ k_constraint_table(const S *__restrict__ base, size_t stride, size_t first, size
 }
 
 inline unsigned grid_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
-// ---- the one dispatch: run-time properties of a batch -> compile-time constants of a kernel instantiation ----
-// A launcher names the AXES its kernel is instantiated on and gets, inside RP_DISPATCH's statement,
-//   S     storage type in HBM: double (RP_DTYPE_F64) or float (RP_DTYPE_F32, RP_DTYPE_F32_STATE)                       always
-//   T     arithmetic type in registers    kArith: double / float / double for the three dtypes
-//                                         kDoubleArith: double whatever the dtype (mu_mode 1; rp_batch_set_params refuses it for pure fp32)
-//                                         neither: S
-//   V, M  variant and its row length      kVariant: 3, 16 or 4, 12; otherwise 3, 16
-//   Z     BatchView::zero_end_vel         kZeroVel: as the batch says; otherwise true
-// An axis that is not named is not branched on: a kernel is instantiated for the combinations its launchers can reach and no others
-// (no MU = 1 in float arithmetic, the transposes on S and M only, k_solution / k_init_const / k_nudge / k_sample_records on S only).
-enum : unsigned { kStorage = 0, kArith = 1, kDoubleArith = 2, kVariant = 4, kZeroVel = 8 };
-
-template <typename S_, typename T_, int V_, bool Z_> struct Tag {
-    using S = S_;
-    using T = T_;
-    static constexpr int V = V_, M = V_ == 4 ? 12 : 16;      // M: state_len(V)
-    static constexpr bool Z = Z_;
-};
-
-template <unsigned AXES, typename F> void dispatch(const BatchView &b, F f)
-{
-    auto on_zero_vel = [&](auto s, auto t, auto v) {
-        constexpr int V = decltype(v)::value;
-        if constexpr ((AXES & kZeroVel) != 0) { if (!b.zero_end_vel) return f(Tag<decltype(s), decltype(t), V, false>{}); }
-        f(Tag<decltype(s), decltype(t), V, true>{});
-    };
-    auto on_variant = [&](auto s, auto t) {
-        if constexpr ((AXES & kVariant) != 0) { if (b.variant != 3) return on_zero_vel(s, t, std::integral_constant<int, 4>{}); }
-        on_zero_vel(s, t, std::integral_constant<int, 3>{});
-    };
-    if (b.dtype == 0) on_variant(double{}, double{});
-    else if constexpr ((AXES & kDoubleArith) != 0) on_variant(float{}, double{});
-    else if constexpr ((AXES & kArith) != 0) { if (b.dtype == 1) on_variant(float{}, float{}); else on_variant(float{}, double{}); }
-    else on_variant(float{}, float{});
-}
-
-#define RP_DISPATCH(AXES, b, ...)                                         \
-    dispatch<(AXES)>((b), [&](auto tag_) {                                \
-        using S [[maybe_unused]] = typename decltype(tag_)::S;            \
-        using T [[maybe_unused]] = typename decltype(tag_)::T;            \
-        [[maybe_unused]] constexpr int V = decltype(tag_)::V, M = decltype(tag_)::M; \
-        [[maybe_unused]] constexpr bool Z = decltype(tag_)::Z;            \
-        __VA_ARGS__;                                                      \
-    })
 
 }  // namespace
 
@@ -1580,10 +1375,6 @@ hipError_t launch_reduce(const BatchView &b, const HostParams &hp, double host_s
     return hipGetLastError();
 }
 
-// where the problems lie, for the kernels that walk problems (slots) and those that walk positions (problems); null: in problem order
-static const uint32_t *slots(const BatchView &b) { return b.scheduled ? b.slot_of : nullptr; }
-static const uint32_t *problems(const BatchView &b) { return b.scheduled ? b.prob_of : nullptr; }
-
 hipError_t launch_solution(const BatchView &b, Solution *d_out, hipStream_t stream)
 {
     if (b.n == 0) return hipSuccess;
@@ -1619,34 +1410,28 @@ hipError_t launch_soa_to_aos(const BatchView &b, double *d_aos, hipStream_t stre
     return hipGetLastError();
 }
 
-hipError_t launch_restart_feasible(const BatchView &b, const HostParams &hp, hipStream_t stream)
+hipError_t launch_restart(const BatchView &b, const HostParams &hp, bool vel, hipStream_t stream)
 {
-    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_restart_feasible<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
-                                                (S *)b.base, b.stride, b.n, hp.accel_limit));
+    if (vel)
+        RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_restart_feasible<S, V, true>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                    (S *)b.base, b.stride, b.n, hp.accel_limit));
+    else
+        RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_restart_feasible<S, V, false>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                    (S *)b.base, b.stride, b.n, hp.accel_limit));
     return hipGetLastError();
 }
 
-hipError_t launch_start_from_records(const BatchView &b, const HostParams &hp, hipStream_t stream)
+hipError_t launch_start_from_records(const BatchView &b, const HostParams &hp, const double *d_vel0, const double *d_vel2, bool vel, hipStream_t stream)
 {
-    if (!b.records) return hipErrorInvalidValue;
-    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_start_from_records<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
-                                                (S *)b.base, b.stride, b.n, hp.accel_limit, (const StartRecord *)b.records, (const uint32_t *)b.prob_of, b.iters, b.status));
-    return hipGetLastError();
-}
-
-hipError_t launch_start_vel_from_records(const BatchView &b, const HostParams &hp, const double *d_vel0, const double *d_vel2, hipStream_t stream)
-{
-    if (!b.records || !b.scheduled) return hipErrorInvalidValue;
-    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_start_vel_from_records<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
-                                                (S *)b.base, b.stride, b.n, hp.accel_limit, (const StartRecord *)b.records, (const uint32_t *)b.prob_of,
-                                                d_vel0, d_vel2, b.iters, b.status));
-    return hipGetLastError();
-}
-
-hipError_t launch_restart_vel(const BatchView &b, const HostParams &hp, hipStream_t stream)
-{
-    RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_restart_vel<S, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
-                                                (S *)b.base, b.stride, b.n, hp.accel_limit));
+    if (!b.records || (vel && !b.scheduled)) return hipErrorInvalidValue;
+    if (vel)
+        RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_start_from_records<S, V, true>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                    (S *)b.base, b.stride, b.n, hp.accel_limit, (const StartRecord *)b.records, (const uint32_t *)b.prob_of,
+                                                    b.iters, b.status, d_vel0, d_vel2));
+    else
+        RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_start_from_records<S, V, false>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
+                                                    (S *)b.base, b.stride, b.n, hp.accel_limit, (const StartRecord *)b.records, (const uint32_t *)b.prob_of,
+                                                    b.iters, b.status, nullptr, nullptr));
     return hipGetLastError();
 }
 
@@ -1678,30 +1463,6 @@ hipError_t launch_move_toward_feasibility(const BatchView &b, const HostParams &
     // it is a one-off between solves, not the hot path.  An fp32 state gets the fp64 move rounded to fp32.
     RP_DISPATCH(kVariant, b, hipLaunchKernelGGL((k_move_toward_feasibility<S, double, V>), dim3(grid_for(b.n)), dim3(kBlock), 0, stream,
                                                 (S *)b.base, b.stride, b.n, make_kparams<double>(hp, V)));
-    return hipGetLastError();
-}
-
-// ---- read-backs by problem index: a range [first, first + count) of problems, wherever they lie in the batch ----
-hipError_t launch_sample_range(const BatchView &b, size_t first, size_t count, double *d_pos66, double *d_acc4, hipStream_t stream)
-{
-    if (count == 0) return hipSuccess;
-    const dim3 grid((unsigned)((count + kSampleProblems - 1) / kSampleProblems));
-    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_sample<S, V, Z>), grid, dim3(kBlock), 0, stream,
-                                                           (const S *)b.base, b.stride, first, count, slots(b), d_pos66, d_acc4));
-    return hipGetLastError();
-}
-
-hipError_t launch_sample(const BatchView &b, double *d_pos66, double *d_acc4, hipStream_t stream) { return launch_sample_range(b, 0, b.n, d_pos66, d_acc4, stream); }
-
-hipError_t launch_sample_from_records(const BatchView &b, Solution *d_solution_scratch, double *d_pos66, double *d_acc4, hipStream_t stream)
-{
-    if (b.n == 0) return hipSuccess;
-    if (!b.scheduled || !b.zero_end_vel || !b.records) return hipErrorInvalidValue;
-    hipError_t e = launch_solution(b, d_solution_scratch, stream);      // every problem's (vel1, duration0, duration1) in problem order
-    if (e != hipSuccess) return e;
-    const dim3 grid((unsigned)((b.n + kSampleProblems - 1) / kSampleProblems));
-    RP_DISPATCH(kStorage, b, hipLaunchKernelGGL((k_sample_records<S>), grid, dim3(kBlock), 0, stream,
-                                                (const StartRecord *)b.records, (const Solution *)d_solution_scratch, b.n, d_pos66, d_acc4));
     return hipGetLastError();
 }
 

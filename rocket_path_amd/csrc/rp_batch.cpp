@@ -164,7 +164,7 @@ int materialize(rp_batch *b)
 {
     if (!b->at_start) return RP_OK;
     left_lazy_start(b);
-    RP_HIP(rp::launch_start_from_records(b->view, b->params, b->stream));      // (the progress counters were zeroed by the scheduling pass)
+    RP_HIP(rp::launch_start_from_records(b->view, b->params, nullptr, nullptr, false, b->stream));      // (the progress counters were zeroed by the scheduling pass)
     return RP_OK;
 }
 
@@ -584,7 +584,7 @@ int rp_batch_set_problems_vel_device(rp_batch *b, const double *d_pos0, const do
     int st = schedule(b, d_pos0, d_pos1, d_pos2, 1, true);
     if (st != RP_OK) return st;
     problems_vel_given(b);
-    RP_HIP(rp::launch_start_vel_from_records(b->view, b->params, d_vel0, d_vel2, b->stream));
+    RP_HIP(rp::launch_start_from_records(b->view, b->params, d_vel0, d_vel2, true, b->stream));
     return RP_OK;
 }
 
@@ -594,8 +594,7 @@ int rp_batch_restart(rp_batch *b)
     const bool lazy = b->at_start, vel = b->vel_start;
     restarted(b);
     if (lazy) return materialize(b);      // already at the start of its positions: write it out
-    if (vel) RP_HIP(rp::launch_restart_vel(b->view, b->params, b->stream));      // back to the start with the end velocities the batch holds
-    else RP_HIP(rp::launch_restart_feasible(b->view, b->params, b->stream));
+    RP_HIP(rp::launch_restart(b->view, b->params, vel, b->stream));      // vel: back to the start with the end velocities the batch holds
     RP_HIP(rp::launch_clear_progress(b->view, b->stream));      // the positions have not changed: the scheduled order stays as it is
     return RP_OK;
 }

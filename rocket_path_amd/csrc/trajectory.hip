@@ -1,20 +1,21 @@
 // trajectory.hip -- a solved two-segment spline evaluated at the caller's own times, and the first derivatives of that
 // evaluation, gfx950: rp_trajectory_eval, rp_trajectory_eval_vjp, rp_trajectory_eval_jvp and rp_batch_trajectory_device
-// (include/rp_batch.h).
+// (include/rp_batch.h); and the plot data, the same spline on the reference's fixed grid: rp_batch_sample,
+// rp_batch_sample_device, rp_batch_sample_range (k_sample, k_sample_records, at the end of the kernels).
 //
 // Per problem the spline is (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1) -- this order wherever eight pointers travel
 // together -- and the k query times tau[i, j] (row-major n x k) count from the start of segment 0.  A query with tau < duration0
 // lies in segment 0, (pos0, vel0) -> (pos1, vel1) over h = duration0 at s = tau; every other one in segment 1, (pos1, vel1) ->
 // (pos2, vel2) over h = duration1 at s = tau - duration0.  The cubic is the one the reference draws (drawSegment,
-// onedpath_ip.cpp:1065-1088) and k_sample restates (ip_kernels.hip), with k_sample's arithmetic:
+// onedpath_ip.cpp:1065-1088), with the constants of spline_core.h:
 //     acc0 = 6 (x1 - x0) / h^2 - (4 va + 2 vb) / h        jrk0 = 2 (vb - va) / h^2 - 2 acc0 / h
 //     pos = x0 + (va + (acc0 + jrk0 s / 3) s / 2) s       vel = va + (acc0 + jrk0 s / 2) s       acc = acc0 + jrk0 s
 // No clamping: outside [0, duration0 + duration1] the end segments' cubics continue.  A problem with a duration that is not finite
 // or not > 0 gets NaN everywhere (its constants are NaN); a NaN tau gives NaN for that query.
 //
 // All three kernels move 8-32 B per query and ~128 B per problem and do ~20 flops per query: streaming kernels, built the way k_sample
-// was rebuilt.  A block takes P consecutive problems per trip (P a function of k alone, P k ~ 4096 queries); its first P threads
-// read one problem's eight parameters each, do the two reciprocals (rcp_, as k_sample) and leave the per-segment constants and
+// is.  A block takes P consecutive problems per trip (P a function of k alone, P k ~ 4096 queries); its first P threads
+// read one problem's eight parameters each, do the two reciprocals (rcp_) and leave the per-segment constants and
 // duration0 in LDS; then the block streams.  The grid is capped and strides over the trips.
 //   k_trajectory_eval / k_trajectory_jvp / k_batch_trajectory: pointwise.  The block's P k queries are consecutive elements of
 //     tau (P is even, so a trip starts on a 16-byte boundary): each thread takes two at a time -- one 16-byte load, one 16-byte
@@ -30,7 +31,9 @@
 #include "ip_kernels.h"
 
 #include "../../include/rp_batch.h"
+#include "batch_dispatch.h"
 #include "ip_core.h"
+#include "spline_core.h"
 
 namespace rp {
 
@@ -43,58 +46,7 @@ constexpr size_t kTrajTrip = 4096;       // queries per trip a block aims at
 
 typedef double v2 __attribute__((ext_vector_type(2)));
 
-struct Spline8 { const double *p[8]; };      // pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1
 struct SplineBar8 { double *p[8]; };
-
-__device__ __forceinline__ double quiet_nan() { return __builtin_nan(""); }
-
-// one problem's eight numbers in the order the segments use them
-struct Knots {
-    double p0, p1, p2, v0, v2, v1, t0, t1;
-    // the NaN rule: a duration that is not finite or not > 0 poisons both (then every constant of the problem, then every output)
-    __device__ __forceinline__ void check()
-    {
-        if (!(finite_(t0) && t0 > 0.0 && finite_(t1) && t1 > 0.0)) t0 = t1 = quiet_nan();
-    }
-};
-
-// where a problem's eight numbers come from: eight arrays in problem order (the stateless entries) ...
-struct FromArrays {
-    Spline8 s;
-    __device__ __forceinline__ Knots load(size_t i) const
-    {
-        Knots k;
-        k.p0 = s.p[0][i]; k.p1 = s.p[1][i]; k.p2 = s.p[2][i];
-        k.v0 = s.p[3] ? s.p[3][i] : 0.0; k.v2 = s.p[4] ? s.p[4][i] : 0.0;
-        k.v1 = s.p[5][i]; k.t0 = s.p[6][i]; k.t1 = s.p[7][i];
-        return k;
-    }
-};
-
-// ... or a batch's fields, gathered through the slot map in the batch's storage type (k_sample's reads)
-template <typename S, int VARIANT, bool ZV> struct FromBatch {
-    const S *base;
-    size_t stride;
-    const uint32_t *slot_of;
-    __device__ __forceinline__ Knots load(size_t i) const
-    {
-        constexpr int CB = 3 + CMap<VARIANT>::NC;
-        const S *f = base + (slot_of ? (size_t)slot_of[i] : i);
-        Knots k;
-        k.v1 = (double)f[0]; k.t0 = (double)f[1 * stride]; k.t1 = (double)f[2 * stride];
-        k.p0 = (double)f[(CB + 0) * stride]; k.p1 = (double)f[(CB + 2) * stride]; k.p2 = (double)f[(CB + 3) * stride];
-        k.v0 = ZV ? 0.0 : (double)f[(CB + 1) * stride]; k.v2 = ZV ? 0.0 : (double)f[(CB + 4) * stride];
-        return k;
-    }
-};
-
-// the constants of one segment, k_sample's arithmetic: ih = 1 / h (rcp_)
-__device__ __forceinline__ void segment_constants(double x0, double x1, double va, double vb, double ih, double &acc0, double &jrk0)
-{
-    const double ih2 = ih * ih;
-    acc0 = (x1 - x0) * (6.0 * ih2) - (va * 4.0 + vb * 2.0) * ih;
-    jrk0 = (vb - va) * (2.0 * ih2) - acc0 * (2.0 * ih);
-}
 
 __device__ __forceinline__ int problems_here(size_t n, size_t p_first, int P)
 {
@@ -245,7 +197,7 @@ k_trajectory_jvp(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const
             const size_t i = p_first + q;
             const Spline8 &s = stage.s;
             double t0 = s.p[6][i], t1 = s.p[7][i];
-            if (!(finite_(t0) && t0 > 0.0 && finite_(t1) && t1 > 0.0)) t0 = t1 = quiet_nan();
+            check_durations(t0, t1);
             const double t0d = dot.p[6] ? dot.p[6][i] : 0.0, t1d = dot.p[7] ? dot.p[7][i] : 0.0;
             L.d0[q] = t0;
             L.d0_dot[q] = t0d;
@@ -410,6 +362,86 @@ k_trajectory_vjp(FromArrays stage, size_t n, size_t k, int P, int G, const doubl
     }
 }
 
+// ---- plot data ----
+// Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
+// (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
+// kernel.  A 256-thread block takes 128 problems: its first 128 threads read one problem each (through the loader) and leave,
+// per segment, the six numbers a sample is made of in LDS; then all threads write the block's 8,448 positions
+// and 512 accelerations as consecutive elements (full coalesced segments), each from the constants of its problem.  The
+// reference's divisions are multiplications by a refined reciprocal (rcp_: IEEE 1/x), one per segment instead of nine per
+// sample; the parity test allows 1e-13.  (The first form -- one thread per output element, every thread reading the eight
+// fields and dividing for itself -- ran at 0.17 of the HBM peak: it was bound by its 9 broadcast loads per wave.)
+// No NaN rule here (Knots::check is not called): a duration that is not positive gives what the arithmetic gives.
+constexpr int kSampleProblems = 128;
+
+template <class Load>
+__device__ __forceinline__ void sample_block(const Load &from, size_t first, size_t count, double *__restrict__ pos66, double *__restrict__ acc4)
+{
+    __shared__ double s_seg[2][6][kSampleProblems];      // per segment: x0, x1, va, acc0, jrk0, h / 32
+    __shared__ double s_acc[4][kSampleProblems];
+    const size_t p_first = (size_t)blockIdx.x * kSampleProblems;      // output row of the block's first problem
+    const int here = problems_here(count, p_first, kSampleProblems);
+    if (threadIdx.x < here) {
+        const int q = threadIdx.x;
+        const Knots kn = from.load(first + p_first + q);
+#pragma unroll
+        for (int seg = 0; seg < 2; ++seg) {
+            const double x0 = seg ? kn.p1 : kn.p0, x1 = seg ? kn.p2 : kn.p1, va = seg ? kn.v1 : kn.v0, vb = seg ? kn.v2 : kn.v1, h = seg ? kn.t1 : kn.t0;
+            const double ih = rcp_<double>(h);
+            double acc0, jrk0;
+            segment_constants(x0, x1, va, vb, ih, acc0, jrk0);
+            s_seg[seg][0][q] = x0; s_seg[seg][1][q] = x1; s_seg[seg][2][q] = va;
+            s_seg[seg][3][q] = acc0; s_seg[seg][4][q] = jrk0; s_seg[seg][5][q] = h * 0.03125;
+            // end accelerations of the segment (evalAccelInit / evalAccelFinal's formulas)
+            s_acc[2 * seg][q] = ((x1 - x0) * 6.0 * ih + va * -4.0 + vb * -2.0) * ih;
+            s_acc[2 * seg + 1][q] = ((x1 - x0) * -6.0 * ih + va * 2.0 + vb * 4.0) * ih;
+        }
+    }
+    __syncthreads();
+    // two consecutive positions per thread and trip (a problem's 66 are 33 pairs): 16-byte nontemporal stores, 1 KiB per wave
+    auto position = [&](int q, int slot) -> double {
+        const int seg = slot >= 33, j = slot - 33 * seg;
+        if (j == 0) return s_seg[seg][0][q];
+        if (j == 32) return s_seg[seg][1][q];
+        const double t = s_seg[seg][5][q] * (double)j;      // h j / 32
+        return s_seg[seg][0][q] + (s_seg[seg][2][q] + (s_seg[seg][3][q] + s_seg[seg][4][q] * (t * (1.0 / 3.0))) * (t * 0.5)) * t;
+    };
+    v2 *out_pos = reinterpret_cast<v2 *>(pos66 + p_first * 66);      // 16-byte aligned: 66 doubles per problem, 128 problems per block
+    for (int pr = threadIdx.x; pr < here * 33; pr += kTrajBlock) {
+        const int q = pr / 33, pair = pr - q * 33;
+        const v2 both = {position(q, 2 * pair), position(q, 2 * pair + 1)};
+        __builtin_nontemporal_store(both, out_pos + pr);
+    }
+    double *out_acc = acc4 + p_first * 4;
+    for (int o = threadIdx.x; o < here * 4; o += kTrajBlock) out_acc[o] = s_acc[o & 3][o >> 2];
+}
+
+// Problems [first, first + count) of a batch, rows in problem order, gathered field by field through slot_of.
+// (Walking POSITIONS instead -- coalesced field reads, each problem's 528-byte row scattered to where prob_of says -- was measured
+// and is slower, 0.227 against 0.194 ms at 1 Mi problems: rows start on alternating 16-byte offsets, so every row ends in two
+// partial sectors.  The gather through slot_of costs eight -- with zero end velocities, which are then not read, six --
+// 32-byte sectors per problem on top of the 560 B written; that traffic is what the launch time is made of.)
+template <typename T, int VARIANT, bool ZV>
+__global__ void __launch_bounds__(kTrajBlock)
+k_sample(const T *__restrict__ base, size_t stride, size_t first, size_t count, const uint32_t *__restrict__ slot_of,
+         double *__restrict__ pos66, double *__restrict__ acc4)
+{
+    sample_block(FromBatch<T, VARIANT, ZV>{base, stride, slot_of}, first, count, pos66, acc4);
+}
+
+// The same plot data for a WHOLE scheduled batch from two problem-order records per problem (round 4): the positions the batch
+// was given (StartRecord, kept by the scheduling pass) and the problem's solution record (k_solution writes them into a scratch
+// first: 68 B per problem).  Both reads are coalesced whole sectors -- 64 B per problem where the gather through slot_of touches
+// six 32-byte sectors for 48 B.  Zero end velocities only, and only while the records are the batch's positions (rp_batch.cpp
+// keeps the flag).
+template <typename S>
+__global__ void __launch_bounds__(kTrajBlock)
+k_sample_records(const StartRecord *__restrict__ records, const Solution *__restrict__ sol, size_t count,
+                 double *__restrict__ pos66, double *__restrict__ acc4)
+{
+    sample_block(FromRecords<S>{records, sol}, 0, count, pos66, acc4);
+}
+
 // problems per trip: a function of k alone; even where the pointwise kernels need a trip to start on a 16-byte boundary
 int problems_per_trip(size_t k, bool even)
 {
@@ -469,29 +501,37 @@ hipError_t launch_trajectory_vjp(size_t n, size_t k, const double *const d_splin
     return hipGetLastError();
 }
 
-// the batch's state through its slot map, over variant, storage type and zero-velocity form as launch_sample_range (ip_kernels.hip)
+// the batch's state through its slot map: one k_batch_trajectory per storage type, variant and zero-velocity form
 hipError_t launch_trajectory_batch(const BatchView &b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc, hipStream_t stream)
 {
     if (b.n == 0) return hipSuccess;
     const int P = problems_per_trip(k, true);
-    const dim3 grid(trajectory_grid(b.n, P)), block(kTrajBlock);
-    const uint32_t *slot_of = b.scheduled ? b.slot_of : nullptr;
-    auto on_zero_vel = [&](auto s, auto v) {
-        using S = decltype(s);
-        constexpr int V = decltype(v)::value;
-        if (b.zero_end_vel)
-            hipLaunchKernelGGL((k_batch_trajectory<S, V, true>), grid, block, 0, stream, FromBatch<S, V, true>{(const S *)b.base, b.stride, slot_of},
-                               b.n, k, P, d_tau, d_pos, d_vel, d_acc);
-        else
-            hipLaunchKernelGGL((k_batch_trajectory<S, V, false>), grid, block, 0, stream, FromBatch<S, V, false>{(const S *)b.base, b.stride, slot_of},
-                               b.n, k, P, d_tau, d_pos, d_vel, d_acc);
-    };
-    auto on_variant = [&](auto s) {
-        if (b.variant != 3) on_zero_vel(s, std::integral_constant<int, 4>{});
-        else on_zero_vel(s, std::integral_constant<int, 3>{});
-    };
-    if (b.dtype == 0) on_variant(double{});
-    else on_variant(float{});
+    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_trajectory<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
+                                                           FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_tau, d_pos, d_vel, d_acc));
+    return hipGetLastError();
+}
+
+// ---- plot data by problem index: a range [first, first + count) of problems, wherever they lie in the batch ----
+hipError_t launch_sample_range(const BatchView &b, size_t first, size_t count, double *d_pos66, double *d_acc4, hipStream_t stream)
+{
+    if (count == 0) return hipSuccess;
+    const dim3 grid((unsigned)((count + kSampleProblems - 1) / kSampleProblems));
+    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_sample<S, V, Z>), grid, dim3(kTrajBlock), 0, stream,
+                                                           (const S *)b.base, b.stride, first, count, slots(b), d_pos66, d_acc4));
+    return hipGetLastError();
+}
+
+hipError_t launch_sample(const BatchView &b, double *d_pos66, double *d_acc4, hipStream_t stream) { return launch_sample_range(b, 0, b.n, d_pos66, d_acc4, stream); }
+
+hipError_t launch_sample_from_records(const BatchView &b, Solution *d_solution_scratch, double *d_pos66, double *d_acc4, hipStream_t stream)
+{
+    if (b.n == 0) return hipSuccess;
+    if (!b.scheduled || !b.zero_end_vel || !b.records) return hipErrorInvalidValue;
+    hipError_t e = launch_solution(b, d_solution_scratch, stream);      // every problem's (vel1, duration0, duration1) in problem order
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)((b.n + kSampleProblems - 1) / kSampleProblems));
+    RP_DISPATCH(kStorage, b, hipLaunchKernelGGL((k_sample_records<S>), grid, dim3(kTrajBlock), 0, stream,
+                                                (const StartRecord *)b.records, (const Solution *)d_solution_scratch, b.n, d_pos66, d_acc4));
     return hipGetLastError();
 }
 

@@ -158,6 +158,40 @@ def test_f4_and_f32_state_start_and_fixed_steps():
         assert err < tol
 
 
+def test_every_start_form_follows_the_one_rule():
+    """k_start_from_records and k_restart_feasible in every number mode: the written start, a restart (with end velocities: only F3 /
+    float64 restarts anywhere else) and the zero-velocity form against set_problems_device.  Two full blocks and a ragged one."""
+    orc = Oracle()
+    n = 2 * 256 + 17
+    args = _inputs(orc, 0.1, n)
+    args[3][[0, 5, 255, 256, n - 1]] = -0.0      # stored as +0
+    args[4][[1, 5, 511, 512, n - 1]] = -0.0
+    zeros = np.zeros(n)
+    for variant, dtype, storage in ((rp.VARIANT_F3, rp.DTYPE_F64, np.float64), (rp.VARIANT_F3, rp.DTYPE_F32_STATE, np.float32),
+                                    (rp.VARIANT_F4, rp.DTYPE_F64, np.float64), (rp.VARIANT_F4, rp.DTYPE_F32, np.float32)):
+        mode = (variant, dtype)
+        with rp.Batch(n, variant, dtype) as b:
+            # both velocities given, then vel0 NULL and vel2 given: the written start, and the same start again after a restart
+            for given in (args, args[:3] + [zeros, args[4]]):
+                start = er.start_state(*given, variant=variant, storage=storage)
+                ts = [_t(a) for a in given]
+                b.set_problems_vel_device(*[t.data_ptr() for t in ts[:3]], ts[3].data_ptr() if given is args else 0, ts[4].data_ptr())
+                b.sync()
+                assert np.array_equal(_bits(b.get_state()), _bits(start)), ("start", mode, given is args)
+                b.step(2)
+                assert not np.array_equal(_bits(b.get_state()), _bits(start)), ("stepped", mode)
+                b.restart()
+                assert np.array_equal(_bits(b.get_state()), _bits(start)), ("restart", mode, given is args)
+                assert np.all(b.get_iters()[0] == 0), ("restart", mode)
+            # zero velocities: the bits set_problems_device leaves in a second batch
+            _set_vel(b, args[:3] + [zeros, zeros])
+            with rp.Batch(n, variant, dtype) as rest:
+                ts = [_t(a) for a in args[:3]]
+                rest.set_problems_device(*[t.data_ptr() for t in ts])
+                rest.sync()
+                assert np.array_equal(_bits(b.get_state()), _bits(rest.get_state())), ("zero velocities", mode)
+
+
 def test_derivative_kernels_against_longdouble_and_existing_kernels():
     orc = Oracle()
     for kappa in (0.0, 0.1, 0.3):

@@ -11,7 +11,8 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CASES = ["test_zero_and_null_velocities_equal_set_problems_device", "test_start_solve_and_restart_with_velocities",
-         "test_f4_and_f32_state_start_and_fixed_steps", "test_derivative_kernels_against_longdouble_and_existing_kernels",
+         "test_f4_and_f32_state_start_and_fixed_steps", "test_every_start_form_follows_the_one_rule",
+         "test_derivative_kernels_against_longdouble_and_existing_kernels",
          "test_autograd_and_forward_ad_against_differences", "test_pool_reuse_after_velocities_is_bit_identical",
          "test_batch_edges_and_padding"]
 

@@ -3,34 +3,15 @@ without a GPU).  Any scratch (spilled VGPRs) makes the fused solve's launch time
 FOUR resident waves per SIMD (128 VGPRs: its step works in place, the cold values wait in LDS), and since round 4 so is its
 fixed-step sibling (F3: the same in-place step); the k = 1 streaming launch fits three -- all measured, see DESIGN.md's tuning log."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import kernel_usage
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+@pytest.mark.skipif(not os.path.exists(kernel_usage.HIPCC), reason="no hipcc")
 def test_headline_kernels_fit_their_waves_without_scratch():
-    src = os.path.join(ROOT, "rocket_path_amd", "csrc", "ip_kernels.hip")
-    r = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull, src],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage = {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
+    usage = kernel_usage.usage("ip_kernels.hip")
     # the benchmark's kernel k_solve_chunks<double, double, 3, STALL=false, ZV=true, MU=0, START=false>, its START=true twin (a
     # fresh batch's first solve), its ROUNDS=true twin (round 6: the watched kernel for states that were set or nudged: same budget) and
     # its fixed-step sibling k_steps_chunks<double, double, 3, ZV=true>
@@ -69,27 +50,13 @@ def test_headline_kernels_fit_their_waves_without_scratch():
     assert checked > 60
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+@pytest.mark.skipif(not os.path.exists(kernel_usage.HIPCC), reason="no hipcc")
 def test_one_wave_scheduling_kernels_fit_where_one_solve_wave_has_left():
     # schedule.hip, slim::: beside a resident solve (16 single-wave blocks of 128 VGPRs and 6.5 KB of LDS per CU) a block gets in only
     # if it needs no more than ONE retiring solve wave leaves behind in registers -- 128 VGPRs -- and its LDS fits beside the other 15
     # columns (160 KB - 15 x 6.5 KB = 62 KB free)
-    src = os.path.join(ROOT, "rocket_path_amd", "csrc", "schedule.hip")
-    r = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull, src],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert "warning" not in r.stderr, r.stderr[-2000:]
-    usage, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1)] = int(m.group(2))
+    assert "warning" not in kernel_usage.remarks("schedule.hip"), kernel_usage.remarks("schedule.hip")[-2000:]
+    usage = kernel_usage.usage("schedule.hip")
     slim = {k: v for k, v in usage.items() if "4slim" in k}
     assert len(slim) == 4, sorted(usage)      # count<records>, count<no records>, scan, scatter
     for k, v in slim.items():
