@@ -29,8 +29,8 @@
 //    same expression gives the same bits wherever it is inlined.  That is what makes the
 //    re-uses exact: a trial point that is bitwise the current point re-uses the current
 //    point's evaluation (the reference recomputes the same numbers; MEMO), the evaluation at
-//    the accepted trial point is carried into the next step instead of being recomputed, and in
-//    the gated kernels so are the sums its residual test was made of (residual_sums).
+//    the accepted trial point is carried into the next step instead of being recomputed, and by
+//    the in-place step so are the sums its residual test was made of (residual_sums).
 //  * the kernels are fp64-ALU bound (the vector ALU issues ~80 % of the cycles of a power-capped clock), so the
 //    currency is instructions: ~300 per gated Newton step (profiles/r4_sq_counters.json has the count of the
 //    shipped kernels).  An IEEE fp64 division costs 11 of them on gfx950 (v_div_scale x2, v_rcp, 5 fma,
@@ -40,11 +40,11 @@
 //    divides by t about 20 times per constraint sweep, onedpath_ip.cpp:385-391, 404-410), one for all
 //    constraints, one for the two arrow pivots, one for the boundary fraction -- 4-5 per step where the first
 //    version of this file had 19.
-//  * two forms of the step.  newton_step_inplace (the gated solve, and since round 4 every fixed-step launch of F3): the trial
+//  * two forms of the step.  newton_step_inplace (the gated solve, and every fixed-step launch of F3): the trial
 //    overwrites the state, the step's start waits in LDS (or, for small batches, registers), residual sums carried, loops tested
 //    by ballots over comparisons; FROZEN adds the post-convergence regime's search on affine pieces with its certain failures
 //    counted in closed form.  newton_step_to (F4's fixed-step launches, mu_mode 1): template switches MEMO (exact memoisation
-//    for the reference's post-convergence regime), AFFINE (with MEMO: that regime's residual loop on affine pieces), MU
+//    for the reference's post-convergence regime; F4 runs that regime's residual loop on affine pieces, kAffine), MU
 //    (rp_params.mu_mode), WAVE (stragglers of the residual loop served by the whole wave).  Both take a bookkeeping hook
 //    (halving counts for rp_batch_step_counted).
 #pragma once
@@ -228,9 +228,10 @@ template <typename T> __device__ __forceinline__ T scalar_const(T c)
 // What a lane carries from one step to the next: the reciprocals and the four accelerations.
 // GT = false: the time derivatives are rebuilt at the start of the step (14 flop) -- eight registers that are then free in
 // the residual backtracking loop, the register peak of the fixed-step kernels (memoisation state on top).  GT = true
-// (gated kernels, which have the registers): they are carried too.
-// RS = true (gated reference-mode kernels): also the three sums the residual test and the gate are made of, taken at
+// (gated kernels and the in-place step, which have the registers): they are carried too.
+// RS = true (the in-place step, newton_step_inplace): also the three sums the residual test and the gate are made of, taken at
 // the accepted trial point -- X = |grad f + G^T lam|^2, Q1 = S lam_i c_i (= -gap), Q2 = S (lam_i c_i)^2; see residual_sums.
+// X, Q1, Q2, cm, cp and x are read only by newton_step_inplace and by run_lane's evaluate / current_gap / status code.
 template <typename T, bool GT = false, bool RS = false> struct AccCarry {
     static constexpr bool has_sums = RS;
     T r0, r1;
@@ -522,7 +523,7 @@ __device__ __forceinline__ T residual_norm(const Acc<T> &e, const T (&lam)[CMap<
     return (accm + accp) + accx;
 }
 
-// The same residual in the form the gated kernels carry from step to step.  With t_i = lam_i c_i,
+// The same residual in the form the in-place step carries from step to step.  With t_i = lam_i c_i,
 //     |r(p)|^2 = X + S (t_i + p)^2 = X + Q2 + p (2 Q1 + m p),      X = |grad f + G^T lam|^2, Q1 = S t_i, Q2 = S t_i^2,
 // and the surrogate gap of the same point is -Q1.  X, Q1 and Q2 do not depend on p: evaluated once at the accepted trial
 // point they serve that step's residual test, the next step's gate and perturbation (gap = -Q1, p = gap / (10 m)) AND the
@@ -670,7 +671,7 @@ __device__ __forceinline__ void solve_arrow(T a, T b, T c, T d, T e, T rv, T r0,
 
 // ---- the Newton direction (onedpath_ip.cpp:812-887, condensed) --------------------------
 // In: point (v; e = values + grads there), multipliers, perturbation p.  Out: dx, d lam.
-// HAVE_C: cm_in / cp_in hold -a_j - L and a_j - L of this very point (gated kernels carry them from the residual sums of the
+// HAVE_C: cm_in / cp_in hold -a_j - L and a_j - L of this very point (the in-place step carries them from the residual sums of the
 // accepted trial); otherwise they are formed here.
 // sg[i]: a number whose SIGN BIT is set iff the full step would drive multiplier i negative (lam_i + dl_i < 0) -- what the
 // fraction-to-boundary rule screens on.  F3 gets it for nothing: lam_i + dl_i = (1/c_i) (lam_i g_i.dx -+ p) and 1/c_i < 0 at a
@@ -1135,9 +1136,7 @@ __device__ __forceinline__ int skip_certain_halvings(const P &k, const KParams<T
 // (the reference recomputes the same numbers); what it buys is the reference's post-convergence regime, where x no
 // longer moves and every step still walks ~48 residual halvings (onedpath_ip.cpp:932-945) -- fixed-step runs.  A gated
 // solve stops long before that regime, so its kernels are built without the checks.
-// AFFINE (with MEMO): the post-convergence loop runs on the affine pieces of the residual (44 more
-// registers: the one-problem-per-lane streaming kernels, which run the small fixed-step batches, have them; the tiled
-// kernels at 168 VGPRs do not).
+// kAffine (with MEMO): the post-convergence loop runs on the affine pieces of the residual (44 more registers).
 //
 // MU (rp_params.mu_mode): 0 = the reference's fixed centring, p = gap / (m * mu_divisor) (onedpath_ip.cpp:812) -- the only
 // mode the parity tests are about.  1 = centring by trial: with the split direction d(p) = d_a + p d_c, the candidates
@@ -1149,15 +1148,23 @@ __device__ __forceinline__ int skip_certain_halvings(const P &k, const KParams<T
 // WAVE (ungated kernels whose lanes all take the same number of steps: every live lane of the wave is inside this function at
 // the same time; the value is the instantiating kernel's block size and must be 64): the residual loop's stragglers are served by
 // the whole wave, see "wave-parallel line search" below.
-template <typename T, int VARIANT, class P, bool MEMO = true, bool AFFINE = false, int MU = 0, class D = NoDiag, int WAVE = 0>
+//
+// Which residual-loop form this step uses once the trial point has become x: every kernel of a variant uses the same one, so
+// that all launch shapes agree bit for bit.  F4 runs on affine pieces: it reaches that regime within a dozen steps and has the
+// registers.  F3's fixed-step launches run newton_step_inplace<FROZEN>, whose post-convergence search is on affine pieces as
+// well; what is left of F3 here is mu_mode 1.  (F3 on affine pieces here was measured: no gain, 168 VGPRs + 2 spilled in its
+// chunk kernel, profiles/r3_tuning.md.)
+template <int VARIANT> constexpr bool kAffine = (VARIANT == 4);
+
+template <typename T, int VARIANT, class P, bool MEMO = true, int MU = 0, int WAVE = 0, class D = NoDiag>
 __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp, T gap,
                                                const T v, const T t0, const T t1, const T (&lam)[CMap<VARIANT>::NC],
-                                               const AccCarry<T, !MEMO, !MEMO && MU == 0> &c,
-                                               T &nv, T &nt0, T &nt1, T (&nlam)[CMap<VARIANT>::NC], AccCarry<T, !MEMO, !MEMO && MU == 0> &nc,
+                                               const AccCarry<T, !MEMO> &c,
+                                               T &nv, T &nt0, T &nt1, T (&nlam)[CMap<VARIANT>::NC], AccCarry<T, !MEMO> &nc,
                                                D &diag)
 {
     constexpr int NC = CMap<VARIANT>::NC;
-    constexpr bool SUMS = !MEMO && MU == 0;      // the residual in its carried form (residual_sums)
+    static_assert(MEMO || MU != 0, "gated reference-mode launches step in place (kStepInPlace, newton_step_inplace): this function has no carried-sums form");
     const T L = kp.limit;
     const T p = gap * kp.inv_mu_den;                      // onedpath_ip.cpp:812
 
@@ -1178,11 +1185,8 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
             for (int j = 0; j < 4; ++j) e.gt[j] = c.gt[j];
         }
         if constexpr (MU == 0) {
-            // carried C: 18 more VGPRs for 8 fewer instructions per step
-            if constexpr (SUMS && VARIANT == 3) direction<T, VARIANT, P, true>(k, kp, v, lam, e, p, dxv, dx0, dx1, dl, sg, suspect, c.cm, c.cp, &c.x);
-            else direction<T, VARIANT, P>(k, kp, v, lam, e, p, dxv, dx0, dx1, dl, sg, suspect);
-            if constexpr (SUMS) r0n = residual_from_sums<T, NC>(c.X, c.Q1, c.Q2, p);
-            else r0n = residual_norm<T, VARIANT, false>(e, lam, dl, T(0), p, L);      // onedpath_ip.cpp:932
+            direction<T, VARIANT, P>(k, kp, v, lam, e, p, dxv, dx0, dx1, dl, sg, suspect);
+            r0n = residual_norm<T, VARIANT, false>(e, lam, dl, T(0), p, L);      // onedpath_ip.cpp:932
         } else {
             T dxa[3], dla[NC], dxc[3], dlc[NC];
             direction_split<T, VARIANT, P>(k, kp, v, lam, e, dxa, dla, dxc, dlc);
@@ -1273,10 +1277,9 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
 
     // -- backtrack until the residual decreases (onedpath_ip.cpp:932-945) --
     bool accepted = false;         // et = values at the point the loop broke on
-    T tl[SUMS ? NC : 1];           // gated kernels: the trial multipliers lam + s dl of the last evaluated trial
     int it = 0;
     bool frozen = false;           // the trial point has become bitwise x (and stays so: s only shrinks)
-    if constexpr (WAVE != 0 && !SUMS) {
+    if constexpr (WAVE != 0) {
         // ---- wave-parallel line search ----
         // WAVE = the THREADS PER BLOCK of the kernel that instantiates this form (0: the serial search).  The service below broadcasts
         // through one LDS area per block with no barrier, which is correct only in a single-wave block (a wave's LDS operations
@@ -1382,7 +1385,7 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
             }
         }
     } else if constexpr (!MEMO) {
-        // Kernels without memoisation (the gated ones): the trial point and its accelerations are formed where s changes --
+        // Kernels without memoisation (mu_mode 1's gated launches): the trial point and its accelerations are formed where s changes --
         // by the feasibility loop, or after a failed residual trial -- so the common case, first trial accepted, runs straight
         // through with nothing to select.  (The feasibility loop leaves no evaluation only when it ran out of halvings.)
         if (!et_valid && it < kp.max_bt) {
@@ -1394,15 +1397,7 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
         while (it < kp.max_bt) {
             accel_grads(k, tv, et);
             diag.moving();
-            T rn;
-            if constexpr (SUMS) {
-#pragma unroll
-                for (int i = 0; i < NC; ++i) tl[i] = fma_(dl[i], s, lam[i]);              // kept: the accepted trial IS the update
-                residual_sums<T, VARIANT, false>(et, tl, dl, T(0), L, nc.X, nc.Q1, nc.Q2, nc.cm, nc.cp);   // overwritten by every trial: the accepted one stays
-                rn = residual_from_sums<T, NC>(nc.X, nc.Q1, nc.Q2, p);
-            } else {
-                rn = residual_norm<T, VARIANT, true>(et, lam, dl, s, p, L);
-            }
+            const T rn = residual_norm<T, VARIANT, true>(et, lam, dl, s, p, L);
             if (rn <= r0n * (T(1) - kp.armijo * s)) {
                 accepted = true;
                 break;
@@ -1428,15 +1423,7 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
         if (!et_valid) accel_values(k, tv, tt0, tt1, et);
         accel_grads(k, tv, et);
         diag.moving();
-        T rn;
-        if constexpr (SUMS) {
-#pragma unroll
-            for (int i = 0; i < NC; ++i) tl[i] = fma_(dl[i], s, lam[i]);              // kept: the accepted trial IS the update
-            residual_sums<T, VARIANT, false>(et, tl, dl, T(0), L, nc.X, nc.Q1, nc.Q2, nc.cm, nc.cp);   // overwritten by every trial: the accepted one stays
-            rn = residual_from_sums<T, NC>(nc.X, nc.Q1, nc.Q2, p);
-        } else {
-            rn = residual_norm<T, VARIANT, true>(et, lam, dl, s, p, L);
-        }
+        const T rn = residual_norm<T, VARIANT, true>(et, lam, dl, s, p, L);
         et_valid = false;
         if (rn <= r0n * (T(1) - kp.armijo * s)) {
             accepted = true;
@@ -1453,7 +1440,7 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
 #pragma unroll
             for (int j = 0; j < 4; ++j) et.a[j] = c.a[j];
             accel_grads(k, v, et);
-            if constexpr (!AFFINE) {      // the kernels without the registers for the affine pieces: the direct evaluation
+            if constexpr (!kAffine<VARIANT>) {      // the kernels without the registers for the affine pieces: the direct evaluation
                 for (; it < kp.max_bt; ++it) {
                     const T rn = residual_norm<T, VARIANT, true>(et, lam, dl, s, p, L);
                     if (rn <= r0n * (T(1) - kp.armijo * s)) {
@@ -1473,33 +1460,14 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
     }
 
     // -- take the step (onedpath_ip.cpp:949-952) --
-    if constexpr (SUMS) {
-        // Gated kernels: the accepted trial point and multipliers ARE the update, bit for bit.  A loop that ran out of
-        // halvings (its last s was never evaluated) forms that last trial here, into the same registers, so that one set
-        // of values leaves the step whichever way it ended.
-        if (!accepted) {
-            tv = fma_(dxv, s, v);
-            tt0 = fma_(dx0, s, t0);
-            tt1 = fma_(dx1, s, t1);
+    nv = fma_(dxv, s, v);
+    nt0 = fma_(dx0, s, t0);
+    nt1 = fma_(dx1, s, t1);
 #pragma unroll
-            for (int i = 0; i < NC; ++i) tl[i] = fma_(dl[i], s, lam[i]);
-            accel_values(k, tv, tt0, tt1, et);
-            accel_grads(k, tv, et);
-            residual_sums<T, VARIANT, false>(et, tl, dl, T(0), L, nc.X, nc.Q1, nc.Q2, nc.cm, nc.cp);
-        }
-        nv = tv; nt0 = tt0; nt1 = tt1;
-#pragma unroll
-        for (int i = 0; i < NC; ++i) nlam[i] = tl[SUMS ? i : 0];
-    } else {
-        nv = fma_(dxv, s, v);
-        nt0 = fma_(dx0, s, t0);
-        nt1 = fma_(dx1, s, t1);
-#pragma unroll
-        for (int i = 0; i < NC; ++i) nlam[i] = fma_(dl[i], s, lam[i]);
-        if (!accepted) {                               // the loop ran out of halvings: its last s was never evaluated
-            accel_values(k, nv, nt0, nt1, et);
-            if constexpr (!MEMO) accel_grads(k, nv, et);
-        }
+    for (int i = 0; i < NC; ++i) nlam[i] = fma_(dl[i], s, lam[i]);
+    if (!accepted) {                               // the loop ran out of halvings: its last s was never evaluated
+        accel_values(k, nv, nt0, nt1, et);
+        if constexpr (!MEMO) accel_grads(k, nv, et);
     }
     nc.r0 = et.r0; nc.r1 = et.r1;
 #pragma unroll
@@ -1511,22 +1479,22 @@ __device__ __forceinline__ void newton_step_to(const P &k, const KParams<T> &kp,
 }
 
 // the same in place
-template <typename T, int VARIANT, class P, bool MEMO = true, bool AFFINE = false, int MU = 0, class D = NoDiag, int WAVE = 0>
+template <typename T, int VARIANT, class P, bool MEMO = true, int MU = 0, int WAVE = 0, class D = NoDiag>
 __device__ __forceinline__ void newton_step(const P &k, const KParams<T> &kp, T gap,
-                                            T &v, T &t0, T &t1, T (&lam)[CMap<VARIANT>::NC], AccCarry<T, !MEMO, !MEMO && MU == 0> &c,
+                                            T &v, T &t0, T &t1, T (&lam)[CMap<VARIANT>::NC], AccCarry<T, !MEMO> &c,
                                             D &diag)
 {
     constexpr int NC = CMap<VARIANT>::NC;
     T nv, nt0, nt1, nlam[NC];
-    AccCarry<T, !MEMO, !MEMO && MU == 0> nc;
-    newton_step_to<T, VARIANT, P, MEMO, AFFINE, MU, D, WAVE>(k, kp, gap, v, t0, t1, lam, c, nv, nt0, nt1, nlam, nc, diag);
+    AccCarry<T, !MEMO> nc;
+    newton_step_to<T, VARIANT, P, MEMO, MU, WAVE>(k, kp, gap, v, t0, t1, lam, c, nv, nt0, nt1, nlam, nc, diag);
     v = nv; t0 = nt0; t1 = nt1;
 #pragma unroll
     for (int i = 0; i < NC; ++i) lam[i] = nlam[i];
     c = nc;
 }
 
-// ---- the same step IN PLACE, for the gated solve ----------------------------------------------------------------------
+// ---- the same step IN PLACE: the gated solve in the reference's mu mode, and every fixed-step launch of F3 -------------
 // newton_step_to keeps the point and multipliers a step starts from next to the trial it is evaluating (a rejected trial is
 // followed by another from the same start), and its loops are left by every lane when that lane is done -- for which the
 // compiler copies every value that is live after such a loop once per trip, for the lanes that have left: 11 + 9 64-bit moves
@@ -1534,8 +1502,9 @@ __device__ __forceinline__ void newton_step(const P &k, const KParams<T> &kp, T 
 // overwrites the state (a multiply-add onto itself), the start of the step waits in LDS instead -- 11 ds_write per step, which
 // issue on the LDS port beside the other waves' arithmetic -- to be read back only when a trial is rejected (one step in five
 // has a rejected feasibility trial, a rejected residual trial is rare before convergence), and the loops run while ANY lane of
-// the wave is inside (wave-uniform exits: nothing to copy).  Same functions, same operands, same order of decisions as
-// newton_step_to<MEMO = false, MU = 0>: every bit of every iterate was the same (36 cases, profiles/r3_inplace_ab.log).
+// the wave is inside (wave-uniform exits: nothing to copy).  Same functions, same operands, same order of decisions as the
+// out-of-place form it replaced, which carried the same sums: every bit of every iterate was the same (36 cases,
+// profiles/r3_inplace_ab.log); that form is no longer in the source.
 // bk: where the step's start waits (LdsColumn: this lane's column of the block's backup area, field q at p[q * 64]; volatile so that the compiler neither forwards the
 // stored values to the reads (keeping them in registers is what this form is there to avoid) nor drops the stores.
 // The loops are written with the trial formed where s is set (at the bottom, from the backed-up start), so that a trial
@@ -1578,6 +1547,7 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
         e.r0 = c.r0; e.r1 = c.r1;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { e.a[j] = c.a[j]; e.gt[j] = c.gt[j]; }
+        // carried C: 18 more VGPRs for 8 fewer instructions per step
         if constexpr (VARIANT == 3) direction<T, VARIANT, P, true>(k, kp, v, lam, e, p, dxv, dx0, dx1, dl, sg, suspect, c.cm, c.cp, &c.x);
         else direction<T, VARIANT, P>(k, kp, v, lam, e, p, dxv, dx0, dx1, dl, sg, suspect);
     }
@@ -1758,22 +1728,15 @@ __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T>
     for (int j = 0; j < 4; ++j) { c.a[j] = et.a[j]; c.gt[j] = et.gt[j]; }
 }
 
-// (the gated solve's call: no bookkeeping, no frozen regime)
+// (the gated solve's call: no bookkeeping, no frozen regime.  It is a function of its own only because, with run_lane's
+// bookkeeping hook passed through instead, fifteen k_solve_chunks instantiations compile to other instruction streams
+// (profiles/step_forms_refactor.md); once the streams allow it, it folds into its caller)
 template <typename T, int VARIANT, class P, class BK>
 __device__ __forceinline__ void newton_step_inplace(const P &k, const KParams<T> &kp, T gap, T &v, T &t0, T &t1, T (&lam)[CMap<VARIANT>::NC],
                                                     AccCarry<T, true, true> &c, BK &bk, int &it)
 {
     NoDiag none;
-    newton_step_inplace<T, VARIANT, P, false, NoDiag, BK>(k, kp, gap, v, t0, t1, lam, c, bk, it, none);
-}
-
-// the common call: no bookkeeping
-template <typename T, int VARIANT, class P, bool MEMO = true, bool AFFINE = false, int MU = 0>
-__device__ __forceinline__ void newton_step(const P &k, const KParams<T> &kp, T gap,
-                                            T &v, T &t0, T &t1, T (&lam)[CMap<VARIANT>::NC], AccCarry<T, !MEMO, !MEMO && MU == 0> &c)
-{
-    NoDiag none;
-    newton_step<T, VARIANT, P, MEMO, AFFINE, MU, NoDiag>(k, kp, gap, v, t0, t1, lam, c, none);
+    newton_step_inplace<T, VARIANT, P, false>(k, kp, gap, v, t0, t1, lam, c, bk, it, none);
 }
 
 }  // namespace rp

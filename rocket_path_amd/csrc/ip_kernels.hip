@@ -19,7 +19,7 @@
 //                      single-wave block, state in registers from its first load to its last store (LDS only as the in-place
 //                      step's backup column, no staging), longest chunks dispatched first
 //   k_steps_chunks     k >= 2 ungated steps: the same shape, fixed step count.  F3 runs the gated solve's in-place step here too
-//                      (round 4; below three waves per SIMD an instantiation that keeps the step's start in registers); F4 keeps
+//                      (below three waves per SIMD an instantiation that keeps the step's start in registers); F4 keeps
 //                      newton_step_to with the wave-parallel line search -- a wave's stragglers in the residual loop are served
 //                      by the whole wave
 //   k_newton_stream16  k = 1 (one launch per Newton step), the HBM-streaming form: 16 B per lane (two doubles / four floats =
@@ -99,46 +99,62 @@ constexpr int kNewtonWaves = 2;      // minimum waves per SIMD the register allo
 constexpr int kGatedWaves = 4;       // 128 VGPRs (112-128 used): the in-place step with the cold values parked in LDS fits without a spill in the loop; 1 Mi problems = 16,384
                                      // waves = exactly four full rounds of the chip's 4,096 wave slots (three per SIMD: 5.33 rounds).  The stall-detector
                                      // twin (two more live values, 10 spilled at 128) stays at three
-// Which residual-loop form the fixed-step kernels use once the trial point has become x (newton_step's AFFINE): every kernel of
-// a variant uses the same one, so that all launch shapes agree bit for bit.  This switch concerns newton_step_to, i.e. F4 (affine
-// pieces: it reaches that regime within a dozen steps and has the registers) and mu_mode 1; since round 4 F3's fixed-step
-// launches run newton_step_inplace<FROZEN>, whose post-convergence search is on affine pieces as well (ip_core.h).
-// (F3 on affine pieces as well was measured: no gain, 168 VGPRs + 2 spilled in its chunk kernel, profiles/r3_tuning.md.)
-template <int VARIANT> constexpr bool kAffine = (VARIANT == 4);
 constexpr int kTiledWaves = 3;      // F4's fixed-step chunk kernels (156-168 VGPRs) and F3's register-column instantiation; the in-place kernels have kGatedWaves
 
-// The per-lane body shared by both Newton kernels: up to k steps on the state held in registers.
-// STALL: compile the stall detector in (two more live registers); the tiled solve instantiates both
-// forms and picks by rp_params.stall_window, so the default (off) pays nothing for it.
-// S = storage type of the batch.  When it differs from the compute type T (fp32 state, fp64 arithmetic) the state is
-// rounded to S after every step, so that a step is a function "S state -> S state" whatever the launch shape:
-// step(k) stays bit-identical to k x step(1).
-// WAVE (ungated launches only, whose live lanes all take the same k steps together): the residual loop's stragglers are served
-// by the whole wave (newton_step_to, "wave-parallel line search").
-// Which step a launch runs.  In place (newton_step_inplace: the step's start waits in LDS, residual sums carried, wave-uniform
-// loops): the gated solve in the reference's mu mode, and -- round 4 -- EVERY fixed-step launch of F3, whose kernels ran
-// newton_step_to with per-lane loop exits until then (389 VALU instructions per step against the gated kernel's 307).  Since all
-// of F3's fixed-step kernels run the one function, step(k) is k x step(1) bit for bit in every launch shape as before, and a
-// gated launch whose gate never closes now takes the very same steps as well.  F4's fixed-step launches keep newton_step_to (the
-// wave-parallel line search and the affine post-convergence loop are built on it); mu_mode 1 likewise.
+// Which step a launch runs.  In place (newton_step_inplace: the step's start waits in LDS or registers, residual sums carried,
+// wave-uniform loops): the gated solve in the reference's mu mode and EVERY fixed-step launch of F3 (with FROZEN, the
+// post-convergence regime's loops).  All of F3's fixed-step kernels run the one function, so step(k) is k x step(1) bit for bit in
+// every launch shape, and a gated launch whose gate never closes takes the very same steps.  Out of place (newton_step_to): F4's
+// fixed-step launches (the wave-parallel line search, the parked fixed points and the affine post-convergence loop are built on
+// it) and every launch in mu_mode 1.
 template <int VARIANT, bool GATED, int MU, class D>
 constexpr bool kStepInPlace = MU == 0 && (GATED ? std::is_same<D, NoDiag>::value : VARIANT == 3);
 
-// PARK (F4's fused fixed-step launches on an fp32 state with fp64 arithmetic): a lane whose step has left its STORED
-// state bit for bit where it was sits the remaining steps of the launch out -- see the ungated loop below.  (Pure fp32 arithmetic keeps
-// the plain loop: there the stuck problems are few -- its Armijo test stops resolving long before a state freezes -- and the bookkeeping
-// cost more than it saved: 50.0 against 53.8 G steps/s at 1 Mi x 50, profiles/r6_f4_park_ab.log.  The code below still handles S == T.)
-template <typename T, int VARIANT, bool GATED, bool STALL = GATED, class P = Prob<T>, typename S = T, bool AFFINE = false, int MU = 0, class D = NoDiag, int WAVE = 0,
-          class BK = LdsColumn<T>, bool PARK = false, bool ROUNDS = false>
+// What a launch chooses for run_lane, as one type: Steps is the default -- k ungated steps, the reference's centring, every
+// lane searching for itself -- and a call site names only what it does differently.
+//   GATED   stop at the gate (run_lane below)
+//   STALL   compile the stall detector in (two more live registers); the gated solve instantiates both forms and picks by
+//           rp_params.stall_window, so the default (off) pays nothing for it
+//   MU      rp_params.mu_mode
+//   WAVE    (ungated launches only, whose live lanes all take the same k steps together; the kernel's block size, 64) the
+//           residual loop's stragglers are served by the whole wave (newton_step_to, "wave-parallel line search")
+//   PARK    (F4's fused fixed-step launches on an fp32 state with fp64 arithmetic) a lane whose step has left its STORED state
+//           bit for bit where it was sits the remaining steps of the launch out -- see the loop below.  (Pure fp32 arithmetic
+//           keeps the plain loop: there the stuck problems are few -- its Armijo test stops resolving long before a state
+//           freezes -- and the bookkeeping cost more than it saved: 50.0 against 53.8 G steps/s at 1 Mi x 50,
+//           profiles/r6_f4_park_ab.log.  The code below still handles S == T.)
+//   ROUNDS  the launch is one round of a solve in rounds (k_solve_chunks)
+struct Steps {
+    static constexpr bool GATED = false, STALL = false, PARK = false, ROUNDS = false;
+    static constexpr int MU = 0, WAVE = 0;
+};
+template <int MU_> struct StepsMu : Steps { static constexpr int MU = MU_; };
+template <int WAVE_, bool PARK_> struct StepsWave : Steps { static constexpr int WAVE = WAVE_; static constexpr bool PARK = PARK_; };
+template <bool STALL_, int MU_, bool ROUNDS_> struct Gated : Steps {
+    static constexpr bool GATED = true, STALL = STALL_, ROUNDS = ROUNDS_;
+    static constexpr int MU = MU_;
+};
+
+// The per-lane body shared by all Newton kernels: up to k steps on the state held in registers.  O: one of the types above.
+// S = storage type of the batch.  When it differs from the compute type T (fp32 state, fp64 arithmetic) the state is
+// rounded to S after every step, so that a step is a function "S state -> S state" whatever the launch shape:
+// step(k) stays bit-identical to k x step(1).
+// diag: line-search bookkeeping (NoDiag: none); backup: where the in-place step's start waits (unused out of place).
+// Each of the three plain loops below spells the step and the rounding out only because, as a shared lambda or function, either
+// of them moves instruction and register counts of the gated kernels (profiles/step_forms_refactor.md); once the compiled streams
+// allow it they are one step() and one round_to_storage().
+template <typename T, int VARIANT, typename S, class O, class P, class D, class BK = LdsColumn<T>>
 __device__ __forceinline__ void run_lane(const P &pr, const KParams<T> &kp, int k, T tol, int max_iter,
                                          T &v, T &t0, T &t1, T (&lam)[CMap<VARIANT>::NC],
                                          int &it, uint32_t &st, int &steps_here, bool &still_open, D &diag, BK backup = BK{})
 {
+    constexpr bool GATED = O::GATED, STALL = O::STALL, PARK = O::PARK, ROUNDS = O::ROUNDS;
+    constexpr int MU = O::MU, WAVE = O::WAVE;
     static_assert(!(WAVE != 0 && GATED), "lanes of a gated solve leave the loop at different steps");
     constexpr bool INPLACE = kStepInPlace<VARIANT, GATED, MU, D>;
-    // gated kernels carry the time derivatives as well (newton_step's MEMO = !GATED) and, in the reference's mu mode, the
-    // residual sums, from which the gap of the current point comes for free; so does every launch that steps in place
-    using Carry = AccCarry<T, GATED || INPLACE, (GATED && MU == 0) || INPLACE>;
+    // a launch that steps in place carries the time derivatives and the residual sums, from which the gap of the current point
+    // comes for free; a gated launch out of place (mu_mode 1: newton_step_to without memoisation) the time derivatives
+    using Carry = AccCarry<T, GATED || INPLACE, INPLACE>;
     Carry e;            // the evaluation at the current point, carried from step to step
     auto evaluate = [&]() {
         Acc<T> e0;
@@ -191,10 +207,8 @@ __device__ __forceinline__ void run_lane(const P &pr, const KParams<T> &kp, int 
                 if (__popcll(stepping) <= kp.handoff_lanes) { if (++lonely > kp.handoff_patience) break; }
             }
             if (above && may) {
-                if constexpr (INPLACE)
-                    newton_step_inplace<T, VARIANT, P, BK>(pr, kp, gap, v, t0, t1, lam, e, backup, halvings);      // the step's start waits in LDS, the accepted trial is the state
-                else
-                    newton_step<T, VARIANT, P, false, AFFINE, MU, D, WAVE>(pr, kp, gap, v, t0, t1, lam, e, diag);      // gated solves never reach the regime the memoisation is for
+                if constexpr (INPLACE) newton_step_inplace<T, VARIANT>(pr, kp, gap, v, t0, t1, lam, e, backup, halvings);      // the step's start waits in LDS, the accepted trial is the state
+                else newton_step<T, VARIANT, P, false, MU, WAVE>(pr, kp, gap, v, t0, t1, lam, e, diag);      // gated solves never reach the regime the memoisation is for
                 if constexpr (sizeof(S) != sizeof(T)) {
                     v = (T)(S)v; t0 = (T)(S)t0; t1 = (T)(S)t1;
 #pragma unroll
@@ -235,10 +249,8 @@ __device__ __forceinline__ void run_lane(const P &pr, const KParams<T> &kp, int 
                     else if (++since_best >= kp.stall_window) { st |= RP_ST_STALLED; done = true; open = false; }
                 }
                 if (open) {
-                    if constexpr (INPLACE)
-                        newton_step_inplace<T, VARIANT, P, BK>(pr, kp, gap, v, t0, t1, lam, e, backup, halvings);
-                    else
-                        newton_step<T, VARIANT, P, false, AFFINE, MU, D, WAVE>(pr, kp, gap, v, t0, t1, lam, e, diag);
+                    if constexpr (INPLACE) newton_step_inplace<T, VARIANT>(pr, kp, gap, v, t0, t1, lam, e, backup, halvings);
+                    else newton_step<T, VARIANT, P, false, MU, WAVE>(pr, kp, gap, v, t0, t1, lam, e, diag);
                     if constexpr (sizeof(S) != sizeof(T)) {
                         v = (T)(S)v; t0 = (T)(S)t0; t1 = (T)(S)t1;
 #pragma unroll
@@ -279,7 +291,7 @@ __device__ __forceinline__ void run_lane(const P &pr, const KParams<T> &kp, int 
                 // fp32-state instantiation, 166 of the 168 VGPRs three waves allow, spills; recomputing them is six instructions per step)
                 P pq = pr;
                 if constexpr (sizeof(T) == 8) asm volatile("" : "+v"(pq.dx0), "+v"(pq.dx1));
-                newton_step_to<T, VARIANT, P, true, AFFINE, MU, D, WAVE>(pq, kp, gap, v, t0, t1, lam, e, nv, nt0, nt1, nlam, ne, diag);
+                newton_step_to<T, VARIANT, P, true, MU, WAVE>(pq, kp, gap, v, t0, t1, lam, e, nv, nt0, nt1, nlam, ne, diag);
                 // Round to the storage type and take the new state; behind a screen on vel1 alone (a moving iterate never repeats its velocity
                 // bit for bit: one conversion and one compare per step) the whole state is compared with what was stored, value by value
                 // before it is overwritten (the kernel has no registers to hold two states side by side).
@@ -309,10 +321,8 @@ __device__ __forceinline__ void run_lane(const P &pr, const KParams<T> &kp, int 
     } else
     for (int s = 0; s < k; ++s) {
         const T gap = current_gap();
-        if constexpr (INPLACE)
-            newton_step_inplace<T, VARIANT, P, true, D, BK>(pr, kp, gap, v, t0, t1, lam, e, backup, halvings, diag);      // FROZEN: with the post-convergence regime's loops
-        else
-            newton_step<T, VARIANT, P, true, AFFINE, MU, D, WAVE>(pr, kp, gap, v, t0, t1, lam, e, diag);
+        if constexpr (INPLACE) newton_step_inplace<T, VARIANT, P, true>(pr, kp, gap, v, t0, t1, lam, e, backup, halvings, diag);      // FROZEN: with the post-convergence regime's loops
+        else newton_step<T, VARIANT, P, true, MU, WAVE>(pr, kp, gap, v, t0, t1, lam, e, diag);
         if constexpr (sizeof(S) != sizeof(T)) {
             v = (T)(S)v; t0 = (T)(S)t0; t1 = (T)(S)t1;
 #pragma unroll
@@ -350,14 +360,40 @@ __device__ __forceinline__ void run_lane(const P &pr, const KParams<T> &kp, int 
     }
 }
 
-// the common call: no line-search bookkeeping
-template <typename T, int VARIANT, bool GATED, bool STALL = GATED, class P = Prob<T>, typename S = T, bool AFFINE = false, int MU = 0, int WAVE = 0, bool PARK = false>
-__device__ __forceinline__ void run_lane(const P &pr, const KParams<T> &kp, int k, T tol, int max_iter,
-                                         T &v, T &t0, T &t1, T (&lam)[CMap<VARIANT>::NC],
-                                         int &it, uint32_t &st, int &steps_here, bool &still_open, LdsColumn<T> backup = LdsColumn<T>{})
+// run_lane for the launches without bookkeeping that name no column or one in LDS.  It is a function level of its own only because
+// eleven kernels (mu_mode 1 with zero end velocities, F4's k_steps_chunks) compile to other instruction streams when they call
+// run_lane with a NoDiag of their own (profiles/step_forms_refactor.md); once the streams allow it, it folds into its callers.
+template <typename T, int VARIANT, typename S, class O, class P>
+__device__ __forceinline__ void run_lane_plain(const P &pr, const KParams<T> &kp, int k, T tol, int max_iter,
+                                               T &v, T &t0, T &t1, T (&lam)[CMap<VARIANT>::NC],
+                                               int &it, uint32_t &st, int &steps_here, bool &still_open, LdsColumn<T> backup = LdsColumn<T>{})
 {
     NoDiag none;
-    run_lane<T, VARIANT, GATED, STALL, P, S, AFFINE, MU, NoDiag, WAVE, LdsColumn<T>, PARK>(pr, kp, k, tol, max_iter, v, t0, t1, lam, it, st, steps_here, still_open, none, backup);
+    run_lane<T, VARIANT, S, O>(pr, kp, k, tol, max_iter, v, t0, t1, lam, it, st, steps_here, still_open, none, backup);
+}
+
+// ---- what the kernels around run_lane share ----
+// The single-wave chunk kernels' LDS column: 3 + NC fields x 64 lanes where the in-place step parks the point and multipliers
+// a step started from, and two more for the problem's deltas.  The deltas go there here; the problem comes back in the form
+// whose every use of them is a ds_read (ProbLds).
+template <int NC> constexpr int kChunkColumn = (3 + NC + 2) * 64;
+template <int NC, typename T, class P>
+__device__ __forceinline__ ProbLds<T, P::zero_vel> park_deltas(LdsBackup<T> col, const P &pr)
+{
+    col[(3 + NC) * 64] = pr.dx0;
+    col[(3 + NC + 1) * 64] = pr.dx1;
+    ProbLds<T, P::zero_vel> pl;
+    if constexpr (!P::zero_vel) { pl.v0 = pr.v0; pl.v2 = pr.v2; }
+    pl.dx0.at = col + (3 + NC) * 64;
+    pl.dx1.at = col + (3 + NC + 1) * 64;
+    return pl;
+}
+// The 256-thread streaming kernels' backup area: one column set per wave, fields 64 apart; this lane's column in its wave's
+template <int NC> constexpr int kBlockColumns = (3 + NC) * kBlock;
+template <int NC, typename T>
+__device__ __forceinline__ LdsBackup<T> wave_column(T *s_backup)
+{
+    return (LdsBackup<T>)&s_backup[(threadIdx.x >> 6) * (3 + NC) * 64 + (threadIdx.x & 63)];
 }
 
 // ---------------------------------------------------------------------------------------
@@ -444,7 +480,7 @@ k_solve_chunks(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T> 
     // where the in-place step (newton_step_inplace) parks the point and multipliers a step started from: 11 (F4: 7) fields x 64 lanes
     // ... and the problem's two deltas (ProbLds): 13 (9) fields
     constexpr bool kInPlace = kStepInPlace<VARIANT, true, MU, NoDiag>;
-    __shared__ T s_backup[kInPlace ? (3 + NC + 2) * 64 : 1];
+    __shared__ T s_backup[kInPlace ? kChunkColumn<NC> : 1];
 
     if (active) {
         S *f = base + i;
@@ -482,19 +518,16 @@ k_solve_chunks(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T> 
         // in, and both are read again (START: known) when the results are merged below.
         int it_new = it;
         uint32_t flags = 0;
+        using Solve = Gated<STALL, MU, ROUNDS>;
         if constexpr (kInPlace) {
             LdsBackup<T> col = (LdsBackup<T>)&s_backup[threadIdx.x];
-            col[(3 + NC) * 64] = pr.dx0;
-            col[(3 + NC + 1) * 64] = pr.dx1;
-            ProbLds<T, ZV> pl;
-            if constexpr (!ZV) { pl.v0 = pr.v0; pl.v2 = pr.v2; }
-            pl.dx0.at = col + (3 + NC) * 64;
-            pl.dx1.at = col + (3 + NC + 1) * 64;
+            const auto pl = park_deltas<NC>(col, pr);
+            const LdsColumn<T> start{col};
             NoDiag none;
-            run_lane<T, VARIANT, true, STALL, ProbLds<T, ZV>, S, false, MU, NoDiag, 0, LdsColumn<T>, false, ROUNDS>(pl, kp, k, tol, max_iter, v, t0, t1, lam, it_new, flags, steps_here, still_open, none, LdsColumn<T>{col});
+            run_lane<T, VARIANT, S, Solve>(pl, kp, k, tol, max_iter, v, t0, t1, lam, it_new, flags, steps_here, still_open, none, start);
         } else {
             static_assert(!ROUNDS, "rounds are built on the in-place step's launch shape");
-            run_lane<T, VARIANT, true, STALL, Prob<T, ZV>, S, false, MU>(pr, kp, k, tol, max_iter, v, t0, t1, lam, it_new, flags, steps_here, still_open);
+            run_lane_plain<T, VARIANT, S, Solve>(pr, kp, k, tol, max_iter, v, t0, t1, lam, it_new, flags, steps_here, still_open);
         }
         // the store addresses are formed only now (the barrier keeps the compiler from holding them in registers across the steps),
         // from the lane number the hardware counts rather than the thread index that came in a register
@@ -582,11 +615,11 @@ k_steps_chunks(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T> 
 {
     constexpr int NC = CMap<VARIANT>::NC;
     constexpr int CB = 3 + NC;
-    // F3 steps in place, as the gated solve does (round 4): the step's start and the problem's two deltas wait in LDS, 128 VGPRs,
+    // F3 steps in place, as the gated solve does: the step's start and the problem's two deltas wait in LDS, 128 VGPRs,
     // four waves per SIMD; F4 keeps newton_step_to with the wave-parallel line search at three
     constexpr bool kInPlace = kStepInPlace<VARIANT, false, 0, NoDiag>;
     static_assert(kInPlace || !REGBK, "the register column belongs to the in-place step");
-    __shared__ T s_backup[(kInPlace && !REGBK) ? (3 + NC + 2) * 64 : 1];
+    __shared__ T s_backup[(kInPlace && !REGBK) ? kChunkColumn<NC> : 1];
     // lanes: problems per wave -- 64 in every shipped launch; tuning builds can leave the upper lanes of every wave empty
     // (RP_LANES_PER_WAVE: part-filled waves for batches that cannot fill the chip, measured and not kept: profiles/r5_tuning.md)
     const size_t i = (size_t)blockIdx.x * lanes + threadIdx.x;
@@ -610,29 +643,25 @@ k_steps_chunks(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T> 
     int it = 0, steps_here = 0;
     uint32_t st = 0u;
     bool still_open = false;
+    NoDiag none;
     if constexpr (kInPlace && REGBK) {
-        NoDiag none;
         Prob<T, ZV> pq;
         if constexpr (!ZV) { pq.v0 = pr.v0; pq.v2 = pr.v2; }
         pq.dx0 = pr.dx0;
         pq.dx1 = pr.dx1;
-        run_lane<T, VARIANT, false, false, Prob<T, ZV>, S, false, 0, NoDiag, false, RegColumn<T, 3 + NC>>(pq, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open, none);
+        const RegColumn<T, 3 + NC> start{};
+        run_lane<T, VARIANT, S, Steps>(pq, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open, none, start);
     } else if constexpr (kInPlace) {
         LdsBackup<T> col = (LdsBackup<T>)&s_backup[threadIdx.x];
-        col[(3 + NC) * 64] = pr.dx0;
-        col[(3 + NC + 1) * 64] = pr.dx1;
-        ProbLds<T, ZV> pl;
-        if constexpr (!ZV) { pl.v0 = pr.v0; pl.v2 = pr.v2; }
-        pl.dx0.at = col + (3 + NC) * 64;
-        pl.dx1.at = col + (3 + NC + 1) * 64;
-        NoDiag none;
-        run_lane<T, VARIANT, false, false, ProbLds<T, ZV>, S, false, 0, NoDiag, false>(pl, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open, none, LdsColumn<T>{col});
+        const auto pl = park_deltas<NC>(col, pr);
+        const LdsColumn<T> start{col};
+        run_lane<T, VARIANT, S, Steps>(pl, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open, none, start);
     } else {
-    // F4 has the registers for the affine post-convergence loop (and reaches "the trial point is x" within a dozen steps:
-    // its stalled problems), so all its fixed-step kernels use it and agree bit for bit
-    // (newton_step_to<WAVE> broadcasts through LDS without a barrier: single-wave blocks only -- the block size travels into the step as
-    // the template argument WAVE and is asserted THERE, inside the WAVE branch, so that no multi-wave kernel can instantiate it: ADVICE r5)
-    run_lane<T, VARIANT, false, false, Pk, S, kAffine<VARIANT>, 0, VARIANT == 4 ? kChunkBlock : 0, (VARIANT == 4 && sizeof(S) == 4 && sizeof(T) == 8)>(pr, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open);
+        // F4: the wave-parallel line search, and on an fp32 state with fp64 arithmetic the parked fixed points.
+        // (newton_step_to<WAVE> broadcasts through LDS without a barrier: single-wave blocks only -- the block size travels into the step as
+        // the template argument WAVE and is asserted THERE, inside the WAVE branch, so that no multi-wave kernel can instantiate it)
+        static_assert(VARIANT == 4, "F3's fixed-step launches step in place");
+        run_lane_plain<T, VARIANT, S, StepsWave<kChunkBlock, sizeof(S) == 4 && sizeof(T) == 8>>(pr, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open);
     }
     // the store addresses are formed only now: the barrier keeps the compiler from holding eleven of them in registers
     // across the steps (168 VGPRs and 4-10 spilled without it, 152 with it)
@@ -664,8 +693,8 @@ k_newton_stream(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T>
     constexpr int CB = 3 + NC;
     constexpr int NF = CB + 5;
     constexpr bool kInPlace = kStepInPlace<VARIANT, false, MU, NoDiag>;      // F3 in the reference's mu mode: the step's start waits in LDS
-    __shared__ T s_backup[kInPlace ? (3 + NC) * kBlock : 1];
-    [[maybe_unused]] LdsBackup<T> col = (LdsBackup<T>)&s_backup[(threadIdx.x >> 6) * (3 + NC) * 64 + (threadIdx.x & 63)];      // per wave: fields 64 apart
+    __shared__ T s_backup[kInPlace ? kBlockColumns<NC> : 1];
+    const LdsColumn<T> col{wave_column<NC>(s_backup)};
     const size_t step = (size_t)gridDim.x * kBlock;
     size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     LaneState<S, NF> cur, nxt;      // the prefetched state waits in the storage type
@@ -697,7 +726,7 @@ k_newton_stream(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T>
         int it = 0, steps_here = 0;
         uint32_t st = 0;
         bool still_open = false;
-        run_lane<T, VARIANT, false, false, Prob<T, ZV>, S, kAffine<VARIANT>, MU>(pr, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open, LdsColumn<T>{col});
+        run_lane_plain<T, VARIANT, S, StepsMu<MU>>(pr, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open, col);
         S *f = base + i;
         f[0 * stride] = (S)v;
         f[1 * stride] = (S)t0;
@@ -721,8 +750,8 @@ k_newton_counted(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T
     constexpr int NC = CMap<VARIANT>::NC;
     constexpr int CB = 3 + NC;
     constexpr bool kInPlace = kStepInPlace<VARIANT, false, 0, HalvingDiag>;
-    __shared__ T s_backup[kInPlace ? (3 + NC) * kBlock : 1];
-    [[maybe_unused]] LdsBackup<T> col = (LdsBackup<T>)&s_backup[(threadIdx.x >> 6) * (3 + NC) * 64 + (threadIdx.x & 63)];
+    __shared__ T s_backup[kInPlace ? kBlockColumns<NC> : 1];
+    const LdsColumn<T> col{wave_column<NC>(s_backup)};
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     S *f = base + i;
@@ -740,8 +769,7 @@ k_newton_counted(S *__restrict__ base, size_t stride, size_t n, int k, KParams<T
     int it = 0, steps_here = 0;
     uint32_t st = 0u;
     bool still_open = false;
-    run_lane<T, VARIANT, false, false, Prob<T, false>, S, kAffine<VARIANT>, 0, HalvingDiag, false>(pr, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open, diag,
-                                                                                                   LdsColumn<T>{col});
+    run_lane<T, VARIANT, S, Steps>(pr, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open, diag, col);
     f[0 * stride] = (S)v;
     f[1 * stride] = (S)t0;
     f[2 * stride] = (S)t1;
@@ -776,8 +804,8 @@ k_newton_stream16(S *__restrict__ base, size_t stride, int k, KParams<T> kp)
     constexpr int PER = Vec16<S, T>::PER;
     using V = typename Vec16<S, T>::type;
     constexpr bool kInPlace = kStepInPlace<VARIANT, false, 0, NoDiag>;      // F3: the step's start waits in LDS
-    __shared__ T s_backup[kInPlace ? (3 + NC) * kBlock : 1];
-    [[maybe_unused]] LdsBackup<T> col = (LdsBackup<T>)&s_backup[(threadIdx.x >> 6) * (3 + NC) * 64 + (threadIdx.x & 63)];
+    __shared__ T s_backup[kInPlace ? kBlockColumns<NC> : 1];
+    const LdsColumn<T> col{wave_column<NC>(s_backup)};
     const size_t i = ((size_t)blockIdx.x * kBlock + threadIdx.x) * PER;
     V f[NF];
 #pragma unroll
@@ -806,7 +834,7 @@ k_newton_stream16(S *__restrict__ base, size_t stride, int k, KParams<T> kp)
         int it = 0, steps_here = 0;
         uint32_t st = 0;
         bool still_open = false;
-        run_lane<T, VARIANT, false, false, Prob<T, ZV>, S, kAffine<VARIANT>>(pr, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open, LdsColumn<T>{col});
+        run_lane_plain<T, VARIANT, S, Steps>(pr, kp, k, T(0), 0, v, t0, t1, lam, it, st, steps_here, still_open, col);
         f[0][c] = (S)v;
         f[1][c] = (S)t0;
         f[2][c] = (S)t1;
