@@ -55,7 +55,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      rp_batch_solution_vjp_vel, rp_batch_solution_jvp_vel and rp_batch_solution_jacobian_vel (problems with end velocities and the
  *      first derivatives in them; new entries only); rp_trajectory_eval, rp_trajectory_eval_vjp, rp_trajectory_eval_jvp and
  *      rp_batch_trajectory_device (a solved spline at the caller's own times, and the first derivatives of that evaluation; new entries
- *      only) */
+ *      only); rp_trajectory_crossing and rp_batch_crossing_device (the first time a spline reaches a level; new entries only: no
+ *      struct changes size and no existing entry changes meaning, so the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -362,6 +363,32 @@ RP_API int rp_trajectory_eval_jvp(int device, void *stream, size_t n, size_t k, 
  * rp_batch_get_state returns).  d_tau and the outputs: n x k doubles, 16-byte aligned, with rp_trajectory_eval's segment, extrapolation,
  * NaN and NULL rules.  Asynchronous on the batch stream; works on any state. */
 RP_API int rp_batch_trajectory_device(rp_batch *b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc);
+
+/* ---- the first time a spline reaches a level (new: the reference only draws the curve, drawSegment, onedpath_ip.cpp:1065-1088; replaces
+ * a root search in the caller around rp_trajectory_eval, one launch per iteration) ----
+ * d_level holds k levels per problem, n x k doubles row-major; d_time[i, j] becomes the earliest tau in [0, duration0 + duration1] with
+ * pos(tau) = d_level[i, j] -- pos the cubic of rp_trajectory_eval, segment rule included -- and d_vel[i, j] (NULL: not wanted, not written)
+ * the velocity there: rp_trajectory_eval's vel expression at the returned time.  d_time is required.  No extrapolation: a level the spline
+ * does not reach on [0, duration0 + duration1] gives NaN in both outputs.
+ * Piece rule: the roots of a segment's velocity strictly inside (0, h) cut it into at most three monotone pieces; the query takes the first
+ * of the problem's six pieces, in time order, whose end positions hold the level between them.  A level equal to the position at the
+ * start of its piece gives that breakpoint itself (level == pos0: 0.0 exactly); otherwise pos(s) = level is solved inside the piece by
+ * Newton steps kept in a shrinking bracket (bisection where a step leaves it), until the residual is exactly zero or the step or the
+ * bracket is below 2 ulp of the piece's end.  The trip count is bounded by a compile-time constant (64) for every input.
+ * NaN rule: rp_trajectory_eval's -- a duration that is not finite or not > 0 makes every query of its problem NaN; a NaN (or infinite)
+ * level gives NaN for that query only.  A level within rounding of an extremum of pos (a tangential touch) may come out as the touch, as a
+ * later crossing, or as NaN.
+ * Derivatives need no entry of their own: d time = (d level - d pos at fixed time) / vel, so reverse mode is one
+ * rp_trajectory_eval_vjp launch with g_pos = -g / vel at the returned times, forward mode one rp_trajectory_eval_jvp launch.
+ * Argument rules are rp_trajectory_eval's: d_spline[3] and [4] may be NULL (zeros), every n x k array 16-byte aligned, n and k positive,
+ * k < 2^31; RP_ERR_INVALID before any device call otherwise.  Asynchronous on `stream`; never throws.  Pointwise: a query's bits depend on
+ * its problem's eight numbers and its level only. */
+RP_API int rp_trajectory_crossing(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_level,
+                                  double *d_time, double *d_vel);
+/* rp_trajectory_crossing of the batch's current state, PROBLEM order, every variant and dtype (the state read in the batch's storage
+ * type, the search in double: bit for bit rp_trajectory_crossing on what rp_batch_get_state returns; replaces reading the state back
+ * and searching on the host).  Asynchronous on the batch stream; works on any state. */
+RP_API int rp_batch_crossing_device(rp_batch *b, const double *d_level, size_t k, double *d_time, double *d_vel);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

@@ -22,6 +22,8 @@ torch's once_differentiable error).  Without them the code path is the rest-to-r
 trajectory_eval is stateless: one rp_trajectory_eval launch on the current stream, differentiable to first order
 in all eight spline inputs and in tau through one rp_trajectory_eval_vjp (backward) or rp_trajectory_eval_jvp (forward mode) launch.
 min_time_trajectory composes it with min_time_solve, whose derivatives supply the rest of the chain.
+trajectory_crossing (section 14) is its inverse -- the first time the spline is at a level, one rp_trajectory_crossing launch -- with both
+derivative modes composed from the evaluator's launches; min_time_crossing composes it with min_time_solve.
 """
 import ctypes
 import threading
@@ -418,8 +420,9 @@ def min_time_hessian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=Non
 
 # ---- the solved spline at the caller's own times ----
 # (tables of eight tensors are in the C ABI's order: pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)
-def _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0, vel2, who):
-    """The evaluator's arguments in the style of _check_positions; returns tau as (n, k) (a (k,) tau is broadcast)."""
+def _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0, vel2, who, queries="tau"):
+    """The evaluator's arguments in the style of _check_positions; returns tau as (n, k) (a (k,) tau is broadcast).  `queries`: what the
+    per-query argument is called in `who` (trajectory_crossing's is `level`)."""
     _check_positions(pos0, pos1, pos2, who)
     for name, t in (("vel1", vel1), ("duration0", duration0), ("duration1", duration1)):
         _check_is_tensor(name, t, who)
@@ -429,20 +432,21 @@ def _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0, v
         if t.shape != pos0.shape:
             raise ValueError(who + ": %s has shape %s, the positions %s" % (name, tuple(t.shape), tuple(pos0.shape)))
     _check_velocities(pos0, vel0, vel2, who)
-    return _check_tau(pos0, tau, who)
+    return _check_tau(pos0, tau, who, queries)
 
 
-def _check_tau(pos0, tau, who):
-    """tau against the (checked) positions; returns it as (n, k) (a (k,) tau is broadcast)."""
-    _check_is_tensor("tau", tau, who)
+def _check_tau(pos0, tau, who, name="tau"):
+    """tau (or, under another name, the levels of trajectory_crossing) against the (checked) positions; returns it as (n, k) (a (k,) tau
+    is broadcast)."""
+    _check_is_tensor(name, tau, who)
     if tau.device.type != "cuda" or tau.device != pos0.device:
-        raise TypeError(who + ": tau is on %s; it must be on the positions' ROCm device %s" % (tau.device, pos0.device))
-    _check_is_float64("tau", tau, who)
+        raise TypeError(who + ": %s is on %s; it must be on the positions' ROCm device %s" % (name, tau.device, pos0.device))
+    _check_is_float64(name, tau, who)
     n = pos0.shape[0]
     if tau.dim() == 1 and tau.shape[0] > 0:
         return tau.unsqueeze(0).expand(n, tau.shape[0])
     if tau.dim() != 2 or tau.shape[0] != n or tau.shape[1] == 0:
-        raise ValueError(who + ": tau must have shape (%d, k) or (k,) with k >= 1, got %s" % (n, tuple(tau.shape)))
+        raise ValueError(who + ": %s must have shape (%d, k) or (k,) with k >= 1, got %s" % (name, n, tuple(tau.shape)))
     return tau
 
 
@@ -534,6 +538,89 @@ def min_time_trajectory(pos0, pos1, pos2, tau, *, normalized=False, vel0=None, v
         tau = tau * (duration0 + duration1).unsqueeze(1)
     pos, vel, acc = trajectory_eval(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0=vel0, vel2=vel2)
     return pos, vel, acc, vel1, duration0, duration1, iters, status
+
+
+# ---- the inverse: when the spline first reaches a level ----
+class _TrajectoryCrossing(torch.autograd.Function):
+    """(time, vel) of the first crossing of each level: time differentiable to first order in the eight spline inputs (the table's order)
+    and in the level, through the evaluator's derivative launches -- pos(theta, time) = level gives
+    d time = (d level - d pos at fixed time) / vel.  vel is for the backward and is not differentiable."""
+
+    @staticmethod
+    def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, level):
+        spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
+        level = level.contiguous()
+        time, vel = (torch.empty(level.shape, dtype=torch.float64, device=level.device) for _ in range(2))
+        _trajectory_launch(capi.trajectory_crossing, level.device, spline, level, time, vel)
+        return time, vel
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(output[1])
+        ctx.given = [t is not None for t in inputs[:8]]
+        kept = [t for t in inputs[:8] if t is not None] + list(output)      # the level itself is in neither derivative
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _saved(ctx):
+        """(the eight spline tensors, the times with 0 where no crossing exists, vel, where no crossing exists)"""
+        kept = iter(ctx.saved_tensors)
+        spline = [_dense(next(kept)) if given else None for given in ctx.given]
+        time, vel = next(kept), next(kept)
+        missing = torch.isnan(time)
+        return spline, torch.where(missing, torch.zeros_like(time), time), vel, missing
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_time, _g_vel):
+        if g_time is None:
+            return (None,) * 9
+        spline, tau, vel, missing = _TrajectoryCrossing._saved(ctx)
+        w = torch.where(missing, torch.zeros_like(tau), g_time / vel)      # an unreached level: gradient 0
+        bars = [torch.empty(tau.shape[0], dtype=torch.float64, device=tau.device) if need else None for need in ctx.needs_input_grad[:8]]
+        if any(b is not None for b in bars):
+            _trajectory_launch(capi.trajectory_eval_vjp, tau.device, spline, tau, -w, None, None, bars, None)
+        return tuple(bars) + (w if ctx.needs_input_grad[8] else None,)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        spline, tau, vel, missing = _TrajectoryCrossing._saved(ctx)
+        dots = [_dense(t) for t in tangents[:8]]
+        pos_dot = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
+        _trajectory_launch(capi.trajectory_eval_jvp, tau.device, spline, tau, dots, None, pos_dot, None, None)
+        level_dot = tangents[8] if tangents[8] is not None else torch.zeros_like(tau)
+        time_dot = torch.where(missing, torch.full_like(tau, float("nan")), (level_dot - pos_dot) / vel)
+        return time_dot, None
+
+
+def trajectory_crossing(pos0, pos1, pos2, vel1, duration0, duration1, level, *, vel0=None, vel2=None):
+    """The first time in [0, duration0 + duration1] at which the spline of trajectory_eval is at each level -- level (n, k), or (k,) for
+    the same levels in every problem -- counted from the start of segment 0: (n, k), NaN where the spline does not reach the level (no
+    extrapolation).  The inverse of trajectory_eval's pos.
+
+    One rp_trajectory_crossing launch on the current stream (include/rp_batch.h: the first of the spline's six monotone pieces that holds
+    the level, then a bracketed Newton search with a fixed trip bound; a problem with a duration that is not finite or not > 0 is NaN, a
+    NaN level is NaN for itself; a level within rounding of an extremum of pos may give the touch, a later crossing, or NaN).
+    Differentiable to first order in all eight spline inputs and in the level, d time = (d level - d pos) / vel: reverse mode is one
+    rp_trajectory_eval_vjp launch, forward mode one rp_trajectory_eval_jvp launch; a double backward raises
+    torch's once_differentiable error.  An unreached level has gradient 0 (forward mode: NaN, as the time); where the velocity at the
+    crossing is 0 (a touch) there is no derivative and the result is inf or NaN.  Does not synchronise the host."""
+    level = _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, level, vel0, vel2, "trajectory_crossing", "level")
+    return _TrajectoryCrossing.apply(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, level)[0]
+
+
+def min_time_crossing(pos0, pos1, pos2, level, *, vel0=None, vel2=None, gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve, then trajectory_crossing of its solution at level ((n, k) or (k,)): returns (time, vel1, duration0, duration1, iters,
+    status).  Plain composition: time is differentiable in the positions, the end velocities and the level through the solve's
+    derivatives and the crossing's."""
+    _check_positions(pos0, pos1, pos2, "min_time_crossing")
+    level = _check_tau(pos0, level, "min_time_crossing", "level")      # before the solve: a bad level costs none
+    vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2, gap_tol=gap_tol, max_iter=max_iter, params=params,
+                                                                vel0=vel0, vel2=vel2)
+    time = trajectory_crossing(pos0, pos1, pos2, vel1, duration0, duration1, level, vel0=vel0, vel2=vel2)
+    return time, vel1, duration0, duration1, iters, status
 
 
 def clear_pool():

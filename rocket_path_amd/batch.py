@@ -240,6 +240,12 @@ class Batch:
         an output of None / 0 is not wanted.  Asynchronous on the batch stream."""
         capi.check(self._lib.rp_batch_trajectory_device(self._h, ctypes.c_void_p(d_tau) if d_tau else None, int(k), *_addrs(d_pos, d_vel, d_acc)))
 
+    def crossing_device(self, d_level, k, d_time, d_vel=None):
+        """The first time the batch's current state reaches each of k levels per problem, and the velocity there (rp_batch_crossing_device):
+        addresses of (n, k) float64 arrays in device memory, 16-byte aligned, problem order; NaN where a level is not reached; d_vel of
+        None / 0 is not wanted.  Asynchronous on the batch stream."""
+        capi.check(self._lib.rp_batch_crossing_device(self._h, ctypes.c_void_p(d_level) if d_level else None, int(k), *_addrs(d_time, d_vel)))
+
     def sample_range(self, first, count):
         pos = np.empty((count, 66), dtype=np.float64)
         acc = np.empty((count, 4), dtype=np.float64)

@@ -105,6 +105,8 @@ SIGNATURES = {
     "rp_trajectory_eval_jvp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp),
                                               _vp, _vp, _vp, _vp]),
     "rp_batch_trajectory_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "rp_trajectory_crossing": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, _vp]),
+    "rp_batch_crossing_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp]),
     "rp_batch_sample_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
     "rp_batch_constraints_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rp_batch_sync": (ctypes.c_int, [_vp]),
@@ -192,6 +194,12 @@ def trajectory_eval_jvp(device, stream, n, k, spline, d_tau, spline_dot=None, d_
     """rp_trajectory_eval_jvp: `spline_dot` the eight tangent addresses (None entries: zeros), tangents of pos, vel, acc out."""
     _trajectory("rp_trajectory_eval_jvp", device, stream, n, k, spline, d_tau, list(spline_dot) if spline_dot is not None else None,
                 d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot)
+
+
+def trajectory_crossing(device, stream, n, k, spline, d_level, d_time, d_vel=None):
+    """rp_trajectory_crossing: the first time in [0, duration0 + duration1] at which the spline is at each level (n, k), NaN where it never
+    is, and (d_vel given) the velocity there.  Addresses as for trajectory_eval."""
+    _trajectory("rp_trajectory_crossing", device, stream, n, k, spline, d_level, d_time, d_vel)
 
 
 def device_count():

@@ -953,15 +953,15 @@ namespace {
 
 bool misaligned16(const void *p) { return ((uintptr_t)p & 15u) != 0; }
 
-// what the four trajectory entries check before any device call: the sizes, the times, and the 16-byte alignment of everything that
+// what the trajectory and crossing entries check before any device call: the sizes, the times (or levels), and the 16-byte alignment of everything that
 // is read or written per query (null: not given)
-int check_queries(const char *who, size_t n, size_t k, const double *d_tau, const void *const per_query[], int count)
+int check_queries(const char *who, size_t n, size_t k, const double *d_tau, const void *const per_query[], int count, const char *queries = "d_tau")
 {
     if (n == 0 || k == 0) return fail(RP_ERR_INVALID, "%s: n and k must be positive", who);
     if (k >= ((size_t)1 << 31)) return fail(RP_ERR_INVALID, "%s: k must be below 2^31", who);
     if (n > SIZE_MAX / sizeof(double) / k) return fail(RP_ERR_INVALID, "%s: n x k does not fit", who);
-    if (!d_tau) return fail(RP_ERR_INVALID, "%s: d_tau is null", who);
-    if (misaligned16(d_tau)) return fail(RP_ERR_INVALID, "%s: d_tau must be 16-byte aligned (the queries move as 16-byte vectors)", who);
+    if (!d_tau) return fail(RP_ERR_INVALID, "%s: %s is null", who, queries);
+    if (misaligned16(d_tau)) return fail(RP_ERR_INVALID, "%s: %s must be 16-byte aligned (the queries move as 16-byte vectors)", who, queries);
     for (int i = 0; i < count; ++i)
         if (misaligned16(per_query[i])) return fail(RP_ERR_INVALID, "%s: every n x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
     return RP_OK;
@@ -1032,6 +1032,32 @@ int rp_batch_trajectory_device(rp_batch *b, const double *d_tau, size_t k, doubl
     if (!d_pos && !d_vel && !d_acc) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
     RP_NEED_STATE(b);
     RP_HIP(rp::launch_trajectory_batch(b->view, d_tau, k, d_pos, d_vel, d_acc, b->stream));
+    return RP_OK;
+}
+
+// ---- the first time a spline reaches a level (trajectory.hip) ----
+int rp_trajectory_crossing(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_level, double *d_time,
+                           double *d_vel)
+{
+    const void *const per_query[] = {d_time, d_vel};
+    int st = check_spline(__func__, device, d_spline);
+    if (st == RP_OK) st = check_queries(__func__, n, k, d_level, per_query, 2, "d_level");
+    if (st != RP_OK) return st;
+    if (!d_time) return fail(RP_ERR_INVALID, "%s: d_time is null", __func__);
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_crossing(n, k, d_spline, d_level, d_time, d_vel, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_batch_crossing_device(rp_batch *b, const double *d_level, size_t k, double *d_time, double *d_vel)
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    const void *const per_query[] = {d_time, d_vel};
+    const int st = check_queries(__func__, b->view.n, k, d_level, per_query, 2, "d_level");
+    if (st != RP_OK) return st;
+    if (!d_time) return fail(RP_ERR_INVALID, "%s: d_time is null", __func__);
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_crossing_batch(b->view, d_level, k, d_time, d_vel, b->stream));
     return RP_OK;
 }
 

@@ -1,7 +1,9 @@
 // trajectory.hip -- a solved two-segment spline evaluated at the caller's own times, and the first derivatives of that
 // evaluation, gfx950: rp_trajectory_eval, rp_trajectory_eval_vjp, rp_trajectory_eval_jvp and rp_batch_trajectory_device
 // (include/rp_batch.h); and the plot data, the same spline on the reference's fixed grid: rp_batch_sample,
-// rp_batch_sample_device, rp_batch_sample_range (k_sample, k_sample_records, at the end of the kernels).
+// rp_batch_sample_device, rp_batch_sample_range (k_sample, k_sample_records, at the end of the kernels); and the inverse of the
+// evaluation, the first time the spline reaches a level: rp_trajectory_crossing, rp_batch_crossing_device (k_crossing, k_batch_crossing;
+// DESIGN.md section 14).
 //
 // Per problem the spline is (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1) -- this order wherever eight pointers travel
 // together -- and the k query times tau[i, j] (row-major n x k) count from the start of segment 0.  A query with tau < duration0
@@ -362,6 +364,166 @@ k_trajectory_vjp(FromArrays stage, size_t n, size_t k, int P, int G, const doubl
     }
 }
 
+// ---- the inverse question: when does the spline first reach a level (rp_trajectory_crossing, rp_batch_crossing_device) ----
+// In a segment the velocity va + acc0 s + (jrk0 / 2) s^2 has at most two roots strictly inside (0, h): they cut the segment into at most
+// three monotone pieces, padded to exactly three with breakpoints 0 <= c1 <= c2 <= h (a missing smaller root: c1 = 0, a missing larger
+// one: c2 = h; a piece of length zero is harmless).  The block's first P threads leave per problem, next to the evaluator's constants, the
+// four inner breakpoints, duration1 and pos at the seven piece ends (pos1 itself at the knot, as the evaluator gives it at tau =
+// duration0).  A query walks the six pieces in time order, takes the first whose end positions hold its level between them, and solves
+// pos(s) = level inside that bracket by Newton steps kept inside it (bisection where a step leaves the bracket or fails to halve the step
+// before last), in eval_query's arithmetic, until g == 0, the bracket or the step is within 2 ulp of the piece's later end, or a Newton step's
+// own error estimate is; the answer is the point of smallest |g| among those looked at.  The loop's trip bound is a compile-time constant:
+// no input can make it spin.
+constexpr int kCrossTrips = 64;                        // bisection alone reaches 2 ulp of any double bracket in ~53
+constexpr double kCrossTol = 2.0 * 2.220446049250313e-16;      // the stopping width, as a fraction of the piece's later end: 2 ulp
+
+struct CrossLds {
+    EvalLds e;
+    double brk[2][2][kTrajProblems];      // per segment: c1, c2
+    double d1[kTrajProblems];
+    double end[7][kTrajProblems];         // pos at 0, c1, c2 of segment 0, at the knot, at c1, c2, duration1 of segment 1
+};
+
+// the breakpoints of one segment, by the quadratic formula that does not cancel: q = -(b + sgn(b) sqrt(disc)) / 2, roots q / a and c / q
+__device__ __forceinline__ void velocity_breaks(double va, double acc0, double jrk0, double h, double &c1, double &c2)
+{
+    const double a = jrk0 * 0.5, b = acc0, c = va;
+    const double disc = b * b - 4.0 * (a * c);
+    double r0 = quiet_nan(), r1 = quiet_nan();
+    if (disc >= 0.0) {      // a NaN fails
+        const double q = -0.5 * (b + __builtin_copysign(sqrt_<double>(disc), b));
+        if (a != 0.0) r0 = q / a;
+        r1 = c / q;      // q == 0: inf or NaN, not inside
+    }
+    const bool in0 = r0 > 0.0 && r0 < h, in1 = r1 > 0.0 && r1 < h;      // strictly inside: a rest start's root at s = 0 is not
+    c1 = 0.0;
+    c2 = h;
+    if (in0 && in1) {
+        c1 = r0 < r1 ? r0 : r1;
+        c2 = r0 < r1 ? r1 : r0;
+    } else if (in0 || in1) {
+        const double r = in0 ? r0 : r1, other = in0 ? r1 : r0;
+        if (other <= 0.0) c2 = r; else c1 = r;      // the one inside is the larger root | the smaller (or the only) one
+    }
+}
+
+__device__ __forceinline__ double pos_at(const EvalLds &L, int seg, int q, double s)
+{
+    const double x0 = L.c[seg][0][q], va = L.c[seg][1][q], acc0 = L.c[seg][2][q], jrk0 = L.c[seg][3][q];
+    return x0 + (va + (acc0 + jrk0 * (s * (1.0 / 3.0))) * (s * 0.5)) * s;
+}
+
+__device__ __forceinline__ void stage_crossing(CrossLds &L, int q, Knots kn)
+{
+    kn.check();
+    stage_eval(L.e, q, kn);
+    L.d1[q] = kn.t1;
+#pragma unroll
+    for (int seg = 0; seg < 2; ++seg) {
+        const double h = seg ? kn.t1 : kn.t0;
+        double c1, c2;
+        velocity_breaks(L.e.c[seg][1][q], L.e.c[seg][2][q], L.e.c[seg][3][q], h, c1, c2);
+        L.brk[seg][0][q] = c1;
+        L.brk[seg][1][q] = c2;
+        L.end[3 * seg][q] = pos_at(L.e, seg, q, 0.0);      // x0, or NaN with the problem's constants
+        L.end[3 * seg + 1][q] = pos_at(L.e, seg, q, c1);
+        L.end[3 * seg + 2][q] = pos_at(L.e, seg, q, c2);
+        if (seg) L.end[6][q] = pos_at(L.e, 1, q, h);
+    }
+}
+
+__device__ __forceinline__ void crossing_query(const CrossLds &L, int q, double p, double &time, double &vel)
+{
+    // the first piece, in time order, whose end positions hold p between them (a NaN or infinite p, NaN ends: none)
+    int m = -1;
+    double p_lo = 0.0, p_hi = 0.0, later = L.end[6][q];
+#pragma unroll
+    for (int j = 5; j >= 0; --j) {
+        const double sooner = L.end[j][q];
+        if ((sooner <= p && p <= later) || (later <= p && p <= sooner)) { m = j; p_lo = sooner; p_hi = later; }
+        later = sooner;
+    }
+    time = vel = quiet_nan();
+    if (m < 0) return;
+    const int seg = m >= 3, j = m - 3 * seg;
+    double lo = j == 0 ? 0.0 : L.brk[seg][j - 1][q];
+    double hi = j == 2 ? (seg ? L.d1[q] : L.e.d0[q]) : L.brk[seg][j][q];
+    const double x0 = L.e.c[seg][0][q], va = L.e.c[seg][1][q], acc0 = L.e.c[seg][2][q], jrk0 = L.e.c[seg][3][q];
+    const double g_lo = p_lo - p, g_hi = p_hi - p;
+    double s = lo;      // g_lo == 0: the breakpoint itself (p == pos0: tau = 0 exactly)
+    if (g_lo != 0.0) {
+        const bool up = g_lo < 0.0;
+        const double tol = kCrossTol * hi;
+        double width = hi - lo;
+        double best = abs_(g_hi) < abs_(g_lo) ? hi : lo, best_g = min_(abs_(g_lo), abs_(g_hi));      // the smallest |g| seen, and where
+        s = lo + width * (g_lo * rcp_<double>(g_lo - g_hi));      // the secant point of the bracket
+        if (!(s > lo && s < hi)) s = lo + 0.5 * width;
+        double dx_old = width, dx = width;
+        bool last = false;
+        for (int trip = 0; trip < kCrossTrips; ++trip) {
+            const double g = (x0 + (va + (acc0 + jrk0 * (s * (1.0 / 3.0))) * (s * 0.5)) * s) - p;
+            const double v = va + (acc0 + jrk0 * (s * 0.5)) * s;
+            if (abs_(g) < best_g) { best_g = abs_(g); best = s; }
+            if (g == 0.0 || last) break;
+            if ((g < 0.0) == up) lo = s; else hi = s;
+            width = hi - lo;
+            if (!(width > tol)) break;
+            const double step = g * rcp_<double>(v);      // v == 0: infinite, outside
+            double next = s - step;
+            const bool newton = next > lo && next < hi && 2.0 * abs_(step) <= abs_(dx_old);
+            if (!newton) next = lo + 0.5 * width;
+            // a Newton step leaves an error of about |acc / (2 vel)| step^2: once that is below the stopping width, the point it leads to is
+            // the last one looked at (further steps would only follow the rounding of g around)
+            last = newton && abs_(acc0 + jrk0 * s) * (step * step) <= (2.0 * tol) * abs_(v);
+            dx_old = dx;
+            dx = next - s;
+            if (!(abs_(dx) > tol)) break;
+            s = next;
+        }
+        s = best;
+    }
+    time = seg ? L.e.d0[q] + s : s;
+    vel = va + (acc0 + jrk0 * (s * 0.5)) * s;
+}
+
+template <class Stage>
+__device__ __forceinline__ void crossing_trips(const Stage &stage, size_t n, size_t k, int P, const double *__restrict__ level,
+                                               double *__restrict__ time, double *__restrict__ vel)
+{
+    __shared__ CrossLds L;
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        const size_t p_first = trip * (size_t)P;
+        const int here = problems_here(n, p_first, P);
+        if ((int)threadIdx.x < here) stage_crossing(L, threadIdx.x, stage.load(p_first + threadIdx.x));
+        __syncthreads();
+        const size_t e_first = p_first * k;
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double pa, pb, ta, tb, va, vb;
+            load_pair(level, e_first + e, two, pa, pb);
+            crossing_query(L, qa, pa, ta, va);
+            if (two) crossing_query(L, qb, pb, tb, vb); else { tb = ta; vb = va; }
+            store_pair(time, e_first + e, ta, tb, two);
+            if (vel) store_pair(vel, e_first + e, va, vb, two);
+        });
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_crossing(FromArrays stage, size_t n, size_t k, int P, const double *__restrict__ level, double *__restrict__ time, double *__restrict__ vel)
+{
+    crossing_trips(stage, n, k, P, level, time, vel);
+}
+
+template <typename S, int VARIANT, bool ZV>
+__global__ void __launch_bounds__(kTrajBlock)
+k_batch_crossing(FromBatch<S, VARIANT, ZV> stage, size_t n, size_t k, int P, const double *__restrict__ level, double *__restrict__ time,
+                 double *__restrict__ vel)
+{
+    crossing_trips(stage, n, k, P, level, time, vel);
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -508,6 +670,24 @@ hipError_t launch_trajectory_batch(const BatchView &b, const double *d_tau, size
     const int P = problems_per_trip(k, true);
     RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_trajectory<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
                                                            FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_tau, d_pos, d_vel, d_acc));
+    return hipGetLastError();
+}
+
+// the first time each level is reached: the evaluator's launch shape
+hipError_t launch_crossing(size_t n, size_t k, const double *const d_spline[8], const double *d_level, double *d_time, double *d_vel, hipStream_t stream)
+{
+    const int P = problems_per_trip(k, true);
+    hipLaunchKernelGGL(k_crossing, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, d_level,
+                       d_time, d_vel);
+    return hipGetLastError();
+}
+
+hipError_t launch_crossing_batch(const BatchView &b, const double *d_level, size_t k, double *d_time, double *d_vel, hipStream_t stream)
+{
+    if (b.n == 0) return hipSuccess;
+    const int P = problems_per_trip(k, true);
+    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_crossing<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
+                                                           FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_level, d_time, d_vel));
     return hipGetLastError();
 }
 
