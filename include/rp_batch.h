@@ -56,7 +56,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      first derivatives in them; new entries only); rp_trajectory_eval, rp_trajectory_eval_vjp, rp_trajectory_eval_jvp and
  *      rp_batch_trajectory_device (a solved spline at the caller's own times, and the first derivatives of that evaluation; new entries
  *      only); rp_trajectory_crossing and rp_batch_crossing_device (the first time a spline reaches a level; new entries only: no
- *      struct changes size and no existing entry changes meaning, so the revision stays) */
+ *      struct changes size and no existing entry changes meaning, so the revision stays); rp_trajectory_extrema and
+ *      rp_batch_extrema_device (the extreme position and velocity over a window of times; new entries only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -389,6 +390,43 @@ RP_API int rp_trajectory_crossing(int device, void *stream, size_t n, size_t k, 
  * type, the search in double: bit for bit rp_trajectory_crossing on what rp_batch_get_state returns; replaces reading the state back
  * and searching on the host).  Asynchronous on the batch stream; works on any state. */
 RP_API int rp_batch_crossing_device(rp_batch *b, const double *d_level, size_t k, double *d_time, double *d_vel);
+
+/* ---- how far and how fast at most: the extreme position and velocity of a spline over a window of times (new: the reference only draws
+ * the curve, drawSegment, onedpath_ip.cpp:1065-1088; replaces a dense grid of times through rp_trajectory_eval and a reduction over it) ----
+ * Inputs: the spline, the table's order, the cubic, the segment rule (tau < duration0 selects segment 0) and the per-problem NaN rule are
+ * rp_trajectory_eval's.  T = duration0 + duration1, the float64 sum.
+ * Windows: query (i, j) has the window [lo, hi]; d_lo and d_hi are n x k doubles, row-major, 16-byte aligned.  A NULL d_lo counts as
+ * -inf, a NULL d_hi as +inf; +-inf are allowed values.  No extrapolation: the window is clamped, a = lo > 0 ? lo : +0.0 and
+ * b = hi < T ? hi : T (a NaN end stays NaN).  If !(a <= b) -- a NaN end, a window wholly outside [0, T], a problem under the NaN rule --
+ * every output of the query is NaN.
+ * Outputs: two tables of four pointers in the order (pos_min, pos_max, vel_min, vel_max): d_value[f] the extreme value on [a, b],
+ * d_time[f] a time at which it is attained, each n x k.  A NULL entry (or a NULL table) is not wanted and costs no traffic; at least one
+ * of the eight must be given.
+ * Candidates, in time order: a; the interior candidates strictly inside (a, b) -- for position the real roots of each segment's velocity
+ * strictly inside (0, h), for velocity each segment's s = -acc0 / jrk0 strictly inside (0, h) (jrk0 == 0 or anything not finite: none);
+ * a segment-1 candidate's time is duration0 + s --; the knot duration0 if a <= duration0 <= b, for position too: a non-monotone optimum
+ * has vel1 equal to 0 or to rounding, its velocity root then sits on s = 0 or s = h, which is not strictly inside, and without the knot
+ * pos0 = 0, pos1 = 100, pos2 = 0, vel1 = 0 would have the maximum 0; and b.
+ * Value and selection: every candidate's value is rp_trajectory_eval's at the candidate's time, so a returned value is bit for bit what
+ * rp_trajectory_eval gives at the returned time.  The extreme is chosen by strict comparison along the candidates in time order: among
+ * equal values the earliest time wins; a NaN candidate is skipped.
+ * Returned time bits: the candidate's own -- a returns lo's bits (+0.0 when clamped), b returns hi's (T's when clamped), the knot
+ * duration0's, a stationary point s or duration0 + s -- so that a caller can tell the candidates apart by equality.
+ * Derivatives need no entry of their own: at a stationary candidate the value does not move with the time (the
+ * envelope theorem), at the others the time is one of the inputs, so reverse mode is one rp_trajectory_eval_vjp launch at the returned
+ * times with tau_bar routed to lo, hi, the durations or nowhere, forward mode one rp_trajectory_eval_jvp launch.
+ * Not here: acceleration -- linear in each segment, its extremes are the four end accelerations the constraints already bound.
+ * Argument rules are rp_trajectory_crossing's: d_spline[3] and [4] may be NULL (zeros), every given n x k array 16-byte aligned, n and k
+ * positive, k < 2^31; RP_ERR_INVALID before any device call otherwise, also when all eight outputs (or both tables) are NULL.
+ * Asynchronous on `stream`; never throws.  No loop whose trip count depends on data.  Pointwise: a query's bits depend on its problem's
+ * eight numbers and its two window ends only. */
+RP_API int rp_trajectory_extrema(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo,
+                                 const double *d_hi, double *const d_value[4], double *const d_time[4]);
+/* rp_trajectory_extrema of the batch's current state, PROBLEM order, every variant and dtype (the state read in the batch's storage type,
+ * evaluated in double: bit for bit rp_trajectory_extrema on what rp_batch_get_state returns; replaces reading the state back and
+ * scanning a grid on the host).  Asynchronous on the batch stream; works on any state. */
+RP_API int rp_batch_extrema_device(rp_batch *b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4],
+                                   double *const d_time[4]);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

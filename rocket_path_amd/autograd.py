@@ -24,6 +24,9 @@ in all eight spline inputs and in tau through one rp_trajectory_eval_vjp (backwa
 min_time_trajectory composes it with min_time_solve, whose derivatives supply the rest of the chain.
 trajectory_crossing (section 14) is its inverse -- the first time the spline is at a level, one rp_trajectory_crossing launch -- with both
 derivative modes composed from the evaluator's launches; min_time_crossing composes it with min_time_solve.
+trajectory_extrema (section 15) answers how far and how fast at most: the extreme position and velocity over a window of times, one
+rp_trajectory_extrema launch, both derivative modes one launch of the evaluator's at the times the extremes are attained, with the time's
+own derivative routed to the window end or the duration the time is; min_time_extrema composes it with min_time_solve.
 """
 import ctypes
 import threading
@@ -422,7 +425,7 @@ def min_time_hessian(pos0, pos1, pos2, *, gap_tol=1e-8, max_iter=200, params=Non
 # (tables of eight tensors are in the C ABI's order: pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)
 def _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0, vel2, who, queries="tau"):
     """The evaluator's arguments in the style of _check_positions; returns tau as (n, k) (a (k,) tau is broadcast).  `queries`: what the
-    per-query argument is called in `who` (trajectory_crossing's is `level`)."""
+    per-query argument is called in `who` (trajectory_crossing's is `level`; None: there is none to check here)."""
     _check_positions(pos0, pos1, pos2, who)
     for name, t in (("vel1", vel1), ("duration0", duration0), ("duration1", duration1)):
         _check_is_tensor(name, t, who)
@@ -432,7 +435,7 @@ def _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0, v
         if t.shape != pos0.shape:
             raise ValueError(who + ": %s has shape %s, the positions %s" % (name, tuple(t.shape), tuple(pos0.shape)))
     _check_velocities(pos0, vel0, vel2, who)
-    return _check_tau(pos0, tau, who, queries)
+    return _check_tau(pos0, tau, who, queries) if queries is not None else None
 
 
 def _check_tau(pos0, tau, who, name="tau"):
@@ -621,6 +624,151 @@ def min_time_crossing(pos0, pos1, pos2, level, *, vel0=None, vel2=None, gap_tol=
                                                                 vel0=vel0, vel2=vel2)
     time = trajectory_crossing(pos0, pos1, pos2, vel1, duration0, duration1, level, vel0=vel0, vel2=vel2)
     return time, vel1, duration0, duration1, iters, status
+
+
+# ---- how far and how fast at most: the extreme position and velocity over a window ----
+class _TrajectoryExtrema(torch.autograd.Function):
+    """(pos_min, pos_max, vel_min, vel_max, and a time at which each is attained) over the windows [lo, hi] clamped to the spline: the values
+    differentiable to first order in the eight spline inputs (the table's order) and in lo and hi, through the evaluator's derivative
+    launches at the returned times.  Each time is classified by equality -- lo, else hi, else duration0 + duration1, else duration0, else
+    interior -- and the evaluator's derivative in the time goes to that input: to nothing at an interior time, where the value is
+    stationary (the envelope theorem).  The times are not differentiable."""
+
+    @staticmethod
+    def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, lo, hi):
+        spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
+        lo, hi = _dense(lo), _dense(hi)
+        shape = lo.shape if lo is not None else hi.shape if hi is not None else (pos0.shape[0], 1)
+        outs = [torch.empty(shape, dtype=torch.float64, device=pos0.device) for _ in range(8)]
+        n, k = shape
+        with torch.cuda.device(pos0.device):      # as _trajectory_launch
+            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_extrema(pos0.device.index, torch.cuda.current_stream(pos0.device).cuda_stream, n, k, [addr(t) for t in spline],
+                                    addr(lo), addr(hi), [addr(t) for t in outs[:4]], [addr(t) for t in outs[4:]])
+        return tuple(outs)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*output[4:])
+        ctx.given = [t is not None for t in inputs]
+        kept = [t for t in inputs if t is not None] + list(output)
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _saved(ctx):
+        """(the eight spline tensors; the four times side by side, (n, 4 k), 0 where the value is NaN; where it is NaN; the class masks
+        LO, HI, END, KNOT of each time, exclusive and in that priority)"""
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        outs = list(kept)
+        spline, lo, hi = [_dense(t) for t in inputs[:8]], inputs[8], inputs[9]
+        time = torch.cat(outs[4:], dim=1)
+        missing = torch.isnan(torch.cat(outs[:4], dim=1)) | torch.isnan(time)
+        t0 = torch.where(missing, torch.zeros_like(time), time)
+        d0, T = spline[6].unsqueeze(1), (spline[6] + spline[7]).unsqueeze(1)
+        none = torch.zeros_like(missing)
+        is_lo = (t0 == lo.repeat(1, 4)) & ~missing if lo is not None else none
+        is_hi = (t0 == hi.repeat(1, 4)) & ~missing & ~is_lo if hi is not None else none
+        is_end = (t0 == T) & ~missing & ~is_lo & ~is_hi
+        is_knot = (t0 == d0) & ~missing & ~is_lo & ~is_hi & ~is_end
+        return spline, t0, missing, (is_lo, is_hi, is_end, is_knot)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g0, g1, g2, g3, *_g_times):
+        if g0 is None and g1 is None and g2 is None and g3 is None:
+            return (None,) * 10
+        spline, t0, missing, (is_lo, is_hi, is_end, is_knot) = _TrajectoryExtrema._saved(ctx)
+        n, k = t0.shape[0], t0.shape[1] // 4
+        zero = torch.zeros((n, k), dtype=torch.float64, device=t0.device)
+        part = lambda g: g if g is not None else zero      # noqa: E731
+        g_pos = torch.cat([part(g0), part(g1), zero, zero], dim=1)
+        g_vel = torch.cat([zero, zero, part(g2), part(g3)], dim=1)
+        g_pos = torch.where(missing, torch.zeros_like(g_pos), g_pos)      # a NaN value: gradient 0
+        g_vel = torch.where(missing, torch.zeros_like(g_vel), g_vel)
+        need = ctx.needs_input_grad
+        bars = [torch.empty(n, dtype=torch.float64, device=t0.device) if need[f] else None for f in range(8)]
+        want_tau = need[6] or need[7] or need[8] or need[9]
+        tau_bar = torch.empty(t0.shape, dtype=torch.float64, device=t0.device) if want_tau else None
+        _trajectory_launch(capi.trajectory_eval_vjp, t0.device, spline, t0, g_pos, g_vel, None, bars, tau_bar)
+        lo_bar = hi_bar = None
+        if want_tau:
+            routed = lambda mask: torch.where(mask, tau_bar, torch.zeros_like(tau_bar))      # noqa: E731
+            fold = lambda x: x.reshape(n, 4, k).sum(dim=1)      # noqa: E731
+            end = routed(is_end).sum(dim=1)
+            if need[6]:
+                bars[6] = bars[6] + (end + routed(is_knot).sum(dim=1))
+            if need[7]:
+                bars[7] = bars[7] + end
+            if need[8]:
+                lo_bar = fold(routed(is_lo))
+            if need[9]:
+                hi_bar = fold(routed(is_hi))
+        return tuple(bars) + (lo_bar, hi_bar)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        spline, t0, missing, (is_lo, is_hi, is_end, is_knot) = _TrajectoryExtrema._saved(ctx)
+        n, k = t0.shape[0], t0.shape[1] // 4
+        dots = [_dense(t) for t in tangents[:8]]
+        tau_dot = torch.zeros_like(t0)
+        col = lambda t: t.unsqueeze(1).expand(n, 4 * k) if t is not None else None      # noqa: E731
+        d0_dot, d1_dot = col(dots[6]), col(dots[7])
+        if tangents[8] is not None:
+            tau_dot = torch.where(is_lo, tangents[8].repeat(1, 4), tau_dot)
+        if tangents[9] is not None:
+            tau_dot = torch.where(is_hi, tangents[9].repeat(1, 4), tau_dot)
+        if d0_dot is not None:
+            tau_dot = torch.where(is_end | is_knot, d0_dot, tau_dot)
+        if d1_dot is not None:
+            tau_dot = torch.where(is_end, tau_dot + d1_dot, tau_dot)
+        pos_dot, vel_dot = (torch.empty(t0.shape, dtype=torch.float64, device=t0.device) for _ in range(2))
+        _trajectory_launch(capi.trajectory_eval_jvp, t0.device, spline, t0, dots, tau_dot.contiguous(), pos_dot, vel_dot, None)
+        nan = torch.full_like(t0, float("nan"))
+        pos_dot, vel_dot = torch.where(missing, nan, pos_dot), torch.where(missing, nan, vel_dot)
+        return tuple(x.clone() for x in (pos_dot[:, :k], pos_dot[:, k:2 * k], vel_dot[:, 2 * k:3 * k], vel_dot[:, 3 * k:])) + (None,) * 4
+
+
+def _check_window(pos0, lo, hi, who):
+    """lo and hi (None: -inf / +inf) against the (checked) positions, each like tau; both given: the same shape after broadcasting."""
+    lo = _check_tau(pos0, lo, who, "lo") if lo is not None else None
+    hi = _check_tau(pos0, hi, who, "hi") if hi is not None else None
+    if lo is not None and hi is not None and lo.shape != hi.shape:
+        raise ValueError(who + ": lo has shape %s, hi %s" % (tuple(lo.shape), tuple(hi.shape)))
+    return lo, hi
+
+
+def trajectory_extrema(pos0, pos1, pos2, vel1, duration0, duration1, lo=None, hi=None, *, vel0=None, vel2=None):
+    """The extreme position and velocity of the spline of trajectory_eval over the windows of time [lo, hi] -- (n, k), or (k,) for the same
+    windows in every problem; None: -inf / +inf, both None: k = 1, the whole spline -- clamped to [0, duration0 + duration1] (no
+    extrapolation).  Returns (pos_min, pos_max, vel_min, vel_max, t_pos_min, t_pos_max, t_vel_min, t_vel_max), (n, k) each: the values and a
+    time at which each is attained.  NaN where the clamped window is empty (a NaN end, a window wholly outside the spline).
+
+    One rp_trajectory_extrema launch on the current stream (include/rp_batch.h: the candidates are the window's ends, the knot and the
+    stationary points strictly inside; the earliest among equal values wins; a value is bit for bit trajectory_eval's at the returned
+    time).  The values are differentiable to first order in all eight spline inputs and in lo and hi: reverse mode is one
+    rp_trajectory_eval_vjp launch, forward mode one rp_trajectory_eval_jvp launch, at the returned times; a double
+    backward raises torch's once_differentiable error.  At a tie between candidates, and where a window end is clamped, the derivative is
+    that of the branch the forward pass found.  A NaN value has gradient 0 (forward mode: NaN).  The times are not differentiable.  Does
+    not synchronise the host."""
+    who = "trajectory_extrema"
+    _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, None, vel0, vel2, who, None)
+    lo, hi = _check_window(pos0, lo, hi, who)
+    return _TrajectoryExtrema.apply(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, lo, hi)
+
+
+def min_time_extrema(pos0, pos1, pos2, lo=None, hi=None, *, vel0=None, vel2=None, gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve, then trajectory_extrema of its solution over [lo, hi] ((n, k), (k,) or None): returns the eight of
+    trajectory_extrema, then (vel1, duration0, duration1, iters, status).  Plain composition: the values are differentiable in the
+    positions, the end velocities and the window's ends through the solve's derivatives and the extrema's."""
+    _check_positions(pos0, pos1, pos2, "min_time_extrema")
+    lo, hi = _check_window(pos0, lo, hi, "min_time_extrema")      # before the solve: a bad window costs none
+    vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2, gap_tol=gap_tol, max_iter=max_iter, params=params,
+                                                                vel0=vel0, vel2=vel2)
+    out = trajectory_extrema(pos0, pos1, pos2, vel1, duration0, duration1, lo, hi, vel0=vel0, vel2=vel2)
+    return tuple(out) + (vel1, duration0, duration1, iters, status)
 
 
 def clear_pool():

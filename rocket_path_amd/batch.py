@@ -246,6 +246,14 @@ class Batch:
         None / 0 is not wanted.  Asynchronous on the batch stream."""
         capi.check(self._lib.rp_batch_crossing_device(self._h, ctypes.c_void_p(d_level) if d_level else None, int(k), *_addrs(d_time, d_vel)))
 
+    def extrema_device(self, d_lo, d_hi, k, value=None, time=None):
+        """The extreme position and velocity of the batch's current state over k windows [lo, hi] per problem, and a time at which each is
+        attained (rp_batch_extrema_device): addresses of (n, k) float64 arrays in device memory, 16-byte aligned, problem order; d_lo /
+        d_hi of None / 0 are -inf / +inf; `value` and `time` four addresses each in the order (pos_min, pos_max, vel_min, vel_max), None / 0
+        not wanted.  NaN where the clamped window is empty.  Asynchronous on the batch stream."""
+        vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+        capi.check(self._lib.rp_batch_extrema_device(self._h, vp(d_lo), vp(d_hi), int(k), capi.extrema_table(value), capi.extrema_table(time)))
+
     def sample_range(self, first, count):
         pos = np.empty((count, 66), dtype=np.float64)
         acc = np.empty((count, 4), dtype=np.float64)

@@ -107,6 +107,9 @@ SIGNATURES = {
     "rp_batch_trajectory_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "rp_trajectory_crossing": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, _vp]),
     "rp_batch_crossing_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp]),
+    "rp_trajectory_extrema": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp),
+                                             ctypes.POINTER(_vp)]),
+    "rp_batch_extrema_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "rp_batch_sample_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
     "rp_batch_constraints_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rp_batch_sync": (ctypes.c_int, [_vp]),
@@ -200,6 +203,27 @@ def trajectory_crossing(device, stream, n, k, spline, d_level, d_time, d_vel=Non
     """rp_trajectory_crossing: the first time in [0, duration0 + duration1] at which the spline is at each level (n, k), NaN where it never
     is, and (d_vel given) the velocity there.  Addresses as for trajectory_eval."""
     _trajectory("rp_trajectory_crossing", device, stream, n, k, spline, d_level, d_time, d_vel)
+
+
+def extrema_table(addresses):
+    """Four device addresses (ints; None / 0: NULL) as a `double *const [4]` table of the extrema entries, in the order (pos_min, pos_max,
+    vel_min, vel_max); None gives a NULL table."""
+    if addresses is None:
+        return None
+    addresses = list(addresses)
+    if len(addresses) != 4:
+        raise ValueError("an extrema table has four entries, got %d" % len(addresses))
+    return (_vp * 4)(*[a if a else None for a in addresses])
+
+
+def trajectory_extrema(device, stream, n, k, spline, d_lo=None, d_hi=None, value=None, time=None):
+    """rp_trajectory_extrema: the extreme position and velocity of the spline over the windows [lo, hi] (n, k) clamped to
+    [0, duration0 + duration1] (None / 0: -inf, +inf), and a time at which each is attained.  `value` and `time`: four addresses each in
+    the order (pos_min, pos_max, vel_min, vel_max), None / 0 entries (or None for the table) not wanted.  Addresses as for
+    trajectory_eval."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_extrema(int(device), vp(stream), int(n), int(k), pointer_table(spline), vp(d_lo), vp(d_hi),
+                                               extrema_table(value), extrema_table(time)))
 
 
 def device_count():

@@ -158,5 +158,11 @@ hipError_t launch_trajectory_batch(const BatchView &b, const double *d_tau, size
 // stateless and of the batch's current state
 hipError_t launch_crossing(size_t n, size_t k, const double *const d_spline[8], const double *d_level, double *d_time, double *d_vel, hipStream_t stream);
 hipError_t launch_crossing_batch(const BatchView &b, const double *d_level, size_t k, double *d_time, double *d_vel, hipStream_t stream);
+// the extreme position and velocity over the windows [lo, hi] (n x k each; null: -inf / +inf) clamped to [0, duration0 + duration1], and a
+// time at which each is attained: tables of four in the order (pos_min, pos_max, vel_min, vel_max), a null entry not wanted
+hipError_t launch_extrema(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, double *const d_value[4],
+                          double *const d_time[4], hipStream_t stream);
+hipError_t launch_extrema_batch(const BatchView &b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4],
+                                double *const d_time[4], hipStream_t stream);
 
 }  // namespace rp

@@ -953,17 +953,40 @@ namespace {
 
 bool misaligned16(const void *p) { return ((uintptr_t)p & 15u) != 0; }
 
-// what the trajectory and crossing entries check before any device call: the sizes, the times (or levels), and the 16-byte alignment of everything that
-// is read or written per query (null: not given)
-int check_queries(const char *who, size_t n, size_t k, const double *d_tau, const void *const per_query[], int count, const char *queries = "d_tau")
+// what the trajectory, crossing and extrema entries check before any device call: the sizes ...
+int check_sizes(const char *who, size_t n, size_t k)
 {
     if (n == 0 || k == 0) return fail(RP_ERR_INVALID, "%s: n and k must be positive", who);
     if (k >= ((size_t)1 << 31)) return fail(RP_ERR_INVALID, "%s: k must be below 2^31", who);
     if (n > SIZE_MAX / sizeof(double) / k) return fail(RP_ERR_INVALID, "%s: n x k does not fit", who);
+    return RP_OK;
+}
+
+// ... the times (or levels), and the 16-byte alignment of everything that is read or written per query (null: not given)
+int check_queries(const char *who, size_t n, size_t k, const double *d_tau, const void *const per_query[], int count, const char *queries = "d_tau")
+{
+    const int st = check_sizes(who, n, k);
+    if (st != RP_OK) return st;
     if (!d_tau) return fail(RP_ERR_INVALID, "%s: %s is null", who, queries);
     if (misaligned16(d_tau)) return fail(RP_ERR_INVALID, "%s: %s must be 16-byte aligned (the queries move as 16-byte vectors)", who, queries);
     for (int i = 0; i < count; ++i)
         if (misaligned16(per_query[i])) return fail(RP_ERR_INVALID, "%s: every n x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
+    return RP_OK;
+}
+
+// the extrema entries: both window ends may be null (-inf, +inf); the two tables of four outputs must hold at least one
+int check_extrema(const char *who, size_t n, size_t k, const double *d_lo, const double *d_hi, double *const d_value[4], double *const d_time[4])
+{
+    const int st = check_sizes(who, n, k);
+    if (st != RP_OK) return st;
+    bool any = false, odd = misaligned16(d_lo) || misaligned16(d_hi);
+    for (int f = 0; f < 4; ++f) {
+        double *const v = d_value ? d_value[f] : nullptr, *const t = d_time ? d_time[f] : nullptr;
+        any = any || v || t;
+        odd = odd || misaligned16(v) || misaligned16(t);
+    }
+    if (!any) return fail(RP_ERR_INVALID, "%s: no output asked for", who);
+    if (odd) return fail(RP_ERR_INVALID, "%s: every n x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
     return RP_OK;
 }
 
@@ -1058,6 +1081,32 @@ int rp_batch_crossing_device(rp_batch *b, const double *d_level, size_t k, doubl
     if (!d_time) return fail(RP_ERR_INVALID, "%s: d_time is null", __func__);
     RP_NEED_STATE(b);
     RP_HIP(rp::launch_crossing_batch(b->view, d_level, k, d_time, d_vel, b->stream));
+    return RP_OK;
+}
+
+// ---- the extreme position and velocity over a window (trajectory.hip) ----
+namespace {
+double *const kNoExtrema[4] = {nullptr, nullptr, nullptr, nullptr};
+}
+
+int rp_trajectory_extrema(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
+                          double *const d_value[4], double *const d_time[4])
+{
+    int st = check_spline(__func__, device, d_spline);
+    if (st == RP_OK) st = check_extrema(__func__, n, k, d_lo, d_hi, d_value, d_time);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_extrema(n, k, d_spline, d_lo, d_hi, d_value ? d_value : kNoExtrema, d_time ? d_time : kNoExtrema, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_batch_extrema_device(rp_batch *b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4], double *const d_time[4])
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    const int st = check_extrema(__func__, b->view.n, k, d_lo, d_hi, d_value, d_time);
+    if (st != RP_OK) return st;
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_extrema_batch(b->view, d_lo, d_hi, k, d_value ? d_value : kNoExtrema, d_time ? d_time : kNoExtrema, b->stream));
     return RP_OK;
 }
 

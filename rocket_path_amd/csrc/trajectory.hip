@@ -3,7 +3,8 @@
 // (include/rp_batch.h); and the plot data, the same spline on the reference's fixed grid: rp_batch_sample,
 // rp_batch_sample_device, rp_batch_sample_range (k_sample, k_sample_records, at the end of the kernels); and the inverse of the
 // evaluation, the first time the spline reaches a level: rp_trajectory_crossing, rp_batch_crossing_device (k_crossing, k_batch_crossing;
-// DESIGN.md section 14).
+// DESIGN.md section 14); and the extreme position and velocity over a window of times: rp_trajectory_extrema, rp_batch_extrema_device
+// (k_extrema, k_batch_extrema).
 //
 // Per problem the spline is (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1) -- this order wherever eight pointers travel
 // together -- and the k query times tau[i, j] (row-major n x k) count from the start of segment 0.  A query with tau < duration0
@@ -384,17 +385,25 @@ struct CrossLds {
     double end[7][kTrajProblems];         // pos at 0, c1, c2 of segment 0, at the knot, at c1, c2, duration1 of segment 1
 };
 
-// the breakpoints of one segment, by the quadratic formula that does not cancel: q = -(b + sgn(b) sqrt(disc)) / 2, roots q / a and c / q
-__device__ __forceinline__ void velocity_breaks(double va, double acc0, double jrk0, double h, double &c1, double &c2)
+// the roots of one segment's velocity, by the quadratic formula that does not cancel: q = -(b + sgn(b) sqrt(disc)) / 2, roots q / a and
+// c / q (NaN: no such root)
+__device__ __forceinline__ void velocity_roots(double va, double acc0, double jrk0, double &r0, double &r1)
 {
     const double a = jrk0 * 0.5, b = acc0, c = va;
     const double disc = b * b - 4.0 * (a * c);
-    double r0 = quiet_nan(), r1 = quiet_nan();
+    r0 = r1 = quiet_nan();
     if (disc >= 0.0) {      // a NaN fails
         const double q = -0.5 * (b + __builtin_copysign(sqrt_<double>(disc), b));
         if (a != 0.0) r0 = q / a;
         r1 = c / q;      // q == 0: inf or NaN, not inside
     }
+}
+
+// the breakpoints of one segment
+__device__ __forceinline__ void velocity_breaks(double va, double acc0, double jrk0, double h, double &c1, double &c2)
+{
+    double r0, r1;
+    velocity_roots(va, acc0, jrk0, r0, r1);
     const bool in0 = r0 > 0.0 && r0 < h, in1 = r1 > 0.0 && r1 < h;      // strictly inside: a rest start's root at s = 0 is not
     c1 = 0.0;
     c2 = h;
@@ -522,6 +531,163 @@ k_batch_crossing(FromBatch<S, VARIANT, ZV> stage, size_t n, size_t k, int P, con
                  double *__restrict__ vel)
 {
     crossing_trips(stage, n, k, P, level, time, vel);
+}
+
+// ---- how far and how fast at most: the extreme position and velocity over a window (rp_trajectory_extrema, rp_batch_extrema_device;
+// DESIGN.md section 15) ----
+// On a window [a, b] inside [0, T] the extreme of pos is at a, at b, at the knot, or at a root of a segment's velocity strictly inside
+// (0, h); that of vel at a, at b, at the knot, or at a segment's s = -acc0 / jrk0 strictly inside (0, h).  The block's first P threads
+// leave per problem, next to the evaluator's constants, those six stationary times as global times (NaN: none; the smaller root of a
+// segment first), pos or vel there through eval_query at that global time, and T = duration0 + duration1.  A query clamps its window,
+// evaluates a, the knot and b, and walks the candidates in time order keeping the strictly better one: the earliest among equals, a NaN
+// never.  No search and no loop: selects only.  The time that comes back carries its candidate's own bits (lo or +0.0, hi or T,
+// duration0, the staged time) -- the torch layer tells the candidates apart by equality -- and the value is eval_query's at that time.
+struct ExtLds {
+    EvalLds e;
+    double tp[4][kTrajProblems];      // the roots of vel, global: two of segment 0, two of segment 1
+    double pp[4][kTrajProblems];      // pos there
+    double tv[2][kTrajProblems];      // the root of acc, global: segment 0, segment 1
+    double vv[2][kTrajProblems];      // vel there
+    double T[kTrajProblems];
+};
+
+struct Extrema4 { double *p[4]; };      // pos_min, pos_max, vel_min, vel_max
+
+__device__ __forceinline__ void stage_extrema(ExtLds &L, int q, Knots kn)
+{
+    kn.check();
+    stage_eval(L.e, q, kn);
+    L.T[q] = kn.t0 + kn.t1;
+#pragma unroll
+    for (int seg = 0; seg < 2; ++seg) {
+        const double h = seg ? kn.t1 : kn.t0, off = seg ? kn.t0 : 0.0;
+        const double va = L.e.c[seg][1][q], acc0 = L.e.c[seg][2][q], jrk0 = L.e.c[seg][3][q];
+        double r0, r1;
+        velocity_roots(va, acc0, jrk0, r0, r1);
+        if (!(r0 > 0.0 && r0 < h)) r0 = quiet_nan();
+        if (!(r1 > 0.0 && r1 < h)) r1 = quiet_nan();
+        const bool swap = r1 < r0 || r0 != r0;      // time order; a lone root comes first
+        const double first = swap ? r1 : r0, second = swap ? r0 : r1;
+        double s = jrk0 != 0.0 ? -acc0 / jrk0 : quiet_nan();
+        if (!(s > 0.0 && s < h)) s = quiet_nan();      // an infinite or NaN quotient is not inside
+        const double t[3] = {off + first, off + second, off + s};
+        double pos, vel, acc;
+        eval_query(L.e, q, t[0], pos, vel, acc);
+        L.tp[2 * seg][q] = t[0]; L.pp[2 * seg][q] = pos;
+        eval_query(L.e, q, t[1], pos, vel, acc);
+        L.tp[2 * seg + 1][q] = t[1]; L.pp[2 * seg + 1][q] = pos;
+        eval_query(L.e, q, t[2], pos, vel, acc);
+        L.tv[seg][q] = t[2]; L.vv[seg][q] = vel;
+    }
+}
+
+// the running extremes of one quantity: a candidate replaces the minimum (maximum) only where it is strictly smaller (larger), or where
+// nothing has been taken yet; a NaN value never compares
+struct Extreme {
+    double lo_v, lo_t, hi_v, hi_t;
+    __device__ __forceinline__ void take(bool ok, double t, double v)
+    {
+        const bool less = ok && (v < lo_v || (lo_v != lo_v && v == v)), more = ok && (v > hi_v || (hi_v != hi_v && v == v));
+        lo_v = less ? v : lo_v; lo_t = less ? t : lo_t;
+        hi_v = more ? v : hi_v; hi_t = more ? t : hi_t;
+    }
+};
+
+template <bool POS, bool VEL>
+__device__ __forceinline__ void extrema_query(const ExtLds &L, int q, double lo, double hi, Extreme &P, Extreme &V)
+{
+    const double nan = quiet_nan();
+    P = Extreme{nan, nan, nan, nan};
+    V = Extreme{nan, nan, nan, nan};
+    const double T = L.T[q], d0 = L.e.d0[q];
+    const double a = lo > 0.0 ? lo : (lo != lo ? lo : 0.0);      // a NaN end stays one
+    const double b = hi < T ? hi : (hi != hi ? hi : T);
+    const bool ok = a <= b;      // a NaN end, a NaN T, a window outside [0, T]: no candidate at all
+    double pa, va, pk, vk, pb, vb, acc;
+    eval_query(L.e, q, a, pa, va, acc);
+    eval_query(L.e, q, d0, pk, vk, acc);
+    eval_query(L.e, q, b, pb, vb, acc);
+    const bool knot = ok && a <= d0 && d0 <= b;
+    if (POS) {
+        P.take(ok, a, pa);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (c == 2) P.take(knot, d0, pk);
+            const double t = L.tp[c][q];
+            P.take(ok && a < t && t < b, t, L.pp[c][q]);
+        }
+        P.take(ok, b, pb);
+    }
+    if (VEL) {
+        V.take(ok, a, va);
+        const double t0 = L.tv[0][q], t1 = L.tv[1][q];
+        V.take(ok && a < t0 && t0 < b, t0, L.vv[0][q]);
+        V.take(knot, d0, vk);
+        V.take(ok && a < t1 && t1 < b, t1, L.vv[1][q]);
+        V.take(ok, b, vb);
+    }
+}
+
+template <bool POS, bool VEL>
+__device__ __forceinline__ void extrema_stream(const ExtLds &L, int here, size_t k, size_t e_first, const double *__restrict__ lo,
+                                               const double *__restrict__ hi, const Extrema4 &value, const Extrema4 &time)
+{
+    const double inf = __builtin_inf();
+    stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+        double la = -inf, lb = -inf, ha = inf, hb = inf;
+        if (lo) load_pair(lo, e_first + e, two, la, lb);
+        if (hi) load_pair(hi, e_first + e, two, ha, hb);
+        Extreme Pa, Va, Pb, Vb;
+        extrema_query<POS, VEL>(L, qa, la, ha, Pa, Va);
+        extrema_query<POS, VEL>(L, qb, lb, hb, Pb, Vb);
+        if (POS) {
+            if (value.p[0]) store_pair(value.p[0], e_first + e, Pa.lo_v, Pb.lo_v, two);
+            if (value.p[1]) store_pair(value.p[1], e_first + e, Pa.hi_v, Pb.hi_v, two);
+            if (time.p[0]) store_pair(time.p[0], e_first + e, Pa.lo_t, Pb.lo_t, two);
+            if (time.p[1]) store_pair(time.p[1], e_first + e, Pa.hi_t, Pb.hi_t, two);
+        }
+        if (VEL) {
+            if (value.p[2]) store_pair(value.p[2], e_first + e, Va.lo_v, Vb.lo_v, two);
+            if (value.p[3]) store_pair(value.p[3], e_first + e, Va.hi_v, Vb.hi_v, two);
+            if (time.p[2]) store_pair(time.p[2], e_first + e, Va.lo_t, Vb.lo_t, two);
+            if (time.p[3]) store_pair(time.p[3], e_first + e, Va.hi_t, Vb.hi_t, two);
+        }
+    });
+}
+
+template <class Stage>
+__device__ __forceinline__ void extrema_trips(const Stage &stage, size_t n, size_t k, int P, const double *__restrict__ lo,
+                                              const double *__restrict__ hi, const Extrema4 &value, const Extrema4 &time)
+{
+    __shared__ ExtLds L;
+    const bool pos = value.p[0] || value.p[1] || time.p[0] || time.p[1], vel = value.p[2] || value.p[3] || time.p[2] || time.p[3];      // uniform
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        const size_t p_first = trip * (size_t)P;
+        const int here = problems_here(n, p_first, P);
+        if ((int)threadIdx.x < here) stage_extrema(L, threadIdx.x, stage.load(p_first + threadIdx.x));
+        __syncthreads();
+        const size_t e_first = p_first * k;
+        // the half nobody asked for is not computed (a speed limit wants vel alone)
+        if (pos && vel) extrema_stream<true, true>(L, here, k, e_first, lo, hi, value, time);
+        else if (pos) extrema_stream<true, false>(L, here, k, e_first, lo, hi, value, time);
+        else extrema_stream<false, true>(L, here, k, e_first, lo, hi, value, time);
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_extrema(FromArrays stage, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi, Extrema4 value, Extrema4 time)
+{
+    extrema_trips(stage, n, k, P, lo, hi, value, time);
+}
+
+template <typename S, int VARIANT, bool ZV>
+__global__ void __launch_bounds__(kTrajBlock)
+k_batch_extrema(FromBatch<S, VARIANT, ZV> stage, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
+                Extrema4 value, Extrema4 time)
+{
+    extrema_trips(stage, n, k, P, lo, hi, value, time);
 }
 
 // ---- plot data ----
@@ -688,6 +854,36 @@ hipError_t launch_crossing_batch(const BatchView &b, const double *d_level, size
     const int P = problems_per_trip(k, true);
     RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_crossing<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
                                                            FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_level, d_time, d_vel));
+    return hipGetLastError();
+}
+
+// the extreme position and velocity over each window: the evaluator's launch shape
+namespace {
+Extrema4 extrema_of(double *const t[4])
+{
+    Extrema4 x;
+    for (int f = 0; f < 4; ++f) x.p[f] = t[f];
+    return x;
+}
+}  // namespace
+
+hipError_t launch_extrema(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, double *const d_value[4],
+                          double *const d_time[4], hipStream_t stream)
+{
+    const int P = problems_per_trip(k, true);
+    hipLaunchKernelGGL(k_extrema, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, d_lo, d_hi,
+                       extrema_of(d_value), extrema_of(d_time));
+    return hipGetLastError();
+}
+
+hipError_t launch_extrema_batch(const BatchView &b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4],
+                                double *const d_time[4], hipStream_t stream)
+{
+    if (b.n == 0) return hipSuccess;
+    const int P = problems_per_trip(k, true);
+    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_extrema<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
+                                                           FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_lo, d_hi,
+                                                           extrema_of(d_value), extrema_of(d_time)));
     return hipGetLastError();
 }
 
