@@ -57,7 +57,9 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      rp_batch_trajectory_device (a solved spline at the caller's own times, and the first derivatives of that evaluation; new entries
  *      only); rp_trajectory_crossing and rp_batch_crossing_device (the first time a spline reaches a level; new entries only: no
  *      struct changes size and no existing entry changes meaning, so the revision stays); rp_trajectory_extrema and
- *      rp_batch_extrema_device (the extreme position and velocity over a window of times; new entries only, the revision stays) */
+ *      rp_batch_extrema_device (the extreme position and velocity over a window of times; new entries only, the revision stays);
+ *      rp_trajectory_integrals, rp_trajectory_integrals_vjp, rp_trajectory_integrals_jvp and rp_batch_integrals_device (integrals over a
+ *      window of times and their first derivatives; new entries only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -427,6 +429,50 @@ RP_API int rp_trajectory_extrema(int device, void *stream, size_t n, size_t k, c
  * scanning a grid on the host).  Asynchronous on the batch stream; works on any state. */
 RP_API int rp_batch_extrema_device(rp_batch *b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4],
                                    double *const d_time[4]);
+
+/* How much: the integrals of the spline of rp_trajectory_eval over windows of time (replaces a dense grid through
+ * rp_trajectory_eval summed on the host or in torch -- k times the traffic, an answer as good as the grid, and a wrong gradient of |vel| near
+ * its sign changes -- and Gauss points placed by hand).  The spline, the order of the eight-pointer table, the cubic, the segment constants
+ * and the per-problem NaN rule are rp_trajectory_eval's; the windows are rp_trajectory_extrema's: d_lo and d_hi n x k, a NULL d_lo counts as
+ * -inf and a NULL d_hi as +inf, infinite values allowed; a = lo > 0 ? lo : +0.0, b = hi < T ? hi : T with T = duration0 + duration1 the
+ * double sum, a NaN end stays NaN; unless a <= b every output of the query is NaN; if a == b every output is exactly +0.0.
+ * Outputs: one table of four pointers in the order (pos_int, distance, vel_sq, acc_sq), each n x k: the integrals over [a, b] of pos, of
+ * |vel| (the distance actually travelled: the sum of |pos increment| over the monotone pieces the roots of the velocity strictly inside a
+ * segment cut it into, clipped to the window), of vel^2 and of acc^2.  A NULL entry is not wanted and costs no traffic (and the distance,
+ * the expensive one, no work); at least one must be given.  Each output is the sum of the two segments' contributions, segment 0's
+ * (if a < duration0, over [a, min(b, duration0)]) first, then segment 1's (if b > duration0): acc jumps at the knot and the window is
+ * split there.
+ * Arithmetic: each contribution is a polynomial in the piece's length, taken from the global ends, with coefficients from pos, vel, acc at
+ * the piece's start; no antiderivative is differenced, so a window of 1e-9 T late in a segment keeps its digits.
+ * Argument rules are rp_trajectory_extrema's: d_spline[3] and [4] may be NULL (zeros), every given n x k array 16-byte aligned, n and k
+ * positive, k < 2^31; RP_ERR_INVALID before any device call otherwise, also when all four outputs (or the table) are NULL.
+ * Asynchronous on `stream`; never throws.  No loop whose trip count depends on data.  Pointwise: a query's bits depend on its problem's
+ * eight numbers and its two window ends only. */
+RP_API int rp_trajectory_integrals(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo,
+                                   const double *d_hi, double *const d_value[4]);
+/* Reverse mode of rp_trajectory_integrals (replaces differentiating the grid sum or the hand-placed Gauss points through a dozen elementwise
+ * launches whose `where` chains give NaN gradients on the branches not taken): for upstream gradients d_g[4] on the four outputs (n x k each;
+ * a NULL entry or table: zeros, the same bits as explicit zeros; a query whose outputs are NaN counts as zeros), the gradients in the eight
+ * spline inputs d_spline_bar[8] (n each, the table's order) and in the window's ends d_lo_bar, d_hi_bar (n x k).  A NULL output is not wanted
+ * and not written; at least one must be given.  The derivative is that of the branch the forward took: an end's term goes to lo_bar where
+ * a = lo, nowhere where a is the clamp +0.0, to hi_bar where b = hi, to the durations where b = T, to duration0_bar where a segment ends or
+ * starts on the knot's side of a window that crosses it (DESIGN.md section 16 has the table and the kinks at ties).
+ * A problem's gradient is the same bits alone and in a batch of any size, and from run to run: rp_trajectory_eval_vjp's order of additions
+ * (a function of k alone), no atomics.  Argument rules as above. */
+RP_API int rp_trajectory_integrals_vjp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo,
+                                       const double *d_hi, const double *const d_g[4], double *const d_spline_bar[8], double *d_lo_bar,
+                                       double *d_hi_bar);
+/* Forward mode of rp_trajectory_integrals (replaces the same torch compositions under forward_ad): tangents on the eight spline inputs
+ * d_spline_dot[8] (n each) and on the window's ends d_lo_dot, d_hi_dot (n x k) in -- any of them NULL: zeros, the same bits as explicit zeros
+ * --, the tangents of the wanted outputs d_value_dot[4] out (NaN where the output is).  Pointwise; the same routing of the ends as the
+ * reverse mode.  Argument rules as above. */
+RP_API int rp_trajectory_integrals_jvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo,
+                                       const double *d_hi, const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot,
+                                       double *const d_value_dot[4]);
+/* rp_trajectory_integrals of the batch's current state, PROBLEM order, every variant and dtype (the state read in the batch's storage type,
+ * evaluated in double: bit for bit rp_trajectory_integrals on what rp_batch_get_state returns; replaces reading the state back and summing
+ * a grid on the host).  Asynchronous on the batch stream; works on any state. */
+RP_API int rp_batch_integrals_device(rp_batch *b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4]);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

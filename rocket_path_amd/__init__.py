@@ -13,7 +13,8 @@ from .capi import (DTYPE_F32, DTYPE_F32_STATE, DTYPE_F64, ST_CONVERGED, ST_INFEA
 def __getattr__(name):
     # the torch layer (autograd.py) is imported on first use: everything else here works without importing torch
     if name in ("min_time_solve", "min_time_jacobian", "min_time_hessian", "trajectory_eval", "min_time_trajectory",
-                "trajectory_crossing", "min_time_crossing", "trajectory_extrema", "min_time_extrema"):
+                "trajectory_crossing", "min_time_crossing", "trajectory_extrema", "min_time_extrema", "trajectory_integrals",
+                "min_time_integrals"):
         from . import autograd
         return getattr(autograd, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

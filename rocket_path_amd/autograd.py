@@ -27,6 +27,9 @@ derivative modes composed from the evaluator's launches; min_time_crossing compo
 trajectory_extrema (section 15) answers how far and how fast at most: the extreme position and velocity over a window of times, one
 rp_trajectory_extrema launch, both derivative modes one launch of the evaluator's at the times the extremes are attained, with the time's
 own derivative routed to the window end or the duration the time is; min_time_extrema composes it with min_time_solve.
+trajectory_integrals (section 16) answers how much: the integrals of pos, |vel|, vel^2 and acc^2 over a window of times, one
+rp_trajectory_integrals launch, reverse mode one rp_trajectory_integrals_vjp launch, forward mode one rp_trajectory_integrals_jvp launch;
+min_time_integrals composes it with min_time_solve.
 """
 import ctypes
 import threading
@@ -768,6 +771,95 @@ def min_time_extrema(pos0, pos1, pos2, lo=None, hi=None, *, vel0=None, vel2=None
     vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2, gap_tol=gap_tol, max_iter=max_iter, params=params,
                                                                 vel0=vel0, vel2=vel2)
     out = trajectory_extrema(pos0, pos1, pos2, vel1, duration0, duration1, lo, hi, vel0=vel0, vel2=vel2)
+    return tuple(out) + (vel1, duration0, duration1, iters, status)
+
+
+# ---- how much: integrals over a window ----
+class _TrajectoryIntegrals(torch.autograd.Function):
+    """(pos_int, distance, vel_sq, acc_sq) over the windows [lo, hi] clamped to the spline: differentiable to first order in the eight spline
+    inputs (the table's order) and in lo and hi, each mode one launch of its own entry."""
+
+    @staticmethod
+    def _launch(entry, pos0, spline, lo, hi, shape, *rest):
+        """One rp_trajectory_integrals* launch on the current stream; rest: tensors, None or lists of them (tables)."""
+        addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+        n, k = shape
+        with torch.cuda.device(pos0.device):      # as _trajectory_launch
+            entry(pos0.device.index, torch.cuda.current_stream(pos0.device).cuda_stream, n, k, [addr(t) for t in spline], addr(lo), addr(hi),
+                  *[[addr(t) for t in a] if isinstance(a, (list, tuple)) else addr(a) for a in rest])
+
+    @staticmethod
+    def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, lo, hi):
+        spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
+        lo, hi = _dense(lo), _dense(hi)
+        shape = lo.shape if lo is not None else hi.shape if hi is not None else (pos0.shape[0], 1)
+        outs = [torch.empty(shape, dtype=torch.float64, device=pos0.device) for _ in range(4)]
+        _TrajectoryIntegrals._launch(capi.trajectory_integrals, pos0, spline, lo, hi, shape, outs)
+        return tuple(outs)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None and goes to the kernel as NULL: not read
+        ctx.given = [t is not None for t in inputs]
+        ctx.shape = tuple(output[0].shape)
+        kept = [t for t in inputs if t is not None]
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _inputs(ctx):
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        return [_dense(t) for t in inputs[:8]], _dense(inputs[8]), _dense(inputs[9])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *g):
+        if all(x is None for x in g):
+            return (None,) * 10
+        spline, lo, hi = _TrajectoryIntegrals._inputs(ctx)
+        need, (n, k), dev = ctx.needs_input_grad, ctx.shape, spline[0].device
+        bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(8)]
+        lo_bar, hi_bar = (torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (8, 9))
+        _TrajectoryIntegrals._launch(capi.trajectory_integrals_vjp, spline[0], spline, lo, hi, (n, k), [_dense(x) for x in g], bars, lo_bar, hi_bar)
+        return tuple(bars) + (lo_bar, hi_bar)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        spline, lo, hi = _TrajectoryIntegrals._inputs(ctx)
+        dots = [_dense(t) for t in tangents]
+        outs = [torch.empty(ctx.shape, dtype=torch.float64, device=spline[0].device) for _ in range(4)]
+        _TrajectoryIntegrals._launch(capi.trajectory_integrals_jvp, spline[0], spline, lo, hi, ctx.shape, dots[:8], dots[8], dots[9], outs)
+        return tuple(outs)
+
+
+def trajectory_integrals(pos0, pos1, pos2, vel1, duration0, duration1, lo=None, hi=None, *, vel0=None, vel2=None):
+    """The integrals of the spline of trajectory_eval over the windows of time [lo, hi] -- (n, k), or (k,) for the same windows in every
+    problem; None: -inf / +inf, both None: k = 1, the whole spline -- clamped to [0, duration0 + duration1] (no extrapolation).  Returns
+    (pos_int, distance, vel_sq, acc_sq), (n, k) each: the integrals of pos, |vel| (the distance actually travelled), vel^2 and acc^2.  NaN
+    where the clamped window is empty (a NaN end, a window wholly outside the spline); exactly 0 where its ends coincide.
+
+    One rp_trajectory_integrals launch on the current stream (include/rp_batch.h: closed forms in the segment constants, the window split
+    at the knot and, for the distance, at the roots of the velocity).  Differentiable to first order in all eight spline inputs and in lo
+    and hi: reverse mode is one rp_trajectory_integrals_vjp launch that forms only the gradients autograd asks for, forward mode
+    (torch.autograd.forward_ad, torch.func.jvp) one rp_trajectory_integrals_jvp launch; a double backward raises
+    torch's once_differentiable error.  Where a window end is clamped, and at ties (an end on the knot), the derivative is that of the
+    branch the forward pass took.  A NaN output has gradient 0 (forward mode: NaN).  Does not synchronise the host."""
+    who = "trajectory_integrals"
+    _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, None, vel0, vel2, who, None)
+    lo, hi = _check_window(pos0, lo, hi, who)
+    return _TrajectoryIntegrals.apply(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, lo, hi)
+
+
+def min_time_integrals(pos0, pos1, pos2, lo=None, hi=None, *, vel0=None, vel2=None, gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve, then trajectory_integrals of its solution over [lo, hi] ((n, k), (k,) or None): returns the four of
+    trajectory_integrals, then (vel1, duration0, duration1, iters, status).  Plain composition: the integrals are differentiable in the
+    positions, the end velocities and the window's ends through the solve's derivatives and the integrals'."""
+    _check_positions(pos0, pos1, pos2, "min_time_integrals")
+    lo, hi = _check_window(pos0, lo, hi, "min_time_integrals")      # before the solve: a bad window costs none
+    vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2, gap_tol=gap_tol, max_iter=max_iter, params=params,
+                                                                vel0=vel0, vel2=vel2)
+    out = trajectory_integrals(pos0, pos1, pos2, vel1, duration0, duration1, lo, hi, vel0=vel0, vel2=vel2)
     return tuple(out) + (vel1, duration0, duration1, iters, status)
 
 

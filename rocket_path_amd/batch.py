@@ -254,6 +254,14 @@ class Batch:
         vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
         capi.check(self._lib.rp_batch_extrema_device(self._h, vp(d_lo), vp(d_hi), int(k), capi.extrema_table(value), capi.extrema_table(time)))
 
+    def integrals_device(self, d_lo, d_hi, k, value):
+        """The integrals of pos, |vel|, vel^2 and acc^2 of the batch's current state over k windows [lo, hi] per problem
+        (rp_batch_integrals_device): addresses of (n, k) float64 arrays in device memory, 16-byte aligned, problem order; d_lo / d_hi of
+        None / 0 are -inf / +inf; `value` four addresses in the order (pos_int, distance, vel_sq, acc_sq), None / 0 not wanted.  NaN where
+        the clamped window is empty.  Asynchronous on the batch stream."""
+        vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+        capi.check(self._lib.rp_batch_integrals_device(self._h, vp(d_lo), vp(d_hi), int(k), capi.integrals_table(value)))
+
     def sample_range(self, first, count):
         pos = np.empty((count, 66), dtype=np.float64)
         acc = np.empty((count, 4), dtype=np.float64)

@@ -110,6 +110,12 @@ SIGNATURES = {
     "rp_trajectory_extrema": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp),
                                              ctypes.POINTER(_vp)]),
     "rp_batch_extrema_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rp_trajectory_integrals": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp)]),
+    "rp_trajectory_integrals_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp,
+                                                   ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp]),
+    "rp_trajectory_integrals_jvp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp,
+                                                   ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp)]),
+    "rp_batch_integrals_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "rp_batch_sample_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
     "rp_batch_constraints_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rp_batch_sync": (ctypes.c_int, [_vp]),
@@ -224,6 +230,42 @@ def trajectory_extrema(device, stream, n, k, spline, d_lo=None, d_hi=None, value
     vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
     check(load_library().rp_trajectory_extrema(int(device), vp(stream), int(n), int(k), pointer_table(spline), vp(d_lo), vp(d_hi),
                                                extrema_table(value), extrema_table(time)))
+
+
+def integrals_table(addresses):
+    """Four device addresses (ints; None / 0: NULL) as a `double *const [4]` table of the integrals entries, in the order (pos_int,
+    distance, vel_sq, acc_sq); None gives a NULL table."""
+    if addresses is None:
+        return None
+    addresses = list(addresses)
+    if len(addresses) != 4:
+        raise ValueError("an integrals table has four entries, got %d" % len(addresses))
+    return (_vp * 4)(*[a if a else None for a in addresses])
+
+
+def trajectory_integrals(device, stream, n, k, spline, d_lo=None, d_hi=None, value=None):
+    """rp_trajectory_integrals: the integrals of pos, |vel|, vel^2 and acc^2 over the windows [lo, hi] (n, k) clamped to
+    [0, duration0 + duration1] (None / 0: -inf, +inf).  `value`: four addresses in the order (pos_int, distance, vel_sq, acc_sq), None / 0
+    entries not wanted.  Addresses as for trajectory_eval."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_integrals(int(device), vp(stream), int(n), int(k), pointer_table(spline), vp(d_lo), vp(d_hi),
+                                                 integrals_table(value)))
+
+
+def trajectory_integrals_vjp(device, stream, n, k, spline, d_lo=None, d_hi=None, g=None, spline_bar=None, d_lo_bar=None, d_hi_bar=None):
+    """rp_trajectory_integrals_vjp: `g` the four upstream gradients (None entries, or None: zeros), `spline_bar` the eight output addresses
+    and d_lo_bar, d_hi_bar (n, k) (None: not wanted)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_integrals_vjp(int(device), vp(stream), int(n), int(k), pointer_table(spline), vp(d_lo), vp(d_hi),
+                                                     integrals_table(g), pointer_table(spline_bar), vp(d_lo_bar), vp(d_hi_bar)))
+
+
+def trajectory_integrals_jvp(device, stream, n, k, spline, d_lo=None, d_hi=None, spline_dot=None, d_lo_dot=None, d_hi_dot=None, value_dot=None):
+    """rp_trajectory_integrals_jvp: `spline_dot` the eight tangent addresses and d_lo_dot, d_hi_dot (None: zeros), `value_dot` the four
+    output addresses (None entries: not wanted)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_integrals_jvp(int(device), vp(stream), int(n), int(k), pointer_table(spline), vp(d_lo), vp(d_hi),
+                                                     pointer_table(spline_dot), vp(d_lo_dot), vp(d_hi_dot), integrals_table(value_dot)))
 
 
 def device_count():

@@ -164,5 +164,14 @@ hipError_t launch_extrema(size_t n, size_t k, const double *const d_spline[8], c
                           double *const d_time[4], hipStream_t stream);
 hipError_t launch_extrema_batch(const BatchView &b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4],
                                 double *const d_time[4], hipStream_t stream);
+// the integrals of pos, |vel|, vel^2 and acc^2 over each window (d_value: pos_int, distance, vel_sq, acc_sq), and their first derivatives
+hipError_t launch_integrals(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, double *const d_value[4],
+                            hipStream_t stream);
+hipError_t launch_integrals_batch(const BatchView &b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4], hipStream_t stream);
+hipError_t launch_integrals_vjp(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, const double *const d_g[4],
+                                double *const d_spline_bar[8], double *d_lo_bar, double *d_hi_bar, hipStream_t stream);
+hipError_t launch_integrals_jvp(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
+                                const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot, double *const d_value_dot[4],
+                                hipStream_t stream);
 
 }  // namespace rp

@@ -1110,6 +1110,81 @@ int rp_batch_extrema_device(rp_batch *b, const double *d_lo, const double *d_hi,
     return RP_OK;
 }
 
+// ---- the integrals over a window and their first derivatives (trajectory.hip) ----
+namespace {
+const double *const kNoSpline[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+double *const kNoSplineBar[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+const double *const kNoGradient[4] = {nullptr, nullptr, nullptr, nullptr};
+
+// the integrals entries: sizes, and the 16-byte alignment of every n x k array given (null: not given); `any`: whether an output is
+int check_integrals(const char *who, size_t n, size_t k, const void *const per_query[], int count, bool any)
+{
+    const int st = check_sizes(who, n, k);
+    if (st != RP_OK) return st;
+    if (!any) return fail(RP_ERR_INVALID, "%s: no output asked for", who);
+    for (int i = 0; i < count; ++i)
+        if (misaligned16(per_query[i])) return fail(RP_ERR_INVALID, "%s: every n x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
+    return RP_OK;
+}
+
+int check_integrals_forward(const char *who, size_t n, size_t k, const double *d_lo, const double *d_hi, double *const d_value[4])
+{
+    const void *const per_query[] = {d_lo, d_hi, d_value ? d_value[0] : nullptr, d_value ? d_value[1] : nullptr, d_value ? d_value[2] : nullptr,
+                                     d_value ? d_value[3] : nullptr};
+    return check_integrals(who, n, k, per_query, 6, per_query[2] || per_query[3] || per_query[4] || per_query[5]);
+}
+}  // namespace
+
+int rp_trajectory_integrals(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
+                            double *const d_value[4])
+{
+    int st = check_spline(__func__, device, d_spline);
+    if (st == RP_OK) st = check_integrals_forward(__func__, n, k, d_lo, d_hi, d_value);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_integrals(n, k, d_spline, d_lo, d_hi, d_value, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_trajectory_integrals_vjp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
+                                const double *const d_g[4], double *const d_spline_bar[8], double *d_lo_bar, double *d_hi_bar)
+{
+    const double *const *g = d_g ? d_g : kNoGradient;
+    double *const *bars = d_spline_bar ? d_spline_bar : kNoSplineBar;
+    const void *const per_query[] = {d_lo, d_hi, g[0], g[1], g[2], g[3], d_lo_bar, d_hi_bar};
+    bool any = d_lo_bar || d_hi_bar;
+    for (int f = 0; f < 8; ++f) any = any || bars[f];
+    int st = check_spline(__func__, device, d_spline);
+    if (st == RP_OK) st = check_integrals(__func__, n, k, per_query, 8, any);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_integrals_vjp(n, k, d_spline, d_lo, d_hi, g, bars, d_lo_bar, d_hi_bar, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_trajectory_integrals_jvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
+                                const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot, double *const d_value_dot[4])
+{
+    double *const *out = d_value_dot ? d_value_dot : kNoExtrema;
+    const void *const per_query[] = {d_lo, d_hi, d_lo_dot, d_hi_dot, out[0], out[1], out[2], out[3]};
+    int st = check_spline(__func__, device, d_spline);
+    if (st == RP_OK) st = check_integrals(__func__, n, k, per_query, 8, out[0] || out[1] || out[2] || out[3]);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_integrals_jvp(n, k, d_spline, d_lo, d_hi, d_spline_dot ? d_spline_dot : kNoSpline, d_lo_dot, d_hi_dot, out, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_batch_integrals_device(rp_batch *b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4])
+{
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    const int st = check_integrals_forward(__func__, b->view.n, k, d_lo, d_hi, d_value);
+    if (st != RP_OK) return st;
+    RP_NEED_STATE(b);
+    RP_HIP(rp::launch_integrals_batch(b->view, d_lo, d_hi, k, d_value, b->stream));
+    return RP_OK;
+}
+
 int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4)
 {
     RP_NEED_STATE(b);

@@ -4,7 +4,9 @@
 // rp_batch_sample_device, rp_batch_sample_range (k_sample, k_sample_records, at the end of the kernels); and the inverse of the
 // evaluation, the first time the spline reaches a level: rp_trajectory_crossing, rp_batch_crossing_device (k_crossing, k_batch_crossing;
 // DESIGN.md section 14); and the extreme position and velocity over a window of times: rp_trajectory_extrema, rp_batch_extrema_device
-// (k_extrema, k_batch_extrema).
+// (k_extrema, k_batch_extrema); and the integrals of pos, |vel|, vel^2 and acc^2 over such a window with their first
+// derivatives: rp_trajectory_integrals, _vjp, _jvp, rp_batch_integrals_device (k_integrals, k_batch_integrals, k_jvp_integrals,
+// k_vjp_integrals).
 //
 // Per problem the spline is (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1) -- this order wherever eight pointers travel
 // together -- and the k query times tau[i, j] (row-major n x k) count from the start of segment 0.  A query with tau < duration0
@@ -183,6 +185,34 @@ __device__ __forceinline__ void segment_tangents(double dx, double va, double vb
     jrk0d = (vbd - vad) * (2.0 * ih2) - (vb - va) * (4.0 * ih3) * hd - acc0d * (2.0 * ih) + acc0 * (2.0 * ih2) * hd;
 }
 
+// one problem's constants and their tangents into LDS
+__device__ __forceinline__ void stage_tangents(JvpLds &L, int q, size_t i, const Spline8 &s, const Spline8 &dot)
+{
+    // one segment at a time (a loop the compiler is told to keep): the sixteen loads of a problem and its tangents, taken at
+    // once, cost the registers of two waves per SIMD.  pos1, vel1 and their tangents are asked for in both passes (same thread,
+    // same address: the second is a cache hit)
+    double t0 = s.p[6][i], t1 = s.p[7][i];
+    check_durations(t0, t1);
+    const double t0d = dot.p[6] ? dot.p[6][i] : 0.0, t1d = dot.p[7] ? dot.p[7][i] : 0.0;
+    L.d0[q] = t0;
+    L.d0_dot[q] = t0d;
+#pragma nounroll
+    for (int seg = 0; seg < 2; ++seg) {
+        const double *pva = seg ? s.p[5] : s.p[3], *pvb = seg ? s.p[4] : s.p[5];      // vel0, vel1 | vel1, vel2
+        const double *pvad = seg ? dot.p[5] : dot.p[3], *pvbd = seg ? dot.p[4] : dot.p[5];
+        const double *px0 = seg ? s.p[1] : s.p[0], *px1 = seg ? s.p[2] : s.p[1];
+        const double *px0d = seg ? dot.p[1] : dot.p[0], *px1d = seg ? dot.p[2] : dot.p[1];
+        const double x0 = px0[i], x1 = px1[i], va = pva ? pva[i] : 0.0, vb = pvb ? pvb[i] : 0.0;
+        const double x0d = px0d ? px0d[i] : 0.0, x1d = px1d ? px1d[i] : 0.0, vad = pvad ? pvad[i] : 0.0, vbd = pvbd ? pvbd[i] : 0.0;
+        const double ih = rcp_<double>(seg ? t1 : t0);
+        double acc0, jrk0, acc0d, jrk0d;
+        segment_constants(x0, x1, va, vb, ih, acc0, jrk0);
+        segment_tangents(x1 - x0, va, vb, acc0, ih, x1d - x0d, vad, vbd, seg ? t1d : t0d, acc0d, jrk0d);
+        L.c[seg][0][q] = x0; L.c[seg][1][q] = va; L.c[seg][2][q] = acc0; L.c[seg][3][q] = jrk0;
+        L.t[seg][0][q] = x0d; L.t[seg][1][q] = vad; L.t[seg][2][q] = acc0d; L.t[seg][3][q] = jrk0d;
+    }
+}
+
 __global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(8)))      // 64 VGPRs: without the hint the allocator stops at 65
 k_trajectory_jvp(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const double *__restrict__ tau, const double *__restrict__ tau_dot,
                  double *__restrict__ pos_dot, double *__restrict__ vel_dot, double *__restrict__ acc_dot)
@@ -192,34 +222,7 @@ k_trajectory_jvp(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const
     for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
         const size_t p_first = trip * (size_t)P;
         const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) {
-            // one segment at a time (a loop the compiler is told to keep): the sixteen loads of a problem and its tangents, taken at
-            // once, cost the registers of two waves per SIMD.  pos1, vel1 and their tangents are asked for in both passes (same thread,
-            // same address: the second is a cache hit)
-            const int q = threadIdx.x;
-            const size_t i = p_first + q;
-            const Spline8 &s = stage.s;
-            double t0 = s.p[6][i], t1 = s.p[7][i];
-            check_durations(t0, t1);
-            const double t0d = dot.p[6] ? dot.p[6][i] : 0.0, t1d = dot.p[7] ? dot.p[7][i] : 0.0;
-            L.d0[q] = t0;
-            L.d0_dot[q] = t0d;
-#pragma nounroll
-            for (int seg = 0; seg < 2; ++seg) {
-                const double *pva = seg ? s.p[5] : s.p[3], *pvb = seg ? s.p[4] : s.p[5];      // vel0, vel1 | vel1, vel2
-                const double *pvad = seg ? dot.p[5] : dot.p[3], *pvbd = seg ? dot.p[4] : dot.p[5];
-                const double *px0 = seg ? s.p[1] : s.p[0], *px1 = seg ? s.p[2] : s.p[1];
-                const double *px0d = seg ? dot.p[1] : dot.p[0], *px1d = seg ? dot.p[2] : dot.p[1];
-                const double x0 = px0[i], x1 = px1[i], va = pva ? pva[i] : 0.0, vb = pvb ? pvb[i] : 0.0;
-                const double x0d = px0d ? px0d[i] : 0.0, x1d = px1d ? px1d[i] : 0.0, vad = pvad ? pvad[i] : 0.0, vbd = pvbd ? pvbd[i] : 0.0;
-                const double ih = rcp_<double>(seg ? t1 : t0);
-                double acc0, jrk0, acc0d, jrk0d;
-                segment_constants(x0, x1, va, vb, ih, acc0, jrk0);
-                segment_tangents(x1 - x0, va, vb, acc0, ih, x1d - x0d, vad, vbd, seg ? t1d : t0d, acc0d, jrk0d);
-                L.c[seg][0][q] = x0; L.c[seg][1][q] = va; L.c[seg][2][q] = acc0; L.c[seg][3][q] = jrk0;
-                L.t[seg][0][q] = x0d; L.t[seg][1][q] = vad; L.t[seg][2][q] = acc0d; L.t[seg][3][q] = jrk0d;
-            }
-        }
+        if ((int)threadIdx.x < here) stage_tangents(L, threadIdx.x, p_first + threadIdx.x, stage.s, dot);
         __syncthreads();
         const size_t e_first = p_first * k;
         auto query = [&](int q, double ta, double td, double &pd, double &vd, double &ad) {
@@ -279,6 +282,19 @@ __device__ __forceinline__ SegmentBar segment_chain(const VjpLds &L, int seg, in
     return b;
 }
 
+// one problem's constants for the reverse rule into LDS
+__device__ __forceinline__ void stage_vjp(VjpLds &L, int q, Knots kn)
+{
+    kn.check();
+    const double ih0 = rcp_<double>(kn.t0), ih1 = rcp_<double>(kn.t1);
+    double acc0, jrk0;
+    segment_constants(kn.p0, kn.p1, kn.v0, kn.v1, ih0, acc0, jrk0);
+    L.c[0][0][q] = kn.v0; L.c[0][1][q] = kn.v1; L.c[0][2][q] = kn.p1 - kn.p0; L.c[0][3][q] = acc0; L.c[0][4][q] = jrk0; L.c[0][5][q] = ih0;
+    segment_constants(kn.p1, kn.p2, kn.v1, kn.v2, ih1, acc0, jrk0);
+    L.c[1][0][q] = kn.v1; L.c[1][1][q] = kn.v2; L.c[1][2][q] = kn.p2 - kn.p1; L.c[1][3][q] = acc0; L.c[1][4][q] = jrk0; L.c[1][5][q] = ih1;
+    L.d0[q] = kn.t0;
+}
+
 __global__ void __launch_bounds__(kTrajBlock)
 k_trajectory_vjp(FromArrays stage, size_t n, size_t k, int P, int G, const double *__restrict__ tau, const double *__restrict__ g_pos,
                  const double *__restrict__ g_vel, const double *__restrict__ g_acc, SplineBar8 bar, double *__restrict__ tau_bar)
@@ -289,18 +305,7 @@ k_trajectory_vjp(FromArrays stage, size_t n, size_t k, int P, int G, const doubl
     for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
         const size_t p_first = trip * (size_t)P;
         const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) {
-            const int q = threadIdx.x;
-            Knots kn = stage.load(p_first + q);
-            kn.check();
-            const double ih0 = rcp_<double>(kn.t0), ih1 = rcp_<double>(kn.t1);
-            double acc0, jrk0;
-            segment_constants(kn.p0, kn.p1, kn.v0, kn.v1, ih0, acc0, jrk0);
-            L.c[0][0][q] = kn.v0; L.c[0][1][q] = kn.v1; L.c[0][2][q] = kn.p1 - kn.p0; L.c[0][3][q] = acc0; L.c[0][4][q] = jrk0; L.c[0][5][q] = ih0;
-            segment_constants(kn.p1, kn.p2, kn.v1, kn.v2, ih1, acc0, jrk0);
-            L.c[1][0][q] = kn.v1; L.c[1][1][q] = kn.v2; L.c[1][2][q] = kn.p2 - kn.p1; L.c[1][3][q] = acc0; L.c[1][4][q] = jrk0; L.c[1][5][q] = ih1;
-            L.d0[q] = kn.t0;
-        }
+        if ((int)threadIdx.x < here) stage_vjp(L, threadIdx.x, stage.load(p_first + threadIdx.x));
         __syncthreads();
         for (int q = group; q < here; q += groups) {
             const size_t row = (p_first + (size_t)q) * k;
@@ -690,6 +695,456 @@ k_batch_extrema(FromBatch<S, VARIANT, ZV> stage, size_t n, size_t k, int P, cons
     extrema_trips(stage, n, k, P, lo, hi, value, time);
 }
 
+// ---- how much: the integrals of pos, |vel|, vel^2 and acc^2 over a window (rp_trajectory_integrals, _vjp, _jvp, rp_batch_integrals_device;
+// DESIGN.md section 16) ----
+// The window is clamped as the extrema's, [a, b] inside [0, T], and split at the knot: segment 0 contributes over the local piece that
+// starts at a and is min(b, duration0) - a long (if a < duration0), segment 1 over the one that starts at max(a, duration0) - duration0 and
+// is b - max(a, duration0) long (if b > duration0).  Every integral is a polynomial in the piece's length w -- taken from the GLOBAL ends, so
+// that it carries the rounding of b - a and not of the segment -- with coefficients from (X, V, A), the evaluator's pos, vel, acc at the
+// piece's local start, and J = jrk0: no antiderivative is differenced, so a short window late in a segment keeps its digits.  The distance
+// walks the segment's three monotone pieces (velocity_breaks) clipped to the window and adds |pos increment| of each, in the same shifted
+// form from each piece's own start; a piece that holds the whole window has the window's own length w.  The block's first P threads leave per
+// problem the evaluator's constants, the four inner breakpoints and T; selects only, no loop whose trip count depends on data.
+// The derivatives: for one segment's contribution I(x0, va, acc0, jrk0; sa, sb), dI/dsb = f(sb), dI/dsa = -f(sa) with f the integrand, and
+// the partials in the four constants are moments of the piece, again in the shifted form (segment_partials).  Reverse mode adds them, weighted
+// by the upstream gradients, to k_trajectory_vjp's four sums per segment, in its order of additions, and the end terms to two more sums for
+// the durations; forward mode contracts them with segment_tangents' tangents.  The end terms go where the end came from: a = lo -> lo;
+// a = +0.0 -> nowhere; b = hi -> hi; b = T -> duration1 (as a local time of segment 1 the end is T - duration0 = duration1); segment 0's end
+// on the knot -> duration0; a segment-1 end that is lo or hi -> also duration0, negated (its local time is the end - duration0).
+struct IntLds {
+    EvalLds e;
+    double brk[2][2][kTrajProblems];      // per segment: c1, c2
+    double T[kTrajProblems];
+};
+
+struct Integrals4 { double *p[4]; };            // pos_int, distance, vel_sq, acc_sq
+struct IntegralsIn4 { const double *p[4]; };
+
+// a segment's constants and inner breakpoints, wherever the kernel keeps them
+struct SegmentConst { double x0, va, acc0, jrk0, c1, c2; };
+
+struct Window {
+    double a, b;
+    bool ok, lo_taken, hi_taken;      // a <= b; a is lo (not the clamp +0.0); b is hi (not the clamp T)
+};
+
+__device__ __forceinline__ Window clamp_window(double lo, double hi, double T)
+{
+    Window w;
+    w.lo_taken = lo > 0.0;
+    w.hi_taken = hi < T;
+    w.a = w.lo_taken ? lo : (lo != lo ? lo : 0.0);      // a NaN end stays one
+    w.b = w.hi_taken ? hi : (hi != hi ? hi : T);
+    w.ok = w.a <= w.b;      // a NaN end, a NaN T, a window outside [0, T]: nothing
+    return w;
+}
+
+// the piece of the window in one segment: its local start and its length (both 0 where the segment does not contribute)
+struct Piece {
+    bool on;
+    double sa, w;
+};
+
+__device__ __forceinline__ Piece segment_piece(int seg, const Window &win, double d0)
+{
+    Piece p;
+    if (seg == 0) {
+        p.on = win.ok && win.a < d0;
+        p.sa = win.a;
+        p.w = (win.b < d0 ? win.b : d0) - win.a;
+    } else {
+        p.on = win.ok && win.b > d0;
+        const double start = win.a > d0 ? win.a : d0;
+        p.sa = start - d0;
+        p.w = win.b - start;
+    }
+    p.sa = p.on ? p.sa : 0.0;
+    p.w = p.on ? p.w : 0.0;
+    return p;
+}
+
+__device__ __forceinline__ void local_state(const SegmentConst &c, double s, double &X, double &V, double &A)
+{
+    X = c.x0 + (c.va + (c.acc0 + c.jrk0 * (s * (1.0 / 3.0))) * (s * 0.5)) * s;
+    V = c.va + (c.acc0 + c.jrk0 * (s * 0.5)) * s;
+    A = c.acc0 + c.jrk0 * s;
+}
+
+// the three monotone pieces [0, c1], [c1, c2], [c2, ...) clipped to [sa, sa + w]: each(u, l, inc) gets the clipped piece's local start,
+// its length (0: not in the window) and the pos increment over it.  The last piece has no end of its own: the window is inside the segment.
+// UNROLLED: the three side by side (the forward), or a loop the compiler is told to keep (the derivatives, for their registers)
+template <bool UNROLLED, class Each> __device__ __forceinline__ void monotone_pieces(const SegmentConst &c, const Piece &p, Each each)
+{
+    const double se = p.sa + p.w;
+    auto piece = [&](int j) {
+        const double pl = j == 0 ? 0.0 : (j == 1 ? c.c1 : c.c2), ph = j == 0 ? c.c1 : c.c2;
+        const bool starts = p.sa >= pl, ends = j == 2 || se <= ph;
+        const double u = starts ? p.sa : pl, e = ends ? se : ph;
+        double l = starts && ends ? p.w : e - u;      // the window's own length where the piece holds all of it
+        l = l > 0.0 ? l : 0.0;
+        const double Vu = c.va + (c.acc0 + c.jrk0 * (u * 0.5)) * u, Au = c.acc0 + c.jrk0 * u;
+        each(u, l, l * (Vu + (l * 0.5) * (Au + (l * (1.0 / 3.0)) * c.jrk0)));
+    };
+    if (UNROLLED) {
+        piece(0);
+        piece(1);
+        piece(2);
+    } else {
+#pragma nounroll
+        for (int j = 0; j < 3; ++j) piece(j);
+    }
+}
+
+// one segment's contributions to the four integrals
+template <bool DIST> __device__ __forceinline__ void segment_values(const SegmentConst &c, const Piece &p, double v[4])
+{
+    const double w = p.w, J = c.jrk0;
+    double X, V, A;
+    local_state(c, p.sa, X, V, A);
+    v[0] = w * (X + (w * 0.5) * (V + (w * (1.0 / 3.0)) * (A + (w * 0.25) * J)));
+    v[2] = w * (V * V + w * (V * A + (w * (1.0 / 3.0)) * ((A * A + V * J) + w * (0.75 * (A * J) + (0.15 * w) * (J * J)))));
+    v[3] = w * (A * A + w * (A * J + (w * (1.0 / 3.0)) * (J * J)));
+    double dist = 0.0 * w;
+    if (DIST) monotone_pieces<true>(c, p, [&](double, double, double inc) { dist += abs_(inc); });
+    v[1] = dist;
+}
+
+__device__ __forceinline__ SegmentConst segment_const(const EvalLds &e, const double (&brk)[2][2][kTrajProblems], int seg, int q)
+{
+    return SegmentConst{e.c[seg][0][q], e.c[seg][1][q], e.c[seg][2][q], e.c[seg][3][q], brk[seg][0][q], brk[seg][1][q]};
+}
+
+__device__ __forceinline__ void stage_integrals(IntLds &L, int q, Knots kn)
+{
+    kn.check();
+    stage_eval(L.e, q, kn);
+    L.T[q] = kn.t0 + kn.t1;
+#pragma unroll
+    for (int seg = 0; seg < 2; ++seg) {
+        double c1, c2;
+        velocity_breaks(L.e.c[seg][1][q], L.e.c[seg][2][q], L.e.c[seg][3][q], seg ? kn.t1 : kn.t0, c1, c2);
+        L.brk[seg][0][q] = c1;
+        L.brk[seg][1][q] = c2;
+    }
+}
+
+template <bool DIST> __device__ __forceinline__ void integrals_query(const IntLds &L, int q, double lo, double hi, double out[4])
+{
+    const double d0 = L.e.d0[q];
+    const Window win = clamp_window(lo, hi, L.T[q]);
+    double v0[4], v1[4];
+    segment_values<DIST>(segment_const(L.e, L.brk, 0, q), segment_piece(0, win, d0), v0);
+    segment_values<DIST>(segment_const(L.e, L.brk, 1, q), segment_piece(1, win, d0), v1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[i] = win.ok ? (win.a == win.b ? 0.0 : v0[i] + v1[i]) : quiet_nan();
+}
+
+template <bool DIST>
+__device__ __forceinline__ void integrals_stream(const IntLds &L, int here, size_t k, size_t e_first, const double *__restrict__ lo,
+                                                 const double *__restrict__ hi, const Integrals4 &value)
+{
+    const double inf = __builtin_inf();
+    stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+        double la = -inf, lb = -inf, ha = inf, hb = inf, a[4], b[4];
+        if (lo) load_pair(lo, e_first + e, two, la, lb);
+        if (hi) load_pair(hi, e_first + e, two, ha, hb);
+        integrals_query<DIST>(L, qa, la, ha, a);
+        integrals_query<DIST>(L, qb, lb, hb, b);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (value.p[i]) store_pair(value.p[i], e_first + e, a[i], b[i], two);      // without DIST value.p[1] is null
+    });
+}
+
+template <class Stage>
+__device__ __forceinline__ void integrals_trips(const Stage &stage, size_t n, size_t k, int P, const double *__restrict__ lo,
+                                                const double *__restrict__ hi, const Integrals4 &value)
+{
+    __shared__ IntLds L;
+    const bool dist = value.p[1] != nullptr;      // uniform
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        const size_t p_first = trip * (size_t)P;
+        const int here = problems_here(n, p_first, P);
+        if ((int)threadIdx.x < here) stage_integrals(L, threadIdx.x, stage.load(p_first + threadIdx.x));
+        __syncthreads();
+        // the walk over the monotone pieces is most of the work: not taken where nobody asked for the distance
+        if (dist) integrals_stream<true>(L, here, k, p_first * k, lo, hi, value);
+        else integrals_stream<false>(L, here, k, p_first * k, lo, hi, value);
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_integrals(FromArrays stage, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi, Integrals4 value)
+{
+    integrals_trips(stage, n, k, P, lo, hi, value);
+}
+
+template <typename S, int VARIANT, bool ZV>
+__global__ void __launch_bounds__(kTrajBlock)
+k_batch_integrals(FromBatch<S, VARIANT, ZV> stage, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
+                  Integrals4 value)
+{
+    integrals_trips(stage, n, k, P, lo, hi, value);
+}
+
+// The partials of one segment's contributions in (x0, va, acc0, jrk0) -- pos_int's four, the distance's, vel_sq's (none in x0) and acc_sq's
+// (none in x0, va) -- and the four integrands at the piece's start and end.  With s = sa + t on the piece and vel = V + A t + J t^2 / 2:
+//     pos_int   (w, M1, M2 / 2, M3 / 6)                              Mm = the integral of s^m
+//     distance  the signed sums over its monotone pieces of (l, the integral of s, of s^2 / 2); a root inside contributes nothing, |vel| is 0 there
+//     vel_sq    (2 Q0, 2 (sa Q0 + Q1), sa^2 Q0 + 2 sa Q1 + Q2)      Qm = the integral of vel t^m
+//     acc_sq    (2 R0, 2 (sa R0 + R1))                               Rm = the integral of acc t^m
+// each(i, m0, m1, m2, m3, fa, fb) gets output i's four partials and its integrand at the two ends, one output at a time and in the outputs'
+// order, so that no more than one output's numbers are live
+template <class Each> __device__ __forceinline__ void segment_partials(const SegmentConst &c, const Piece &p, Each each)
+{
+    const double w = p.w, sa = p.sa, J = c.jrk0, third = 1.0 / 3.0;
+    double X, V, A;
+    local_state(c, sa, X, V, A);
+    const double Vb = V + w * (A + (w * 0.5) * J), Ab = A + w * J;
+    {
+        const double Xb = X + w * (V + (w * 0.5) * (A + (w * third) * J));
+        const double M1 = w * (sa + w * 0.5), M2 = w * (sa * sa + w * (sa + w * third));
+        const double M3 = w * (sa * sa * sa + w * (1.5 * (sa * sa) + w * (sa + w * 0.25)));
+        each(0, w, M1, M2 * 0.5, M3 * (1.0 / 6.0), X, Xb);
+    }
+    {
+        double d1 = 0.0 * w, d2 = d1, d3 = d1;
+        monotone_pieces<false>(c, p, [&](double u, double l, double inc) {
+            const double sign = inc > 0.0 ? 1.0 : (inc < 0.0 ? -1.0 : 0.0);
+            d1 += sign * l;
+            d2 += sign * (l * (u + l * 0.5));
+            d3 += sign * (0.5 * (l * (u * u + l * (u + l * third))));
+        });
+        each(1, 0.0, d1, d2, d3, abs_(V), abs_(Vb));
+    }
+    {
+        const double Q0 = w * (V + (w * 0.5) * (A + (w * third) * J));
+        const double Q1 = (w * w) * (V * 0.5 + w * (A * third + (w * 0.125) * J));
+        const double Q2 = (w * w * w) * (V * third + w * (A * 0.25 + (w * 0.1) * J));
+        each(2, 0.0, 2.0 * Q0, 2.0 * (sa * Q0 + Q1), (sa * sa) * Q0 + (2.0 * sa) * Q1 + Q2, V * V, Vb * Vb);
+    }
+    {
+        const double R0 = w * (A + (w * 0.5) * J), R1 = (w * w) * (A * 0.5 + (w * third) * J);
+        each(3, 0.0, 0.0, 2.0 * R0, 2.0 * (sa * R0 + R1), A * A, Ab * Ab);
+    }
+}
+
+// ---- forward mode: tangents on the eight parameters and on lo and hi in, tangents of the four integrals out ----
+struct IntJvpLds {
+    JvpLds j;
+    double brk[2][2][kTrajProblems];
+    double T[kTrajProblems], d1_dot[kTrajProblems];
+};
+
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(4)))      // 123 VGPRs: without the hint 153
+k_jvp_integrals(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
+                const double *__restrict__ lo_dot, const double *__restrict__ hi_dot, Integrals4 value_dot)
+{
+    __shared__ IntJvpLds L;
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    const double inf = __builtin_inf();
+    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        const size_t p_first = trip * (size_t)P;
+        const int here = problems_here(n, p_first, P);
+        if ((int)threadIdx.x < here) {
+            const int q = threadIdx.x;
+            const size_t i = p_first + q;
+            stage_tangents(L.j, q, i, stage.s, dot);
+            double t0 = stage.s.p[6][i], t1 = stage.s.p[7][i];      // again, for the breakpoints and T: cache hits
+            check_durations(t0, t1);
+            L.T[q] = t0 + t1;
+            L.d1_dot[q] = dot.p[7] ? dot.p[7][i] : 0.0;
+#pragma unroll
+            for (int seg = 0; seg < 2; ++seg) {
+                double c1, c2;
+                velocity_breaks(L.j.c[seg][1][q], L.j.c[seg][2][q], L.j.c[seg][3][q], seg ? t1 : t0, c1, c2);
+                L.brk[seg][0][q] = c1;
+                L.brk[seg][1][q] = c2;
+            }
+        }
+        __syncthreads();
+        const size_t e_first = p_first * k;
+        // one query, one segment at a time (loops the compiler is told to keep: the two queries of a pair and their two segments, taken at
+        // once, cost more than the 128 registers of four waves per SIMD)
+        auto query = [&](int q, double lo_q, double hi_q, double lo_d, double hi_d, double out[4]) {
+            const double d0 = L.j.d0[q], d0d = L.j.d0_dot[q], d1d = L.d1_dot[q];
+            const Window win = clamp_window(lo_q, hi_q, L.T[q]);
+            const double a_dot = win.lo_taken ? lo_d : 0.0;
+            double sum[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma nounroll
+            for (int seg = 0; seg < 2; ++seg) {
+                const SegmentConst c{L.j.c[seg][0][q], L.j.c[seg][1][q], L.j.c[seg][2][q], L.j.c[seg][3][q], L.brk[seg][0][q], L.brk[seg][1][q]};
+                const Piece p = segment_piece(seg, win, d0);
+                // the tangents of the piece's local ends, by where each end came from
+                const double sad = seg ? (p.on && win.a > d0 ? a_dot - d0d : 0.0) : (p.on ? a_dot : 0.0);
+                const double end0 = win.b > d0 ? d0d : (win.hi_taken ? hi_d : d0d + d1d), end1 = win.hi_taken ? hi_d - d0d : d1d;
+                const double sbd = p.on ? (seg ? end1 : end0) : 0.0;
+                const double x0d = L.j.t[seg][0][q], vad = L.j.t[seg][1][q], acc0d = L.j.t[seg][2][q], jrk0d = L.j.t[seg][3][q];
+                segment_partials(c, p, [&](int i, double m0, double m1, double m2, double m3, double fa, double fb) {
+                    // a partial that is 0 by structure is not a term
+                    const double lead = i == 0 ? m0 * x0d + m1 * vad + m2 * acc0d : (i == 3 ? m2 * acc0d : m1 * vad + m2 * acc0d);
+                    sum[i] += lead + m3 * jrk0d + fb * sbd - fa * sad;
+                });
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) out[i] = win.ok ? sum[i] : quiet_nan();
+        };
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double la = -inf, lb = -inf, ha = inf, hb = inf, lda = 0.0, ldb = 0.0, hda = 0.0, hdb = 0.0, a[4], b[4];
+            if (lo) load_pair(lo, e_first + e, two, la, lb);
+            if (hi) load_pair(hi, e_first + e, two, ha, hb);
+            if (lo_dot) load_pair(lo_dot, e_first + e, two, lda, ldb);
+            if (hi_dot) load_pair(hi_dot, e_first + e, two, hda, hdb);
+#pragma nounroll
+            for (int second = 0; second < 2; ++second) {
+                double r[4];
+                query(second ? qb : qa, second ? lb : la, second ? hb : ha, second ? ldb : lda, second ? hdb : hda, r);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { a[i] = second ? a[i] : r[i]; b[i] = r[i]; }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (value_dot.p[i]) store_pair(value_dot.p[i], e_first + e, a[i], b[i], two);
+        });
+        __syncthreads();
+    }
+}
+
+// ---- reverse mode: k_trajectory_vjp's reduction -- the same group of G lanes per problem, the same lane stride, the same butterfly -- over
+// ten sums: the four per segment that segment_chain takes, and what the window's ends put on duration0 and on duration1.  A query whose
+// output is NaN counts with upstream gradients of zero.
+struct IntVjpLds {
+    VjpLds v;
+    double x0[2][kTrajProblems];
+    double brk[2][2][kTrajProblems];
+    double T[kTrajProblems];
+};
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_vjp_integrals(FromArrays stage, size_t n, size_t k, int P, int G, const double *__restrict__ lo, const double *__restrict__ hi, IntegralsIn4 g,
+                SplineBar8 bar, double *__restrict__ lo_bar, double *__restrict__ hi_bar)
+{
+    __shared__ IntVjpLds L;
+    const int groups = kTrajBlock / G, group = (int)threadIdx.x / G, lane = (int)threadIdx.x & (G - 1);
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    const double inf = __builtin_inf();
+    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        const size_t p_first = trip * (size_t)P;
+        const int here = problems_here(n, p_first, P);
+        if ((int)threadIdx.x < here) {
+            const int q = threadIdx.x;
+            Knots kn = stage.load(p_first + q);
+            kn.check();
+            stage_vjp(L.v, q, kn);
+            L.x0[0][q] = kn.p0;
+            L.x0[1][q] = kn.p1;
+            L.T[q] = kn.t0 + kn.t1;
+#pragma unroll
+            for (int seg = 0; seg < 2; ++seg) {
+                double c1, c2;
+                velocity_breaks(L.v.c[seg][0][q], L.v.c[seg][3][q], L.v.c[seg][4][q], seg ? kn.t1 : kn.t0, c1, c2);
+                L.brk[seg][0][q] = c1;
+                L.brk[seg][1][q] = c2;
+            }
+        }
+        __syncthreads();
+        for (int q = group; q < here; q += groups) {
+            const size_t row = (p_first + (size_t)q) * k;
+            const double d0 = L.v.d0[q], T = L.T[q];
+            double S[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, D0 = 0.0, D1 = 0.0;      // this lane's ten sums
+            // one segment at a time (a loop the compiler is told to keep, as the pair's below: registers)
+            auto query = [&](double lo_q, double hi_q, double g0, double g1, double g2, double g3, double &lo_b, double &hi_b) {
+                const Window win = clamp_window(lo_q, hi_q, T);
+                const double g[4] = {win.ok ? g0 : 0.0, win.ok ? g1 : 0.0, win.ok ? g2 : 0.0, win.ok ? g3 : 0.0};
+                double Ea0 = 0.0, Ea1 = 0.0, Eb0 = 0.0, Eb1 = 0.0;
+                bool on0 = false, on1 = false;
+#pragma nounroll
+                for (int seg = 0; seg < 2; ++seg) {
+                    const SegmentConst c{L.x0[seg][q], L.v.c[seg][0][q], L.v.c[seg][3][q], L.v.c[seg][4][q], L.brk[seg][0][q], L.brk[seg][1][q]};
+                    const Piece p = segment_piece(seg, win, d0);
+                    double W[4] = {0.0, 0.0, 0.0, 0.0}, ea = 0.0, eb = 0.0;
+                    segment_partials(c, p, [&](int i, double m0, double m1, double m2, double m3, double fa, double fb) {
+                        // a partial that is 0 by structure is not a term; the first term of a sum starts it
+                        if (i == 0) { W[0] = g[0] * m0; W[1] = g[0] * m1; W[2] = g[0] * m2; W[3] = g[0] * m3; ea = g[0] * fa; eb = g[0] * fb; return; }
+                        if (i < 3) W[1] += g[i] * m1;
+                        W[2] += g[i] * m2;
+                        W[3] += g[i] * m3;
+                        ea += g[i] * fa;
+                        eb += g[i] * fb;
+                    });
+#pragma unroll
+                    for (int f = 0; f < 4; ++f) { S[0][f] += seg ? 0.0 : W[f]; S[1][f] += seg ? W[f] : 0.0; }
+                    Ea0 = seg ? Ea0 : ea; Ea1 = seg ? ea : Ea1;
+                    Eb0 = seg ? Eb0 : eb; Eb1 = seg ? eb : Eb1;
+                    on0 = seg ? on0 : p.on; on1 = seg ? p.on : on1;
+                }
+                const bool knot = on0 && win.b > d0, end0_b = on0 && !knot;      // segment 0 ends on the knot | at b
+                const double a1 = on1 && win.a > d0 && win.lo_taken ? Ea1 : 0.0;
+                D0 += ((knot || (end0_b && !win.hi_taken) ? Eb0 : 0.0) + a1) - (on1 && win.hi_taken ? Eb1 : 0.0);
+                D1 += (on1 && !win.hi_taken ? Eb1 : 0.0) + (end0_b && !win.hi_taken ? Eb0 : 0.0);
+                lo_b = -((on0 && win.lo_taken ? Ea0 : 0.0) + a1);
+                hi_b = (end0_b && win.hi_taken ? Eb0 : 0.0) + (on1 && win.hi_taken ? Eb1 : 0.0);
+            };
+            if ((k & 1) == 0) {      // k even: the row starts on a 16-byte boundary
+                const size_t units = k >> 1;
+                for (size_t u = lane; u < units; u += G) {
+                    const size_t at = row + 2 * u;
+                    double la = -inf, lb = -inf, ha = inf, hb = inf, ga[4] = {0.0, 0.0, 0.0, 0.0}, gb[4] = {0.0, 0.0, 0.0, 0.0}, ba, bb, ca, cb;
+                    if (lo) load_pair(lo, at, true, la, lb);
+                    if (hi) load_pair(hi, at, true, ha, hb);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (g.p[i]) load_pair(g.p[i], at, true, ga[i], gb[i]);
+#pragma nounroll
+                    for (int second = 0; second < 2; ++second) {
+                        double b, c;
+                        query(second ? lb : la, second ? hb : ha, second ? gb[0] : ga[0], second ? gb[1] : ga[1], second ? gb[2] : ga[2],
+                              second ? gb[3] : ga[3], b, c);
+                        ba = second ? ba : b; bb = b;
+                        ca = second ? ca : c; cb = c;
+                    }
+                    if (lo_bar) store_pair(lo_bar, at, ba, bb, true);
+                    if (hi_bar) store_pair(hi_bar, at, ca, cb, true);
+                }
+            } else {
+                for (size_t u = lane; u < k; u += G) {
+                    const size_t at = row + u;
+                    double b, c;
+                    query(lo ? lo[at] : -inf, hi ? hi[at] : inf, g.p[0] ? g.p[0][at] : 0.0, g.p[1] ? g.p[1][at] : 0.0, g.p[2] ? g.p[2][at] : 0.0,
+                          g.p[3] ? g.p[3][at] : 0.0, b, c);
+                    if (lo_bar) lo_bar[at] = b;
+                    if (hi_bar) hi_bar[at] = c;
+                }
+            }
+            // the group's lanes combine: after the butterfly every lane holds the same ten sums
+            for (int m = 1; m < G; m <<= 1) {
+#pragma unroll
+                for (int seg = 0; seg < 2; ++seg)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) S[seg][c] += __shfl_xor(S[seg][c], m, 64);
+                D0 += __shfl_xor(D0, m, 64);
+                D1 += __shfl_xor(D1, m, 64);
+            }
+            if (lane == 0) {
+                const SegmentBar a = segment_chain(L.v, 0, q, S[0][0], S[0][1], S[0][2], S[0][3]);
+                const SegmentBar b = segment_chain(L.v, 1, q, S[1][0], S[1][1], S[1][2], S[1][3]);
+                L.v.bar[0][q] = a.x0; L.v.bar[1][q] = a.x1 + b.x0; L.v.bar[2][q] = b.x1;
+                L.v.bar[3][q] = a.va; L.v.bar[4][q] = b.vb; L.v.bar[5][q] = a.vb + b.va;
+                L.v.bar[6][q] = a.h + D0; L.v.bar[7][q] = b.h + D1;
+            }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < here) {
+#pragma unroll
+            for (int f = 0; f < 8; ++f)
+                if (bar.p[f]) bar.p[f][p_first + threadIdx.x] = L.v.bar[f][threadIdx.x];
+        }
+        __syncthreads();
+    }
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -786,6 +1241,15 @@ unsigned trajectory_grid(size_t n, int P)
     return (unsigned)(trips < kTrajGridCap ? trips : kTrajGridCap);
 }
 
+// lanes per problem of the reverse-mode kernels: a power of two <= 64 from k alone
+int vjp_group(size_t k)
+{
+    const size_t units = (k & 1) == 0 ? k >> 1 : k;      // what a lane takes at a time: pairs when k is even
+    int G = 1;
+    while (G < 64 && (size_t)G < units) G <<= 1;
+    return G;
+}
+
 Spline8 spline_of(const double *const s[8])
 {
     Spline8 t;
@@ -816,11 +1280,7 @@ hipError_t launch_trajectory_jvp(size_t n, size_t k, const double *const d_splin
 hipError_t launch_trajectory_vjp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *d_g_pos,
                                  const double *d_g_vel, const double *d_g_acc, double *const d_spline_bar[8], double *d_tau_bar, hipStream_t stream)
 {
-    const bool vec = (k & 1) == 0;
-    const size_t units = vec ? k >> 1 : k;      // what a lane takes at a time
-    int G = 1;
-    while (G < 64 && (size_t)G < units) G <<= 1;
-    const int P = problems_per_trip(k, false);
+    const int G = vjp_group(k), P = problems_per_trip(k, false);
     SplineBar8 bar;
     for (int f = 0; f < 8; ++f) bar.p[f] = d_spline_bar[f];
     const dim3 grid(trajectory_grid(n, P)), block(kTrajBlock);
@@ -884,6 +1344,58 @@ hipError_t launch_extrema_batch(const BatchView &b, const double *d_lo, const do
     RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_extrema<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
                                                            FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_lo, d_hi,
                                                            extrema_of(d_value), extrema_of(d_time)));
+    return hipGetLastError();
+}
+
+// the integrals over each window: the evaluator's launch shape, the derivative in reverse mode k_trajectory_vjp's
+namespace {
+Integrals4 integrals_of(double *const t[4])
+{
+    Integrals4 x;
+    for (int f = 0; f < 4; ++f) x.p[f] = t[f];
+    return x;
+}
+}  // namespace
+
+hipError_t launch_integrals(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, double *const d_value[4],
+                            hipStream_t stream)
+{
+    const int P = problems_per_trip(k, true);
+    hipLaunchKernelGGL(k_integrals, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, d_lo, d_hi,
+                       integrals_of(d_value));
+    return hipGetLastError();
+}
+
+hipError_t launch_integrals_batch(const BatchView &b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4], hipStream_t stream)
+{
+    if (b.n == 0) return hipSuccess;
+    const int P = problems_per_trip(k, true);
+    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_integrals<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
+                                                           FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_lo, d_hi,
+                                                           integrals_of(d_value)));
+    return hipGetLastError();
+}
+
+hipError_t launch_integrals_jvp(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
+                                const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot, double *const d_value_dot[4],
+                                hipStream_t stream)
+{
+    const int P = problems_per_trip(k, true);
+    hipLaunchKernelGGL(k_jvp_integrals, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)},
+                       spline_of(d_spline_dot), n, k, P, d_lo, d_hi, d_lo_dot, d_hi_dot, integrals_of(d_value_dot));
+    return hipGetLastError();
+}
+
+hipError_t launch_integrals_vjp(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, const double *const d_g[4],
+                                double *const d_spline_bar[8], double *d_lo_bar, double *d_hi_bar, hipStream_t stream)
+{
+    const int G = vjp_group(k), P = problems_per_trip(k, false);
+    SplineBar8 bar;
+    for (int f = 0; f < 8; ++f) bar.p[f] = d_spline_bar[f];
+    IntegralsIn4 g;
+    for (int f = 0; f < 4; ++f) g.p[f] = d_g[f];
+    hipLaunchKernelGGL(k_vjp_integrals, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, G, d_lo,
+                       d_hi, g, bar, d_lo_bar, d_hi_bar);
     return hipGetLastError();
 }
 
