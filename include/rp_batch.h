@@ -59,7 +59,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      struct changes size and no existing entry changes meaning, so the revision stays); rp_trajectory_extrema and
  *      rp_batch_extrema_device (the extreme position and velocity over a window of times; new entries only, the revision stays);
  *      rp_trajectory_integrals, rp_trajectory_integrals_vjp, rp_trajectory_integrals_jvp and rp_batch_integrals_device (integrals over a
- *      window of times and their first derivatives; new entries only, the revision stays) */
+ *      window of times and their first derivatives; new entries only, the revision stays); rp_trajectory_eval_hvp (the second derivative
+ *      of the evaluation along a direction; a new entry only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -361,6 +362,20 @@ RP_API int rp_trajectory_eval_vjp(int device, void *stream, size_t n, size_t k, 
 RP_API int rp_trajectory_eval_jvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau,
                                   const double *const d_spline_dot[8], const double *d_tau_dot,
                                   double *d_pos_dot, double *d_vel_dot, double *d_acc_dot);
+/* Second order: the derivative of rp_trajectory_eval_vjp's outputs (spline_bar[8], tau_bar) along the direction (spline_dot, tau_dot),
+ * the upstream gradients held fixed -- S_o g_o (the second derivative of o) (spline_dot, tau_dot) over the outputs o of pos, vel, acc
+ * (DESIGN.md section 17).  That matrix is symmetric: the one entry is forward-over-reverse and the (spline, tau) part of
+ * reverse-over-reverse; the part of a double backward in the upstream gradients is rp_trajectory_eval_jvp.  The derivatives at a query are
+ * the selected segment's, as everywhere.  Rules as rp_trajectory_eval_vjp's and _jvp's: any d_g_* NULL: zeros, not read; any entry of
+ * d_spline_dot, the table, or d_tau_dot NULL: zeros, not read (NULL and explicit zeros give the same bits); any output NULL: not wanted,
+ * not written, at least one given; every n x k array 16-byte aligned.  The k queries reduce as rp_trajectory_eval_vjp's do, in an order
+ * that depends on k alone, no atomics: a problem's result is the same bits in any batch and from run to run.  NaN rule: a problem with a
+ * duration that is not finite or not > 0 is NaN in all its outputs; a NaN tau or tau_dot makes its own tau_bar_dot NaN, and the sums of
+ * its problem with it. */
+RP_API int rp_trajectory_eval_hvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau,
+                                  const double *d_g_pos, const double *d_g_vel, const double *d_g_acc,
+                                  const double *const d_spline_dot[8], const double *d_tau_dot,
+                                  double *const d_spline_bar_dot[8], double *d_tau_bar_dot);
 /* The arbitrary-time sibling of rp_batch_sample_device: rp_trajectory_eval of the batch's current state, PROBLEM order, every variant
  * and dtype (the state read in the batch's storage type, evaluated in double: bit for bit rp_trajectory_eval on what
  * rp_batch_get_state returns).  d_tau and the outputs: n x k doubles, 16-byte aligned, with rp_trajectory_eval's segment, extrapolation,

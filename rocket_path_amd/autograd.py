@@ -21,7 +21,9 @@ torch's once_differentiable error).  Without them the code path is the rest-to-r
 
 trajectory_eval is stateless: one rp_trajectory_eval launch on the current stream, differentiable to first order
 in all eight spline inputs and in tau through one rp_trajectory_eval_vjp (backward) or rp_trajectory_eval_jvp (forward mode) launch.
-min_time_trajectory composes it with min_time_solve, whose derivatives supply the rest of the chain.
+min_time_trajectory composes it with min_time_solve, whose derivatives supply the rest of the chain.  With order=2 (section 17) the
+evaluator's backward is differentiable once more: the backward of the backward is one rp_trajectory_eval_jvp launch (the part in the
+upstream gradients) and one rp_trajectory_eval_hvp launch (the part in the spline inputs and tau); order=1, the default, is first order.
 trajectory_crossing (section 14) is its inverse -- the first time the spline is at a level, one rp_trajectory_crossing launch -- with both
 derivative modes composed from the evaluator's launches; min_time_crossing composes it with min_time_solve.
 trajectory_extrema (section 15) answers how far and how fast at most: the extreme position and velocity over a window of times, one
@@ -517,7 +519,71 @@ class _TrajectoryEval(torch.autograd.Function):
         return tuple(outs)
 
 
-def trajectory_eval(pos0, pos1, pos2, vel1, duration0, duration1, tau, *, vel0=None, vel2=None):
+class _TrajectoryEval2(_TrajectoryEval):
+    """_TrajectoryEval with a backward that can be differentiated again (order=2): the same forward, the same forward-mode rule, and
+    the same one rp_trajectory_eval_vjp launch in backward, made through _TrajectoryVJP so that a create_graph backward records it."""
+
+    @staticmethod
+    def backward(ctx, g_pos, g_vel, g_acc):
+        if g_pos is None and g_vel is None and g_acc is None:
+            return (None,) * 9
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        return _TrajectoryVJP.apply(*inputs, g_pos, g_vel, g_acc, tuple(ctx.needs_input_grad[:9]))
+
+
+class _TrajectoryVJP(torch.autograd.Function):
+    """(the eight spline inputs, tau, g_pos, g_vel, g_acc) -> (the eight bars, tau_bar): one rp_trajectory_eval_vjp launch that forms the
+    bars `need` names (the others are None), as a function that can be differentiated once.  For cotangents u on its outputs:
+        (g_pos, g_vel, g_acc)_bar = J u                          one rp_trajectory_eval_jvp launch with tangents u
+        (spline, tau)_bar = (S_o g_o (second derivative of o)) u   one rp_trajectory_eval_hvp launch with direction u (symmetric)
+    each made only if something on its side requires grad."""
+
+    @staticmethod
+    def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, tau, g_pos, g_vel, g_acc, need):
+        spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
+        tau = tau.contiguous()
+        n = tau.shape[0]
+        bars = [torch.empty(n, dtype=torch.float64, device=tau.device) if need[f] else None for f in range(8)]
+        tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if need[8] else None
+        _trajectory_launch(capi.trajectory_eval_vjp, tau.device, spline, tau, _dense(g_pos), _dense(g_vel), _dense(g_acc), bars, tau_bar)
+        return tuple(bars) + (tau_bar,)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)      # a bar nothing downstream uses arrives as None and goes to the kernels as NULL: not read
+        ctx.given = [t is not None for t in inputs[:12]]
+        ctx.save_for_backward(*[t for t in inputs[:12] if t is not None])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *u):
+        out = [None] * 13
+        if all(x is None for x in u):
+            return tuple(out)
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        spline, tau, g = [_dense(t) for t in inputs[:8]], inputs[8].contiguous(), [_dense(t) for t in inputs[9:12]]
+        need, n, dev = ctx.needs_input_grad, tau.shape[0], tau.device
+        dots, tau_dot = [_dense(x) for x in u[:8]], _dense(u[8])
+        if any(need[9:12]):
+            outs = [torch.empty(tau.shape, dtype=torch.float64, device=dev) if need[9 + c] else None for c in range(3)]
+            _trajectory_launch(capi.trajectory_eval_jvp, dev, spline, tau, dots, tau_dot, *outs)
+            out[9:12] = outs
+        if any(need[:9]) and any(x is not None for x in g):
+            bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(8)]
+            tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=dev) if need[8] else None
+            _trajectory_launch(capi.trajectory_eval_hvp, dev, spline, tau, *g, dots, tau_dot, bars, tau_bar)
+            out[:9] = bars + [tau_bar]
+        return tuple(out)
+
+
+def _check_order(order, who):
+    if order not in (1, 2):
+        raise ValueError("%s: order must be 1 or 2, got %r" % (who, order))
+
+
+def trajectory_eval(pos0, pos1, pos2, vel1, duration0, duration1, tau, *, vel0=None, vel2=None, order=1):
     """Position, velocity and acceleration of the two-segment spline (pos0, vel0) -> (pos1, vel1) -> (pos2, vel2) with the durations
     duration0, duration1 -- 1-D float64 tensors on one ROCm device; vel0 / vel2 of None count as zeros -- at the times tau, (n, k) or
     (k,) (the same times for every problem), counted from the start of segment 0.  Returns (pos, vel, acc), (n, k) each.
@@ -526,23 +592,36 @@ def trajectory_eval(pos0, pos1, pos2, vel1, duration0, duration1, tau, *, vel0=N
     [0, duration0 + duration1] the end segments' cubics continue; a problem with a duration that is not finite or not > 0 is NaN).
     Differentiable to first order in all eight spline inputs and in tau: reverse mode is one rp_trajectory_eval_vjp launch (tau's
     gradient is formed only when tau requires it; a double backward raises torch's once_differentiable error), forward mode
-    (torch.autograd.forward_ad, torch.func.jvp) one rp_trajectory_eval_jvp launch.  Does not synchronise the host."""
+    (torch.autograd.forward_ad, torch.func.jvp) one rp_trajectory_eval_jvp launch.  Does not synchronise the host.
+
+    order=2 (1 or 2; anything else: ValueError) makes the backward differentiable once more -- torch.autograd.grad(..., create_graph=True),
+    torch.autograd.functional.hvp / hessian: the values, the gradients and the forward-mode tangents are the same launches and the same
+    bits as with order=1; the backward of the backward is one rp_trajectory_eval_jvp launch (for the gradients in the first backward's
+    grad_outputs) and one rp_trajectory_eval_hvp launch (for those in the spline inputs and tau), each only if something on its side
+    requires grad.  A third derivative raises torch's once_differentiable error."""
+    _check_order(order, "trajectory_eval")
     tau = _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0, vel2, "trajectory_eval")
-    return _TrajectoryEval.apply(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, tau)
+    function = _TrajectoryEval if order == 1 else _TrajectoryEval2
+    return function.apply(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, tau)
 
 
-def min_time_trajectory(pos0, pos1, pos2, tau, *, normalized=False, vel0=None, vel2=None, gap_tol=1e-8, max_iter=200, params=None):
+def min_time_trajectory(pos0, pos1, pos2, tau, *, normalized=False, vel0=None, vel2=None, gap_tol=1e-8, max_iter=200, params=None, order=1):
     """min_time_solve, then trajectory_eval of its solution at tau ((n, k) or (k,)): returns (pos, vel, acc, vel1, duration0, duration1,
     iters, status).  normalized=True: tau is a fraction of each problem's total time (0: the start, 1: the end), multiplied by
     duration0 + duration1 in torch, so that its dependence on the solution is differentiated too.  Plain composition: pos, vel and acc
-    are differentiable in the positions, the end velocities and tau through the solve's derivatives and the evaluator's."""
+    are differentiable in the positions, the end velocities and tau through the solve's derivatives and the evaluator's.
+
+    order=2 (trajectory_eval's): with the solve's own double backward, pos, vel and acc are twice differentiable in the positions and tau
+    for rest-to-rest problems (normalized=True included: a torch multiplication).  With vel0 / vel2 that require grad the solve is first
+    order, and a double backward through it raises torch's once_differentiable error as it does with order=1."""
+    _check_order(order, "min_time_trajectory")
     _check_positions(pos0, pos1, pos2, "min_time_trajectory")
     tau = _check_tau(pos0, tau, "min_time_trajectory")      # before the solve: a bad tau costs none
     vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2, gap_tol=gap_tol, max_iter=max_iter, params=params,
                                                                 vel0=vel0, vel2=vel2)
     if normalized:
         tau = tau * (duration0 + duration1).unsqueeze(1)
-    pos, vel, acc = trajectory_eval(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0=vel0, vel2=vel2)
+    pos, vel, acc = trajectory_eval(pos0, pos1, pos2, vel1, duration0, duration1, tau, vel0=vel0, vel2=vel2, order=order)
     return pos, vel, acc, vel1, duration0, duration1, iters, status
 
 

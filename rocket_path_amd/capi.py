@@ -104,6 +104,8 @@ SIGNATURES = {
                                               ctypes.POINTER(_vp), _vp]),
     "rp_trajectory_eval_jvp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp),
                                               _vp, _vp, _vp, _vp]),
+    "rp_trajectory_eval_hvp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, _vp, _vp,
+                                              ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp), _vp]),
     "rp_batch_trajectory_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "rp_trajectory_crossing": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, _vp]),
     "rp_batch_crossing_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp]),
@@ -203,6 +205,15 @@ def trajectory_eval_jvp(device, stream, n, k, spline, d_tau, spline_dot=None, d_
     """rp_trajectory_eval_jvp: `spline_dot` the eight tangent addresses (None entries: zeros), tangents of pos, vel, acc out."""
     _trajectory("rp_trajectory_eval_jvp", device, stream, n, k, spline, d_tau, list(spline_dot) if spline_dot is not None else None,
                 d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot)
+
+
+def trajectory_eval_hvp(device, stream, n, k, spline, d_tau, d_g_pos=None, d_g_vel=None, d_g_acc=None, spline_dot=None, d_tau_dot=None,
+                        spline_bar_dot=None, d_tau_bar_dot=None):
+    """rp_trajectory_eval_hvp: the derivative of trajectory_eval_vjp's outputs along (`spline_dot`, d_tau_dot) (None entries: zeros) at fixed
+    upstream gradients; `spline_bar_dot` the eight output addresses (None entries: not wanted)."""
+    _trajectory("rp_trajectory_eval_hvp", device, stream, n, k, spline, d_tau, d_g_pos, d_g_vel, d_g_acc,
+                list(spline_dot) if spline_dot is not None else None, d_tau_dot,
+                list(spline_bar_dot) if spline_bar_dot is not None else None, d_tau_bar_dot)
 
 
 def trajectory_crossing(device, stream, n, k, spline, d_level, d_time, d_vel=None):

@@ -153,6 +153,9 @@ hipError_t launch_trajectory_vjp(size_t n, size_t k, const double *const d_splin
 hipError_t launch_trajectory_jvp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *const d_spline_dot[8],
                                  const double *d_tau_dot, double *d_pos_dot, double *d_vel_dot, double *d_acc_dot, hipStream_t stream);
 // the same evaluation of the batch's current state, problem order, every variant and dtype (launch_sample_range's loader: spline_core.h, FromBatch)
+hipError_t launch_trajectory_hvp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *d_g_pos,
+                                 const double *d_g_vel, const double *d_g_acc, const double *const d_spline_dot[8], const double *d_tau_dot,
+                                 double *const d_spline_bar_dot[8], double *d_tau_bar_dot, hipStream_t stream);
 hipError_t launch_trajectory_batch(const BatchView &b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc, hipStream_t stream);
 // the first time in [0, duration0 + duration1] at which the spline is at each level (n x k), and the velocity there (null: not wanted);
 // stateless and of the batch's current state

@@ -1046,6 +1046,26 @@ int rp_trajectory_eval_jvp(int device, void *stream, size_t n, size_t k, const d
     return RP_OK;
 }
 
+int rp_trajectory_eval_hvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau,
+                           const double *d_g_pos, const double *d_g_vel, const double *d_g_acc, const double *const d_spline_dot[8],
+                           const double *d_tau_dot, double *const d_spline_bar_dot[8], double *d_tau_bar_dot)
+{
+    const void *const per_query[] = {d_g_pos, d_g_vel, d_g_acc, d_tau_dot, d_tau_bar_dot};
+    int st = check_spline(__func__, device, d_spline);
+    if (st == RP_OK) st = check_queries(__func__, n, k, d_tau, per_query, 5);
+    if (st != RP_OK) return st;
+    double *const no_bars[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const double *const no_dots[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double *const *bars = d_spline_bar_dot ? d_spline_bar_dot : no_bars;
+    bool any = d_tau_bar_dot != nullptr;
+    for (int f = 0; f < 8; ++f) any = any || bars[f];
+    if (!any) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_trajectory_hvp(n, k, d_spline, d_tau, d_g_pos, d_g_vel, d_g_acc, d_spline_dot ? d_spline_dot : no_dots, d_tau_dot, bars,
+                                     d_tau_bar_dot, (hipStream_t)stream));
+    return RP_OK;
+}
+
 int rp_batch_trajectory_device(rp_batch *b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc)
 {
     if (!b) return fail(RP_ERR_INVALID, "null batch handle");

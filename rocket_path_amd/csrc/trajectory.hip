@@ -1,6 +1,7 @@
 // trajectory.hip -- a solved two-segment spline evaluated at the caller's own times, and the first derivatives of that
 // evaluation, gfx950: rp_trajectory_eval, rp_trajectory_eval_vjp, rp_trajectory_eval_jvp and rp_batch_trajectory_device
-// (include/rp_batch.h); and the plot data, the same spline on the reference's fixed grid: rp_batch_sample,
+// (include/rp_batch.h); and the derivative of the reverse rule along a direction, rp_trajectory_eval_hvp
+// (k_trajectory_hvp); and the plot data, the same spline on the reference's fixed grid: rp_batch_sample,
 // rp_batch_sample_device, rp_batch_sample_range (k_sample, k_sample_records, at the end of the kernels); and the inverse of the
 // evaluation, the first time the spline reaches a level: rp_trajectory_crossing, rp_batch_crossing_device (k_crossing, k_batch_crossing;
 // DESIGN.md section 14); and the extreme position and velocity over a window of times: rp_trajectory_extrema, rp_batch_extrema_device
@@ -358,6 +359,162 @@ k_trajectory_vjp(FromArrays stage, size_t n, size_t k, int P, int G, const doubl
                 L.bar[0][q] = a.x0; L.bar[1][q] = a.x1 + b.x0; L.bar[2][q] = b.x1;
                 L.bar[3][q] = a.va; L.bar[4][q] = b.vb; L.bar[5][q] = a.vb + b.va;
                 L.bar[6][q] = a.h - T1; L.bar[7][q] = b.h;
+            }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < here) {
+#pragma unroll
+            for (int f = 0; f < 8; ++f)
+                if (bar.p[f]) bar.p[f][p_first + threadIdx.x] = L.bar[f][threadIdx.x];
+        }
+        __syncthreads();
+    }
+}
+
+// ---- second order: the derivative of the reverse rule along a direction (rp_trajectory_eval_hvp) ----
+// With the upstream gradients held fixed and the direction (x0d, x1d, vad, vbd, hd) on the segment's ends, sd on its local time (tau_dot in
+// segment 0, tau_dot - duration0_dot in segment 1) and (acc0d, jrk0d) from segment_tangents, the four weights w0 .. w3 of the reverse rule:
+//     vel_d = vad + (acc0d + jrk0d s / 2) s + acc sd      acc_d = acc0d + jrk0d s + jrk0 sd
+//     tau_bar_dot = gp vel_d + gv acc_d + ga jrk0d                                       (per query)
+//     S_vd = S w0 sd    S_ad = S w1 sd    S_jd = S w2 sd      (S_x has no derivative)
+//     A_d = S_ad - 2 S_jd / h + 2 S_j hd / h^2
+//     x1_bar_dot = 6 A_d / h^2 - 12 A hd / h^3      x0_bar_dot = -x1_bar_dot
+//     va_bar_dot = S_vd - 4 A_d / h + 4 A hd / h^2 - 2 S_jd / h^2 + 4 S_j hd / h^3
+//     vb_bar_dot = -2 A_d / h + 2 A hd / h^2 + 2 S_jd / h^2 - 4 S_j hd / h^3
+//     h_bar_dot = A_d c1 + A c1d + S_jd c2 + S_j c2d      (c1, c2 the two brackets of h_bar, c1d, c2d their derivatives)
+// routed as the reverse rule's, duration0 taking off the sum of tau_bar_dot over segment 1.  k_trajectory_vjp's reduction -- the same
+// group of G lanes per problem, the same lane stride, the same butterfly -- over eleven sums: S_a and S_j of each segment (S_x and S_v are in
+// no derivative: they enter the reverse rule linearly, with constant coefficients), the six dotted ones and that sum.
+struct HvpLds {
+    double c[2][6][kTrajProblems];      // per segment: va, vb, x1 - x0, acc0, jrk0, 1 / h ...
+    double t[2][6][kTrajProblems];      // ... and along the direction: vad, vbd, x1d - x0d, acc0d, jrk0d, hd
+    double d0[kTrajProblems], d0_dot[kTrajProblems];
+    double bar[8][kTrajProblems];       // the problem's eight results, in the pointer table's order
+};
+
+// one problem's constants and their derivatives along the direction into LDS
+__device__ __forceinline__ void stage_hvp(HvpLds &L, int q, size_t i, const Spline8 &s, const Spline8 &dot)
+{
+    // one segment at a time, as stage_tangents (registers)
+    double t0 = s.p[6][i], t1 = s.p[7][i];
+    check_durations(t0, t1);
+    const double t0d = dot.p[6] ? dot.p[6][i] : 0.0, t1d = dot.p[7] ? dot.p[7][i] : 0.0;
+    L.d0[q] = t0;
+    L.d0_dot[q] = t0d;
+#pragma nounroll
+    for (int seg = 0; seg < 2; ++seg) {
+        const double *pva = seg ? s.p[5] : s.p[3], *pvb = seg ? s.p[4] : s.p[5];      // vel0, vel1 | vel1, vel2
+        const double *pvad = seg ? dot.p[5] : dot.p[3], *pvbd = seg ? dot.p[4] : dot.p[5];
+        const double *px0 = seg ? s.p[1] : s.p[0], *px1 = seg ? s.p[2] : s.p[1];
+        const double *px0d = seg ? dot.p[1] : dot.p[0], *px1d = seg ? dot.p[2] : dot.p[1];
+        const double x0 = px0[i], x1 = px1[i], va = pva ? pva[i] : 0.0, vb = pvb ? pvb[i] : 0.0;
+        const double x0d = px0d ? px0d[i] : 0.0, x1d = px1d ? px1d[i] : 0.0, vad = pvad ? pvad[i] : 0.0, vbd = pvbd ? pvbd[i] : 0.0;
+        const double ih = rcp_<double>(seg ? t1 : t0), hd = seg ? t1d : t0d;
+        const double dx = x1 - x0, dxd = x1d - x0d;
+        double acc0, jrk0, acc0d, jrk0d;
+        segment_constants(x0, x1, va, vb, ih, acc0, jrk0);
+        segment_tangents(dx, va, vb, acc0, ih, dxd, vad, vbd, hd, acc0d, jrk0d);
+        L.c[seg][0][q] = va; L.c[seg][1][q] = vb; L.c[seg][2][q] = dx; L.c[seg][3][q] = acc0; L.c[seg][4][q] = jrk0; L.c[seg][5][q] = ih;
+        L.t[seg][0][q] = vad; L.t[seg][1][q] = vbd; L.t[seg][2][q] = dxd; L.t[seg][3][q] = acc0d; L.t[seg][4][q] = jrk0d; L.t[seg][5][q] = hd;
+    }
+}
+
+// S: S_a, S_j of the segment; D: S_vd, S_ad, S_jd
+__device__ __forceinline__ SegmentBar segment_chain_dot(const HvpLds &L, int seg, int q, const double (&S)[2], const double (&D)[3])
+{
+    const double va = L.c[seg][0][q], vb = L.c[seg][1][q], dx = L.c[seg][2][q], acc0 = L.c[seg][3][q], ih = L.c[seg][5][q];
+    const double vad = L.t[seg][0][q], vbd = L.t[seg][1][q], dxd = L.t[seg][2][q], acc0d = L.t[seg][3][q], hd = L.t[seg][5][q];
+    const double ih2 = ih * ih, ih3 = ih2 * ih, ih4 = ih2 * ih2;
+    const double Sj = S[1], Svd = D[0], Sad = D[1], Sjd = D[2];
+    const double A = S[0] - (2.0 * ih) * Sj;
+    const double Ad = Sad - (2.0 * ih) * Sjd + ((2.0 * ih2) * Sj) * hd;
+    SegmentBar b;
+    b.x1 = (6.0 * ih2) * Ad - ((12.0 * ih3) * A) * hd;
+    b.x0 = -b.x1;
+    b.va = Svd - (4.0 * ih) * Ad + ((4.0 * ih2) * A) * hd - (2.0 * ih2) * Sjd + ((4.0 * ih3) * Sj) * hd;
+    b.vb = (2.0 * ih2) * Sjd - (2.0 * ih) * Ad + ((2.0 * ih2) * A) * hd - ((4.0 * ih3) * Sj) * hd;
+    const double c1 = (va * 4.0 + vb * 2.0) * ih2 - dx * (12.0 * ih3), c2 = acc0 * (2.0 * ih2) - (vb - va) * (4.0 * ih3);
+    const double c1d = (vad * 4.0 + vbd * 2.0) * ih2 - dxd * (12.0 * ih3) + (dx * (36.0 * ih4) - (va * 4.0 + vb * 2.0) * (2.0 * ih3)) * hd;
+    const double c2d = acc0d * (2.0 * ih2) - (vbd - vad) * (4.0 * ih3) + ((vb - va) * (12.0 * ih4) - acc0 * (4.0 * ih3)) * hd;
+    b.h = Ad * c1 + A * c1d + Sjd * c2 + Sj * c2d;
+    return b;
+}
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_trajectory_hvp(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, int G, const double *__restrict__ tau, const double *__restrict__ g_pos,
+                 const double *__restrict__ g_vel, const double *__restrict__ g_acc, const double *__restrict__ tau_dot, SplineBar8 bar,
+                 double *__restrict__ tau_bar_dot)
+{
+    __shared__ HvpLds L;
+    const int groups = kTrajBlock / G, group = (int)threadIdx.x / G, lane = (int)threadIdx.x & (G - 1);
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        const size_t p_first = trip * (size_t)P;
+        const int here = problems_here(n, p_first, P);
+        if ((int)threadIdx.x < here) stage_hvp(L, threadIdx.x, p_first + threadIdx.x, stage.s, dot);
+        __syncthreads();
+        for (int q = group; q < here; q += groups) {
+            const size_t row = (p_first + (size_t)q) * k;
+            const double d0 = L.d0[q], d0d = L.d0_dot[q];
+            // this lane's eleven sums: S_a, S_j and S_vd, S_ad, S_jd per segment, and tau_bar_dot over segment 1
+            double S[2][2] = {{0.0, 0.0}, {0.0, 0.0}}, D[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, T1d = 0.0;
+            auto query = [&](double ta, double td, double gp, double gv, double ga) -> double {
+                const bool seg = !(ta < d0);
+                const double s = seg ? ta - d0 : ta, sd = seg ? td - d0d : td;
+                const double acc0 = L.c[seg][3][q], jrk0 = L.c[seg][4][q];
+                const double vad = L.t[seg][0][q], acc0d = L.t[seg][3][q], jrk0d = L.t[seg][4][q];
+                const double acc = acc0 + jrk0 * s;
+                const double vel_d = vad + (acc0d + jrk0d * (s * 0.5)) * s + acc * sd, acc_d = acc0d + jrk0d * s + jrk0 * sd;
+                const double tbd = gp * vel_d + gv * acc_d + ga * jrk0d;
+                const double h2 = s * (s * 0.5), h3 = h2 * (s * (1.0 / 3.0));
+                const double w0 = gp, w1 = gp * s + gv, w2 = gp * h2 + gv * s + ga, w3 = gp * h3 + gv * h2 + ga * s;
+                const double u0 = w0 * sd, u1 = w1 * sd, u2 = w2 * sd;
+                S[0][0] += seg ? 0.0 : w2; S[0][1] += seg ? 0.0 : w3;
+                S[1][0] += seg ? w2 : 0.0; S[1][1] += seg ? w3 : 0.0;
+                D[0][0] += seg ? 0.0 : u0; D[0][1] += seg ? 0.0 : u1; D[0][2] += seg ? 0.0 : u2;
+                D[1][0] += seg ? u0 : 0.0; D[1][1] += seg ? u1 : 0.0; D[1][2] += seg ? u2 : 0.0;
+                T1d += seg ? tbd : 0.0;
+                return tbd;
+            };
+            if ((k & 1) == 0) {      // k even: the row starts on a 16-byte boundary
+                const size_t units = k >> 1;
+                for (size_t u = lane; u < units; u += G) {
+                    const size_t at = row + 2 * u;
+                    double ta, tb, da = 0.0, db = 0.0, pa = 0.0, pb = 0.0, va = 0.0, vb = 0.0, aa = 0.0, ab = 0.0;
+                    load_pair(tau, at, true, ta, tb);
+                    if (tau_dot) load_pair(tau_dot, at, true, da, db);
+                    if (g_pos) load_pair(g_pos, at, true, pa, pb);
+                    if (g_vel) load_pair(g_vel, at, true, va, vb);
+                    if (g_acc) load_pair(g_acc, at, true, aa, ab);
+                    const double ba = query(ta, da, pa, va, aa);
+                    const double bb = query(tb, db, pb, vb, ab);
+                    if (tau_bar_dot) store_pair(tau_bar_dot, at, ba, bb, true);
+                }
+            } else {
+                for (size_t u = lane; u < k; u += G) {
+                    const size_t at = row + u;
+                    const double b = query(tau[at], tau_dot ? tau_dot[at] : 0.0, g_pos ? g_pos[at] : 0.0, g_vel ? g_vel[at] : 0.0,
+                                           g_acc ? g_acc[at] : 0.0);
+                    if (tau_bar_dot) tau_bar_dot[at] = b;
+                }
+            }
+            // the group's lanes combine: after the butterfly every lane holds the same eleven sums
+            for (int m = 1; m < G; m <<= 1) {
+#pragma unroll
+                for (int seg = 0; seg < 2; ++seg) {
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) S[seg][c] += __shfl_xor(S[seg][c], m, 64);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) D[seg][c] += __shfl_xor(D[seg][c], m, 64);
+                }
+                T1d += __shfl_xor(T1d, m, 64);
+            }
+            if (lane == 0) {
+                const SegmentBar a = segment_chain_dot(L, 0, q, S[0], D[0]);
+                const SegmentBar b = segment_chain_dot(L, 1, q, S[1], D[1]);
+                L.bar[0][q] = a.x0; L.bar[1][q] = a.x1 + b.x0; L.bar[2][q] = b.x1;
+                L.bar[3][q] = a.va; L.bar[4][q] = b.vb; L.bar[5][q] = a.vb + b.va;
+                L.bar[6][q] = a.h - T1d; L.bar[7][q] = b.h;
             }
         }
         __syncthreads();
@@ -1286,6 +1443,18 @@ hipError_t launch_trajectory_vjp(size_t n, size_t k, const double *const d_splin
     const dim3 grid(trajectory_grid(n, P)), block(kTrajBlock);
     hipLaunchKernelGGL(k_trajectory_vjp, grid, block, 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, G, d_tau, d_g_pos, d_g_vel, d_g_acc,
                        bar, d_tau_bar);
+    return hipGetLastError();
+}
+
+hipError_t launch_trajectory_hvp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *d_g_pos,
+                                 const double *d_g_vel, const double *d_g_acc, const double *const d_spline_dot[8], const double *d_tau_dot,
+                                 double *const d_spline_bar_dot[8], double *d_tau_bar_dot, hipStream_t stream)
+{
+    const int G = vjp_group(k), P = problems_per_trip(k, false);
+    SplineBar8 bar;
+    for (int f = 0; f < 8; ++f) bar.p[f] = d_spline_bar_dot[f];
+    hipLaunchKernelGGL(k_trajectory_hvp, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)},
+                       spline_of(d_spline_dot), n, k, P, G, d_tau, d_g_pos, d_g_vel, d_g_acc, d_tau_dot, bar, d_tau_bar_dot);
     return hipGetLastError();
 }
 
