@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 
 #include "ip_kernels.h"
@@ -948,55 +949,54 @@ int rp_batch_sample_device(rp_batch *b, double *d_pos66, double *d_acc4)
     return RP_OK;
 }
 
-// ---- a spline at the caller's own times (trajectory.hip) ----
+// ---- what can be asked of a spline: its value at the caller's own times, the first crossing of a level, the extremes and the integrals
+// over a window, and their derivatives (trajectory.hip; DESIGN.md sections 13-17) ----
 namespace {
 
 bool misaligned16(const void *p) { return ((uintptr_t)p & 15u) != 0; }
 
-// what the trajectory, crossing and extrema entries check before any device call: the sizes ...
-int check_sizes(const char *who, size_t n, size_t k)
+// all-null tables, for a table the caller left out
+const double *const kNoInputs[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+double *const kNoOutputs[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+
+bool any_of(double *const t[], int count)
+{
+    bool any = false;
+    for (int f = 0; f < count; ++f) any = any || t[f];
+    return any;
+}
+
+// What every one of these entries checks of its queries before any device call: the sizes; the one n x k array the entry cannot do
+// without (`required`, under its name; the windowed entries have none: a null window end is -inf or +inf); the 16-byte alignment of
+// every other n x k array that is read or written (null: not given); and that an output was asked for -- after the alignment where
+// there is a required array, before it where there is none.
+int check_queries(const char *who, size_t n, size_t k, const double *required, const char *name, std::initializer_list<const void *> per_query,
+                  bool any_output)
 {
     if (n == 0 || k == 0) return fail(RP_ERR_INVALID, "%s: n and k must be positive", who);
     if (k >= ((size_t)1 << 31)) return fail(RP_ERR_INVALID, "%s: k must be below 2^31", who);
     if (n > SIZE_MAX / sizeof(double) / k) return fail(RP_ERR_INVALID, "%s: n x k does not fit", who);
-    return RP_OK;
-}
-
-// ... the times (or levels), and the 16-byte alignment of everything that is read or written per query (null: not given)
-int check_queries(const char *who, size_t n, size_t k, const double *d_tau, const void *const per_query[], int count, const char *queries = "d_tau")
-{
-    const int st = check_sizes(who, n, k);
-    if (st != RP_OK) return st;
-    if (!d_tau) return fail(RP_ERR_INVALID, "%s: %s is null", who, queries);
-    if (misaligned16(d_tau)) return fail(RP_ERR_INVALID, "%s: %s must be 16-byte aligned (the queries move as 16-byte vectors)", who, queries);
-    for (int i = 0; i < count; ++i)
-        if (misaligned16(per_query[i])) return fail(RP_ERR_INVALID, "%s: every n x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
-    return RP_OK;
-}
-
-// the extrema entries: both window ends may be null (-inf, +inf); the two tables of four outputs must hold at least one
-int check_extrema(const char *who, size_t n, size_t k, const double *d_lo, const double *d_hi, double *const d_value[4], double *const d_time[4])
-{
-    const int st = check_sizes(who, n, k);
-    if (st != RP_OK) return st;
-    bool any = false, odd = misaligned16(d_lo) || misaligned16(d_hi);
-    for (int f = 0; f < 4; ++f) {
-        double *const v = d_value ? d_value[f] : nullptr, *const t = d_time ? d_time[f] : nullptr;
-        any = any || v || t;
-        odd = odd || misaligned16(v) || misaligned16(t);
+    if (name) {
+        if (!required) return fail(RP_ERR_INVALID, "%s: %s is null", who, name);
+        if (misaligned16(required)) return fail(RP_ERR_INVALID, "%s: %s must be 16-byte aligned (the queries move as 16-byte vectors)", who, name);
+    } else if (!any_output) {
+        return fail(RP_ERR_INVALID, "%s: no output asked for", who);
     }
-    if (!any) return fail(RP_ERR_INVALID, "%s: no output asked for", who);
-    if (odd) return fail(RP_ERR_INVALID, "%s: every n x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
+    for (const void *array : per_query)
+        if (misaligned16(array)) return fail(RP_ERR_INVALID, "%s: every n x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
+    if (!any_output) return fail(RP_ERR_INVALID, "%s: no output asked for", who);
     return RP_OK;
 }
 
-int check_spline(const char *who, int device, const double *const d_spline[8])
+// the stateless entries: the device and the spline first
+int check_stateless(const char *who, int device, const double *const d_spline[8], size_t n, size_t k, const double *required, const char *name,
+                    std::initializer_list<const void *> per_query, bool any_output)
 {
     if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", who, device);
     if (!d_spline) return fail(RP_ERR_INVALID, "%s: d_spline is null", who);
     for (int f = 0; f < 8; ++f)
         if (!d_spline[f] && f != 3 && f != 4) return fail(RP_ERR_INVALID, "%s: d_spline[%d] is null (only the end velocities, [3] and [4], may be)", who, f);
-    return RP_OK;
+    return check_queries(who, n, k, required, name, per_query, any_output);
 }
 
 }  // namespace
@@ -1004,11 +1004,8 @@ int check_spline(const char *who, int device, const double *const d_spline[8])
 int rp_trajectory_eval(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau, double *d_pos,
                        double *d_vel, double *d_acc)
 {
-    const void *const per_query[] = {d_pos, d_vel, d_acc};
-    int st = check_spline(__func__, device, d_spline);
-    if (st == RP_OK) st = check_queries(__func__, n, k, d_tau, per_query, 3);
+    const int st = check_stateless(__func__, device, d_spline, n, k, d_tau, "d_tau", {d_pos, d_vel, d_acc}, d_pos || d_vel || d_acc);
     if (st != RP_OK) return st;
-    if (!d_pos && !d_vel && !d_acc) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
     RP_HIP(hipSetDevice(device));
     RP_HIP(rp::launch_trajectory_eval(n, k, d_spline, d_tau, d_pos, d_vel, d_acc, (hipStream_t)stream));
     return RP_OK;
@@ -1017,15 +1014,9 @@ int rp_trajectory_eval(int device, void *stream, size_t n, size_t k, const doubl
 int rp_trajectory_eval_vjp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau,
                            const double *d_g_pos, const double *d_g_vel, const double *d_g_acc, double *const d_spline_bar[8], double *d_tau_bar)
 {
-    const void *const per_query[] = {d_g_pos, d_g_vel, d_g_acc, d_tau_bar};
-    int st = check_spline(__func__, device, d_spline);
-    if (st == RP_OK) st = check_queries(__func__, n, k, d_tau, per_query, 4);
+    double *const *bars = d_spline_bar ? d_spline_bar : kNoOutputs;
+    const int st = check_stateless(__func__, device, d_spline, n, k, d_tau, "d_tau", {d_g_pos, d_g_vel, d_g_acc, d_tau_bar}, d_tau_bar || any_of(bars, 8));
     if (st != RP_OK) return st;
-    double *const none[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    double *const *bars = d_spline_bar ? d_spline_bar : none;
-    bool any = d_tau_bar != nullptr;
-    for (int f = 0; f < 8; ++f) any = any || bars[f];
-    if (!any) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
     RP_HIP(hipSetDevice(device));
     RP_HIP(rp::launch_trajectory_vjp(n, k, d_spline, d_tau, d_g_pos, d_g_vel, d_g_acc, bars, d_tau_bar, (hipStream_t)stream));
     return RP_OK;
@@ -1034,14 +1025,11 @@ int rp_trajectory_eval_vjp(int device, void *stream, size_t n, size_t k, const d
 int rp_trajectory_eval_jvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_tau,
                            const double *const d_spline_dot[8], const double *d_tau_dot, double *d_pos_dot, double *d_vel_dot, double *d_acc_dot)
 {
-    const void *const per_query[] = {d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot};
-    int st = check_spline(__func__, device, d_spline);
-    if (st == RP_OK) st = check_queries(__func__, n, k, d_tau, per_query, 4);
+    const int st = check_stateless(__func__, device, d_spline, n, k, d_tau, "d_tau", {d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot},
+                                   d_pos_dot || d_vel_dot || d_acc_dot);
     if (st != RP_OK) return st;
-    if (!d_pos_dot && !d_vel_dot && !d_acc_dot) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
-    const double *const none[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_trajectory_jvp(n, k, d_spline, d_tau, d_spline_dot ? d_spline_dot : none, d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot,
+    RP_HIP(rp::launch_trajectory_jvp(n, k, d_spline, d_tau, d_spline_dot ? d_spline_dot : kNoInputs, d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot,
                                      (hipStream_t)stream));
     return RP_OK;
 }
@@ -1050,18 +1038,12 @@ int rp_trajectory_eval_hvp(int device, void *stream, size_t n, size_t k, const d
                            const double *d_g_pos, const double *d_g_vel, const double *d_g_acc, const double *const d_spline_dot[8],
                            const double *d_tau_dot, double *const d_spline_bar_dot[8], double *d_tau_bar_dot)
 {
-    const void *const per_query[] = {d_g_pos, d_g_vel, d_g_acc, d_tau_dot, d_tau_bar_dot};
-    int st = check_spline(__func__, device, d_spline);
-    if (st == RP_OK) st = check_queries(__func__, n, k, d_tau, per_query, 5);
+    double *const *bars = d_spline_bar_dot ? d_spline_bar_dot : kNoOutputs;
+    const int st = check_stateless(__func__, device, d_spline, n, k, d_tau, "d_tau", {d_g_pos, d_g_vel, d_g_acc, d_tau_dot, d_tau_bar_dot},
+                                   d_tau_bar_dot || any_of(bars, 8));
     if (st != RP_OK) return st;
-    double *const no_bars[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const double *const no_dots[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    double *const *bars = d_spline_bar_dot ? d_spline_bar_dot : no_bars;
-    bool any = d_tau_bar_dot != nullptr;
-    for (int f = 0; f < 8; ++f) any = any || bars[f];
-    if (!any) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
     RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_trajectory_hvp(n, k, d_spline, d_tau, d_g_pos, d_g_vel, d_g_acc, d_spline_dot ? d_spline_dot : no_dots, d_tau_dot, bars,
+    RP_HIP(rp::launch_trajectory_hvp(n, k, d_spline, d_tau, d_g_pos, d_g_vel, d_g_acc, d_spline_dot ? d_spline_dot : kNoInputs, d_tau_dot, bars,
                                      d_tau_bar_dot, (hipStream_t)stream));
     return RP_OK;
 }
@@ -1069,22 +1051,18 @@ int rp_trajectory_eval_hvp(int device, void *stream, size_t n, size_t k, const d
 int rp_batch_trajectory_device(rp_batch *b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc)
 {
     if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    const void *const per_query[] = {d_pos, d_vel, d_acc};
-    const int st = check_queries(__func__, b->view.n, k, d_tau, per_query, 3);
+    const int st = check_queries(__func__, b->view.n, k, d_tau, "d_tau", {d_pos, d_vel, d_acc}, d_pos || d_vel || d_acc);
     if (st != RP_OK) return st;
-    if (!d_pos && !d_vel && !d_acc) return fail(RP_ERR_INVALID, "%s: no output asked for", __func__);
     RP_NEED_STATE(b);
     RP_HIP(rp::launch_trajectory_batch(b->view, d_tau, k, d_pos, d_vel, d_acc, b->stream));
     return RP_OK;
 }
 
-// ---- the first time a spline reaches a level (trajectory.hip) ----
+// the first time a spline reaches a level: the times are the output that cannot be left out
 int rp_trajectory_crossing(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_level, double *d_time,
                            double *d_vel)
 {
-    const void *const per_query[] = {d_time, d_vel};
-    int st = check_spline(__func__, device, d_spline);
-    if (st == RP_OK) st = check_queries(__func__, n, k, d_level, per_query, 2, "d_level");
+    const int st = check_stateless(__func__, device, d_spline, n, k, d_level, "d_level", {d_time, d_vel}, true);
     if (st != RP_OK) return st;
     if (!d_time) return fail(RP_ERR_INVALID, "%s: d_time is null", __func__);
     RP_HIP(hipSetDevice(device));
@@ -1095,8 +1073,7 @@ int rp_trajectory_crossing(int device, void *stream, size_t n, size_t k, const d
 int rp_batch_crossing_device(rp_batch *b, const double *d_level, size_t k, double *d_time, double *d_vel)
 {
     if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    const void *const per_query[] = {d_time, d_vel};
-    const int st = check_queries(__func__, b->view.n, k, d_level, per_query, 2, "d_level");
+    const int st = check_queries(__func__, b->view.n, k, d_level, "d_level", {d_time, d_vel}, true);
     if (st != RP_OK) return st;
     if (!d_time) return fail(RP_ERR_INVALID, "%s: d_time is null", __func__);
     RP_NEED_STATE(b);
@@ -1104,78 +1081,50 @@ int rp_batch_crossing_device(rp_batch *b, const double *d_level, size_t k, doubl
     return RP_OK;
 }
 
-// ---- the extreme position and velocity over a window (trajectory.hip) ----
-namespace {
-double *const kNoExtrema[4] = {nullptr, nullptr, nullptr, nullptr};
-}
-
+// the extreme position and velocity over a window: two tables of four outputs, which must hold at least one between them
 int rp_trajectory_extrema(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                           double *const d_value[4], double *const d_time[4])
 {
-    int st = check_spline(__func__, device, d_spline);
-    if (st == RP_OK) st = check_extrema(__func__, n, k, d_lo, d_hi, d_value, d_time);
+    double *const *v = d_value ? d_value : kNoOutputs, *const *t = d_time ? d_time : kNoOutputs;
+    const int st = check_stateless(__func__, device, d_spline, n, k, nullptr, nullptr, {d_lo, d_hi, v[0], v[1], v[2], v[3], t[0], t[1], t[2], t[3]},
+                                   any_of(v, 4) || any_of(t, 4));
     if (st != RP_OK) return st;
     RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_extrema(n, k, d_spline, d_lo, d_hi, d_value ? d_value : kNoExtrema, d_time ? d_time : kNoExtrema, (hipStream_t)stream));
+    RP_HIP(rp::launch_extrema(n, k, d_spline, d_lo, d_hi, v, t, (hipStream_t)stream));
     return RP_OK;
 }
 
 int rp_batch_extrema_device(rp_batch *b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4], double *const d_time[4])
 {
     if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    const int st = check_extrema(__func__, b->view.n, k, d_lo, d_hi, d_value, d_time);
+    double *const *v = d_value ? d_value : kNoOutputs, *const *t = d_time ? d_time : kNoOutputs;
+    const int st = check_queries(__func__, b->view.n, k, nullptr, nullptr, {d_lo, d_hi, v[0], v[1], v[2], v[3], t[0], t[1], t[2], t[3]},
+                                 any_of(v, 4) || any_of(t, 4));
     if (st != RP_OK) return st;
     RP_NEED_STATE(b);
-    RP_HIP(rp::launch_extrema_batch(b->view, d_lo, d_hi, k, d_value ? d_value : kNoExtrema, d_time ? d_time : kNoExtrema, b->stream));
+    RP_HIP(rp::launch_extrema_batch(b->view, d_lo, d_hi, k, v, t, b->stream));
     return RP_OK;
 }
 
-// ---- the integrals over a window and their first derivatives (trajectory.hip) ----
-namespace {
-const double *const kNoSpline[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-double *const kNoSplineBar[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-const double *const kNoGradient[4] = {nullptr, nullptr, nullptr, nullptr};
-
-// the integrals entries: sizes, and the 16-byte alignment of every n x k array given (null: not given); `any`: whether an output is
-int check_integrals(const char *who, size_t n, size_t k, const void *const per_query[], int count, bool any)
-{
-    const int st = check_sizes(who, n, k);
-    if (st != RP_OK) return st;
-    if (!any) return fail(RP_ERR_INVALID, "%s: no output asked for", who);
-    for (int i = 0; i < count; ++i)
-        if (misaligned16(per_query[i])) return fail(RP_ERR_INVALID, "%s: every n x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
-    return RP_OK;
-}
-
-int check_integrals_forward(const char *who, size_t n, size_t k, const double *d_lo, const double *d_hi, double *const d_value[4])
-{
-    const void *const per_query[] = {d_lo, d_hi, d_value ? d_value[0] : nullptr, d_value ? d_value[1] : nullptr, d_value ? d_value[2] : nullptr,
-                                     d_value ? d_value[3] : nullptr};
-    return check_integrals(who, n, k, per_query, 6, per_query[2] || per_query[3] || per_query[4] || per_query[5]);
-}
-}  // namespace
-
+// the integrals over a window and their first derivatives
 int rp_trajectory_integrals(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                             double *const d_value[4])
 {
-    int st = check_spline(__func__, device, d_spline);
-    if (st == RP_OK) st = check_integrals_forward(__func__, n, k, d_lo, d_hi, d_value);
+    double *const *v = d_value ? d_value : kNoOutputs;
+    const int st = check_stateless(__func__, device, d_spline, n, k, nullptr, nullptr, {d_lo, d_hi, v[0], v[1], v[2], v[3]}, any_of(v, 4));
     if (st != RP_OK) return st;
     RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_integrals(n, k, d_spline, d_lo, d_hi, d_value, (hipStream_t)stream));
+    RP_HIP(rp::launch_integrals(n, k, d_spline, d_lo, d_hi, v, (hipStream_t)stream));
     return RP_OK;
 }
 
 int rp_trajectory_integrals_vjp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                                 const double *const d_g[4], double *const d_spline_bar[8], double *d_lo_bar, double *d_hi_bar)
 {
-    const double *const *g = d_g ? d_g : kNoGradient;
-    double *const *bars = d_spline_bar ? d_spline_bar : kNoSplineBar;
-    const void *const per_query[] = {d_lo, d_hi, g[0], g[1], g[2], g[3], d_lo_bar, d_hi_bar};
-    bool any = d_lo_bar || d_hi_bar;
-    for (int f = 0; f < 8; ++f) any = any || bars[f];
-    int st = check_spline(__func__, device, d_spline);
-    if (st == RP_OK) st = check_integrals(__func__, n, k, per_query, 8, any);
+    const double *const *g = d_g ? d_g : kNoInputs;
+    double *const *bars = d_spline_bar ? d_spline_bar : kNoOutputs;
+    const int st = check_stateless(__func__, device, d_spline, n, k, nullptr, nullptr, {d_lo, d_hi, g[0], g[1], g[2], g[3], d_lo_bar, d_hi_bar},
+                                   d_lo_bar || d_hi_bar || any_of(bars, 8));
     if (st != RP_OK) return st;
     RP_HIP(hipSetDevice(device));
     RP_HIP(rp::launch_integrals_vjp(n, k, d_spline, d_lo, d_hi, g, bars, d_lo_bar, d_hi_bar, (hipStream_t)stream));
@@ -1185,23 +1134,23 @@ int rp_trajectory_integrals_vjp(int device, void *stream, size_t n, size_t k, co
 int rp_trajectory_integrals_jvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                                 const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot, double *const d_value_dot[4])
 {
-    double *const *out = d_value_dot ? d_value_dot : kNoExtrema;
-    const void *const per_query[] = {d_lo, d_hi, d_lo_dot, d_hi_dot, out[0], out[1], out[2], out[3]};
-    int st = check_spline(__func__, device, d_spline);
-    if (st == RP_OK) st = check_integrals(__func__, n, k, per_query, 8, out[0] || out[1] || out[2] || out[3]);
+    double *const *out = d_value_dot ? d_value_dot : kNoOutputs;
+    const int st = check_stateless(__func__, device, d_spline, n, k, nullptr, nullptr, {d_lo, d_hi, d_lo_dot, d_hi_dot, out[0], out[1], out[2], out[3]},
+                                   any_of(out, 4));
     if (st != RP_OK) return st;
     RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_integrals_jvp(n, k, d_spline, d_lo, d_hi, d_spline_dot ? d_spline_dot : kNoSpline, d_lo_dot, d_hi_dot, out, (hipStream_t)stream));
+    RP_HIP(rp::launch_integrals_jvp(n, k, d_spline, d_lo, d_hi, d_spline_dot ? d_spline_dot : kNoInputs, d_lo_dot, d_hi_dot, out, (hipStream_t)stream));
     return RP_OK;
 }
 
 int rp_batch_integrals_device(rp_batch *b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4])
 {
     if (!b) return fail(RP_ERR_INVALID, "null batch handle");
-    const int st = check_integrals_forward(__func__, b->view.n, k, d_lo, d_hi, d_value);
+    double *const *v = d_value ? d_value : kNoOutputs;
+    const int st = check_queries(__func__, b->view.n, k, nullptr, nullptr, {d_lo, d_hi, v[0], v[1], v[2], v[3]}, any_of(v, 4));
     if (st != RP_OK) return st;
     RP_NEED_STATE(b);
-    RP_HIP(rp::launch_integrals_batch(b->view, d_lo, d_hi, k, d_value, b->stream));
+    RP_HIP(rp::launch_integrals_batch(b->view, d_lo, d_hi, k, v, b->stream));
     return RP_OK;
 }
 

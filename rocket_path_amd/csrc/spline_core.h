@@ -1,8 +1,10 @@
 // spline_core.h -- one problem's two-segment spline as the kernels that evaluate it see it (internal; trajectory.hip): the eight
-// numbers, where they come from, and the constants of a segment's cubic
+// numbers, where they come from, the constants of a segment's cubic
 //     acc0 = 6 (x1 - x0) / h^2 - (4 va + 2 vb) / h        jrk0 = 2 (vb - va) / h^2 - 2 acc0 / h
-// with the divisions as multiplications by one refined reciprocal per segment (rcp_: IEEE 1/x).  Every kernel that draws or
-// evaluates a spline stages through these: same statements, same bits.
+// with the divisions as multiplications by one refined reciprocal per segment (rcp_: IEEE 1/x), and the cubic itself
+//     pos = x0 + (va + (acc0 + jrk0 s / 3) s / 2) s       vel = va + (acc0 + jrk0 s / 2) s       acc = acc0 + jrk0 s
+// Every kernel that draws or evaluates a spline stages and evaluates through these: same statements, same bits (the build has
+// -ffp-contract=off: the operand order written here is the arithmetic).
 #pragma once
 
 #include "ip_core.h"
@@ -12,7 +14,17 @@ namespace rp {
 
 namespace {
 
-struct Spline8 { const double *p[8]; };      // pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1
+// N pointers that travel together as one kernel argument (null: not given)
+template <class T, int N> struct Table { T *p[N]; };
+
+template <int N, class T> Table<T, N> table_of(T *const *t)
+{
+    Table<T, N> x;
+    for (int f = 0; f < N; ++f) x.p[f] = t[f];
+    return x;
+}
+
+using Spline8 = Table<const double, 8>;      // pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1
 
 __device__ __forceinline__ double quiet_nan() { return __builtin_nan(""); }
 
@@ -83,6 +95,16 @@ __device__ __forceinline__ void segment_constants(double x0, double x1, double v
     acc0 = (x1 - x0) * (6.0 * ih2) - (va * 4.0 + vb * 2.0) * ih;
     jrk0 = (vb - va) * (2.0 * ih2) - acc0 * (2.0 * ih);
 }
+
+// the cubic of one segment at local time s, in the constants above
+__device__ __forceinline__ double cubic_pos(double x0, double va, double acc0, double jrk0, double s)
+{
+    return x0 + (va + (acc0 + jrk0 * (s * (1.0 / 3.0))) * (s * 0.5)) * s;
+}
+
+__device__ __forceinline__ double cubic_vel(double va, double acc0, double jrk0, double s) { return va + (acc0 + jrk0 * (s * 0.5)) * s; }
+
+__device__ __forceinline__ double cubic_acc(double acc0, double jrk0, double s) { return acc0 + jrk0 * s; }
 
 }  // namespace
 

@@ -1,39 +1,39 @@
-// trajectory.hip -- a solved two-segment spline evaluated at the caller's own times, and the first derivatives of that
-// evaluation, gfx950: rp_trajectory_eval, rp_trajectory_eval_vjp, rp_trajectory_eval_jvp and rp_batch_trajectory_device
-// (include/rp_batch.h); and the derivative of the reverse rule along a direction, rp_trajectory_eval_hvp
-// (k_trajectory_hvp); and the plot data, the same spline on the reference's fixed grid: rp_batch_sample,
-// rp_batch_sample_device, rp_batch_sample_range (k_sample, k_sample_records, at the end of the kernels); and the inverse of the
-// evaluation, the first time the spline reaches a level: rp_trajectory_crossing, rp_batch_crossing_device (k_crossing, k_batch_crossing;
-// DESIGN.md section 14); and the extreme position and velocity over a window of times: rp_trajectory_extrema, rp_batch_extrema_device
-// (k_extrema, k_batch_extrema); and the integrals of pos, |vel|, vel^2 and acc^2 over such a window with their first
-// derivatives: rp_trajectory_integrals, _vjp, _jvp, rp_batch_integrals_device (k_integrals, k_batch_integrals, k_jvp_integrals,
-// k_vjp_integrals).
+// trajectory.hip -- what can be asked of a solved two-segment spline, gfx950.  The families, in the order of the file:
+//   evaluation at the caller's own times       k_trajectory_eval, k_batch_trajectory            DESIGN.md section 13
+//   ... its first derivatives                  k_trajectory_jvp, k_trajectory_vjp               section 13
+//   ... the reverse rule along a direction     k_trajectory_hvp                                 section 17
+//   the first time a level is reached          k_crossing, k_batch_crossing                     section 14
+//   extreme pos and vel over a window          k_extrema, k_batch_extrema                       section 15
+//   integrals over a window                    k_integrals, k_batch_integrals                   section 16
+//   ... their first derivatives                k_jvp_integrals, k_vjp_integrals                 section 16
+//   plot data on the reference's fixed grid    k_sample, k_sample_records
+// The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
+// rp_batch_integrals_device and rp_batch_sample*; the launchers are at the end of the file.
 //
 // Per problem the spline is (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1) -- this order wherever eight pointers travel
 // together -- and the k query times tau[i, j] (row-major n x k) count from the start of segment 0.  A query with tau < duration0
 // lies in segment 0, (pos0, vel0) -> (pos1, vel1) over h = duration0 at s = tau; every other one in segment 1, (pos1, vel1) ->
 // (pos2, vel2) over h = duration1 at s = tau - duration0.  The cubic is the one the reference draws (drawSegment,
-// onedpath_ip.cpp:1065-1088), with the constants of spline_core.h:
-//     acc0 = 6 (x1 - x0) / h^2 - (4 va + 2 vb) / h        jrk0 = 2 (vb - va) / h^2 - 2 acc0 / h
-//     pos = x0 + (va + (acc0 + jrk0 s / 3) s / 2) s       vel = va + (acc0 + jrk0 s / 2) s       acc = acc0 + jrk0 s
-// No clamping: outside [0, duration0 + duration1] the end segments' cubics continue.  A problem with a duration that is not finite
-// or not > 0 gets NaN everywhere (its constants are NaN); a NaN tau gives NaN for that query.
+// onedpath_ip.cpp:1065-1088), constants and expressions in spline_core.h.  No clamping: outside [0, duration0 + duration1] the end
+// segments' cubics continue.  A problem with a duration that is not finite or not > 0 gets NaN everywhere (its constants are NaN); a
+// NaN tau gives NaN for that query.
 //
-// All three kernels move 8-32 B per query and ~128 B per problem and do ~20 flops per query: streaming kernels, built the way k_sample
-// is.  A block takes P consecutive problems per trip (P a function of k alone, P k ~ 4096 queries); its first P threads
-// read one problem's eight parameters each, do the two reciprocals (rcp_) and leave the per-segment constants and
-// duration0 in LDS; then the block streams.  The grid is capped and strides over the trips.
-//   k_trajectory_eval / k_trajectory_jvp / k_batch_trajectory: pointwise.  The block's P k queries are consecutive elements of
-//     tau (P is even, so a trip starts on a 16-byte boundary): each thread takes two at a time -- one 16-byte load, one 16-byte
-//     nontemporal store per wanted output -- and finds each query's problem by carrying (problem, column) along, without a division.
-//   k_trajectory_vjp: a problem's k queries reduce to nine sums (four per segment, and the sum of tau_bar over segment 1).  A group
-//     of G lanes (a power of two <= 64, from k alone) owns one problem at a time: lane l adds queries l, l + G, l + 2 G, ... (pairs
-//     2 l, 2 l + 1, ... as 16-byte vectors when k is even -- every row then starts on a 16-byte boundary; single elements when k is
-//     odd) in that order into its own nine sums, the lanes combine by an xor butterfly (a + b == b + a bit for bit: every lane holds
-//     the same sums), and lane 0 runs the chain rule once.  The order of every addition is a function of k: a problem's gradient is
-//     the same bits in any batch, in any block, in every run.  No atomics.
+// The shape every family but the plot data shares.  The kernels move 8-32 B per query and ~128 B per problem and do tens of flops per
+// query: streaming kernels.  A block takes P consecutive problems per trip (P a function of k alone, P k ~ 4096 queries); its first
+// P threads read one problem each, do the two reciprocals (rcp_) and leave what the queries need in LDS; a barrier; the block works
+// through the trip's queries; a barrier.  The grid is capped and strides over the trips.  That loop is for_each_trip.
+//   The pointwise kernels (everything but the two reverse rules): the block's P k queries are consecutive elements of tau (P is even,
+//     so a trip starts on a 16-byte boundary): each thread takes two at a time -- one 16-byte load, one 16-byte nontemporal store per
+//     wanted output -- and finds each query's problem by carrying (problem, column) along, without a division (stream_pairs).
+//   The reverse rules (k_trajectory_vjp, k_trajectory_hvp, k_vjp_integrals): a problem's k queries reduce to N sums (reduce_rows).  A
+//     group of G lanes (a power of two <= 64, from k alone) owns one problem at a time: lane l adds queries l, l + G, l + 2 G, ...
+//     (pairs 2 l, 2 l + 1, ... as 16-byte vectors when k is even -- every row then starts on a 16-byte boundary; single elements
+//     when k is odd) in that order into its own sums, the lanes combine by an xor butterfly (a + b == b + a bit for bit: every lane
+//     holds the same sums), and lane 0 runs the chain rule once and leaves the problem's eight gradients in LDS (route_bars), from
+//     where the block's first P threads write them (write_bars).  The order of every addition is a function of k: a problem's
+//     gradient is the same bits in any batch, in any block, in every run.  No atomics.
 // A null output is not written, a null gradient or tangent is not read and counts as zeros -- as the VALUE zero in the same
-// expression, so that null and explicit zeros give the same bits.
+// expression, so that null and explicit zeros give the same bits; a null window end is -inf or +inf (load_window).
 #include "ip_kernels.h"
 
 #include "../../include/rp_batch.h"
@@ -52,11 +52,28 @@ constexpr size_t kTrajTrip = 4096;       // queries per trip a block aims at
 
 typedef double v2 __attribute__((ext_vector_type(2)));
 
-struct SplineBar8 { double *p[8]; };
+using SplineBar8 = Table<double, 8>;           // the eight gradients, in Spline8's order
+using Out4 = Table<double, 4>;                 // pos_min, pos_max, vel_min, vel_max | pos_int, distance, vel_sq, acc_sq
+using In4 = Table<const double, 4>;
 
 __device__ __forceinline__ int problems_here(size_t n, size_t p_first, int P)
 {
     return (int)(n - p_first < (size_t)P ? n - p_first : (size_t)P);
+}
+
+// The trips of a block: stage(q, i) by the first `here` threads (problem i into place q of the block's LDS), then body(p_first, here)
+// by all of them, between two barriers.
+template <class Stage, class Body> __device__ __forceinline__ void for_each_trip(size_t n, int P, Stage stage, Body body)
+{
+    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
+    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
+        const size_t p_first = trip * (size_t)P;
+        const int here = problems_here(n, p_first, P);
+        if ((int)threadIdx.x < here) stage((int)threadIdx.x, p_first + threadIdx.x);
+        __syncthreads();
+        body(p_first, here);
+        __syncthreads();
+    }
 }
 
 // The streaming loop of the pointwise kernels: the block's `here` x k queries, consecutive from element p_first * k (even), two per
@@ -102,9 +119,9 @@ __device__ __forceinline__ void eval_query(const EvalLds &L, int q, double tau, 
     const int seg = !(tau < d0);
     const double s = seg ? tau - d0 : tau;
     const double x0 = L.c[seg][0][q], va = L.c[seg][1][q], acc0 = L.c[seg][2][q], jrk0 = L.c[seg][3][q];
-    pos = x0 + (va + (acc0 + jrk0 * (s * (1.0 / 3.0))) * (s * 0.5)) * s;
-    vel = va + (acc0 + jrk0 * (s * 0.5)) * s;
-    acc = acc0 + jrk0 * s;
+    pos = cubic_pos(x0, va, acc0, jrk0, s);
+    vel = cubic_vel(va, acc0, jrk0, s);
+    acc = cubic_acc(acc0, jrk0, s);
 }
 
 __device__ __forceinline__ void store_pair(double *out, size_t at, double a, double b, bool two)
@@ -129,17 +146,22 @@ __device__ __forceinline__ void load_pair(const double *in, size_t at, bool two,
     }
 }
 
+// a window's two ends, for a pair or a single query; a null array: the whole spline
+__device__ __forceinline__ void load_window(const double *lo, const double *hi, size_t at, bool two, double &la, double &lb, double &ha, double &hb)
+{
+    const double inf = __builtin_inf();
+    la = lb = -inf;
+    ha = hb = inf;
+    if (lo) load_pair(lo, at, two, la, lb);
+    if (hi) load_pair(hi, at, two, ha, hb);
+}
+
 template <class Stage>
 __device__ __forceinline__ void eval_trips(const Stage &stage, size_t n, size_t k, int P, const double *__restrict__ tau,
                                            double *__restrict__ pos, double *__restrict__ vel, double *__restrict__ acc)
 {
     __shared__ EvalLds L;
-    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
-    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
-        const size_t p_first = trip * (size_t)P;
-        const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) stage_eval(L, threadIdx.x, stage.load(p_first + threadIdx.x));
-        __syncthreads();
+    for_each_trip(n, P, [&](int q, size_t i) { stage_eval(L, q, stage.load(i)); }, [&](size_t p_first, int here) {
         const size_t e_first = p_first * k;
         stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
             double ta, tb, pa, va, aa, pb, vb, ab;
@@ -150,8 +172,7 @@ __device__ __forceinline__ void eval_trips(const Stage &stage, size_t n, size_t 
             if (vel) store_pair(vel, e_first + e, va, vb, two);
             if (acc) store_pair(acc, e_first + e, aa, ab, two);
         });
-        __syncthreads();
-    }
+    });
 }
 
 __global__ void __launch_bounds__(kTrajBlock)
@@ -186,17 +207,22 @@ __device__ __forceinline__ void segment_tangents(double dx, double va, double vb
     jrk0d = (vbd - vad) * (2.0 * ih2) - (vb - va) * (4.0 * ih3) * hd - acc0d * (2.0 * ih) + acc0 * (2.0 * ih2) * hd;
 }
 
-// one problem's constants and their tangents into LDS
-__device__ __forceinline__ void stage_tangents(JvpLds &L, int q, size_t i, const Spline8 &s, const Spline8 &dot)
+
+// One problem's constants and their tangents along a direction, one segment at a time (a loop the compiler is told to keep): the
+// sixteen loads of a problem and its tangents, taken at once, cost the registers of two waves per SIMD.  pos1, vel1 and their tangents
+// are asked for in both passes (same thread, same address: the second is a cache hit).  store(seg, segment) puts a segment's numbers
+// where the kernel keeps them; the durations and their tangents come back.
+struct DirectedSegment { double x0, va, vb, dx, acc0, jrk0, ih, x0d, vad, vbd, dxd, acc0d, jrk0d, hd; };
+struct DirectedDurations { double t0, t1, t0d, t1d; };
+
+template <class Store> __device__ __forceinline__ DirectedDurations stage_directed(size_t i, const Spline8 &s, const Spline8 &dot, Store store)
 {
-    // one segment at a time (a loop the compiler is told to keep): the sixteen loads of a problem and its tangents, taken at
-    // once, cost the registers of two waves per SIMD.  pos1, vel1 and their tangents are asked for in both passes (same thread,
-    // same address: the second is a cache hit)
-    double t0 = s.p[6][i], t1 = s.p[7][i];
-    check_durations(t0, t1);
-    const double t0d = dot.p[6] ? dot.p[6][i] : 0.0, t1d = dot.p[7] ? dot.p[7][i] : 0.0;
-    L.d0[q] = t0;
-    L.d0_dot[q] = t0d;
+    DirectedDurations d;
+    d.t0 = s.p[6][i];
+    d.t1 = s.p[7][i];
+    check_durations(d.t0, d.t1);
+    d.t0d = dot.p[6] ? dot.p[6][i] : 0.0;
+    d.t1d = dot.p[7] ? dot.p[7][i] : 0.0;
 #pragma nounroll
     for (int seg = 0; seg < 2; ++seg) {
         const double *pva = seg ? s.p[5] : s.p[3], *pvb = seg ? s.p[4] : s.p[5];      // vel0, vel1 | vel1, vel2
@@ -205,13 +231,25 @@ __device__ __forceinline__ void stage_tangents(JvpLds &L, int q, size_t i, const
         const double *px0d = seg ? dot.p[1] : dot.p[0], *px1d = seg ? dot.p[2] : dot.p[1];
         const double x0 = px0[i], x1 = px1[i], va = pva ? pva[i] : 0.0, vb = pvb ? pvb[i] : 0.0;
         const double x0d = px0d ? px0d[i] : 0.0, x1d = px1d ? px1d[i] : 0.0, vad = pvad ? pvad[i] : 0.0, vbd = pvbd ? pvbd[i] : 0.0;
-        const double ih = rcp_<double>(seg ? t1 : t0);
+        const double ih = rcp_<double>(seg ? d.t1 : d.t0), hd = seg ? d.t1d : d.t0d;
+        const double dx = x1 - x0, dxd = x1d - x0d;
         double acc0, jrk0, acc0d, jrk0d;
         segment_constants(x0, x1, va, vb, ih, acc0, jrk0);
-        segment_tangents(x1 - x0, va, vb, acc0, ih, x1d - x0d, vad, vbd, seg ? t1d : t0d, acc0d, jrk0d);
-        L.c[seg][0][q] = x0; L.c[seg][1][q] = va; L.c[seg][2][q] = acc0; L.c[seg][3][q] = jrk0;
-        L.t[seg][0][q] = x0d; L.t[seg][1][q] = vad; L.t[seg][2][q] = acc0d; L.t[seg][3][q] = jrk0d;
+        segment_tangents(dx, va, vb, acc0, ih, dxd, vad, vbd, hd, acc0d, jrk0d);
+        store(seg, DirectedSegment{x0, va, vb, dx, acc0, jrk0, ih, x0d, vad, vbd, dxd, acc0d, jrk0d, hd});
     }
+    return d;
+}
+
+__device__ __forceinline__ DirectedDurations stage_tangents(JvpLds &L, int q, size_t i, const Spline8 &s, const Spline8 &dot)
+{
+    const DirectedDurations d = stage_directed(i, s, dot, [&](int seg, const DirectedSegment &g) {
+        L.c[seg][0][q] = g.x0; L.c[seg][1][q] = g.va; L.c[seg][2][q] = g.acc0; L.c[seg][3][q] = g.jrk0;
+        L.t[seg][0][q] = g.x0d; L.t[seg][1][q] = g.vad; L.t[seg][2][q] = g.acc0d; L.t[seg][3][q] = g.jrk0d;
+    });
+    L.d0[q] = d.t0;
+    L.d0_dot[q] = d.t0d;
+    return d;
 }
 
 __global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(8)))      // 64 VGPRs: without the hint the allocator stops at 65
@@ -219,12 +257,7 @@ k_trajectory_jvp(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const
                  double *__restrict__ pos_dot, double *__restrict__ vel_dot, double *__restrict__ acc_dot)
 {
     __shared__ JvpLds L;
-    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
-    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
-        const size_t p_first = trip * (size_t)P;
-        const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) stage_tangents(L, threadIdx.x, p_first + threadIdx.x, stage.s, dot);
-        __syncthreads();
+    for_each_trip(n, P, [&](int q, size_t i) { stage_tangents(L, q, i, stage.s, dot); }, [&](size_t p_first, int here) {
         const size_t e_first = p_first * k;
         auto query = [&](int q, double ta, double td, double &pd, double &vd, double &ad) {
             const double d0 = L.d0[q];
@@ -232,10 +265,10 @@ k_trajectory_jvp(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const
             const double s = seg ? ta - d0 : ta, sd = seg ? td - L.d0_dot[q] : td;
             const double va = L.c[seg][1][q], acc0 = L.c[seg][2][q], jrk0 = L.c[seg][3][q];
             const double x0d = L.t[seg][0][q], vad = L.t[seg][1][q], acc0d = L.t[seg][2][q], jrk0d = L.t[seg][3][q];
-            const double vel = va + (acc0 + jrk0 * (s * 0.5)) * s, acc = acc0 + jrk0 * s;
-            pd = x0d + (vad + (acc0d + jrk0d * (s * (1.0 / 3.0))) * (s * 0.5)) * s + vel * sd;
-            vd = vad + (acc0d + jrk0d * (s * 0.5)) * s + acc * sd;
-            ad = acc0d + jrk0d * s + jrk0 * sd;
+            const double vel = cubic_vel(va, acc0, jrk0, s), acc = cubic_acc(acc0, jrk0, s);
+            pd = cubic_pos(x0d, vad, acc0d, jrk0d, s) + vel * sd;
+            vd = cubic_vel(vad, acc0d, jrk0d, s) + acc * sd;
+            ad = cubic_acc(acc0d, jrk0d, s) + jrk0 * sd;
         };
         stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
             double ta, tb, da = 0.0, db = 0.0, pa, va, aa, pb, vb, ab;
@@ -247,8 +280,7 @@ k_trajectory_jvp(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const
             if (vel_dot) store_pair(vel_dot, e_first + e, va, vb, two);
             if (acc_dot) store_pair(acc_dot, e_first + e, aa, ab, two);
         });
-        __syncthreads();
-    }
+    });
 }
 
 // ---- reverse mode ----
@@ -296,79 +328,93 @@ __device__ __forceinline__ void stage_vjp(VjpLds &L, int q, Knots kn)
     L.d0[q] = kn.t0;
 }
 
+// The reduction of the reverse rules: a group of G lanes per problem; row(q, at, two, sums) adds the pair of queries at element `at`
+// (two) or the single one there to the lane's N sums, the lanes combine, and lane 0 gets finish(q, sums).  `two` is a literal in
+// each of the two loops: a row body is compiled once for pairs and once for single elements.
+// (The sums sit in a struct: a bare one-dimensional array the compiler turns into one wide vector register before it takes it apart,
+// and k_vjp_integrals then carries some fifty register copies more per problem.)
+template <int N> struct LaneSums { double s[N]; };
+
+template <int N, class Row, class Finish>
+__device__ __forceinline__ void reduce_rows(int G, int here, size_t p_first, size_t k, Row row, Finish finish)
+{
+    const int groups = kTrajBlock / G, group = (int)threadIdx.x / G, lane = (int)threadIdx.x & (G - 1);
+    for (int q = group; q < here; q += groups) {
+        const size_t first = (p_first + (size_t)q) * k;
+        LaneSums<N> lane_sums = {};
+        double (&sums)[N] = lane_sums.s;
+        if ((k & 1) == 0) {      // k even: the row starts on a 16-byte boundary
+            const size_t units = k >> 1;
+            for (size_t u = lane; u < units; u += G) row(q, first + 2 * u, true, sums);
+        } else {
+            for (size_t u = lane; u < k; u += G) row(q, first + u, false, sums);
+        }
+        // the group's lanes combine: after the butterfly every lane holds the same N sums
+        for (int m = 1; m < G; m <<= 1) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) sums[i] += __shfl_xor(sums[i], m, 64);
+        }
+        if (lane == 0) finish(q, sums);
+    }
+}
+
+// Segment 0's results go to (pos0, pos1, vel0, vel1), segment 1's to (pos1, pos2, vel1, vel2), in the pointer table's order; h0 and h1
+// are the duration rows: the segments' own h and what the queries put on them.
+__device__ __forceinline__ void route_bars(double (&bar)[8][kTrajProblems], int q, const SegmentBar &a, const SegmentBar &b, double h0, double h1)
+{
+    bar[0][q] = a.x0; bar[1][q] = a.x1 + b.x0; bar[2][q] = b.x1;
+    bar[3][q] = a.va; bar[4][q] = b.vb; bar[5][q] = a.vb + b.va;
+    bar[6][q] = h0; bar[7][q] = h1;
+}
+
+// once every group is through: the block's first `here` threads write their problem's wanted gradients
+__device__ __forceinline__ void write_bars(const double (&bar)[8][kTrajProblems], const SplineBar8 &out, size_t p_first, int here)
+{
+    __syncthreads();
+    if ((int)threadIdx.x < here) {
+#pragma unroll
+        for (int f = 0; f < 8; ++f)
+            if (out.p[f]) out.p[f][p_first + threadIdx.x] = bar[f][threadIdx.x];
+    }
+}
+
+// nine sums: S_x, S_v, S_a, S_j of segment 0, of segment 1, and the sum of tau_bar over segment 1
 __global__ void __launch_bounds__(kTrajBlock)
 k_trajectory_vjp(FromArrays stage, size_t n, size_t k, int P, int G, const double *__restrict__ tau, const double *__restrict__ g_pos,
                  const double *__restrict__ g_vel, const double *__restrict__ g_acc, SplineBar8 bar, double *__restrict__ tau_bar)
 {
     __shared__ VjpLds L;
-    const int groups = kTrajBlock / G, group = (int)threadIdx.x / G, lane = (int)threadIdx.x & (G - 1);
-    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
-    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
-        const size_t p_first = trip * (size_t)P;
-        const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) stage_vjp(L, threadIdx.x, stage.load(p_first + threadIdx.x));
-        __syncthreads();
-        for (int q = group; q < here; q += groups) {
-            const size_t row = (p_first + (size_t)q) * k;
+    for_each_trip(n, P, [&](int q, size_t i) { stage_vjp(L, q, stage.load(i)); }, [&](size_t p_first, int here) {
+        auto query = [&](int q, double ta, double gp, double gv, double ga, double *S) -> double {
             const double d0 = L.d0[q];
-            double S[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, T1 = 0.0;      // this lane's nine sums
-            auto query = [&](double ta, double gp, double gv, double ga) -> double {
-                const bool seg = !(ta < d0);
-                const double s = seg ? ta - d0 : ta;
-                const double va = L.c[seg][0][q], acc0 = L.c[seg][3][q], jrk0 = L.c[seg][4][q];
-                const double vel = va + (acc0 + jrk0 * (s * 0.5)) * s, acc = acc0 + jrk0 * s;
-                const double tb = gp * vel + gv * acc + ga * jrk0;
-                const double h2 = s * (s * 0.5), h3 = h2 * (s * (1.0 / 3.0));
-                const double w0 = gp, w1 = gp * s + gv, w2 = gp * h2 + gv * s + ga, w3 = gp * h3 + gv * h2 + ga * s;
-                S[0][0] += seg ? 0.0 : w0; S[0][1] += seg ? 0.0 : w1; S[0][2] += seg ? 0.0 : w2; S[0][3] += seg ? 0.0 : w3;
-                S[1][0] += seg ? w0 : 0.0; S[1][1] += seg ? w1 : 0.0; S[1][2] += seg ? w2 : 0.0; S[1][3] += seg ? w3 : 0.0;
-                T1 += seg ? tb : 0.0;
-                return tb;
-            };
-            if ((k & 1) == 0) {      // k even: the row starts on a 16-byte boundary
-                const size_t units = k >> 1;
-                for (size_t u = lane; u < units; u += G) {
-                    const size_t at = row + 2 * u;
-                    double ta, tb, pa = 0.0, pb = 0.0, va = 0.0, vb = 0.0, aa = 0.0, ab = 0.0;
-                    load_pair(tau, at, true, ta, tb);
-                    if (g_pos) load_pair(g_pos, at, true, pa, pb);
-                    if (g_vel) load_pair(g_vel, at, true, va, vb);
-                    if (g_acc) load_pair(g_acc, at, true, aa, ab);
-                    const double ba = query(ta, pa, va, aa);
-                    const double bb = query(tb, pb, vb, ab);
-                    if (tau_bar) store_pair(tau_bar, at, ba, bb, true);
-                }
-            } else {
-                for (size_t u = lane; u < k; u += G) {
-                    const size_t at = row + u;
-                    const double b = query(tau[at], g_pos ? g_pos[at] : 0.0, g_vel ? g_vel[at] : 0.0, g_acc ? g_acc[at] : 0.0);
-                    if (tau_bar) tau_bar[at] = b;
-                }
-            }
-            // the group's lanes combine: after the butterfly every lane holds the same nine sums
-            for (int m = 1; m < G; m <<= 1) {
-#pragma unroll
-                for (int seg = 0; seg < 2; ++seg)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) S[seg][c] += __shfl_xor(S[seg][c], m, 64);
-                T1 += __shfl_xor(T1, m, 64);
-            }
-            if (lane == 0) {
-                const SegmentBar a = segment_chain(L, 0, q, S[0][0], S[0][1], S[0][2], S[0][3]);
-                const SegmentBar b = segment_chain(L, 1, q, S[1][0], S[1][1], S[1][2], S[1][3]);
-                L.bar[0][q] = a.x0; L.bar[1][q] = a.x1 + b.x0; L.bar[2][q] = b.x1;
-                L.bar[3][q] = a.va; L.bar[4][q] = b.vb; L.bar[5][q] = a.vb + b.va;
-                L.bar[6][q] = a.h - T1; L.bar[7][q] = b.h;
-            }
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < here) {
-#pragma unroll
-            for (int f = 0; f < 8; ++f)
-                if (bar.p[f]) bar.p[f][p_first + threadIdx.x] = L.bar[f][threadIdx.x];
-        }
-        __syncthreads();
-    }
+            const bool seg = !(ta < d0);
+            const double s = seg ? ta - d0 : ta;
+            const double va = L.c[seg][0][q], acc0 = L.c[seg][3][q], jrk0 = L.c[seg][4][q];
+            const double vel = cubic_vel(va, acc0, jrk0, s), acc = cubic_acc(acc0, jrk0, s);
+            const double tb = gp * vel + gv * acc + ga * jrk0;
+            const double h2 = s * (s * 0.5), h3 = h2 * (s * (1.0 / 3.0));
+            const double w0 = gp, w1 = gp * s + gv, w2 = gp * h2 + gv * s + ga, w3 = gp * h3 + gv * h2 + ga * s;
+            S[0] += seg ? 0.0 : w0; S[1] += seg ? 0.0 : w1; S[2] += seg ? 0.0 : w2; S[3] += seg ? 0.0 : w3;
+            S[4] += seg ? w0 : 0.0; S[5] += seg ? w1 : 0.0; S[6] += seg ? w2 : 0.0; S[7] += seg ? w3 : 0.0;
+            S[8] += seg ? tb : 0.0;
+            return tb;
+        };
+        reduce_rows<9>(G, here, p_first, k, [&](int q, size_t at, bool two, double *S) {
+            double ta, tb, pa = 0.0, pb = 0.0, va = 0.0, vb = 0.0, aa = 0.0, ab = 0.0;
+            load_pair(tau, at, two, ta, tb);
+            if (g_pos) load_pair(g_pos, at, two, pa, pb);
+            if (g_vel) load_pair(g_vel, at, two, va, vb);
+            if (g_acc) load_pair(g_acc, at, two, aa, ab);
+            const double ba = query(q, ta, pa, va, aa, S);
+            const double bb = two ? query(q, tb, pb, vb, ab, S) : ba;
+            if (tau_bar) store_pair(tau_bar, at, ba, bb, two);
+        }, [&](int q, const double *S) {
+            const SegmentBar a = segment_chain(L, 0, q, S[0], S[1], S[2], S[3]);
+            const SegmentBar b = segment_chain(L, 1, q, S[4], S[5], S[6], S[7]);
+            route_bars(L.bar, q, a, b, a.h - S[8], b.h);
+        });
+        write_bars(L.bar, bar, p_first, here);
+    });
 }
 
 // ---- second order: the derivative of the reverse rule along a direction (rp_trajectory_eval_hvp) ----
@@ -382,9 +428,9 @@ k_trajectory_vjp(FromArrays stage, size_t n, size_t k, int P, int G, const doubl
 //     va_bar_dot = S_vd - 4 A_d / h + 4 A hd / h^2 - 2 S_jd / h^2 + 4 S_j hd / h^3
 //     vb_bar_dot = -2 A_d / h + 2 A hd / h^2 + 2 S_jd / h^2 - 4 S_j hd / h^3
 //     h_bar_dot = A_d c1 + A c1d + S_jd c2 + S_j c2d      (c1, c2 the two brackets of h_bar, c1d, c2d their derivatives)
-// routed as the reverse rule's, duration0 taking off the sum of tau_bar_dot over segment 1.  k_trajectory_vjp's reduction -- the same
-// group of G lanes per problem, the same lane stride, the same butterfly -- over eleven sums: S_a and S_j of each segment (S_x and S_v are in
-// no derivative: they enter the reverse rule linearly, with constant coefficients), the six dotted ones and that sum.
+// routed as the reverse rule's, duration0 taking off the sum of tau_bar_dot over segment 1.  reduce_rows over eleven sums: S_a and S_j
+// of each segment (S_x and S_v are in no derivative: they enter the reverse rule linearly, with constant coefficients), the six dotted
+// ones and that sum.
 struct HvpLds {
     double c[2][6][kTrajProblems];      // per segment: va, vb, x1 - x0, acc0, jrk0, 1 / h ...
     double t[2][6][kTrajProblems];      // ... and along the direction: vad, vbd, x1d - x0d, acc0d, jrk0d, hd
@@ -395,32 +441,16 @@ struct HvpLds {
 // one problem's constants and their derivatives along the direction into LDS
 __device__ __forceinline__ void stage_hvp(HvpLds &L, int q, size_t i, const Spline8 &s, const Spline8 &dot)
 {
-    // one segment at a time, as stage_tangents (registers)
-    double t0 = s.p[6][i], t1 = s.p[7][i];
-    check_durations(t0, t1);
-    const double t0d = dot.p[6] ? dot.p[6][i] : 0.0, t1d = dot.p[7] ? dot.p[7][i] : 0.0;
-    L.d0[q] = t0;
-    L.d0_dot[q] = t0d;
-#pragma nounroll
-    for (int seg = 0; seg < 2; ++seg) {
-        const double *pva = seg ? s.p[5] : s.p[3], *pvb = seg ? s.p[4] : s.p[5];      // vel0, vel1 | vel1, vel2
-        const double *pvad = seg ? dot.p[5] : dot.p[3], *pvbd = seg ? dot.p[4] : dot.p[5];
-        const double *px0 = seg ? s.p[1] : s.p[0], *px1 = seg ? s.p[2] : s.p[1];
-        const double *px0d = seg ? dot.p[1] : dot.p[0], *px1d = seg ? dot.p[2] : dot.p[1];
-        const double x0 = px0[i], x1 = px1[i], va = pva ? pva[i] : 0.0, vb = pvb ? pvb[i] : 0.0;
-        const double x0d = px0d ? px0d[i] : 0.0, x1d = px1d ? px1d[i] : 0.0, vad = pvad ? pvad[i] : 0.0, vbd = pvbd ? pvbd[i] : 0.0;
-        const double ih = rcp_<double>(seg ? t1 : t0), hd = seg ? t1d : t0d;
-        const double dx = x1 - x0, dxd = x1d - x0d;
-        double acc0, jrk0, acc0d, jrk0d;
-        segment_constants(x0, x1, va, vb, ih, acc0, jrk0);
-        segment_tangents(dx, va, vb, acc0, ih, dxd, vad, vbd, hd, acc0d, jrk0d);
-        L.c[seg][0][q] = va; L.c[seg][1][q] = vb; L.c[seg][2][q] = dx; L.c[seg][3][q] = acc0; L.c[seg][4][q] = jrk0; L.c[seg][5][q] = ih;
-        L.t[seg][0][q] = vad; L.t[seg][1][q] = vbd; L.t[seg][2][q] = dxd; L.t[seg][3][q] = acc0d; L.t[seg][4][q] = jrk0d; L.t[seg][5][q] = hd;
-    }
+    const DirectedDurations d = stage_directed(i, s, dot, [&](int seg, const DirectedSegment &g) {
+        L.c[seg][0][q] = g.va; L.c[seg][1][q] = g.vb; L.c[seg][2][q] = g.dx; L.c[seg][3][q] = g.acc0; L.c[seg][4][q] = g.jrk0; L.c[seg][5][q] = g.ih;
+        L.t[seg][0][q] = g.vad; L.t[seg][1][q] = g.vbd; L.t[seg][2][q] = g.dxd; L.t[seg][3][q] = g.acc0d; L.t[seg][4][q] = g.jrk0d; L.t[seg][5][q] = g.hd;
+    });
+    L.d0[q] = d.t0;
+    L.d0_dot[q] = d.t0d;
 }
 
 // S: S_a, S_j of the segment; D: S_vd, S_ad, S_jd
-__device__ __forceinline__ SegmentBar segment_chain_dot(const HvpLds &L, int seg, int q, const double (&S)[2], const double (&D)[3])
+__device__ __forceinline__ SegmentBar segment_chain_dot(const HvpLds &L, int seg, int q, const double *S, const double *D)
 {
     const double va = L.c[seg][0][q], vb = L.c[seg][1][q], dx = L.c[seg][2][q], acc0 = L.c[seg][3][q], ih = L.c[seg][5][q];
     const double vad = L.t[seg][0][q], vbd = L.t[seg][1][q], dxd = L.t[seg][2][q], acc0d = L.t[seg][3][q], hd = L.t[seg][5][q];
@@ -440,91 +470,50 @@ __device__ __forceinline__ SegmentBar segment_chain_dot(const HvpLds &L, int seg
     return b;
 }
 
+// eleven sums: S_a, S_j, S_vd, S_ad, S_jd of segment 0, of segment 1, and the sum of tau_bar_dot over segment 1
 __global__ void __launch_bounds__(kTrajBlock)
 k_trajectory_hvp(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, int G, const double *__restrict__ tau, const double *__restrict__ g_pos,
                  const double *__restrict__ g_vel, const double *__restrict__ g_acc, const double *__restrict__ tau_dot, SplineBar8 bar,
                  double *__restrict__ tau_bar_dot)
 {
     __shared__ HvpLds L;
-    const int groups = kTrajBlock / G, group = (int)threadIdx.x / G, lane = (int)threadIdx.x & (G - 1);
-    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
-    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
-        const size_t p_first = trip * (size_t)P;
-        const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) stage_hvp(L, threadIdx.x, p_first + threadIdx.x, stage.s, dot);
-        __syncthreads();
-        for (int q = group; q < here; q += groups) {
-            const size_t row = (p_first + (size_t)q) * k;
+    for_each_trip(n, P, [&](int q, size_t i) { stage_hvp(L, q, i, stage.s, dot); }, [&](size_t p_first, int here) {
+        auto query = [&](int q, double ta, double td, double gp, double gv, double ga, double *S) -> double {
             const double d0 = L.d0[q], d0d = L.d0_dot[q];
-            // this lane's eleven sums: S_a, S_j and S_vd, S_ad, S_jd per segment, and tau_bar_dot over segment 1
-            double S[2][2] = {{0.0, 0.0}, {0.0, 0.0}}, D[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, T1d = 0.0;
-            auto query = [&](double ta, double td, double gp, double gv, double ga) -> double {
-                const bool seg = !(ta < d0);
-                const double s = seg ? ta - d0 : ta, sd = seg ? td - d0d : td;
-                const double acc0 = L.c[seg][3][q], jrk0 = L.c[seg][4][q];
-                const double vad = L.t[seg][0][q], acc0d = L.t[seg][3][q], jrk0d = L.t[seg][4][q];
-                const double acc = acc0 + jrk0 * s;
-                const double vel_d = vad + (acc0d + jrk0d * (s * 0.5)) * s + acc * sd, acc_d = acc0d + jrk0d * s + jrk0 * sd;
-                const double tbd = gp * vel_d + gv * acc_d + ga * jrk0d;
-                const double h2 = s * (s * 0.5), h3 = h2 * (s * (1.0 / 3.0));
-                const double w0 = gp, w1 = gp * s + gv, w2 = gp * h2 + gv * s + ga, w3 = gp * h3 + gv * h2 + ga * s;
-                const double u0 = w0 * sd, u1 = w1 * sd, u2 = w2 * sd;
-                S[0][0] += seg ? 0.0 : w2; S[0][1] += seg ? 0.0 : w3;
-                S[1][0] += seg ? w2 : 0.0; S[1][1] += seg ? w3 : 0.0;
-                D[0][0] += seg ? 0.0 : u0; D[0][1] += seg ? 0.0 : u1; D[0][2] += seg ? 0.0 : u2;
-                D[1][0] += seg ? u0 : 0.0; D[1][1] += seg ? u1 : 0.0; D[1][2] += seg ? u2 : 0.0;
-                T1d += seg ? tbd : 0.0;
-                return tbd;
-            };
-            if ((k & 1) == 0) {      // k even: the row starts on a 16-byte boundary
-                const size_t units = k >> 1;
-                for (size_t u = lane; u < units; u += G) {
-                    const size_t at = row + 2 * u;
-                    double ta, tb, da = 0.0, db = 0.0, pa = 0.0, pb = 0.0, va = 0.0, vb = 0.0, aa = 0.0, ab = 0.0;
-                    load_pair(tau, at, true, ta, tb);
-                    if (tau_dot) load_pair(tau_dot, at, true, da, db);
-                    if (g_pos) load_pair(g_pos, at, true, pa, pb);
-                    if (g_vel) load_pair(g_vel, at, true, va, vb);
-                    if (g_acc) load_pair(g_acc, at, true, aa, ab);
-                    const double ba = query(ta, da, pa, va, aa);
-                    const double bb = query(tb, db, pb, vb, ab);
-                    if (tau_bar_dot) store_pair(tau_bar_dot, at, ba, bb, true);
-                }
-            } else {
-                for (size_t u = lane; u < k; u += G) {
-                    const size_t at = row + u;
-                    const double b = query(tau[at], tau_dot ? tau_dot[at] : 0.0, g_pos ? g_pos[at] : 0.0, g_vel ? g_vel[at] : 0.0,
-                                           g_acc ? g_acc[at] : 0.0);
-                    if (tau_bar_dot) tau_bar_dot[at] = b;
-                }
-            }
-            // the group's lanes combine: after the butterfly every lane holds the same eleven sums
-            for (int m = 1; m < G; m <<= 1) {
-#pragma unroll
-                for (int seg = 0; seg < 2; ++seg) {
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) S[seg][c] += __shfl_xor(S[seg][c], m, 64);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) D[seg][c] += __shfl_xor(D[seg][c], m, 64);
-                }
-                T1d += __shfl_xor(T1d, m, 64);
-            }
-            if (lane == 0) {
-                const SegmentBar a = segment_chain_dot(L, 0, q, S[0], D[0]);
-                const SegmentBar b = segment_chain_dot(L, 1, q, S[1], D[1]);
-                L.bar[0][q] = a.x0; L.bar[1][q] = a.x1 + b.x0; L.bar[2][q] = b.x1;
-                L.bar[3][q] = a.va; L.bar[4][q] = b.vb; L.bar[5][q] = a.vb + b.va;
-                L.bar[6][q] = a.h - T1d; L.bar[7][q] = b.h;
-            }
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < here) {
-#pragma unroll
-            for (int f = 0; f < 8; ++f)
-                if (bar.p[f]) bar.p[f][p_first + threadIdx.x] = L.bar[f][threadIdx.x];
-        }
-        __syncthreads();
-    }
+            const bool seg = !(ta < d0);
+            const double s = seg ? ta - d0 : ta, sd = seg ? td - d0d : td;
+            const double acc0 = L.c[seg][3][q], jrk0 = L.c[seg][4][q];
+            const double vad = L.t[seg][0][q], acc0d = L.t[seg][3][q], jrk0d = L.t[seg][4][q];
+            const double acc = cubic_acc(acc0, jrk0, s);
+            const double vel_d = cubic_vel(vad, acc0d, jrk0d, s) + acc * sd, acc_d = cubic_acc(acc0d, jrk0d, s) + jrk0 * sd;
+            const double tbd = gp * vel_d + gv * acc_d + ga * jrk0d;
+            const double h2 = s * (s * 0.5), h3 = h2 * (s * (1.0 / 3.0));
+            const double w0 = gp, w1 = gp * s + gv, w2 = gp * h2 + gv * s + ga, w3 = gp * h3 + gv * h2 + ga * s;
+            const double u0 = w0 * sd, u1 = w1 * sd, u2 = w2 * sd;
+            S[0] += seg ? 0.0 : w2; S[1] += seg ? 0.0 : w3;
+            S[5] += seg ? w2 : 0.0; S[6] += seg ? w3 : 0.0;
+            S[2] += seg ? 0.0 : u0; S[3] += seg ? 0.0 : u1; S[4] += seg ? 0.0 : u2;
+            S[7] += seg ? u0 : 0.0; S[8] += seg ? u1 : 0.0; S[9] += seg ? u2 : 0.0;
+            S[10] += seg ? tbd : 0.0;
+            return tbd;
+        };
+        reduce_rows<11>(G, here, p_first, k, [&](int q, size_t at, bool two, double *S) {
+            double ta, tb, da = 0.0, db = 0.0, pa = 0.0, pb = 0.0, va = 0.0, vb = 0.0, aa = 0.0, ab = 0.0;
+            load_pair(tau, at, two, ta, tb);
+            if (tau_dot) load_pair(tau_dot, at, two, da, db);
+            if (g_pos) load_pair(g_pos, at, two, pa, pb);
+            if (g_vel) load_pair(g_vel, at, two, va, vb);
+            if (g_acc) load_pair(g_acc, at, two, aa, ab);
+            const double ba = query(q, ta, da, pa, va, aa, S);
+            const double bb = two ? query(q, tb, db, pb, vb, ab, S) : ba;
+            if (tau_bar_dot) store_pair(tau_bar_dot, at, ba, bb, two);
+        }, [&](int q, const double *S) {
+            const SegmentBar a = segment_chain_dot(L, 0, q, S, S + 2);
+            const SegmentBar b = segment_chain_dot(L, 1, q, S + 5, S + 7);
+            route_bars(L.bar, q, a, b, a.h - S[10], b.h);
+        });
+        write_bars(L.bar, bar, p_first, here);
+    });
 }
 
 // ---- the inverse question: when does the spline first reach a level (rp_trajectory_crossing, rp_batch_crossing_device) ----
@@ -580,8 +569,31 @@ __device__ __forceinline__ void velocity_breaks(double va, double acc0, double j
 
 __device__ __forceinline__ double pos_at(const EvalLds &L, int seg, int q, double s)
 {
-    const double x0 = L.c[seg][0][q], va = L.c[seg][1][q], acc0 = L.c[seg][2][q], jrk0 = L.c[seg][3][q];
-    return x0 + (va + (acc0 + jrk0 * (s * (1.0 / 3.0))) * (s * 0.5)) * s;
+    return cubic_pos(L.c[seg][0][q], L.c[seg][1][q], L.c[seg][2][q], L.c[seg][3][q], s);
+}
+
+// both segments' breakpoints from constants already staged: va, acc0, jrk0 are the rows of c that hold them; each(seg, h, c1, c2) for
+// what else a kernel keeps per segment
+template <int ROWS, class Each>
+__device__ __forceinline__ void stage_breaks(double (&brk)[2][2][kTrajProblems], int q, const double (&c)[2][ROWS][kTrajProblems], int va, int acc0,
+                                             int jrk0, double t0, double t1, Each each)
+{
+#pragma unroll
+    for (int seg = 0; seg < 2; ++seg) {
+        const double h = seg ? t1 : t0;
+        double c1, c2;
+        velocity_breaks(c[seg][va][q], c[seg][acc0][q], c[seg][jrk0][q], h, c1, c2);
+        brk[seg][0][q] = c1;
+        brk[seg][1][q] = c2;
+        each(seg, h, c1, c2);
+    }
+}
+
+template <int ROWS>
+__device__ __forceinline__ void stage_breaks(double (&brk)[2][2][kTrajProblems], int q, const double (&c)[2][ROWS][kTrajProblems], int va, int acc0,
+                                             int jrk0, double t0, double t1)
+{
+    stage_breaks(brk, q, c, va, acc0, jrk0, t0, t1, [](int, double, double, double) {});
 }
 
 __device__ __forceinline__ void stage_crossing(CrossLds &L, int q, Knots kn)
@@ -589,18 +601,12 @@ __device__ __forceinline__ void stage_crossing(CrossLds &L, int q, Knots kn)
     kn.check();
     stage_eval(L.e, q, kn);
     L.d1[q] = kn.t1;
-#pragma unroll
-    for (int seg = 0; seg < 2; ++seg) {
-        const double h = seg ? kn.t1 : kn.t0;
-        double c1, c2;
-        velocity_breaks(L.e.c[seg][1][q], L.e.c[seg][2][q], L.e.c[seg][3][q], h, c1, c2);
-        L.brk[seg][0][q] = c1;
-        L.brk[seg][1][q] = c2;
+    stage_breaks(L.brk, q, L.e.c, 1, 2, 3, kn.t0, kn.t1, [&](int seg, double h, double c1, double c2) {
         L.end[3 * seg][q] = pos_at(L.e, seg, q, 0.0);      // x0, or NaN with the problem's constants
         L.end[3 * seg + 1][q] = pos_at(L.e, seg, q, c1);
         L.end[3 * seg + 2][q] = pos_at(L.e, seg, q, c2);
         if (seg) L.end[6][q] = pos_at(L.e, 1, q, h);
-    }
+    });
 }
 
 __device__ __forceinline__ void crossing_query(const CrossLds &L, int q, double p, double &time, double &vel)
@@ -632,8 +638,8 @@ __device__ __forceinline__ void crossing_query(const CrossLds &L, int q, double 
         double dx_old = width, dx = width;
         bool last = false;
         for (int trip = 0; trip < kCrossTrips; ++trip) {
-            const double g = (x0 + (va + (acc0 + jrk0 * (s * (1.0 / 3.0))) * (s * 0.5)) * s) - p;
-            const double v = va + (acc0 + jrk0 * (s * 0.5)) * s;
+            const double g = cubic_pos(x0, va, acc0, jrk0, s) - p;
+            const double v = cubic_vel(va, acc0, jrk0, s);
             if (abs_(g) < best_g) { best_g = abs_(g); best = s; }
             if (g == 0.0 || last) break;
             if ((g < 0.0) == up) lo = s; else hi = s;
@@ -645,7 +651,7 @@ __device__ __forceinline__ void crossing_query(const CrossLds &L, int q, double 
             if (!newton) next = lo + 0.5 * width;
             // a Newton step leaves an error of about |acc / (2 vel)| step^2: once that is below the stopping width, the point it leads to is
             // the last one looked at (further steps would only follow the rounding of g around)
-            last = newton && abs_(acc0 + jrk0 * s) * (step * step) <= (2.0 * tol) * abs_(v);
+            last = newton && abs_(cubic_acc(acc0, jrk0, s)) * (step * step) <= (2.0 * tol) * abs_(v);
             dx_old = dx;
             dx = next - s;
             if (!(abs_(dx) > tol)) break;
@@ -654,7 +660,7 @@ __device__ __forceinline__ void crossing_query(const CrossLds &L, int q, double 
         s = best;
     }
     time = seg ? L.e.d0[q] + s : s;
-    vel = va + (acc0 + jrk0 * (s * 0.5)) * s;
+    vel = cubic_vel(va, acc0, jrk0, s);
 }
 
 template <class Stage>
@@ -662,14 +668,11 @@ __device__ __forceinline__ void crossing_trips(const Stage &stage, size_t n, siz
                                                double *__restrict__ time, double *__restrict__ vel)
 {
     __shared__ CrossLds L;
-    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
-    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
-        const size_t p_first = trip * (size_t)P;
-        const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) stage_crossing(L, threadIdx.x, stage.load(p_first + threadIdx.x));
-        __syncthreads();
+    // (the two query lambdas hold copies, not references: with references the compiler leaves a few more address-space checks of the LDS
+    // pointers that crossing_query selects among)
+    for_each_trip(n, P, [&](int q, size_t i) { stage_crossing(L, q, stage.load(i)); }, [=](size_t p_first, int here) {
         const size_t e_first = p_first * k;
-        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+        stream_pairs(here, k, [=](size_t e, int qa, int qb, bool two) {
             double pa, pb, ta, tb, va, vb;
             load_pair(level, e_first + e, two, pa, pb);
             crossing_query(L, qa, pa, ta, va);
@@ -677,8 +680,7 @@ __device__ __forceinline__ void crossing_trips(const Stage &stage, size_t n, siz
             store_pair(time, e_first + e, ta, tb, two);
             if (vel) store_pair(vel, e_first + e, va, vb, two);
         });
-        __syncthreads();
-    }
+    });
 }
 
 __global__ void __launch_bounds__(kTrajBlock)
@@ -693,6 +695,22 @@ k_batch_crossing(FromBatch<S, VARIANT, ZV> stage, size_t n, size_t k, int P, con
                  double *__restrict__ vel)
 {
     crossing_trips(stage, n, k, P, level, time, vel);
+}
+// a query's window [lo, hi], clamped to [0, T]
+struct Window {
+    double a, b;
+    bool ok, lo_taken, hi_taken;      // a <= b; a is lo (not the clamp +0.0); b is hi (not the clamp T)
+};
+
+__device__ __forceinline__ Window clamp_window(double lo, double hi, double T)
+{
+    Window w;
+    w.lo_taken = lo > 0.0;
+    w.hi_taken = hi < T;
+    w.a = w.lo_taken ? lo : (lo != lo ? lo : 0.0);      // a NaN end stays one
+    w.b = w.hi_taken ? hi : (hi != hi ? hi : T);
+    w.ok = w.a <= w.b;      // a NaN end, a NaN T, a window outside [0, T]: nothing
+    return w;
 }
 
 // ---- how far and how fast at most: the extreme position and velocity over a window (rp_trajectory_extrema, rp_batch_extrema_device;
@@ -712,8 +730,6 @@ struct ExtLds {
     double vv[2][kTrajProblems];      // vel there
     double T[kTrajProblems];
 };
-
-struct Extrema4 { double *p[4]; };      // pos_min, pos_max, vel_min, vel_max
 
 __device__ __forceinline__ void stage_extrema(ExtLds &L, int q, Knots kn)
 {
@@ -761,10 +777,10 @@ __device__ __forceinline__ void extrema_query(const ExtLds &L, int q, double lo,
     const double nan = quiet_nan();
     P = Extreme{nan, nan, nan, nan};
     V = Extreme{nan, nan, nan, nan};
-    const double T = L.T[q], d0 = L.e.d0[q];
-    const double a = lo > 0.0 ? lo : (lo != lo ? lo : 0.0);      // a NaN end stays one
-    const double b = hi < T ? hi : (hi != hi ? hi : T);
-    const bool ok = a <= b;      // a NaN end, a NaN T, a window outside [0, T]: no candidate at all
+    const double d0 = L.e.d0[q];
+    const Window win = clamp_window(lo, hi, L.T[q]);
+    const double a = win.a, b = win.b;
+    const bool ok = win.ok;      // not: no candidate at all
     double pa, va, pk, vk, pb, vb, acc;
     eval_query(L.e, q, a, pa, va, acc);
     eval_query(L.e, q, d0, pk, vk, acc);
@@ -792,13 +808,11 @@ __device__ __forceinline__ void extrema_query(const ExtLds &L, int q, double lo,
 
 template <bool POS, bool VEL>
 __device__ __forceinline__ void extrema_stream(const ExtLds &L, int here, size_t k, size_t e_first, const double *__restrict__ lo,
-                                               const double *__restrict__ hi, const Extrema4 &value, const Extrema4 &time)
+                                               const double *__restrict__ hi, const Out4 &value, const Out4 &time)
 {
-    const double inf = __builtin_inf();
     stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
-        double la = -inf, lb = -inf, ha = inf, hb = inf;
-        if (lo) load_pair(lo, e_first + e, two, la, lb);
-        if (hi) load_pair(hi, e_first + e, two, ha, hb);
+        double la, lb, ha, hb;
+        load_window(lo, hi, e_first + e, two, la, lb, ha, hb);
         Extreme Pa, Va, Pb, Vb;
         extrema_query<POS, VEL>(L, qa, la, ha, Pa, Va);
         extrema_query<POS, VEL>(L, qb, lb, hb, Pb, Vb);
@@ -819,27 +833,21 @@ __device__ __forceinline__ void extrema_stream(const ExtLds &L, int here, size_t
 
 template <class Stage>
 __device__ __forceinline__ void extrema_trips(const Stage &stage, size_t n, size_t k, int P, const double *__restrict__ lo,
-                                              const double *__restrict__ hi, const Extrema4 &value, const Extrema4 &time)
+                                              const double *__restrict__ hi, const Out4 &value, const Out4 &time)
 {
     __shared__ ExtLds L;
     const bool pos = value.p[0] || value.p[1] || time.p[0] || time.p[1], vel = value.p[2] || value.p[3] || time.p[2] || time.p[3];      // uniform
-    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
-    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
-        const size_t p_first = trip * (size_t)P;
-        const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) stage_extrema(L, threadIdx.x, stage.load(p_first + threadIdx.x));
-        __syncthreads();
+    for_each_trip(n, P, [&](int q, size_t i) { stage_extrema(L, q, stage.load(i)); }, [&](size_t p_first, int here) {
         const size_t e_first = p_first * k;
         // the half nobody asked for is not computed (a speed limit wants vel alone)
         if (pos && vel) extrema_stream<true, true>(L, here, k, e_first, lo, hi, value, time);
         else if (pos) extrema_stream<true, false>(L, here, k, e_first, lo, hi, value, time);
         else extrema_stream<false, true>(L, here, k, e_first, lo, hi, value, time);
-        __syncthreads();
-    }
+    });
 }
 
 __global__ void __launch_bounds__(kTrajBlock)
-k_extrema(FromArrays stage, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi, Extrema4 value, Extrema4 time)
+k_extrema(FromArrays stage, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi, Out4 value, Out4 time)
 {
     extrema_trips(stage, n, k, P, lo, hi, value, time);
 }
@@ -847,11 +855,10 @@ k_extrema(FromArrays stage, size_t n, size_t k, int P, const double *__restrict_
 template <typename S, int VARIANT, bool ZV>
 __global__ void __launch_bounds__(kTrajBlock)
 k_batch_extrema(FromBatch<S, VARIANT, ZV> stage, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
-                Extrema4 value, Extrema4 time)
+                Out4 value, Out4 time)
 {
     extrema_trips(stage, n, k, P, lo, hi, value, time);
 }
-
 // ---- how much: the integrals of pos, |vel|, vel^2 and acc^2 over a window (rp_trajectory_integrals, _vjp, _jvp, rp_batch_integrals_device;
 // DESIGN.md section 16) ----
 // The window is clamped as the extrema's, [a, b] inside [0, T], and split at the knot: segment 0 contributes over the local piece that
@@ -874,27 +881,8 @@ struct IntLds {
     double T[kTrajProblems];
 };
 
-struct Integrals4 { double *p[4]; };            // pos_int, distance, vel_sq, acc_sq
-struct IntegralsIn4 { const double *p[4]; };
-
 // a segment's constants and inner breakpoints, wherever the kernel keeps them
 struct SegmentConst { double x0, va, acc0, jrk0, c1, c2; };
-
-struct Window {
-    double a, b;
-    bool ok, lo_taken, hi_taken;      // a <= b; a is lo (not the clamp +0.0); b is hi (not the clamp T)
-};
-
-__device__ __forceinline__ Window clamp_window(double lo, double hi, double T)
-{
-    Window w;
-    w.lo_taken = lo > 0.0;
-    w.hi_taken = hi < T;
-    w.a = w.lo_taken ? lo : (lo != lo ? lo : 0.0);      // a NaN end stays one
-    w.b = w.hi_taken ? hi : (hi != hi ? hi : T);
-    w.ok = w.a <= w.b;      // a NaN end, a NaN T, a window outside [0, T]: nothing
-    return w;
-}
 
 // the piece of the window in one segment: its local start and its length (both 0 where the segment does not contribute)
 struct Piece {
@@ -922,9 +910,9 @@ __device__ __forceinline__ Piece segment_piece(int seg, const Window &win, doubl
 
 __device__ __forceinline__ void local_state(const SegmentConst &c, double s, double &X, double &V, double &A)
 {
-    X = c.x0 + (c.va + (c.acc0 + c.jrk0 * (s * (1.0 / 3.0))) * (s * 0.5)) * s;
-    V = c.va + (c.acc0 + c.jrk0 * (s * 0.5)) * s;
-    A = c.acc0 + c.jrk0 * s;
+    X = cubic_pos(c.x0, c.va, c.acc0, c.jrk0, s);
+    V = cubic_vel(c.va, c.acc0, c.jrk0, s);
+    A = cubic_acc(c.acc0, c.jrk0, s);
 }
 
 // the three monotone pieces [0, c1], [c1, c2], [c2, ...) clipped to [sa, sa + w]: each(u, l, inc) gets the clipped piece's local start,
@@ -939,7 +927,7 @@ template <bool UNROLLED, class Each> __device__ __forceinline__ void monotone_pi
         const double u = starts ? p.sa : pl, e = ends ? se : ph;
         double l = starts && ends ? p.w : e - u;      // the window's own length where the piece holds all of it
         l = l > 0.0 ? l : 0.0;
-        const double Vu = c.va + (c.acc0 + c.jrk0 * (u * 0.5)) * u, Au = c.acc0 + c.jrk0 * u;
+        const double Vu = cubic_vel(c.va, c.acc0, c.jrk0, u), Au = cubic_acc(c.acc0, c.jrk0, u);
         each(u, l, l * (Vu + (l * 0.5) * (Au + (l * (1.0 / 3.0)) * c.jrk0)));
     };
     if (UNROLLED) {
@@ -976,13 +964,7 @@ __device__ __forceinline__ void stage_integrals(IntLds &L, int q, Knots kn)
     kn.check();
     stage_eval(L.e, q, kn);
     L.T[q] = kn.t0 + kn.t1;
-#pragma unroll
-    for (int seg = 0; seg < 2; ++seg) {
-        double c1, c2;
-        velocity_breaks(L.e.c[seg][1][q], L.e.c[seg][2][q], L.e.c[seg][3][q], seg ? kn.t1 : kn.t0, c1, c2);
-        L.brk[seg][0][q] = c1;
-        L.brk[seg][1][q] = c2;
-    }
+    stage_breaks(L.brk, q, L.e.c, 1, 2, 3, kn.t0, kn.t1);
 }
 
 template <bool DIST> __device__ __forceinline__ void integrals_query(const IntLds &L, int q, double lo, double hi, double out[4])
@@ -998,13 +980,11 @@ template <bool DIST> __device__ __forceinline__ void integrals_query(const IntLd
 
 template <bool DIST>
 __device__ __forceinline__ void integrals_stream(const IntLds &L, int here, size_t k, size_t e_first, const double *__restrict__ lo,
-                                                 const double *__restrict__ hi, const Integrals4 &value)
+                                                 const double *__restrict__ hi, const Out4 &value)
 {
-    const double inf = __builtin_inf();
     stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
-        double la = -inf, lb = -inf, ha = inf, hb = inf, a[4], b[4];
-        if (lo) load_pair(lo, e_first + e, two, la, lb);
-        if (hi) load_pair(hi, e_first + e, two, ha, hb);
+        double la, lb, ha, hb, a[4], b[4];
+        load_window(lo, hi, e_first + e, two, la, lb, ha, hb);
         integrals_query<DIST>(L, qa, la, ha, a);
         integrals_query<DIST>(L, qb, lb, hb, b);
 #pragma unroll
@@ -1015,25 +995,19 @@ __device__ __forceinline__ void integrals_stream(const IntLds &L, int here, size
 
 template <class Stage>
 __device__ __forceinline__ void integrals_trips(const Stage &stage, size_t n, size_t k, int P, const double *__restrict__ lo,
-                                                const double *__restrict__ hi, const Integrals4 &value)
+                                                const double *__restrict__ hi, const Out4 &value)
 {
     __shared__ IntLds L;
     const bool dist = value.p[1] != nullptr;      // uniform
-    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
-    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
-        const size_t p_first = trip * (size_t)P;
-        const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) stage_integrals(L, threadIdx.x, stage.load(p_first + threadIdx.x));
-        __syncthreads();
+    for_each_trip(n, P, [&](int q, size_t i) { stage_integrals(L, q, stage.load(i)); }, [&](size_t p_first, int here) {
         // the walk over the monotone pieces is most of the work: not taken where nobody asked for the distance
         if (dist) integrals_stream<true>(L, here, k, p_first * k, lo, hi, value);
         else integrals_stream<false>(L, here, k, p_first * k, lo, hi, value);
-        __syncthreads();
-    }
+    });
 }
 
 __global__ void __launch_bounds__(kTrajBlock)
-k_integrals(FromArrays stage, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi, Integrals4 value)
+k_integrals(FromArrays stage, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi, Out4 value)
 {
     integrals_trips(stage, n, k, P, lo, hi, value);
 }
@@ -1041,7 +1015,7 @@ k_integrals(FromArrays stage, size_t n, size_t k, int P, const double *__restric
 template <typename S, int VARIANT, bool ZV>
 __global__ void __launch_bounds__(kTrajBlock)
 k_batch_integrals(FromBatch<S, VARIANT, ZV> stage, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
-                  Integrals4 value)
+                  Out4 value)
 {
     integrals_trips(stage, n, k, P, lo, hi, value);
 }
@@ -1097,31 +1071,16 @@ struct IntJvpLds {
 
 __global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(4)))      // 123 VGPRs: without the hint 153
 k_jvp_integrals(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
-                const double *__restrict__ lo_dot, const double *__restrict__ hi_dot, Integrals4 value_dot)
+                const double *__restrict__ lo_dot, const double *__restrict__ hi_dot, Out4 value_dot)
 {
     __shared__ IntJvpLds L;
-    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
-    const double inf = __builtin_inf();
-    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
-        const size_t p_first = trip * (size_t)P;
-        const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) {
-            const int q = threadIdx.x;
-            const size_t i = p_first + q;
-            stage_tangents(L.j, q, i, stage.s, dot);
-            double t0 = stage.s.p[6][i], t1 = stage.s.p[7][i];      // again, for the breakpoints and T: cache hits
-            check_durations(t0, t1);
-            L.T[q] = t0 + t1;
-            L.d1_dot[q] = dot.p[7] ? dot.p[7][i] : 0.0;
-#pragma unroll
-            for (int seg = 0; seg < 2; ++seg) {
-                double c1, c2;
-                velocity_breaks(L.j.c[seg][1][q], L.j.c[seg][2][q], L.j.c[seg][3][q], seg ? t1 : t0, c1, c2);
-                L.brk[seg][0][q] = c1;
-                L.brk[seg][1][q] = c2;
-            }
-        }
-        __syncthreads();
+    auto stage_problem = [&](int q, size_t i) {
+        const DirectedDurations d = stage_tangents(L.j, q, i, stage.s, dot);
+        L.T[q] = d.t0 + d.t1;
+        L.d1_dot[q] = d.t1d;
+        stage_breaks(L.brk, q, L.j.c, 1, 2, 3, d.t0, d.t1);
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
         const size_t e_first = p_first * k;
         // one query, one segment at a time (loops the compiler is told to keep: the two queries of a pair and their two segments, taken at
         // once, cost more than the 128 registers of four waves per SIMD)
@@ -1149,9 +1108,8 @@ k_jvp_integrals(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const 
             for (int i = 0; i < 4; ++i) out[i] = win.ok ? sum[i] : quiet_nan();
         };
         stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
-            double la = -inf, lb = -inf, ha = inf, hb = inf, lda = 0.0, ldb = 0.0, hda = 0.0, hdb = 0.0, a[4], b[4];
-            if (lo) load_pair(lo, e_first + e, two, la, lb);
-            if (hi) load_pair(hi, e_first + e, two, ha, hb);
+            double la, lb, ha, hb, lda = 0.0, ldb = 0.0, hda = 0.0, hdb = 0.0, a[4], b[4];
+            load_window(lo, hi, e_first + e, two, la, lb, ha, hb);
             if (lo_dot) load_pair(lo_dot, e_first + e, two, lda, ldb);
             if (hi_dot) load_pair(hi_dot, e_first + e, two, hda, hdb);
 #pragma nounroll
@@ -1165,13 +1123,11 @@ k_jvp_integrals(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, const 
             for (int i = 0; i < 4; ++i)
                 if (value_dot.p[i]) store_pair(value_dot.p[i], e_first + e, a[i], b[i], two);
         });
-        __syncthreads();
-    }
+    });
 }
 
-// ---- reverse mode: k_trajectory_vjp's reduction -- the same group of G lanes per problem, the same lane stride, the same butterfly -- over
-// ten sums: the four per segment that segment_chain takes, and what the window's ends put on duration0 and on duration1.  A query whose
-// output is NaN counts with upstream gradients of zero.
+// ---- reverse mode: reduce_rows over ten sums: the four per segment that segment_chain takes, and what the window's ends put on duration0
+// and on duration1.  A query whose output is NaN counts with upstream gradients of zero.
 struct IntVjpLds {
     VjpLds v;
     double x0[2][kTrajProblems];
@@ -1180,126 +1136,77 @@ struct IntVjpLds {
 };
 
 __global__ void __launch_bounds__(kTrajBlock)
-k_vjp_integrals(FromArrays stage, size_t n, size_t k, int P, int G, const double *__restrict__ lo, const double *__restrict__ hi, IntegralsIn4 g,
+k_vjp_integrals(FromArrays stage, size_t n, size_t k, int P, int G, const double *__restrict__ lo, const double *__restrict__ hi, In4 g,
                 SplineBar8 bar, double *__restrict__ lo_bar, double *__restrict__ hi_bar)
 {
     __shared__ IntVjpLds L;
-    const int groups = kTrajBlock / G, group = (int)threadIdx.x / G, lane = (int)threadIdx.x & (G - 1);
-    const size_t trips = (n + (size_t)P - 1) / (size_t)P;
-    const double inf = __builtin_inf();
-    for (size_t trip = blockIdx.x; trip < trips; trip += gridDim.x) {
-        const size_t p_first = trip * (size_t)P;
-        const int here = problems_here(n, p_first, P);
-        if ((int)threadIdx.x < here) {
-            const int q = threadIdx.x;
-            Knots kn = stage.load(p_first + q);
-            kn.check();
-            stage_vjp(L.v, q, kn);
-            L.x0[0][q] = kn.p0;
-            L.x0[1][q] = kn.p1;
-            L.T[q] = kn.t0 + kn.t1;
-#pragma unroll
+    auto stage_problem = [&](int q, size_t i) {
+        Knots kn = stage.load(i);
+        kn.check();
+        stage_vjp(L.v, q, kn);
+        L.x0[0][q] = kn.p0;
+        L.x0[1][q] = kn.p1;
+        L.T[q] = kn.t0 + kn.t1;
+        stage_breaks(L.brk, q, L.v.c, 0, 3, 4, kn.t0, kn.t1);
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
+        // one query, one segment at a time (a loop the compiler is told to keep, as the pair's below: registers).  S: the ten sums
+        auto query = [&](int q, double lo_q, double hi_q, double g0, double g1, double g2, double g3, double *S, double &lo_b, double &hi_b) {
+            const double d0 = L.v.d0[q];
+            const Window win = clamp_window(lo_q, hi_q, L.T[q]);
+            const double g[4] = {win.ok ? g0 : 0.0, win.ok ? g1 : 0.0, win.ok ? g2 : 0.0, win.ok ? g3 : 0.0};
+            double Ea0 = 0.0, Ea1 = 0.0, Eb0 = 0.0, Eb1 = 0.0;
+            bool on0 = false, on1 = false;
+#pragma nounroll
             for (int seg = 0; seg < 2; ++seg) {
-                double c1, c2;
-                velocity_breaks(L.v.c[seg][0][q], L.v.c[seg][3][q], L.v.c[seg][4][q], seg ? kn.t1 : kn.t0, c1, c2);
-                L.brk[seg][0][q] = c1;
-                L.brk[seg][1][q] = c2;
+                const SegmentConst c{L.x0[seg][q], L.v.c[seg][0][q], L.v.c[seg][3][q], L.v.c[seg][4][q], L.brk[seg][0][q], L.brk[seg][1][q]};
+                const Piece p = segment_piece(seg, win, d0);
+                double W[4] = {0.0, 0.0, 0.0, 0.0}, ea = 0.0, eb = 0.0;
+                segment_partials(c, p, [&](int i, double m0, double m1, double m2, double m3, double fa, double fb) {
+                    // a partial that is 0 by structure is not a term; the first term of a sum starts it
+                    if (i == 0) { W[0] = g[0] * m0; W[1] = g[0] * m1; W[2] = g[0] * m2; W[3] = g[0] * m3; ea = g[0] * fa; eb = g[0] * fb; return; }
+                    if (i < 3) W[1] += g[i] * m1;
+                    W[2] += g[i] * m2;
+                    W[3] += g[i] * m3;
+                    ea += g[i] * fa;
+                    eb += g[i] * fb;
+                });
+#pragma unroll
+                for (int f = 0; f < 4; ++f) { S[f] += seg ? 0.0 : W[f]; S[4 + f] += seg ? W[f] : 0.0; }
+                Ea0 = seg ? Ea0 : ea; Ea1 = seg ? ea : Ea1;
+                Eb0 = seg ? Eb0 : eb; Eb1 = seg ? eb : Eb1;
+                on0 = seg ? on0 : p.on; on1 = seg ? p.on : on1;
             }
-        }
-        __syncthreads();
-        for (int q = group; q < here; q += groups) {
-            const size_t row = (p_first + (size_t)q) * k;
-            const double d0 = L.v.d0[q], T = L.T[q];
-            double S[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, D0 = 0.0, D1 = 0.0;      // this lane's ten sums
-            // one segment at a time (a loop the compiler is told to keep, as the pair's below: registers)
-            auto query = [&](double lo_q, double hi_q, double g0, double g1, double g2, double g3, double &lo_b, double &hi_b) {
-                const Window win = clamp_window(lo_q, hi_q, T);
-                const double g[4] = {win.ok ? g0 : 0.0, win.ok ? g1 : 0.0, win.ok ? g2 : 0.0, win.ok ? g3 : 0.0};
-                double Ea0 = 0.0, Ea1 = 0.0, Eb0 = 0.0, Eb1 = 0.0;
-                bool on0 = false, on1 = false;
+            const bool knot = on0 && win.b > d0, end0_b = on0 && !knot;      // segment 0 ends on the knot | at b
+            const double a1 = on1 && win.a > d0 && win.lo_taken ? Ea1 : 0.0;
+            S[8] += ((knot || (end0_b && !win.hi_taken) ? Eb0 : 0.0) + a1) - (on1 && win.hi_taken ? Eb1 : 0.0);
+            S[9] += (on1 && !win.hi_taken ? Eb1 : 0.0) + (end0_b && !win.hi_taken ? Eb0 : 0.0);
+            lo_b = -((on0 && win.lo_taken ? Ea0 : 0.0) + a1);
+            hi_b = (end0_b && win.hi_taken ? Eb0 : 0.0) + (on1 && win.hi_taken ? Eb1 : 0.0);
+        };
+        reduce_rows<10>(G, here, p_first, k, [&](int q, size_t at, bool two, double *S) {
+            double la, lb, ha, hb, ga[4] = {0.0, 0.0, 0.0, 0.0}, gb[4] = {0.0, 0.0, 0.0, 0.0}, ba, bb, ca, cb;
+            load_window(lo, hi, at, two, la, lb, ha, hb);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (g.p[i]) load_pair(g.p[i], at, two, ga[i], gb[i]);
 #pragma nounroll
-                for (int seg = 0; seg < 2; ++seg) {
-                    const SegmentConst c{L.x0[seg][q], L.v.c[seg][0][q], L.v.c[seg][3][q], L.v.c[seg][4][q], L.brk[seg][0][q], L.brk[seg][1][q]};
-                    const Piece p = segment_piece(seg, win, d0);
-                    double W[4] = {0.0, 0.0, 0.0, 0.0}, ea = 0.0, eb = 0.0;
-                    segment_partials(c, p, [&](int i, double m0, double m1, double m2, double m3, double fa, double fb) {
-                        // a partial that is 0 by structure is not a term; the first term of a sum starts it
-                        if (i == 0) { W[0] = g[0] * m0; W[1] = g[0] * m1; W[2] = g[0] * m2; W[3] = g[0] * m3; ea = g[0] * fa; eb = g[0] * fb; return; }
-                        if (i < 3) W[1] += g[i] * m1;
-                        W[2] += g[i] * m2;
-                        W[3] += g[i] * m3;
-                        ea += g[i] * fa;
-                        eb += g[i] * fb;
-                    });
-#pragma unroll
-                    for (int f = 0; f < 4; ++f) { S[0][f] += seg ? 0.0 : W[f]; S[1][f] += seg ? W[f] : 0.0; }
-                    Ea0 = seg ? Ea0 : ea; Ea1 = seg ? ea : Ea1;
-                    Eb0 = seg ? Eb0 : eb; Eb1 = seg ? eb : Eb1;
-                    on0 = seg ? on0 : p.on; on1 = seg ? p.on : on1;
-                }
-                const bool knot = on0 && win.b > d0, end0_b = on0 && !knot;      // segment 0 ends on the knot | at b
-                const double a1 = on1 && win.a > d0 && win.lo_taken ? Ea1 : 0.0;
-                D0 += ((knot || (end0_b && !win.hi_taken) ? Eb0 : 0.0) + a1) - (on1 && win.hi_taken ? Eb1 : 0.0);
-                D1 += (on1 && !win.hi_taken ? Eb1 : 0.0) + (end0_b && !win.hi_taken ? Eb0 : 0.0);
-                lo_b = -((on0 && win.lo_taken ? Ea0 : 0.0) + a1);
-                hi_b = (end0_b && win.hi_taken ? Eb0 : 0.0) + (on1 && win.hi_taken ? Eb1 : 0.0);
-            };
-            if ((k & 1) == 0) {      // k even: the row starts on a 16-byte boundary
-                const size_t units = k >> 1;
-                for (size_t u = lane; u < units; u += G) {
-                    const size_t at = row + 2 * u;
-                    double la = -inf, lb = -inf, ha = inf, hb = inf, ga[4] = {0.0, 0.0, 0.0, 0.0}, gb[4] = {0.0, 0.0, 0.0, 0.0}, ba, bb, ca, cb;
-                    if (lo) load_pair(lo, at, true, la, lb);
-                    if (hi) load_pair(hi, at, true, ha, hb);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (g.p[i]) load_pair(g.p[i], at, true, ga[i], gb[i]);
-#pragma nounroll
-                    for (int second = 0; second < 2; ++second) {
-                        double b, c;
-                        query(second ? lb : la, second ? hb : ha, second ? gb[0] : ga[0], second ? gb[1] : ga[1], second ? gb[2] : ga[2],
-                              second ? gb[3] : ga[3], b, c);
-                        ba = second ? ba : b; bb = b;
-                        ca = second ? ca : c; cb = c;
-                    }
-                    if (lo_bar) store_pair(lo_bar, at, ba, bb, true);
-                    if (hi_bar) store_pair(hi_bar, at, ca, cb, true);
-                }
-            } else {
-                for (size_t u = lane; u < k; u += G) {
-                    const size_t at = row + u;
-                    double b, c;
-                    query(lo ? lo[at] : -inf, hi ? hi[at] : inf, g.p[0] ? g.p[0][at] : 0.0, g.p[1] ? g.p[1][at] : 0.0, g.p[2] ? g.p[2][at] : 0.0,
-                          g.p[3] ? g.p[3][at] : 0.0, b, c);
-                    if (lo_bar) lo_bar[at] = b;
-                    if (hi_bar) hi_bar[at] = c;
-                }
+            for (int second = 0; second < (two ? 2 : 1); ++second) {
+                double b, c;
+                query(q, second ? lb : la, second ? hb : ha, second ? gb[0] : ga[0], second ? gb[1] : ga[1], second ? gb[2] : ga[2],
+                      second ? gb[3] : ga[3], S, b, c);
+                ba = second ? ba : b; bb = b;
+                ca = second ? ca : c; cb = c;
             }
-            // the group's lanes combine: after the butterfly every lane holds the same ten sums
-            for (int m = 1; m < G; m <<= 1) {
-#pragma unroll
-                for (int seg = 0; seg < 2; ++seg)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) S[seg][c] += __shfl_xor(S[seg][c], m, 64);
-                D0 += __shfl_xor(D0, m, 64);
-                D1 += __shfl_xor(D1, m, 64);
-            }
-            if (lane == 0) {
-                const SegmentBar a = segment_chain(L.v, 0, q, S[0][0], S[0][1], S[0][2], S[0][3]);
-                const SegmentBar b = segment_chain(L.v, 1, q, S[1][0], S[1][1], S[1][2], S[1][3]);
-                L.v.bar[0][q] = a.x0; L.v.bar[1][q] = a.x1 + b.x0; L.v.bar[2][q] = b.x1;
-                L.v.bar[3][q] = a.va; L.v.bar[4][q] = b.vb; L.v.bar[5][q] = a.vb + b.va;
-                L.v.bar[6][q] = a.h + D0; L.v.bar[7][q] = b.h + D1;
-            }
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < here) {
-#pragma unroll
-            for (int f = 0; f < 8; ++f)
-                if (bar.p[f]) bar.p[f][p_first + threadIdx.x] = L.v.bar[f][threadIdx.x];
-        }
-        __syncthreads();
-    }
+            if (lo_bar) store_pair(lo_bar, at, ba, bb, two);
+            if (hi_bar) store_pair(hi_bar, at, ca, cb, two);
+        }, [&](int q, const double *S) {
+            const SegmentBar a = segment_chain(L.v, 0, q, S[0], S[1], S[2], S[3]);
+            const SegmentBar b = segment_chain(L.v, 1, q, S[4], S[5], S[6], S[7]);
+            route_bars(L.v.bar, q, a, b, a.h + S[8], b.h + S[9]);
+        });
+        write_bars(L.v.bar, bar, p_first, here);
+    });
 }
 
 // ---- plot data ----
@@ -1344,7 +1251,7 @@ __device__ __forceinline__ void sample_block(const Load &from, size_t first, siz
         if (j == 0) return s_seg[seg][0][q];
         if (j == 32) return s_seg[seg][1][q];
         const double t = s_seg[seg][5][q] * (double)j;      // h j / 32
-        return s_seg[seg][0][q] + (s_seg[seg][2][q] + (s_seg[seg][3][q] + s_seg[seg][4][q] * (t * (1.0 / 3.0))) * (t * 0.5)) * t;
+        return cubic_pos(s_seg[seg][0][q], s_seg[seg][2][q], s_seg[seg][3][q], s_seg[seg][4][q], t);
     };
     v2 *out_pos = reinterpret_cast<v2 *>(pos66 + p_first * 66);      // 16-byte aligned: 66 doubles per problem, 128 problems per block
     for (int pr = threadIdx.x; pr < here * 33; pr += kTrajBlock) {
@@ -1407,11 +1314,23 @@ int vjp_group(size_t k)
     return G;
 }
 
-Spline8 spline_of(const double *const s[8])
+// A stateless launch: the pointwise shape (P even) or, REVERSE, the reverse rules' (any P, G lanes per problem).
+// launch(grid, block, P, G) enqueues the kernel.
+template <bool REVERSE, class Launch> hipError_t launch_stateless(size_t n, size_t k, Launch launch)
 {
-    Spline8 t;
-    for (int f = 0; f < 8; ++f) t.p[f] = s[f];
-    return t;
+    const int P = problems_per_trip(k, !REVERSE), G = REVERSE ? vjp_group(k) : 0;
+    launch(dim3(trajectory_grid(n, P)), dim3(kTrajBlock), P, G);
+    return hipGetLastError();
+}
+
+// A launch on a batch's current state, PROBLEM order through its slot map: one kernel per storage type, variant and zero-velocity form.
+// launch(stage, grid, block, P) enqueues the kernel that the type of `stage` selects.
+template <class Launch> hipError_t launch_on_batch(const BatchView &b, size_t k, Launch launch)
+{
+    if (b.n == 0) return hipSuccess;
+    const int P = problems_per_trip(k, true);
+    RP_DISPATCH(kVariant | kZeroVel, b, launch(FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), P));
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -1419,153 +1338,109 @@ Spline8 spline_of(const double *const s[8])
 hipError_t launch_trajectory_eval(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, double *d_pos, double *d_vel,
                                   double *d_acc, hipStream_t stream)
 {
-    const int P = problems_per_trip(k, true);
-    hipLaunchKernelGGL(k_trajectory_eval, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)}, n, k, P,
-                       d_tau, d_pos, d_vel, d_acc);
-    return hipGetLastError();
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_trajectory_eval, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, n, k, P, d_tau, d_pos, d_vel, d_acc);
+    });
 }
 
 hipError_t launch_trajectory_jvp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *const d_spline_dot[8],
                                  const double *d_tau_dot, double *d_pos_dot, double *d_vel_dot, double *d_acc_dot, hipStream_t stream)
 {
-    const int P = problems_per_trip(k, true);
-    hipLaunchKernelGGL(k_trajectory_jvp, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)},
-                       spline_of(d_spline_dot), n, k, P, d_tau, d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot);
-    return hipGetLastError();
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_trajectory_jvp, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, table_of<8>(d_spline_dot), n, k, P, d_tau,
+                           d_tau_dot, d_pos_dot, d_vel_dot, d_acc_dot);
+    });
 }
 
 hipError_t launch_trajectory_vjp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *d_g_pos,
                                  const double *d_g_vel, const double *d_g_acc, double *const d_spline_bar[8], double *d_tau_bar, hipStream_t stream)
 {
-    const int G = vjp_group(k), P = problems_per_trip(k, false);
-    SplineBar8 bar;
-    for (int f = 0; f < 8; ++f) bar.p[f] = d_spline_bar[f];
-    const dim3 grid(trajectory_grid(n, P)), block(kTrajBlock);
-    hipLaunchKernelGGL(k_trajectory_vjp, grid, block, 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, G, d_tau, d_g_pos, d_g_vel, d_g_acc,
-                       bar, d_tau_bar);
-    return hipGetLastError();
+    return launch_stateless<true>(n, k, [&](dim3 grid, dim3 block, int P, int G) {
+        hipLaunchKernelGGL(k_trajectory_vjp, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, n, k, P, G, d_tau, d_g_pos, d_g_vel, d_g_acc,
+                           table_of<8>(d_spline_bar), d_tau_bar);
+    });
 }
 
 hipError_t launch_trajectory_hvp(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, const double *d_g_pos,
                                  const double *d_g_vel, const double *d_g_acc, const double *const d_spline_dot[8], const double *d_tau_dot,
                                  double *const d_spline_bar_dot[8], double *d_tau_bar_dot, hipStream_t stream)
 {
-    const int G = vjp_group(k), P = problems_per_trip(k, false);
-    SplineBar8 bar;
-    for (int f = 0; f < 8; ++f) bar.p[f] = d_spline_bar_dot[f];
-    hipLaunchKernelGGL(k_trajectory_hvp, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)},
-                       spline_of(d_spline_dot), n, k, P, G, d_tau, d_g_pos, d_g_vel, d_g_acc, d_tau_dot, bar, d_tau_bar_dot);
-    return hipGetLastError();
+    return launch_stateless<true>(n, k, [&](dim3 grid, dim3 block, int P, int G) {
+        hipLaunchKernelGGL(k_trajectory_hvp, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, table_of<8>(d_spline_dot), n, k, P, G, d_tau,
+                           d_g_pos, d_g_vel, d_g_acc, d_tau_dot, table_of<8>(d_spline_bar_dot), d_tau_bar_dot);
+    });
 }
 
-// the batch's state through its slot map: one k_batch_trajectory per storage type, variant and zero-velocity form
 hipError_t launch_trajectory_batch(const BatchView &b, const double *d_tau, size_t k, double *d_pos, double *d_vel, double *d_acc, hipStream_t stream)
 {
-    if (b.n == 0) return hipSuccess;
-    const int P = problems_per_trip(k, true);
-    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_trajectory<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
-                                                           FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_tau, d_pos, d_vel, d_acc));
-    return hipGetLastError();
+    return launch_on_batch(b, k, [&](auto stage, dim3 grid, dim3 block, int P) {
+        hipLaunchKernelGGL(k_batch_trajectory, grid, block, 0, stream, stage, b.n, k, P, d_tau, d_pos, d_vel, d_acc);
+    });
 }
 
-// the first time each level is reached: the evaluator's launch shape
 hipError_t launch_crossing(size_t n, size_t k, const double *const d_spline[8], const double *d_level, double *d_time, double *d_vel, hipStream_t stream)
 {
-    const int P = problems_per_trip(k, true);
-    hipLaunchKernelGGL(k_crossing, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, d_level,
-                       d_time, d_vel);
-    return hipGetLastError();
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_crossing, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, n, k, P, d_level, d_time, d_vel);
+    });
 }
 
 hipError_t launch_crossing_batch(const BatchView &b, const double *d_level, size_t k, double *d_time, double *d_vel, hipStream_t stream)
 {
-    if (b.n == 0) return hipSuccess;
-    const int P = problems_per_trip(k, true);
-    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_crossing<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
-                                                           FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_level, d_time, d_vel));
-    return hipGetLastError();
+    return launch_on_batch(b, k, [&](auto stage, dim3 grid, dim3 block, int P) {
+        hipLaunchKernelGGL(k_batch_crossing, grid, block, 0, stream, stage, b.n, k, P, d_level, d_time, d_vel);
+    });
 }
-
-// the extreme position and velocity over each window: the evaluator's launch shape
-namespace {
-Extrema4 extrema_of(double *const t[4])
-{
-    Extrema4 x;
-    for (int f = 0; f < 4; ++f) x.p[f] = t[f];
-    return x;
-}
-}  // namespace
 
 hipError_t launch_extrema(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, double *const d_value[4],
                           double *const d_time[4], hipStream_t stream)
 {
-    const int P = problems_per_trip(k, true);
-    hipLaunchKernelGGL(k_extrema, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, d_lo, d_hi,
-                       extrema_of(d_value), extrema_of(d_time));
-    return hipGetLastError();
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_extrema, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, n, k, P, d_lo, d_hi, table_of<4>(d_value),
+                           table_of<4>(d_time));
+    });
 }
 
 hipError_t launch_extrema_batch(const BatchView &b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4],
                                 double *const d_time[4], hipStream_t stream)
 {
-    if (b.n == 0) return hipSuccess;
-    const int P = problems_per_trip(k, true);
-    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_extrema<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
-                                                           FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_lo, d_hi,
-                                                           extrema_of(d_value), extrema_of(d_time)));
-    return hipGetLastError();
+    return launch_on_batch(b, k, [&](auto stage, dim3 grid, dim3 block, int P) {
+        hipLaunchKernelGGL(k_batch_extrema, grid, block, 0, stream, stage, b.n, k, P, d_lo, d_hi, table_of<4>(d_value), table_of<4>(d_time));
+    });
 }
-
-// the integrals over each window: the evaluator's launch shape, the derivative in reverse mode k_trajectory_vjp's
-namespace {
-Integrals4 integrals_of(double *const t[4])
-{
-    Integrals4 x;
-    for (int f = 0; f < 4; ++f) x.p[f] = t[f];
-    return x;
-}
-}  // namespace
 
 hipError_t launch_integrals(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, double *const d_value[4],
                             hipStream_t stream)
 {
-    const int P = problems_per_trip(k, true);
-    hipLaunchKernelGGL(k_integrals, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, d_lo, d_hi,
-                       integrals_of(d_value));
-    return hipGetLastError();
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_integrals, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, n, k, P, d_lo, d_hi, table_of<4>(d_value));
+    });
 }
 
 hipError_t launch_integrals_batch(const BatchView &b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4], hipStream_t stream)
 {
-    if (b.n == 0) return hipSuccess;
-    const int P = problems_per_trip(k, true);
-    RP_DISPATCH(kVariant | kZeroVel, b, hipLaunchKernelGGL((k_batch_integrals<S, V, Z>), dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), 0, stream,
-                                                           FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, b.n, k, P, d_lo, d_hi,
-                                                           integrals_of(d_value)));
-    return hipGetLastError();
+    return launch_on_batch(b, k, [&](auto stage, dim3 grid, dim3 block, int P) {
+        hipLaunchKernelGGL(k_batch_integrals, grid, block, 0, stream, stage, b.n, k, P, d_lo, d_hi, table_of<4>(d_value));
+    });
 }
 
 hipError_t launch_integrals_jvp(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                                 const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot, double *const d_value_dot[4],
                                 hipStream_t stream)
 {
-    const int P = problems_per_trip(k, true);
-    hipLaunchKernelGGL(k_jvp_integrals, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)},
-                       spline_of(d_spline_dot), n, k, P, d_lo, d_hi, d_lo_dot, d_hi_dot, integrals_of(d_value_dot));
-    return hipGetLastError();
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_jvp_integrals, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, table_of<8>(d_spline_dot), n, k, P, d_lo, d_hi,
+                           d_lo_dot, d_hi_dot, table_of<4>(d_value_dot));
+    });
 }
 
 hipError_t launch_integrals_vjp(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, const double *const d_g[4],
                                 double *const d_spline_bar[8], double *d_lo_bar, double *d_hi_bar, hipStream_t stream)
 {
-    const int G = vjp_group(k), P = problems_per_trip(k, false);
-    SplineBar8 bar;
-    for (int f = 0; f < 8; ++f) bar.p[f] = d_spline_bar[f];
-    IntegralsIn4 g;
-    for (int f = 0; f < 4; ++f) g.p[f] = d_g[f];
-    hipLaunchKernelGGL(k_vjp_integrals, dim3(trajectory_grid(n, P)), dim3(kTrajBlock), 0, stream, FromArrays{spline_of(d_spline)}, n, k, P, G, d_lo,
-                       d_hi, g, bar, d_lo_bar, d_hi_bar);
-    return hipGetLastError();
+    return launch_stateless<true>(n, k, [&](dim3 grid, dim3 block, int P, int G) {
+        hipLaunchKernelGGL(k_vjp_integrals, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, n, k, P, G, d_lo, d_hi, table_of<4>(d_g),
+                           table_of<8>(d_spline_bar), d_lo_bar, d_hi_bar);
+    });
 }
 
 // ---- plot data by problem index: a range [first, first + count) of problems, wherever they lie in the batch ----

@@ -165,6 +165,10 @@ def test_bits_depend_on_the_problem_and_the_level_only():
             moved = _cross([roll(a) for a in sp_big], roll(lv_big))
             for a, b in zip(moved, first):
                 assert _same_bits(a[-1], b[0]) and _same_bits(a[:-1], b[1:]), (family, k)
+    # ... nor on which of a block's trips the problem is in: more trips than the grid's cap
+    sp = tr.random_states(tg.GRID_N, 77)
+    for k in tg.GRID_KS:
+        tg.rows_equal_their_own_batch(("crossing", k), lambda s, lv: list(_cross(s, lv)), sp, _levels(sp, k, 800 + k)[0])
 
 
 # ---------------------------------------------------------------- 4. autograd

@@ -204,6 +204,10 @@ def test_bits_depend_on_the_problem_and_its_window_only():
         worst = max(worst, float(np.where(missing, 0, np.abs(got_v[j] - v64[j]) / sc[0 if j < 2 else 1]).max()))
     print("%d problems x 1 window: %.2f %% empty, values within %.2e of the scale of the float64 restatement" % (n, 100 * missing.mean(), worst))
     assert 0.002 < missing.mean() < 0.03 and worst <= 1e-13
+    # two windows each (a trip is still 128 problems): the rows at the start, where the blocks begin their second trip and at the end are
+    # those of a batch of their own
+    lo, hi = xr.windows(sp, 2, 79)
+    tg.rows_equal_their_own_batch(("extrema", 2), lambda s, a, b: (lambda r: r[0] + r[1])(_ext(s, a, b)), sp, lo, hi)
 
 
 # ---------------------------------------------------------------- 5. autograd

@@ -306,6 +306,14 @@ def test_bits_depend_on_the_problem_and_its_windows_only():
         worst = max(worst, float(np.where(missing, 0, np.abs(got[j] - f64[j]) / (scale * W)).max()))
     print("%d problems x 1 window: %.2f %% empty, values within %.2e of scale x (b - a) of the float64 restatement" % (n, 100 * missing.mean(), worst))
     assert 0.002 < missing.mean() < 0.03 and worst <= 1e-12      # section 16's bound on the float64 arithmetic itself
+    # the derivatives there: the rows at the start, where the blocks begin their second trip and at the end are those of a batch of their own
+    for k in tg.GRID_KS:
+        lo, hi = xr.windows(sp, k, 800 + k)
+        rng = np.random.default_rng(810 + k)
+        g = [rng.standard_normal((n, k)) for _ in range(4)]
+        dots, lo_dot = tg._tangents(n, k, 820 + k)
+        tg.rows_equal_their_own_batch(("integrals vjp", k), lambda s, a, b, gg: _flat(_ivjp(s, a, b, gg)), sp, lo, hi, g)
+        tg.rows_equal_their_own_batch(("integrals jvp", k), _ijvp, sp, lo, hi, dots, lo_dot, rng.standard_normal((n, k)))
 
 
 # ---------------------------------------------------------------- 5. autograd

@@ -24,6 +24,11 @@ DEV = "cuda:0"
 NS = (1, 63, 64, 65, 255, 257, 4097)
 KS = (1, 2, 33, 63, 64, 65, 200)
 BIG = 4097
+# beyond the grid's cap: at k = 1 and 2 a block takes 128 problems per trip, so 300,001 problems are 2,344 trips for the grid's 2,048 blocks,
+# the last one partial and the total odd; the rows looked at are the first 257, those around problem 2,048 x 128 = 262,144, where the
+# blocks start their second trip, and the last 257
+GRID_N, GRID_KS = 300001, (1, 2)
+GRID_ROWS = (slice(0, 257), slice(262016, 262401), slice(GRID_N - 257, GRID_N))
 PAD, SENTINEL = 16, 7.0      # doubles behind every output buffer, and what they hold
 
 
@@ -58,6 +63,24 @@ class Out:
         a = self.buf.cpu().numpy()
         assert np.all(a[self.size:] == SENTINEL), "the padding behind an output was written"
         return a[:self.size].reshape(self.shape).copy()
+
+
+def _rows(a, rows):
+    """Rows `rows` of an array, of every array of a list, or None."""
+    if a is None:
+        return None
+    return [_rows(x, rows) for x in a] if isinstance(a, (list, tuple)) else a[rows]
+
+
+def rows_equal_their_own_batch(what, run, *arrays):
+    """run(*arrays) on GRID_N problems (arrays, or lists of arrays, with the problem as their first axis; the outputs come back as one flat
+    list): GRID_ROWS of every output equal, bit for bit, the same problems run as a batch of their own."""
+    full = run(*arrays)
+    for rows in GRID_ROWS:
+        own = run(*[_rows(a, rows) for a in arrays])
+        assert len(own) == len(full)
+        for j, (a, b) in enumerate(zip(full, own)):
+            assert _same_bits(a[rows], b), (what, rows, "output %d" % j)
 
 
 def _inputs(orc, kappa, n, seed=41):
@@ -308,6 +331,14 @@ def test_bits_do_not_depend_on_the_batch_or_the_run():
             m = _vjp(moved, roll(tau_big), [roll(x) for x in g_big])
             for a, b in zip(m[0] + [m[1]], bars + [tb]):
                 assert _same_bits(a[-1], b[0]) and _same_bits(a[:-1], b[1:]), (name, k)
+    # ... nor on which of a block's trips the problem is in: more trips than the grid's cap
+    sp = tr.random_states(GRID_N, 77)
+    for k in GRID_KS:
+        tau = tr.query_times(sp, k, 800 + k)
+        dots, tdot = _tangents(GRID_N, k, 820 + k)
+        rows_equal_their_own_batch(("eval", k), _eval, sp, tau)
+        rows_equal_their_own_batch(("vjp", k), lambda s, t, g: (lambda r: r[0] + [r[1]])(_vjp(s, t, g)), sp, tau, _gradients(GRID_N, k, 810 + k))
+        rows_equal_their_own_batch(("jvp", k), _jvp, sp, tau, dots, tdot)
 
 
 # ---------------------------------------------------------------- 5. autograd

@@ -158,6 +158,12 @@ def test_bits_do_not_depend_on_the_batch_or_the_run():
             m = _hvp([roll(a) for a in sp_big], roll(tau_big), [roll(x) for x in g_big], [roll(x) for x in dots_big], roll(tdot_big))
             for a, b in zip(_all(m), big):
                 assert _same_bits(a[-1], b[0]) and _same_bits(a[:-1], b[1:]), (name, k)
+    # ... nor on which of a block's trips the problem is in: more trips than the grid's cap
+    sp = tr.random_states(tc.GRID_N, 77)
+    for k in tc.GRID_KS:
+        dots, tdot = hr.directions(tc.GRID_N, k, 820 + k)
+        tc.rows_equal_their_own_batch(("hvp", k), lambda s, t, g, d, td: _all(_hvp(s, t, g, d, td)), sp, tr.query_times(sp, k, 800 + k),
+                                      hr.gradients(tc.GRID_N, k, 810 + k), dots, tdot)
 
 
 # ---------------------------------------------------------------- 3. identities on the device
