@@ -58,6 +58,7 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      only); rp_trajectory_crossing and rp_batch_crossing_device (the first time a spline reaches a level; new entries only: no
  *      struct changes size and no existing entry changes meaning, so the revision stays); rp_trajectory_extrema and
  *      rp_batch_extrema_device (the extreme position and velocity over a window of times; new entries only, the revision stays);
+ *      rp_trajectory_gap (the extreme gap between two splines over a window of times; a new entry only, the revision stays);
  *      rp_trajectory_integrals, rp_trajectory_integrals_vjp, rp_trajectory_integrals_jvp and rp_batch_integrals_device (integrals over a
  *      window of times and their first derivatives; new entries only, the revision stays); rp_trajectory_eval_hvp (the second derivative
  *      of the evaluation along a direction; a new entry only, the revision stays) */
@@ -488,6 +489,46 @@ RP_API int rp_trajectory_integrals_jvp(int device, void *stream, size_t n, size_
  * evaluated in double: bit for bit rp_trajectory_integrals on what rp_batch_get_state returns; replaces reading the state back and summing
  * a grid on the host).  Asynchronous on the batch stream; works on any state. */
 RP_API int rp_batch_integrals_device(rp_batch *b, const double *d_lo, const double *d_hi, size_t k, double *const d_value[4]);
+
+/* ---- how close two splines get: the extreme gap between two splines in one frame over a window of times (new: the
+ * reference draws one curve, drawSegment, onedpath_ip.cpp:1065-1088; replaces a dense grid of times through rp_trajectory_eval on both
+ * splines -- k times the traffic, an answer as good as the grid -- and two rp_trajectory_extrema calls, which bound the gap but do not
+ * give it) ----
+ * Inputs: spline A and spline B, each the eight pointers of rp_trajectory_eval in its table's order, with its cubic, its segment rule and
+ * its per-problem NaN rule: if either spline is under the rule every output of the problem is NaN.  T_A and T_B are the float64 sums
+ * duration0 + duration1.
+ * Queries: query (i, j) has a window [lo, hi] and a delay: B's clock starts `delay` after A's, B is at t - delay when A is at t.  d_lo,
+ * d_hi and d_delay are n x k doubles, row-major, 16-byte aligned.  A NULL d_lo counts as -inf, a NULL d_hi as +inf, a NULL d_delay as 0;
+ * +-inf window ends are allowed; a NaN or infinite delay makes the query's outputs NaN.
+ * Gap: D(t) = pos_A(t) - pos_B(t - delay), pos the evaluator's.  No extrapolation: the common domain is [S, E], S = delay > 0 ? delay :
+ * +0.0, E = min(T_A, delay + T_B) with delay + T_B the float64 sum delay + (duration0_B + duration1_B), T_A among equals.  The window is
+ * clamped, a = lo > S ? lo : S and b = hi < E ? hi : E (a NaN end stays NaN); if !(a <= b) every output of the query is NaN.
+ * Knots and pieces: k_A = duration0_A and k_B = delay + duration0_B (the float64 sum), walked in time order, k_A first among equals; those
+ * that lie in [a, b] cut it into at most three pieces.  On a piece with left end c, A is in segment 1 if k_A <= c (local time c - k_A,
+ * else c) and B if k_B <= c (local time c - k_B, else c - delay); the relative velocity is a quadratic in u = t - c whose constants are
+ * the difference of the two segments' (vel, acc, jrk0) at c, its roots those of rp_trajectory_crossing's quadratic formula.  A root is a
+ * candidate if it is strictly inside (0, the piece's length) and its time c + u strictly inside (a, b); the smaller root first.
+ * Candidates, in time order: a; piece 0's roots; the first knot if it lies in [a, b]; piece 1's roots; the second knot if it lies in
+ * [a, b]; piece 2's roots; b.
+ * Value and selection: every candidate's value is the float64 difference of rp_trajectory_eval's pos of A at the candidate's time and of
+ * B at time - delay (the float64 difference), so a returned value is bit for bit rp_trajectory_eval(A, time) - rp_trajectory_eval(B,
+ * time - delay).  The extreme is chosen by strict comparison along the candidates in time order, as rp_trajectory_extrema's: among equal
+ * values the earliest time wins; a NaN candidate is skipped.
+ * Outputs: two tables of two pointers in the order (gap_min, gap_max): d_value[f] the extreme gap on [a, b], d_time[f] a time (on A's
+ * clock) at which it is attained, each n x k.  A NULL entry (or table) is not wanted and costs no traffic; at least one of the four must be
+ * given.  Returned time bits: the candidate's own -- a returns lo's bits, or delay's or +0.0 when clamped; b returns hi's, or T_A's or
+ * the sum delay + T_B's when clamped; a knot k_A's or k_B's; a root the sum c + u -- so that a caller can tell the candidates apart by
+ * equality.  The unsigned separation of the two is clamp(max(gap_min, -gap_max), min = 0).
+ * Derivatives need no entry of their own: reverse mode is one rp_trajectory_eval_vjp launch on each spline at the
+ * returned times (B's minus the delay), forward mode one rp_trajectory_eval_jvp launch on each, with the derivative in the time routed to
+ * lo, hi, the delay, the durations, or nowhere (a stationary point: the envelope theorem).
+ * There is no batch entry: two batches would multiply the storage-type x variant x zero-velocity dispatch to 64 forms.
+ * Argument rules are rp_trajectory_extrema's: entries [3] and [4] of either table may be NULL (zeros), every given n x k array 16-byte
+ * aligned, n and k positive, k < 2^31; RP_ERR_INVALID before any device call otherwise, also when all four outputs (or both tables) are
+ * NULL.  Asynchronous on `stream`; never throws.  No loop whose trip count depends on data.  Pointwise: a query's bits depend on its
+ * problem's sixteen numbers and its own window ends and delay only. */
+RP_API int rp_trajectory_gap(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8],
+                             const double *d_lo, const double *d_hi, const double *d_delay, double *const d_value[2], double *const d_time[2]);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

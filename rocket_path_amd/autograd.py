@@ -32,6 +32,9 @@ own derivative routed to the window end or the duration the time is; min_time_ex
 trajectory_integrals (section 16) answers how much: the integrals of pos, |vel|, vel^2 and acc^2 over a window of times, one
 rp_trajectory_integrals launch, reverse mode one rp_trajectory_integrals_vjp launch, forward mode one rp_trajectory_integrals_jvp launch;
 min_time_integrals composes it with min_time_solve.
+trajectory_gap (section 18) answers how close two splines in one frame get: the extreme of pos_a(t) - pos_b(t - delay) over a window of
+times, one rp_trajectory_gap launch, both derivative modes one launch of the evaluator's on each spline at the times the extremes are
+attained; min_time_gap composes it with two min_time_solve calls.
 """
 import ctypes
 import threading
@@ -851,6 +854,211 @@ def min_time_extrema(pos0, pos1, pos2, lo=None, hi=None, *, vel0=None, vel2=None
                                                                 vel0=vel0, vel2=vel2)
     out = trajectory_extrema(pos0, pos1, pos2, vel1, duration0, duration1, lo, hi, vel0=vel0, vel2=vel2)
     return tuple(out) + (vel1, duration0, duration1, iters, status)
+
+
+# ---- how close two splines get: the extreme gap over a window ----
+class _TrajectoryGap(torch.autograd.Function):
+    """(gap_min, gap_max, and a time at which each is attained) of pos_A(t) - pos_B(t - delay) over the windows [lo, hi] clamped to the two
+    splines' common domain: the values differentiable to first order in the sixteen spline inputs (A's table, then B's), in lo, hi and the
+    delay, through the evaluator's derivative launches on each spline at the returned times.  Each time is classified by equality -- lo,
+    hi, A's end, B's end, A's knot, B's knot, the delayed start, else a clamped +0.0 or a stationary point -- and the derivative in the
+    time goes to the inputs that time is made of.  The times are not differentiable."""
+
+    @staticmethod
+    def forward(*inputs):
+        a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
+        lo, hi, delay = (_dense(t) for t in inputs[16:19])
+        given = lo if lo is not None else hi if hi is not None else delay
+        shape = given.shape if given is not None else (inputs[0].shape[0], 1)
+        device = inputs[0].device
+        outs = [torch.empty(shape, dtype=torch.float64, device=device) for _ in range(4)]
+        n, k = shape
+        with torch.cuda.device(device):      # as _trajectory_launch
+            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_gap(device.index, torch.cuda.current_stream(device).cuda_stream, n, k, [addr(t) for t in a], [addr(t) for t in b],
+                                addr(lo), addr(hi), addr(delay), [addr(t) for t in outs[:2]], [addr(t) for t in outs[2:]])
+        return tuple(outs)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*output[2:])
+        ctx.given = [t is not None for t in inputs]
+        kept = [t for t in inputs if t is not None] + list(output)
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _saved(ctx):
+        """(A's and B's eight tensors; the delay side by side, (n, 2 k), zeros for None; the two times side by side, 0 where the value is
+        NaN, and B's, those minus the delay; where it is NaN; the class masks LO, HI, END_A, END_B, KNOT_A, KNOT_B, START of each time,
+        exclusive and in that priority)"""
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        outs = list(kept)
+        a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
+        lo, hi, delay = inputs[16:19]
+        time = torch.cat(outs[2:], dim=1)
+        missing = torch.isnan(torch.cat(outs[:2], dim=1)) | torch.isnan(time)
+        zero = torch.zeros_like(time)
+        t_a = torch.where(missing, zero, time)
+        shift = delay.repeat(1, 2) if delay is not None else zero
+        t_b = torch.where(missing, zero, t_a - shift)
+        masks, taken = [], missing
+        tests = ((lo.repeat(1, 2) if lo is not None else None), (hi.repeat(1, 2) if hi is not None else None),
+                 (a[6] + a[7]).unsqueeze(1), shift + (b[6] + b[7]).unsqueeze(1), a[6].unsqueeze(1), shift + b[6].unsqueeze(1), shift)
+        for at, ref in enumerate(tests):
+            mask = (t_a == ref) & ~taken if ref is not None else torch.zeros_like(missing)
+            if at == 6:
+                mask = mask & (shift > 0)      # a start clamped to +0.0 is a constant
+            masks.append(mask)
+            taken = taken | mask
+        return a, b, t_a.contiguous(), t_b.contiguous(), missing, masks
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_min, g_max, *_g_times):
+        if g_min is None and g_max is None:
+            return (None,) * 19
+        a, b, t_a, t_b, missing, (is_lo, is_hi, end_a, end_b, knot_a, knot_b, start) = _TrajectoryGap._saved(ctx)
+        n, k = t_a.shape[0], t_a.shape[1] // 2
+        zero = torch.zeros((n, k), dtype=torch.float64, device=t_a.device)
+        g = torch.cat([g_min if g_min is not None else zero, g_max if g_max is not None else zero], dim=1)
+        g = torch.where(missing, torch.zeros_like(g), g)      # a NaN value: gradient 0
+        need = ctx.needs_input_grad
+        want_time = need[6] or need[7] or need[14] or need[15] or need[16] or need[17] or need[18]
+        bars, tau_bars = [], []
+        for first, spline, tau, g_pos in ((0, a, t_a, g), (8, b, t_b, -g)):
+            bar = [torch.empty(n, dtype=torch.float64, device=tau.device) if need[first + f] else None for f in range(8)]
+            tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if want_time else None
+            if want_time or any(x is not None for x in bar):
+                _trajectory_launch(capi.trajectory_eval_vjp, tau.device, spline, tau, g_pos.contiguous(), None, None, bar, tau_bar)
+            bars += bar
+            tau_bars.append(tau_bar)
+        lo_bar = hi_bar = delay_bar = None
+        if want_time:
+            time_bar = tau_bars[0] + tau_bars[1]
+            routed = lambda mask: torch.where(mask, time_bar, torch.zeros_like(time_bar))      # noqa: E731
+            fold = lambda x: x.reshape(n, 2, k).sum(dim=1)      # noqa: E731
+            for f, masks in ((6, (end_a, knot_a)), (7, (end_a,)), (14, (end_b, knot_b)), (15, (end_b,))):
+                if need[f]:
+                    bars[f] = bars[f] + sum(routed(m).sum(dim=1) for m in masks)
+            if need[16]:
+                lo_bar = fold(routed(is_lo))
+            if need[17]:
+                hi_bar = fold(routed(is_hi))
+            if need[18]:      # B is at time - delay, and the times that hold the delay move with it
+                delay_bar = fold(routed(end_b | knot_b | start) - tau_bars[1])
+        return tuple(bars) + (lo_bar, hi_bar, delay_bar)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        a, b, t_a, t_b, missing, (is_lo, is_hi, end_a, end_b, knot_a, knot_b, start) = _TrajectoryGap._saved(ctx)
+        n, k = t_a.shape[0], t_a.shape[1] // 2
+        dots = [_dense(t) for t in tangents[:16]]
+        zero = torch.zeros_like(t_a)
+        col = lambda t: t.unsqueeze(1).expand(n, 2 * k) if t is not None else zero      # noqa: E731
+        wide = lambda t: t.repeat(1, 2) if t is not None else zero      # noqa: E731
+        delay_dot = wide(tangents[18])
+        time_dot = torch.where(is_lo, wide(tangents[16]), zero)
+        time_dot = torch.where(is_hi, wide(tangents[17]), time_dot)
+        time_dot = torch.where(end_a, col(dots[6]) + col(dots[7]), time_dot)
+        time_dot = torch.where(end_b, delay_dot + col(dots[14]) + col(dots[15]), time_dot)
+        time_dot = torch.where(knot_a, col(dots[6]), time_dot)
+        time_dot = torch.where(knot_b, delay_dot + col(dots[14]), time_dot)
+        time_dot = torch.where(start, delay_dot, time_dot)
+        pos_a, pos_b = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
+        _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, a, t_a, dots[:8], time_dot.contiguous(), pos_a, None, None)
+        _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, b, t_b, dots[8:], (time_dot - delay_dot).contiguous(), pos_b, None, None)
+        gap_dot = torch.where(missing, torch.full_like(t_a, float("nan")), pos_a - pos_b)
+        return gap_dot[:, :k].clone(), gap_dot[:, k:].clone(), None, None
+
+
+def _check_spline_arg(name, spline, who):
+    """One vehicle's spline as trajectory_gap takes it: a sequence of six tensors (pos0, pos1, pos2, vel1, duration0, duration1) or of
+    eight, with (vel0, vel2) appended (either may be None: zeros)."""
+    if not isinstance(spline, (list, tuple)):
+        raise TypeError("%s: %s must be a list or tuple of six or eight tensors, got %s" % (who, name, type(spline).__name__))
+    if len(spline) not in (6, 8):
+        raise ValueError("%s: %s must hold six tensors (pos0, pos1, pos2, vel1, duration0, duration1) or eight (vel0, vel2 appended), got %d"
+                         % (who, name, len(spline)))
+
+
+def _spline_table(name, spline, who):
+    """The (checked) sequence's tensors checked as trajectory_eval's arguments; returns the eight in the C ABI's table order."""
+    pos0, pos1, pos2, vel1, duration0, duration1 = spline[:6]
+    vel0, vel2 = spline[6:] if len(spline) == 8 else (None, None)
+    _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, None, vel0, vel2, "%s: %s" % (who, name), None)
+    return [pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1]
+
+
+def _check_gap_queries(pos0, lo, hi, delay, who):
+    """lo, hi (None: -inf / +inf) and delay (None: 0) against the (checked) positions, each like tau; those given: one shape after
+    broadcasting."""
+    given = [(name, _check_tau(pos0, t, who, name) if t is not None else None) for name, t in (("lo", lo), ("hi", hi), ("delay", delay))]
+    shapes = [(name, t.shape) for name, t in given if t is not None]
+    for name, shape in shapes[1:]:
+        if shape != shapes[0][1]:
+            raise ValueError(who + ": %s has shape %s, %s %s" % (shapes[0][0], tuple(shapes[0][1]), name, tuple(shape)))
+    return [t for _, t in given]
+
+
+def _check_same_batch(pos_a, pos_b, who):
+    if pos_b.device != pos_a.device:
+        raise TypeError(who + ": b is on %s; it must be on a's ROCm device %s" % (pos_b.device, pos_a.device))
+    if pos_b.shape != pos_a.shape:
+        raise ValueError(who + ": a holds %d problems, b %d" % (pos_a.shape[0], pos_b.shape[0]))
+
+
+def trajectory_gap(a, b, lo=None, hi=None, delay=None):
+    """The extreme gap between two splines of trajectory_eval in one frame, D(t) = pos_a(t) - pos_b(t - delay), over the windows of time
+    [lo, hi].  a, b: each a sequence of six tensors (pos0, pos1, pos2, vel1, duration0, duration1), or of eight with (vel0, vel2) appended,
+    of the same n on the same ROCm device.  lo, hi, delay: (n, k), or (k,) for the same queries in every problem; None: -inf / +inf / 0,
+    all three None: k = 1, the whole common domain.  b's clock starts `delay` after a's; no extrapolation: the window is clamped to
+    [max(delay, 0), min(T_a, delay + T_b)].  Returns (gap_min, gap_max, t_gap_min, t_gap_max), (n, k) each: the values and a time (on a's
+    clock) at which each is attained; NaN where the clamped window is empty, where the delay is NaN or infinite, and for a problem either
+    of whose splines has a duration that is not finite or not > 0.  The unsigned separation: torch.clamp(torch.maximum(gap_min, -gap_max),
+    min=0).
+
+    One rp_trajectory_gap launch on the current stream (include/rp_batch.h: the candidates are the window's ends, the two knots and the
+    roots of the relative velocity strictly inside each piece; the earliest among equal values wins; a value is bit for bit
+    trajectory_eval(a, time) - trajectory_eval(b, time - delay)).  The values are differentiable to first order in all sixteen spline
+    inputs, lo, hi and delay: reverse mode is one rp_trajectory_eval_vjp launch on each spline, forward mode one rp_trajectory_eval_jvp
+    launch on each, at the returned times; a double backward raises torch's once_differentiable error.  At a tie
+    between candidates, and where a window end is clamped, the derivative is that of the branch the forward pass found.  A NaN value has
+    gradient 0 (forward mode: NaN).  The times are not differentiable.  Does not synchronise the host."""
+    who = "trajectory_gap"
+    _check_spline_arg("a", a, who)
+    _check_spline_arg("b", b, who)
+    table_a, table_b = _spline_table("a", a, who), _spline_table("b", b, who)
+    _check_same_batch(table_a[0], table_b[0], who)
+    lo, hi, delay = _check_gap_queries(table_a[0], lo, hi, delay, who)
+    return _TrajectoryGap.apply(*table_a, *table_b, lo, hi, delay)
+
+
+def min_time_gap(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None, vel_b=None, gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve of two vehicles' problems, then trajectory_gap of the two solutions.  pos_a, pos_b: (pos0, pos1, pos2) of each
+    vehicle; vel_a, vel_b: (vel0, vel2) of each (None: rest to rest; either entry None: zeros); lo, hi, delay as trajectory_gap's.
+    Returns (gap_min, gap_max, t_gap_min, t_gap_max, solution_a, solution_b) with each solution min_time_solve's (vel1, duration0,
+    duration1, iters, status).  Plain composition: the gaps are differentiable to first order in both vehicles' positions and end
+    velocities, in lo, hi and delay, in both modes, through the solves' derivatives and the gap's."""
+    who = "min_time_gap"
+    for name, pos, vel in (("pos_a", pos_a, vel_a), ("pos_b", pos_b, vel_b)):
+        if not isinstance(pos, (list, tuple)) or len(pos) != 3:
+            raise TypeError("%s: %s must be a list or tuple of three tensors (pos0, pos1, pos2)" % (who, name))
+        if vel is not None and (not isinstance(vel, (list, tuple)) or len(vel) != 2):
+            raise TypeError("%s: the velocities of %s must be None or a pair (vel0, vel2)" % (who, name))
+    for name, pos in (("pos_a", pos_a), ("pos_b", pos_b)):
+        _check_positions(*pos, "%s: %s" % (who, name))
+    _check_same_batch(pos_a[0], pos_b[0], who)
+    lo, hi, delay = _check_gap_queries(pos_a[0], lo, hi, delay, who)      # before the solves: a bad query costs none
+    splines, solutions = [], []
+    for pos, vel in ((pos_a, vel_a), (pos_b, vel_b)):
+        vel0, vel2 = vel if vel is not None else (None, None)
+        solution = min_time_solve(*pos, gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
+        splines.append(tuple(pos) + tuple(solution[:3]) + (tuple(vel) if vel is not None else ()))
+        solutions.append(tuple(solution))
+    return tuple(trajectory_gap(splines[0], splines[1], lo, hi, delay)) + (solutions[0], solutions[1])
 
 
 # ---- how much: integrals over a window ----

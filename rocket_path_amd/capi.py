@@ -112,6 +112,8 @@ SIGNATURES = {
     "rp_trajectory_extrema": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp),
                                              ctypes.POINTER(_vp)]),
     "rp_batch_extrema_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rp_trajectory_gap": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp,
+                                         ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "rp_trajectory_integrals": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_integrals_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp,
                                                    ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp]),
@@ -241,6 +243,27 @@ def trajectory_extrema(device, stream, n, k, spline, d_lo=None, d_hi=None, value
     vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
     check(load_library().rp_trajectory_extrema(int(device), vp(stream), int(n), int(k), pointer_table(spline), vp(d_lo), vp(d_hi),
                                                extrema_table(value), extrema_table(time)))
+
+
+def gap_table(addresses):
+    """Two device addresses (ints; None / 0: NULL) as a `double *const [2]` table of the gap entry, in the order (gap_min, gap_max); None
+    gives a NULL table."""
+    if addresses is None:
+        return None
+    addresses = list(addresses)
+    if len(addresses) != 2:
+        raise ValueError("a gap table has two entries, got %d" % len(addresses))
+    return (_vp * 2)(*[a if a else None for a in addresses])
+
+
+def trajectory_gap(device, stream, n, k, spline_a, spline_b, d_lo=None, d_hi=None, d_delay=None, value=None, time=None):
+    """rp_trajectory_gap: the extreme gap pos_A(t) - pos_B(t - delay) between two splines over the windows [lo, hi] (n, k) clamped to their
+    common time domain (None / 0: -inf, +inf, a delay of 0), and a time at which each is attained.  `spline_a`, `spline_b`: eight addresses
+    each, as for trajectory_eval; `value` and `time`: two addresses each in the order (gap_min, gap_max), None / 0 entries (or None for the
+    table) not wanted."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_gap(int(device), vp(stream), int(n), int(k), pointer_table(spline_a), pointer_table(spline_b), vp(d_lo),
+                                           vp(d_hi), vp(d_delay), gap_table(value), gap_table(time)))
 
 
 def integrals_table(addresses):

@@ -176,5 +176,9 @@ hipError_t launch_integrals_vjp(size_t n, size_t k, const double *const d_spline
 hipError_t launch_integrals_jvp(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                                 const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot, double *const d_value_dot[4],
                                 hipStream_t stream);
+// the extreme gap pos_A(t) - pos_B(t - delay) between two splines over the windows [lo, hi] clamped to their common time domain (lo, hi,
+// delay n x k each; null: -inf / +inf / 0), and a time at which each is attained: tables of two in the order (gap_min, gap_max)
+hipError_t launch_gap(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
+                      const double *d_hi, const double *d_delay, double *const d_value[2], double *const d_time[2], hipStream_t stream);
 
 }  // namespace rp

@@ -988,15 +988,22 @@ int check_queries(const char *who, size_t n, size_t k, const double *required, c
     return RP_OK;
 }
 
+// a table of eight spline pointers, under the name the entry gives it
+int check_spline(const char *who, const char *table, const double *const d_spline[8])
+{
+    if (!d_spline) return fail(RP_ERR_INVALID, "%s: %s is null", who, table);
+    for (int f = 0; f < 8; ++f)
+        if (!d_spline[f] && f != 3 && f != 4) return fail(RP_ERR_INVALID, "%s: %s[%d] is null (only the end velocities, [3] and [4], may be)", who, table, f);
+    return RP_OK;
+}
+
 // the stateless entries: the device and the spline first
 int check_stateless(const char *who, int device, const double *const d_spline[8], size_t n, size_t k, const double *required, const char *name,
                     std::initializer_list<const void *> per_query, bool any_output)
 {
     if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", who, device);
-    if (!d_spline) return fail(RP_ERR_INVALID, "%s: d_spline is null", who);
-    for (int f = 0; f < 8; ++f)
-        if (!d_spline[f] && f != 3 && f != 4) return fail(RP_ERR_INVALID, "%s: d_spline[%d] is null (only the end velocities, [3] and [4], may be)", who, f);
-    return check_queries(who, n, k, required, name, per_query, any_output);
+    const int st = check_spline(who, "d_spline", d_spline);
+    return st != RP_OK ? st : check_queries(who, n, k, required, name, per_query, any_output);
 }
 
 }  // namespace
@@ -1103,6 +1110,21 @@ int rp_batch_extrema_device(rp_batch *b, const double *d_lo, const double *d_hi,
     if (st != RP_OK) return st;
     RP_NEED_STATE(b);
     RP_HIP(rp::launch_extrema_batch(b->view, d_lo, d_hi, k, v, t, b->stream));
+    return RP_OK;
+}
+
+// the extreme gap between two splines over a window: both spline tables, then the queries; two tables of two outputs
+int rp_trajectory_gap(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8],
+                      const double *d_lo, const double *d_hi, const double *d_delay, double *const d_value[2], double *const d_time[2])
+{
+    double *const *v = d_value ? d_value : kNoOutputs, *const *t = d_time ? d_time : kNoOutputs;
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
+    int st = check_spline(__func__, "d_spline_a", d_spline_a);
+    if (st == RP_OK) st = check_spline(__func__, "d_spline_b", d_spline_b);
+    if (st == RP_OK) st = check_queries(__func__, n, k, nullptr, nullptr, {d_lo, d_hi, d_delay, v[0], v[1], t[0], t[1]}, any_of(v, 2) || any_of(t, 2));
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_gap(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, v, t, (hipStream_t)stream));
     return RP_OK;
 }
 

@@ -6,6 +6,7 @@
 //   extreme pos and vel over a window          k_extrema, k_batch_extrema                       section 15
 //   integrals over a window                    k_integrals, k_batch_integrals                   section 16
 //   ... their first derivatives                k_jvp_integrals, k_vjp_integrals                 section 16
+//   the extreme gap between two splines        k_gap                                            section 18
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
 // rp_batch_integrals_device and rp_batch_sample*; the launchers are at the end of the file.
@@ -54,6 +55,7 @@ typedef double v2 __attribute__((ext_vector_type(2)));
 
 using SplineBar8 = Table<double, 8>;           // the eight gradients, in Spline8's order
 using Out4 = Table<double, 4>;                 // pos_min, pos_max, vel_min, vel_max | pos_int, distance, vel_sq, acc_sq
+using Out2 = Table<double, 2>;                 // gap_min, gap_max
 using In4 = Table<const double, 4>;
 
 __device__ __forceinline__ int problems_here(size_t n, size_t p_first, int P)
@@ -1209,6 +1211,105 @@ k_vjp_integrals(FromArrays stage, size_t n, size_t k, int P, int G, const double
     });
 }
 
+// ---- how close two splines get: the extreme gap over a window (rp_trajectory_gap) ----
+// D(t) = pos_A(t) - pos_B(t - delay) on the common domain [S, E], S = delay > 0 ? delay : +0.0, E = min(T_A, delay + T_B): a piecewise
+// cubic whose pieces end at A's knot k_A = duration0_A and at B's, k_B = delay + duration0_B.  A query clamps its window to [a, b] inside
+// [S, E], clamps the two knots (in time order, k_A first among equals) into [a, b] -- a knot outside leaves a piece of length zero, which
+// has no root strictly inside -- and walks a, then per piece the roots of the relative velocity and the knot that ends it (if it lies in
+// [a, b]), then b.  On a piece with left end c the relative velocity is a quadratic in u = t - c whose constants are the difference of the
+// two selected segments' (vel, acc, jrk0) at c (A's segment 1 if k_A <= c, local time c - k_A; B's if k_B <= c, local time c - k_B, else
+// c - delay); its roots are velocity_roots', candidates where strictly inside (0, the piece's length) and, as times c + u, strictly
+// inside (a, b); the smaller first.  Every candidate's value is eval_query of A at its time minus eval_query of B at time - delay, the walk
+// is the extrema's (Extreme::take: strict, the earliest among equals, a NaN never) and the time that comes back carries its candidate's
+// own bits.  Selects only; the three pieces are a loop of three trips that the compiler is told to keep (registers: eleven candidates of
+// two evaluations each per query, two queries per thread).  The block's first P threads leave per problem the two splines' evaluator
+// constants, T_A and T_B.
+struct GapLds {
+    EvalLds a, b;
+    double Ta[kTrajProblems], Tb[kTrajProblems];
+};
+
+__device__ __forceinline__ double gap_at(const GapLds &L, int q, double t, double delay)
+{
+    double pa, pb, vel, acc;
+    eval_query(L.a, q, t, pa, vel, acc);
+    eval_query(L.b, q, t - delay, pb, vel, acc);
+    return pa - pb;
+}
+
+// one spline's (vel, acc, jrk0) in segment seg at local time s
+__device__ __forceinline__ void local_motion(const EvalLds &L, int seg, int q, double s, double &vel, double &acc, double &jrk0)
+{
+    const double va = L.c[seg][1][q], acc0 = L.c[seg][2][q];
+    jrk0 = L.c[seg][3][q];
+    vel = cubic_vel(va, acc0, jrk0, s);
+    acc = cubic_acc(acc0, jrk0, s);
+}
+
+__device__ __forceinline__ void gap_query(const GapLds &L, int q, double lo, double hi, double delay, Extreme &X)
+{
+    const double nan = quiet_nan();
+    X = Extreme{nan, nan, nan, nan};
+    const double kA = L.a.d0[q], kB = delay + L.b.d0[q], TA = L.Ta[q], EB = delay + L.Tb[q];
+    const double S = delay > 0.0 ? delay : 0.0, E = EB < TA ? EB : TA;      // the common domain; T_A among equals
+    const double a = lo > S ? lo : (lo != lo ? lo : S), b = hi < E ? hi : (hi != hi ? hi : E);      // clamp_window's rule from S on
+    const bool ok = a <= b && finite_(delay) && EB == EB;      // a NaN or infinite delay, spline B under the NaN rule: nothing
+    const bool b_first = kB < kA;      // the knots in time order, k_A first among equals
+    X.take(ok, a, gap_at(L, q, a, delay));
+    double c = a;
+#pragma nounroll
+    for (int piece = 0; piece < 3; ++piece) {
+        const double knot = (piece == 0) == b_first ? kB : kA;      // the knot that ends the piece (the last piece ends at b)
+        const bool inside = piece < 2 && ok && a <= knot && knot <= b;
+        const double e = piece == 2 ? b : (knot < a ? a : (knot > b ? b : knot));
+        const int seg_a = kA <= c, seg_b = kB <= c;
+        double vel_a, acc_a, jrk_a, vel_b, acc_b, jrk_b, r0, r1;
+        local_motion(L.a, seg_a, q, seg_a ? c - kA : c, vel_a, acc_a, jrk_a);
+        local_motion(L.b, seg_b, q, seg_b ? c - kB : c - delay, vel_b, acc_b, jrk_b);
+        velocity_roots(vel_a - vel_b, acc_a - acc_b, jrk_a - jrk_b, r0, r1);
+        const double length = e - c, t0 = c + r0, t1 = c + r1;
+        const bool in0 = ok && r0 > 0.0 && r0 < length && a < t0 && t0 < b, in1 = ok && r1 > 0.0 && r1 < length && a < t1 && t1 < b;
+        const bool swap = in1 && (!in0 || r1 < r0);      // time order; a lone root comes first
+        const double first = swap ? t1 : t0, second = swap ? t0 : t1;
+        X.take(swap ? in1 : in0, first, gap_at(L, q, first, delay));
+        X.take(swap ? in0 : in1, second, gap_at(L, q, second, delay));
+        X.take(inside, knot, gap_at(L, q, knot, delay));
+        c = e;
+    }
+    X.take(ok, b, gap_at(L, q, b, delay));
+}
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_gap(FromArrays a, FromArrays b, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
+      const double *__restrict__ delay, Out2 value, Out2 time)
+{
+    __shared__ GapLds L;
+    auto stage_problem = [&](int q, size_t i) {
+        Knots ka = a.load(i), kb = b.load(i);
+        ka.check();
+        kb.check();
+        stage_eval(L.a, q, ka);
+        stage_eval(L.b, q, kb);
+        L.Ta[q] = ka.t0 + ka.t1;
+        L.Tb[q] = kb.t0 + kb.t1;
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k;
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double la, lb, ha, hb, da = 0.0, db = 0.0;
+            load_window(lo, hi, e_first + e, two, la, lb, ha, hb);
+            if (delay) load_pair(delay, e_first + e, two, da, db);
+            Extreme A, B;
+            gap_query(L, qa, la, ha, da, A);
+            gap_query(L, qb, lb, hb, db, B);
+            if (value.p[0]) store_pair(value.p[0], e_first + e, A.lo_v, B.lo_v, two);
+            if (value.p[1]) store_pair(value.p[1], e_first + e, A.hi_v, B.hi_v, two);
+            if (time.p[0]) store_pair(time.p[0], e_first + e, A.lo_t, B.lo_t, two);
+            if (time.p[1]) store_pair(time.p[1], e_first + e, A.hi_t, B.hi_t, two);
+        });
+    });
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -1440,6 +1541,15 @@ hipError_t launch_integrals_vjp(size_t n, size_t k, const double *const d_spline
     return launch_stateless<true>(n, k, [&](dim3 grid, dim3 block, int P, int G) {
         hipLaunchKernelGGL(k_vjp_integrals, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, n, k, P, G, d_lo, d_hi, table_of<4>(d_g),
                            table_of<8>(d_spline_bar), d_lo_bar, d_hi_bar);
+    });
+}
+
+hipError_t launch_gap(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
+                      const double *d_hi, const double *d_delay, double *const d_value[2], double *const d_time[2], hipStream_t stream)
+{
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_gap, grid, block, 0, stream, FromArrays{table_of<8>(d_spline_a)}, FromArrays{table_of<8>(d_spline_b)}, n, k, P, d_lo,
+                           d_hi, d_delay, table_of<2>(d_value), table_of<2>(d_time));
     });
 }
 
