@@ -61,7 +61,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      rp_trajectory_gap (the extreme gap between two splines over a window of times; a new entry only, the revision stays);
  *      rp_trajectory_integrals, rp_trajectory_integrals_vjp, rp_trajectory_integrals_jvp and rp_batch_integrals_device (integrals over a
  *      window of times and their first derivatives; new entries only, the revision stays); rp_trajectory_eval_hvp (the second derivative
- *      of the evaluation along a direction; a new entry only, the revision stays) */
+ *      of the evaluation along a direction; a new entry only, the revision stays); rp_trajectory_integrals_hvp (the second derivative of
+ *      the integrals along a direction; a new entry only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -485,6 +486,33 @@ RP_API int rp_trajectory_integrals_vjp(int device, void *stream, size_t n, size_
 RP_API int rp_trajectory_integrals_jvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo,
                                        const double *d_hi, const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot,
                                        double *const d_value_dot[4]);
+/* Second order of rp_trajectory_integrals (replaces differencing rp_trajectory_integrals_vjp along the direction --
+ * two launches, a step to choose, half the digits -- and makes torch.autograd.functional.hvp / hessian and Newton or Gauss-Newton outer
+ * loops on effort, distance and mean-position losses possible at all): the derivative of rp_trajectory_integrals_vjp's ten outputs
+ * (d_spline_bar[8], d_lo_bar, d_hi_bar) along the direction (d_spline_dot[8], d_lo_dot, d_hi_dot) with the upstream gradients d_g[4] held
+ * fixed, that is (sum over the four outputs o of g_o x the second derivative of o) x the direction.  The matrix is symmetric: the one entry
+ * is forward-over-reverse and the (spline, lo, hi) part of reverse-over-reverse; the part of a double backward in d_g is
+ * rp_trajectory_integrals_jvp.  The derivative is that of the formulas rp_trajectory_integrals_vjp evaluates on the branch the forward
+ * took: which end is lo, hi or a clamp, which segment contributes and whether segment 0 ends on the knot or at b are held fixed (a second
+ * derivative is one-sided at section 16's ties).  Exact: the four integrals are polynomials in the segment constants and the local ends.
+ * The distance's second derivative is concentrated on the sign changes of the velocity: a root c of a segment's velocity strictly inside
+ * the clipped piece adds 2 g_distance vel_dot(c) / |acc(c)| x (1, c, c^2 / 2) to the dotted partials in (va, acc0, jrk0), with vel_dot the
+ * direction's velocity at fixed local time; a touch (acc(c) == 0 exactly) adds nothing, and there is no guard otherwise: near a double root
+ * the term is large because the function is like that there (a factor that is not finite counts as 0).  The sign of the velocity at an end
+ * of a piece is taken from inside the piece -- the segment's first sign, turned once per root passed -- not from the end's own velocity,
+ * which is rounding at a rest-to-rest spline's own ends: along directions that keep the end velocities (the solve's duration tangents
+ * included) the result is the two-sided derivative there; along one that moves a zero end velocity the distance's is one-sided.
+ * A NULL d_g entry or table, a NULL entry of d_spline_dot, the whole table, d_lo_dot or d_hi_dot: zeros, the same bits as explicit zeros (a
+ * NULL d_g[1] also costs no walk over the monotone pieces).  A NULL output is not wanted and not written; at least one must be given.  A
+ * query whose outputs are NaN counts with gradients of zero and gets lo_bar_dot = hi_bar_dot = 0 -- also in a problem under the per-problem
+ * NaN rule (rp_trajectory_integrals_vjp's convention), which is NaN in its eight per-problem outputs only; a NaN d_lo_dot (d_hi_dot) on an
+ * end that is taken makes its own query's lo_bar_dot (hi_bar_dot) and the sums of its problem that its segment reaches NaN, not the other
+ * end's output (the mixed derivative in the two ends is zero); on a clamped end it is not read.  A problem's bits depend on its own inputs and on k only -- rp_trajectory_eval_vjp's order of additions, no atomics.
+ * Argument rules as above.  Asynchronous on `stream`; never throws. */
+RP_API int rp_trajectory_integrals_hvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo,
+                                       const double *d_hi, const double *const d_g[4], const double *const d_spline_dot[8],
+                                       const double *d_lo_dot, const double *d_hi_dot, double *const d_spline_bar_dot[8], double *d_lo_bar_dot,
+                                       double *d_hi_bar_dot);
 /* rp_trajectory_integrals of the batch's current state, PROBLEM order, every variant and dtype (the state read in the batch's storage type,
  * evaluated in double: bit for bit rp_trajectory_integrals on what rp_batch_get_state returns; replaces reading the state back and summing
  * a grid on the host).  Asynchronous on the batch stream; works on any state. */

@@ -31,7 +31,8 @@ rp_trajectory_extrema launch, both derivative modes one launch of the evaluator'
 own derivative routed to the window end or the duration the time is; min_time_extrema composes it with min_time_solve.
 trajectory_integrals (section 16) answers how much: the integrals of pos, |vel|, vel^2 and acc^2 over a window of times, one
 rp_trajectory_integrals launch, reverse mode one rp_trajectory_integrals_vjp launch, forward mode one rp_trajectory_integrals_jvp launch;
-min_time_integrals composes it with min_time_solve.
+min_time_integrals composes it with min_time_solve; order=2 makes its backward differentiable once more (section 19): the backward of the
+backward is one rp_trajectory_integrals_jvp launch and one rp_trajectory_integrals_hvp launch.
 trajectory_gap (section 18) answers how close two splines in one frame get: the extreme of pos_a(t) - pos_b(t - delay) over a window of
 times, one rp_trajectory_gap launch, both derivative modes one launch of the evaluator's on each spline at the times the extremes are
 attained; min_time_gap composes it with two min_time_solve calls.
@@ -1120,7 +1121,69 @@ class _TrajectoryIntegrals(torch.autograd.Function):
         return tuple(outs)
 
 
-def trajectory_integrals(pos0, pos1, pos2, vel1, duration0, duration1, lo=None, hi=None, *, vel0=None, vel2=None):
+class _TrajectoryIntegrals2(_TrajectoryIntegrals):
+    """_TrajectoryIntegrals with a backward that can be differentiated again (order=2): the same forward, the same forward-mode rule, and
+    the same one rp_trajectory_integrals_vjp launch in backward, made through _IntegralsVJP so that a create_graph backward records it."""
+
+    @staticmethod
+    def backward(ctx, *g):
+        if all(x is None for x in g):
+            return (None,) * 10
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        return _IntegralsVJP.apply(*inputs, *g, tuple(ctx.needs_input_grad[:10]), ctx.shape)
+
+
+class _IntegralsVJP(torch.autograd.Function):
+    """(the eight spline inputs, lo, hi, the four upstream gradients) -> (the eight bars, lo_bar, hi_bar): one rp_trajectory_integrals_vjp
+    launch that forms the bars `need` names (the others are None), as a function that can be differentiated once.  For cotangents u on
+    its outputs:
+        g_bar = J u                                                    one rp_trajectory_integrals_jvp launch with tangents u
+        (spline, lo, hi)_bar = (S_o g_o (second derivative of o)) u    one rp_trajectory_integrals_hvp launch with direction u (symmetric)
+    each made only if something on its side requires grad."""
+
+    @staticmethod
+    def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, lo, hi, g0, g1, g2, g3, need, shape):
+        spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
+        (n, k), dev = shape, pos0.device
+        bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(8)]
+        lo_bar, hi_bar = (torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (8, 9))
+        _TrajectoryIntegrals._launch(capi.trajectory_integrals_vjp, spline[0], spline, _dense(lo), _dense(hi), (n, k),
+                                     [_dense(x) for x in (g0, g1, g2, g3)], bars, lo_bar, hi_bar)
+        return tuple(bars) + (lo_bar, hi_bar)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)      # a bar nothing downstream uses arrives as None and goes to the kernels as NULL: not read
+        ctx.given = [t is not None for t in inputs[:14]]
+        ctx.shape = tuple(inputs[15])
+        ctx.save_for_backward(*[t for t in inputs[:14] if t is not None])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *u):
+        out = [None] * 16
+        if all(x is None for x in u):
+            return tuple(out)
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        spline, lo, hi, g = [_dense(t) for t in inputs[:8]], _dense(inputs[8]), _dense(inputs[9]), [_dense(t) for t in inputs[10:14]]
+        need, (n, k), dev = ctx.needs_input_grad, ctx.shape, spline[0].device
+        dots, lo_dot, hi_dot = [_dense(x) for x in u[:8]], _dense(u[8]), _dense(u[9])
+        if any(need[10:14]):
+            outs = [torch.empty((n, k), dtype=torch.float64, device=dev) if need[10 + c] else None for c in range(4)]
+            _TrajectoryIntegrals._launch(capi.trajectory_integrals_jvp, spline[0], spline, lo, hi, (n, k), dots, lo_dot, hi_dot, outs)
+            out[10:14] = outs
+        if any(need[:10]) and any(x is not None for x in g):
+            bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(8)]
+            lo_bar, hi_bar = (torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (8, 9))
+            _TrajectoryIntegrals._launch(capi.trajectory_integrals_hvp, spline[0], spline, lo, hi, (n, k), g, dots, lo_dot, hi_dot, bars, lo_bar,
+                                         hi_bar)
+            out[:10] = bars + [lo_bar, hi_bar]
+        return tuple(out)
+
+
+def trajectory_integrals(pos0, pos1, pos2, vel1, duration0, duration1, lo=None, hi=None, *, vel0=None, vel2=None, order=1):
     """The integrals of the spline of trajectory_eval over the windows of time [lo, hi] -- (n, k), or (k,) for the same windows in every
     problem; None: -inf / +inf, both None: k = 1, the whole spline -- clamped to [0, duration0 + duration1] (no extrapolation).  Returns
     (pos_int, distance, vel_sq, acc_sq), (n, k) each: the integrals of pos, |vel| (the distance actually travelled), vel^2 and acc^2.  NaN
@@ -1131,22 +1194,37 @@ def trajectory_integrals(pos0, pos1, pos2, vel1, duration0, duration1, lo=None, 
     and hi: reverse mode is one rp_trajectory_integrals_vjp launch that forms only the gradients autograd asks for, forward mode
     (torch.autograd.forward_ad, torch.func.jvp) one rp_trajectory_integrals_jvp launch; a double backward raises
     torch's once_differentiable error.  Where a window end is clamped, and at ties (an end on the knot), the derivative is that of the
-    branch the forward pass took.  A NaN output has gradient 0 (forward mode: NaN).  Does not synchronise the host."""
+    branch the forward pass took.  A NaN output has gradient 0 (forward mode: NaN).  Does not synchronise the host.
+
+    order=2 (1 or 2; anything else: ValueError) makes the backward differentiable once more -- torch.autograd.grad(..., create_graph=True),
+    torch.autograd.functional.hvp / hessian: the values, the gradients and the forward-mode tangents are the same launches and the same
+    bits as with order=1; the backward of the backward is one rp_trajectory_integrals_jvp launch (for the gradients in the first
+    backward's grad_outputs) and one rp_trajectory_integrals_hvp launch (for those in the spline inputs, lo and hi), each only if something
+    on its side requires grad.  The second derivative is that of the branch the forward took; the distance's has a
+    term at every sign change of the velocity inside the window, large near a double root.  A third derivative raises torch's
+    once_differentiable error."""
     who = "trajectory_integrals"
+    _check_order(order, who)
     _check_trajectory(pos0, pos1, pos2, vel1, duration0, duration1, None, vel0, vel2, who, None)
     lo, hi = _check_window(pos0, lo, hi, who)
-    return _TrajectoryIntegrals.apply(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, lo, hi)
+    function = _TrajectoryIntegrals if order == 1 else _TrajectoryIntegrals2
+    return function.apply(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, lo, hi)
 
 
-def min_time_integrals(pos0, pos1, pos2, lo=None, hi=None, *, vel0=None, vel2=None, gap_tol=1e-8, max_iter=200, params=None):
+def min_time_integrals(pos0, pos1, pos2, lo=None, hi=None, *, vel0=None, vel2=None, gap_tol=1e-8, max_iter=200, params=None, order=1):
     """min_time_solve, then trajectory_integrals of its solution over [lo, hi] ((n, k), (k,) or None): returns the four of
     trajectory_integrals, then (vel1, duration0, duration1, iters, status).  Plain composition: the integrals are differentiable in the
-    positions, the end velocities and the window's ends through the solve's derivatives and the integrals'."""
+    positions, the end velocities and the window's ends through the solve's derivatives and the integrals'.
+
+    order=2 (trajectory_integrals'): with the solve's own double backward, the integrals are twice differentiable in the positions and the
+    window's ends for rest-to-rest problems.  With vel0 / vel2 that require grad the solve is first order, and a double backward through
+    it raises torch's once_differentiable error as it does with order=1."""
+    _check_order(order, "min_time_integrals")
     _check_positions(pos0, pos1, pos2, "min_time_integrals")
     lo, hi = _check_window(pos0, lo, hi, "min_time_integrals")      # before the solve: a bad window costs none
     vel1, duration0, duration1, iters, status = min_time_solve(pos0, pos1, pos2, gap_tol=gap_tol, max_iter=max_iter, params=params,
                                                                 vel0=vel0, vel2=vel2)
-    out = trajectory_integrals(pos0, pos1, pos2, vel1, duration0, duration1, lo, hi, vel0=vel0, vel2=vel2)
+    out = trajectory_integrals(pos0, pos1, pos2, vel1, duration0, duration1, lo, hi, vel0=vel0, vel2=vel2, order=order)
     return tuple(out) + (vel1, duration0, duration1, iters, status)
 
 

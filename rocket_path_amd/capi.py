@@ -119,6 +119,8 @@ SIGNATURES = {
                                                    ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp]),
     "rp_trajectory_integrals_jvp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp,
                                                    ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp)]),
+    "rp_trajectory_integrals_hvp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp,
+                                                   ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp), _vp, _vp]),
     "rp_batch_integrals_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "rp_batch_sample_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp]),
     "rp_batch_constraints_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
@@ -300,6 +302,17 @@ def trajectory_integrals_jvp(device, stream, n, k, spline, d_lo=None, d_hi=None,
     vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
     check(load_library().rp_trajectory_integrals_jvp(int(device), vp(stream), int(n), int(k), pointer_table(spline), vp(d_lo), vp(d_hi),
                                                      pointer_table(spline_dot), vp(d_lo_dot), vp(d_hi_dot), integrals_table(value_dot)))
+
+
+def trajectory_integrals_hvp(device, stream, n, k, spline, d_lo=None, d_hi=None, g=None, spline_dot=None, d_lo_dot=None, d_hi_dot=None,
+                             spline_bar_dot=None, d_lo_bar_dot=None, d_hi_bar_dot=None):
+    """rp_trajectory_integrals_hvp: the derivative of trajectory_integrals_vjp's outputs along (`spline_dot`, d_lo_dot, d_hi_dot) (None
+    entries: zeros) at fixed upstream gradients `g`; `spline_bar_dot` the eight output addresses and d_lo_bar_dot, d_hi_bar_dot (None: not
+    wanted)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_integrals_hvp(int(device), vp(stream), int(n), int(k), pointer_table(spline), vp(d_lo), vp(d_hi),
+                                                     integrals_table(g), pointer_table(spline_dot), vp(d_lo_dot), vp(d_hi_dot),
+                                                     pointer_table(spline_bar_dot), vp(d_lo_bar_dot), vp(d_hi_bar_dot)))
 
 
 def device_count():

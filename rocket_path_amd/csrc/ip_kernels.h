@@ -176,6 +176,10 @@ hipError_t launch_integrals_vjp(size_t n, size_t k, const double *const d_spline
 hipError_t launch_integrals_jvp(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                                 const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot, double *const d_value_dot[4],
                                 hipStream_t stream);
+// the derivative of launch_integrals_vjp's ten outputs along a direction on the spline and on the window's ends, d_g held fixed
+hipError_t launch_integrals_hvp(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, const double *const d_g[4],
+                                const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot,
+                                double *const d_spline_bar_dot[8], double *d_lo_bar_dot, double *d_hi_bar_dot, hipStream_t stream);
 // the extreme gap pos_A(t) - pos_B(t - delay) between two splines over the windows [lo, hi] clamped to their common time domain (lo, hi,
 // delay n x k each; null: -inf / +inf / 0), and a time at which each is attained: tables of two in the order (gap_min, gap_max)
 hipError_t launch_gap(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,

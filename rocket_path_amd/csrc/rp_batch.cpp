@@ -950,7 +950,7 @@ int rp_batch_sample_device(rp_batch *b, double *d_pos66, double *d_acc4)
 }
 
 // ---- what can be asked of a spline: its value at the caller's own times, the first crossing of a level, the extremes and the integrals
-// over a window, and their derivatives (trajectory.hip; DESIGN.md sections 13-17) ----
+// over a window, and their derivatives (trajectory.hip; DESIGN.md sections 13-19) ----
 namespace {
 
 bool misaligned16(const void *p) { return ((uintptr_t)p & 15u) != 0; }
@@ -1128,7 +1128,7 @@ int rp_trajectory_gap(int device, void *stream, size_t n, size_t k, const double
     return RP_OK;
 }
 
-// the integrals over a window and their first derivatives
+// the integrals over a window, their first derivatives and the reverse rule's derivative along a direction
 int rp_trajectory_integrals(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                             double *const d_value[4])
 {
@@ -1162,6 +1162,22 @@ int rp_trajectory_integrals_jvp(int device, void *stream, size_t n, size_t k, co
     if (st != RP_OK) return st;
     RP_HIP(hipSetDevice(device));
     RP_HIP(rp::launch_integrals_jvp(n, k, d_spline, d_lo, d_hi, d_spline_dot ? d_spline_dot : kNoInputs, d_lo_dot, d_hi_dot, out, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_trajectory_integrals_hvp(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
+                                const double *const d_g[4], const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot,
+                                double *const d_spline_bar_dot[8], double *d_lo_bar_dot, double *d_hi_bar_dot)
+{
+    const double *const *g = d_g ? d_g : kNoInputs;
+    double *const *bars = d_spline_bar_dot ? d_spline_bar_dot : kNoOutputs;
+    const int st = check_stateless(__func__, device, d_spline, n, k, nullptr, nullptr,
+                                   {d_lo, d_hi, g[0], g[1], g[2], g[3], d_lo_dot, d_hi_dot, d_lo_bar_dot, d_hi_bar_dot},
+                                   d_lo_bar_dot || d_hi_bar_dot || any_of(bars, 8));
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_integrals_hvp(n, k, d_spline, d_lo, d_hi, g, d_spline_dot ? d_spline_dot : kNoInputs, d_lo_dot, d_hi_dot, bars, d_lo_bar_dot,
+                                    d_hi_bar_dot, (hipStream_t)stream));
     return RP_OK;
 }
 

@@ -6,6 +6,7 @@
 //   extreme pos and vel over a window          k_extrema, k_batch_extrema                       section 15
 //   integrals over a window                    k_integrals, k_batch_integrals                   section 16
 //   ... their first derivatives                k_jvp_integrals, k_vjp_integrals                 section 16
+//   ... the reverse rule along a direction     k_window_hvp                                     section 19
 //   the extreme gap between two splines        k_gap                                            section 18
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
@@ -26,7 +27,7 @@
 //   The pointwise kernels (everything but the two reverse rules): the block's P k queries are consecutive elements of tau (P is even,
 //     so a trip starts on a 16-byte boundary): each thread takes two at a time -- one 16-byte load, one 16-byte nontemporal store per
 //     wanted output -- and finds each query's problem by carrying (problem, column) along, without a division (stream_pairs).
-//   The reverse rules (k_trajectory_vjp, k_trajectory_hvp, k_vjp_integrals): a problem's k queries reduce to N sums (reduce_rows).  A
+//   The reverse rules (k_trajectory_vjp, k_trajectory_hvp, k_vjp_integrals, k_window_hvp): a problem's k queries reduce to N sums (reduce_rows).  A
 //     group of G lanes (a power of two <= 64, from k alone) owns one problem at a time: lane l adds queries l, l + G, l + 2 G, ...
 //     (pairs 2 l, 2 l + 1, ... as 16-byte vectors when k is even -- every row then starts on a 16-byte boundary; single elements
 //     when k is odd) in that order into its own sums, the lanes combine by an xor butterfly (a + b == b + a bit for bit: every lane
@@ -441,7 +442,7 @@ struct HvpLds {
 };
 
 // one problem's constants and their derivatives along the direction into LDS
-__device__ __forceinline__ void stage_hvp(HvpLds &L, int q, size_t i, const Spline8 &s, const Spline8 &dot)
+__device__ __forceinline__ DirectedDurations stage_hvp(HvpLds &L, int q, size_t i, const Spline8 &s, const Spline8 &dot)
 {
     const DirectedDurations d = stage_directed(i, s, dot, [&](int seg, const DirectedSegment &g) {
         L.c[seg][0][q] = g.va; L.c[seg][1][q] = g.vb; L.c[seg][2][q] = g.dx; L.c[seg][3][q] = g.acc0; L.c[seg][4][q] = g.jrk0; L.c[seg][5][q] = g.ih;
@@ -449,6 +450,7 @@ __device__ __forceinline__ void stage_hvp(HvpLds &L, int q, size_t i, const Spli
     });
     L.d0[q] = d.t0;
     L.d0_dot[q] = d.t0d;
+    return d;
 }
 
 // S: S_a, S_j of the segment; D: S_vd, S_ad, S_jd
@@ -1029,8 +1031,9 @@ k_batch_integrals(FromBatch<S, VARIANT, ZV> stage, size_t n, size_t k, int P, co
 //     vel_sq    (2 Q0, 2 (sa Q0 + Q1), sa^2 Q0 + 2 sa Q1 + Q2)      Qm = the integral of vel t^m
 //     acc_sq    (2 R0, 2 (sa R0 + R1))                               Rm = the integral of acc t^m
 // each(i, m0, m1, m2, m3, fa, fb) gets output i's four partials and its integrand at the two ends, one output at a time and in the outputs'
-// order, so that no more than one output's numbers are live
-template <class Each> __device__ __forceinline__ void segment_partials(const SegmentConst &c, const Piece &p, Each each)
+// order, so that no more than one output's numbers are live.  Without DIST the walk over the monotone pieces is not made and the distance's
+// partials are zeros (for a caller whose gradient on the distance is zero)
+template <bool DIST = true, class Each> __device__ __forceinline__ void segment_partials(const SegmentConst &c, const Piece &p, Each each)
 {
     const double w = p.w, sa = p.sa, J = c.jrk0, third = 1.0 / 3.0;
     double X, V, A;
@@ -1044,7 +1047,7 @@ template <class Each> __device__ __forceinline__ void segment_partials(const Seg
     }
     {
         double d1 = 0.0 * w, d2 = d1, d3 = d1;
-        monotone_pieces<false>(c, p, [&](double u, double l, double inc) {
+        if (DIST) monotone_pieces<false>(c, p, [&](double u, double l, double inc) {
             const double sign = inc > 0.0 ? 1.0 : (inc < 0.0 ? -1.0 : 0.0);
             d1 += sign * l;
             d2 += sign * (l * (u + l * 0.5));
@@ -1208,6 +1211,223 @@ k_vjp_integrals(FromArrays stage, size_t n, size_t k, int P, int G, const double
             route_bars(L.v.bar, q, a, b, a.h + S[8], b.h + S[9]);
         });
         write_bars(L.v.bar, bar, p_first, here);
+    });
+}
+
+// ---- second order: the derivative of the integrals' reverse rule along a direction (rp_trajectory_integrals_hvp) ----
+// The upstream gradients g are held fixed; the direction is (x0d, vad, acc0d, jrk0d) on a segment's constants (stage_directed) and (sad, sbd)
+// on the piece's local ends, by where each end came from, as in k_jvp_integrals; everything that routes -- lo_taken, hi_taken, which segment
+// contributes, where segment 0 ends -- is the forward's.  For one segment's contribution I(C; sa, sb) with integrand f and phi = d vel / d C
+// = (0, 1, s, s^2 / 2), with pos_d, vel_d, acc_d the direction's own cubic at a fixed local time and Nm the integral of s^m over the piece:
+//     (dI / dC)_dot = (d2I / dC2) C_dot + (df(sb) / dC) sbd - (df(sa) / dC) sad
+//     f(end)_dot    = (df(end) / dC) C_dot + f'(end) end_dot                  f' = vel, sign(vel) acc, 2 vel acc, 2 acc jrk0
+//     d2I / dC2     = 0 (pos_int), 2 the integral of phi_i phi_j (vel_sq: N0 .. N4), the same with d acc / d C = (0, 0, 1, s) (acc_sq: N0 .. N2)
+//     distance      piece by piece 0, but the sign of vel turns at its roots: a breakpoint c of velocity_breaks that is a root (c1 != 0,
+//                   c2 != h) strictly inside the piece (sa < c < sa + w) adds 2 vel_d(c) / |acc(c)| (1, c, c^2 / 2) to the three dotted
+//                   partials; acc(c) == 0 (a touch) adds nothing.  The factor 2 vel_d(c) / |acc(c)| is the problem's: staged, no division
+//                   per query.  sign(vel) at an end of the piece is the segment's first sign turned once per root passed (staged too),
+//                   not the sign of the end's own velocity, which at a rest end is rounding
+// segment_partials_dot hands these out one output at a time; segment_partials gives the first-order partials in (acc0, jrk0) beside them.
+// reduce_rows over fourteen sums.  Per segment S_a and S_j (the reverse rule's own: segment_chain's coefficients depend on h, and their
+// derivative multiplies them; S_x and S_v enter it with constant coefficients and are in no derivative) and the dotted S_xd, S_vd, S_ad,
+// S_jd -- S_xd because here the sum of g dpos_int / dx0 = g w has a derivative, g (sbd - sad), which the evaluator's rule has not: it goes
+// to x0_bar_dot next to segment_chain_dot's; and the two dotted end terms for duration0 and duration1.
+struct WinHvpLds {
+    HvpLds h;
+    double x0[2][kTrajProblems], x0d[2][kTrajProblems];
+    double brk[2][2][kTrajProblems];      // per segment: c1, c2
+    double root[2][2][kTrajProblems];     // the breakpoints that are roots of the velocity (c1 != 0, c2 != h); NaN: none
+    double rt[2][2][kTrajProblems];       // 2 vel_d(c) / |acc(c)| there; 0 where there is no root, acc(c) == 0 or the quotient is not finite
+    double s0[2][kTrajProblems];          // the sign of the velocity from the segment's start to its first root
+    double T[kTrajProblems], d1_dot[kTrajProblems];
+};
+
+// the direction on one segment's constants and on the piece's local ends, and the staged root factors
+struct SegmentDot { double x0d, vad, acc0d, jrk0d, sad, sbd, root1, root2, r1, r2, s0; };
+
+// The dotted partials of one segment's contributions: each(i, n0, n1, n2, n3, fad, fbd) gets output i's (dI / dC)_dot in (x0, va, acc0,
+// jrk0) and its integrand's derivative along the direction at the piece's start and end, one output at a time in the outputs' order.
+// Without DIST the roots are not looked at.
+template <bool DIST, class Each>
+__device__ __forceinline__ void segment_partials_dot(const SegmentConst &c, const Piece &p, const SegmentDot &d, Each each)
+{
+    const double w = p.w, sa = p.sa, sb = sa + w, J = c.jrk0, third = 1.0 / 3.0;
+    double X, V, A;
+    local_state(c, sa, X, V, A);
+    const double Vb = V + w * (A + (w * 0.5) * J), Ab = A + w * J;
+    // the direction's cubic at the two ends, and the tangents of vel and acc there
+    const double vda = cubic_vel(d.vad, d.acc0d, d.jrk0d, sa), vdb = cubic_vel(d.vad, d.acc0d, d.jrk0d, sb);
+    const double ada = cubic_acc(d.acc0d, d.jrk0d, sa), adb = cubic_acc(d.acc0d, d.jrk0d, sb);
+    const double Va_dot = vda + A * d.sad, Vb_dot = vdb + Ab * d.sbd;
+    const double ha = sa * (sa * 0.5), hb = sb * (sb * 0.5);      // s^2 / 2 at the ends
+    {
+        const double ta = ha * (sa * third), tb = hb * (sb * third);
+        each(0, d.sbd - d.sad, sb * d.sbd - sa * d.sad, hb * d.sbd - ha * d.sad, tb * d.sbd - ta * d.sad,
+             cubic_pos(d.x0d, d.vad, d.acc0d, d.jrk0d, sa) + V * d.sad, cubic_pos(d.x0d, d.vad, d.acc0d, d.jrk0d, sb) + Vb * d.sbd);
+    }
+    {
+        // the sign of the velocity just inside each end: the segment's first sign, turned once per root passed (a root on the start is
+        // passed, one on the end is not: the same count that decides below which roots lie inside).  Not the sign of V or Vb themselves:
+        // at a rest end they are of rounding size, and |vel| there is the continuation from inside
+        const bool odd_a = (d.root1 <= sa) != (d.root2 <= sa), odd_b = (d.root1 < sb) != (d.root2 < sb);
+        const double ga = odd_a ? -d.s0 : d.s0, gb = odd_b ? -d.s0 : d.s0;
+        const double ea = ga * d.sad, eb = gb * d.sbd;
+        double n1 = eb - ea, n2 = sb * eb - sa * ea, n3 = hb * eb - ha * ea;
+        if (DIST) {
+            const double r1 = d.root1 > sa && d.root1 < sb ? d.r1 : 0.0, r2 = d.root2 > sa && d.root2 < sb ? d.r2 : 0.0;
+            n1 += r1 + r2;
+            n2 += c.c1 * r1 + c.c2 * r2;
+            n3 += (c.c1 * (c.c1 * 0.5)) * r1 + (c.c2 * (c.c2 * 0.5)) * r2;
+        }
+        each(1, 0.0, n1, n2, n3, ga * Va_dot, gb * Vb_dot);
+    }
+    const double N1 = w * (sa + w * 0.5), N2 = w * (sa * sa + w * (sa + w * third));
+    {
+        const double s2 = sa * sa;
+        const double N3 = w * (s2 * sa + w * (1.5 * s2 + w * (sa + w * 0.25)));
+        const double N4 = w * (s2 * s2 + w * (2.0 * (s2 * sa) + w * (2.0 * s2 + w * (sa + w * 0.2))));
+        const double hj = 0.5 * d.jrk0d, ea = (2.0 * V) * d.sad, eb = (2.0 * Vb) * d.sbd;
+        each(2, 0.0, 2.0 * (w * d.vad + N1 * d.acc0d + N2 * hj) + (eb - ea), 2.0 * (N1 * d.vad + N2 * d.acc0d + N3 * hj) + (sb * eb - sa * ea),
+             (N2 * d.vad + N3 * d.acc0d + N4 * hj) + (hb * eb - ha * ea), (2.0 * V) * Va_dot, (2.0 * Vb) * Vb_dot);
+    }
+    {
+        const double ea = (2.0 * A) * d.sad, eb = (2.0 * Ab) * d.sbd;
+        each(3, 0.0, 0.0, 2.0 * (w * d.acc0d + N1 * d.jrk0d) + (eb - ea), 2.0 * (N1 * d.acc0d + N2 * d.jrk0d) + (sb * eb - sa * ea),
+             (2.0 * A) * (ada + J * d.sad), (2.0 * Ab) * (adb + J * d.sbd));
+    }
+}
+
+// S: the fourteen sums -- segment 0's S_a, S_j, S_xd, S_vd, S_ad, S_jd, segment 1's, then duration0's and duration1's dotted end terms
+template <bool DIST>
+__device__ __forceinline__ void window_hvp_query(const WinHvpLds &L, int q, double lo_q, double hi_q, double lo_d, double hi_d, const double (&g_in)[4],
+                                                 double *S, double &lo_b, double &hi_b)
+{
+    const double d0 = L.h.d0[q], d0d = L.h.d0_dot[q], d1d = L.d1_dot[q];
+    const Window win = clamp_window(lo_q, hi_q, L.T[q]);
+    const double a_dot = win.lo_taken ? lo_d : 0.0;
+    const double g[4] = {win.ok ? g_in[0] : 0.0, win.ok ? g_in[1] : 0.0, win.ok ? g_in[2] : 0.0, win.ok ? g_in[3] : 0.0};
+    double Ea0 = 0.0, Ea1 = 0.0, Eb0 = 0.0, Eb1 = 0.0;
+    bool on0 = false, on1 = false;
+#pragma nounroll
+    for (int seg = 0; seg < 2; ++seg) {
+        const SegmentConst c{L.x0[seg][q], L.h.c[seg][0][q], L.h.c[seg][3][q], L.h.c[seg][4][q], L.brk[seg][0][q], L.brk[seg][1][q]};
+        const Piece p = segment_piece(seg, win, d0);
+        // the tangents of the piece's local ends, by where each end came from (k_jvp_integrals')
+        const double sad = seg ? (p.on && win.a > d0 ? a_dot - d0d : 0.0) : (p.on ? a_dot : 0.0);
+        const double end0 = win.b > d0 ? d0d : (win.hi_taken ? hi_d : d0d + d1d), end1 = win.hi_taken ? hi_d - d0d : d1d;
+        const double sbd = p.on ? (seg ? end1 : end0) : 0.0;
+        const SegmentDot d{L.x0d[seg][q], L.h.t[seg][0][q], L.h.t[seg][3][q], L.h.t[seg][4][q], sad, sbd, L.root[seg][0][q], L.root[seg][1][q],
+                           L.rt[seg][0][q], L.rt[seg][1][q], L.s0[seg][q]};
+        double W2 = 0.0, W3 = 0.0;
+        segment_partials<DIST>(c, p, [&](int i, double, double, double m2, double m3, double, double) {
+            if (i == 0) { W2 = g[0] * m2; W3 = g[0] * m3; return; }
+            W2 += g[i] * m2;
+            W3 += g[i] * m3;
+        });
+        double D[4] = {0.0, 0.0, 0.0, 0.0}, ea = 0.0, eb = 0.0;
+        segment_partials_dot<DIST>(c, p, d, [&](int i, double n0, double n1, double n2, double n3, double fad, double fbd) {
+            // a partial that is 0 by structure is not a term; the first term of a sum starts it
+            if (i == 0) { D[0] = g[0] * n0; D[1] = g[0] * n1; D[2] = g[0] * n2; D[3] = g[0] * n3; ea = g[0] * fad; eb = g[0] * fbd; return; }
+            if (i < 3) D[1] += g[i] * n1;
+            D[2] += g[i] * n2;
+            D[3] += g[i] * n3;
+            ea += g[i] * fad;
+            eb += g[i] * fbd;
+        });
+        S[0] += seg ? 0.0 : W2; S[1] += seg ? 0.0 : W3;
+        S[6] += seg ? W2 : 0.0; S[7] += seg ? W3 : 0.0;
+#pragma unroll
+        for (int f = 0; f < 4; ++f) { S[2 + f] += seg ? 0.0 : D[f]; S[8 + f] += seg ? D[f] : 0.0; }
+        Ea0 = seg ? Ea0 : ea; Ea1 = seg ? ea : Ea1;
+        Eb0 = seg ? Eb0 : eb; Eb1 = seg ? eb : Eb1;
+        on0 = seg ? on0 : p.on; on1 = seg ? p.on : on1;
+    }
+    // k_vjp_integrals' routing of the end terms, dotted
+    const bool knot = on0 && win.b > d0, end0_b = on0 && !knot;
+    const double a1 = on1 && win.a > d0 && win.lo_taken ? Ea1 : 0.0;
+    S[12] += ((knot || (end0_b && !win.hi_taken) ? Eb0 : 0.0) + a1) - (on1 && win.hi_taken ? Eb1 : 0.0);
+    S[13] += (on1 && !win.hi_taken ? Eb1 : 0.0) + (end0_b && !win.hi_taken ? Eb0 : 0.0);
+    lo_b = -((on0 && win.lo_taken ? Ea0 : 0.0) + a1);
+    hi_b = (end0_b && win.hi_taken ? Eb0 : 0.0) + (on1 && win.hi_taken ? Eb1 : 0.0);
+}
+
+template <bool DIST>
+__device__ __forceinline__ void window_hvp_rows(WinHvpLds &L, int G, int here, size_t p_first, size_t k, const double *__restrict__ lo,
+                                                const double *__restrict__ hi, const In4 &g, const double *__restrict__ lo_dot,
+                                                const double *__restrict__ hi_dot, double *__restrict__ lo_bar_dot, double *__restrict__ hi_bar_dot)
+{
+    reduce_rows<14>(G, here, p_first, k, [&](int q, size_t at, bool two, double *S) {
+        double la, lb, ha, hb, lda = 0.0, ldb = 0.0, hda = 0.0, hdb = 0.0, ga[4] = {0.0, 0.0, 0.0, 0.0}, gb[4] = {0.0, 0.0, 0.0, 0.0}, ba, bb, ca, cb;
+        load_window(lo, hi, at, two, la, lb, ha, hb);
+        if (lo_dot) load_pair(lo_dot, at, two, lda, ldb);
+        if (hi_dot) load_pair(hi_dot, at, two, hda, hdb);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (g.p[i]) load_pair(g.p[i], at, two, ga[i], gb[i]);
+#pragma nounroll
+        for (int second = 0; second < (two ? 2 : 1); ++second) {
+            double b, c;
+            const double gq[4] = {second ? gb[0] : ga[0], second ? gb[1] : ga[1], second ? gb[2] : ga[2], second ? gb[3] : ga[3]};
+            window_hvp_query<DIST>(L, q, second ? lb : la, second ? hb : ha, second ? ldb : lda, second ? hdb : hda, gq, S, b, c);
+            ba = second ? ba : b; bb = b;
+            ca = second ? ca : c; cb = c;
+        }
+        if (lo_bar_dot) store_pair(lo_bar_dot, at, ba, bb, two);
+        if (hi_bar_dot) store_pair(hi_bar_dot, at, ca, cb, two);
+    }, [&](int q, const double *S) {
+        SegmentBar a = segment_chain_dot(L.h, 0, q, S, S + 3);
+        SegmentBar b = segment_chain_dot(L.h, 1, q, S + 6, S + 9);
+        a.x0 += S[2];
+        b.x0 += S[8];
+        route_bars(L.h.bar, q, a, b, a.h + S[12], b.h + S[13]);
+    });
+}
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_window_hvp(FromArrays stage, Spline8 dot, size_t n, size_t k, int P, int G, const double *__restrict__ lo, const double *__restrict__ hi, In4 g,
+             const double *__restrict__ lo_dot, const double *__restrict__ hi_dot, SplineBar8 bar, double *__restrict__ lo_bar_dot,
+             double *__restrict__ hi_bar_dot)
+{
+    __shared__ WinHvpLds L;
+    const bool dist = g.p[1] != nullptr;      // uniform
+    auto stage_problem = [&](int q, size_t i) {
+        const DirectedDurations d = stage_hvp(L.h, q, i, stage.s, dot);
+        L.T[q] = d.t0 + d.t1;
+        L.d1_dot[q] = d.t1d;
+#pragma unroll
+        for (int seg = 0; seg < 2; ++seg) {
+            const double *px0d = seg ? dot.p[1] : dot.p[0];
+            L.x0[seg][q] = (seg ? stage.s.p[1] : stage.s.p[0])[i];
+            L.x0d[seg][q] = px0d ? px0d[i] : 0.0;
+        }
+        stage_breaks(L.brk, q, L.h.c, 0, 3, 4, d.t0, d.t1, [&](int seg, double h, double c1, double c2) {
+            const double va = L.h.c[seg][0][q], acc0 = L.h.c[seg][3][q], jrk0 = L.h.c[seg][4][q];
+            const double vad = L.h.t[seg][0][q], acc0d = L.h.t[seg][3][q], jrk0d = L.h.t[seg][4][q];
+            const bool root1 = c1 != 0.0, root2 = c2 != h;
+            auto factor = [&](double c, bool root) {
+                const double acc = cubic_acc(acc0, jrk0, c);
+                const double f = root && acc != 0.0 ? 2.0 * cubic_vel(vad, acc0d, jrk0d, c) / abs_(acc) : 0.0;
+                return finite_(f) ? f : 0.0;
+            };
+            L.root[seg][0][q] = root1 ? c1 : quiet_nan();
+            L.root[seg][1][q] = root2 ? c2 : quiet_nan();
+            L.rt[seg][0][q] = factor(c1, root1);
+            L.rt[seg][1][q] = factor(c2, root2);
+            // the first sign: that of the velocity at the middle of the longest of the three pieces (far from every root), turned back by
+            // the roots before it
+            const double l0 = c1, l1 = c2 - c1, l2 = h - c2;
+            const int piece = l0 >= l1 && l0 >= l2 ? 0 : (l1 >= l2 ? 1 : 2);
+            const double mid = piece == 0 ? 0.5 * c1 : (piece == 1 ? c1 + 0.5 * l1 : c2 + 0.5 * l2);
+            const double v = cubic_vel(va, acc0, jrk0, mid), sign = v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0);
+            const bool turned = (piece >= 1 && root1) != (piece == 2 && root2);
+            L.s0[seg][q] = turned ? -sign : sign;
+        });
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
+        // the walk over the monotone pieces and the roots: not taken where the distance has no gradient
+        if (dist) window_hvp_rows<true>(L, G, here, p_first, k, lo, hi, g, lo_dot, hi_dot, lo_bar_dot, hi_bar_dot);
+        else window_hvp_rows<false>(L, G, here, p_first, k, lo, hi, g, lo_dot, hi_dot, lo_bar_dot, hi_bar_dot);
+        write_bars(L.h.bar, bar, p_first, here);
     });
 }
 
@@ -1541,6 +1761,16 @@ hipError_t launch_integrals_vjp(size_t n, size_t k, const double *const d_spline
     return launch_stateless<true>(n, k, [&](dim3 grid, dim3 block, int P, int G) {
         hipLaunchKernelGGL(k_vjp_integrals, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, n, k, P, G, d_lo, d_hi, table_of<4>(d_g),
                            table_of<8>(d_spline_bar), d_lo_bar, d_hi_bar);
+    });
+}
+
+hipError_t launch_integrals_hvp(size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi, const double *const d_g[4],
+                                const double *const d_spline_dot[8], const double *d_lo_dot, const double *d_hi_dot,
+                                double *const d_spline_bar_dot[8], double *d_lo_bar_dot, double *d_hi_bar_dot, hipStream_t stream)
+{
+    return launch_stateless<true>(n, k, [&](dim3 grid, dim3 block, int P, int G) {
+        hipLaunchKernelGGL(k_window_hvp, grid, block, 0, stream, FromArrays{table_of<8>(d_spline)}, table_of<8>(d_spline_dot), n, k, P, G, d_lo, d_hi,
+                           table_of<4>(d_g), d_lo_dot, d_hi_dot, table_of<8>(d_spline_bar_dot), d_lo_bar_dot, d_hi_bar_dot);
     });
 }
 
