@@ -59,6 +59,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      struct changes size and no existing entry changes meaning, so the revision stays); rp_trajectory_extrema and
  *      rp_batch_extrema_device (the extreme position and velocity over a window of times; new entries only, the revision stays);
  *      rp_trajectory_gap (the extreme gap between two splines over a window of times; a new entry only, the revision stays);
+ *      rp_trajectory_tracking, rp_trajectory_tracking_vjp and rp_trajectory_tracking_jvp (the integrals of the gap, its square and the
+ *      square of its rate between two splines, with both derivative rules; new entries only, the revision stays);
  *      rp_trajectory_integrals, rp_trajectory_integrals_vjp, rp_trajectory_integrals_jvp and rp_batch_integrals_device (integrals over a
  *      window of times and their first derivatives; new entries only, the revision stays); rp_trajectory_eval_hvp (the second derivative
  *      of the evaluation along a direction; a new entry only, the revision stays); rp_trajectory_integrals_hvp (the second derivative of
@@ -557,6 +559,53 @@ RP_API int rp_batch_integrals_device(rp_batch *b, const double *d_lo, const doub
  * problem's sixteen numbers and its own window ends and delay only. */
 RP_API int rp_trajectory_gap(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8],
                              const double *d_lo, const double *d_hi, const double *d_delay, double *const d_value[2], double *const d_time[2]);
+
+/* ---- how far apart two splines are on average: the tracking integrals between two splines in one frame over a window of times (DESIGN.md
+ * section 20; new: the reference draws one curve; replaces a dense grid of times through rp_trajectory_eval on both splines -- k times the
+ * traffic, an answer as good as the grid, a dozen elementwise launches in each derivative mode; rp_trajectory_integrals of either spline
+ * alone does not hold the cross term of the squared gap, and rp_trajectory_gap is a maximum, not an average) ----
+ * Inputs, queries, the gap D, the common domain [S, E], the clamped window [a, b], the knots k_A and k_B and the segment each spline is in
+ * on a piece are rp_trajectory_gap's, word for word.  The two knots, in time order with k_A first among equals and each clamped into
+ * [a, b], leave three pieces [c, e], some of length zero; on a piece A's local start is s_A = c - k_A in segment 1, else c, and B's is
+ * s_B = c - k_B in segment 1, else c - delay.
+ * Per piece: X, V, A are the float64 differences of the two selected segments' pos, vel, acc at their local starts in the evaluator's
+ * expressions, J that of their jrk0, w = e - c from the GLOBAL ends, and with third = 1.0 / 3.0
+ *     gap_int   = w (X + (w / 2) (V + (w third) (A + (w / 4) J)))
+ *     gap_sq    = w (X X + w (X V + w t3)),  t3 = (V V + X A) third + w t4,  t4 = (V A + (X J) third) / 4 + w t5,
+ *                 t5 = ((A A) / 4 + (V J) third) / 5 + w t6,  t6 = (A J) / 36 + w ((J J) / 252)
+ *     relvel_sq = w (V V + w (V A + (w third) ((A A + V J) + w (0.75 (A J) + (0.15 w) (J J)))))
+ * (divisions by constants are multiplications by the rounded reciprocals 0.5, 0.25, 0.2, 1.0 / 36.0, 1.0 / 252.0; no contraction).
+ * Outputs: a table of three pointers in the order (gap_int, gap_sq, relvel_sq), n x k each: the integrals over [a, b] of D, of D^2 and of
+ * (dD/dt)^2, each the sum piece 0 + piece 1 + piece 2 in that order; exactly 0.0 where a == b; NaN where !(a <= b), where the delay is NaN
+ * or infinite, and for a problem either of whose splines is under the NaN rule.  A NULL entry is not wanted and costs no traffic; at least
+ * one must be given.
+ * There is no batch entry (rp_trajectory_gap's reason).  Argument rules are rp_trajectory_gap's: entries [3] and [4] of either spline
+ * table may be NULL (zeros), every given n x k array 16-byte aligned, n and k positive, k < 2^31; RP_ERR_INVALID before any device call
+ * otherwise, also when no output is given.  Asynchronous on `stream`; never throws.  No loop whose trip count depends on data.  Pointwise:
+ * a query's bits depend on its problem's sixteen numbers and its own window ends and delay only. */
+RP_API int rp_trajectory_tracking(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8],
+                                  const double *const d_spline_b[8], const double *d_lo, const double *d_hi, const double *d_delay,
+                                  double *const d_value[3]);
+/* The reverse rule of rp_trajectory_tracking (replaces a backward pass through the dense grid).  d_g: the three upstream gradients, n x k
+ * each (NULL entries, or a NULL table: zeros).  Outputs, each optional (NULL: not formed): d_spline_a_bar and d_spline_b_bar, eight arrays
+ * of n each in the spline table's order, and d_lo_bar, d_hi_bar, d_delay_bar, n x k; at least one must be given.  The derivative is that of
+ * the formulas above on the branch the forward took, with every piece end's derivative sent to where the end came from (lo, hi, the delay,
+ * the durations, or nowhere for the clamp +0.0).  A query whose outputs are NaN counts with upstream gradients of
+ * zero (a problem under the NaN rule has NaN constants and NaN gradients).  One launch per spline, back to back on `stream` (side A's also forms the three per-query gradients; a side nothing is wanted of is
+ * not launched).  The order of every addition is a function of k alone: a problem's gradient is the same bits in any batch; no atomics.
+ * Argument rules as above. */
+RP_API int rp_trajectory_tracking_vjp(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8],
+                                      const double *const d_spline_b[8], const double *d_lo, const double *d_hi, const double *d_delay,
+                                      const double *const d_g[3], double *const d_spline_a_bar[8], double *const d_spline_b_bar[8],
+                                      double *d_lo_bar, double *d_hi_bar, double *d_delay_bar);
+/* The forward rule (replaces a forward-mode pass through the dense grid): tangents on both splines' eight inputs (NULL entries or tables:
+ * zeros) and on lo, hi and the delay (NULL: zeros) in, the three outputs' tangents out (NULL entries: not wanted; at least one), NaN where
+ * the output is.  A NULL tangent counts as the value zero in the same expression: NULL and explicit zeros give the same bits.  Pointwise,
+ * one launch.  Argument rules as above. */
+RP_API int rp_trajectory_tracking_jvp(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8],
+                                      const double *const d_spline_b[8], const double *d_lo, const double *d_hi, const double *d_delay,
+                                      const double *const d_spline_a_dot[8], const double *const d_spline_b_dot[8], const double *d_lo_dot,
+                                      const double *d_hi_dot, const double *d_delay_dot, double *const d_value_dot[3]);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

@@ -36,6 +36,9 @@ backward is one rp_trajectory_integrals_jvp launch and one rp_trajectory_integra
 trajectory_gap (section 18) answers how close two splines in one frame get: the extreme of pos_a(t) - pos_b(t - delay) over a window of
 times, one rp_trajectory_gap launch, both derivative modes one launch of the evaluator's on each spline at the times the extremes are
 attained; min_time_gap composes it with two min_time_solve calls.
+trajectory_tracking (section 20) answers how far apart they are on average: the integrals of that gap, of its square and of the square of
+its rate over a window of times, one rp_trajectory_tracking launch, reverse mode one rp_trajectory_tracking_vjp call, forward mode one
+rp_trajectory_tracking_jvp launch; min_time_tracking composes it with two min_time_solve calls.
 """
 import ctypes
 import threading
@@ -1226,6 +1229,120 @@ def min_time_integrals(pos0, pos1, pos2, lo=None, hi=None, *, vel0=None, vel2=No
                                                                 vel0=vel0, vel2=vel2)
     out = trajectory_integrals(pos0, pos1, pos2, vel1, duration0, duration1, lo, hi, vel0=vel0, vel2=vel2, order=order)
     return tuple(out) + (vel1, duration0, duration1, iters, status)
+
+
+# ---- how far apart two splines are on average: the tracking integrals over a window ----
+class _TrajectoryTracking(torch.autograd.Function):
+    """(gap_int, gap_sq, relvel_sq) of D(t) = pos_A(t) - pos_B(t - delay) over the windows [lo, hi] clamped to the two splines' common domain:
+    differentiable to first order in the sixteen spline inputs (A's table, then B's), in lo, hi and the delay, each mode one call of its own
+    entry."""
+
+    @staticmethod
+    def _launch(entry, a, b, lo, hi, delay, shape, *rest):
+        """One rp_trajectory_tracking* call on the current stream; rest: tensors, None or lists of them (tables)."""
+        addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+        n, k = shape
+        device = a[0].device
+        with torch.cuda.device(device):      # as _trajectory_launch
+            entry(device.index, torch.cuda.current_stream(device).cuda_stream, n, k, [addr(t) for t in a], [addr(t) for t in b], addr(lo), addr(hi),
+                  addr(delay), *[[addr(t) for t in x] if isinstance(x, (list, tuple)) else addr(x) for x in rest])
+
+    @staticmethod
+    def forward(*inputs):
+        a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
+        lo, hi, delay = (_dense(t) for t in inputs[16:19])
+        given = lo if lo is not None else hi if hi is not None else delay
+        shape = tuple(given.shape) if given is not None else (inputs[0].shape[0], 1)
+        outs = [torch.empty(shape, dtype=torch.float64, device=inputs[0].device) for _ in range(3)]
+        _TrajectoryTracking._launch(capi.trajectory_tracking, a, b, lo, hi, delay, shape, outs)
+        return tuple(outs)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None and goes to the kernel as NULL: not read
+        ctx.given = [t is not None for t in inputs]
+        ctx.shape = tuple(output[0].shape)
+        kept = [t for t in inputs if t is not None]
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _inputs(ctx):
+        kept = iter(ctx.saved_tensors)
+        inputs = [_dense(next(kept)) if given else None for given in ctx.given]
+        return inputs[:8], inputs[8:16], inputs[16], inputs[17], inputs[18]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *g):
+        if all(x is None for x in g):
+            return (None,) * 19
+        a, b, lo, hi, delay = _TrajectoryTracking._inputs(ctx)
+        need, (n, k), dev = ctx.needs_input_grad, ctx.shape, a[0].device
+        bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(16)]
+        lo_bar, hi_bar, delay_bar = (torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (16, 17, 18))
+        if any(need[:19]):
+            _TrajectoryTracking._launch(capi.trajectory_tracking_vjp, a, b, lo, hi, delay, (n, k), [_dense(x) for x in g], bars[:8], bars[8:],
+                                        lo_bar, hi_bar, delay_bar)
+        return tuple(bars) + (lo_bar, hi_bar, delay_bar)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        a, b, lo, hi, delay = _TrajectoryTracking._inputs(ctx)
+        dots = [_dense(t) for t in tangents]
+        outs = [torch.empty(ctx.shape, dtype=torch.float64, device=a[0].device) for _ in range(3)]
+        _TrajectoryTracking._launch(capi.trajectory_tracking_jvp, a, b, lo, hi, delay, ctx.shape, dots[:8], dots[8:16], dots[16], dots[17],
+                                    dots[18], outs)
+        return tuple(outs)
+
+
+def trajectory_tracking(a, b, lo=None, hi=None, delay=None):
+    """The tracking integrals between two splines of trajectory_eval in one frame: with D(t) = pos_a(t) - pos_b(t - delay), the integrals of
+    D (gap_int), D^2 (gap_sq) and (dD/dt)^2 (relvel_sq) over the windows of time [lo, hi].  a, b, lo, hi, delay: exactly trajectory_gap's
+    -- each spline a sequence of six tensors (pos0, pos1, pos2, vel1, duration0, duration1), or of eight with (vel0, vel2) appended, of the
+    same n on the same ROCm device; the queries (n, k), or (k,) for the same queries in every problem; None: -inf / +inf / 0, all three
+    None: k = 1, the whole common domain.  No extrapolation: the window is clamped to [max(delay, 0), min(T_a, delay + T_b)].  Returns
+    (gap_int, gap_sq, relvel_sq), (n, k) each; NaN where the clamped window is empty, where the delay is NaN or infinite, and for a problem
+    either of whose splines has a duration that is not finite or not > 0; exactly 0 where the window's ends coincide.  The mean gap over a
+    window is gap_int / (b - a), the RMS gap sqrt(gap_sq / (b - a)).
+
+    One rp_trajectory_tracking launch on the current stream (include/rp_batch.h: closed forms on the at most three pieces the two knots cut
+    the window into).  Differentiable to first order in all sixteen spline inputs, lo, hi and delay: reverse mode is one
+    rp_trajectory_tracking_vjp call that forms only the gradients autograd asks for, forward mode (torch.autograd.forward_ad,
+    torch.func.jvp) one rp_trajectory_tracking_jvp launch; a double backward raises torch's once_differentiable
+    error.  Where a window end is clamped, and at ties, the derivative is that of the branch the forward pass took; at a delay of exactly 0
+    the clamped start is the constant +0.0.  A NaN output has gradient 0 (forward mode: NaN).  Does not synchronise the host."""
+    who = "trajectory_tracking"
+    _check_spline_arg("a", a, who)
+    _check_spline_arg("b", b, who)
+    table_a, table_b = _spline_table("a", a, who), _spline_table("b", b, who)
+    _check_same_batch(table_a[0], table_b[0], who)
+    lo, hi, delay = _check_gap_queries(table_a[0], lo, hi, delay, who)
+    return _TrajectoryTracking.apply(*table_a, *table_b, lo, hi, delay)
+
+
+def min_time_tracking(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None, vel_b=None, gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve of two vehicles' problems, then trajectory_tracking of the two solutions.  Arguments as min_time_gap's.  Returns
+    (gap_int, gap_sq, relvel_sq, solution_a, solution_b) with each solution min_time_solve's (vel1, duration0, duration1, iters, status).
+    Plain composition: the integrals are differentiable to first order in both vehicles' positions and end velocities, in lo, hi and delay,
+    in both modes, through the solves' derivatives and the integrals'."""
+    who = "min_time_tracking"
+    for name, pos, vel in (("pos_a", pos_a, vel_a), ("pos_b", pos_b, vel_b)):
+        if not isinstance(pos, (list, tuple)) or len(pos) != 3:
+            raise TypeError("%s: %s must be a list or tuple of three tensors (pos0, pos1, pos2)" % (who, name))
+        if vel is not None and (not isinstance(vel, (list, tuple)) or len(vel) != 2):
+            raise TypeError("%s: the velocities of %s must be None or a pair (vel0, vel2)" % (who, name))
+    for name, pos in (("pos_a", pos_a), ("pos_b", pos_b)):
+        _check_positions(*pos, "%s: %s" % (who, name))
+    _check_same_batch(pos_a[0], pos_b[0], who)
+    lo, hi, delay = _check_gap_queries(pos_a[0], lo, hi, delay, who)      # before the solves: a bad query costs none
+    splines, solutions = [], []
+    for pos, vel in ((pos_a, vel_a), (pos_b, vel_b)):
+        vel0, vel2 = vel if vel is not None else (None, None)
+        solution = min_time_solve(*pos, gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
+        splines.append(tuple(pos) + tuple(solution[:3]) + (tuple(vel) if vel is not None else ()))
+        solutions.append(tuple(solution))
+    return tuple(trajectory_tracking(splines[0], splines[1], lo, hi, delay)) + (solutions[0], solutions[1])
 
 
 def clear_pool():

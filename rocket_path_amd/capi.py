@@ -114,6 +114,12 @@ SIGNATURES = {
     "rp_batch_extrema_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "rp_trajectory_gap": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp,
                                          ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rp_trajectory_tracking": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
+                                              _vp, ctypes.POINTER(_vp)]),
+    "rp_trajectory_tracking_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
+                                                  _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp]),
+    "rp_trajectory_tracking_jvp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
+                                                  _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_integrals": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_integrals_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp,
                                                    ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp]),
@@ -266,6 +272,46 @@ def trajectory_gap(device, stream, n, k, spline_a, spline_b, d_lo=None, d_hi=Non
     vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
     check(load_library().rp_trajectory_gap(int(device), vp(stream), int(n), int(k), pointer_table(spline_a), pointer_table(spline_b), vp(d_lo),
                                            vp(d_hi), vp(d_delay), gap_table(value), gap_table(time)))
+
+
+def tracking_table(addresses):
+    """Three device addresses (ints; None / 0: NULL) as a `double *const [3]` table of the tracking entries, in the order (gap_int, gap_sq,
+    relvel_sq); None gives a NULL table."""
+    if addresses is None:
+        return None
+    addresses = list(addresses)
+    if len(addresses) != 3:
+        raise ValueError("a tracking table has three entries, got %d" % len(addresses))
+    return (_vp * 3)(*[a if a else None for a in addresses])
+
+
+def trajectory_tracking(device, stream, n, k, spline_a, spline_b, d_lo=None, d_hi=None, d_delay=None, value=None):
+    """rp_trajectory_tracking: the integrals of D, D^2 and (dD/dt)^2, D(t) = pos_A(t) - pos_B(t - delay), over the windows [lo, hi] (n, k)
+    clamped to the two splines' common time domain (None / 0: -inf, +inf, a delay of 0).  `spline_a`, `spline_b`: eight addresses each, as
+    for trajectory_eval; `value`: three addresses in the order (gap_int, gap_sq, relvel_sq), None / 0 entries not wanted."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_tracking(int(device), vp(stream), int(n), int(k), pointer_table(spline_a), pointer_table(spline_b),
+                                                vp(d_lo), vp(d_hi), vp(d_delay), tracking_table(value)))
+
+
+def trajectory_tracking_vjp(device, stream, n, k, spline_a, spline_b, d_lo=None, d_hi=None, d_delay=None, g=None, spline_a_bar=None,
+                            spline_b_bar=None, d_lo_bar=None, d_hi_bar=None, d_delay_bar=None):
+    """rp_trajectory_tracking_vjp: `g` the three upstream gradients (None entries, or None: zeros), `spline_a_bar`, `spline_b_bar` the eight
+    output addresses each and d_lo_bar, d_hi_bar, d_delay_bar (n, k) (None: not wanted)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_tracking_vjp(int(device), vp(stream), int(n), int(k), pointer_table(spline_a), pointer_table(spline_b),
+                                                    vp(d_lo), vp(d_hi), vp(d_delay), tracking_table(g), pointer_table(spline_a_bar),
+                                                    pointer_table(spline_b_bar), vp(d_lo_bar), vp(d_hi_bar), vp(d_delay_bar)))
+
+
+def trajectory_tracking_jvp(device, stream, n, k, spline_a, spline_b, d_lo=None, d_hi=None, d_delay=None, spline_a_dot=None, spline_b_dot=None,
+                            d_lo_dot=None, d_hi_dot=None, d_delay_dot=None, value_dot=None):
+    """rp_trajectory_tracking_jvp: `spline_a_dot`, `spline_b_dot` the eight tangent addresses each and d_lo_dot, d_hi_dot, d_delay_dot (None:
+    zeros), `value_dot` the three output addresses (None entries: not wanted)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_tracking_jvp(int(device), vp(stream), int(n), int(k), pointer_table(spline_a), pointer_table(spline_b),
+                                                    vp(d_lo), vp(d_hi), vp(d_delay), pointer_table(spline_a_dot), pointer_table(spline_b_dot),
+                                                    vp(d_lo_dot), vp(d_hi_dot), vp(d_delay_dot), tracking_table(value_dot)))
 
 
 def integrals_table(addresses):

@@ -184,5 +184,16 @@ hipError_t launch_integrals_hvp(size_t n, size_t k, const double *const d_spline
 // delay n x k each; null: -inf / +inf / 0), and a time at which each is attained: tables of two in the order (gap_min, gap_max)
 hipError_t launch_gap(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
                       const double *d_hi, const double *d_delay, double *const d_value[2], double *const d_time[2], hipStream_t stream);
+// the integrals of D, D^2 and D'^2 with D(t) = pos_A(t) - pos_B(t - delay) over the same windows: a table of three in the order (gap_int,
+// gap_sq, relvel_sq); their reverse rule (d_g: the three upstream gradients, null: zeros; one launch per spline) and forward rule
+hipError_t launch_tracking(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
+                           const double *d_hi, const double *d_delay, double *const d_value[3], hipStream_t stream);
+hipError_t launch_tracking_vjp(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
+                               const double *d_hi, const double *d_delay, const double *const d_g[3], double *const d_spline_a_bar[8],
+                               double *const d_spline_b_bar[8], double *d_lo_bar, double *d_hi_bar, double *d_delay_bar, hipStream_t stream);
+hipError_t launch_tracking_jvp(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
+                               const double *d_hi, const double *d_delay, const double *const d_spline_a_dot[8],
+                               const double *const d_spline_b_dot[8], const double *d_lo_dot, const double *d_hi_dot, const double *d_delay_dot,
+                               double *const d_value_dot[3], hipStream_t stream);
 
 }  // namespace rp

@@ -1128,6 +1128,59 @@ int rp_trajectory_gap(int device, void *stream, size_t n, size_t k, const double
     return RP_OK;
 }
 
+// the tracking integrals between two splines over a window and their first derivatives: rp_trajectory_gap's argument rules
+static int check_tracking(const char *who, int device, const double *const d_spline_a[8], const double *const d_spline_b[8], size_t n, size_t k,
+                          std::initializer_list<const void *> arrays, bool any_output)
+{
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", who, device);
+    int st = check_spline(who, "d_spline_a", d_spline_a);
+    if (st == RP_OK) st = check_spline(who, "d_spline_b", d_spline_b);
+    if (st == RP_OK) st = check_queries(who, n, k, nullptr, nullptr, arrays, any_output);
+    return st;
+}
+
+int rp_trajectory_tracking(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8],
+                           const double *d_lo, const double *d_hi, const double *d_delay, double *const d_value[3])
+{
+    double *const *v = d_value ? d_value : kNoOutputs;
+    const int st = check_tracking(__func__, device, d_spline_a, d_spline_b, n, k, {d_lo, d_hi, d_delay, v[0], v[1], v[2]}, any_of(v, 3));
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_tracking(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, v, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_trajectory_tracking_vjp(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8],
+                               const double *d_lo, const double *d_hi, const double *d_delay, const double *const d_g[3],
+                               double *const d_spline_a_bar[8], double *const d_spline_b_bar[8], double *d_lo_bar, double *d_hi_bar,
+                               double *d_delay_bar)
+{
+    const double *const *g = d_g ? d_g : kNoInputs;
+    double *const *bars_a = d_spline_a_bar ? d_spline_a_bar : kNoOutputs, *const *bars_b = d_spline_b_bar ? d_spline_b_bar : kNoOutputs;
+    const int st = check_tracking(__func__, device, d_spline_a, d_spline_b, n, k, {d_lo, d_hi, d_delay, g[0], g[1], g[2], d_lo_bar, d_hi_bar, d_delay_bar},
+                                  d_lo_bar || d_hi_bar || d_delay_bar || any_of(bars_a, 8) || any_of(bars_b, 8));
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_tracking_vjp(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, g, bars_a, bars_b, d_lo_bar, d_hi_bar, d_delay_bar,
+                                   (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_trajectory_tracking_jvp(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8],
+                               const double *d_lo, const double *d_hi, const double *d_delay, const double *const d_spline_a_dot[8],
+                               const double *const d_spline_b_dot[8], const double *d_lo_dot, const double *d_hi_dot, const double *d_delay_dot,
+                               double *const d_value_dot[3])
+{
+    double *const *out = d_value_dot ? d_value_dot : kNoOutputs;
+    const int st = check_tracking(__func__, device, d_spline_a, d_spline_b, n, k,
+                                  {d_lo, d_hi, d_delay, d_lo_dot, d_hi_dot, d_delay_dot, out[0], out[1], out[2]}, any_of(out, 3));
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_tracking_jvp(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_spline_a_dot ? d_spline_a_dot : kNoInputs,
+                                   d_spline_b_dot ? d_spline_b_dot : kNoInputs, d_lo_dot, d_hi_dot, d_delay_dot, out, (hipStream_t)stream));
+    return RP_OK;
+}
+
 // the integrals over a window, their first derivatives and the reverse rule's derivative along a direction
 int rp_trajectory_integrals(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                             double *const d_value[4])

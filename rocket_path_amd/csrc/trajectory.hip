@@ -8,6 +8,8 @@
 //   ... their first derivatives                k_jvp_integrals, k_vjp_integrals                 section 16
 //   ... the reverse rule along a direction     k_window_hvp                                     section 19
 //   the extreme gap between two splines        k_gap                                            section 18
+//   the tracking integrals of two splines      k_tracking                                       section 20
+//   ... their first derivatives                k_tracking_jvp, k_tracking_vjp                   section 20
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
 // rp_batch_integrals_device and rp_batch_sample*; the launchers are at the end of the file.
@@ -1530,6 +1532,462 @@ k_gap(FromArrays a, FromArrays b, size_t n, size_t k, int P, const double *__res
     });
 }
 
+// ---- how far apart two splines are on average: the integrals of the gap D, of D^2 and of D'^2 over a window (rp_trajectory_tracking, _vjp,
+// _jvp) ----
+// D, the common domain, the clamped window [a, b], the two knots clamped into it and the segment each spline is in on a piece are k_gap's,
+// in its expressions (track_window, track_pieces).  On a piece [c, e] with (X, V, A) the differences of the two selected segments' pos, vel,
+// acc at their local starts s_A, s_B (the evaluator's expressions), J the difference of their jrk0 and w = e - c from the GLOBAL ends, each
+// integral is a polynomial in w in shifted form from the piece's own start (track_values): no antiderivative is differenced.  A query's
+// output is piece 0 + piece 1 + piece 2 in that order, exactly 0.0 where a == b, NaN where !(a <= b) or the NaN rule holds.  Selects only;
+// the three pieces are a loop of three trips that the compiler is told to keep.
+// The derivative rule.  For one piece, with C_A, C_B = (x0, va, acc0, jrk0) of the selected segments:
+//     dI = S_i mA_i dC_A,i - S_i mB_i dC_B,i + P_A ds_A - P_B ds_B + f(w) dw
+//     mA_i = the integral over u in [0, w] of g'(u) phi_i(s_A + u), mB_i the same with s_B
+//     gap_int: g' = 1, phi = (1, s, s^2 / 2, s^3 / 6)      gap_sq: g' = 2 D, the same phi      relvel_sq: g' = 2 D', phi = (0, 1, s, s^2 / 2)
+//     P_A = the integral of g' vel_A(s_A + u) (acc_A for relvel_sq), P_B likewise; f the integrand at the piece's end
+// all polynomials in w from the local states at the piece's start (gap_moments, rate_moments); P_A - P_B = f(w) - f(0) holds, unused.  With
+// s_A = c - off_A, s_B = c - off_B, w = e - c, off_A in {0, k_A}, off_B in {delay, k_B}, the tangent of a piece end is that of where it came
+// from: a = lo -> lo, a = the clamp S = delay > 0 -> delay (START), a = +0.0 -> nothing; b = hi -> hi, b = T_A -> d0A + d1A (END_A, first among
+// equals), b = delay + T_B -> delay + d0B + d1B (END_B); a knot k_A -> d0A, k_B -> delay + d0B; a knot clamped to an end carries that end's
+// tangent (its piece has length zero; track_pieces names a piece end a, b, k_A or k_B, and the kernels resolve a and b once per query).
+// f is continuous across a knot, so what an inner end carries cancels between its two pieces up to
+// rounding: ties between classes change nothing.  START needs delay > 0: at a delay of exactly 0 the start is the constant +0.0 (the kink of
+// section 18).  Forward mode contracts the rule with segment_tangents' tangents; reverse mode adds the m's, weighted by the upstream
+// gradients, to segment_chain's four sums per segment and the end terms to two sums for the durations -- ten sums per spline, one spline per
+// launch (k_tracking_vjp<SIDE>; side A's launch also writes lo_bar, hi_bar, delay_bar).
+// Nine to thirteen n x k arrays travel through the two derivative kernels.  Left alone, the compiler carries one 64-bit address per array from
+// element to element (and one per gradient row from trip to trip): some thirty registers that hold no data.  An element index that it cannot
+// see through is added to each base where it is used instead: one instruction per access.
+__device__ __forceinline__ size_t opaque_index(size_t at)
+{
+    asm volatile("" : "+v"(at));
+    return at;
+}
+
+__device__ __forceinline__ int opaque_place(int q)
+{
+    asm volatile("" : "+v"(q));
+    return q;
+}
+
+// (the same for what a thread derives from its own number once and would keep for the whole launch: a value of the trip instead)
+__device__ __forceinline__ int opaque_uniform(int g)
+{
+    asm volatile("" : "+s"(g));
+    return g;
+}
+
+using Out3 = Table<double, 3>;                 // gap_int, gap_sq, relvel_sq
+using In3 = Table<const double, 3>;
+
+struct TrackLds {
+    EvalLds a, b;
+    double Ta[kTrajProblems], Tb[kTrajProblems];
+};
+
+enum { kPtNone, kPtLo, kPtStart, kPtHi, kPtEndA, kPtEndB };      // where a window end came from
+enum { kEndA, kEndB, kEndKnotA, kEndKnotB };                     // what a piece's end is: the window's a or b, or a knot inside it
+
+struct TrackWindow {
+    double a, b, kA, kB, delay;
+    int cls_a, cls_b;
+    bool ok, b_first;
+};
+
+// gap_query's domain, window and knots.  SAFE (the reverse rule): a query without an answer walks the empty window at 0 with a delay of 0,
+// so that its terms are finite and count with upstream gradients of zero
+template <bool SAFE>
+__device__ __forceinline__ TrackWindow track_window(double d0A, double TA, double d0B, double TB, double lo, double hi, double delay)
+{
+    TrackWindow win;
+    const double EB = delay + TB;
+    const double S = delay > 0.0 ? delay : 0.0, E = EB < TA ? EB : TA;      // the common domain; T_A among equals
+    win.a = lo > S ? lo : (lo != lo ? lo : S);
+    win.b = hi < E ? hi : (hi != hi ? hi : E);
+    win.ok = win.a <= win.b && finite_(delay) && EB == EB;
+    win.cls_a = lo > S ? kPtLo : (delay > 0.0 ? kPtStart : kPtNone);
+    win.cls_b = hi < E ? kPtHi : (EB < TA ? kPtEndB : kPtEndA);
+    win.delay = delay;
+    if (SAFE && !win.ok) win.a = win.b = win.delay = 0.0;
+    win.kA = d0A;
+    win.kB = win.delay + d0B;
+    win.b_first = win.kB < win.kA;      // the knots in time order, k_A first among equals
+    return win;
+}
+
+struct TrackPiece {
+    double w, sA, sB;
+    int seg_a, seg_b, cls_c, cls_e;
+};
+
+template <class Each> __device__ __forceinline__ void track_pieces(const TrackWindow &win, Each each)
+{
+    double c = win.a;
+    int cls_c = kEndA;
+#pragma nounroll
+    for (int piece = 0; piece < 3; ++piece) {
+        const bool kb = (piece == 0) == win.b_first;      // the knot that ends the piece (the last piece ends at b)
+        const double knot = kb ? win.kB : win.kA;
+        const bool before = knot < win.a, after = knot > win.b;
+        const double e = piece == 2 ? win.b : (before ? win.a : (after ? win.b : knot));
+        const int cls_e = piece == 2 ? kEndB : (before ? kEndA : (after ? kEndB : (kb ? kEndKnotB : kEndKnotA)));
+        TrackPiece p;
+        p.seg_a = win.kA <= c;
+        p.seg_b = win.kB <= c;
+        p.sA = p.seg_a ? c - win.kA : c;
+        p.sB = p.seg_b ? c - win.kB : c - win.delay;
+        p.w = e - c;
+        p.cls_c = cls_c;
+        p.cls_e = cls_e;
+        each(p);
+        c = e;
+        cls_c = cls_e;
+    }
+}
+
+// the two selected segments at their local starts: the gap's (X, V, A, J) and each side's own (vel, acc, jrk0)
+struct TrackState { double X, V, A, J, VA, AA, JA, VB, AB, JB; };
+
+__device__ __forceinline__ TrackState track_state(const SegmentConst &ca, const SegmentConst &cb, const TrackPiece &p)
+{
+    TrackState t;
+    double XA, XB;
+    local_state(ca, p.sA, XA, t.VA, t.AA);
+    local_state(cb, p.sB, XB, t.VB, t.AB);
+    t.JA = ca.jrk0;
+    t.JB = cb.jrk0;
+    t.X = XA - XB;
+    t.V = t.VA - t.VB;
+    t.A = t.AA - t.AB;
+    t.J = t.JA - t.JB;
+    return t;
+}
+
+__device__ __forceinline__ SegmentConst eval_const(const double (&c)[2][4][kTrajProblems], int seg, int q)
+{
+    return SegmentConst{c[seg][0][q], c[seg][1][q], c[seg][2][q], c[seg][3][q], 0.0, 0.0};
+}
+
+// one piece's contributions: the integrals over [0, w] of D, D^2, D'^2 with D(u) = X + V u + A u^2 / 2 + J u^3 / 6
+__device__ __forceinline__ void track_values(const TrackState &t, double w, double v[3])
+{
+    const double X = t.X, V = t.V, A = t.A, J = t.J, third = 1.0 / 3.0;
+    v[0] = w * (X + (w * 0.5) * (V + (w * third) * (A + (w * 0.25) * J)));
+    const double t6 = (A * J) * (1.0 / 36.0) + w * ((J * J) * (1.0 / 252.0));
+    const double t5 = ((A * A) * 0.25 + (V * J) * third) * 0.2 + w * t6;
+    const double t4 = (V * A + (X * J) * third) * 0.25 + w * t5;
+    const double t3 = (V * V + X * A) * third + w * t4;
+    v[1] = w * (X * X + w * (X * V + w * t3));
+    v[2] = w * (V * V + w * (V * A + (w * third) * ((A * A + V * J) + w * (0.75 * (A * J) + (0.15 * w) * (J * J)))));
+}
+
+__device__ __forceinline__ void tracking_query(const TrackLds &L, int q, double lo, double hi, double delay, double out[3])
+{
+    const TrackWindow win = track_window<false>(L.a.d0[q], L.Ta[q], L.b.d0[q], L.Tb[q], lo, hi, delay);
+    double sum[3] = {0.0, 0.0, 0.0};
+    track_pieces(win, [&](const TrackPiece &p) {
+        double v[3];
+        track_values(track_state(eval_const(L.a.c, p.seg_a, q), eval_const(L.b.c, p.seg_b, q), p), p.w, v);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) sum[i] += v[i];
+    });
+#pragma unroll
+    for (int i = 0; i < 3; ++i) out[i] = win.ok ? (win.a == win.b ? 0.0 : sum[i]) : quiet_nan();
+}
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_tracking(FromArrays a, FromArrays b, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
+           const double *__restrict__ delay, Out3 value)
+{
+    __shared__ TrackLds L;
+    auto stage_problem = [&](int q, size_t i) {
+        Knots ka = a.load(i), kb = b.load(i);
+        ka.check();
+        kb.check();
+        stage_eval(L.a, q, ka);
+        stage_eval(L.b, q, kb);
+        L.Ta[q] = ka.t0 + ka.t1;
+        L.Tb[q] = kb.t0 + kb.t1;
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k;
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double la, lb, ha, hb, da = 0.0, db = 0.0, A[3], B[3];
+            load_window(lo, hi, e_first + e, two, la, lb, ha, hb);
+            if (delay) load_pair(delay, e_first + e, two, da, db);
+            tracking_query(L, qa, la, ha, da, A);
+            tracking_query(L, qb, lb, hb, db, B);
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                if (value.p[i]) store_pair(value.p[i], e_first + e, A[i], B[i], two);
+        });
+    });
+}
+
+// The moments of one piece that both derivative rules are made of, one output at a time and in the outputs' order so that no more than one
+// output's numbers are live: Em = the integral of D u^m, Qm = that of D' u^m over [0, w].  With phi_i(s + u) expanded in u the rule's sums
+// regroup: S_i m_i dC_i = the integral of g'(u) times the tangent cubic of the segment at s + u, so with (Xd, Vd, Ad, Jd) the tangent of the
+// piece's own (X, V, A, J) at fixed u -- the tangent cubics' local states at s_A, s_B, their difference, plus (vel, acc, jrk0) of each side
+// times ds_A, ds_B --
+//     d gap_int = Xd w + Vd w^2 / 2 + Ad w^3 / 6 + Jd w^4 / 24 + D(w) dw
+//     d gap_sq = 2 (Xd E0 + Vd E1 + Ad E2 / 2 + Jd E3 / 6) + D(w)^2 dw            d relvel_sq = 2 (Vd Q0 + Ad Q1 + Jd Q2 / 2) + D'(w)^2 dw
+// the same numbers as the rule's m_i and P, contracted in another order.  Reverse mode reads the same lines backwards: the upstream gradients
+// weight the coefficients of (Xd, Vd, Ad, Jd) into (Xb, Vb, Ab, Jb), and a side's four sums are k_trajectory_vjp's w0 .. w3 of (Xb, Vb, Ab) at
+// its local start, with Jb on the last.
+__device__ __forceinline__ double piece_end_gap(const TrackState &t, double w) { return t.X + w * (t.V + (w * 0.5) * (t.A + (w * (1.0 / 3.0)) * t.J)); }
+__device__ __forceinline__ double piece_end_rate(const TrackState &t, double w) { return t.V + w * (t.A + (w * 0.5) * t.J); }
+
+__device__ __forceinline__ void gap_moments(const TrackState &t, double w, double &E0, double &E1, double &E2, double &E3)
+{
+    const double X = t.X, V = t.V, A = t.A, J = t.J, w2 = w * w;
+    E0 = w * (X + w * (V * 0.5 + w * (A * (1.0 / 6.0) + (w * (1.0 / 24.0)) * J)));
+    E1 = w2 * (X * 0.5 + w * (V * (1.0 / 3.0) + w * (A * 0.125 + (w * (1.0 / 30.0)) * J)));
+    E2 = (w2 * w) * (X * (1.0 / 3.0) + w * (V * 0.25 + w * (A * 0.1 + (w * (1.0 / 36.0)) * J)));
+    E3 = (w2 * w2) * (X * 0.25 + w * (V * 0.2 + w * (A * (1.0 / 12.0) + (w * (1.0 / 42.0)) * J)));
+}
+
+__device__ __forceinline__ void rate_moments(const TrackState &t, double w, double &Q0, double &Q1, double &Q2)
+{
+    const double V = t.V, A = t.A, J = t.J;
+    Q0 = w * (V + (w * 0.5) * (A + (w * (1.0 / 3.0)) * J));
+    Q1 = (w * w) * (V * 0.5 + w * (A * (1.0 / 3.0) + (w * 0.125) * J));
+    Q2 = (w * w * w) * (V * (1.0 / 3.0) + w * (A * 0.25 + (w * 0.1) * J));
+}
+
+// ---- forward mode: tangents on both splines' eight parameters and on lo, hi, delay in, tangents of the three integrals out ----
+struct TrackJvpLds {
+    JvpLds a, b;
+    double Ta[kTrajProblems], Tb[kTrajProblems], Ta_dot[kTrajProblems], Tb_dot[kTrajProblems];
+};
+
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(4)))
+k_tracking_jvp(FromArrays a, FromArrays b, Spline8 a_dot, Spline8 b_dot, size_t n, size_t k, int P, const double *__restrict__ lo,
+               const double *__restrict__ hi, const double *__restrict__ delay, const double *__restrict__ lo_dot,
+               const double *__restrict__ hi_dot, const double *__restrict__ delay_dot, Out3 value_dot)
+{
+    __shared__ TrackJvpLds L;
+    auto stage_problem = [&](int q, size_t at) {
+        const size_t i = opaque_index(at);
+        const DirectedDurations da = stage_tangents(L.a, q, i, a.s, a_dot);
+        L.Ta[q] = da.t0 + da.t1;
+        L.Ta_dot[q] = da.t0d + da.t1d;
+        const DirectedDurations db = stage_tangents(L.b, q, i, b.s, b_dot);
+        L.Tb[q] = db.t0 + db.t1;
+        L.Tb_dot[q] = db.t0d + db.t1d;
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k;
+        auto query = [&](int q, double lo_q, double hi_q, double dl_q, double lo_d, double hi_d, double dl_d, double out[3]) {
+            const TrackWindow win = track_window<false>(L.a.d0[q], L.Ta[q], L.b.d0[q], L.Tb[q], lo_q, hi_q, dl_q);
+            // the tangent of a piece end, by where it came from
+            const double d0Ad = L.a.d0_dot[q], kBd = dl_d + L.b.d0_dot[q];
+            const double ad = win.cls_a == kPtLo ? lo_d : (win.cls_a == kPtStart ? dl_d : 0.0);
+            const double bd = win.cls_b == kPtHi ? hi_d : (win.cls_b == kPtEndA ? L.Ta_dot[q] : dl_d + L.Tb_dot[q]);
+            auto tangent = [&](int cls) { return cls == kEndA ? ad : (cls == kEndB ? bd : (cls == kEndKnotA ? d0Ad : kBd)); };
+            double sum[3] = {0.0, 0.0, 0.0};
+            track_pieces(win, [&](const TrackPiece &p) {
+                const TrackState t = track_state(eval_const(L.a.c, p.seg_a, q), eval_const(L.b.c, p.seg_b, q), p);
+                const double cd = tangent(p.cls_c), ed = tangent(p.cls_e);
+                const double dsA = cd - (p.seg_a ? d0Ad : 0.0), dsB = cd - (p.seg_b ? kBd : dl_d), dw = ed - cd;
+                // the tangent cubics' local states, and the tangent of the piece's own state at fixed u
+                double XAd, VAd, AAd, XBd, VBd, ABd;
+                const SegmentConst da = eval_const(L.a.t, p.seg_a, q), db = eval_const(L.b.t, p.seg_b, q);
+                local_state(da, p.sA, XAd, VAd, AAd);
+                local_state(db, p.sB, XBd, VBd, ABd);
+                const double Xd = (XAd - XBd) + (t.VA * dsA - t.VB * dsB), Vd = (VAd - VBd) + (t.AA * dsA - t.AB * dsB);
+                const double Ad = (AAd - ABd) + (t.JA * dsA - t.JB * dsB), Jd = da.jrk0 - db.jrk0;
+                const double w = p.w, Dw = piece_end_gap(t, w), Vw = piece_end_rate(t, w);
+                sum[0] += w * (Xd + (w * 0.5) * (Vd + (w * (1.0 / 3.0)) * (Ad + (w * 0.25) * Jd))) + Dw * dw;
+                {
+                    double E0, E1, E2, E3;
+                    gap_moments(t, w, E0, E1, E2, E3);
+                    sum[1] += 2.0 * (Xd * E0 + Vd * E1 + (0.5 * Ad) * E2 + (Jd * (1.0 / 6.0)) * E3) + (Dw * Dw) * dw;
+                }
+                {
+                    double Q0, Q1, Q2;
+                    rate_moments(t, w, Q0, Q1, Q2);
+                    sum[2] += 2.0 * (Vd * Q0 + Ad * Q1 + (0.5 * Jd) * Q2) + (Vw * Vw) * dw;
+                }
+            });
+#pragma unroll
+            for (int i = 0; i < 3; ++i) out[i] = win.ok ? sum[i] : quiet_nan();
+        };
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            // (the pair's two queries one after the other, each with its own 8-byte loads -- the second's are cache hits: both queries' six
+            // inputs held at once cost the registers that four waves per SIMD leave; the results leave as 16-byte pairs)
+            const double inf = __builtin_inf();
+            const size_t at = opaque_index(e_first + e);
+            double A[3], B[3];
+#pragma nounroll
+            for (int second = 0; second < 2; ++second) {
+                const size_t el = opaque_index(at + (two ? second : 0));
+                double r[3];
+                query(second ? qb : qa, lo ? lo[el] : -inf, hi ? hi[el] : inf, delay ? delay[el] : 0.0, lo_dot ? lo_dot[el] : 0.0,
+                      hi_dot ? hi_dot[el] : 0.0, delay_dot ? delay_dot[el] : 0.0, r);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) { A[i] = second ? A[i] : r[i]; B[i] = r[i]; }
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                if (value_dot.p[i]) store_pair(value_dot.p[i], at, A[i], B[i], two);
+        });
+    });
+}
+
+// ---- reverse mode: one spline per launch (SIDE 0: A, 1: B).  reduce_rows over ten sums: the four per segment that segment_chain takes of
+// the launch's own spline, and what the piece ends put on its duration0 and duration1.  Side A's launch writes lo_bar, hi_bar and delay_bar.
+// A query whose outputs are NaN counts with upstream gradients of zero.
+struct TrackVjpLds {
+    VjpLds v;                           // the launch's own spline: segment_chain's constants and the eight results
+    double x0[2][kTrajProblems];
+    EvalLds o;                          // the other spline
+    double Tv[kTrajProblems], To[kTrajProblems];
+    double g[3][kTrajBlock];            // each thread's upstream gradients of the query it is at (read per piece, not kept in registers)
+};
+
+template <int SIDE>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(4)))
+k_tracking_vjp(FromArrays a, FromArrays b, size_t n, size_t k, int P, int G, const double *__restrict__ lo, const double *__restrict__ hi,
+               const double *__restrict__ delay, In3 g, SplineBar8 bar, double *__restrict__ lo_bar, double *__restrict__ hi_bar,
+               double *__restrict__ delay_bar)
+{
+    __shared__ TrackVjpLds L;
+    auto stage_problem = [&](int place, size_t at) {
+        const int q = opaque_place(place);
+        const size_t i = opaque_index(at);
+        Knots own = SIDE ? b.load(i) : a.load(i), other = SIDE ? a.load(i) : b.load(i);
+        own.check();
+        other.check();
+        stage_vjp(L.v, q, own);
+        L.x0[0][q] = own.p0;
+        L.x0[1][q] = own.p1;
+        L.Tv[q] = own.t0 + own.t1;
+        stage_eval(L.o, q, other);
+        L.To[q] = other.t0 + other.t1;
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
+        // one query, one piece at a time.  S: the ten sums
+        auto query = [&](int q, double lo_q, double hi_q, double dl_q, double g0, double g1, double g2, double *S, double &lo_b, double &hi_b,
+                         double &dl_b) {
+            const double d0v = L.v.d0[q], d0o = L.o.d0[q], Tv = L.Tv[q], To = L.To[q];
+            const TrackWindow win = track_window<true>(SIDE ? d0o : d0v, SIDE ? To : Tv, SIDE ? d0v : d0o, SIDE ? Tv : To, lo_q, hi_q, dl_q);
+            const int me = opaque_place((int)threadIdx.x);
+            L.g[0][me] = win.ok ? g0 : 0.0;      // ok: of the query as given
+            L.g[1][me] = win.ok ? g1 : 0.0;
+            L.g[2][me] = win.ok ? g2 : 0.0;
+            // what the window's a and b take, what the launch's own duration0 takes (its knot as a piece end and as an offset), what the delay
+            // takes (B's knot and B's offset)
+            double bar_a = 0.0, bar_b = 0.0, dl = 0.0, carry = 0.0;
+            double &own0 = S[8];
+            auto route = [&](int cls, double v) {
+                bar_b += cls == kEndB ? v : 0.0;
+                if (SIDE == 0) {
+                    bar_a += cls == kEndA ? v : 0.0;
+                    own0 += cls == kEndKnotA ? v : 0.0;
+                    dl += cls == kEndKnotB ? v : 0.0;
+                } else {
+                    own0 += cls == kEndKnotB ? v : 0.0;
+                }
+            };
+            track_pieces(win, [&](const TrackPiece &p) {
+                const int seg_v = SIDE ? p.seg_b : p.seg_a, seg_o = SIDE ? p.seg_a : p.seg_b;
+                auto state = [&](int at) {
+                    const SegmentConst cv{L.x0[seg_v][at], L.v.c[seg_v][0][at], L.v.c[seg_v][3][at], L.v.c[seg_v][4][at], 0.0, 0.0};
+                    const SegmentConst co = eval_const(L.o.c, seg_o, at);
+                    return track_state(SIDE ? co : cv, SIDE ? cv : co, p);
+                };
+                // the gradients on the tangent of the piece's state, (Xb, Vb, Ab, Jb), and on its length, F
+                const double gq[3] = {L.g[0][me], L.g[1][me], L.g[2][me]};
+                const double w = p.w, w2 = w * (w * 0.5), w3 = w2 * (w * (1.0 / 3.0));
+                double Xb = gq[0] * w, Vb = gq[0] * w2, Ab = gq[0] * w3, Jb = gq[0] * (w3 * (w * 0.25));
+                {
+                    const TrackState t = state(q);
+                    {
+                        double E0, E1, E2, E3;
+                        gap_moments(t, w, E0, E1, E2, E3);
+                        const double h = 2.0 * gq[1];
+                        Xb += h * E0; Vb += h * E1; Ab += gq[1] * E2; Jb += gq[1] * (E3 * (1.0 / 3.0));
+                    }
+                    {
+                        double Q0, Q1, Q2;
+                        rate_moments(t, w, Q0, Q1, Q2);
+                        const double h = 2.0 * gq[2];
+                        Vb += h * Q0; Ab += h * Q1; Jb += gq[2] * Q2;
+                    }
+                }
+                // the launch's own side: k_trajectory_vjp's weights at its local start; B enters the gap with a minus
+                {
+                    const double s = SIDE ? p.sB : p.sA, h2 = s * (s * 0.5), h3 = h2 * (s * (1.0 / 3.0));
+                    const double W[4] = {Xb, Xb * s + Vb, Xb * h2 + Vb * s + Ab, Xb * h3 + Vb * h2 + Ab * s + Jb};
+#pragma unroll
+                    for (int f = 0; f < 4; ++f) {
+                        const double Wf = SIDE ? -W[f] : W[f];
+                        S[f] += seg_v ? 0.0 : Wf;
+                        S[4 + f] += seg_v ? Wf : 0.0;
+                    }
+                }
+                // the piece's state and each side's (vel, acc, jrk0) at its local start once more (read again, not kept: the moments above need
+                // the registers)
+                const TrackState t = state(opaque_place(q));
+                const double Dw = piece_end_gap(t, w), Vw = piece_end_rate(t, w);
+                const double F = gq[0] * Dw + gq[1] * (Dw * Dw) + gq[2] * (Vw * Vw);
+                const double PA = Xb * t.VA + Vb * t.AA + Ab * t.JA, PB = Xb * t.VB + Vb * t.AB + Ab * t.JB;
+                // ds_A = dc - doff_A, ds_B = dc - doff_B, dw = de - dc
+                route(p.cls_c, carry + ((PA - PB) - F));
+                carry = F;
+                if (SIDE == 0) {
+                    own0 -= p.seg_a ? PA : 0.0;
+                    dl += PB;
+                } else {
+                    own0 += p.seg_b ? PB : 0.0;
+                }
+            });
+            route(kEndB, carry);
+            // ... and where each window end came from
+            const bool own_end = win.cls_b == (SIDE ? kPtEndB : kPtEndA);
+            S[8] += own_end ? bar_b : 0.0;
+            S[9] += own_end ? bar_b : 0.0;
+            if (SIDE == 0) {
+                lo_b = win.cls_a == kPtLo ? bar_a : 0.0;
+                hi_b = win.cls_b == kPtHi ? bar_b : 0.0;
+                dl_b = (dl + (win.cls_a == kPtStart ? bar_a : 0.0)) + (win.cls_b == kPtEndB ? bar_b : 0.0);
+            } else {
+                lo_b = hi_b = dl_b = 0.0;
+            }
+        };
+        // (a pair's two queries one after the other, each with its own 8-byte loads and stores: both queries' nine inputs and three results held
+        // at once cost the registers of a wave per SIMD)
+        reduce_rows<10>(opaque_uniform(G), here, p_first, k, [&](int q, size_t at, bool two, double *S) {
+            const double inf = __builtin_inf();
+#pragma nounroll
+            for (int second = 0; second < (two ? 2 : 1); ++second) {
+                const size_t el = opaque_index(at + second);
+                double lo_b, hi_b, dl_b;
+                query(q, lo ? lo[el] : -inf, hi ? hi[el] : inf, delay ? delay[el] : 0.0, g.p[0] ? g.p[0][el] : 0.0, g.p[1] ? g.p[1][el] : 0.0,
+                      g.p[2] ? g.p[2][el] : 0.0, S, lo_b, hi_b, dl_b);
+                if (SIDE == 0) {
+                    if (lo_bar) lo_bar[el] = lo_b;
+                    if (hi_bar) hi_bar[el] = hi_b;
+                    if (delay_bar) delay_bar[el] = dl_b;
+                }
+            }
+        }, [&](int q, const double *S) {
+            const SegmentBar s0 = segment_chain(L.v, 0, q, S[0], S[1], S[2], S[3]);
+            const SegmentBar s1 = segment_chain(L.v, 1, q, S[4], S[5], S[6], S[7]);
+            route_bars(L.v.bar, q, s0, s1, s0.h + S[8], s1.h + S[9]);
+        });
+        // write_bars
+        __syncthreads();
+        if ((int)threadIdx.x < here) {
+            const int me = opaque_place((int)threadIdx.x);
+            const size_t i = p_first + (size_t)me;
+#pragma unroll
+            for (int f = 0; f < 8; ++f)
+                if (bar.p[f]) bar.p[f][i] = L.v.bar[f][me];
+        }
+    });
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -1781,6 +2239,53 @@ hipError_t launch_gap(size_t n, size_t k, const double *const d_spline_a[8], con
         hipLaunchKernelGGL(k_gap, grid, block, 0, stream, FromArrays{table_of<8>(d_spline_a)}, FromArrays{table_of<8>(d_spline_b)}, n, k, P, d_lo,
                            d_hi, d_delay, table_of<2>(d_value), table_of<2>(d_time));
     });
+}
+
+hipError_t launch_tracking(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
+                           const double *d_hi, const double *d_delay, double *const d_value[3], hipStream_t stream)
+{
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_tracking, grid, block, 0, stream, FromArrays{table_of<8>(d_spline_a)}, FromArrays{table_of<8>(d_spline_b)}, n, k, P,
+                           d_lo, d_hi, d_delay, table_of<3>(d_value));
+    });
+}
+
+hipError_t launch_tracking_jvp(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
+                               const double *d_hi, const double *d_delay, const double *const d_spline_a_dot[8],
+                               const double *const d_spline_b_dot[8], const double *d_lo_dot, const double *d_hi_dot, const double *d_delay_dot,
+                               double *const d_value_dot[3], hipStream_t stream)
+{
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_tracking_jvp, grid, block, 0, stream, FromArrays{table_of<8>(d_spline_a)}, FromArrays{table_of<8>(d_spline_b)},
+                           table_of<8>(d_spline_a_dot), table_of<8>(d_spline_b_dot), n, k, P, d_lo, d_hi, d_delay, d_lo_dot, d_hi_dot, d_delay_dot,
+                           table_of<3>(d_value_dot));
+    });
+}
+
+// one launch per spline, back to back on the stream: side A's (made if any of its eight gradients or of lo_bar, hi_bar, delay_bar is
+// wanted) writes the three per-query gradients, side B's is made if any of its eight is wanted
+hipError_t launch_tracking_vjp(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
+                               const double *d_hi, const double *d_delay, const double *const d_g[3], double *const d_spline_a_bar[8],
+                               double *const d_spline_b_bar[8], double *d_lo_bar, double *d_hi_bar, double *d_delay_bar, hipStream_t stream)
+{
+    bool side_a = d_lo_bar || d_hi_bar || d_delay_bar, side_b = false;
+    for (int f = 0; f < 8; ++f) {
+        side_a = side_a || d_spline_a_bar[f];
+        side_b = side_b || d_spline_b_bar[f];
+    }
+    hipError_t e = hipSuccess;
+    if (side_a)
+        e = launch_stateless<true>(n, k, [&](dim3 grid, dim3 block, int P, int G) {
+            hipLaunchKernelGGL(k_tracking_vjp<0>, grid, block, 0, stream, FromArrays{table_of<8>(d_spline_a)}, FromArrays{table_of<8>(d_spline_b)}, n,
+                               k, P, G, d_lo, d_hi, d_delay, table_of<3>(d_g), table_of<8>(d_spline_a_bar), d_lo_bar, d_hi_bar, d_delay_bar);
+        });
+    if (e == hipSuccess && side_b)
+        e = launch_stateless<true>(n, k, [&](dim3 grid, dim3 block, int P, int G) {
+            hipLaunchKernelGGL(k_tracking_vjp<1>, grid, block, 0, stream, FromArrays{table_of<8>(d_spline_a)}, FromArrays{table_of<8>(d_spline_b)}, n,
+                               k, P, G, d_lo, d_hi, d_delay, table_of<3>(d_g), table_of<8>(d_spline_b_bar), (double *)nullptr, (double *)nullptr,
+                               (double *)nullptr);
+        });
+    return e;
 }
 
 // ---- plot data by problem index: a range [first, first + count) of problems, wherever they lie in the batch ----
