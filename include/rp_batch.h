@@ -17,8 +17,15 @@
  *
  * Threading: a handle is not thread-safe (the reference is single-threaded: one GLUT
  * thread calls Problem::onKey).  Different handles may be used from different threads.
- * Calls that enqueue work are asynchronous on the batch's stream unless the doc says
- * "synchronous"; rp_batch_sync() waits.
+ * Batches that share a stream may be used from different threads too: the library takes a
+ * per-stream lock for the length of each call.
+ * Calls that enqueue work are asynchronous unless the doc says "synchronous"; rp_batch_sync()
+ * waits.  They are ordered as if all of them ran on the batch's stream: that is where they run,
+ * with one exception the caller cannot observe -- a fused rp_batch_solve that touches nothing
+ * but memory the library owns may run on an auxiliary stream the library keeps beside the
+ * batch's, so that back-to-back solves of DIFFERENT batches on one stream overlap (see
+ * rp_solve_overlap_set for the rule).  Every other call on any batch of the stream, the stream
+ * handle (rp_batch_stream), rp_batch_event_record and rp_batch_sync come after all of it.
  */
 #ifndef RP_BATCH_H
 #define RP_BATCH_H
@@ -64,7 +71,9 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      rp_trajectory_integrals, rp_trajectory_integrals_vjp, rp_trajectory_integrals_jvp and rp_batch_integrals_device (integrals over a
  *      window of times and their first derivatives; new entries only, the revision stays); rp_trajectory_eval_hvp (the second derivative
  *      of the evaluation along a direction; a new entry only, the revision stays); rp_trajectory_integrals_hvp (the second derivative of
- *      the integrals along a direction; a new entry only, the revision stays) */
+ *      the integrals along a direction; a new entry only, the revision stays); rp_solve_overlap_set and rp_solve_overlap_stats
+ *      (back-to-back fused solves of batches that share a stream overlap on an auxiliary stream; new entries only, no struct changes
+ *      size and nothing a caller can observe through an existing entry changes, so the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -162,8 +171,12 @@ RP_API int rp_device_id(int device, char *out, size_t len);
 RP_API void rp_params_default(rp_params *p);
 
 /* ---- lifetime ---- */
-/* `stream` is a hipStream_t the caller owns (e.g. torch's current stream) or NULL for a
- * stream the batch creates.  `device` is the HIP device ordinal. */
+/* `stream` is a hipStream_t the caller owns (e.g. torch's current stream), the stream of another batch (rp_batch_stream), or NULL for
+ * a stream the batch creates.  `device` is the HIP device ordinal.  A stream a batch created lives until the last batch on it has
+ * been destroyed: the batch that created it may be destroyed before or after the batches that borrowed it.  Work the caller itself
+ * enqueues on the stream is ordered after every library call made before it, except that fused solves still running on the
+ * auxiliary stream (rp_solve_overlap_set) may not have finished: they touch no memory the caller can reach, and every call that
+ * hands anything out waits for them. */
 RP_API int rp_batch_create(rp_batch **out, int variant, int dtype, size_t n, int device, void *stream);
 RP_API int rp_batch_destroy(rp_batch *b);
 RP_API int rp_batch_set_params(rp_batch *b, const rp_params *p);
@@ -621,6 +634,27 @@ RP_API int rp_batch_constraints_range(rp_batch *b, size_t first, size_t count, d
 RP_API int rp_batch_traffic_probe(rp_batch *b);
 RP_API int rp_batch_sync(rp_batch *b);
 RP_API int rp_batch_stream(rp_batch *b, void **stream);
+/* Overlap of back-to-back fused solves of batches that share a stream (process-wide switch and counters; new entries only, the
+ * revision stays).  A launch's wave slots empty out while its last chunks drain, and the next launch on the same stream waits for
+ * the previous one to retire; a caller who solves batch after batch on ONE stream gets what a caller with two streams gets if
+ * every second solve runs on an auxiliary stream the library keeps beside the caller's (one per stream and device, created at
+ * the first solve that may overlap, destroyed with the last batch on the stream).
+ * Which solves: rp_batch_solve in its fused form (steps_per_launch <= 0) as a single launch (not in rounds), of a batch with no
+ * bound solution buffer, no raw pointer handed out (rp_batch_field_ptr), outside an rp_pipeline, and -- in mode 1 -- of at least
+ * 65,536 problems.  Such a solve reads and writes nothing but memory the library owns.
+ * The ordering rule: eligible solves that follow one another directly alternate between the caller's stream and the auxiliary
+ * one.  The auxiliary stream waits, through an event recorded on the caller's stream, for everything the library enqueued there
+ * before -- in particular for the last operation of the batch being solved; a solve on the caller's stream of a batch whose
+ * previous solve ran on the auxiliary stream waits for that solve.  EVERY other call that takes a batch (set_problems, restart,
+ * step, every read-back, reduce, the derivative and trajectory entries, rp_batch_event_record, rp_batch_sync, rp_batch_stream,
+ * rp_batch_destroy ...) first makes the caller's stream wait for everything on the auxiliary one.  So consecutive solves of
+ * different batches overlap pairwise, and whatever can be observed through this API or through the stream is ordered as before;
+ * only the moment a solve's kernel runs relative to FOREIGN work on the stream is not, which no memory the caller owns depends on.
+ * mode 0: off, every call runs on the batch's stream.  1 (default): automatic.  2: every eligible solve whatever its size (tests).
+ * out[4]: solves sent to the auxiliary stream / solves kept on the caller's stream although eligible (alternation, or size in
+ * mode 1) / joins enqueued / solves excluded by the list above.  Counted in modes 1 and 2 since the library was loaded. */
+RP_API int rp_solve_overlap_set(int mode);
+RP_API int rp_solve_overlap_stats(unsigned long long out[4]);
 /* HIP events on the batch's own stream: record slot 0..7, elapsed between two recorded slots. */
 RP_API int rp_batch_event_record(rp_batch *b, int slot);
 RP_API int rp_batch_event_elapsed_ms(rp_batch *b, int slot_start, int slot_stop, float *ms);

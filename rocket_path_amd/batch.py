@@ -306,6 +306,17 @@ class Batch:
         return out
 
 
+def solve_overlap(mode):
+    """The process-wide switch of the overlap of back-to-back fused solves of batches that share a stream (rp_solve_overlap_set):
+    0 = off, 1 = automatic (the default), 2 = every eligible solve whatever its size."""
+    capi.solve_overlap_set(mode)
+
+
+def solve_overlap_stats():
+    """rp_solve_overlap_stats: {"aux", "kept", "joins", "excluded"}."""
+    return capi.solve_overlap_stats()
+
+
 class Pipeline:
     """rp_pipeline: positions in -> solutions out, job after job, the batches dealt onto `n_streams` streams (include/rp_batch.h).
     submit() enqueues one job (scheduling pass + fused gated solve, records into d_out in problem order) and returns its number."""

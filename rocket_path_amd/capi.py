@@ -132,6 +132,8 @@ SIGNATURES = {
     "rp_batch_constraints_range": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, _vp]),
     "rp_batch_sync": (ctypes.c_int, [_vp]),
     "rp_batch_stream": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "rp_solve_overlap_set": (ctypes.c_int, [ctypes.c_int]),
+    "rp_solve_overlap_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
     "rp_batch_event_record": (ctypes.c_int, [_vp, ctypes.c_int]),
     "rp_batch_event_elapsed_ms": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "rp_batch_field_ptr": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(_vp)]),
@@ -359,6 +361,23 @@ def trajectory_integrals_hvp(device, stream, n, k, spline, d_lo=None, d_hi=None,
     check(load_library().rp_trajectory_integrals_hvp(int(device), vp(stream), int(n), int(k), pointer_table(spline), vp(d_lo), vp(d_hi),
                                                      integrals_table(g), pointer_table(spline_dot), vp(d_lo_dot), vp(d_hi_dot),
                                                      pointer_table(spline_bar_dot), vp(d_lo_bar_dot), vp(d_hi_bar_dot)))
+
+
+OVERLAP_OFF, OVERLAP_AUTO, OVERLAP_ALWAYS = 0, 1, 2      # rp_solve_overlap_set's modes
+
+
+def solve_overlap_set(mode):
+    """rp_solve_overlap_set: 0 = every call on the batch's stream, 1 = back-to-back fused solves of batches that share a stream overlap on
+    an auxiliary stream (the default; batches of 65,536 problems or more), 2 = every eligible solve whatever its size.  Process-wide."""
+    check(load_library().rp_solve_overlap_set(int(mode)))
+
+
+def solve_overlap_stats():
+    """rp_solve_overlap_stats as a dict: solves sent to the auxiliary stream, eligible solves kept on the caller's stream, joins enqueued,
+    solves excluded by the eligibility list (counted since the library was loaded)."""
+    out = (ctypes.c_ulonglong * 4)()
+    check(load_library().rp_solve_overlap_stats(out))
+    return {"aux": int(out[0]), "kept": int(out[1]), "joins": int(out[2]), "excluded": int(out[3])}
 
 
 def device_count():

@@ -14,7 +14,9 @@
 #include <cstdlib>
 #include <cstdint>
 #include <cstring>
+#include <atomic>
 #include <initializer_list>
+#include <mutex>
 #include <new>
 
 #include "ip_kernels.h"
@@ -54,6 +56,8 @@
 //   raw_pointer_out: field_ptr (start written out first) -> records not current, stale, unpredicted, raw_positions_out or raw_state_out,
 //       an end-velocity field: not zero_end_vel
 //   solution_bound: bind_solution -> stale.     solution_current: solve, solve_launch -> not stale, only behind a launch that succeeded
+struct rp_overlap;      // the lanes of a caller stream: below, "overlap of back-to-back fused solves"
+
 struct rp_batch {
     rp::BatchView view;
     rp::HostParams params;
@@ -74,6 +78,10 @@ struct rp_batch {
     unsigned long long *h_pinned;   // 72 pinned host words: [0,64) counter shards, [64,68) reduction: read-backs without pageable staging
     hipEvent_t events[8];
     bool event_live[8];
+    rp_overlap *lanes;        // the overlap context of `stream` (one per device and stream, shared by every batch on it); holds a reference
+    uint64_t s_ticket;        // ticket of the last operation of this batch enqueued on the caller's stream
+    uint64_t aux_seq;         // number of its last solve on the auxiliary lane (0: none)
+    bool pipelined;           // configuration: a slot of an rp_pipeline (its stream is swapped for the scheduling pass): never overlapped
 };
 
 namespace {
@@ -96,10 +104,240 @@ int fail(int status, const char *fmt, ...)
             return fail(e_ == hipErrorOutOfMemory ? RP_ERR_NOMEM : RP_ERR_DEVICE, "%s: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
-#define RP_NEED(b)                                                  \
-    do {                                                            \
-        if (!(b)) return fail(RP_ERR_INVALID, "null batch handle"); \
-        RP_HIP(hipSetDevice((b)->device));                          \
+// ---- overlap of back-to-back fused solves of batches that share a stream ----
+// A launch's wave slots empty out while its last chunks drain, and the next launch on the same stream starts only once the previous one
+// has retired.  A fused solve of a materialised batch touches nothing but memory the library owns, so consecutive solves of DIFFERENT
+// batches on one caller stream S may run side by side: every second one goes to an auxiliary stream ("aux") that the library keeps beside
+// S.  One context per (device, S), shared by every batch created on S; each batch holds a reference from create to destroy, the last
+// reference destroys aux, the events and -- where a batch created S -- S itself, so the batch that owns S may go before its borrowers.
+//
+// The ordering rule (the whole correctness argument).  Every operation the library enqueues takes a ticket from the context.
+//   * Eligible solves (rp_batch_solve: the list there) alternate between S and aux as long as they follow one another directly; one
+//     that follows anything else runs on S.
+//   * `fork` is an event recorded on S.  It is (re)recorded only if the library has enqueued something on S since it was recorded last
+//     (dirty_ticket > fork_ticket); eligible solves on S do not count for other batches.  It is recorded ahead of an S-lane solve
+//     already (choose_lane says when), so that the aux solve that follows waits for what preceded that solve and not for the solve.
+//   * An aux launch of batch b needs b's last S-side operation at or before the recorded fork (b->s_ticket <= fork_ticket): if not,
+//     fork is re-recorded first.  aux waits on fork whenever it has been re-recorded; aux is in order, so an earlier aux solve of b
+//     needs nothing.  After the launch `done[seq % ring]` is recorded on aux.
+//   * An S-lane solve of a batch whose last solve is un-joined on aux first makes S wait on that solve's done event (a ring slot that
+//     has been re-recorded since holds a LATER aux solve, which implies the earlier one).
+//   * Every other entry point that takes a batch JOINS first (RP_NEED, the single choke point; rp_batch_stream and rp_batch_destroy too):
+//     S waits on the newest un-joined done event -- aux is in order, one event suffices -- and the operation counts as S-side work
+//     of its batch (dirty_ticket, s_ticket).
+// So consecutive solves of different batches overlap pairwise, and whatever a caller can observe through the API or through its own stream
+// -- results, events, rp_batch_sync, the stream handle -- is ordered as before.  Foreign work on S cannot conflict: eligible solves touch
+// only library-private memory (no bound solution buffer, no raw pointer out); a path that breaks that is excluded, not synchronised.
+// The context's mutex is held for the length of an entry point (lane_guard), so tickets are taken in the order the work is enqueued
+// also where threads share a stream.  A failed launch leaves the tickets as they were.
+// mode 1: the smallest of 65,536 / 262,144 / 1,048,576 problems at which overlapping every eligible solve was not slower than none over 40
+// back-to-back solves (1.50x, 1.22x, 1.04x: profiles/solve_overlap_ab.log).  Below it a solve is a few waves per SIMD and unmeasured.
+constexpr size_t kOverlapMinProblems = 65536;
+constexpr unsigned kDoneRing = 8;
+
+}  // namespace
+
+struct rp_overlap {
+    int device;
+    hipStream_t S;
+    bool own_S;                // a batch created S (rp_batch_create without a stream): destroyed with the last reference
+    int refs;                  // under g_overlap_registry_mutex
+    std::recursive_mutex mu;   // everything below
+    bool lanes_live;           // aux, fork and done[] exist (created at the first solve that may overlap)
+    hipStream_t aux;
+    hipEvent_t fork, done[kDoneRing];
+    uint64_t ticket;           // of the last operation enqueued
+    uint64_t dirty_ticket;     // of the last S-side operation that was not an eligible solve
+    uint64_t fork_ticket;      // the ticket at which fork was recorded last: S-side operations up to it precede fork
+    uint64_t aux_fork_ticket;  // the fork_ticket aux has waited on
+    uint64_t aux_seq;          // aux solves enqueued
+    uint64_t joined_seq;       // aux solves up to this one precede work S has been made to wait for
+    bool after_S_solve;        // the last operation enqueued was an eligible solve on S: the next eligible solve goes to aux
+    rp_overlap *next;
+};
+
+namespace {
+
+std::mutex g_overlap_registry_mutex;
+rp_overlap *g_overlap_registry = nullptr;
+std::atomic<int> g_overlap_mode{1};
+std::atomic<unsigned long long> g_overlap_stats[4];      // solves sent to aux / kept on S although eligible / joins enqueued / solves excluded
+
+rp_overlap *overlap_acquire(int device, hipStream_t stream, bool own)
+{
+    std::lock_guard<std::mutex> lock(g_overlap_registry_mutex);
+    rp_overlap *c = g_overlap_registry;
+    while (c && !(c->device == device && c->S == stream)) c = c->next;
+    if (!c) {
+        c = new (std::nothrow) rp_overlap();
+        if (!c) return nullptr;
+        c->device = device;
+        c->S = stream;
+        c->next = g_overlap_registry;
+        g_overlap_registry = c;
+    }
+    c->own_S = c->own_S || own;
+    ++c->refs;
+    return c;
+}
+
+void overlap_release(rp_overlap *c)
+{
+    if (!c) return;
+    {
+        std::lock_guard<std::mutex> lock(g_overlap_registry_mutex);
+        if (--c->refs > 0) return;
+        rp_overlap **at = &g_overlap_registry;
+        while (*at && *at != c) at = &(*at)->next;
+        if (*at) *at = c->next;
+    }
+    if (c->lanes_live) {
+        (void)hipStreamSynchronize(c->aux);
+        (void)hipStreamDestroy(c->aux);
+        (void)hipEventDestroy(c->fork);
+        for (unsigned i = 0; i < kDoneRing; ++i) (void)hipEventDestroy(c->done[i]);
+    }
+    if (c->own_S && c->S) (void)hipStreamDestroy(c->S);
+    delete c;
+}
+
+// The HIP runtime multiplexes a process's streams onto a handful of hardware queues, and two streams that share one serialise
+// (profiles/r6_tuning.md): an auxiliary stream that merely exists can cost a caller who deals work onto streams of its own the queue it
+// counted on.  rp_pipeline_create calls this: every context of the device gives its auxiliary stream back, once that has drained.  The
+// next solve that may overlap creates it again (need_lanes), and records fork anew.
+void overlap_retire_lanes(int device)
+{
+    std::lock_guard<std::mutex> lock(g_overlap_registry_mutex);
+    for (rp_overlap *c = g_overlap_registry; c; c = c->next) {
+        if (c->device != device) continue;
+        std::lock_guard<std::recursive_mutex> own(c->mu);
+        if (!c->lanes_live) continue;
+        (void)hipStreamSynchronize(c->aux);      // everything on aux has finished: nothing is left to join
+        c->joined_seq = c->aux_seq;
+        (void)hipStreamDestroy(c->aux);
+        (void)hipEventDestroy(c->fork);
+        for (unsigned i = 0; i < kDoneRing; ++i) (void)hipEventDestroy(c->done[i]);
+        c->fork_ticket = c->aux_fork_ticket = 0;
+        c->lanes_live = false;
+    }
+}
+
+// holds the context's mutex for the length of an entry point
+struct lane_guard {
+    rp_overlap *c;
+    explicit lane_guard(rp_overlap *c_) : c(c_) { if (c) c->mu.lock(); }
+    ~lane_guard() { unlock(); }
+    void unlock() { if (c) c->mu.unlock(); c = nullptr; }
+    lane_guard(const lane_guard &) = delete;
+    lane_guard &operator=(const lane_guard &) = delete;
+};
+
+// the join, and the ticket of an operation that goes onto the caller's stream (under the guard)
+int on_caller_stream(rp_batch *b)
+{
+    rp_overlap *c = b->lanes;
+    if (!c) return RP_OK;
+    if (c->aux_seq > c->joined_seq) {
+        RP_HIP(hipStreamWaitEvent(b->stream, c->done[c->aux_seq % kDoneRing], 0));
+        if (b->stream == c->S) c->joined_seq = c->aux_seq;
+        ++g_overlap_stats[2];
+    }
+    c->dirty_ticket = b->s_ticket = ++c->ticket;
+    c->after_S_solve = false;
+    return RP_OK;
+}
+
+int need_lanes(rp_overlap *c)
+{
+    if (c->lanes_live) return RP_OK;
+    hipStream_t aux = nullptr;
+    hipEvent_t ev[kDoneRing + 1];
+    unsigned made = 0;
+    hipError_t e = hipStreamCreateWithFlags(&aux, hipStreamNonBlocking);
+    if (e != hipSuccess) aux = nullptr;
+    for (; e == hipSuccess && made < kDoneRing + 1; ++made) {
+        e = hipEventCreateWithFlags(&ev[made], hipEventDisableTiming);
+        if (e != hipSuccess) break;
+    }
+    if (e != hipSuccess) {
+        for (unsigned i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]);
+        if (aux) (void)hipStreamDestroy(aux);
+        return fail(e == hipErrorOutOfMemory ? RP_ERR_NOMEM : RP_ERR_DEVICE, "overlap lanes: %s", hipGetErrorString(e));
+    }
+    c->aux = aux;
+    c->fork = ev[kDoneRing];
+    for (unsigned i = 0; i < kDoneRing; ++i) c->done[i] = ev[i];
+    c->lanes_live = true;
+    return RP_OK;
+}
+
+int record_fork(rp_overlap *c)
+{
+    RP_HIP(hipEventRecord(c->fork, c->S));
+    c->fork_ticket = c->ticket;
+    return RP_OK;
+}
+
+// the lane of an eligible solve of b and the waits ahead of it (the ordering rule above); nothing here takes a ticket
+int choose_lane(rp_batch *b, hipStream_t *lane, bool *on_aux)
+{
+    rp_overlap *c = b->lanes;
+    int st = need_lanes(c);
+    if (st != RP_OK) return st;
+    *on_aux = c->after_S_solve;
+    if (*on_aux) {
+        if (c->dirty_ticket > c->fork_ticket || b->s_ticket > c->fork_ticket) st = record_fork(c);
+        if (st != RP_OK) return st;
+        if (c->aux_fork_ticket != c->fork_ticket) {
+            RP_HIP(hipStreamWaitEvent(c->aux, c->fork, 0));
+            c->aux_fork_ticket = c->fork_ticket;
+        }
+        *lane = c->aux;
+        return RP_OK;
+    }
+    if (b->aux_seq > c->joined_seq) {
+        RP_HIP(hipStreamWaitEvent(c->S, c->done[b->aux_seq % kDoneRing], 0));
+        c->joined_seq = b->aux_seq;
+        ++g_overlap_stats[2];
+    }
+    // fork ahead of this solve, for the aux solve that may follow -- unless what dirtied S was work on this very batch (set_problems, solve;
+    // restart, solve; ...): in such a per-batch sequence the next solve follows work of its own too and stays on S, and an event per
+    // solve is not free (1.5 % of the by-hand loop of bench.py's end_to_end).  Should an aux solve follow after all, it records fork itself.
+    if (c->dirty_ticket > c->fork_ticket && b->s_ticket != c->dirty_ticket) st = record_fork(c);
+    *lane = c->S;
+    return st;
+}
+
+// behind a launch that succeeded: its ticket, and on aux its done event
+int solve_enqueued(rp_batch *b, bool on_aux)
+{
+    rp_overlap *c = b->lanes;
+    const uint64_t t = ++c->ticket;
+    c->after_S_solve = !on_aux;
+    if (!on_aux) {
+        b->s_ticket = t;
+        ++g_overlap_stats[1];
+        return RP_OK;
+    }
+    b->aux_seq = ++c->aux_seq;
+    ++g_overlap_stats[0];
+    const hipError_t e = hipEventRecord(c->done[b->aux_seq % kDoneRing], c->aux);
+    if (e != hipSuccess) {      // no event to wait on: wait here, once
+        (void)hipStreamSynchronize(c->aux);
+        c->joined_seq = c->aux_seq;
+        return fail(RP_ERR_DEVICE, "hipEventRecord: %s", hipGetErrorString(e));
+    }
+    return RP_OK;
+}
+
+// (not a do-while: the guard lives to the end of the entry point)
+#define RP_NEED(b)                                              \
+    if (!(b)) return fail(RP_ERR_INVALID, "null batch handle"); \
+    lane_guard lane_guard_((b)->lanes);                         \
+    do {                                                        \
+        RP_HIP(hipSetDevice((b)->device));                      \
+        const int js_ = on_caller_stream(b);                    \
+        if (js_ != RP_OK) return js_;                           \
     } while (0)
 
 // ---- the transitions (the table above the struct) ----
@@ -208,22 +446,20 @@ int before_gated_launch(rp_batch *b, bool seed)
 }
 
 #define RP_NEED_STATE(b)                     \
+    RP_NEED(b);                              \
     do {                                     \
-        RP_NEED(b);                          \
         const int ms_ = materialize(b);      \
         if (ms_ != RP_OK) return ms_;        \
     } while (0)
 
 // What every derivative entry (rp_batch_solution_vjp ... rp_batch_solution_jacobian_vel) asks for, in the order it is tested: a
 // handle, an F3 batch in double storage (the message names the entry), every output (`outputs`: all of them given), the state
-#define RP_NEED_F3_STATE(b, outputs)                                                    \
-    do {                                                                                \
-        if (!(b)) return fail(RP_ERR_INVALID, "null batch handle");                     \
-        if ((b)->view.variant != RP_VARIANT_F3 || (b)->view.dtype != RP_DTYPE_F64)      \
-            return fail(RP_ERR_UNSUPPORTED, "%s: F3 with RP_DTYPE_F64 only", __func__); \
-        if (!(outputs)) return fail(RP_ERR_INVALID, "null output");                     \
-        RP_NEED_STATE(b);                                                               \
-    } while (0)
+#define RP_NEED_F3_STATE(b, outputs)                                                \
+    if (!(b)) return fail(RP_ERR_INVALID, "null batch handle");                     \
+    if ((b)->view.variant != RP_VARIANT_F3 || (b)->view.dtype != RP_DTYPE_F64)      \
+        return fail(RP_ERR_UNSUPPORTED, "%s: F3 with RP_DTYPE_F64 only", __func__); \
+    if (!(outputs)) return fail(RP_ERR_INVALID, "null output");                     \
+    RP_NEED_STATE(b)
 
 // The *_range calls (a watched problem, a page of a table) go through one small device buffer that lives as long as
 // the batch: kRangeChunk problems x the widest row (the F3 constraint table, 1 + 14 * 8 doubles) = 0.9 MB.
@@ -430,6 +666,8 @@ int rp_batch_create(rp_batch **out, int variant, int dtype, size_t n, int device
     hipError_t e = hipSuccess;
     if (stream) { b->stream = (hipStream_t)stream; b->own_stream = false; }
     else { e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking); b->own_stream = (e == hipSuccess); }
+    if (e == hipSuccess && !(b->lanes = overlap_acquire(device, b->stream, b->own_stream))) e = hipErrorOutOfMemory;      // (the context now owns a stream created here)
+    lane_guard guard(b->lanes);
     if (e == hipSuccess) e = hipMalloc(&b->view.base, fields * b->view.stride * rp::storage_size(dtype));
     if (e == hipSuccess) e = hipMalloc((void **)&b->view.iters, n * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&b->view.status, n * sizeof(uint32_t));
@@ -442,8 +680,15 @@ int rp_batch_create(rp_batch **out, int variant, int dtype, size_t n, int device
     if (e == hipSuccess) e = rp::launch_clear_progress(b->view, b->stream);
     if (e != hipSuccess) {
         const int code = fail(e == hipErrorOutOfMemory ? RP_ERR_NOMEM : RP_ERR_DEVICE, "rp_batch_create: %s", hipGetErrorString(e));
+        guard.unlock();
         rp_batch_destroy(b);
         return code;
+    }
+    st = on_caller_stream(b);      // the clearing above is S-side work of this batch
+    if (st != RP_OK) {
+        guard.unlock();
+        rp_batch_destroy(b);
+        return st;
     }
     *out = b;
     return RP_OK;
@@ -453,7 +698,14 @@ int rp_batch_destroy(rp_batch *b)
 {
     if (!b) return RP_OK;
     (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    {
+        // join, synchronise as ever, and aux too if this batch has work pending there (its memory is freed below)
+        lane_guard guard(b->lanes);
+        const bool on_aux = b->lanes && b->lanes->lanes_live && b->aux_seq > b->lanes->joined_seq;
+        if (b->stream) (void)on_caller_stream(b);
+        if (b->stream) (void)hipStreamSynchronize(b->stream);
+        if (on_aux) (void)hipStreamSynchronize(b->lanes->aux);
+    }
     for (int i = 0; i < 8; ++i) if (b->event_live[i]) (void)hipEventDestroy(b->events[i]);
     if (b->view.base) (void)hipFree(b->view.base);
     if (b->view.iters) (void)hipFree(b->view.iters);
@@ -471,7 +723,8 @@ int rp_batch_destroy(rp_batch *b)
     if (b->d_pos) (void)hipFree(b->d_pos);
     if (b->d_range) (void)hipFree(b->d_range);
     if (b->d_solscratch) (void)hipFree(b->d_solscratch);
-    if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
+    if (b->lanes) overlap_release(b->lanes);      // the last batch on the stream destroys aux, the events and a stream a batch created
+    else if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
     return RP_OK;
 }
@@ -731,23 +984,40 @@ int rp_batch_step_counted(rp_batch *b, int k, uint32_t *feas_halvings, uint32_t 
 
 int rp_batch_solve(rp_batch *b, double gap_tol, int max_iter, int steps_per_launch)
 {
-    RP_NEED(b);
+    if (!b) return fail(RP_ERR_INVALID, "null batch handle");
+    lane_guard guard(b->lanes);
+    RP_HIP(hipSetDevice(b->device));
     int st = check_max_iter(max_iter);
     if (st == RP_OK) st = check_gap_tol(gap_tol);
     if (st != RP_OK) return st;
     const bool fused = steps_per_launch <= 0, from_start = fused && starts_in_registers(b, max_iter);
+    const int rounds = fused ? gated_rounds(b, from_start, max_iter) : 0;
+    // The eligibility list of the overlap (the ordering rule above RP_NEED): one fused launch that touches library-private memory only.
+    // A bound solution buffer and a raw pointer out are the caller's memory or the caller's writes: such a solve stays in S's order.
+    const int mode = g_overlap_mode.load(std::memory_order_relaxed);
+    const bool eligible = fused && rounds <= 1 && !b->view.solution && !b->raw_state_out && !b->raw_positions_out && !b->pipelined && b->lanes;
+    const bool overlapped = mode != 0 && eligible && (mode == 2 || b->view.n >= kOverlapMinProblems);
+    if (mode != 0 && !overlapped) ++g_overlap_stats[eligible ? 1 : 3];
+    // anything but an overlapped solve joins and is S-side work, as under RP_NEED; so is a start that has to be written out first
+    if (!overlapped || (!from_start && b->at_start)) st = on_caller_stream(b);
+    if (st != RP_OK) return st;
     if (from_start) left_lazy_start(b);
     else st = materialize(b);
     if (st == RP_OK) st = before_gated_launch(b, !from_start);
     if (st != RP_OK) return st;
     if (fused) {      // every problem to its gate in one launch (or one per round)
-        const int rounds = gated_rounds(b, from_start, max_iter);
+        hipStream_t lane = b->stream;
+        bool on_aux = false;
+        if (overlapped) st = choose_lane(b, &lane, &on_aux);
+        if (st != RP_OK) return st;
         if (rounds > 0) {
             if (rounds > 1 && !b->view.lists) RP_HIP(hipMalloc((void **)&b->view.lists, (2 * b->view.n + 16) * sizeof(uint32_t)));
-            RP_HIP(rp::launch_solve_rounds(b->view, b->params, gap_tol, max_iter, rounds, b->params.handoff_lanes, 1, b->stream));
+            RP_HIP(rp::launch_solve_rounds(b->view, b->params, gap_tol, max_iter, rounds, b->params.handoff_lanes, 1, lane));
         } else {
-            RP_HIP(rp::launch_solve_fused(b->view, b->params, gap_tol, max_iter, from_start, b->stream));
+            RP_HIP(rp::launch_solve_fused(b->view, b->params, gap_tol, max_iter, from_start, lane));
         }
+        if (overlapped) st = solve_enqueued(b, on_aux);
+        if (st != RP_OK) return st;
         solution_current(b);
         return RP_OK;
     }
@@ -1281,7 +1551,22 @@ int rp_batch_sync(rp_batch *b)
 int rp_batch_stream(rp_batch *b, void **stream)
 {
     if (!b || !stream) return fail(RP_ERR_INVALID, "null argument");
+    RP_NEED(b);      // the join: what the caller enqueues on the handle follows every solve enqueued so far
     *stream = (void *)b->stream;
+    return RP_OK;
+}
+
+int rp_solve_overlap_set(int mode)
+{
+    if (mode < 0 || mode > 2) return fail(RP_ERR_INVALID, "overlap mode %d (want 0 = off, 1 = automatic, 2 = every eligible solve)", mode);
+    g_overlap_mode.store(mode, std::memory_order_relaxed);
+    return RP_OK;
+}
+
+int rp_solve_overlap_stats(unsigned long long out[4])
+{
+    if (!out) return fail(RP_ERR_INVALID, "null output");
+    for (int i = 0; i < 4; ++i) out[i] = g_overlap_stats[i].load(std::memory_order_relaxed);
     return RP_OK;
 }
 
@@ -1372,12 +1657,14 @@ int rp_pipeline_create(rp_pipeline **out, int variant, int dtype, size_t n, int 
     p->job_of = new (std::nothrow) int64_t[depth]();
     if (!p->slots || !p->done || !p->consumed || !p->job_of) { rp_pipeline_destroy(p); return fail(RP_ERR_NOMEM, "host allocation failed"); }
     for (int j = 0; j < depth; ++j) p->job_of[j] = -1;
+    overlap_retire_lanes(device);      // the pipeline's streams want the hardware queues that idle auxiliary streams hold
     int st = RP_OK;
     for (int j = 0; j < depth && st == RP_OK; ++j) {
         // the first batch of a stream creates it (a non-blocking stream of its own); the others of that stream share it
         st = rp_batch_create(&p->slots[j], variant, dtype, n, device, j < n_streams ? nullptr : (void *)p->streams[j % n_streams]);
         if (st == RP_OK && j < n_streams) p->streams[j] = p->slots[j]->stream;
         if (st == RP_OK) p->slots[j]->slim_schedule = n_streams > 1;      // beside a running solve only one-wave blocks get in (schedule.hip)
+        if (st == RP_OK) p->slots[j]->pipelined = true;                   // the pipeline deals its batches onto streams itself: no auxiliary lane
         if (st == RP_OK && hipEventCreateWithFlags(&p->done[j], hipEventDisableTiming) != hipSuccess) st = fail(RP_ERR_DEVICE, "hipEventCreate failed");
         if (st == RP_OK && hipEventCreateWithFlags(&p->consumed[j], hipEventDisableTiming) != hipSuccess) st = fail(RP_ERR_DEVICE, "hipEventCreate failed");
     }
