@@ -73,7 +73,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      of the evaluation along a direction; a new entry only, the revision stays); rp_trajectory_integrals_hvp (the second derivative of
  *      the integrals along a direction; a new entry only, the revision stays); rp_solve_overlap_set and rp_solve_overlap_stats
  *      (back-to-back fused solves of batches that share a stream overlap on an auxiliary stream; new entries only, no struct changes
- *      size and nothing a caller can observe through an existing entry changes, so the revision stays) */
+ *      size and nothing a caller can observe through an existing entry changes, so the revision stays); rp_trajectory_meeting (the first
+ *      time the gap between two splines reaches a level; a new entry only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -619,6 +620,39 @@ RP_API int rp_trajectory_tracking_jvp(int device, void *stream, size_t n, size_t
                                       const double *const d_spline_b[8], const double *d_lo, const double *d_hi, const double *d_delay,
                                       const double *const d_spline_a_dot[8], const double *const d_spline_b_dot[8], const double *d_lo_dot,
                                       const double *d_hi_dot, const double *d_delay_dot, double *const d_value_dot[3]);
+
+/* ---- when two splines meet: the first time in a window at which the gap between two splines reaches a level (new:
+ * the reference draws one curve; the inverse of rp_trajectory_gap's D as rp_trajectory_crossing is of rp_trajectory_eval's pos; replaces a
+ * root search on the host around two rp_trajectory_eval calls -- two launches per iteration and no derivative through the root) ----
+ * Inputs, queries, the gap D(t) = pos_A(t) - pos_B(t - delay), the common domain [S, E], the clamped window [a, b], the knots k_A and k_B
+ * (k_A first among equals) and the per-problem NaN rule are rp_trajectory_gap's, word for word; a NaN or infinite delay, or !(a <= b),
+ * makes the query NaN.  d_level, n x k doubles: the level of each query; NULL counts as 0 (the two at the same position); a NaN or
+ * infinite level makes its own query NaN.
+ * The meeting time is the earliest t in [a, b] with D(t) = level, on A's clock; NaN if the gap does not reach the level in the window (no
+ * extrapolation).  Sub-pieces: rp_trajectory_gap's up to three pieces, each cut at its candidate roots of the relative velocity (the same
+ * roots by the same tests, the smaller first; a root that is no candidate leaves a sub-piece of length zero): nine monotone sub-pieces
+ * between ten breakpoints in time order -- a, roots, knot, roots, knot, roots, b; a knot outside [a, b] is the end it is clamped to.  Each
+ * breakpoint's gap is rp_trajectory_eval(A, t) - rp_trajectory_eval(B, t - delay), computed once.  The query takes the first sub-piece
+ * whose two end values hold the level between them, inclusive, in either direction (a NaN fails).  If the level equals the value at the
+ * sub-piece's start the time is that breakpoint with its own bits (lo's, delay's, +0.0, k_A's, k_B's, or a root's sum c + u).  Otherwise
+ * D(c + u) = level is solved by rp_trajectory_crossing's search -- secant start, Newton steps kept in the bracket and bisected where
+ * they leave it or fail to halve the step before last, until g == 0, the bracket or the step is within 2 ulp of the sub-piece's later end
+ * (as a time on A's clock), or one step after a Newton step whose own error estimate is; the point of smallest |g| seen; at most 64
+ * trips, whatever the input -- on the piece's local cubic: (X, V, A, J) the differences of the two selected segments' pos, vel, acc and
+ * jrk0 at the piece's start c, u = t - c; the time is c + u, kept inside the sub-piece's two ends.
+ * Outputs: d_time (required) and d_relvel (NULL: not wanted), n x k each.  d_relvel is the closing velocity at the returned time, bit for
+ * bit vel of rp_trajectory_eval(A, time) minus vel of rp_trajectory_eval(B, time - delay), NaN exactly where the time is.
+ * A level within rounding of an extreme of D in the window may come out as the touch, as a later meeting, or as NaN
+ * (rp_trajectory_crossing's rule).
+ * Derivatives need no entry of their own: D(theta_A, theta_B, t, delay) = level gives d time = (d level - d pos_A
+ * + d pos_B - vel_B(time - delay) d delay) / relvel -- one rp_trajectory_eval_vjp or _jvp launch on each spline.
+ * There is no batch entry (rp_trajectory_gap's reason).  Argument rules are rp_trajectory_gap's: entries [3] and [4] of either spline
+ * table may be NULL (zeros), every given n x k array 16-byte aligned, n and k positive, k < 2^31, d_time not NULL; RP_ERR_INVALID before
+ * any device call otherwise.  Asynchronous on `stream`; never throws.  Pointwise: a query's bits depend on its problem's sixteen numbers
+ * and its own level, window ends and delay only. */
+RP_API int rp_trajectory_meeting(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8],
+                                 const double *const d_spline_b[8], const double *d_level, const double *d_lo, const double *d_hi,
+                                 const double *d_delay, double *d_time, double *d_relvel);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

@@ -14,7 +14,8 @@ def __getattr__(name):
     # the torch layer (autograd.py) is imported on first use: everything else here works without importing torch
     if name in ("min_time_solve", "min_time_jacobian", "min_time_hessian", "trajectory_eval", "min_time_trajectory",
                 "trajectory_crossing", "min_time_crossing", "trajectory_extrema", "min_time_extrema", "trajectory_integrals",
-                "min_time_integrals", "trajectory_gap", "min_time_gap", "trajectory_tracking", "min_time_tracking"):
+                "min_time_integrals", "trajectory_gap", "min_time_gap", "trajectory_tracking", "min_time_tracking",
+                "trajectory_meeting", "min_time_meeting"):
         from . import autograd
         return getattr(autograd, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -39,6 +39,9 @@ attained; min_time_gap composes it with two min_time_solve calls.
 trajectory_tracking (section 20) answers how far apart they are on average: the integrals of that gap, of its square and of the square of
 its rate over a window of times, one rp_trajectory_tracking launch, reverse mode one rp_trajectory_tracking_vjp call, forward mode one
 rp_trajectory_tracking_jvp launch; min_time_tracking composes it with two min_time_solve calls.
+trajectory_meeting (section 22) inverts that gap as trajectory_crossing inverts pos: the first time in a window at which the gap is at a
+level, one rp_trajectory_meeting launch, both derivative modes one launch of the evaluator's on each spline through the implicit function
+theorem; min_time_meeting composes it with two min_time_solve calls.
 """
 import ctypes
 import threading
@@ -996,15 +999,20 @@ def _spline_table(name, spline, who):
     return [pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1]
 
 
-def _check_gap_queries(pos0, lo, hi, delay, who):
-    """lo, hi (None: -inf / +inf) and delay (None: 0) against the (checked) positions, each like tau; those given: one shape after
-    broadcasting."""
-    given = [(name, _check_tau(pos0, t, who, name) if t is not None else None) for name, t in (("lo", lo), ("hi", hi), ("delay", delay))]
+def _check_named_queries(pos0, named, who):
+    """Optional per-query arguments, (name, tensor or None) each, against the (checked) positions, each like tau; those given: one shape
+    after broadcasting."""
+    given = [(name, _check_tau(pos0, t, who, name) if t is not None else None) for name, t in named]
     shapes = [(name, t.shape) for name, t in given if t is not None]
     for name, shape in shapes[1:]:
         if shape != shapes[0][1]:
             raise ValueError(who + ": %s has shape %s, %s %s" % (shapes[0][0], tuple(shapes[0][1]), name, tuple(shape)))
     return [t for _, t in given]
+
+
+def _check_gap_queries(pos0, lo, hi, delay, who):
+    """lo, hi (None: -inf / +inf) and delay (None: 0)."""
+    return _check_named_queries(pos0, (("lo", lo), ("hi", hi), ("delay", delay)), who)
 
 
 def _check_same_batch(pos_a, pos_b, who):
@@ -1040,13 +1048,8 @@ def trajectory_gap(a, b, lo=None, hi=None, delay=None):
     return _TrajectoryGap.apply(*table_a, *table_b, lo, hi, delay)
 
 
-def min_time_gap(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None, vel_b=None, gap_tol=1e-8, max_iter=200, params=None):
-    """min_time_solve of two vehicles' problems, then trajectory_gap of the two solutions.  pos_a, pos_b: (pos0, pos1, pos2) of each
-    vehicle; vel_a, vel_b: (vel0, vel2) of each (None: rest to rest; either entry None: zeros); lo, hi, delay as trajectory_gap's.
-    Returns (gap_min, gap_max, t_gap_min, t_gap_max, solution_a, solution_b) with each solution min_time_solve's (vel1, duration0,
-    duration1, iters, status).  Plain composition: the gaps are differentiable to first order in both vehicles' positions and end
-    velocities, in lo, hi and delay, in both modes, through the solves' derivatives and the gap's."""
-    who = "min_time_gap"
+def _check_vehicles(pos_a, pos_b, vel_a, vel_b, who):
+    """Two vehicles' problems as the min_time_* functions of two splines take them."""
     for name, pos, vel in (("pos_a", pos_a, vel_a), ("pos_b", pos_b, vel_b)):
         if not isinstance(pos, (list, tuple)) or len(pos) != 3:
             raise TypeError("%s: %s must be a list or tuple of three tensors (pos0, pos1, pos2)" % (who, name))
@@ -1055,14 +1058,152 @@ def min_time_gap(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None, vel_
     for name, pos in (("pos_a", pos_a), ("pos_b", pos_b)):
         _check_positions(*pos, "%s: %s" % (who, name))
     _check_same_batch(pos_a[0], pos_b[0], who)
-    lo, hi, delay = _check_gap_queries(pos_a[0], lo, hi, delay, who)      # before the solves: a bad query costs none
+
+
+def _solve_vehicles(pos_a, pos_b, vel_a, vel_b, gap_tol, max_iter, params):
+    """min_time_solve of each (checked) vehicle: (the two splines as trajectory_gap takes them, the two solutions)."""
     splines, solutions = [], []
     for pos, vel in ((pos_a, vel_a), (pos_b, vel_b)):
         vel0, vel2 = vel if vel is not None else (None, None)
         solution = min_time_solve(*pos, gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
         splines.append(tuple(pos) + tuple(solution[:3]) + (tuple(vel) if vel is not None else ()))
         solutions.append(tuple(solution))
+    return splines, solutions
+
+
+def min_time_gap(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None, vel_b=None, gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve of two vehicles' problems, then trajectory_gap of the two solutions.  pos_a, pos_b: (pos0, pos1, pos2) of each
+    vehicle; vel_a, vel_b: (vel0, vel2) of each (None: rest to rest; either entry None: zeros); lo, hi, delay as trajectory_gap's.
+    Returns (gap_min, gap_max, t_gap_min, t_gap_max, solution_a, solution_b) with each solution min_time_solve's (vel1, duration0,
+    duration1, iters, status).  Plain composition: the gaps are differentiable to first order in both vehicles' positions and end
+    velocities, in lo, hi and delay, in both modes, through the solves' derivatives and the gap's."""
+    who = "min_time_gap"
+    _check_vehicles(pos_a, pos_b, vel_a, vel_b, who)
+    lo, hi, delay = _check_gap_queries(pos_a[0], lo, hi, delay, who)      # before the solves: a bad query costs none
+    splines, solutions = _solve_vehicles(pos_a, pos_b, vel_a, vel_b, gap_tol, max_iter, params)
     return tuple(trajectory_gap(splines[0], splines[1], lo, hi, delay)) + (solutions[0], solutions[1])
+
+
+# ---- when two splines meet: the first time the gap reaches a level ----
+class _TrajectoryMeeting(torch.autograd.Function):
+    """(time, relvel) of the first time in the window at which pos_A(t) - pos_B(t - delay) is at the level: time differentiable to first
+    order in the sixteen spline inputs (A's table, then B's), in the level and in the delay, through the evaluator's derivative launches
+    on each spline -- pos_A(theta_A, time) - pos_B(theta_B, time - delay) = level gives
+    d time = (d level - d pos_A + d pos_B - vel_B d delay) / relvel.  lo and hi only choose the branch.  relvel is for the backward and is
+    not differentiable."""
+
+    @staticmethod
+    def forward(*inputs):
+        a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
+        level, lo, hi, delay = (_dense(t) for t in inputs[16:20])
+        given = next((t for t in (level, lo, hi, delay) if t is not None), None)
+        shape = given.shape if given is not None else (inputs[0].shape[0], 1)
+        device = inputs[0].device
+        time, relvel = (torch.empty(shape, dtype=torch.float64, device=device) for _ in range(2))
+        n, k = shape
+        with torch.cuda.device(device):      # as _trajectory_launch
+            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_meeting(device.index, torch.cuda.current_stream(device).cuda_stream, n, k, [addr(t) for t in a],
+                                    [addr(t) for t in b], addr(level), addr(lo), addr(hi), addr(delay), addr(time), addr(relvel))
+        return time, relvel
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(output[1])
+        ctx.given = [t is not None for t in inputs[:16]] + [False, False, False, inputs[19] is not None]      # neither derivative reads
+        kept = [t for t, given in zip(inputs, ctx.given) if given] + list(output)                             # the level, lo or hi
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _saved(ctx):
+        """(A's and B's eight tensors; A's times, 0 where there is no meeting, and B's, those minus the delay; relvel; where there is no
+        meeting)"""
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        time, relvel = next(kept), next(kept)
+        a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
+        delay = inputs[19]
+        missing = torch.isnan(time)
+        zero = torch.zeros_like(time)
+        t_b = torch.where(missing, zero, time - delay if delay is not None else time)
+        return a, b, torch.where(missing, zero, time), t_b.contiguous(), relvel, missing
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_time, _g_relvel):
+        if g_time is None:
+            return (None,) * 20
+        a, b, t_a, t_b, relvel, missing = _TrajectoryMeeting._saved(ctx)
+        need = ctx.needs_input_grad
+        w = torch.where(missing, torch.zeros_like(t_a), g_time / relvel)      # an unreached level: gradient 0
+        n = t_a.shape[0]
+        bars = [torch.empty(n, dtype=torch.float64, device=t_a.device) if need[f] else None for f in range(16)]
+        tau_bar = torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) if need[19] else None
+        if any(x is not None for x in bars[:8]):
+            _trajectory_launch(capi.trajectory_eval_vjp, t_a.device, a, t_a, -w, None, None, bars[:8], None)
+        if tau_bar is not None or any(x is not None for x in bars[8:]):      # B is at time - delay
+            _trajectory_launch(capi.trajectory_eval_vjp, t_a.device, b, t_b, w, None, None, bars[8:], tau_bar)
+        return tuple(bars) + (w if need[16] else None, None, None, -tau_bar if tau_bar is not None else None)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        a, b, t_a, t_b, relvel, missing = _TrajectoryMeeting._saved(ctx)
+        dots = [_dense(t) for t in tangents[:16]]
+        level_dot, delay_dot = tangents[16], tangents[19]
+        pos_a, pos_b = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
+        _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, a, t_a, dots[:8], None, pos_a, None, None)
+        _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, b, t_b, dots[8:], (-delay_dot).contiguous() if delay_dot is not None else None,
+                           pos_b, None, None)
+        if level_dot is None:
+            level_dot = torch.zeros_like(t_a)
+        time_dot = torch.where(missing, torch.full_like(t_a, float("nan")), (level_dot - pos_a + pos_b) / relvel)
+        return time_dot, None
+
+
+def _check_meeting_queries(pos0, level, lo, hi, delay, who):
+    """level (None: 0), lo, hi (None: -inf / +inf) and delay (None: 0)."""
+    return _check_named_queries(pos0, (("level", level), ("lo", lo), ("hi", hi), ("delay", delay)), who)
+
+
+def trajectory_meeting(a, b, level=None, lo=None, hi=None, delay=None):
+    """The first time at which the gap between two splines of trajectory_eval in one frame, D(t) = pos_a(t) - pos_b(t - delay), is at
+    `level`, within the windows of time [lo, hi]: the inverse of trajectory_gap's D as trajectory_crossing is of trajectory_eval's pos.
+    a, b, lo, hi, delay: exactly trajectory_gap's; level: (n, k) or (k,) like them; None: 0, the two vehicles at the same position; all
+    four None: k = 1, the whole common domain.  Returns the times (on a's clock), (n, k): NaN where the gap does not reach the level in the
+    window clamped to [max(delay, 0), min(T_a, delay + T_b)] (no extrapolation), where the clamped window is empty, where the level is NaN
+    or infinite or the delay NaN or infinite, and for a problem either of whose splines has a duration that is not finite or not > 0.
+
+    One rp_trajectory_meeting launch on the current stream (include/rp_batch.h: the first of the gap's nine monotone sub-pieces that holds
+    the level, then trajectory_crossing's bracketed Newton search with its fixed trip bound; a level within rounding of an extreme of D
+    may give the touch, a later meeting, or NaN).  Differentiable to first order in all sixteen spline inputs, the level and the delay,
+    d time = (d level - d pos_a + d pos_b - vel_b d delay) / relvel with relvel the closing velocity D'(time): reverse mode is one
+    rp_trajectory_eval_vjp launch on each spline, forward mode one rp_trajectory_eval_jvp launch on each; a double
+    backward raises torch's once_differentiable error.  lo and hi get no gradient: the time depends on them through the branch only --
+    a time that sits on the window's start because D is at the level there still moves with the level, not with lo.  An unreached level
+    has gradient 0 (forward mode: NaN, as the time); where the closing velocity is 0 (a touch) there is no derivative and the result is inf
+    or NaN; the time jumps where an earlier extreme of D passes through the level.  Does not synchronise the host."""
+    who = "trajectory_meeting"
+    _check_spline_arg("a", a, who)
+    _check_spline_arg("b", b, who)
+    table_a, table_b = _spline_table("a", a, who), _spline_table("b", b, who)
+    _check_same_batch(table_a[0], table_b[0], who)
+    level, lo, hi, delay = _check_meeting_queries(table_a[0], level, lo, hi, delay, who)
+    return _TrajectoryMeeting.apply(*table_a, *table_b, level, lo, hi, delay)[0]
+
+
+def min_time_meeting(pos_a, pos_b, level=None, lo=None, hi=None, delay=None, *, vel_a=None, vel_b=None, gap_tol=1e-8, max_iter=200,
+                     params=None):
+    """min_time_solve of two vehicles' problems, then trajectory_meeting of the two solutions.  pos_a, pos_b, vel_a, vel_b as
+    min_time_gap's; level, lo, hi, delay as trajectory_meeting's.  Returns (time, solution_a, solution_b) with each solution
+    min_time_solve's (vel1, duration0, duration1, iters, status).  Plain composition: the times are differentiable to first order in both
+    vehicles' positions and end velocities, in the level and the delay, in both modes, through the solves' derivatives and the meeting's."""
+    who = "min_time_meeting"
+    _check_vehicles(pos_a, pos_b, vel_a, vel_b, who)
+    level, lo, hi, delay = _check_meeting_queries(pos_a[0], level, lo, hi, delay, who)      # before the solves: a bad query costs none
+    splines, solutions = _solve_vehicles(pos_a, pos_b, vel_a, vel_b, gap_tol, max_iter, params)
+    return trajectory_meeting(splines[0], splines[1], level, lo, hi, delay), solutions[0], solutions[1]
 
 
 # ---- how much: integrals over a window ----
@@ -1327,21 +1468,9 @@ def min_time_tracking(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None,
     Plain composition: the integrals are differentiable to first order in both vehicles' positions and end velocities, in lo, hi and delay,
     in both modes, through the solves' derivatives and the integrals'."""
     who = "min_time_tracking"
-    for name, pos, vel in (("pos_a", pos_a, vel_a), ("pos_b", pos_b, vel_b)):
-        if not isinstance(pos, (list, tuple)) or len(pos) != 3:
-            raise TypeError("%s: %s must be a list or tuple of three tensors (pos0, pos1, pos2)" % (who, name))
-        if vel is not None and (not isinstance(vel, (list, tuple)) or len(vel) != 2):
-            raise TypeError("%s: the velocities of %s must be None or a pair (vel0, vel2)" % (who, name))
-    for name, pos in (("pos_a", pos_a), ("pos_b", pos_b)):
-        _check_positions(*pos, "%s: %s" % (who, name))
-    _check_same_batch(pos_a[0], pos_b[0], who)
+    _check_vehicles(pos_a, pos_b, vel_a, vel_b, who)
     lo, hi, delay = _check_gap_queries(pos_a[0], lo, hi, delay, who)      # before the solves: a bad query costs none
-    splines, solutions = [], []
-    for pos, vel in ((pos_a, vel_a), (pos_b, vel_b)):
-        vel0, vel2 = vel if vel is not None else (None, None)
-        solution = min_time_solve(*pos, gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
-        splines.append(tuple(pos) + tuple(solution[:3]) + (tuple(vel) if vel is not None else ()))
-        solutions.append(tuple(solution))
+    splines, solutions = _solve_vehicles(pos_a, pos_b, vel_a, vel_b, gap_tol, max_iter, params)
     return tuple(trajectory_tracking(splines[0], splines[1], lo, hi, delay)) + (solutions[0], solutions[1])
 
 

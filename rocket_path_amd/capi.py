@@ -114,6 +114,8 @@ SIGNATURES = {
     "rp_batch_extrema_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "rp_trajectory_gap": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp,
                                          ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rp_trajectory_meeting": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
+                                             _vp, _vp, _vp, _vp]),
     "rp_trajectory_tracking": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
                                               _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_tracking_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
@@ -274,6 +276,15 @@ def trajectory_gap(device, stream, n, k, spline_a, spline_b, d_lo=None, d_hi=Non
     vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
     check(load_library().rp_trajectory_gap(int(device), vp(stream), int(n), int(k), pointer_table(spline_a), pointer_table(spline_b), vp(d_lo),
                                            vp(d_hi), vp(d_delay), gap_table(value), gap_table(time)))
+
+
+def trajectory_meeting(device, stream, n, k, spline_a, spline_b, d_level=None, d_lo=None, d_hi=None, d_delay=None, d_time=None, d_relvel=None):
+    """rp_trajectory_meeting: the first time in the windows [lo, hi] (n, k) clamped to the two splines' common time domain at which the gap
+    pos_A(t) - pos_B(t - delay) is at `level` (None / 0: a level of 0, -inf, +inf, a delay of 0), NaN where it is not reached, and the
+    closing velocity there (None / 0: not wanted).  `spline_a`, `spline_b`: eight addresses each, as for trajectory_eval."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_meeting(int(device), vp(stream), int(n), int(k), pointer_table(spline_a), pointer_table(spline_b),
+                                               vp(d_level), vp(d_lo), vp(d_hi), vp(d_delay), vp(d_time), vp(d_relvel)))
 
 
 def tracking_table(addresses):

@@ -1451,6 +1451,18 @@ int rp_trajectory_tracking_jvp(int device, void *stream, size_t n, size_t k, con
     return RP_OK;
 }
 
+// the first time the gap between two splines reaches a level: rp_trajectory_gap's argument rules; the times cannot be left out
+int rp_trajectory_meeting(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8],
+                          const double *d_level, const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_relvel)
+{
+    const int st = check_tracking(__func__, device, d_spline_a, d_spline_b, n, k, {d_level, d_lo, d_hi, d_delay, d_time, d_relvel}, true);
+    if (st != RP_OK) return st;
+    if (!d_time) return fail(RP_ERR_INVALID, "%s: d_time is null", __func__);
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_meeting(n, k, d_spline_a, d_spline_b, d_level, d_lo, d_hi, d_delay, d_time, d_relvel, (hipStream_t)stream));
+    return RP_OK;
+}
+
 // the integrals over a window, their first derivatives and the reverse rule's derivative along a direction
 int rp_trajectory_integrals(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                             double *const d_value[4])

@@ -10,6 +10,7 @@
 //   the extreme gap between two splines        k_gap                                            section 18
 //   the tracking integrals of two splines      k_tracking                                       section 20
 //   ... their first derivatives                k_tracking_jvp, k_tracking_vjp                   section 20
+//   the first time two splines meet            k_meeting                                        section 22
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
 // rp_batch_integrals_device and rp_batch_sample*; the launchers are at the end of the file.
@@ -615,6 +616,41 @@ __device__ __forceinline__ void stage_crossing(CrossLds &L, int q, Knots kn)
     });
 }
 
+// The search both inverse questions share (crossing_query, meeting_query): the root of cubic_pos(x0, va, acc0, jrk0, s) - p in the bracket
+// [lo, hi] of one monotone piece, whose ends leave g_lo != 0 and g_hi; tol is the stopping width.  The point of smallest |g| looked at.
+__device__ __forceinline__ double bracket_search(double x0, double va, double acc0, double jrk0, double p, double lo, double hi, double g_lo,
+                                                 double g_hi, double tol)
+{
+    const bool up = g_lo < 0.0;
+    double width = hi - lo;
+    double best = abs_(g_hi) < abs_(g_lo) ? hi : lo, best_g = min_(abs_(g_lo), abs_(g_hi));      // the smallest |g| seen, and where
+    double s = lo + width * (g_lo * rcp_<double>(g_lo - g_hi));      // the secant point of the bracket
+    if (!(s > lo && s < hi)) s = lo + 0.5 * width;
+    double dx_old = width, dx = width;
+    bool last = false;
+    for (int trip = 0; trip < kCrossTrips; ++trip) {
+        const double g = cubic_pos(x0, va, acc0, jrk0, s) - p;
+        const double v = cubic_vel(va, acc0, jrk0, s);
+        if (abs_(g) < best_g) { best_g = abs_(g); best = s; }
+        if (g == 0.0 || last) break;
+        if ((g < 0.0) == up) lo = s; else hi = s;
+        width = hi - lo;
+        if (!(width > tol)) break;
+        const double step = g * rcp_<double>(v);      // v == 0: infinite, outside
+        double next = s - step;
+        const bool newton = next > lo && next < hi && 2.0 * abs_(step) <= abs_(dx_old);
+        if (!newton) next = lo + 0.5 * width;
+        // a Newton step leaves an error of about |acc / (2 vel)| step^2: once that is below the stopping width, the point it leads to is
+        // the last one looked at (further steps would only follow the rounding of g around)
+        last = newton && abs_(cubic_acc(acc0, jrk0, s)) * (step * step) <= (2.0 * tol) * abs_(v);
+        dx_old = dx;
+        dx = next - s;
+        if (!(abs_(dx) > tol)) break;
+        s = next;
+    }
+    return best;
+}
+
 __device__ __forceinline__ void crossing_query(const CrossLds &L, int q, double p, double &time, double &vel)
 {
     // the first piece, in time order, whose end positions hold p between them (a NaN or infinite p, NaN ends: none)
@@ -629,42 +665,12 @@ __device__ __forceinline__ void crossing_query(const CrossLds &L, int q, double 
     time = vel = quiet_nan();
     if (m < 0) return;
     const int seg = m >= 3, j = m - 3 * seg;
-    double lo = j == 0 ? 0.0 : L.brk[seg][j - 1][q];
-    double hi = j == 2 ? (seg ? L.d1[q] : L.e.d0[q]) : L.brk[seg][j][q];
+    const double lo = j == 0 ? 0.0 : L.brk[seg][j - 1][q];
+    const double hi = j == 2 ? (seg ? L.d1[q] : L.e.d0[q]) : L.brk[seg][j][q];
     const double x0 = L.e.c[seg][0][q], va = L.e.c[seg][1][q], acc0 = L.e.c[seg][2][q], jrk0 = L.e.c[seg][3][q];
     const double g_lo = p_lo - p, g_hi = p_hi - p;
     double s = lo;      // g_lo == 0: the breakpoint itself (p == pos0: tau = 0 exactly)
-    if (g_lo != 0.0) {
-        const bool up = g_lo < 0.0;
-        const double tol = kCrossTol * hi;
-        double width = hi - lo;
-        double best = abs_(g_hi) < abs_(g_lo) ? hi : lo, best_g = min_(abs_(g_lo), abs_(g_hi));      // the smallest |g| seen, and where
-        s = lo + width * (g_lo * rcp_<double>(g_lo - g_hi));      // the secant point of the bracket
-        if (!(s > lo && s < hi)) s = lo + 0.5 * width;
-        double dx_old = width, dx = width;
-        bool last = false;
-        for (int trip = 0; trip < kCrossTrips; ++trip) {
-            const double g = cubic_pos(x0, va, acc0, jrk0, s) - p;
-            const double v = cubic_vel(va, acc0, jrk0, s);
-            if (abs_(g) < best_g) { best_g = abs_(g); best = s; }
-            if (g == 0.0 || last) break;
-            if ((g < 0.0) == up) lo = s; else hi = s;
-            width = hi - lo;
-            if (!(width > tol)) break;
-            const double step = g * rcp_<double>(v);      // v == 0: infinite, outside
-            double next = s - step;
-            const bool newton = next > lo && next < hi && 2.0 * abs_(step) <= abs_(dx_old);
-            if (!newton) next = lo + 0.5 * width;
-            // a Newton step leaves an error of about |acc / (2 vel)| step^2: once that is below the stopping width, the point it leads to is
-            // the last one looked at (further steps would only follow the rounding of g around)
-            last = newton && abs_(cubic_acc(acc0, jrk0, s)) * (step * step) <= (2.0 * tol) * abs_(v);
-            dx_old = dx;
-            dx = next - s;
-            if (!(abs_(dx) > tol)) break;
-            s = next;
-        }
-        s = best;
-    }
+    if (g_lo != 0.0) s = bracket_search(x0, va, acc0, jrk0, p, lo, hi, g_lo, g_hi, kCrossTol * hi);
     time = seg ? L.e.d0[q] + s : s;
     vel = cubic_vel(va, acc0, jrk0, s);
 }
@@ -1988,6 +1994,110 @@ k_tracking_vjp(FromArrays a, FromArrays b, size_t n, size_t k, int P, int G, con
     });
 }
 
+// ---- when two splines meet: the first time the gap reaches a level (rp_trajectory_meeting) ----
+// The inverse of section 18's gap, as the crossing is the evaluator's.  D, the common domain, the clamped window [a, b], the knots and the
+// pieces are gap_query's; each piece is cut at its candidate roots of the relative velocity (gap_query's tests, the smaller first; a root
+// that is no candidate leaves a sub-piece of length zero at the breakpoint before it), which leaves nine monotone sub-pieces between ten
+// breakpoints in time order: a, roots, knot, roots, knot, roots, b (a knot outside [a, b]: the end it is clamped to).  Every breakpoint's
+// gap is gap_at there, once: the end of one sub-piece and the start of the next are the same number, so a level between D(a) and D(b) is
+// held by some sub-piece.  A query takes the first sub-piece whose end values hold its level between them; a level equal to the value at
+// the sub-piece's start is that breakpoint with its own bits; otherwise bracket_search solves D(c + u) = level in the piece's local form --
+// (X, V, A, J) the differences of the two selected segments at the piece's start c, as track_state forms them, u from the sub-piece's
+// start - c to its end - c, the stopping width 2 ulp of the sub-piece's later end as a time on A's clock -- and the time is c + u, kept
+// inside the sub-piece.  The closing velocity that comes back is the evaluators' at that time.  The local form, not two eval_query calls
+// per trip: the search then holds five numbers instead of reading ten per trip from LDS behind two selects.  The two queries of a pair run
+// one after the other: each search's trip count is its own.
+__device__ __forceinline__ void meeting_query(const GapLds &L, int q, double level, double lo, double hi, double delay, double &time,
+                                              double &relvel)
+{
+    const double kA = L.a.d0[q], kB = delay + L.b.d0[q], TA = L.Ta[q], EB = delay + L.Tb[q];
+    const double S = delay > 0.0 ? delay : 0.0, E = EB < TA ? EB : TA;      // gap_query's domain, window and knots
+    const double a = lo > S ? lo : (lo != lo ? lo : S), b = hi < E ? hi : (hi != hi ? hi : E);
+    const bool ok = a <= b && finite_(delay) && EB == EB;
+    const bool b_first = kB < kA;
+    bool found = false;
+    double t_lo = 0.0, t_hi = 0.0, g_lo = 0.0, g_hi = 0.0, c_at = 0.0;      // the sub-piece taken, its end values minus the level, its piece's start
+    double c = a, t_prev = a, v_prev = gap_at(L, q, a, delay);
+    auto breakpoint = [&](bool real, double t) {
+        const double v = gap_at(L, q, t, delay);
+        const double t_next = real ? t : t_prev, v_next = real ? v : v_prev;
+        const bool holds = (v_prev <= level && level <= v_next) || (v_next <= level && level <= v_prev);      // a NaN fails
+        if (ok && !found && holds) {
+            found = true;
+            t_lo = t_prev; t_hi = t_next;
+            g_lo = v_prev - level; g_hi = v_next - level;
+            c_at = c;
+        }
+        t_prev = t_next;
+        v_prev = v_next;
+    };
+#pragma nounroll
+    for (int piece = 0; piece < 3; ++piece) {
+        const double knot = (piece == 0) == b_first ? kB : kA;
+        const double e = piece == 2 ? b : (knot < a ? a : (knot > b ? b : knot));
+        const int seg_a = kA <= c, seg_b = kB <= c;
+        double vel_a, acc_a, jrk_a, vel_b, acc_b, jrk_b, r0, r1;
+        local_motion(L.a, seg_a, q, seg_a ? c - kA : c, vel_a, acc_a, jrk_a);
+        local_motion(L.b, seg_b, q, seg_b ? c - kB : c - delay, vel_b, acc_b, jrk_b);
+        velocity_roots(vel_a - vel_b, acc_a - acc_b, jrk_a - jrk_b, r0, r1);
+        const double length = e - c, t0 = c + r0, t1 = c + r1;
+        const bool in0 = ok && r0 > 0.0 && r0 < length && a < t0 && t0 < b, in1 = ok && r1 > 0.0 && r1 < length && a < t1 && t1 < b;
+        const bool swap = in1 && (!in0 || r1 < r0);
+        breakpoint(swap ? in1 : in0, swap ? t1 : t0);
+        breakpoint(swap ? in0 : in1, swap ? t0 : t1);
+        breakpoint(true, e);
+        c = e;
+    }
+    time = relvel = quiet_nan();
+    if (!found) return;
+    double t = t_lo;
+    if (g_lo != 0.0) {
+        TrackPiece p;
+        p.seg_a = kA <= c_at;
+        p.seg_b = kB <= c_at;
+        p.sA = p.seg_a ? c_at - kA : c_at;
+        p.sB = p.seg_b ? c_at - kB : c_at - delay;
+        const TrackState st = track_state(eval_const(L.a.c, p.seg_a, q), eval_const(L.b.c, p.seg_b, q), p);
+        const double u = bracket_search(st.X, st.V, st.A, st.J, level, t_lo - c_at, t_hi - c_at, g_lo, g_hi, kCrossTol * t_hi);
+        t = c_at + u;
+        t = t < t_lo ? t_lo : (t > t_hi ? t_hi : t);
+    }
+    double pos, vel_a, vel_b, acc;
+    eval_query(L.a, q, t, pos, vel_a, acc);
+    eval_query(L.b, q, t - delay, pos, vel_b, acc);
+    time = t;
+    relvel = vel_a - vel_b;
+}
+
+__global__ void __launch_bounds__(kTrajBlock)
+k_meeting(FromArrays a, FromArrays b, size_t n, size_t k, int P, const double *__restrict__ level, const double *__restrict__ lo,
+          const double *__restrict__ hi, const double *__restrict__ delay, double *__restrict__ time, double *__restrict__ relvel)
+{
+    __shared__ GapLds L;
+    auto stage_problem = [&](int q, size_t i) {
+        Knots ka = a.load(i), kb = b.load(i);
+        ka.check();
+        kb.check();
+        stage_eval(L.a, q, ka);
+        stage_eval(L.b, q, kb);
+        L.Ta[q] = ka.t0 + ka.t1;
+        L.Tb[q] = kb.t0 + kb.t1;
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k;
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double pa = 0.0, pb = 0.0, la, lb, ha, hb, da = 0.0, db = 0.0, ta, tb, va, vb;
+            if (level) load_pair(level, e_first + e, two, pa, pb);
+            load_window(lo, hi, e_first + e, two, la, lb, ha, hb);
+            if (delay) load_pair(delay, e_first + e, two, da, db);
+            meeting_query(L, qa, pa, la, ha, da, ta, va);
+            if (two) meeting_query(L, qb, pb, lb, hb, db, tb, vb); else { tb = ta; vb = va; }
+            store_pair(time, e_first + e, ta, tb, two);
+            if (relvel) store_pair(relvel, e_first + e, va, vb, two);
+        });
+    });
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -2286,6 +2396,15 @@ hipError_t launch_tracking_vjp(size_t n, size_t k, const double *const d_spline_
                                (double *)nullptr);
         });
     return e;
+}
+
+hipError_t launch_meeting(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_level,
+                          const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_relvel, hipStream_t stream)
+{
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_meeting, grid, block, 0, stream, FromArrays{table_of<8>(d_spline_a)}, FromArrays{table_of<8>(d_spline_b)}, n, k, P,
+                           d_level, d_lo, d_hi, d_delay, d_time, d_relvel);
+    });
 }
 
 // ---- plot data by problem index: a range [first, first + count) of problems, wherever they lie in the batch ----
