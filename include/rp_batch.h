@@ -74,7 +74,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      the integrals along a direction; a new entry only, the revision stays); rp_solve_overlap_set and rp_solve_overlap_stats
  *      (back-to-back fused solves of batches that share a stream overlap on an auxiliary stream; new entries only, no struct changes
  *      size and nothing a caller can observe through an existing entry changes, so the revision stays); rp_trajectory_meeting (the first
- *      time the gap between two splines reaches a level; a new entry only, the revision stays) */
+ *      time the gap between two splines reaches a level; a new entry only, the revision stays); rp_trajectory_tracking_hvp (the second
+ *      derivative of the tracking integrals along a direction; a new entry only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -620,6 +621,31 @@ RP_API int rp_trajectory_tracking_jvp(int device, void *stream, size_t n, size_t
                                       const double *const d_spline_b[8], const double *d_lo, const double *d_hi, const double *d_delay,
                                       const double *const d_spline_a_dot[8], const double *const d_spline_b_dot[8], const double *d_lo_dot,
                                       const double *d_hi_dot, const double *d_delay_dot, double *const d_value_dot[3]);
+/* Second order of rp_trajectory_tracking (replaces differencing rp_trajectory_tracking_vjp along the direction -- four
+ * launches, a step to choose, half the digits -- and makes torch.autograd.functional.hvp / hessian and Newton or Gauss-Newton outer loops on
+ * tracking and spacing losses possible): the derivative of rp_trajectory_tracking_vjp's nineteen outputs (d_spline_a_bar[8],
+ * d_spline_b_bar[8], d_lo_bar, d_hi_bar, d_delay_bar) along the direction (d_spline_a_dot[8], d_spline_b_dot[8], d_lo_dot, d_hi_dot,
+ * d_delay_dot) with the upstream gradients d_g[3] held fixed, that is (sum over the three outputs o of g_o x the second derivative of o) x
+ * the direction.  The matrix is symmetric: the one entry is forward-over-reverse and the input part of reverse-over-reverse; the part of a
+ * double backward in d_g is rp_trajectory_tracking_jvp.  The derivative is that of the formulas rp_trajectory_tracking_vjp evaluates on the
+ * branch the forward took: the classes of a and b (lo / the START / the clamp +0.0; hi / END_A / END_B), the order of the two knots, which
+ * knot is clamped to which end and the segment each spline is in on each piece are held fixed.  Every piece end is an affine function of
+ * lo, hi, the delay and the durations with constant coefficients and carries rp_trajectory_tracking_jvp's tangent; at ties, and at a delay
+ * of exactly 0, a second derivative is one-sided.  Exact: the three integrals are polynomials in the segment constants, the local piece
+ * starts and the piece lengths; there is no root term and no division per query.
+ * A NULL d_g entry or table, a NULL entry of either _dot table or a whole table, d_lo_dot, d_hi_dot or d_delay_dot: zeros, the same bits as
+ * explicit zeros.  A NULL output is not formed; at least one must be given.  A query whose outputs are NaN counts with gradients of zero; a
+ * problem either of whose splines is under the NaN rule is NaN in its sixteen per-problem results, and its per-query results are 0 or NaN
+ * where rp_trajectory_tracking_vjp's are.  A NaN d_lo_dot (d_hi_dot) on an end that is clamped is not read.  One launch per spline, back to
+ * back on `stream` (side A's also forms the three per-query results; a side nothing is wanted of is not launched).  A problem's bits depend
+ * on its own inputs and on k only -- rp_trajectory_eval_vjp's order of additions, no atomics, no loop whose trip count depends on data.
+ * Argument rules as above.  Asynchronous on `stream`; never throws. */
+RP_API int rp_trajectory_tracking_hvp(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8],
+                                      const double *const d_spline_b[8], const double *d_lo, const double *d_hi, const double *d_delay,
+                                      const double *const d_g[3], const double *const d_spline_a_dot[8], const double *const d_spline_b_dot[8],
+                                      const double *d_lo_dot, const double *d_hi_dot, const double *d_delay_dot,
+                                      double *const d_spline_a_bar_dot[8], double *const d_spline_b_bar_dot[8], double *d_lo_bar_dot,
+                                      double *d_hi_bar_dot, double *d_delay_bar_dot);
 
 /* ---- when two splines meet: the first time in a window at which the gap between two splines reaches a level (new:
  * the reference draws one curve; the inverse of rp_trajectory_gap's D as rp_trajectory_crossing is of rp_trajectory_eval's pos; replaces a

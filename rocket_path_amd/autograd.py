@@ -38,7 +38,8 @@ times, one rp_trajectory_gap launch, both derivative modes one launch of the eva
 attained; min_time_gap composes it with two min_time_solve calls.
 trajectory_tracking (section 20) answers how far apart they are on average: the integrals of that gap, of its square and of the square of
 its rate over a window of times, one rp_trajectory_tracking launch, reverse mode one rp_trajectory_tracking_vjp call, forward mode one
-rp_trajectory_tracking_jvp launch; min_time_tracking composes it with two min_time_solve calls.
+rp_trajectory_tracking_jvp launch; min_time_tracking composes it with two min_time_solve calls; order=2 makes its backward differentiable
+once more (section 23): the backward of the backward is one rp_trajectory_tracking_jvp launch and one rp_trajectory_tracking_hvp call.
 trajectory_meeting (section 22) inverts that gap as trajectory_crossing inverts pos: the first time in a window at which the gap is at a
 level, one rp_trajectory_meeting launch, both derivative modes one launch of the evaluator's on each spline through the implicit function
 theorem; min_time_meeting composes it with two min_time_solve calls.
@@ -1437,7 +1438,74 @@ class _TrajectoryTracking(torch.autograd.Function):
         return tuple(outs)
 
 
-def trajectory_tracking(a, b, lo=None, hi=None, delay=None):
+class _TrajectoryTracking2(_TrajectoryTracking):
+    """_TrajectoryTracking with a backward that can be differentiated again (order=2): the same forward, the same forward-mode rule, and
+    the same one rp_trajectory_tracking_vjp call in backward, made through _TrackingVJP so that a create_graph backward records it."""
+
+    @staticmethod
+    def backward(ctx, *g):
+        if all(x is None for x in g):
+            return (None,) * 19
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        return _TrackingVJP.apply(*inputs, *g, tuple(ctx.needs_input_grad[:19]), ctx.shape)
+
+
+class _TrackingVJP(torch.autograd.Function):
+    """(the sixteen spline inputs, lo, hi, delay, the three upstream gradients) -> (the sixteen bars, lo_bar, hi_bar, delay_bar): one
+    rp_trajectory_tracking_vjp call that forms the bars `need` names (the others are None), as a function that can be differentiated once.
+    For cotangents u on its outputs:
+        g_bar = J u                                                  one rp_trajectory_tracking_jvp launch with tangents u
+        (splines, lo, hi, delay)_bar = (S_o g_o (second derivative of o)) u
+                                                                     one rp_trajectory_tracking_hvp call with direction u (symmetric)
+    each made only if something on its side requires grad."""
+
+    @staticmethod
+    def forward(*inputs):
+        need, shape = inputs[22], inputs[23]
+        a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
+        lo, hi, delay = (_dense(t) for t in inputs[16:19])
+        (n, k), dev = shape, inputs[0].device
+        bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(16)]
+        lo_bar, hi_bar, delay_bar = (torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (16, 17, 18))
+        if any(need[:19]):
+            _TrajectoryTracking._launch(capi.trajectory_tracking_vjp, a, b, lo, hi, delay, (n, k), [_dense(x) for x in inputs[19:22]], bars[:8],
+                                        bars[8:], lo_bar, hi_bar, delay_bar)
+        return tuple(bars) + (lo_bar, hi_bar, delay_bar)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)      # a bar nothing downstream uses arrives as None and goes to the kernels as NULL: not read
+        ctx.given = [t is not None for t in inputs[:22]]
+        ctx.shape = tuple(inputs[23])
+        ctx.save_for_backward(*[t for t in inputs[:22] if t is not None])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *u):
+        out = [None] * 24
+        if all(x is None for x in u):
+            return tuple(out)
+        kept = iter(ctx.saved_tensors)
+        inputs = [_dense(next(kept)) if given else None for given in ctx.given]
+        a, b, (lo, hi, delay), g = inputs[:8], inputs[8:16], inputs[16:19], inputs[19:22]
+        need, (n, k), dev = ctx.needs_input_grad, ctx.shape, a[0].device
+        dots = [_dense(x) for x in u]
+        if any(need[19:22]):
+            outs = [torch.empty((n, k), dtype=torch.float64, device=dev) if need[19 + c] else None for c in range(3)]
+            _TrajectoryTracking._launch(capi.trajectory_tracking_jvp, a, b, lo, hi, delay, (n, k), dots[:8], dots[8:16], dots[16], dots[17],
+                                        dots[18], outs)
+            out[19:22] = outs
+        if any(need[:19]) and any(x is not None for x in g):
+            bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(16)]
+            per_query = [torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (16, 17, 18)]
+            _TrajectoryTracking._launch(capi.trajectory_tracking_hvp, a, b, lo, hi, delay, (n, k), g, dots[:8], dots[8:16], dots[16], dots[17],
+                                        dots[18], bars[:8], bars[8:], *per_query)
+            out[:19] = bars + per_query
+        return tuple(out)
+
+
+def trajectory_tracking(a, b, lo=None, hi=None, delay=None, *, order=1):
     """The tracking integrals between two splines of trajectory_eval in one frame: with D(t) = pos_a(t) - pos_b(t - delay), the integrals of
     D (gap_int), D^2 (gap_sq) and (dD/dt)^2 (relvel_sq) over the windows of time [lo, hi].  a, b, lo, hi, delay: exactly trajectory_gap's
     -- each spline a sequence of six tensors (pos0, pos1, pos2, vel1, duration0, duration1), or of eight with (vel0, vel2) appended, of the
@@ -1452,26 +1520,43 @@ def trajectory_tracking(a, b, lo=None, hi=None, delay=None):
     rp_trajectory_tracking_vjp call that forms only the gradients autograd asks for, forward mode (torch.autograd.forward_ad,
     torch.func.jvp) one rp_trajectory_tracking_jvp launch; a double backward raises torch's once_differentiable
     error.  Where a window end is clamped, and at ties, the derivative is that of the branch the forward pass took; at a delay of exactly 0
-    the clamped start is the constant +0.0.  A NaN output has gradient 0 (forward mode: NaN).  Does not synchronise the host."""
+    the clamped start is the constant +0.0.  A NaN output has gradient 0 (forward mode: NaN).  Does not synchronise the host.
+
+    order=2 (1 or 2; anything else: ValueError) makes the backward differentiable once more -- torch.autograd.grad(..., create_graph=True),
+    torch.autograd.functional.vhp / hessian: the values, the gradients and the forward-mode tangents are the same launches and the same
+    bits as with order=1; the backward of the backward is one rp_trajectory_tracking_jvp launch (for the gradients in the first backward's
+    grad_outputs) and one rp_trajectory_tracking_hvp call (for those in the spline inputs, lo, hi and delay), each only if something on its
+    side requires grad.  The second derivative is that of the branch the forward took: exact, one-sided at ties and
+    at a delay of exactly 0.  A third derivative raises torch's once_differentiable error.  (torch.autograd.functional.hvp runs but forms
+    its product by differentiating the double backward in its own cotangent, which a once-differentiable backward does not offer, and
+    reports zeros: the matrix is symmetric, so functional.vhp, which is the double backward, gives the same product.)"""
     who = "trajectory_tracking"
+    _check_order(order, who)
     _check_spline_arg("a", a, who)
     _check_spline_arg("b", b, who)
     table_a, table_b = _spline_table("a", a, who), _spline_table("b", b, who)
     _check_same_batch(table_a[0], table_b[0], who)
     lo, hi, delay = _check_gap_queries(table_a[0], lo, hi, delay, who)
-    return _TrajectoryTracking.apply(*table_a, *table_b, lo, hi, delay)
+    function = _TrajectoryTracking if order == 1 else _TrajectoryTracking2
+    return function.apply(*table_a, *table_b, lo, hi, delay)
 
 
-def min_time_tracking(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None, vel_b=None, gap_tol=1e-8, max_iter=200, params=None):
+def min_time_tracking(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None, vel_b=None, gap_tol=1e-8, max_iter=200, params=None,
+                      order=1):
     """min_time_solve of two vehicles' problems, then trajectory_tracking of the two solutions.  Arguments as min_time_gap's.  Returns
     (gap_int, gap_sq, relvel_sq, solution_a, solution_b) with each solution min_time_solve's (vel1, duration0, duration1, iters, status).
     Plain composition: the integrals are differentiable to first order in both vehicles' positions and end velocities, in lo, hi and delay,
-    in both modes, through the solves' derivatives and the integrals'."""
+    in both modes, through the solves' derivatives and the integrals'.
+
+    order=2 (trajectory_tracking's): with the solves' own double backward, the integrals are twice differentiable in both vehicles'
+    positions, the window's ends and the delay for rest-to-rest problems.  With vel_a / vel_b that require grad the solve is first order,
+    and a double backward through it raises torch's once_differentiable error as it does with order=1."""
     who = "min_time_tracking"
+    _check_order(order, who)
     _check_vehicles(pos_a, pos_b, vel_a, vel_b, who)
     lo, hi, delay = _check_gap_queries(pos_a[0], lo, hi, delay, who)      # before the solves: a bad query costs none
     splines, solutions = _solve_vehicles(pos_a, pos_b, vel_a, vel_b, gap_tol, max_iter, params)
-    return tuple(trajectory_tracking(splines[0], splines[1], lo, hi, delay)) + (solutions[0], solutions[1])
+    return tuple(trajectory_tracking(splines[0], splines[1], lo, hi, delay, order=order)) + (solutions[0], solutions[1])
 
 
 def clear_pool():

@@ -122,6 +122,9 @@ SIGNATURES = {
                                                   _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp]),
     "rp_trajectory_tracking_jvp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
                                                   _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, ctypes.POINTER(_vp)]),
+    "rp_trajectory_tracking_hvp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
+                                                  _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp,
+                                                  ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp]),
     "rp_trajectory_integrals": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_integrals_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), _vp, _vp,
                                                    ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp]),
@@ -325,6 +328,20 @@ def trajectory_tracking_jvp(device, stream, n, k, spline_a, spline_b, d_lo=None,
     check(load_library().rp_trajectory_tracking_jvp(int(device), vp(stream), int(n), int(k), pointer_table(spline_a), pointer_table(spline_b),
                                                     vp(d_lo), vp(d_hi), vp(d_delay), pointer_table(spline_a_dot), pointer_table(spline_b_dot),
                                                     vp(d_lo_dot), vp(d_hi_dot), vp(d_delay_dot), tracking_table(value_dot)))
+
+
+def trajectory_tracking_hvp(device, stream, n, k, spline_a, spline_b, d_lo=None, d_hi=None, d_delay=None, g=None, spline_a_dot=None,
+                            spline_b_dot=None, d_lo_dot=None, d_hi_dot=None, d_delay_dot=None, spline_a_bar_dot=None, spline_b_bar_dot=None,
+                            d_lo_bar_dot=None, d_hi_bar_dot=None, d_delay_bar_dot=None):
+    """rp_trajectory_tracking_hvp: the derivative of trajectory_tracking_vjp's outputs along (`spline_a_dot`, `spline_b_dot`, d_lo_dot,
+    d_hi_dot, d_delay_dot) (None entries: zeros) at fixed upstream gradients `g`; `spline_a_bar_dot`, `spline_b_bar_dot` the eight output
+    addresses each and d_lo_bar_dot, d_hi_bar_dot, d_delay_bar_dot (None: not wanted)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    check(load_library().rp_trajectory_tracking_hvp(int(device), vp(stream), int(n), int(k), pointer_table(spline_a), pointer_table(spline_b),
+                                                    vp(d_lo), vp(d_hi), vp(d_delay), tracking_table(g), pointer_table(spline_a_dot),
+                                                    pointer_table(spline_b_dot), vp(d_lo_dot), vp(d_hi_dot), vp(d_delay_dot),
+                                                    pointer_table(spline_a_bar_dot), pointer_table(spline_b_bar_dot), vp(d_lo_bar_dot),
+                                                    vp(d_hi_bar_dot), vp(d_delay_bar_dot)))
 
 
 def integrals_table(addresses):

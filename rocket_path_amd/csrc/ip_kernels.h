@@ -195,6 +195,12 @@ hipError_t launch_tracking_jvp(size_t n, size_t k, const double *const d_spline_
                                const double *d_hi, const double *d_delay, const double *const d_spline_a_dot[8],
                                const double *const d_spline_b_dot[8], const double *d_lo_dot, const double *d_hi_dot, const double *d_delay_dot,
                                double *const d_value_dot[3], hipStream_t stream);
+// the derivative of launch_tracking_vjp's nineteen outputs along a direction on both splines and on lo, hi, delay, d_g held fixed
+hipError_t launch_tracking_hvp(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
+                               const double *d_hi, const double *d_delay, const double *const d_g[3], const double *const d_spline_a_dot[8],
+                               const double *const d_spline_b_dot[8], const double *d_lo_dot, const double *d_hi_dot, const double *d_delay_dot,
+                               double *const d_spline_a_bar_dot[8], double *const d_spline_b_bar_dot[8], double *d_lo_bar_dot,
+                               double *d_hi_bar_dot, double *d_delay_bar_dot, hipStream_t stream);
 // the first time in the same windows at which D reaches a level (d_level n x k; null: 0), NaN where it does not, and D' there (null: not wanted)
 hipError_t launch_meeting(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_level,
                           const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_relvel, hipStream_t stream);

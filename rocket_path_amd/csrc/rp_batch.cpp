@@ -1451,6 +1451,25 @@ int rp_trajectory_tracking_jvp(int device, void *stream, size_t n, size_t k, con
     return RP_OK;
 }
 
+int rp_trajectory_tracking_hvp(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8],
+                               const double *d_lo, const double *d_hi, const double *d_delay, const double *const d_g[3],
+                               const double *const d_spline_a_dot[8], const double *const d_spline_b_dot[8], const double *d_lo_dot,
+                               const double *d_hi_dot, const double *d_delay_dot, double *const d_spline_a_bar_dot[8],
+                               double *const d_spline_b_bar_dot[8], double *d_lo_bar_dot, double *d_hi_bar_dot, double *d_delay_bar_dot)
+{
+    const double *const *g = d_g ? d_g : kNoInputs;
+    double *const *bars_a = d_spline_a_bar_dot ? d_spline_a_bar_dot : kNoOutputs, *const *bars_b = d_spline_b_bar_dot ? d_spline_b_bar_dot : kNoOutputs;
+    const int st = check_tracking(__func__, device, d_spline_a, d_spline_b, n, k,
+                                  {d_lo, d_hi, d_delay, g[0], g[1], g[2], d_lo_dot, d_hi_dot, d_delay_dot, d_lo_bar_dot, d_hi_bar_dot, d_delay_bar_dot},
+                                  d_lo_bar_dot || d_hi_bar_dot || d_delay_bar_dot || any_of(bars_a, 8) || any_of(bars_b, 8));
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_tracking_hvp(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, g, d_spline_a_dot ? d_spline_a_dot : kNoInputs,
+                                   d_spline_b_dot ? d_spline_b_dot : kNoInputs, d_lo_dot, d_hi_dot, d_delay_dot, bars_a, bars_b, d_lo_bar_dot,
+                                   d_hi_bar_dot, d_delay_bar_dot, (hipStream_t)stream));
+    return RP_OK;
+}
+
 // the first time the gap between two splines reaches a level: rp_trajectory_gap's argument rules; the times cannot be left out
 int rp_trajectory_meeting(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8],
                           const double *d_level, const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_relvel)

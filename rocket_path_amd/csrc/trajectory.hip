@@ -10,6 +10,7 @@
 //   the extreme gap between two splines        k_gap                                            section 18
 //   the tracking integrals of two splines      k_tracking                                       section 20
 //   ... their first derivatives                k_tracking_jvp, k_tracking_vjp                   section 20
+//   ... the reverse rule along a direction     k_pair_hvp                                       section 23
 //   the first time two splines meet            k_meeting                                        section 22
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
@@ -30,7 +31,7 @@
 //   The pointwise kernels (everything but the two reverse rules): the block's P k queries are consecutive elements of tau (P is even,
 //     so a trip starts on a 16-byte boundary): each thread takes two at a time -- one 16-byte load, one 16-byte nontemporal store per
 //     wanted output -- and finds each query's problem by carrying (problem, column) along, without a division (stream_pairs).
-//   The reverse rules (k_trajectory_vjp, k_trajectory_hvp, k_vjp_integrals, k_window_hvp): a problem's k queries reduce to N sums (reduce_rows).  A
+//   The reverse rules (k_trajectory_vjp, k_trajectory_hvp, k_vjp_integrals, k_window_hvp, k_tracking_vjp, k_pair_hvp): a problem's k queries reduce to N sums (reduce_rows).  A
 //     group of G lanes (a power of two <= 64, from k alone) owns one problem at a time: lane l adds queries l, l + G, l + 2 G, ...
 //     (pairs 2 l, 2 l + 1, ... as 16-byte vectors when k is even -- every row then starts on a 16-byte boundary; single elements
 //     when k is odd) in that order into its own sums, the lanes combine by an xor butterfly (a + b == b + a bit for bit: every lane
@@ -1994,6 +1995,198 @@ k_tracking_vjp(FromArrays a, FromArrays b, size_t n, size_t k, int P, int G, con
     });
 }
 
+// ---- second order: the derivative of the tracking integrals' reverse rule along a direction (rp_trajectory_tracking_hvp; DESIGN.md
+// section 23) ----
+// The upstream gradients g are held fixed; the direction is on both splines' eight parameters and on lo, hi, delay.  Everything that routes
+// -- the classes of a and b, the order of the knots, which knot is clamped to which end, the segment each spline is in on a piece -- is the
+// forward's, and every piece end is an affine function of lo, hi, delay and the durations with constant coefficients: the ends carry the
+// forward rule's tangents (cd, ed) and have no second derivative.  Per piece the lines of k_tracking_vjp are differentiated one by one:
+//     (Xd, Vd, Ad, Jd)   the tangent of the piece's state at fixed u (k_tracking_jvp's), wd = ed - cd
+//     Em_dot = Em(Xd, Vd, Ad, Jd) + D(w) w^m wd        Qm_dot = Qm(Vd, Ad, Jd) + D'(w) w^m wd        (the moments are linear in the state)
+//     (Xb, Vb, Ab, Jb)_dot from them, term by term; W[f]_dot = W[f] of the dotted four + W[f - 1] sd at the own local start s
+//     P_A_dot, P_B_dot by the product rule with each side's own (vel, acc, jrk0)_dot = the tangent cubic's local state + (acc, jrk0, 0) ds
+//     F_dot = (g0 + 2 g1 D(w)) (D_d(w) + D'(w) wd) + 2 g2 D'(w) (D'_d(w) + D''(w) wd)
+// all polynomials in w from the piece's own start; nothing is divided per query.  reduce_rows over fourteen sums per side: S_a, S_j per
+// segment (segment_chain's coefficients on them depend on h), the dotted S_xd, S_vd, S_ad, S_jd per segment (segment_chain_dot; S_xd goes
+// to x0_bar_dot beside it) and the two dotted end terms of the durations.  One spline per launch as in k_tracking_vjp; side A's launch
+// writes lo_bar_dot, hi_bar_dot and delay_bar_dot.  The upstream gradients stay in registers: the staged constants fill the LDS.
+struct PairHvpLds {
+    HvpLds h;                           // the launch's own spline: segment_chain_dot's constants, their tangents and the eight results
+    double x0[2][kTrajProblems], x0d[2][kTrajProblems];
+    JvpLds o;                           // the other spline's constants and tangents
+    double Tv[kTrajProblems], To[kTrajProblems], Tvd[kTrajProblems], Tod[kTrajProblems];
+};
+
+template <int SIDE>
+__global__ void __launch_bounds__(kTrajBlock)
+k_pair_hvp(Spline8 a, Spline8 b, Spline8 a_dot, Spline8 b_dot, size_t n, size_t k, int P, int G, const double *__restrict__ lo,
+           const double *__restrict__ hi, const double *__restrict__ delay, In3 g, const double *__restrict__ lo_dot,
+           const double *__restrict__ hi_dot, const double *__restrict__ delay_dot, SplineBar8 bar, double *__restrict__ lo_bar_dot,
+           double *__restrict__ hi_bar_dot, double *__restrict__ delay_bar_dot)
+{
+    __shared__ PairHvpLds L;
+    auto stage_problem = [&](int place, size_t at) {
+        const int q = opaque_place(place);
+        const size_t i = opaque_index(at);
+        const DirectedDurations dv = stage_directed(i, SIDE ? b : a, SIDE ? b_dot : a_dot, [&](int seg, const DirectedSegment &s) {
+            L.h.c[seg][0][q] = s.va; L.h.c[seg][1][q] = s.vb; L.h.c[seg][2][q] = s.dx; L.h.c[seg][3][q] = s.acc0; L.h.c[seg][4][q] = s.jrk0;
+            L.h.c[seg][5][q] = s.ih;
+            L.h.t[seg][0][q] = s.vad; L.h.t[seg][1][q] = s.vbd; L.h.t[seg][2][q] = s.dxd; L.h.t[seg][3][q] = s.acc0d; L.h.t[seg][4][q] = s.jrk0d;
+            L.h.t[seg][5][q] = s.hd;
+            L.x0[seg][q] = s.x0;
+            L.x0d[seg][q] = s.x0d;
+        });
+        L.h.d0[q] = dv.t0;
+        L.h.d0_dot[q] = dv.t0d;
+        L.Tv[q] = dv.t0 + dv.t1;
+        L.Tvd[q] = dv.t0d + dv.t1d;
+        const DirectedDurations dn = stage_tangents(L.o, q, i, SIDE ? a : b, SIDE ? a_dot : b_dot);
+        L.To[q] = dn.t0 + dn.t1;
+        L.Tod[q] = dn.t0d + dn.t1d;
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
+        // one query, one piece at a time.  S: the fourteen sums -- segment 0's S_a, S_j, S_xd, S_vd, S_ad, S_jd, segment 1's, then the own
+        // duration0's and duration1's dotted end terms
+        auto query = [&](int q, double lo_q, double hi_q, double dl_q, double lo_in, double hi_in, double dl_in, double g0_in, double g1_in,
+                         double g2_in, double *S, double &lo_b, double &hi_b, double &dl_b) {
+            const double d0v = L.h.d0[q], d0o = L.o.d0[q], Tv = L.Tv[q], To = L.To[q];
+            const TrackWindow win = track_window<true>(SIDE ? d0o : d0v, SIDE ? To : Tv, SIDE ? d0v : d0o, SIDE ? Tv : To, lo_q, hi_q, dl_q);
+            // ok: of the query as given; one without an answer counts with gradients and query tangents of zero
+            const double g0 = win.ok ? g0_in : 0.0, g1 = win.ok ? g1_in : 0.0, g2 = win.ok ? g2_in : 0.0;
+            const double dl_d = win.ok ? dl_in : 0.0;
+            // the tangent of a piece end, by where it came from (k_tracking_jvp's)
+            const double d0vd = L.h.d0_dot[q], d0od = L.o.d0_dot[q];
+            const double d0Ad = SIDE ? d0od : d0vd, kBd = dl_d + (SIDE ? d0vd : d0od);
+            const double ad = win.ok ? (win.cls_a == kPtLo ? lo_in : (win.cls_a == kPtStart ? dl_in : 0.0)) : 0.0;
+            const double bd = win.cls_b == kPtHi ? (win.ok ? hi_in : 0.0)
+                                                 : (win.cls_b == kPtEndA ? (SIDE ? L.Tod[q] : L.Tvd[q]) : dl_d + (SIDE ? L.Tvd[q] : L.Tod[q]));
+            auto tangent = [&](int cls) { return cls == kEndA ? ad : (cls == kEndB ? bd : (cls == kEndKnotA ? d0Ad : kBd)); };
+            double bar_a = 0.0, bar_b = 0.0, dl = 0.0, carry = 0.0;
+            double &own0 = S[12];
+            auto route = [&](int cls, double v) {
+                bar_b += cls == kEndB ? v : 0.0;
+                if (SIDE == 0) {
+                    bar_a += cls == kEndA ? v : 0.0;
+                    own0 += cls == kEndKnotA ? v : 0.0;
+                    dl += cls == kEndKnotB ? v : 0.0;
+                } else {
+                    own0 += cls == kEndKnotB ? v : 0.0;
+                }
+            };
+            track_pieces(win, [&](const TrackPiece &p) {
+                const int seg_v = SIDE ? p.seg_b : p.seg_a, seg_o = SIDE ? p.seg_a : p.seg_b;
+                const SegmentConst cv{L.x0[seg_v][q], L.h.c[seg_v][0][q], L.h.c[seg_v][3][q], L.h.c[seg_v][4][q], 0.0, 0.0};
+                const SegmentConst tv{L.x0d[seg_v][q], L.h.t[seg_v][0][q], L.h.t[seg_v][3][q], L.h.t[seg_v][4][q], 0.0, 0.0};
+                const SegmentConst co = eval_const(L.o.c, seg_o, q), to = eval_const(L.o.t, seg_o, q);
+                const TrackState t = track_state(SIDE ? co : cv, SIDE ? cv : co, p);
+                const double cd = tangent(p.cls_c), ed = tangent(p.cls_e);
+                const double dsA = cd - (p.seg_a ? d0Ad : 0.0), dsB = cd - (p.seg_b ? kBd : dl_d), wd = ed - cd;
+                // each side's own (vel, acc, jrk0) along the direction, and the tangent of the piece's state at fixed u
+                double XAd, VAd, AAd, XBd, VBd, ABd;
+                local_state(SIDE ? to : tv, p.sA, XAd, VAd, AAd);
+                local_state(SIDE ? tv : to, p.sB, XBd, VBd, ABd);
+                const double JAd = SIDE ? to.jrk0 : tv.jrk0, JBd = SIDE ? tv.jrk0 : to.jrk0;
+                XAd += t.VA * dsA; VAd += t.AA * dsA; AAd += t.JA * dsA;
+                XBd += t.VB * dsB; VBd += t.AB * dsB; ABd += t.JB * dsB;
+                TrackState td;
+                td.X = XAd - XBd; td.V = VAd - VBd; td.A = AAd - ABd; td.J = JAd - JBd;
+                const double w = p.w, w2 = w * (w * 0.5), w3 = w2 * (w * (1.0 / 3.0));
+                const double Dw = piece_end_gap(t, w), Vw = piece_end_rate(t, w), Aw = t.A + w * t.J;
+                const double Ddw = piece_end_gap(td, w), Vdw = piece_end_rate(td, w);
+                // the gradients on the tangent of the piece's state, (Xb, Vb, Ab, Jb), and their derivatives along the direction
+                double Xb = g0 * w, Vb = g0 * w2, Ab = g0 * w3, Jb = g0 * (w3 * (w * 0.25));
+                double Xbd = g0 * wd, Vbd = g0 * (w * wd), Abd = g0 * (w2 * wd), Jbd = g0 * (w3 * wd);
+                {
+                    double E0, E1, E2, E3;
+                    gap_moments(t, w, E0, E1, E2, E3);
+                    const double h = 2.0 * g1;
+                    Xb += h * E0; Vb += h * E1; Ab += g1 * E2; Jb += g1 * (E3 * (1.0 / 3.0));
+                    gap_moments(td, w, E0, E1, E2, E3);
+                    const double e = Dw * wd;
+                    E0 += e; E1 += w * e; E2 += (w * w) * e; E3 += (w * w * w) * e;
+                    Xbd += h * E0; Vbd += h * E1; Abd += g1 * E2; Jbd += g1 * (E3 * (1.0 / 3.0));
+                }
+                {
+                    double Q0, Q1, Q2;
+                    rate_moments(t, w, Q0, Q1, Q2);
+                    const double h = 2.0 * g2;
+                    Vb += h * Q0; Ab += h * Q1; Jb += g2 * Q2;
+                    rate_moments(td, w, Q0, Q1, Q2);
+                    const double e = Vw * wd;
+                    Q0 += e; Q1 += w * e; Q2 += (w * w) * e;
+                    Vbd += h * Q0; Abd += h * Q1; Jbd += g2 * Q2;
+                }
+                // the launch's own side: the reverse rule's weights at its local start and their derivatives; B enters the gap with a minus
+                {
+                    const double s = SIDE ? p.sB : p.sA, sd = SIDE ? dsB : dsA, h2 = s * (s * 0.5), h3 = h2 * (s * (1.0 / 3.0));
+                    const double W1 = Xb * s + Vb, W2 = Xb * h2 + Vb * s + Ab, W3 = Xb * h3 + Vb * h2 + Ab * s + Jb;
+                    const double U[6] = {W2, W3, Xbd, (Xbd * s + Vbd) + Xb * sd, (Xbd * h2 + Vbd * s + Abd) + W1 * sd,
+                                         (Xbd * h3 + Vbd * h2 + Abd * s + Jbd) + W2 * sd};
+#pragma unroll
+                    for (int f = 0; f < 6; ++f) {
+                        const double Uf = SIDE ? -U[f] : U[f];
+                        S[f] += seg_v ? 0.0 : Uf;
+                        S[6 + f] += seg_v ? Uf : 0.0;
+                    }
+                }
+                const double Fd = (g0 + (2.0 * g1) * Dw) * (Ddw + Vw * wd) + ((2.0 * g2) * Vw) * (Vdw + Aw * wd);
+                const double PAd = (Xbd * t.VA + Vbd * t.AA + Abd * t.JA) + (Xb * VAd + Vb * AAd + Ab * JAd);
+                const double PBd = (Xbd * t.VB + Vbd * t.AB + Abd * t.JB) + (Xb * VBd + Vb * ABd + Ab * JBd);
+                // ds_A = dc - doff_A, ds_B = dc - doff_B, dw = de - dc: the reverse rule's routing, of the dotted terms
+                route(p.cls_c, carry + ((PAd - PBd) - Fd));
+                carry = Fd;
+                if (SIDE == 0) {
+                    own0 -= p.seg_a ? PAd : 0.0;
+                    dl += PBd;
+                } else {
+                    own0 += p.seg_b ? PBd : 0.0;
+                }
+            });
+            route(kEndB, carry);
+            const bool own_end = win.cls_b == (SIDE ? kPtEndB : kPtEndA);
+            S[12] += own_end ? bar_b : 0.0;
+            S[13] += own_end ? bar_b : 0.0;
+            if (SIDE == 0) {
+                lo_b = win.cls_a == kPtLo ? bar_a : 0.0;
+                hi_b = win.cls_b == kPtHi ? bar_b : 0.0;
+                dl_b = (dl + (win.cls_a == kPtStart ? bar_a : 0.0)) + (win.cls_b == kPtEndB ? bar_b : 0.0);
+            } else {
+                lo_b = hi_b = dl_b = 0.0;
+            }
+        };
+        // (a pair's two queries one after the other, each with its own 8-byte loads and stores, as in k_tracking_vjp)
+        reduce_rows<14>(opaque_uniform(G), here, p_first, k, [&](int q, size_t at, bool two, double *S) {
+            const double inf = __builtin_inf();
+#pragma nounroll
+            for (int second = 0; second < (two ? 2 : 1); ++second) {
+                const size_t el = opaque_index(at + second);
+                double lo_b, hi_b, dl_b;
+                query(q, lo ? lo[el] : -inf, hi ? hi[el] : inf, delay ? delay[el] : 0.0, lo_dot ? lo_dot[el] : 0.0, hi_dot ? hi_dot[el] : 0.0,
+                      delay_dot ? delay_dot[el] : 0.0, g.p[0] ? g.p[0][el] : 0.0, g.p[1] ? g.p[1][el] : 0.0, g.p[2] ? g.p[2][el] : 0.0, S, lo_b, hi_b,
+                      dl_b);
+                if (SIDE == 0) {
+                    if (lo_bar_dot) lo_bar_dot[el] = lo_b;
+                    if (hi_bar_dot) hi_bar_dot[el] = hi_b;
+                    if (delay_bar_dot) delay_bar_dot[el] = dl_b;
+                }
+            }
+        }, [&](int q, const double *S) {
+            SegmentBar s0 = segment_chain_dot(L.h, 0, q, S, S + 3);
+            SegmentBar s1 = segment_chain_dot(L.h, 1, q, S + 6, S + 9);
+            s0.x0 += S[2];
+            s1.x0 += S[8];
+            route_bars(L.h.bar, q, s0, s1, s0.h + S[12], s1.h + S[13]);
+            // a pair either of whose splines is under the NaN rule: all eight, also those that the other spline's NaN constants do not
+            // reach (a segment of the own spline that no piece selects)
+            if (L.Tv[q] != L.Tv[q] || L.To[q] != L.To[q]) {
+#pragma unroll
+                for (int f = 0; f < 8; ++f) L.h.bar[f][q] = quiet_nan();
+            }
+        });
+        write_bars(L.h.bar, bar, p_first, here);
+    });
+}
+
 // ---- when two splines meet: the first time the gap reaches a level (rp_trajectory_meeting) ----
 // The inverse of section 18's gap, as the crossing is the evaluator's.  D, the common domain, the clamped window [a, b], the knots and the
 // pieces are gap_query's; each piece is cut at its candidate roots of the relative velocity (gap_query's tests, the smaller first; a root
@@ -2394,6 +2587,34 @@ hipError_t launch_tracking_vjp(size_t n, size_t k, const double *const d_spline_
             hipLaunchKernelGGL(k_tracking_vjp<1>, grid, block, 0, stream, FromArrays{table_of<8>(d_spline_a)}, FromArrays{table_of<8>(d_spline_b)}, n,
                                k, P, G, d_lo, d_hi, d_delay, table_of<3>(d_g), table_of<8>(d_spline_b_bar), (double *)nullptr, (double *)nullptr,
                                (double *)nullptr);
+        });
+    return e;
+}
+
+// the same two launches for the reverse rule's derivative along a direction
+hipError_t launch_tracking_hvp(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_lo,
+                               const double *d_hi, const double *d_delay, const double *const d_g[3], const double *const d_spline_a_dot[8],
+                               const double *const d_spline_b_dot[8], const double *d_lo_dot, const double *d_hi_dot, const double *d_delay_dot,
+                               double *const d_spline_a_bar_dot[8], double *const d_spline_b_bar_dot[8], double *d_lo_bar_dot,
+                               double *d_hi_bar_dot, double *d_delay_bar_dot, hipStream_t stream)
+{
+    bool side_a = d_lo_bar_dot || d_hi_bar_dot || d_delay_bar_dot, side_b = false;
+    for (int f = 0; f < 8; ++f) {
+        side_a = side_a || d_spline_a_bar_dot[f];
+        side_b = side_b || d_spline_b_bar_dot[f];
+    }
+    hipError_t e = hipSuccess;
+    if (side_a)
+        e = launch_stateless<true>(n, k, [&](dim3 grid, dim3 block, int P, int G) {
+            hipLaunchKernelGGL(k_pair_hvp<0>, grid, block, 0, stream, table_of<8>(d_spline_a), table_of<8>(d_spline_b), table_of<8>(d_spline_a_dot),
+                               table_of<8>(d_spline_b_dot), n, k, P, G, d_lo, d_hi, d_delay, table_of<3>(d_g), d_lo_dot, d_hi_dot, d_delay_dot,
+                               table_of<8>(d_spline_a_bar_dot), d_lo_bar_dot, d_hi_bar_dot, d_delay_bar_dot);
+        });
+    if (e == hipSuccess && side_b)
+        e = launch_stateless<true>(n, k, [&](dim3 grid, dim3 block, int P, int G) {
+            hipLaunchKernelGGL(k_pair_hvp<1>, grid, block, 0, stream, table_of<8>(d_spline_a), table_of<8>(d_spline_b), table_of<8>(d_spline_a_dot),
+                               table_of<8>(d_spline_b_dot), n, k, P, G, d_lo, d_hi, d_delay, table_of<3>(d_g), d_lo_dot, d_hi_dot, d_delay_dot,
+                               table_of<8>(d_spline_b_bar_dot), (double *)nullptr, (double *)nullptr, (double *)nullptr);
         });
     return e;
 }
