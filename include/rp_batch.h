@@ -75,7 +75,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      (back-to-back fused solves of batches that share a stream overlap on an auxiliary stream; new entries only, no struct changes
  *      size and nothing a caller can observe through an existing entry changes, so the revision stays); rp_trajectory_meeting (the first
  *      time the gap between two splines reaches a level; a new entry only, the revision stays); rp_trajectory_tracking_hvp (the second
- *      derivative of the tracking integrals along a direction; a new entry only, the revision stays) */
+ *      derivative of the tracking integrals along a direction; a new entry only, the revision stays); rp_trajectory_separation (the
+ *      closest approach of two vehicles moving in up to three axes; a new entry only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -679,6 +680,40 @@ RP_API int rp_trajectory_tracking_hvp(int device, void *stream, size_t n, size_t
 RP_API int rp_trajectory_meeting(int device, void *stream, size_t n, size_t k, const double *const d_spline_a[8],
                                  const double *const d_spline_b[8], const double *d_level, const double *d_lo, const double *d_hi,
                                  const double *d_delay, double *d_time, double *d_relvel);
+
+/* ---- how close two vehicles moving in several axes get: the least squared distance over a window and when it is attained (DESIGN.md
+ * section 24; new: the reference draws one curve.  A vehicle in the plane or in space is d splines, one per axis, solved as d independent
+ * problems; the closest approach is no function of rp_trajectory_gap's per-axis extremes, which are attained at different times) ----
+ * d: the number of axes, 1, 2 or 3.  d_spline_a, d_spline_b: tables of 8 d pointers, axis-major -- entries [8 c .. 8 c + 7] are axis c's
+ * spline in rp_trajectory_eval's order, with its cubic, its segment rule and its NaN rule; if any of the 2 d splines of a problem is
+ * under the NaN rule, every output of that problem is NaN.  Queries are rp_trajectory_gap's: d_lo, d_hi, d_delay, n x k doubles each (NULL
+ * counts as -inf, +inf, 0); vehicle B is at t - delay when A is at t, one delay for all axes; a NaN or infinite delay makes the query NaN.
+ * D_c(t) = pos_Ac(t) - pos_Bc(t - delay) and the value is f(t) = the sum over c of D_c(t)^2, the SQUARED distance (smooth where the
+ * vehicles touch).  No extrapolation: the common domain is [S, E] with S = delay > 0 ? delay : +0.0 and E the smallest of the 2 d ends T_Ac
+ * and delay + T_Bc (A's before B's and a lower axis first among equals); the window is clamped to [a, b] inside it as rp_trajectory_gap
+ * clamps, and !(a <= b) makes the query NaN.
+ * Pieces: the 2 d knots k_Ac = duration0_Ac and k_Bc = delay + duration0_Bc cut [a, b] into at most 2 d + 1 pieces, walked without sorting:
+ * a piece ends at the smallest knot greater than its start and smaller than b, else at b.  On a piece with start c and u = t - c,
+ * g(u) = f'(u) / 2 = the sum of D_c(u) D_c'(u) is a quintic whose coefficients come from each axis' (X, V, A, J), the differences of the two
+ * selected segments' pos, vel, acc and jrk0 at c.  Its roots with a change of sign are isolated by the derivative chain -- the roots of g'''
+ * in closed form bracket those of g'', those the roots of g', those the roots of g -- and each bracket whose end values differ in sign is
+ * solved by rp_trajectory_crossing's kind of search (secant start, Newton steps kept in the bracket and bisected where they leave it or
+ * fail to halve the step before last, until p == 0 or the bracket or the step is within 2 ulp of the piece's end as a time on A's clock;
+ * the point of smallest |p| seen; at most 64 trips, whatever the input).  Nothing divides by a leading coefficient.
+ * Candidates in time order: a; per piece the roots of g strictly inside the piece and strictly inside (a, b), as times c + u, then the knot
+ * that ends it; b.  Each candidate's value is the sum, in axis order, of the squares of pos of rp_trajectory_eval(A_c, t) minus pos of
+ * rp_trajectory_eval(B_c, t - delay), plain products and sums -- a returned value is bit for bit that expression at the returned time.
+ * The least value wins, the earliest among equals; a NaN never.
+ * Outputs, n x k each, either may be NULL but not both: d_value, the least squared distance; d_time, when it is attained, on A's clock,
+ * with its candidate's own bits (lo's, delay's, +0.0, hi's, the winning end's, a knot's, or a root's sum c + u).
+ * Derivatives need no entry of their own: the envelope theorem, one rp_trajectory_eval_vjp or _jvp launch per spline
+ * at the returned time.  There is no batch entry (rp_trajectory_gap's reason).  Argument rules are rp_trajectory_gap's: entries [3] and [4]
+ * of any axis may be NULL (zeros), every given n x k array 16-byte aligned, n and k positive, k < 2^31; d outside 1..3, a NULL table or
+ * both outputs NULL give RP_ERR_INVALID before any device call.  Asynchronous on `stream`; never throws.  Pointwise: a query's bits depend
+ * on its problem's 16 d numbers and its own window ends and delay only. */
+RP_API int rp_trajectory_separation(int device, void *stream, size_t n, size_t k, int d, const double *const *d_spline_a,
+                                    const double *const *d_spline_b, const double *d_lo, const double *d_hi, const double *d_delay,
+                                    double *d_value, double *d_time);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

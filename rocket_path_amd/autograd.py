@@ -43,6 +43,10 @@ once more (section 23): the backward of the backward is one rp_trajectory_tracki
 trajectory_meeting (section 22) inverts that gap as trajectory_crossing inverts pos: the first time in a window at which the gap is at a
 level, one rp_trajectory_meeting launch, both derivative modes one launch of the evaluator's on each spline through the implicit function
 theorem; min_time_meeting composes it with two min_time_solve calls.
+trajectory_separation (section 24) answers how close two vehicles that move in up to three axes get, each axis a spline of its own: the
+least squared distance over a window of times and when it is attained, one rp_trajectory_separation launch, both derivative modes the
+evaluator's launches on each axis' two splines at that time (the envelope theorem); synchronize_axes stretches a vehicle's axes to its
+slowest; min_time_separation composes them with one min_time_solve call per vehicle over its axes.
 """
 import ctypes
 import threading
@@ -1205,6 +1209,260 @@ def min_time_meeting(pos_a, pos_b, level=None, lo=None, hi=None, delay=None, *, 
     level, lo, hi, delay = _check_meeting_queries(pos_a[0], level, lo, hi, delay, who)      # before the solves: a bad query costs none
     splines, solutions = _solve_vehicles(pos_a, pos_b, vel_a, vel_b, gap_tol, max_iter, params)
     return trajectory_meeting(splines[0], splines[1], level, lo, hi, delay), solutions[0], solutions[1]
+
+
+# ---- how close two vehicles moving in several axes get: the least squared distance over a window ----
+class _TrajectorySeparation(torch.autograd.Function):
+    """(sep_sq, t_closest) of two vehicles of d axes over the windows [lo, hi] clamped to the 2 d splines' common domain.  Inputs: d, then
+    A's 8 d tensors (axis-major, each axis in the table's order), B's 8 d, then lo, hi, delay.  The value is differentiable to first order
+    in all 16 d spline inputs, lo, hi and the delay by the envelope theorem: per axis one launch of the evaluator's derivative on A_c at
+    the returned time with 2 g D_c and one on B_c at time - delay with -2 g D_c, the time's own derivative routed by the class of the time
+    -- lo, hi, the end of an A_c, the end of a B_c, the delayed start; dropped at a stationary point, a knot or the clamp +0.0 (DESIGN.md
+    section 24).  The time is not differentiable."""
+
+    @staticmethod
+    def forward(d, *inputs):
+        a, b = [_dense(t) for t in inputs[:8 * d]], [_dense(t) for t in inputs[8 * d:16 * d]]
+        lo, hi, delay = (_dense(t) for t in inputs[16 * d:])
+        given = lo if lo is not None else hi if hi is not None else delay
+        shape = given.shape if given is not None else (inputs[0].shape[0], 1)
+        device = inputs[0].device
+        value, time = (torch.empty(shape, dtype=torch.float64, device=device) for _ in range(2))
+        n, k = shape
+        with torch.cuda.device(device):      # as _trajectory_launch
+            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_separation(device.index, torch.cuda.current_stream(device).cuda_stream, n, k, d, [addr(t) for t in a],
+                                       [addr(t) for t in b], addr(lo), addr(hi), addr(delay), addr(value), addr(time))
+        return value, time
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(output[1])
+        ctx.d = inputs[0]
+        ctx.given = [t is not None for t in inputs[1:]]
+        kept = [t for t in inputs[1:] if t is not None] + list(output)
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _saved(ctx):
+        """(A's and B's d lists of eight tensors; the delay (zeros for None); the time, 0 where the value is NaN, and B's, that minus the
+        delay; where it is NaN; the d gaps D_c there; the class masks LO, HI, [END of A_c], [END of B_c], START, exclusive and in that
+        priority)"""
+        d = ctx.d
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        value, time = list(kept)
+        a = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
+        b = [[_dense(t) for t in inputs[8 * (d + c):8 * (d + c) + 8]] for c in range(d)]
+        lo, hi, delay = inputs[16 * d:]
+        missing = torch.isnan(value) | torch.isnan(time)
+        zero = torch.zeros_like(time)
+        t_a = torch.where(missing, zero, time).contiguous()
+        shift = delay if delay is not None else zero
+        t_b = torch.where(missing, zero, t_a - shift).contiguous()
+        tests = [lo, hi] + [(s[6] + s[7]).unsqueeze(1) for s in a] + [shift + (s[6] + s[7]).unsqueeze(1) for s in b] + [shift]
+        masks, taken = [], missing
+        for at, ref in enumerate(tests):
+            mask = (t_a == ref) & ~taken if ref is not None else torch.zeros_like(missing)
+            if at == len(tests) - 1:
+                mask = mask & (shift > 0)      # a start clamped to +0.0 is a constant
+            masks.append(mask)
+            taken = taken | mask
+        gaps = []
+        for sa, sb in zip(a, b):
+            pa, pb = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
+            _trajectory_launch(capi.trajectory_eval, t_a.device, sa, t_a, pa, None, None)
+            _trajectory_launch(capi.trajectory_eval, t_a.device, sb, t_b, pb, None, None)
+            gaps.append(pa - pb)
+        return a, b, shift, t_a, t_b, missing, gaps, (masks[0], masks[1], masks[2:2 + d], masks[2 + d:2 + 2 * d], masks[-1])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_value, _g_time):
+        d = ctx.d
+        if g_value is None:
+            return (None,) * (16 * d + 4)
+        a, b, _, t_a, t_b, missing, gaps, (is_lo, is_hi, end_a, end_b, start) = _TrajectorySeparation._saved(ctx)
+        n = t_a.shape[0]
+        g = torch.where(missing, torch.zeros_like(g_value), g_value)      # a NaN value: gradient 0
+        need = ctx.needs_input_grad[1:]
+        want_time = any(need[8 * c + 6] or need[8 * c + 7] for c in range(2 * d)) or any(need[16 * d:])
+        bars, time_bar, shift_bar = [None] * (16 * d), None, None
+        for c in range(d):
+            g_pos = ((2.0 * g) * gaps[c]).contiguous()
+            for side, spline, tau, upstream in ((0, a[c], t_a, g_pos), (1, b[c], t_b, -g_pos)):
+                first = 8 * (side * d + c)
+                bar = [torch.empty(n, dtype=torch.float64, device=tau.device) if need[first + f] else None for f in range(8)]
+                tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if want_time else None
+                if want_time or any(x is not None for x in bar):
+                    _trajectory_launch(capi.trajectory_eval_vjp, tau.device, spline, tau, upstream, None, None, bar, tau_bar)
+                bars[first:first + 8] = bar
+                if want_time:
+                    time_bar = tau_bar if time_bar is None else time_bar + tau_bar
+                    if side:
+                        shift_bar = tau_bar if shift_bar is None else shift_bar + tau_bar
+        lo_bar = hi_bar = delay_bar = None
+        if want_time:
+            routed = lambda mask: torch.where(mask, time_bar, torch.zeros_like(time_bar))      # noqa: E731
+            for side, ends in ((0, end_a), (1, end_b)):
+                for c in range(d):
+                    for f in (6, 7):
+                        at = 8 * (side * d + c) + f
+                        if need[at]:
+                            bars[at] = bars[at] + routed(ends[c]).sum(dim=1)
+            if need[16 * d]:
+                lo_bar = routed(is_lo)
+            if need[16 * d + 1]:
+                hi_bar = routed(is_hi)
+            if need[16 * d + 2]:      # B is at time - delay, and the times that hold the delay move with it
+                holds = start
+                for mask in end_b:
+                    holds = holds | mask
+                delay_bar = routed(holds) - shift_bar
+        return (None,) + tuple(bars) + (lo_bar, hi_bar, delay_bar)
+
+    @staticmethod
+    def jvp(ctx, _t_d, *tangents):
+        d = ctx.d
+        a, b, _, t_a, t_b, missing, gaps, (is_lo, is_hi, end_a, end_b, start) = _TrajectorySeparation._saved(ctx)
+        n, k = t_a.shape
+        dots = [_dense(t) for t in tangents[:16 * d]]
+        zero = torch.zeros_like(t_a)
+        col = lambda t: t.unsqueeze(1).expand(n, k) if t is not None else zero      # noqa: E731
+        wide = lambda t: t if t is not None else zero      # noqa: E731
+        delay_dot = wide(tangents[16 * d + 2])
+        time_dot = torch.where(is_lo, wide(tangents[16 * d]), zero)
+        time_dot = torch.where(is_hi, wide(tangents[16 * d + 1]), time_dot)
+        for c in range(d):
+            time_dot = torch.where(end_a[c], col(dots[8 * c + 6]) + col(dots[8 * c + 7]), time_dot)
+            time_dot = torch.where(end_b[c], delay_dot + col(dots[8 * (d + c) + 6]) + col(dots[8 * (d + c) + 7]), time_dot)
+        time_dot = torch.where(start, delay_dot, time_dot)
+        value_dot = zero
+        for c in range(d):
+            pos_a, pos_b = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
+            _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, a[c], t_a, dots[8 * c:8 * c + 8], time_dot.contiguous(), pos_a, None, None)
+            _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, b[c], t_b, dots[8 * (d + c):8 * (d + c) + 8],
+                               (time_dot - delay_dot).contiguous(), pos_b, None, None)
+            value_dot = value_dot + (2.0 * gaps[c]) * (pos_a - pos_b)
+        return torch.where(missing, torch.full_like(t_a, float("nan")), value_dot), None
+
+
+def _check_axes(name, spline, who):
+    """One vehicle's (checked) sequence of six or eight tensors, (n, d) or (n,) each: d, and the d splines as _spline_table takes them."""
+    pos0 = spline[0]
+    _check_is_tensor(name + ": pos0", pos0, who)
+    if pos0.dim() not in (1, 2):
+        raise ValueError("%s: %s: pos0 must have shape (n, d) or (n,), got %s" % (who, name, tuple(pos0.shape)))
+    d = pos0.shape[1] if pos0.dim() == 2 else 1
+    if not 1 <= d <= 3:
+        raise ValueError("%s: %s has %d axes; one, two or three are supported" % (who, name, d))
+    for t in spline[1:]:
+        if t is None:
+            continue
+        _check_is_tensor(name, t, who)
+        if t.shape != pos0.shape:
+            raise ValueError("%s: %s: a tensor has shape %s, pos0 %s" % (who, name, tuple(t.shape), tuple(pos0.shape)))
+    if pos0.dim() == 1:
+        return 1, [list(spline)]
+    return d, [[t[:, c] if t is not None else None for t in spline] for c in range(d)]
+
+
+def trajectory_separation(a, b, lo=None, hi=None, delay=None):
+    """The closest approach of two vehicles that move in d = 1, 2 or 3 axes, each axis a spline of trajectory_eval solved on its own: the
+    least squared distance f(t) = sum over the axes of (pos_a,c(t) - pos_b,c(t - delay))^2 over the windows of time [lo, hi], and when it
+    is attained.  a, b: each a sequence of six tensors (pos0, pos1, pos2, vel1, duration0, duration1), or of eight with (vel0, vel2)
+    appended, each (n, d), or (n,) for d = 1, on the same ROCm device.  lo, hi, delay: (n, k), or (k,) for the same queries in every
+    problem; None: -inf / +inf / 0, all three None: k = 1, the whole common domain.  b's clock starts `delay` after a's, one delay for all
+    axes; no extrapolation: the window is clamped to [max(delay, 0), the smallest of the 2 d ends T_a,c and delay + T_b,c] -- with axes of
+    different total times the domain ends when the fastest axis does (synchronize_axes stretches them to the slowest).  Returns (sep_sq,
+    t_closest), (n, k) each; the distance is sep_sq.sqrt().  NaN where the clamped window is empty, where the delay is NaN or infinite, and
+    for a problem any of whose 2 d splines has a duration that is not finite or not > 0.
+
+    One rp_trajectory_separation launch on the current stream (include/rp_batch.h: the candidates are the window's ends, the knots and
+    the stationary points of f on each piece between knots, the real roots of a quintic; the earliest among equal values wins; a value is
+    bit for bit the sum in axis order of the squares of trajectory_eval(a_c, time) - trajectory_eval(b_c, time - delay)).  sep_sq is
+    differentiable to first order in all 16 d spline inputs, lo, hi and delay by the envelope theorem: per axis one rp_trajectory_eval
+    launch and one rp_trajectory_eval_vjp (reverse mode) or rp_trajectory_eval_jvp (forward mode) launch on each spline at the returned
+    time; a double backward raises torch's once_differentiable error.  At a tie between candidates, and where a
+    window end is clamped, the derivative is that of the branch the forward pass found.  A NaN value has gradient 0 (forward mode: NaN).
+    The time is not differentiable.  Does not synchronise the host."""
+    who = "trajectory_separation"
+    _check_spline_arg("a", a, who)
+    _check_spline_arg("b", b, who)
+    d, axes_a = _check_axes("a", a, who)
+    d_b, axes_b = _check_axes("b", b, who)
+    if d_b != d:
+        raise ValueError("%s: a has %d axes, b %d" % (who, d, d_b))
+    tables_a = [_spline_table("a, axis %d" % c, s, who) for c, s in enumerate(axes_a)]
+    tables_b = [_spline_table("b, axis %d" % c, s, who) for c, s in enumerate(axes_b)]
+    _check_same_batch(tables_a[0][0], tables_b[0][0], who)
+    lo, hi, delay = _check_gap_queries(tables_a[0][0], lo, hi, delay, who)
+    flat = [t for table in tables_a + tables_b for t in table]
+    return _TrajectorySeparation.apply(d, *flat, lo, hi, delay)
+
+
+def synchronize_axes(spline):
+    """A rest-to-rest vehicle's axes stretched in time to its slowest: spline is six tensors (pos0, pos1, pos2, vel1, duration0,
+    duration1), (n, d) each; with T_c = duration0 + duration1 of axis c and s = max_c T_c / T_c >= 1, the durations are multiplied by s
+    and vel1 is divided by it.  Every axis then runs through the same positions at s times the time -- the path is the same, the
+    velocities are divided by s and the accelerations by s^2, so the limits of the solve still hold -- and all axes end together.  Returns
+    (the stretched six tensors, s).  Plain torch: differentiable, on any device."""
+    if not isinstance(spline, (list, tuple)) or len(spline) != 6:
+        raise TypeError("synchronize_axes: spline must be a list or tuple of six tensors (pos0, pos1, pos2, vel1, duration0, duration1)")
+    pos0, pos1, pos2, vel1, duration0, duration1 = spline
+    for name, t in zip(("pos0", "pos1", "pos2", "vel1", "duration0", "duration1"), spline):
+        _check_is_tensor(name, t, "synchronize_axes")
+        if t.dim() != 2 or t.shape != pos0.shape:
+            raise ValueError("synchronize_axes: %s must have pos0's shape (n, d), got %s" % (name, tuple(t.shape)))
+    total = duration0 + duration1
+    s = total.max(dim=1, keepdim=True).values / total
+    return [pos0, pos1, pos2, vel1 / s, duration0 * s, duration1 * s], s
+
+
+def min_time_separation(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None, vel_b=None, synchronize=True, gap_tol=1e-8, max_iter=200,
+                        params=None):
+    """min_time_solve of two vehicles' axes, then trajectory_separation of the two solutions.  pos_a, pos_b: (pos0, pos1, pos2) of each
+    vehicle, (n, d) each; each vehicle is one solve over its n d axis problems.  vel_a, vel_b: (vel0, vel2) of each, (n, d) (None: rest to
+    rest).  synchronize (the default): each vehicle's axes are stretched to its slowest first (synchronize_axes; rest to rest only: with
+    end velocities given it raises ValueError).  lo, hi, delay as trajectory_separation's.  Returns (sep_sq, t_closest, solution_a,
+    solution_b) with each solution min_time_solve's (vel1, duration0, duration1, iters, status) as (n, d), as the solve left them (before
+    the stretch).  Plain composition: sep_sq is differentiable to first order in both vehicles' positions and end velocities, in lo, hi
+    and delay, in both modes."""
+    who = "min_time_separation"
+    if synchronize and (vel_a is not None or vel_b is not None):
+        raise ValueError(who + ": synchronize=True needs rest-to-rest vehicles; pass synchronize=False with end velocities")
+    flat = []
+    for name, pos, vel in (("pos_a", pos_a, vel_a), ("pos_b", pos_b, vel_b)):
+        if not isinstance(pos, (list, tuple)) or len(pos) != 3:
+            raise TypeError("%s: %s must be a list or tuple of three tensors (pos0, pos1, pos2)" % (who, name))
+        if vel is not None and (not isinstance(vel, (list, tuple)) or len(vel) != 2):
+            raise TypeError("%s: the velocities of %s must be None or a pair (vel0, vel2)" % (who, name))
+        for t in list(pos) + [v for v in (vel or ()) if v is not None]:
+            _check_is_tensor(name, t, who)
+            if t.dim() != 2 or t.shape != pos[0].shape or not 1 <= t.shape[1] <= 3:
+                raise ValueError("%s: every tensor of %s must have one shape (n, d) with d in 1..3, got %s" % (who, name, tuple(t.shape)))
+        flat.append(([t.t().reshape(-1) for t in pos], [v.t().reshape(-1) if v is not None else None for v in vel] if vel is not None else None))
+    if pos_a[0].shape != pos_b[0].shape:
+        raise ValueError("%s: pos_a has shape %s, pos_b %s" % (who, tuple(pos_a[0].shape), tuple(pos_b[0].shape)))
+    n, d = pos_a[0].shape
+    _check_vehicles(flat[0][0], flat[1][0], flat[0][1], flat[1][1], who)
+    if any(x is not None for x in (lo, hi, delay)):      # before the solves: a bad query costs none
+        lo, hi, delay = _check_gap_queries(pos_a[0][:, 0], lo, hi, delay, who)
+    splines, solutions = [], []
+    for pos, (flat_pos, flat_vel) in zip((pos_a, pos_b), flat):
+        vel0, vel2 = flat_vel if flat_vel is not None else (None, None)
+        solution = min_time_solve(*flat_pos, gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
+        solution = tuple(t.reshape(d, n).t() for t in solution)
+        spline = list(pos) + list(solution[:3])
+        if synchronize:
+            spline, _ = synchronize_axes(spline)
+        elif flat_vel is not None:
+            spline = spline + [v.reshape(d, n).t() if v is not None else None for v in flat_vel]
+        splines.append(spline)
+        solutions.append(solution)
+    return tuple(trajectory_separation(splines[0], splines[1], lo, hi, delay)) + (solutions[0], solutions[1])
 
 
 # ---- how much: integrals over a window ----

@@ -116,6 +116,8 @@ SIGNATURES = {
                                          ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "rp_trajectory_meeting": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
                                              _vp, _vp, _vp, _vp]),
+    "rp_trajectory_separation": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_vp),
+                                                ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
     "rp_trajectory_tracking": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
                                               _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_tracking_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
@@ -288,6 +290,29 @@ def trajectory_meeting(device, stream, n, k, spline_a, spline_b, d_level=None, d
     vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
     check(load_library().rp_trajectory_meeting(int(device), vp(stream), int(n), int(k), pointer_table(spline_a), pointer_table(spline_b),
                                                vp(d_level), vp(d_lo), vp(d_hi), vp(d_delay), vp(d_time), vp(d_relvel)))
+
+
+def axes_table(addresses, d):
+    """8 d device addresses (ints; None / 0: NULL) as a `double *const [8 d]` table of rp_trajectory_separation, axis-major: axis c's eight in
+    pointer_table's order at [8 c, 8 c + 8); None gives a NULL table."""
+    if addresses is None:
+        return None
+    addresses = list(addresses)
+    if d < 1 or len(addresses) != 8 * d:
+        raise ValueError("a table of %d axes has %d entries, got %d" % (d, 8 * d, len(addresses)))
+    return (_vp * (8 * d))(*[a if a else None for a in addresses])
+
+
+def trajectory_separation(device, stream, n, k, d, spline_a, spline_b, d_lo=None, d_hi=None, d_delay=None, d_value=None, d_time=None):
+    """rp_trajectory_separation: the least squared distance between two vehicles of `d` axes (1..3) over the windows [lo, hi] (n, k) clamped
+    to the common time domain of their 2 d splines (None / 0: -inf, +inf, a delay of 0), and the time at which it is attained (None / 0:
+    not wanted; not both).  `spline_a`, `spline_b`: 8 d addresses each, axis-major, each axis as for trajectory_eval."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d = int(d)
+    if not 1 <= d <= 3:
+        raise ValueError("trajectory_separation: d must be 1, 2 or 3, got %d" % d)
+    check(load_library().rp_trajectory_separation(int(device), vp(stream), int(n), int(k), d, axes_table(spline_a, d), axes_table(spline_b, d),
+                                                  vp(d_lo), vp(d_hi), vp(d_delay), vp(d_value), vp(d_time)))
 
 
 def tracking_table(addresses):

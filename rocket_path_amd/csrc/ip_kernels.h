@@ -204,5 +204,9 @@ hipError_t launch_tracking_hvp(size_t n, size_t k, const double *const d_spline_
 // the first time in the same windows at which D reaches a level (d_level n x k; null: 0), NaN where it does not, and D' there (null: not wanted)
 hipError_t launch_meeting(size_t n, size_t k, const double *const d_spline_a[8], const double *const d_spline_b[8], const double *d_level,
                           const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_relvel, hipStream_t stream);
+// the least squared distance of two vehicles of d axes (1..3) over the same windows and when it is attained: the tables hold 8 d pointers,
+// axis-major (either output null: not wanted)
+hipError_t launch_separation(size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_lo,
+                             const double *d_hi, const double *d_delay, double *d_value, double *d_time, hipStream_t stream);
 
 }  // namespace rp

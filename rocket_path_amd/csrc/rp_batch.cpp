@@ -1482,6 +1482,26 @@ int rp_trajectory_meeting(int device, void *stream, size_t n, size_t k, const do
     return RP_OK;
 }
 
+// the least squared distance of two vehicles moving in d axes: two tables of 8 d pointers, axis-major; rp_trajectory_gap's argument rules
+int rp_trajectory_separation(int device, void *stream, size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b,
+                             const double *d_lo, const double *d_hi, const double *d_delay, double *d_value, double *d_time)
+{
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
+    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
+    if (!d_spline_a) return fail(RP_ERR_INVALID, "%s: d_spline_a is null", __func__);
+    if (!d_spline_b) return fail(RP_ERR_INVALID, "%s: d_spline_b is null", __func__);
+    int st = RP_OK;
+    for (int x = 0; x < d && st == RP_OK; ++x) {
+        st = check_spline(__func__, "d_spline_a", d_spline_a + 8 * x);
+        if (st == RP_OK) st = check_spline(__func__, "d_spline_b", d_spline_b + 8 * x);
+    }
+    if (st == RP_OK) st = check_queries(__func__, n, k, nullptr, nullptr, {d_lo, d_hi, d_delay, d_value, d_time}, d_value || d_time);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_separation(n, k, d, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, (hipStream_t)stream));
+    return RP_OK;
+}
+
 // the integrals over a window, their first derivatives and the reverse rule's derivative along a direction
 int rp_trajectory_integrals(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                             double *const d_value[4])

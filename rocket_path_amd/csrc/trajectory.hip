@@ -12,6 +12,7 @@
 //   ... their first derivatives                k_tracking_jvp, k_tracking_vjp                   section 20
 //   ... the reverse rule along a direction     k_pair_hvp                                       section 23
 //   the first time two splines meet            k_meeting                                        section 22
+//   the closest approach of two vehicles       k_separation                                     section 24
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
 // rp_batch_integrals_device and rp_batch_sample*; the launchers are at the end of the file.
@@ -2291,6 +2292,234 @@ k_meeting(FromArrays a, FromArrays b, size_t n, size_t k, int P, const double *_
     });
 }
 
+// ---- how close two vehicles moving in D axes get: the least squared distance over a window (rp_trajectory_separation; DESIGN.md section
+// 24) ----
+// Vehicle A is D splines, one per axis, vehicle B likewise, B on a clock that starts `delay` after A's; D_c(t) = pos_Ac(t) - pos_Bc(t - delay)
+// and f(t) = the sum over the axes of D_c(t)^2 on the common domain [S, E], S = delay > 0 ? delay : +0.0, E the smallest of the 2 D ends T_Ac and
+// delay + T_Bc (A's before B's and a lower axis first among equals).  A query clamps its window to [a, b] as gap_query does and walks 2 D + 1
+// pieces without sorting the 2 D knots k_Ac = duration0_Ac, k_Bc = delay + duration0_Bc: a piece ends at the smallest knot greater than its
+// start and smaller than b, else at b (after which the remaining pieces have length zero).  On a piece with start c every axis' (X, V, A, J) is
+// track_state's, and with u = t - c
+//     g(u) = f'(u) / 2 = the sum of D_c(u) D_c'(u)
+// is a quintic in u whose six coefficients are plain products and sums of those 4 D numbers.  Its roots with a change of sign are isolated by
+// the derivative chain: the roots of g''' in closed form (velocity_breaks: padded to two breakpoints in [0, length]) bracket those of g'',
+// those bracket the roots of g', those the roots of g.  Between two neighbouring breakpoints a polynomial whose end values differ in sign is
+// solved by poly_search -- bracket_search's shape: Newton steps kept inside the bracket, bisection where a step leaves it or fails to halve the
+// step before last, the point of smallest |p| looked at, kSepTrips trips at most -- and the end values are computed once, the end of one
+// bracket being the start of the next.  No step divides by a leading coefficient: a polynomial of lower degree, or one that is zero (the
+// follower without a delay), has no change of sign.  A bracket without one leaves NaN, which the next level takes as a bracket of length zero.
+// Candidates in time order: a; per piece the roots of g strictly inside (0, length) and, as times c + u, strictly inside (a, b), then the
+// knot that ends the piece; b.  Every candidate's value is sep_at: the sum in axis order of the squares of eval_query(A_c, t) -
+// eval_query(B_c, t - delay); the walk is Extreme::take's for the minimum alone (strict: the earliest among equals, a NaN never) and the
+// time that comes back carries its candidate's own bits.  Selects only outside poly_search's loop; the pieces are a loop of 2 D + 1 trips and
+// the two queries of a pair a loop of two, both kept as loops, and so are the loops over the axes in sep_at and in the coefficient sum:
+// unrolled, the LDS reads of all axes are in flight together and D = 2 takes 149 VGPRs; kept, one axis' numbers are live at a time (125,
+// 126, 130 VGPRs for D = 1, 2, 3).  `trips` counts the searches' trips for the host-side cut of this code (tests/checks); the kernel drops
+// it.  The block's first P threads leave per problem the 2 D splines' evaluator constants and total times: 20 KiB of LDS per axis.
+constexpr int kSepTrips = 64;      // bisection alone reaches 2 ulp of any double bracket in ~53
+
+template <int D> struct SepLds {
+    EvalLds a[D], b[D];
+    double Ta[D][kTrajProblems], Tb[D][kTrajProblems];
+};
+
+// p[0] + p[1] u + ... + p[N - 1] u^(N - 1) and its derivative, by Horner's rule
+template <int N> __device__ __forceinline__ double poly_at(const double (&p)[N], double u)
+{
+    double v = p[N - 1];
+#pragma unroll
+    for (int i = N - 2; i >= 0; --i) v = p[i] + u * v;
+    return v;
+}
+
+template <int N> __device__ __forceinline__ double poly_slope(const double (&p)[N], double u)
+{
+    double v = (double)(N - 1) * p[N - 1];
+#pragma unroll
+    for (int i = N - 2; i >= 1; --i) v = (double)i * p[i] + u * v;
+    return v;
+}
+
+// the root of p in the bracket [lo, hi] whose ends leave p_lo != 0 and p_hi of the other sign: the point of smallest |p| looked at
+template <int N>
+__device__ __forceinline__ double poly_search(const double (&p)[N], double lo, double hi, double p_lo, double p_hi, double tol, int &trips)
+{
+    const bool up = p_lo < 0.0;
+    double width = hi - lo;
+    double best = abs_(p_hi) < abs_(p_lo) ? hi : lo, best_p = min_(abs_(p_lo), abs_(p_hi));
+    double s = lo + width * (p_lo * rcp_<double>(p_lo - p_hi));      // the secant point of the bracket
+    if (!(s > lo && s < hi)) s = lo + 0.5 * width;
+    double dx_old = width, dx = width;
+    for (int trip = 0; trip < kSepTrips; ++trip) {
+        const double g = poly_at(p, s), v = poly_slope(p, s);
+        ++trips;
+        if (abs_(g) < best_p) { best_p = abs_(g); best = s; }
+        if (g == 0.0) break;
+        if ((g < 0.0) == up) lo = s; else hi = s;
+        width = hi - lo;
+        if (!(width > tol)) break;
+        const double step = g * rcp_<double>(v);      // v == 0: infinite, outside
+        double next = s - step;
+        if (!(next > lo && next < hi && 2.0 * abs_(step) <= abs_(dx_old))) next = lo + 0.5 * width;
+        dx_old = dx;
+        dx = next - s;
+        if (!(abs_(dx) > tol)) break;
+        s = next;
+    }
+    return best;
+}
+
+// one level of the chain: the roots of p in (0, len] between the breakpoints brk (in order, NaN: none), one per bracket (NaN: none)
+template <int N, int M>
+__device__ __forceinline__ void roots_between(const double (&p)[N], const double (&brk)[M], double len, double tol, double (&out)[M + 1], int &trips)
+{
+    double lo = 0.0, p_lo = p[0];
+#pragma unroll
+    for (int j = 0; j <= M; ++j) {
+        const double mid = brk[j < M ? j : M - 1];
+        const double hi = j < M ? (mid == mid ? mid : lo) : len;
+        const double p_hi = poly_at(p, hi);
+        const bool cross = (p_lo < 0.0 && p_hi >= 0.0) || (p_lo > 0.0 && p_hi <= 0.0);      // a NaN fails
+        double r = quiet_nan();
+        if (cross) r = p_hi == 0.0 ? hi : poly_search(p, lo, hi, p_lo, p_hi, tol, trips);
+        out[j] = r;
+        lo = hi;
+        p_lo = p_hi;
+    }
+}
+
+template <int D> __device__ __forceinline__ double sep_at(const SepLds<D> &L, int q, double t, double delay)
+{
+    double sum = 0.0;      // (0.0 + x * x is x * x bit for bit)
+#pragma nounroll
+    for (int x = 0; x < D; ++x) {      // a loop that is kept: one axis' numbers live at a time
+        double pa, pb, vel, acc;
+        eval_query(L.a[x], q, t, pa, vel, acc);
+        eval_query(L.b[x], q, t - delay, pb, vel, acc);
+        const double gap = pa - pb;
+        sum = sum + gap * gap;
+    }
+    return sum;
+}
+
+template <int D>
+__device__ __forceinline__ void separation_query(const SepLds<D> &L, int q, double lo, double hi, double delay, double &value, double &time,
+                                                 int &trips)
+{
+    double E = __builtin_inf();
+    bool whole = true;      // none of the 2 D splines under the NaN rule
+#pragma unroll
+    for (int x = 0; x < D; ++x) {
+        const double TA = L.Ta[x][q];
+        whole = whole && TA == TA;
+        E = TA < E ? TA : E;
+    }
+#pragma unroll
+    for (int x = 0; x < D; ++x) {
+        const double EB = delay + L.Tb[x][q];
+        whole = whole && EB == EB;
+        E = EB < E ? EB : E;
+    }
+    const double S = delay > 0.0 ? delay : 0.0;
+    const double a = lo > S ? lo : (lo != lo ? lo : S), b = hi < E ? hi : (hi != hi ? hi : E);      // clamp_window's rule from S on
+    const bool ok = a <= b && finite_(delay) && whole;
+    double best_v = quiet_nan(), best_t = quiet_nan();
+    auto take = [&](bool on, double t) {
+        const double v = sep_at(L, q, t, delay);
+        const bool less = on && (v < best_v || (best_v != best_v && v == v));
+        best_v = less ? v : best_v;
+        best_t = less ? t : best_t;
+    };
+    take(ok, a);
+    double c = a;
+#pragma nounroll
+    for (int piece = 0; piece < 2 * D + 1; ++piece) {
+        double e = b;
+#pragma unroll
+        for (int x = 0; x < D; ++x) {
+            const double kA = L.a[x].d0[q], kB = delay + L.b[x].d0[q];
+            e = kA > c && kA < e ? kA : e;
+            e = kB > c && kB < e ? kB : e;
+        }
+        const bool knot = ok && e < b;
+        double g[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma nounroll
+        for (int x = 0; x < D; ++x) {
+            const double kA = L.a[x].d0[q], kB = delay + L.b[x].d0[q];
+            TrackPiece p;
+            p.seg_a = kA <= c;
+            p.seg_b = kB <= c;
+            p.sA = p.seg_a ? c - kA : c;
+            p.sB = p.seg_b ? c - kB : c - delay;
+            const TrackState st = track_state(eval_const(L.a[x].c, p.seg_a, q), eval_const(L.b[x].c, p.seg_b, q), p);
+            const double p0 = st.X, p1 = st.V, p2 = st.A * 0.5, p3 = st.J * (1.0 / 6.0);      // D_c(u)
+            const double q0 = st.V, q1 = st.A, q2 = st.J * 0.5;                                // D_c'(u)
+            const double t[6] = {p0 * q0, p0 * q1 + p1 * q0, (p0 * q2 + p1 * q1) + p2 * q0, (p1 * q2 + p2 * q1) + p3 * q0, p2 * q2 + p3 * q1,
+                                 p3 * q2};
+#pragma unroll
+            for (int i = 0; i < 6; ++i) g[i] = g[i] + t[i];
+        }
+        const double len = e - c, tol = kCrossTol * e;
+        const double g1[5] = {g[1], 2.0 * g[2], 3.0 * g[3], 4.0 * g[4], 5.0 * g[5]};
+        const double g2[4] = {2.0 * g[2], 6.0 * g[3], 12.0 * g[4], 20.0 * g[5]};
+        double r3[2], r2[3], r1[4], r0[5];
+        velocity_breaks(6.0 * g[3], 24.0 * g[4], 120.0 * g[5], len, r3[0], r3[1]);      // g''' = 6 g3 + 24 g4 u + 60 g5 u^2
+        roots_between(g2, r3, len, tol, r2, trips);
+        roots_between(g1, r2, len, tol, r1, trips);
+        roots_between(g, r1, len, tol, r0, trips);
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const double u = r0[j], t = c + u;
+            take(ok && u > 0.0 && u < len && a < t && t < b, t);
+        }
+        take(knot, e);
+        c = e;
+    }
+    take(ok, b);
+    value = best_v;
+    time = best_t;
+}
+
+template <int D> struct SepSplines { FromArrays a[D], b[D]; };
+
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) 
+k_separation(SepSplines<D> in, size_t n, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
+             const double *__restrict__ delay, double *__restrict__ value, double *__restrict__ time)
+{
+    __shared__ SepLds<D> L;
+    auto stage_problem = [&](int q, size_t i) {
+#pragma unroll
+        for (int x = 0; x < D; ++x) {
+            Knots ka = in.a[x].load(i), kb = in.b[x].load(i);
+            ka.check();
+            kb.check();
+            stage_eval(L.a[x], q, ka);
+            stage_eval(L.b[x], q, kb);
+            L.Ta[x][q] = ka.t0 + ka.t1;
+            L.Tb[x][q] = kb.t0 + kb.t1;
+        }
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k;
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double la, lb, ha, hb, da = 0.0, db = 0.0, va = 0.0, vb = 0.0, ta = 0.0, tb = 0.0;
+            load_window(lo, hi, e_first + e, two, la, lb, ha, hb);
+            if (delay) load_pair(delay, e_first + e, two, da, db);
+#pragma nounroll
+            for (int half = 0; half < (two ? 2 : 1); ++half) {      // one after the other: each query's searches have their own trip counts
+                double v, t;
+                int trips = 0;
+                separation_query(L, half ? qb : qa, half ? lb : la, half ? hb : ha, half ? db : da, v, t, trips);
+                va = half ? va : v; ta = half ? ta : t;
+                vb = half ? v : vb; tb = half ? t : tb;
+            }
+            if (value) store_pair(value, e_first + e, va, vb, two);
+            if (time) store_pair(time, e_first + e, ta, tb, two);
+        });
+    });
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -2626,6 +2855,31 @@ hipError_t launch_meeting(size_t n, size_t k, const double *const d_spline_a[8],
         hipLaunchKernelGGL(k_meeting, grid, block, 0, stream, FromArrays{table_of<8>(d_spline_a)}, FromArrays{table_of<8>(d_spline_b)}, n, k, P,
                            d_level, d_lo, d_hi, d_delay, d_time, d_relvel);
     });
+}
+
+template <int D>
+hipError_t launch_separation_axes(size_t n, size_t k, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_lo,
+                                  const double *d_hi, const double *d_delay, double *d_value, double *d_time, hipStream_t stream)
+{
+    SepSplines<D> in;
+    for (int x = 0; x < D; ++x) {
+        in.a[x] = FromArrays{table_of<8>(d_spline_a + 8 * x)};
+        in.b[x] = FromArrays{table_of<8>(d_spline_b + 8 * x)};
+    }
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_separation<D>, grid, block, 0, stream, in, n, k, P, d_lo, d_hi, d_delay, d_value, d_time);
+    });
+}
+
+hipError_t launch_separation(size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_lo,
+                             const double *d_hi, const double *d_delay, double *d_value, double *d_time, hipStream_t stream)
+{
+    switch (d) {
+    case 1: return launch_separation_axes<1>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
+    case 2: return launch_separation_axes<2>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
+    case 3: return launch_separation_axes<3>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
+    }
+    return hipErrorInvalidValue;
 }
 
 // ---- plot data by problem index: a range [first, first + count) of problems, wherever they lie in the batch ----
