@@ -76,7 +76,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      size and nothing a caller can observe through an existing entry changes, so the revision stays); rp_trajectory_meeting (the first
  *      time the gap between two splines reaches a level; a new entry only, the revision stays); rp_trajectory_tracking_hvp (the second
  *      derivative of the tracking integrals along a direction; a new entry only, the revision stays); rp_trajectory_separation (the
- *      closest approach of two vehicles moving in up to three axes; a new entry only, the revision stays) */
+ *      closest approach of two vehicles moving in up to three axes; a new entry only, the revision stays); rp_trajectory_contact (the
+ *      first time those two come within a distance; a new entry only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -714,6 +715,33 @@ RP_API int rp_trajectory_meeting(int device, void *stream, size_t n, size_t k, c
 RP_API int rp_trajectory_separation(int device, void *stream, size_t n, size_t k, int d, const double *const *d_spline_a,
                                     const double *const *d_spline_b, const double *d_lo, const double *d_hi, const double *d_delay,
                                     double *d_value, double *d_time);
+
+/* ---- when two vehicles moving in several axes first come within a distance (new: the reference draws one curve) ----
+ * The inverse of rp_trajectory_separation: d, the two tables of 8 d pointers, the NaN rule over the 2 d splines, the queries d_lo, d_hi and
+ * d_delay with their NULL meanings, D_c(t), f(t) = the sum over c of D_c(t)^2, the domain [S, E], the clamped window [a, b], the 2 d knots and
+ * the unsorted walk of 2 d + 1 pieces are that entry's, word for word.  d_level_sq, n x k doubles, required: the level of each query in units
+ * of SQUARED distance, like that entry's value (a radius r is the level r r); a NaN or infinite level makes its own query NaN; a negative one
+ * is legal and never reached.  d_time, n x k, required: the earliest t in [a, b] with f(t) = level, on A's clock; NaN where f does not reach
+ * the level in the window (no extrapolation).
+ * Each piece [c, e] is cut at the sign-changing roots of its quintic f' / 2 that are rp_trajectory_separation's candidates (the same
+ * coefficients, the same chain, the same stopping width 2 ulp of e; a root that is no candidate repeats the breakpoint before it), six
+ * sub-pieces on which f is monotone.  A breakpoint's value is the sum, in axis order, of the squares of pos of rp_trajectory_eval(A_c, t)
+ * minus pos of rp_trajectory_eval(B_c, t - delay), computed once: a level between f(a) and f(b) is held by some sub-piece's end values
+ * whatever the rounding.  The first sub-piece, in time order, whose end values hold the level between them (inclusive, either direction; a
+ * NaN holds nothing) gives the answer: its start with its own bits (lo's, delay's, +0.0, a knot's, a root's sum c + u) if the level equals
+ * the value there; otherwise the root of (F0 - level) + the sum of g_i (2 / (i + 1)) u^(i + 1), f - level about c, by the chain's search
+ * between the sub-piece's ends, as the time c + u kept inside the sub-piece (a level equal to the value at the end: that end, its bits).
+ * A level within rounding of an extreme of f may come out as the touch, as a later contact or as NaN.
+ * d_rate, n x k, may be NULL: f' at the returned time, bit for bit 2.0 times the sum in axis order from 0.0 of (pos_Ac - pos_Bc) (vel_Ac -
+ * vel_Bc) on rp_trajectory_eval's outputs at t and t - delay; NaN exactly where the time is.
+ * Derivatives need no entry of their own (section 25): dt = (dlevel - df at fixed t) / rate, one rp_trajectory_eval_vjp or _jvp launch per
+ * spline at the returned time.  There is no batch entry (rp_trajectory_gap's reason).  Argument rules are rp_trajectory_separation's; d
+ * outside 1..3, a NULL table, a NULL d_level_sq or d_time, a misaligned n x k array, n or k of 0 give RP_ERR_INVALID before any device
+ * call.  Asynchronous on `stream`; never throws.  Pointwise: a query's bits depend on its problem's 16 d numbers and its own level, window
+ * ends and delay only. */
+RP_API int rp_trajectory_contact(int device, void *stream, size_t n, size_t k, int d, const double *const *d_spline_a,
+                                 const double *const *d_spline_b, const double *d_level_sq, const double *d_lo, const double *d_hi,
+                                 const double *d_delay, double *d_time, double *d_rate);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

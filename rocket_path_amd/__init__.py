@@ -15,7 +15,8 @@ def __getattr__(name):
     if name in ("min_time_solve", "min_time_jacobian", "min_time_hessian", "trajectory_eval", "min_time_trajectory",
                 "trajectory_crossing", "min_time_crossing", "trajectory_extrema", "min_time_extrema", "trajectory_integrals",
                 "min_time_integrals", "trajectory_gap", "min_time_gap", "trajectory_tracking", "min_time_tracking",
-                "trajectory_meeting", "min_time_meeting", "trajectory_separation", "synchronize_axes", "min_time_separation"):
+                "trajectory_meeting", "min_time_meeting", "trajectory_separation", "synchronize_axes", "min_time_separation",
+                "trajectory_contact", "min_time_contact"):
         from . import autograd
         return getattr(autograd, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

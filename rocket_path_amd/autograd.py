@@ -47,6 +47,9 @@ trajectory_separation (section 24) answers how close two vehicles that move in u
 least squared distance over a window of times and when it is attained, one rp_trajectory_separation launch, both derivative modes the
 evaluator's launches on each axis' two splines at that time (the envelope theorem); synchronize_axes stretches a vehicle's axes to its
 slowest; min_time_separation composes them with one min_time_solve call per vehicle over its axes.
+trajectory_contact (section 25) inverts that squared distance as trajectory_meeting inverts the gap: the first time in a window at which the
+two vehicles are within a radius, one rp_trajectory_contact launch, both derivative modes the evaluator's launches on each axis' two splines
+through the implicit function theorem; min_time_contact composes it with the solves as min_time_separation does.
 """
 import ctypes
 import threading
@@ -1421,16 +1424,9 @@ def synchronize_axes(spline):
     return [pos0, pos1, pos2, vel1 / s, duration0 * s, duration1 * s], s
 
 
-def min_time_separation(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None, vel_b=None, synchronize=True, gap_tol=1e-8, max_iter=200,
-                        params=None):
-    """min_time_solve of two vehicles' axes, then trajectory_separation of the two solutions.  pos_a, pos_b: (pos0, pos1, pos2) of each
-    vehicle, (n, d) each; each vehicle is one solve over its n d axis problems.  vel_a, vel_b: (vel0, vel2) of each, (n, d) (None: rest to
-    rest).  synchronize (the default): each vehicle's axes are stretched to its slowest first (synchronize_axes; rest to rest only: with
-    end velocities given it raises ValueError).  lo, hi, delay as trajectory_separation's.  Returns (sep_sq, t_closest, solution_a,
-    solution_b) with each solution min_time_solve's (vel1, duration0, duration1, iters, status) as (n, d), as the solve left them (before
-    the stretch).  Plain composition: sep_sq is differentiable to first order in both vehicles' positions and end velocities, in lo, hi
-    and delay, in both modes."""
-    who = "min_time_separation"
+def _check_axis_vehicles(pos_a, pos_b, vel_a, vel_b, synchronize, who):
+    """Two vehicles of d axes as min_time_separation and min_time_contact take them: per vehicle (its three positions, its end velocities or
+    None), each (n, d) tensor flattened axis-major to n d problems."""
     if synchronize and (vel_a is not None or vel_b is not None):
         raise ValueError(who + ": synchronize=True needs rest-to-rest vehicles; pass synchronize=False with end velocities")
     flat = []
@@ -1446,10 +1442,14 @@ def min_time_separation(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=Non
         flat.append(([t.t().reshape(-1) for t in pos], [v.t().reshape(-1) if v is not None else None for v in vel] if vel is not None else None))
     if pos_a[0].shape != pos_b[0].shape:
         raise ValueError("%s: pos_a has shape %s, pos_b %s" % (who, tuple(pos_a[0].shape), tuple(pos_b[0].shape)))
-    n, d = pos_a[0].shape
     _check_vehicles(flat[0][0], flat[1][0], flat[0][1], flat[1][1], who)
-    if any(x is not None for x in (lo, hi, delay)):      # before the solves: a bad query costs none
-        lo, hi, delay = _check_gap_queries(pos_a[0][:, 0], lo, hi, delay, who)
+    return flat
+
+
+def _solve_axis_vehicles(pos_a, pos_b, flat, synchronize, gap_tol, max_iter, params):
+    """min_time_solve of each (checked) vehicle over its n d axis problems: (the two vehicles as trajectory_separation takes them, stretched
+    to their slowest axes if asked; the two solutions as (n, d), as the solve left them)."""
+    n, d = pos_a[0].shape
     splines, solutions = [], []
     for pos, (flat_pos, flat_vel) in zip((pos_a, pos_b), flat):
         vel0, vel2 = flat_vel if flat_vel is not None else (None, None)
@@ -1462,7 +1462,188 @@ def min_time_separation(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=Non
             spline = spline + [v.reshape(d, n).t() if v is not None else None for v in flat_vel]
         splines.append(spline)
         solutions.append(solution)
+    return splines, solutions
+
+
+def min_time_separation(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=None, vel_b=None, synchronize=True, gap_tol=1e-8, max_iter=200,
+                        params=None):
+    """min_time_solve of two vehicles' axes, then trajectory_separation of the two solutions.  pos_a, pos_b: (pos0, pos1, pos2) of each
+    vehicle, (n, d) each; each vehicle is one solve over its n d axis problems.  vel_a, vel_b: (vel0, vel2) of each, (n, d) (None: rest to
+    rest).  synchronize (the default): each vehicle's axes are stretched to its slowest first (synchronize_axes; rest to rest only: with
+    end velocities given it raises ValueError).  lo, hi, delay as trajectory_separation's.  Returns (sep_sq, t_closest, solution_a,
+    solution_b) with each solution min_time_solve's (vel1, duration0, duration1, iters, status) as (n, d), as the solve left them (before
+    the stretch).  Plain composition: sep_sq is differentiable to first order in both vehicles' positions and end velocities, in lo, hi
+    and delay, in both modes."""
+    who = "min_time_separation"
+    flat = _check_axis_vehicles(pos_a, pos_b, vel_a, vel_b, synchronize, who)
+    if any(x is not None for x in (lo, hi, delay)):      # before the solves: a bad query costs none
+        lo, hi, delay = _check_gap_queries(pos_a[0][:, 0], lo, hi, delay, who)
+    splines, solutions = _solve_axis_vehicles(pos_a, pos_b, flat, synchronize, gap_tol, max_iter, params)
     return tuple(trajectory_separation(splines[0], splines[1], lo, hi, delay)) + (solutions[0], solutions[1])
+
+
+# ---- when two vehicles moving in several axes first come within a distance ----
+class _TrajectoryContact(torch.autograd.Function):
+    """(time, rate) of the first time in the window at which f(t) = sum over the axes of (pos_Ac(t) - pos_Bc(t - delay))^2 is at the level:
+    the time is differentiable to first order in all 16 d spline inputs, the level and the delay through the evaluator's derivative launches
+    on each axis' two splines -- f(theta, time) = level gives
+    d time = (d level - sum of 2 D_c (d pos_Ac - d pos_Bc + vel_Bc d delay)) / rate with rate = f'(time).  Inputs: d, then A's 8 d tensors
+    (axis-major), B's 8 d, then level_sq, lo, hi, delay.  lo and hi only choose the branch.  rate is for the backward and is not
+    differentiable."""
+
+    @staticmethod
+    def forward(d, *inputs):
+        a, b = [_dense(t) for t in inputs[:8 * d]], [_dense(t) for t in inputs[8 * d:16 * d]]
+        level, lo, hi, delay = (_dense(t) for t in inputs[16 * d:])
+        shape, device = level.shape, inputs[0].device
+        time, rate = (torch.empty(shape, dtype=torch.float64, device=device) for _ in range(2))
+        n, k = shape
+        with torch.cuda.device(device):      # as _trajectory_launch
+            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_contact(device.index, torch.cuda.current_stream(device).cuda_stream, n, k, d, [addr(t) for t in a],
+                                    [addr(t) for t in b], addr(level), addr(lo), addr(hi), addr(delay), addr(time), addr(rate))
+        return time, rate
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(output[1])
+        d = ctx.d = inputs[0]
+        rest = inputs[1:]
+        ctx.given = [t is not None for t in rest[:16 * d]] + [False, False, False, rest[16 * d + 3] is not None]      # neither derivative
+        kept = [t for t, given in zip(rest, ctx.given) if given] + list(output)                                       # reads the level, lo or hi
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _saved(ctx):
+        """(A's and B's d lists of eight tensors; A's times, 0 where there is no contact, and B's, those minus the delay; rate; where there
+        is no contact; the d gaps D_c at those times)"""
+        d = ctx.d
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        time, rate = next(kept), next(kept)
+        a = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
+        b = [[_dense(t) for t in inputs[8 * (d + c):8 * (d + c) + 8]] for c in range(d)]
+        delay = inputs[16 * d + 3]
+        missing = torch.isnan(time)
+        zero = torch.zeros_like(time)
+        t_a = torch.where(missing, zero, time).contiguous()
+        t_b = torch.where(missing, zero, time - delay if delay is not None else time).contiguous()
+        gaps = []
+        for sa, sb in zip(a, b):
+            pa, pb = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
+            _trajectory_launch(capi.trajectory_eval, t_a.device, sa, t_a, pa, None, None)
+            _trajectory_launch(capi.trajectory_eval, t_a.device, sb, t_b, pb, None, None)
+            gaps.append(pa - pb)
+        return a, b, t_a, t_b, rate, missing, gaps
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_time, _g_rate):
+        d = ctx.d
+        if g_time is None:
+            return (None,) * (16 * d + 5)
+        a, b, t_a, t_b, rate, missing, gaps = _TrajectoryContact._saved(ctx)
+        need = ctx.needs_input_grad[1:]
+        w = torch.where(missing, torch.zeros_like(t_a), g_time / rate)      # an unreached level: gradient 0
+        n = t_a.shape[0]
+        bars, delay_bar = [None] * (16 * d), None
+        for c in range(d):
+            g_pos = ((2.0 * w) * gaps[c]).contiguous()
+            bar = [torch.empty(n, dtype=torch.float64, device=t_a.device) if need[8 * c + f] else None for f in range(8)]
+            if any(x is not None for x in bar):
+                _trajectory_launch(capi.trajectory_eval_vjp, t_a.device, a[c], t_a, -g_pos, None, None, bar, None)
+            bars[8 * c:8 * c + 8] = bar
+            first = 8 * (d + c)
+            bar = [torch.empty(n, dtype=torch.float64, device=t_a.device) if need[first + f] else None for f in range(8)]
+            tau_bar = torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) if need[16 * d + 3] else None
+            if tau_bar is not None or any(x is not None for x in bar):      # B is at time - delay
+                _trajectory_launch(capi.trajectory_eval_vjp, t_a.device, b[c], t_b, g_pos, None, None, bar, tau_bar)
+            bars[first:first + 8] = bar
+            if tau_bar is not None:
+                delay_bar = -tau_bar if delay_bar is None else delay_bar - tau_bar
+        return (None,) + tuple(bars) + (w if need[16 * d] else None, None, None, delay_bar)
+
+    @staticmethod
+    def jvp(ctx, _t_d, *tangents):
+        d = ctx.d
+        a, b, t_a, t_b, rate, missing, gaps = _TrajectoryContact._saved(ctx)
+        dots = [_dense(t) for t in tangents[:16 * d]]
+        level_dot, delay_dot = tangents[16 * d], tangents[16 * d + 3]
+        tau_dot_b = (-delay_dot).contiguous() if delay_dot is not None else None
+        total = level_dot if level_dot is not None else torch.zeros_like(t_a)
+        for c in range(d):
+            pos_a, pos_b = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
+            _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, a[c], t_a, dots[8 * c:8 * c + 8], None, pos_a, None, None)
+            _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, b[c], t_b, dots[8 * (d + c):8 * (d + c) + 8], tau_dot_b, pos_b, None, None)
+            total = total - (2.0 * gaps[c]) * (pos_a - pos_b)
+        return torch.where(missing, torch.full_like(t_a, float("nan")), total / rate), None
+
+
+def trajectory_contact(a, b, radius=None, lo=None, hi=None, delay=None, *, level_sq=None):
+    """The first time at which two vehicles that move in d = 1, 2 or 3 axes come within `radius` of each other: the earliest t in the
+    windows of time [lo, hi] at which f(t) = sum over the axes of (pos_a,c(t) - pos_b,c(t - delay))^2 is at radius^2 -- the inverse of
+    trajectory_separation's f as trajectory_meeting is of trajectory_gap's D.  a, b, lo, hi, delay: exactly trajectory_separation's.
+    radius: (n, k), or (k,) for the same radii in every problem; the level is radius * radius, formed in torch, so the radius gets its
+    gradient by the chain rule.  level_sq= may be given instead of radius (giving both, or neither, is a TypeError): the level itself, in
+    units of squared distance; a negative one is legal and never reached.  Returns t_contact (on a's clock), (n, k): NaN where f does not
+    reach the level in the window clamped to the 2 d splines' common domain (no extrapolation), where the clamped window is empty, where the
+    level is NaN or infinite or the delay NaN or infinite, and for a problem any of whose 2 d splines has a duration that is not finite or
+    not > 0.
+
+    One rp_trajectory_contact launch on the current stream (include/rp_batch.h: each piece between knots is cut at the stationary points of
+    f, the first of the monotone sub-pieces whose end values hold the level is solved by a bracketed Newton search with a fixed trip
+    bound; a level within rounding of an extreme of f may give the touch, a later contact, or NaN).  Differentiable to first order in all
+    16 d spline inputs, the level and the delay, d time = (d level - sum of 2 D_c (d pos_a,c - d pos_b,c + vel_b,c d delay)) / rate with
+    rate = f'(time): per axis one rp_trajectory_eval launch on each spline, and one rp_trajectory_eval_vjp (reverse mode) or
+    rp_trajectory_eval_jvp (forward mode) launch on each; a double backward raises torch's once_differentiable
+    error.  lo and hi get no gradient: the time depends on them through the branch only.  An unreached level has gradient 0 (forward
+    mode: NaN, as the time); where rate is 0 (a touch) there is no derivative and the result is inf or NaN; the time jumps where an
+    earlier extreme of f passes through the level.  Does not synchronise the host."""
+    who = "trajectory_contact"
+    if (radius is None) == (level_sq is None):
+        raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
+    _check_spline_arg("a", a, who)
+    _check_spline_arg("b", b, who)
+    d, axes_a = _check_axes("a", a, who)
+    d_b, axes_b = _check_axes("b", b, who)
+    if d_b != d:
+        raise ValueError("%s: a has %d axes, b %d" % (who, d, d_b))
+    tables_a = [_spline_table("a, axis %d" % c, s, who) for c, s in enumerate(axes_a)]
+    tables_b = [_spline_table("b, axis %d" % c, s, who) for c, s in enumerate(axes_b)]
+    _check_same_batch(tables_a[0][0], tables_b[0][0], who)
+    level = _check_contact_level(tables_a[0][0], radius, level_sq, who)
+    level, lo, hi, delay = _check_named_queries(tables_a[0][0], (("radius" if radius is not None else "level_sq", level), ("lo", lo), ("hi", hi),
+                                                                 ("delay", delay)), who)
+    flat = [t for table in tables_a + tables_b for t in table]
+    return _TrajectoryContact.apply(d, *flat, level, lo, hi, delay)[0]
+
+
+def _check_contact_level(pos0, radius, level_sq, who):
+    """The level of trajectory_contact: radius * radius, or level_sq (exactly one is given)."""
+    if radius is None:
+        return level_sq
+    _check_tau(pos0, radius, who, "radius")
+    return radius * radius
+
+
+def min_time_contact(pos_a, pos_b, radius=None, lo=None, hi=None, delay=None, *, level_sq=None, vel_a=None, vel_b=None, synchronize=True,
+                     gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve of two vehicles' axes, then trajectory_contact of the two solutions: min_time_separation's composition -- pos_a,
+    pos_b, vel_a, vel_b, synchronize and the solutions returned are its -- with trajectory_contact's radius (or level_sq=), lo, hi and delay.
+    Returns (t_contact, solution_a, solution_b).  Plain composition: the times are differentiable to first order in both vehicles' positions
+    and end velocities, in the radius and the delay, in both modes."""
+    who = "min_time_contact"
+    if (radius is None) == (level_sq is None):
+        raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
+    flat = _check_axis_vehicles(pos_a, pos_b, vel_a, vel_b, synchronize, who)
+    pos0 = pos_a[0][:, 0]      # before the solves: a bad query costs none
+    level = _check_contact_level(pos0, radius, level_sq, who)
+    level, lo, hi, delay = _check_named_queries(pos0, (("radius" if radius is not None else "level_sq", level), ("lo", lo), ("hi", hi),
+                                                       ("delay", delay)), who)
+    splines, solutions = _solve_axis_vehicles(pos_a, pos_b, flat, synchronize, gap_tol, max_iter, params)
+    return trajectory_contact(splines[0], splines[1], None, lo, hi, delay, level_sq=level), solutions[0], solutions[1]
 
 
 # ---- how much: integrals over a window ----

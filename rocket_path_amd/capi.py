@@ -118,6 +118,8 @@ SIGNATURES = {
                                              _vp, _vp, _vp, _vp]),
     "rp_trajectory_separation": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_vp),
                                                 ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
+    "rp_trajectory_contact": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_vp),
+                                             ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_trajectory_tracking": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
                                               _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_tracking_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
@@ -313,6 +315,19 @@ def trajectory_separation(device, stream, n, k, d, spline_a, spline_b, d_lo=None
         raise ValueError("trajectory_separation: d must be 1, 2 or 3, got %d" % d)
     check(load_library().rp_trajectory_separation(int(device), vp(stream), int(n), int(k), d, axes_table(spline_a, d), axes_table(spline_b, d),
                                                   vp(d_lo), vp(d_hi), vp(d_delay), vp(d_value), vp(d_time)))
+
+
+def trajectory_contact(device, stream, n, k, d, spline_a, spline_b, d_level_sq, d_lo=None, d_hi=None, d_delay=None, d_time=None, d_rate=None):
+    """rp_trajectory_contact: the first time in the windows [lo, hi] (n, k; trajectory_separation's clamping and None meanings) at which the
+    squared distance between two vehicles of `d` axes (1..3) reaches `d_level_sq` (n, k, required), NaN where it does not (`d_time`,
+    required), and the rate of change of the squared distance there (`d_rate`; None / 0: not wanted).  `spline_a`, `spline_b`: 8 d
+    addresses each, axis-major, each axis as for trajectory_eval."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d = int(d)
+    if not 1 <= d <= 3:
+        raise ValueError("trajectory_contact: d must be 1, 2 or 3, got %d" % d)
+    check(load_library().rp_trajectory_contact(int(device), vp(stream), int(n), int(k), d, axes_table(spline_a, d), axes_table(spline_b, d),
+                                               vp(d_level_sq), vp(d_lo), vp(d_hi), vp(d_delay), vp(d_time), vp(d_rate)))
 
 
 def tracking_table(addresses):

@@ -208,5 +208,9 @@ hipError_t launch_meeting(size_t n, size_t k, const double *const d_spline_a[8],
 // axis-major (either output null: not wanted)
 hipError_t launch_separation(size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_lo,
                              const double *d_hi, const double *d_delay, double *d_value, double *d_time, hipStream_t stream);
+// the first time in the same windows at which that squared distance reaches a level (d_level_sq n x k), NaN where it does not, and its rate
+// of change there (null: not wanted)
+hipError_t launch_contact(size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_level_sq,
+                          const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_rate, hipStream_t stream);
 
 }  // namespace rp

@@ -1502,6 +1502,27 @@ int rp_trajectory_separation(int device, void *stream, size_t n, size_t k, int d
     return RP_OK;
 }
 
+// the first time that squared distance reaches a level: rp_trajectory_separation's tables and argument rules, a level and a time that are required
+int rp_trajectory_contact(int device, void *stream, size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b,
+                          const double *d_level_sq, const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_rate)
+{
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
+    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
+    if (!d_spline_a) return fail(RP_ERR_INVALID, "%s: d_spline_a is null", __func__);
+    if (!d_spline_b) return fail(RP_ERR_INVALID, "%s: d_spline_b is null", __func__);
+    int st = RP_OK;
+    for (int x = 0; x < d && st == RP_OK; ++x) {
+        st = check_spline(__func__, "d_spline_a", d_spline_a + 8 * x);
+        if (st == RP_OK) st = check_spline(__func__, "d_spline_b", d_spline_b + 8 * x);
+    }
+    if (st == RP_OK && !d_time) st = fail(RP_ERR_INVALID, "%s: d_time is null", __func__);
+    if (st == RP_OK) st = check_queries(__func__, n, k, d_level_sq, "d_level_sq", {d_lo, d_hi, d_delay, d_time, d_rate}, true);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_contact(n, k, d, d_spline_a, d_spline_b, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate, (hipStream_t)stream));
+    return RP_OK;
+}
+
 // the integrals over a window, their first derivatives and the reverse rule's derivative along a direction
 int rp_trajectory_integrals(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                             double *const d_value[4])

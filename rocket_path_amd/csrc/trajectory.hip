@@ -13,6 +13,7 @@
 //   ... the reverse rule along a direction     k_pair_hvp                                       section 23
 //   the first time two splines meet            k_meeting                                        section 22
 //   the closest approach of two vehicles       k_separation                                     section 24
+//   the first time they come within a distance k_contact                                        section 25
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
 // rp_batch_integrals_device and rp_batch_sample*; the launchers are at the end of the file.
@@ -2520,6 +2521,173 @@ k_separation(SepSplines<D> in, size_t n, size_t k, int P, const double *__restri
     });
 }
 
+// ---- when two vehicles moving in D axes first come within a distance (rp_trajectory_contact) ----
+// The inverse of section 24's squared distance f, as the meeting is the gap's.  The splines, the NaN rule, the domain, the clamped window
+// [a, b], the knots, the unsorted walk of 2 D + 1 pieces and each piece's quintic g = f' / 2 with its sign-changing roots r0[0..4] are
+// separation_query's, operation for operation.  A piece [c, e] is cut at those of its roots that are separation_query's candidates (a root
+// that is none repeats the breakpoint before it: a sub-piece of length zero), which leaves six sub-pieces on which f is monotone.  Every
+// breakpoint's value is sep_at there, once: f(a) before the walk, and the f(e) of one piece is the f(c) of the next, so a level between
+// f(a) and f(b) is held by some sub-piece whatever the rounding.  A query takes the first sub-piece whose end values hold its level between
+// them; a level equal to the value at the sub-piece's start is that breakpoint with its own bits; otherwise poly_search solves
+//     h(u) = (F0 - level) + the sum of g_i (2 / (i + 1)) u^(i + 1) = 0,      F0 = the sum in axis order of X_c^2,
+// f - level in the piece's local form, from the sub-piece's start - c to its end - c with the breakpoint values minus the level as the end
+// values and the piece's stopping width; the time is c + u, kept inside the sub-piece.  The local form inside the search and the evaluator
+// at its ends: meeting_query's reason.  The rate that comes back is f' at that time on the evaluators' outputs.  A query whose window,
+// delay, level or splines make it NaN returns before the walk: no search runs for it.  The walk ends with the piece that holds the answer,
+// and at a piece after the first that starts at b (length zero: its six sub-pieces repeat f(b), which the sub-piece before them has
+// already been asked about); neither changes a bit (section 25 has the A/B).  One search site per piece: the six breakpoints select the
+// sub-piece, the search follows them.
+template <int D> __device__ __forceinline__ double sep_rate_at(const SepLds<D> &L, int q, double t, double delay)
+{
+    double sum = 0.0;
+#pragma nounroll
+    for (int x = 0; x < D; ++x) {
+        double pa, pb, va, vb, acc;
+        eval_query(L.a[x], q, t, pa, va, acc);
+        eval_query(L.b[x], q, t - delay, pb, vb, acc);
+        sum = sum + (pa - pb) * (va - vb);
+    }
+    return 2.0 * sum;
+}
+
+template <int D>
+__device__ __forceinline__ void contact_query(const SepLds<D> &L, int q, double level, double lo, double hi, double delay, double &time,
+                                              double &rate, int &trips)
+{
+    double E = __builtin_inf();
+    bool whole = true;      // none of the 2 D splines under the NaN rule
+#pragma unroll
+    for (int x = 0; x < D; ++x) {
+        const double TA = L.Ta[x][q];
+        whole = whole && TA == TA;
+        E = TA < E ? TA : E;
+    }
+#pragma unroll
+    for (int x = 0; x < D; ++x) {
+        const double EB = delay + L.Tb[x][q];
+        whole = whole && EB == EB;
+        E = EB < E ? EB : E;
+    }
+    const double S = delay > 0.0 ? delay : 0.0;
+    const double a = lo > S ? lo : (lo != lo ? lo : S), b = hi < E ? hi : (hi != hi ? hi : E);      // clamp_window's rule from S on
+    time = rate = quiet_nan();
+    if (!(a <= b && finite_(delay) && finite_(level) && whole)) return;
+    bool found = false;
+    double t_found = 0.0;
+    double c = a, f_c = sep_at(L, q, a, delay);
+#pragma nounroll
+    for (int piece = 0; piece < 2 * D + 1; ++piece) {
+        if (found || (piece > 0 && !(c < b))) break;
+        double e = b;
+#pragma unroll
+        for (int x = 0; x < D; ++x) {
+            const double kA = L.a[x].d0[q], kB = delay + L.b[x].d0[q];
+            e = kA > c && kA < e ? kA : e;
+            e = kB > c && kB < e ? kB : e;
+        }
+        double g[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, F0 = 0.0;
+#pragma nounroll
+        for (int x = 0; x < D; ++x) {
+            const double kA = L.a[x].d0[q], kB = delay + L.b[x].d0[q];
+            TrackPiece p;
+            p.seg_a = kA <= c;
+            p.seg_b = kB <= c;
+            p.sA = p.seg_a ? c - kA : c;
+            p.sB = p.seg_b ? c - kB : c - delay;
+            const TrackState st = track_state(eval_const(L.a[x].c, p.seg_a, q), eval_const(L.b[x].c, p.seg_b, q), p);
+            const double p0 = st.X, p1 = st.V, p2 = st.A * 0.5, p3 = st.J * (1.0 / 6.0);      // D_c(u)
+            const double q0 = st.V, q1 = st.A, q2 = st.J * 0.5;                                // D_c'(u)
+            const double t[6] = {p0 * q0, p0 * q1 + p1 * q0, (p0 * q2 + p1 * q1) + p2 * q0, (p1 * q2 + p2 * q1) + p3 * q0, p2 * q2 + p3 * q1,
+                                 p3 * q2};
+#pragma unroll
+            for (int i = 0; i < 6; ++i) g[i] = g[i] + t[i];
+            F0 = F0 + p0 * p0;
+        }
+        const double len = e - c, tol = kCrossTol * e;
+        const double g1[5] = {g[1], 2.0 * g[2], 3.0 * g[3], 4.0 * g[4], 5.0 * g[5]};
+        const double g2[4] = {2.0 * g[2], 6.0 * g[3], 12.0 * g[4], 20.0 * g[5]};
+        double r3[2], r2[3], r1[4], r0[5];
+        velocity_breaks(6.0 * g[3], 24.0 * g[4], 120.0 * g[5], len, r3[0], r3[1]);      // g''' = 6 g3 + 24 g4 u + 60 g5 u^2
+        roots_between(g2, r3, len, tol, r2, trips);
+        roots_between(g1, r2, len, tol, r1, trips);
+        roots_between(g, r1, len, tol, r0, trips);
+        bool here = false;
+        double t_lo = 0.0, t_hi = 0.0, f_lo = 0.0, f_hi = 0.0;      // the sub-piece taken and its end values
+        double t_prev = c, f_prev = f_c;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const double u = r0[j < 5 ? j : 4], t = j < 5 ? c + u : e;
+            const bool real = j == 5 || (u > 0.0 && u < len && a < t && t < b);
+            const double f = sep_at(L, q, t, delay);
+            const double t_next = real ? t : t_prev, f_next = real ? f : f_prev;
+            const bool holds = (f_prev <= level && level <= f_next) || (f_next <= level && level <= f_prev);      // a NaN fails
+            const bool first = holds && !here;
+            t_lo = first ? t_prev : t_lo; t_hi = first ? t_next : t_hi;
+            f_lo = first ? f_prev : f_lo; f_hi = first ? f_next : f_hi;
+            here = here || holds;
+            t_prev = t_next;
+            f_prev = f_next;
+        }
+        if (here) {
+            double t = t_lo;
+            if (f_lo != level) {
+                const double h[7] = {F0 - level, g[0] * 2.0, g[1] * (2.0 / 2.0), g[2] * (2.0 / 3.0), g[3] * (2.0 / 4.0), g[4] * (2.0 / 5.0),
+                                     g[5] * (2.0 / 6.0)};
+                t = c + poly_search(h, t_lo - c, t_hi - c, f_lo - level, f_hi - level, tol, trips);
+                t = t < t_lo ? t_lo : (t > t_hi ? t_hi : t);
+            }
+            found = true;
+            t_found = t;
+        }
+        c = e;
+        f_c = f_prev;
+    }
+    if (!found) return;
+    time = t_found;
+    rate = sep_rate_at(L, q, t_found, delay);
+}
+
+// Left to itself the allocator takes 132 / 142 / 141 VGPRs -- the level, F0 and the pair's second level more than k_separation carries -- which
+// is three waves per SIMD for D = 1, 2 where k_separation has four; asked for four it fits 128 / 128 without scratch (section 25).
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 3 : 4, 8)))
+k_contact(SepSplines<D> in, size_t n, size_t k, int P, const double *__restrict__ level, const double *__restrict__ lo,
+          const double *__restrict__ hi, const double *__restrict__ delay, double *__restrict__ time, double *__restrict__ rate)
+{
+    __shared__ SepLds<D> L;
+    auto stage_problem = [&](int q, size_t i) {
+#pragma unroll
+        for (int x = 0; x < D; ++x) {
+            Knots ka = in.a[x].load(i), kb = in.b[x].load(i);
+            ka.check();
+            kb.check();
+            stage_eval(L.a[x], q, ka);
+            stage_eval(L.b[x], q, kb);
+            L.Ta[x][q] = ka.t0 + ka.t1;
+            L.Tb[x][q] = kb.t0 + kb.t1;
+        }
+    };
+    for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k;
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double pa, pb, la, lb, ha, hb, da = 0.0, db = 0.0, ta = 0.0, tb = 0.0, ra = 0.0, rb = 0.0;
+            load_pair(level, e_first + e, two, pa, pb);
+            load_window(lo, hi, e_first + e, two, la, lb, ha, hb);
+            if (delay) load_pair(delay, e_first + e, two, da, db);
+#pragma nounroll
+            for (int half = 0; half < (two ? 2 : 1); ++half) {      // one after the other: each query's searches have their own trip counts
+                double t, r;
+                int trips = 0;
+                contact_query(L, half ? qb : qa, half ? pb : pa, half ? lb : la, half ? hb : ha, half ? db : da, t, r, trips);
+                ta = half ? ta : t; ra = half ? ra : r;
+                tb = half ? t : tb; rb = half ? r : rb;
+            }
+            store_pair(time, e_first + e, ta, tb, two);
+            if (rate) store_pair(rate, e_first + e, ra, rb, two);
+        });
+    });
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -2878,6 +3046,31 @@ hipError_t launch_separation(size_t n, size_t k, int d, const double *const *d_s
     case 1: return launch_separation_axes<1>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
     case 2: return launch_separation_axes<2>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
     case 3: return launch_separation_axes<3>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <int D>
+hipError_t launch_contact_axes(size_t n, size_t k, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_level_sq,
+                               const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_rate, hipStream_t stream)
+{
+    SepSplines<D> in;
+    for (int x = 0; x < D; ++x) {
+        in.a[x] = FromArrays{table_of<8>(d_spline_a + 8 * x)};
+        in.b[x] = FromArrays{table_of<8>(d_spline_b + 8 * x)};
+    }
+    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_contact<D>, grid, block, 0, stream, in, n, k, P, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate);
+    });
+}
+
+hipError_t launch_contact(size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_level_sq,
+                          const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_rate, hipStream_t stream)
+{
+    switch (d) {
+    case 1: return launch_contact_axes<1>(n, k, d_spline_a, d_spline_b, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate, stream);
+    case 2: return launch_contact_axes<2>(n, k, d_spline_a, d_spline_b, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate, stream);
+    case 3: return launch_contact_axes<3>(n, k, d_spline_a, d_spline_b, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate, stream);
     }
     return hipErrorInvalidValue;
 }
