@@ -77,7 +77,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      time the gap between two splines reaches a level; a new entry only, the revision stays); rp_trajectory_tracking_hvp (the second
  *      derivative of the tracking integrals along a direction; a new entry only, the revision stays); rp_trajectory_separation (the
  *      closest approach of two vehicles moving in up to three axes; a new entry only, the revision stays); rp_trajectory_contact (the
- *      first time those two come within a distance; a new entry only, the revision stays) */
+ *      first time those two come within a distance; a new entry only, the revision stays); rp_trajectory_fleet_separation (that closest
+ *      approach for every pair of a fleet in one launch; a new entry only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -742,6 +743,23 @@ RP_API int rp_trajectory_separation(int device, void *stream, size_t n, size_t k
 RP_API int rp_trajectory_contact(int device, void *stream, size_t n, size_t k, int d, const double *const *d_spline_a,
                                  const double *const *d_spline_b, const double *d_level_sq, const double *d_lo, const double *d_hi,
                                  const double *d_delay, double *d_time, double *d_rate);
+
+/* ---- the closest approach of every pair of a fleet, in one launch (new: the reference draws one curve) ----
+ * n scenes of m vehicles each, 2 <= m <= 256, all vehicles of a scene on one clock.  d_fleet: ONE table of 8 d pointers, axis-major, in
+ * rp_trajectory_separation's order; each array holds n m doubles, vehicle v of scene s at s m + v.  d_lo, d_hi: n x k doubles, the windows
+ * of scene s for ALL its pairs (NULL: -inf, +inf); read as single values, no alignment rule.  pairs = m (m - 1) / 2, ordered (i, j), i < j,
+ * lexicographic: (0, 1), (0, 2), .., (0, m - 1), (1, 2), ..  The outputs d_value and d_time are n x pairs x k, either may be NULL but not
+ * both.  Output [s, (i, j), q] is what rp_trajectory_separation returns, bit for bit in value and time, for A = vehicle i of scene s,
+ * B = vehicle j of scene s, the window [lo, hi][s, q] and d_delay == NULL: that entry's NaN rule (over the pair's 2 d splines: a vehicle
+ * under it makes exactly its m - 1 pairs NaN), domain, candidates and earliest-among-equals.  No pair-expanded array is read or written:
+ * the staging of a (scene, pair) problem reads the two vehicles where they lie.
+ * Derivatives need no entry of their own (section 26): rp_trajectory_separation's routing per vehicle instead of per pair, one
+ * rp_trajectory_eval and one rp_trajectory_eval_vjp or _jvp launch per axis on the n m splines.  There is no batch entry.  Entries [3] and
+ * [4] of any axis may be NULL (zeros); the outputs 16-byte aligned; m outside 2..256, d outside 1..3, a NULL table, both outputs NULL,
+ * n or k of 0, k >= 2^31 give RP_ERR_INVALID before any device call.  Asynchronous on `stream`; never throws.  Pointwise: a query's
+ * bits depend on its two vehicles' 16 d numbers and its scene's window ends only. */
+RP_API int rp_trajectory_fleet_separation(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                                          const double *d_lo, const double *d_hi, double *d_value, double *d_time);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

@@ -50,8 +50,13 @@ slowest; min_time_separation composes them with one min_time_solve call per vehi
 trajectory_contact (section 25) inverts that squared distance as trajectory_meeting inverts the gap: the first time in a window at which the
 two vehicles are within a radius, one rp_trajectory_contact launch, both derivative modes the evaluator's launches on each axis' two splines
 through the implicit function theorem; min_time_contact composes it with the solves as min_time_separation does.
+trajectory_fleet_separation (section 26) is trajectory_separation for every pair of a fleet, n scenes of m vehicles on one clock, in one
+rp_trajectory_fleet_separation launch, bit for bit the pair call's; its derivatives are that call's routed per vehicle through a slot table
+(fleet_slots), one evaluator launch and one derivative launch per axis on the n m splines, every sum a gather and a sum; fleet_pairs gives
+the order of the pairs; min_time_fleet_separation composes it with one min_time_solve call over all axis problems.
 """
 import ctypes
+import functools
 import threading
 
 import torch
@@ -1480,6 +1485,303 @@ def min_time_separation(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=Non
         lo, hi, delay = _check_gap_queries(pos_a[0][:, 0], lo, hi, delay, who)
     splines, solutions = _solve_axis_vehicles(pos_a, pos_b, flat, synchronize, gap_tol, max_iter, params)
     return tuple(trajectory_separation(splines[0], splines[1], lo, hi, delay)) + (solutions[0], solutions[1])
+
+
+# ---- the closest approach of every pair of a fleet ----
+FLEET_MOST = 256      # vehicles per scene (csrc/fleet_index.h)
+
+
+def _check_fleet_size(m, who):
+    if isinstance(m, bool) or not isinstance(m, int):
+        raise TypeError("%s: m must be an int, got %s" % (who, type(m).__name__))
+    if not 2 <= m <= FLEET_MOST:
+        raise ValueError("%s: a scene holds 2..%d vehicles, got m = %d" % (who, FLEET_MOST, m))
+
+
+def fleet_pairs(m, device=None):
+    """The pairs (i, j), i < j, of m vehicles (2..256) in the order of trajectory_fleet_separation's outputs -- lexicographic,
+    torch.triu_indices(m, m, 1)'s: a (m (m - 1) / 2, 2) int64 tensor on `device`."""
+    _check_fleet_size(m, "fleet_pairs")
+    return torch.triu_indices(m, m, 1, device=device).t().contiguous()
+
+
+@functools.lru_cache(maxsize=64)
+def _fleet_slots_cpu(m):
+    first, second = torch.triu_indices(m, m, 1)
+    pair_at = torch.zeros((m, m), dtype=torch.int64)
+    pair_at[first, second] = torch.arange(first.shape[0])
+    pair_at = pair_at + pair_at.t()
+    vehicle = torch.arange(m).unsqueeze(1)
+    partner = torch.arange(m - 1).unsqueeze(0) + (torch.arange(m - 1).unsqueeze(0) >= vehicle)      # every other vehicle, increasing
+    sign = torch.where(vehicle < partner, 1.0, -1.0).to(torch.float64)
+    return pair_at.gather(1, partner), sign, partner
+
+
+@functools.lru_cache(maxsize=64)
+def _fleet_slots_on(m, device):
+    pair, sign, _ = _fleet_slots_cpu(m)
+    first, second = torch.triu_indices(m, m, 1)
+    # where a pair's two entries lie in the (m, m - 1) table, flattened: vehicle i's row holds partner j > i at j - 1, vehicle j's holds i at i
+    return (pair.to(device), sign.to(device), (first * (m - 1) + second - 1).to(device), (second * (m - 1) + first).to(device),
+            first.to(device), second.to(device))
+
+
+def fleet_slots(m, device=None):
+    """The inverse of fleet_pairs as the derivative routing uses it: (pair, sign, partner), (m, m - 1) each -- vehicle v's row lists the
+    pairs that contain it (indices into fleet_pairs(m)), partners in increasing order, with +1.0 where v is the pair's first vehicle
+    and -1.0 where it is the second.  Every sum over a vehicle's pairs is a gather through this table and a sum: no atomics."""
+    _check_fleet_size(m, "fleet_slots")
+    return tuple(t.to(device) if device is not None else t.clone() for t in _fleet_slots_cpu(m))
+
+
+class _TrajectoryFleetSeparation(torch.autograd.Function):
+    """(sep_sq, t_closest), (n, pairs, k) each, of every pair of n scenes of m vehicles of d axes over the scenes' windows.  Inputs: d, m,
+    the fleet's 8 d tensors (axis-major, each axis in the table's order, each n m values with vehicle v of scene s at s m + v), lo, hi
+    (n, k).  The value is differentiable to first order in all 8 d fleet inputs, lo and hi by _TrajectorySeparation's envelope routing
+    done per vehicle: the returned times gathered through the slot table to (n m, (m - 1) k), per axis one evaluator launch and one
+    launch of its derivative on the n m splines, the time's own derivative routed by the class of the time -- lo, hi, the end of an
+    axis of the pair's first vehicle, of its second; dropped otherwise.  The time is not differentiable."""
+
+    @staticmethod
+    def forward(d, m, *inputs):
+        fleet = [_dense(t) for t in inputs[:8 * d]]
+        lo, hi = (_dense(t) for t in inputs[8 * d:])
+        given = lo if lo is not None else hi
+        n = inputs[0].shape[0] // m
+        k = given.shape[1] if given is not None else 1
+        device = inputs[0].device
+        value, time = (torch.empty((n, m * (m - 1) // 2, k), dtype=torch.float64, device=device) for _ in range(2))
+        with torch.cuda.device(device):      # as _trajectory_launch
+            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_fleet_separation(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in fleet],
+                                             addr(lo), addr(hi), addr(value), addr(time))
+        return value, time
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(output[1])
+        ctx.d, ctx.m = inputs[0], inputs[1]
+        ctx.given = [t is not None for t in inputs[2:]]
+        kept = [t for t in inputs[2:] if t is not None] + list(output)
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _saved(ctx):
+        """(the d lists of eight tensors; the slot tables; the times through the slot table, 0 where the value is NaN, (n m, (m - 1) k);
+        where the value is NaN, (n, pairs, k); the d gaps D_c there; a pair's view of a per-slot array; the class masks LO, HI, [END of
+        the first vehicle's axis c], [END of the second's], exclusive and in that priority)"""
+        d, m = ctx.d, ctx.m
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        value, time = list(kept)
+        fleet = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
+        lo, hi = inputs[8 * d:]
+        n, pairs, k = time.shape
+        slots = _fleet_slots_on(m, time.device)
+        pair, _, at_first, at_second, first, second = slots
+        missing = torch.isnan(value) | torch.isnan(time)
+        t = torch.where(missing, torch.zeros_like(time), time)
+        tau = t[:, pair.reshape(-1), :].reshape(n * m, (m - 1) * k).contiguous()
+
+        def per_pair(x):      # (n m, (m - 1) k) -> the pair's entry in its first vehicle's row and in its second's, (n, pairs, k) each
+            x = x.reshape(n, m * (m - 1), k)
+            return x[:, at_first, :], x[:, at_second, :]
+
+        ends = [(s[6] + s[7]).reshape(n, m) for s in fleet]
+        tests = [lo.unsqueeze(1) if lo is not None else None, hi.unsqueeze(1) if hi is not None else None]
+        tests += [e[:, first].unsqueeze(2) for e in ends] + [e[:, second].unsqueeze(2) for e in ends]
+        masks, taken = [], missing
+        for ref in tests:
+            mask = (t == ref) & ~taken if ref is not None else torch.zeros_like(missing)
+            masks.append(mask)
+            taken = taken | mask
+        gaps = []
+        for s in fleet:
+            pos = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
+            _trajectory_launch(capi.trajectory_eval, tau.device, s, tau, pos, None, None)
+            pos_first, pos_second = per_pair(pos)
+            gaps.append(pos_first - pos_second)
+        return fleet, slots, tau, missing, gaps, per_pair, (masks[0], masks[1], masks[2:2 + d], masks[2 + d:])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_value, _g_time):
+        d, m = ctx.d, ctx.m
+        if g_value is None:
+            return (None,) * (8 * d + 4)
+        fleet, (pair, sign, _, _, _, _), tau, missing, gaps, per_pair, (is_lo, is_hi, end_first, end_second) = _TrajectoryFleetSeparation._saved(ctx)
+        n, pairs, k = missing.shape
+        g = torch.where(missing, torch.zeros_like(g_value), g_value)      # a NaN value: gradient 0
+        need = ctx.needs_input_grad[2:]
+        want_time = any(need[8 * c + 6] or need[8 * c + 7] for c in range(d)) or any(need[8 * d:])
+        through = lambda x: x[:, pair.reshape(-1), :].reshape(n, m, m - 1, k)      # noqa: E731  (n, pairs, k) -> per vehicle and slot
+        signs = sign.reshape(1, m, m - 1, 1)
+        bars, time_bar = [None] * (8 * d), None
+        for c in range(d):
+            g_pos = torch.where(missing, torch.zeros_like(g), (2.0 * g) * gaps[c])      # (a bad vehicle's gap is NaN: not into its partners)
+            upstream = (signs * through(g_pos)).reshape(tau.shape).contiguous()
+            bar = [torch.empty(n * m, dtype=torch.float64, device=tau.device) if need[8 * c + f] else None for f in range(8)]
+            tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if want_time else None
+            if want_time or any(x is not None for x in bar):
+                _trajectory_launch(capi.trajectory_eval_vjp, tau.device, fleet[c], tau, upstream, None, None, bar, tau_bar)
+            bars[8 * c:8 * c + 8] = bar
+            if want_time:      # the pair's: its two vehicles', added in _TrajectorySeparation's order -- the same bits per pair and query
+                for share in per_pair(tau_bar):
+                    time_bar = share if time_bar is None else time_bar + share
+        lo_bar = hi_bar = None
+        if want_time:
+            routed = lambda mask: torch.where(mask, time_bar, torch.zeros_like(time_bar))      # noqa: E731
+            for c in range(d):
+                if need[8 * c + 6] or need[8 * c + 7]:      # a vehicle's pairs: through the slot table, then a plain sum
+                    mine = torch.where(signs > 0, through(routed(end_first[c])), through(routed(end_second[c]))).sum(dim=(2, 3)).reshape(n * m)
+                    for f in (6, 7):
+                        if need[8 * c + f]:
+                            bars[8 * c + f] = bars[8 * c + f] + mine
+            if need[8 * d]:
+                lo_bar = routed(is_lo).sum(dim=1)
+            if need[8 * d + 1]:
+                hi_bar = routed(is_hi).sum(dim=1)
+        return (None, None) + tuple(bars) + (lo_bar, hi_bar)
+
+    @staticmethod
+    def jvp(ctx, _t_d, _t_m, *tangents):
+        d, m = ctx.d, ctx.m
+        fleet, (pair, _, _, _, first, second), tau, missing, gaps, per_pair, (is_lo, is_hi, end_first, end_second) = _TrajectoryFleetSeparation._saved(ctx)
+        n, pairs, k = missing.shape
+        dots = [_dense(t) for t in tangents[:8 * d]]
+        zero = torch.zeros(missing.shape, dtype=torch.float64, device=tau.device)
+        wide = lambda t: t.unsqueeze(1) if t is not None else zero      # noqa: E731
+        time_dot = torch.where(is_lo, wide(tangents[8 * d]), zero)
+        time_dot = torch.where(is_hi, wide(tangents[8 * d + 1]), time_dot)
+        for which, ends in ((first, end_first), (second, end_second)):
+            for c in range(d):
+                total = None
+                for t in (dots[8 * c + 6], dots[8 * c + 7]):
+                    if t is not None:
+                        total = t if total is None else total + t
+                if total is not None:
+                    time_dot = torch.where(ends[c], total.reshape(n, m)[:, which].unsqueeze(2), time_dot)
+        tau_dot = time_dot[:, pair.reshape(-1), :].reshape(tau.shape).contiguous()
+        value_dot = zero
+        for c in range(d):
+            pos_dot = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
+            _trajectory_launch(capi.trajectory_eval_jvp, tau.device, fleet[c], tau, dots[8 * c:8 * c + 8], tau_dot, pos_dot, None, None)
+            dot_first, dot_second = per_pair(pos_dot)
+            value_dot = value_dot + (2.0 * gaps[c]) * (dot_first - dot_second)
+        return torch.where(missing, torch.full_like(zero, float("nan")), value_dot), None
+
+
+def _check_fleet(fleet, who):
+    """A fleet as trajectory_fleet_separation takes it: six or eight float64 tensors (n, m, d): shapes and types (the devices come after
+    the windows' shapes: _check_fleet_devices).  Returns (n, m, d, the d splines as lists of eight (n m,) tensors in the table's order)."""
+    _check_spline_arg("fleet", fleet, who)
+    pos0 = fleet[0]
+    _check_is_tensor("fleet: pos0", pos0, who)
+    if pos0.dim() != 3:
+        raise ValueError("%s: fleet: pos0 must have shape (n, m, d), got %s" % (who, tuple(pos0.shape)))
+    n, m, d = pos0.shape
+    if n == 0:
+        raise ValueError(who + ": empty batch")
+    _check_fleet_size(int(m), who)
+    if not 1 <= d <= 3:
+        raise ValueError("%s: fleet has %d axes; one, two or three are supported" % (who, d))
+    names = ("pos0", "pos1", "pos2", "vel1", "duration0", "duration1", "vel0", "vel2")
+    for name, t in zip(names, fleet):
+        if t is None and name in ("vel0", "vel2"):
+            continue
+        _check_is_tensor("fleet: " + name, t, who)
+        if t.shape != pos0.shape:
+            raise ValueError("%s: fleet: %s has shape %s, pos0 %s" % (who, name, tuple(t.shape), tuple(pos0.shape)))
+        _check_is_float64("fleet: " + name, t, who)
+    vel0, vel2 = fleet[6:] if len(fleet) == 8 else (None, None)
+    table = list(fleet[:3]) + [vel0, vel2] + list(fleet[3:6])
+    return n, int(m), d, [[t[:, :, c].reshape(n * m) if t is not None else None for t in table] for c in range(d)]
+
+
+def _check_fleet_devices(fleet, who):
+    for t in fleet:
+        if t is not None and (t.device.type != "cuda" or t.device != fleet[0].device):
+            raise TypeError("%s: fleet: a tensor is on %s; the fleet must be on one ROCm device" % (who, t.device))
+
+
+def _check_fleet_windows(n, device, lo, hi, who):
+    """lo, hi (None: -inf / +inf): float64, (n, k) -- one window per scene and query, for all its pairs -- or (k,); returned as (n, k)."""
+    out, shapes = [], []
+    for name, t in (("lo", lo), ("hi", hi)):
+        if t is None:
+            out.append(None)
+            continue
+        _check_is_tensor(name, t, who)
+        _check_is_float64(name, t, who)
+        if t.dim() == 1 and t.shape[0] > 0:
+            t = t.unsqueeze(0).expand(n, t.shape[0])
+        elif t.dim() != 2 or t.shape[0] != n or t.shape[1] == 0:
+            raise ValueError("%s: %s must have shape (%d, k) or (k,) with k >= 1 -- a scene's window holds for all its pairs -- got %s"
+                             % (who, name, n, tuple(t.shape)))
+        if t.device != device:
+            raise TypeError("%s: %s is on %s; it must be on the fleet's device %s" % (who, name, t.device, device))
+        out.append(t)
+        shapes.append((name, t.shape))
+    if len(shapes) == 2 and shapes[0][1] != shapes[1][1]:
+        raise ValueError("%s: lo has shape %s, hi %s" % (who, tuple(shapes[0][1]), tuple(shapes[1][1])))
+    return out
+
+
+def trajectory_fleet_separation(fleet, lo=None, hi=None):
+    """trajectory_separation for every pair of a fleet, in one launch: n scenes of m vehicles (2..256) that move in d = 1, 2 or 3 axes, all
+    vehicles of a scene on one clock.  fleet: a sequence of six tensors (pos0, pos1, pos2, vel1, duration0, duration1), or of eight with
+    (vel0, vel2) appended, each (n, m, d) -- always three-dimensional -- float64 on one ROCm device.  lo, hi: (n, k), the windows of a
+    scene for all its pairs, or (k,) for the same in every scene; None: -inf / +inf, both None: k = 1, the whole common domain of each
+    pair.  Returns (sep_sq, t_closest), (n, pairs, k) each, pairs = m (m - 1) / 2 in fleet_pairs(m)'s order: [s, (i, j), q] is bit for bit
+    what trajectory_separation gives for vehicles i and j of scene s, the window [lo, hi][s, q] and no delay -- its NaN rule (a vehicle
+    with a bad duration makes exactly its m - 1 pairs NaN), domain, candidates and earliest-among-equals.
+
+    One rp_trajectory_fleet_separation launch on the current stream; no pair-expanded tensor is made.  sep_sq is differentiable to first
+    order in all fleet tensors, lo and hi, in both modes: per axis one rp_trajectory_eval launch and one rp_trajectory_eval_vjp (reverse)
+    or rp_trajectory_eval_jvp (forward) launch on the n m splines at the returned times; every sum over pairs is a
+    gather and a sum, so a gradient is the same bits in every run; a double backward raises torch's once_differentiable error.  At ties
+    the derivative is that of the branch the forward pass found.  A NaN value has gradient 0 (forward mode: NaN).  The time is not
+    differentiable.  Does not synchronise the host."""
+    who = "trajectory_fleet_separation"
+    n, m, d, tables = _check_fleet(fleet, who)
+    lo, hi = _check_fleet_windows(n, fleet[0].device, lo, hi, who)
+    _check_fleet_devices(fleet, who)
+    return _TrajectoryFleetSeparation.apply(d, m, *[t for table in tables for t in table], lo, hi)
+
+
+def min_time_fleet_separation(pos, lo=None, hi=None, *, vel=None, synchronize=True, gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve of a fleet's axes, then trajectory_fleet_separation of the solutions.  pos: (pos0, pos1, pos2), (n, m, d) each: one
+    solve over the n m d axis problems.  vel: (vel0, vel2), (n, m, d) each (None: rest to rest).  synchronize (the default): each
+    vehicle's axes are stretched to its slowest first (synchronize_axes on (n m, d); rest to rest only: with end velocities given it
+    raises ValueError).  lo, hi as trajectory_fleet_separation's.  Returns (sep_sq, t_closest, solution) with the solution
+    min_time_solve's (vel1, duration0, duration1, iters, status) as (n, m, d), as the solve left them (before the stretch).  Plain
+    composition: sep_sq is differentiable to first order in the positions, the end velocities, lo and hi, in both modes."""
+    who = "min_time_fleet_separation"
+    if synchronize and vel is not None:
+        raise ValueError(who + ": synchronize=True needs rest-to-rest vehicles; pass synchronize=False with end velocities")
+    if not isinstance(pos, (list, tuple)) or len(pos) != 3:
+        raise TypeError("%s: pos must be a list or tuple of three tensors (pos0, pos1, pos2)" % who)
+    if vel is not None and (not isinstance(vel, (list, tuple)) or len(vel) != 2):
+        raise TypeError("%s: vel must be None or a pair (vel0, vel2)" % who)
+    for name, t in [("pos", t) for t in pos] + [("vel", v) for v in (vel or ()) if v is not None]:
+        _check_is_tensor(name, t, who)
+        if t.dim() != 3 or t.shape != pos[0].shape or not 1 <= t.shape[2] <= 3:
+            raise ValueError("%s: every tensor must have one shape (n, m, d) with d in 1..3, got %s" % (who, tuple(t.shape)))
+    n, m, d = pos[0].shape
+    _check_fleet_size(int(m), who)
+    lo, hi = _check_fleet_windows(n, pos[0].device, lo, hi, who)      # before the solve: a bad query costs none
+    flat = lambda t: t.reshape(-1) if t is not None else None      # noqa: E731
+    vel0, vel2 = (flat(v) for v in vel) if vel is not None else (None, None)
+    solution = min_time_solve(*[flat(t) for t in pos], gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
+    spline = list(pos) + [t.reshape(n, m, d) for t in solution[:3]]
+    if synchronize:
+        spline, _ = synchronize_axes([t.reshape(n * m, d) for t in spline])
+        spline = [t.reshape(n, m, d) for t in spline]
+    elif vel is not None:
+        spline = spline + list(vel)
+    return tuple(trajectory_fleet_separation(spline, lo, hi)) + (tuple(t.reshape(n, m, d) for t in solution),)
 
 
 # ---- when two vehicles moving in several axes first come within a distance ----

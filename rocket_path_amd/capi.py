@@ -120,6 +120,8 @@ SIGNATURES = {
                                                 ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
     "rp_trajectory_contact": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_vp),
                                              ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rp_trajectory_fleet_separation": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                      ctypes.POINTER(_vp), _vp, _vp, _vp, _vp]),
     "rp_trajectory_tracking": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
                                               _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_tracking_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
@@ -328,6 +330,21 @@ def trajectory_contact(device, stream, n, k, d, spline_a, spline_b, d_level_sq, 
         raise ValueError("trajectory_contact: d must be 1, 2 or 3, got %d" % d)
     check(load_library().rp_trajectory_contact(int(device), vp(stream), int(n), int(k), d, axes_table(spline_a, d), axes_table(spline_b, d),
                                                vp(d_level_sq), vp(d_lo), vp(d_hi), vp(d_delay), vp(d_time), vp(d_rate)))
+
+
+def trajectory_fleet_separation(device, stream, n, m, k, d, fleet, d_lo=None, d_hi=None, d_value=None, d_time=None):
+    """rp_trajectory_fleet_separation: trajectory_separation's two outputs, bit for bit with no delay, for every pair (i, j), i < j
+    (lexicographic), of `n` scenes of `m` vehicles (2..256) of `d` axes (1..3) on one clock.  `fleet`: 8 d addresses, axis-major, each axis
+    as for trajectory_eval, every array n m values with vehicle v of scene s at s m + v.  d_lo, d_hi: (n, k), the scene's windows for all
+    its pairs (None / 0: -inf, +inf).  d_value, d_time: (n, m (m - 1) / 2, k) (None / 0: not wanted; not both)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = int(d), int(m)
+    if not 1 <= d <= 3:
+        raise ValueError("trajectory_fleet_separation: d must be 1, 2 or 3, got %d" % d)
+    if not 2 <= m <= 256:
+        raise ValueError("trajectory_fleet_separation: m must be 2..256 vehicles per scene, got %d" % m)
+    check(load_library().rp_trajectory_fleet_separation(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_lo), vp(d_hi),
+                                                        vp(d_value), vp(d_time)))
 
 
 def tracking_table(addresses):

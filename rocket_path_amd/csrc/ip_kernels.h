@@ -212,5 +212,10 @@ hipError_t launch_separation(size_t n, size_t k, int d, const double *const *d_s
 // of change there (null: not wanted)
 hipError_t launch_contact(size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_level_sq,
                           const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_rate, hipStream_t stream);
+// that least squared distance and its time for every pair (i, j), i < j, of n scenes of m vehicles (2..256) on one clock: d_fleet holds 8 d
+// pointers, axis-major, to arrays of n m values (vehicle v of scene s at s m + v); d_lo, d_hi n x k (null: -inf, +inf); the outputs
+// n x m (m - 1) / 2 x k, pairs in lexicographic order (either null: not wanted)
+hipError_t launch_fleet_separation(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo, const double *d_hi,
+                                   double *d_value, double *d_time, hipStream_t stream);
 
 }  // namespace rp

@@ -1502,6 +1502,26 @@ int rp_trajectory_separation(int device, void *stream, size_t n, size_t k, int d
     return RP_OK;
 }
 
+// that least squared distance for every pair of n scenes of m vehicles: one table of 8 d pointers to n m values each; the windows are n x k
+// and read as single values, the outputs n x pairs x k and written as 16-byte vectors
+int rp_trajectory_fleet_separation(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo,
+                                   const double *d_hi, double *d_value, double *d_time)
+{
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
+    if (m < 2 || m > 256) return fail(RP_ERR_INVALID, "%s: m must be 2..256 vehicles per scene, got %zu", __func__, m);
+    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
+    if (!d_fleet) return fail(RP_ERR_INVALID, "%s: d_fleet is null", __func__);
+    int st = RP_OK;
+    for (int x = 0; x < d && st == RP_OK; ++x) st = check_spline(__func__, "d_fleet", d_fleet + 8 * x);
+    const size_t pairs = m * (m - 1) / 2;
+    if (st == RP_OK && n > SIZE_MAX / sizeof(double) / pairs) st = fail(RP_ERR_INVALID, "%s: n x pairs does not fit", __func__);
+    if (st == RP_OK) st = check_queries(__func__, n == 0 ? 0 : n * pairs, k, nullptr, nullptr, {d_value, d_time}, d_value || d_time);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_fleet_separation(n, m, k, d, d_fleet, d_lo, d_hi, d_value, d_time, (hipStream_t)stream));
+    return RP_OK;
+}
+
 // the first time that squared distance reaches a level: rp_trajectory_separation's tables and argument rules, a level and a time that are required
 int rp_trajectory_contact(int device, void *stream, size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b,
                           const double *d_level_sq, const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_rate)

@@ -14,6 +14,7 @@
 //   the first time two splines meet            k_meeting                                        section 22
 //   the closest approach of two vehicles       k_separation                                     section 24
 //   the first time they come within a distance k_contact                                        section 25
+//   the closest approach of a fleet's pairs    k_fleet                                          section 26
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
 // rp_batch_integrals_device and rp_batch_sample*; the launchers are at the end of the file.
@@ -46,6 +47,7 @@
 
 #include "../../include/rp_batch.h"
 #include "batch_dispatch.h"
+#include "fleet_index.h"
 #include "ip_core.h"
 #include "spline_core.h"
 
@@ -2521,6 +2523,66 @@ k_separation(SepSplines<D> in, size_t n, size_t k, int P, const double *__restri
     });
 }
 
+// ---- the closest approach of every pair of a fleet (rp_trajectory_fleet_separation) ----
+// n scenes of m vehicles on one clock, vehicle v of scene s at s m + v of every array.  The launch's problems are the n m (m - 1) / 2 (scene,
+// pair) combinations in output order: the staging thread of problem p decodes (s, i, j) (fleet_index.h) and stages vehicle i as k_separation
+// stages A and vehicle j as it stages B -- L2 takes the m - 1 reads of a vehicle; no pair-expanded array exists.  A query finds its scene's
+// window, lo and hi n x k, with plain 8-byte loads at s k + its column.  The scene of a problem is not kept in LDS: 4 x 40 KiB of SepLds<2>
+// are all of a CU's 160 KiB, and any array next to it costs D = 2 its fourth block (the compiler then also answers the four-wave hint with
+// 133 VGPRs).  Instead one 64-bit division per trip gives the trip's first (scene, pair), and place q's are a 32-bit division on from there.
+// Every query is separation_query with a delay of 0.0: k_separation's bits for the gathered pair with a null delay.  Without the hint the
+// allocator takes 127 / 133 / 142 VGPRs.
+template <int D> struct FleetSplines { FromArrays v[D]; };
+
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
+k_fleet(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
+        double *__restrict__ value, double *__restrict__ time)
+{
+    __shared__ SepLds<D> L;
+    const unsigned pairs = fleet_pair_count(m);
+    auto stage_problem = [&](int q, size_t p) {
+        const size_t p_first = p - (size_t)q, s_first = p_first / pairs;
+        const unsigned r = (unsigned)(p_first - s_first * pairs) + (unsigned)q;      // < pairs + kTrajProblems
+        const size_t s = s_first + r / pairs;
+        unsigned i, j;
+        fleet_pair(r % pairs, m, i, j);
+        const size_t first = s * m + i, second = s * m + j;
+#pragma unroll
+        for (int x = 0; x < D; ++x) {
+            Knots ka = in.v[x].load(first), kb = in.v[x].load(second);
+            ka.check();
+            kb.check();
+            stage_eval(L.a[x], q, ka);
+            stage_eval(L.b[x], q, kb);
+            L.Ta[x][q] = ka.t0 + ka.t1;
+            L.Tb[x][q] = kb.t0 + kb.t1;
+        }
+    };
+    for_each_trip(problems, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k, s_first = p_first / pairs;
+        const unsigned r_first = (unsigned)(p_first - s_first * pairs);
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            const double inf = __builtin_inf();
+            const size_t sa = s_first + (r_first + (unsigned)qa) / pairs, sb = s_first + (r_first + (unsigned)qb) / pairs;
+            const size_t wa = sa * k + (e - (size_t)qa * k);                            // the scene's row, the query's column
+            const size_t wb = two ? sb * k + (e + 1 - (size_t)qb * k) : wa;
+            const double la = lo ? lo[wa] : -inf, lb = lo ? lo[wb] : -inf, ha = hi ? hi[wa] : inf, hb = hi ? hi[wb] : inf;
+            double va = 0.0, vb = 0.0, ta = 0.0, tb = 0.0;
+#pragma nounroll
+            for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_separation: each query's searches have their own trip counts
+                double v, t;
+                int trips = 0;
+                separation_query(L, half ? qb : qa, half ? lb : la, half ? hb : ha, 0.0, v, t, trips);
+                va = half ? va : v; ta = half ? ta : t;
+                vb = half ? v : vb; tb = half ? t : tb;
+            }
+            if (value) store_pair(value, e_first + e, va, vb, two);
+            if (time) store_pair(time, e_first + e, ta, tb, two);
+        });
+    });
+}
+
 // ---- when two vehicles moving in D axes first come within a distance (rp_trajectory_contact) ----
 // The inverse of section 24's squared distance f, as the meeting is the gap's.  The splines, the NaN rule, the domain, the clamped window
 // [a, b], the knots, the unsorted walk of 2 D + 1 pieces and each piece's quintic g = f' / 2 with its sign-changing roots r0[0..4] are
@@ -3046,6 +3108,30 @@ hipError_t launch_separation(size_t n, size_t k, int d, const double *const *d_s
     case 1: return launch_separation_axes<1>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
     case 2: return launch_separation_axes<2>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
     case 3: return launch_separation_axes<3>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <int D>
+hipError_t launch_fleet_axes(size_t n, unsigned m, size_t k, const double *const *d_fleet, const double *d_lo, const double *d_hi, double *d_value,
+                             double *d_time, hipStream_t stream)
+{
+    FleetSplines<D> in;
+    for (int x = 0; x < D; ++x) in.v[x] = FromArrays{table_of<8>(d_fleet + 8 * x)};
+    const size_t problems = n * fleet_pair_count(m);
+    return launch_stateless<false>(problems, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_fleet<D>, grid, block, 0, stream, in, problems, m, k, P, d_lo, d_hi, d_value, d_time);
+    });
+}
+
+hipError_t launch_fleet_separation(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo, const double *d_hi,
+                                   double *d_value, double *d_time, hipStream_t stream)
+{
+    if (m < 2 || m > kFleetMost) return hipErrorInvalidValue;
+    switch (d) {
+    case 1: return launch_fleet_axes<1>(n, (unsigned)m, k, d_fleet, d_lo, d_hi, d_value, d_time, stream);
+    case 2: return launch_fleet_axes<2>(n, (unsigned)m, k, d_fleet, d_lo, d_hi, d_value, d_time, stream);
+    case 3: return launch_fleet_axes<3>(n, (unsigned)m, k, d_fleet, d_lo, d_hi, d_value, d_time, stream);
     }
     return hipErrorInvalidValue;
 }
