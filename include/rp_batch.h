@@ -78,7 +78,8 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      derivative of the tracking integrals along a direction; a new entry only, the revision stays); rp_trajectory_separation (the
  *      closest approach of two vehicles moving in up to three axes; a new entry only, the revision stays); rp_trajectory_contact (the
  *      first time those two come within a distance; a new entry only, the revision stays); rp_trajectory_fleet_separation (that closest
- *      approach for every pair of a fleet in one launch; a new entry only, the revision stays) */
+ *      approach for every pair of a fleet in one launch; a new entry only, the revision stays); rp_trajectory_fleet_contact (that first time
+ *      within a distance for every pair of a fleet in one launch; a new entry only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -760,6 +761,27 @@ RP_API int rp_trajectory_contact(int device, void *stream, size_t n, size_t k, i
  * bits depend on its two vehicles' 16 d numbers and its scene's window ends only. */
 RP_API int rp_trajectory_fleet_separation(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
                                           const double *d_lo, const double *d_hi, double *d_value, double *d_time);
+
+/* ---- the first contact of every pair of a fleet, in one launch (new: the reference draws one curve) ----
+ * rp_trajectory_contact for every pair of rp_trajectory_fleet_separation's fleet: n, m, d, d_fleet, the order of the pairs, d_lo and d_hi
+ * (n x k per scene, single values, no alignment rule, NULL: -inf, +inf) are that entry's, word for word.  d_level_sq, required, in units of
+ * SQUARED distance like rp_trajectory_contact's, in one of two layouts: level_per_pair == 0: n x k doubles, one level for all pairs of
+ * scene s at query q, read as single values where the window ends are, no alignment rule; level_per_pair == 1: n x pairs x k doubles in the
+ * outputs' layout, read as 16-byte vectors and 16-byte aligned -- what vehicles of different sizes need, (r_i + r_j)^2 formed by the caller.
+ * d_time, n x pairs x k, required; d_rate, the same shape, may be NULL.  Output [s, (i, j), q] is what rp_trajectory_contact returns, bit for
+ * bit in time and rate, for A = vehicle i of scene s, B = vehicle j of scene s, the window [lo, hi][s, q], that query's level and
+ * d_delay == NULL: that entry's NaN rule (over the pair's 2 d splines: a vehicle under it makes exactly its m - 1 pairs NaN), a NaN or
+ * infinite level making its own query NaN and a negative one never reached, the sub-pieces, the early exit, the zero-length skip and the
+ * rate.  No pair-expanded array of splines is read or written.
+ * Derivatives need no entry of their own (section 27): rp_trajectory_contact's implicit-function formula routed per vehicle, one
+ * rp_trajectory_eval and one rp_trajectory_eval_vjp or _jvp launch per axis on the n m splines.  There is no batch entry.  Entries [3] and
+ * [4] of any axis may be NULL (zeros); m outside 2..256, d outside 1..3, a NULL table, level or time, a level_per_pair other than 0 or 1,
+ * a misaligned output, a misaligned per-pair level, n or k of 0, k >= 2^31, an n x pairs x k that does not fit give RP_ERR_INVALID
+ * before any device call.  Asynchronous on `stream`; never throws.  Pointwise: a query's bits depend on its two vehicles' 16 d numbers,
+ * its level and its scene's window ends only. */
+RP_API int rp_trajectory_fleet_contact(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                                       const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
+                                       double *d_rate);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

@@ -54,6 +54,10 @@ trajectory_fleet_separation (section 26) is trajectory_separation for every pair
 rp_trajectory_fleet_separation launch, bit for bit the pair call's; its derivatives are that call's routed per vehicle through a slot table
 (fleet_slots), one evaluator launch and one derivative launch per axis on the n m splines, every sum a gather and a sum; fleet_pairs gives
 the order of the pairs; min_time_fleet_separation composes it with one min_time_solve call over all axis problems.
+trajectory_fleet_contact (section 27) is trajectory_contact for every pair of such a fleet in one rp_trajectory_fleet_contact launch, bit for
+bit the pair call's, the level per scene or per pair; its derivatives are that call's implicit-function formula routed per vehicle through
+the same slot table; min_time_fleet_contact composes it with the solves, and fleet_first_contact reduces the times to each scene's first
+contact and the pair that makes it, in plain torch.
 """
 import ctypes
 import functools
@@ -1946,6 +1950,226 @@ def min_time_contact(pos_a, pos_b, radius=None, lo=None, hi=None, delay=None, *,
                                                        ("delay", delay)), who)
     splines, solutions = _solve_axis_vehicles(pos_a, pos_b, flat, synchronize, gap_tol, max_iter, params)
     return trajectory_contact(splines[0], splines[1], None, lo, hi, delay, level_sq=level), solutions[0], solutions[1]
+
+
+# ---- the first contact of every pair of a fleet ----
+class _TrajectoryFleetContact(torch.autograd.Function):
+    """(time, rate), (n, pairs, k) each, of the first time in the scene's window at which a pair's squared distance is at the level.  Inputs:
+    d, m, the fleet's 8 d tensors as _TrajectoryFleetSeparation takes them, level_sq -- (n, k): one level for all pairs of a scene, or
+    (n, pairs, k): one per pair --, lo, hi (n, k).  The time is differentiable to first order in all 8 d fleet inputs and the level by
+    _TrajectoryContact's implicit-function formula, d time = (d level - sum of 2 D_c (d pos_first,c - d pos_second,c)) / rate, routed per
+    vehicle as _TrajectoryFleetSeparation routes: the times gathered through the slot table to (n m, (m - 1) k), per axis one evaluator
+    launch and one launch of its derivative on the n m splines.  lo and hi only choose the branch.  rate is for the
+    backward and is not differentiable."""
+
+    @staticmethod
+    def forward(d, m, *inputs):
+        fleet = [_dense(t) for t in inputs[:8 * d]]
+        level, lo, hi = (_dense(t) for t in inputs[8 * d:])
+        per_pair = level.dim() == 3
+        if per_pair and _plain(level).data_ptr() % 16:      # a view that starts in the middle of a 16-byte vector
+            level = level.clone()
+        n, k = level.shape[0], level.shape[-1]
+        device = inputs[0].device
+        time, rate = (torch.empty((n, m * (m - 1) // 2, k), dtype=torch.float64, device=device) for _ in range(2))
+        with torch.cuda.device(device):      # as _trajectory_launch
+            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_fleet_contact(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in fleet],
+                                          addr(level), int(per_pair), addr(lo), addr(hi), addr(time), addr(rate))
+        return time, rate
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(output[1])
+        d, ctx.m = inputs[0], inputs[1]
+        ctx.d = d
+        ctx.per_pair = inputs[2 + 8 * d].dim() == 3
+        ctx.given = [t is not None for t in inputs[2:2 + 8 * d]]      # neither derivative reads the level, lo or hi
+        kept = [t for t in inputs[2:2 + 8 * d] if t is not None] + list(output)
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _saved(ctx):
+        """(the d lists of eight tensors; the slot tables; the times through the slot table, 0 where there is no contact,
+        (n m, (m - 1) k); rate; where there is no contact, (n, pairs, k); the d gaps D_c there; a pair's view of a per-slot array)"""
+        d, m = ctx.d, ctx.m
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        time, rate = list(kept)
+        fleet = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
+        n, pairs, k = time.shape
+        slots = _fleet_slots_on(m, time.device)
+        pair, _, at_first, at_second, _, _ = slots
+        missing = torch.isnan(time)
+        t = torch.where(missing, torch.zeros_like(time), time)
+        tau = t[:, pair.reshape(-1), :].reshape(n * m, (m - 1) * k).contiguous()
+
+        def per_pair(x):      # (n m, (m - 1) k) -> the pair's entry in its first vehicle's row and in its second's, (n, pairs, k) each
+            x = x.reshape(n, m * (m - 1), k)
+            return x[:, at_first, :], x[:, at_second, :]
+
+        gaps = []
+        for s in fleet:
+            pos = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
+            _trajectory_launch(capi.trajectory_eval, tau.device, s, tau, pos, None, None)
+            pos_first, pos_second = per_pair(pos)
+            gaps.append(pos_first - pos_second)
+        return fleet, slots, tau, rate, missing, gaps, per_pair
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_time, _g_rate):
+        d, m = ctx.d, ctx.m
+        if g_time is None:
+            return (None,) * (8 * d + 5)
+        fleet, (pair, sign, _, _, _, _), tau, rate, missing, gaps, _ = _TrajectoryFleetContact._saved(ctx)
+        n, pairs, k = missing.shape
+        need = ctx.needs_input_grad[2:]
+        zero = torch.zeros_like(rate)
+        w = torch.where(missing, zero, g_time / rate)      # an unreached level: gradient 0
+        through = lambda x: x[:, pair.reshape(-1), :].reshape(n, m, m - 1, k)      # noqa: E731  (n, pairs, k) -> per vehicle and slot
+        signs = sign.reshape(1, m, m - 1, 1)
+        bars = [None] * (8 * d)
+        for c in range(d):
+            bar = [torch.empty(n * m, dtype=torch.float64, device=tau.device) if need[8 * c + f] else None for f in range(8)]
+            if any(x is not None for x in bar):
+                g_pos = torch.where(missing, zero, -((2.0 * w) * gaps[c]))      # (a bad vehicle's gap is NaN: not into its partners)
+                upstream = (signs * through(g_pos)).reshape(tau.shape).contiguous()
+                _trajectory_launch(capi.trajectory_eval_vjp, tau.device, fleet[c], tau, upstream, None, None, bar, None)
+            bars[8 * c:8 * c + 8] = bar
+        level_bar = None
+        if need[8 * d]:
+            level_bar = w if ctx.per_pair else w.sum(dim=1)
+        return (None, None) + tuple(bars) + (level_bar, None, None)
+
+    @staticmethod
+    def jvp(ctx, _t_d, _t_m, *tangents):
+        d = ctx.d
+        fleet, _, tau, rate, missing, gaps, per_pair = _TrajectoryFleetContact._saved(ctx)
+        dots = [_dense(t) for t in tangents[:8 * d]]
+        level_dot = tangents[8 * d]
+        if level_dot is None:
+            total = torch.zeros_like(rate)
+        else:
+            total = level_dot if ctx.per_pair else level_dot.unsqueeze(1)
+        for c in range(d):
+            pos_dot = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
+            _trajectory_launch(capi.trajectory_eval_jvp, tau.device, fleet[c], tau, dots[8 * c:8 * c + 8], None, pos_dot, None, None)
+            dot_first, dot_second = per_pair(pos_dot)
+            total = total - (2.0 * gaps[c]) * (dot_first - dot_second)
+        return torch.where(missing, torch.full_like(rate, float("nan")), total / rate), None
+
+
+def _check_fleet_level(n, pairs, radius, level_sq, who):
+    """The level of trajectory_fleet_contact, shape and type (the device comes after the windows' shapes): radius or level_sq, float64,
+    (n, k), (k,) -- one level for all pairs of a scene -- or (n, pairs, k) -- one per pair.  Returns (its name, the level in units of
+    squared distance as (n, k) or (n, pairs, k))."""
+    name, t = ("radius", radius) if radius is not None else ("level_sq", level_sq)
+    _check_is_tensor(name, t, who)
+    _check_is_float64(name, t, who)
+    if t.dim() == 1 and t.shape[0] > 0:
+        t = t.unsqueeze(0).expand(n, t.shape[0])
+    elif not ((t.dim() == 2 and t.shape[0] == n and t.shape[1] > 0) or (t.dim() == 3 and t.shape[:2] == (n, pairs) and t.shape[2] > 0)):
+        raise ValueError("%s: %s must have shape (%d, k) or (k,) -- a scene's level for all its pairs -- or (%d, %d, k) -- one per pair -- "
+                         "with k >= 1, got %s" % (who, name, n, n, pairs, tuple(t.shape)))
+    return name, (t * t if radius is not None else t)
+
+
+def _check_fleet_queries(n, m, device, radius, level_sq, lo, hi, who):
+    """The level and the windows of a fleet's contact query: shapes and types before devices.  Returns (level, lo, hi)."""
+    name, level = _check_fleet_level(n, m * (m - 1) // 2, radius, level_sq, who)
+    lo, hi = _check_fleet_windows(n, device, lo, hi, who)
+    for other, t in (("lo", lo), ("hi", hi)):
+        if t is not None and t.shape[1] != level.shape[-1]:
+            raise ValueError("%s: %s has %d queries per scene, %s %d" % (who, name, level.shape[-1], other, t.shape[1]))
+    if level.device != device:
+        raise TypeError("%s: %s is on %s; it must be on the fleet's device %s" % (who, name, level.device, device))
+    return level, lo, hi
+
+
+def trajectory_fleet_contact(fleet, radius=None, lo=None, hi=None, *, level_sq=None):
+    """trajectory_contact for every pair of a fleet, in one launch: the first time in a scene's windows [lo, hi] at which two of its
+    vehicles come within `radius` of each other.  fleet, lo, hi: exactly trajectory_fleet_separation's.  radius: (n, k), or (k,) for the
+    same in every scene -- one radius for all pairs of a scene --, or (n, pairs, k) -- one per pair, what vehicles of different sizes need:
+    r_i + r_j, formed by the caller.  The level is radius * radius, formed in torch, so the radius gets its gradient by the chain rule.
+    level_sq= may be given instead of radius (giving both, or neither, is a TypeError): the level itself, in units of squared distance, in
+    the same shapes.  Returns t_contact, (n, pairs, k), pairs = m (m - 1) / 2 in fleet_pairs(m)'s order: [s, (i, j), q] is bit for bit what
+    trajectory_contact gives for vehicles i and j of scene s, the window [lo, hi][s, q], that query's level and no delay -- NaN where the
+    pair does not reach the level in the window, and its NaN rule (a vehicle with a bad duration makes exactly its m - 1 pairs NaN).
+
+    One rp_trajectory_fleet_contact launch on the current stream; no pair-expanded tensor is made.  Differentiable to first order in all
+    fleet tensors and the level, in both modes, d time = (d level - sum of 2 D_c (d pos_i,c - d pos_j,c)) / rate: per axis one
+    rp_trajectory_eval launch and one rp_trajectory_eval_vjp (reverse) or rp_trajectory_eval_jvp (forward) launch on the n m splines at
+    the returned times; every sum over pairs is a gather and a sum, so a gradient is the same bits in every run; a
+    double backward raises torch's once_differentiable error.  lo and hi get no gradient.  An unreached level has gradient 0 (forward
+    mode: NaN, as the time); where rate is 0 (a touch) the result is inf or NaN.  fleet_first_contact gives the scene's first contact and
+    its pair.  Does not synchronise the host."""
+    who = "trajectory_fleet_contact"
+    if (radius is None) == (level_sq is None):
+        raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
+    n, m, d, tables = _check_fleet(fleet, who)
+    level, lo, hi = _check_fleet_queries(n, m, fleet[0].device, radius, level_sq, lo, hi, who)
+    _check_fleet_devices(fleet, who)
+    return _TrajectoryFleetContact.apply(d, m, *[t for table in tables for t in table], level, lo, hi)[0]
+
+
+def min_time_fleet_contact(pos, radius=None, lo=None, hi=None, *, level_sq=None, vel=None, synchronize=True, gap_tol=1e-8, max_iter=200,
+                           params=None):
+    """min_time_solve of a fleet's axes, then trajectory_fleet_contact of the solutions: min_time_fleet_separation's composition -- pos,
+    vel, synchronize and the solution returned are its -- with trajectory_fleet_contact's radius (or level_sq=), lo and hi.  Returns
+    (t_contact, solution).  Plain composition: the times are differentiable to first order in the positions, the end velocities and the
+    radius, in both modes."""
+    who = "min_time_fleet_contact"
+    if (radius is None) == (level_sq is None):
+        raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
+    if synchronize and vel is not None:
+        raise ValueError(who + ": synchronize=True needs rest-to-rest vehicles; pass synchronize=False with end velocities")
+    if not isinstance(pos, (list, tuple)) or len(pos) != 3:
+        raise TypeError("%s: pos must be a list or tuple of three tensors (pos0, pos1, pos2)" % who)
+    if vel is not None and (not isinstance(vel, (list, tuple)) or len(vel) != 2):
+        raise TypeError("%s: vel must be None or a pair (vel0, vel2)" % who)
+    for name, t in [("pos", t) for t in pos] + [("vel", v) for v in (vel or ()) if v is not None]:
+        _check_is_tensor(name, t, who)
+        if t.dim() != 3 or t.shape != pos[0].shape or not 1 <= t.shape[2] <= 3:
+            raise ValueError("%s: every tensor must have one shape (n, m, d) with d in 1..3, got %s" % (who, tuple(t.shape)))
+    n, m, d = pos[0].shape
+    _check_fleet_size(int(m), who)
+    level, lo, hi = _check_fleet_queries(n, int(m), pos[0].device, radius, level_sq, lo, hi, who)      # before the solve: a bad query costs none
+    flat = lambda t: t.reshape(-1) if t is not None else None      # noqa: E731
+    vel0, vel2 = (flat(v) for v in vel) if vel is not None else (None, None)
+    solution = min_time_solve(*[flat(t) for t in pos], gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
+    spline = list(pos) + [t.reshape(n, m, d) for t in solution[:3]]
+    if synchronize:
+        spline, _ = synchronize_axes([t.reshape(n * m, d) for t in spline])
+        spline = [t.reshape(n, m, d) for t in spline]
+    elif vel is not None:
+        spline = spline + list(vel)
+    return trajectory_fleet_contact(spline, None, lo, hi, level_sq=level), tuple(t.reshape(n, m, d) for t in solution)
+
+
+def fleet_first_contact(t_contact):
+    """The first contact of each scene: (t_first, pair), (n, k) each, of trajectory_fleet_contact's (n, pairs, k) times.  t_first is the
+    earliest finite time over the scene's pairs, NaN if no pair has one; pair is the int64 index into fleet_pairs(m) of the pair that
+    attains it -- the lowest at ties --, -1 where there is none.  Plain torch on any device: the winner is selected by a one-hot mask and
+    a sum over the pairs, so t_first is differentiable, its gradient goes to exactly the winning (pair, query) entry, and nothing adds
+    with atomics: the same bits in every run."""
+    who = "fleet_first_contact"
+    _check_is_tensor("t_contact", t_contact, who)
+    if t_contact.dim() != 3 or t_contact.shape[1] == 0 or not t_contact.is_floating_point():
+        raise ValueError("%s: t_contact must be a floating-point tensor of shape (n, pairs, k), got %s %s"
+                         % (who, t_contact.dtype, tuple(t_contact.shape)))
+    pairs = t_contact.shape[1]
+    index = torch.arange(pairs, device=t_contact.device).reshape(1, pairs, 1)
+    finite = torch.isfinite(t_contact.detach())
+    least = torch.where(finite, t_contact.detach(), torch.full_like(t_contact, float("inf"))).amin(dim=1, keepdim=True)
+    pair = torch.where(finite & (t_contact.detach() == least), index, torch.full_like(index, pairs)).amin(dim=1)      # the lowest at ties
+    any_finite = finite.any(dim=1)
+    pair = torch.where(any_finite, pair, torch.full_like(pair, -1))
+    one_hot = index == pair.unsqueeze(1)
+    t_first = torch.where(one_hot, t_contact, torch.zeros_like(t_contact)).sum(dim=1)
+    return torch.where(any_finite, t_first, torch.full_like(t_first, float("nan"))), pair
 
 
 # ---- how much: integrals over a window ----

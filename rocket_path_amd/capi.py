@@ -122,6 +122,8 @@ SIGNATURES = {
                                              ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_trajectory_fleet_separation": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
                                                       ctypes.POINTER(_vp), _vp, _vp, _vp, _vp]),
+    "rp_trajectory_fleet_contact": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                   ctypes.POINTER(_vp), _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "rp_trajectory_tracking": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
                                               _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_tracking_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
@@ -345,6 +347,22 @@ def trajectory_fleet_separation(device, stream, n, m, k, d, fleet, d_lo=None, d_
         raise ValueError("trajectory_fleet_separation: m must be 2..256 vehicles per scene, got %d" % m)
     check(load_library().rp_trajectory_fleet_separation(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_lo), vp(d_hi),
                                                         vp(d_value), vp(d_time)))
+
+
+def trajectory_fleet_contact(device, stream, n, m, k, d, fleet, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None, d_time=None, d_rate=None):
+    """rp_trajectory_fleet_contact: trajectory_contact's two outputs, bit for bit with no delay, for every pair (i, j), i < j
+    (lexicographic), of `n` scenes of `m` vehicles (2..256) of `d` axes (1..3) on one clock.  `fleet`, d_lo, d_hi as for
+    trajectory_fleet_separation.  d_level_sq (required), squared distance: (n, k), one level for all pairs of a scene
+    (level_per_pair 0), or (n, m (m - 1) / 2, k), 16-byte aligned (level_per_pair 1).  d_time (required), d_rate (None / 0: not wanted):
+    (n, m (m - 1) / 2, k)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = int(d), int(m)
+    if not 1 <= d <= 3:
+        raise ValueError("trajectory_fleet_contact: d must be 1, 2 or 3, got %d" % d)
+    if not 2 <= m <= 256:
+        raise ValueError("trajectory_fleet_contact: m must be 2..256 vehicles per scene, got %d" % m)
+    check(load_library().rp_trajectory_fleet_contact(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_level_sq),
+                                                     int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_time), vp(d_rate)))
 
 
 def tracking_table(addresses):

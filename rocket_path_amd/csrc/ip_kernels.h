@@ -217,5 +217,9 @@ hipError_t launch_contact(size_t n, size_t k, int d, const double *const *d_spli
 // n x m (m - 1) / 2 x k, pairs in lexicographic order (either null: not wanted)
 hipError_t launch_fleet_separation(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo, const double *d_hi,
                                    double *d_value, double *d_time, hipStream_t stream);
+// the first time a pair's squared distance reaches a level, for every pair of such a fleet: d_level_sq n x k (level_per_pair 0: one level for
+// all pairs of a scene) or n x m (m - 1) / 2 x k (1); d_time required, d_rate may be null; both n x m (m - 1) / 2 x k
+hipError_t launch_fleet_contact(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq, int level_per_pair,
+                                const double *d_lo, const double *d_hi, double *d_time, double *d_rate, hipStream_t stream);
 
 }  // namespace rp

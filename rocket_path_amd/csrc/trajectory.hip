@@ -15,6 +15,7 @@
 //   the closest approach of two vehicles       k_separation                                     section 24
 //   the first time they come within a distance k_contact                                        section 25
 //   the closest approach of a fleet's pairs    k_fleet                                          section 26
+//   the first contact of a fleet's pairs       k_encounter                                      section 27
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
 // rp_batch_integrals_device and rp_batch_sample*; the launchers are at the end of the file.
@@ -2750,6 +2751,66 @@ k_contact(SepSplines<D> in, size_t n, size_t k, int P, const double *__restrict_
     });
 }
 
+// ---- the first contact of every pair of a fleet (rp_trajectory_fleet_contact) ----
+// k_fleet's staging and scene arithmetic around contact_query: the launch's problems are the n m (m - 1) / 2 (scene, pair) combinations in
+// output order, the staging thread of problem p decodes (s, i, j) and stages vehicles i and j where they lie, and the scene of a problem is
+// not kept in LDS (one 64-bit division per trip, 32-bit divisions from there: section 26).  A query's window ends are 8-byte loads at
+// s k + its column.  The level, in units of squared distance, is either per scene (level_per_pair 0: n x k, read where the window
+// ends are) or per pair (1: n x pairs x k, in the outputs' layout, read with load_pair as k_contact reads its level).  Every query is
+// contact_query with a delay of 0.0: k_contact's bits for the gathered pair with a null delay.
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
+k_encounter(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const double *__restrict__ level, int level_per_pair,
+            const double *__restrict__ lo, const double *__restrict__ hi, double *__restrict__ time, double *__restrict__ rate)
+{
+    __shared__ SepLds<D> L;
+    const unsigned pairs = fleet_pair_count(m);
+    auto stage_problem = [&](int q, size_t p) {
+        const size_t p_first = p - (size_t)q, s_first = p_first / pairs;
+        const unsigned r = (unsigned)(p_first - s_first * pairs) + (unsigned)q;      // < pairs + kTrajProblems
+        const size_t s = s_first + r / pairs;
+        unsigned i, j;
+        fleet_pair(r % pairs, m, i, j);
+        const size_t first = s * m + i, second = s * m + j;
+#pragma unroll
+        for (int x = 0; x < D; ++x) {
+            Knots ka = in.v[x].load(first), kb = in.v[x].load(second);
+            ka.check();
+            kb.check();
+            stage_eval(L.a[x], q, ka);
+            stage_eval(L.b[x], q, kb);
+            L.Ta[x][q] = ka.t0 + ka.t1;
+            L.Tb[x][q] = kb.t0 + kb.t1;
+        }
+    };
+    for_each_trip(problems, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k, s_first = p_first / pairs;
+        const unsigned r_first = (unsigned)(p_first - s_first * pairs);
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            const double inf = __builtin_inf();
+            const size_t sa = s_first + (r_first + (unsigned)qa) / pairs, sb = s_first + (r_first + (unsigned)qb) / pairs;
+            const size_t wa = sa * k + (e - (size_t)qa * k);                            // the scene's row, the query's column
+            const size_t wb = two ? sb * k + (e + 1 - (size_t)qb * k) : wa;
+            const double la = lo ? lo[wa] : -inf, lb = lo ? lo[wb] : -inf, ha = hi ? hi[wa] : inf, hb = hi ? hi[wb] : inf;
+            double pa, pb, ta = 0.0, tb = 0.0, ra = 0.0, rb = 0.0;
+            // one load_pair for both layouts (the per-scene one is its single-value form, where the window ends are): with a branch around
+            // two forms D = 1 spills a register at the four-wave step (section 27)
+            load_pair(level, level_per_pair ? e_first + e : wa, two && level_per_pair, pa, pb);
+            if (!level_per_pair) pb = level[wb];
+#pragma nounroll
+            for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_contact: each query's searches have their own trip counts
+                double t, r;
+                int trips = 0;
+                contact_query<D>(L, half ? qb : qa, half ? pb : pa, half ? lb : la, half ? hb : ha, 0.0, t, r, trips);
+                ta = half ? ta : t; ra = half ? ra : r;
+                tb = half ? t : tb; rb = half ? r : rb;
+            }
+            store_pair(time, e_first + e, ta, tb, two);
+            if (rate) store_pair(rate, e_first + e, ra, rb, two);
+        });
+    });
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -3157,6 +3218,30 @@ hipError_t launch_contact(size_t n, size_t k, int d, const double *const *d_spli
     case 1: return launch_contact_axes<1>(n, k, d_spline_a, d_spline_b, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate, stream);
     case 2: return launch_contact_axes<2>(n, k, d_spline_a, d_spline_b, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate, stream);
     case 3: return launch_contact_axes<3>(n, k, d_spline_a, d_spline_b, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <int D>
+hipError_t launch_fleet_contact_axes(size_t n, unsigned m, size_t k, const double *const *d_fleet, const double *d_level_sq, int level_per_pair,
+                                     const double *d_lo, const double *d_hi, double *d_time, double *d_rate, hipStream_t stream)
+{
+    FleetSplines<D> in;
+    for (int x = 0; x < D; ++x) in.v[x] = FromArrays{table_of<8>(d_fleet + 8 * x)};
+    const size_t problems = n * fleet_pair_count(m);
+    return launch_stateless<false>(problems, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_encounter<D>, grid, block, 0, stream, in, problems, m, k, P, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate);
+    });
+}
+
+hipError_t launch_fleet_contact(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq, int level_per_pair,
+                                const double *d_lo, const double *d_hi, double *d_time, double *d_rate, hipStream_t stream)
+{
+    if (m < 2 || m > kFleetMost || !d_level_sq || !d_time) return hipErrorInvalidValue;
+    switch (d) {
+    case 1: return launch_fleet_contact_axes<1>(n, (unsigned)m, k, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, stream);
+    case 2: return launch_fleet_contact_axes<2>(n, (unsigned)m, k, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, stream);
+    case 3: return launch_fleet_contact_axes<3>(n, (unsigned)m, k, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, stream);
     }
     return hipErrorInvalidValue;
 }
