@@ -79,7 +79,9 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      closest approach of two vehicles moving in up to three axes; a new entry only, the revision stays); rp_trajectory_contact (the
  *      first time those two come within a distance; a new entry only, the revision stays); rp_trajectory_fleet_separation (that closest
  *      approach for every pair of a fleet in one launch; a new entry only, the revision stays); rp_trajectory_fleet_contact (that first time
- *      within a distance for every pair of a fleet in one launch; a new entry only, the revision stays) */
+ *      within a distance for every pair of a fleet in one launch; a new entry only, the revision stays);
+ *      rp_trajectory_fleet_separation_staggered and rp_trajectory_fleet_contact_staggered (those two with a start time per vehicle; new
+ *      entries only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -782,6 +784,26 @@ RP_API int rp_trajectory_fleet_separation(int device, void *stream, size_t n, si
 RP_API int rp_trajectory_fleet_contact(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
                                        const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
                                        double *d_rate);
+
+/* ---- the two fleet queries with a start time per vehicle (new entries only, the revision stays) ----
+ * d_start, required: n x m doubles, vehicle v of scene s at s m + v, read as single values, no alignment rule.  Vehicle v runs its spline
+ * over [start, start + T] of the scene's clock; d_lo, d_hi (n x k, NULL: -inf, +inf) and d_time are on the scene's clock.  For pair (i, j),
+ * i < j, with s_i and s_j the two starts: delay = s_j - s_i, lo' = lo - s_i, hi' = hi - s_i, one fp64 subtraction each (a NULL end is the
+ * infinity before the subtraction).  Output [s, (i, j), q] is what rp_trajectory_separation (rp_trajectory_contact, at the same level)
+ * returns, bit for bit in value, time and rate, for A = vehicle i, B = vehicle j, the window [lo', hi'] and that delay: d_time_local is
+ * that entry's time t', on vehicle i's clock, and d_time is t' + s_i, one fp64 addition (NaN stays NaN).  So the pair entry's NaN rule (a
+ * NaN or infinite start makes exactly that vehicle's m - 1 pairs NaN), common domain (pairs never under way together are NaN), candidates,
+ * delayed start and earliest-among-equals hold.  Every other argument, the order of the pairs and every refusal are
+ * rp_trajectory_fleet_separation's and rp_trajectory_fleet_contact's, except that any output may be NULL (d_value, d_time, d_time_local;
+ * d_time, d_time_local, d_rate) but not all; a NULL d_start gives RP_ERR_INVALID, before any device call like the rest.  No pair-expanded
+ * array is read or written: a query decodes its pair again and loads the two starts where they lie.  Asynchronous on `stream`; never
+ * throws.  Pointwise: a query's bits depend on its two vehicles' 16 d numbers and starts, its level and its scene's window ends only. */
+RP_API int rp_trajectory_fleet_separation_staggered(int device, void *stream, size_t n, size_t m, size_t k, int d,
+                                                    const double *const *d_fleet, const double *d_start, const double *d_lo,
+                                                    const double *d_hi, double *d_value, double *d_time, double *d_time_local);
+RP_API int rp_trajectory_fleet_contact_staggered(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                                                 const double *d_start, const double *d_level_sq, int level_per_pair, const double *d_lo,
+                                                 const double *d_hi, double *d_time, double *d_time_local, double *d_rate);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

@@ -58,6 +58,9 @@ trajectory_fleet_contact (section 27) is trajectory_contact for every pair of su
 bit the pair call's, the level per scene or per pair; its derivatives are that call's implicit-function formula routed per vehicle through
 the same slot table; min_time_fleet_contact composes it with the solves, and fleet_first_contact reduces the times to each scene's first
 contact and the pair that makes it, in plain torch.
+start= on those four (section 28) gives every vehicle a start time of its own on the scene's clock: pair (i, j) is the pair call with the
+delay start_j - start_i over the window shifted by start_i, bit for bit, in one rp_trajectory_fleet_separation_staggered or
+rp_trajectory_fleet_contact_staggered launch, differentiable in start through the same slot table; start=None is the call without it.
 """
 import ctypes
 import functools
@@ -1677,6 +1680,196 @@ class _TrajectoryFleetSeparation(torch.autograd.Function):
         return torch.where(missing, torch.full_like(zero, float("nan")), value_dot), None
 
 
+def _staggered_times(m, start, time_local, missing):
+    """What both staggered fleet functions evaluate at: (the slot tables; the pair's delay start_j - start_i,
+    (n, pairs, 1), the kernel's bits; the pair's local time t', 0 where missing, (n, pairs, k); the times through the slot table,
+    (n m, (m - 1) k): t' in the row of the pair's first vehicle and t' - delay, the pair entry's t_b, in the row of its second; a pair's
+    view of a per-slot array; (n, pairs, k) -> per vehicle and slot, (n, m, m - 1, k))"""
+    n, pairs, k = time_local.shape
+    slots = _fleet_slots_on(m, time_local.device)
+    pair, sign, at_first, at_second, first, second = slots
+    delay = (start[:, second] - start[:, first]).unsqueeze(2)
+    zero = torch.zeros_like(time_local)
+    t_first = torch.where(missing, zero, time_local)
+    t_second = torch.where(missing, zero, t_first - delay)
+    through = lambda x: x[:, pair.reshape(-1), :].reshape(n, m, m - 1, k)      # noqa: E731
+    signs = sign.reshape(1, m, m - 1, 1)
+    tau = torch.where(signs > 0, through(t_first), through(t_second)).reshape(n * m, (m - 1) * k).contiguous()
+
+    def per_pair(x):      # (n m, (m - 1) k) -> the pair's entry in its first vehicle's row and in its second's, (n, pairs, k) each
+        x = x.reshape(n, m * (m - 1), k)
+        return x[:, at_first, :], x[:, at_second, :]
+
+    return slots, delay, t_first, tau, per_pair, through
+
+
+def _fleet_gaps(fleet, tau, per_pair):
+    gaps = []
+    for s in fleet:
+        pos = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
+        _trajectory_launch(capi.trajectory_eval, tau.device, s, tau, pos, None, None)
+        pos_first, pos_second = per_pair(pos)
+        gaps.append(pos_first - pos_second)
+    return gaps
+
+
+class _TrajectoryStaggeredSeparation(torch.autograd.Function):
+    """_TrajectoryFleetSeparation with a start time per vehicle: (sep_sq, t_closest on the scene's clock, t_closest on the clock of the pair's
+    first vehicle), (n, pairs, k) each.  Inputs: d, m, the fleet's 8 d tensors, start (n, m), lo, hi (n, k).  Pair (i, j) is
+    _TrajectorySeparation's query with delay = start_j - start_i over [lo - start_i, hi - start_i], and so are its derivatives: vehicle i
+    is evaluated at the local time t', vehicle j at t' - delay, the classes are tested on t' in that function's priority -- LO, HI, the
+    END of an axis of the first vehicle, of the second (delay + T), the delayed START --, delay_bar = routed(END of the second | START) -
+    the sum of the second vehicle's tau_bar, and start_j gets delay_bar, start_i minus (delay_bar + the pair's lo_bar + hi_bar): every sum
+    over pairs a gather through the slot table and a sum.  The times are not differentiable."""
+
+    @staticmethod
+    def forward(d, m, *inputs):
+        fleet = [_dense(t) for t in inputs[:8 * d]]
+        start, lo, hi = (_dense(t) for t in inputs[8 * d:])
+        given = lo if lo is not None else hi
+        n = start.shape[0]
+        k = given.shape[1] if given is not None else 1
+        device = inputs[0].device
+        value, time, local = (torch.empty((n, m * (m - 1) // 2, k), dtype=torch.float64, device=device) for _ in range(3))
+        with torch.cuda.device(device):      # as _trajectory_launch
+            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_fleet_separation_staggered(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d,
+                                                       [addr(t) for t in fleet], addr(start), addr(lo), addr(hi), addr(value), addr(time),
+                                                       addr(local))
+        return value, time, local
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(output[1], output[2])
+        ctx.d, ctx.m = inputs[0], inputs[1]
+        ctx.given = [t is not None for t in inputs[2:]]
+        kept = [t for t in inputs[2:] if t is not None] + [output[0], output[2]]
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _saved(ctx):
+        d, m = ctx.d, ctx.m
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        value, local = list(kept)
+        fleet = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
+        start, lo, hi = inputs[8 * d:]
+        n = start.shape[0]
+        missing = torch.isnan(value) | torch.isnan(local)
+        slots, delay, t, tau, per_pair, through = _staggered_times(m, start, local, missing)
+        first, second = slots[4], slots[5]
+        s_first = start[:, first].unsqueeze(2)
+        ends = [(s[6] + s[7]).reshape(n, m) for s in fleet]
+        tests = [lo.unsqueeze(1) - s_first if lo is not None else None, hi.unsqueeze(1) - s_first if hi is not None else None]
+        tests += [e[:, first].unsqueeze(2) for e in ends] + [delay + e[:, second].unsqueeze(2) for e in ends] + [delay]
+        masks, taken = [], missing
+        for at, ref in enumerate(tests):
+            mask = (t == ref) & ~taken if ref is not None else torch.zeros_like(missing)
+            if at == len(tests) - 1:
+                mask = mask & (delay > 0)      # a start clamped to +0.0 is a constant
+            masks.append(mask)
+            taken = taken | mask
+        gaps = _fleet_gaps(fleet, tau, per_pair)
+        return fleet, slots, tau, missing, gaps, per_pair, through, (masks[0], masks[1], masks[2:2 + d], masks[2 + d:2 + 2 * d], masks[-1])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_value, _g_time, _g_local):
+        d, m = ctx.d, ctx.m
+        if g_value is None:
+            return (None,) * (8 * d + 5)
+        fleet, slots, tau, missing, gaps, per_pair, through, (is_lo, is_hi, end_first, end_second, is_start) = _TrajectoryStaggeredSeparation._saved(ctx)
+        sign = slots[1]
+        n, pairs, k = missing.shape
+        g = torch.where(missing, torch.zeros_like(g_value), g_value)      # a NaN value: gradient 0
+        need = ctx.needs_input_grad[2:]
+        want_time = any(need[8 * c + 6] or need[8 * c + 7] for c in range(d)) or any(need[8 * d:])
+        signs = sign.reshape(1, m, m - 1, 1)
+        bars, time_bar, shift_bar = [None] * (8 * d), None, None
+        for c in range(d):
+            g_pos = torch.where(missing, torch.zeros_like(g), (2.0 * g) * gaps[c])      # (a bad vehicle's gap is NaN: not into its partners)
+            upstream = (signs * through(g_pos)).reshape(tau.shape).contiguous()
+            bar = [torch.empty(n * m, dtype=torch.float64, device=tau.device) if need[8 * c + f] else None for f in range(8)]
+            tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if want_time else None
+            if want_time or any(x is not None for x in bar):
+                _trajectory_launch(capi.trajectory_eval_vjp, tau.device, fleet[c], tau, upstream, None, None, bar, tau_bar)
+            bars[8 * c:8 * c + 8] = bar
+            if want_time:      # the pair's: its two vehicles', added in _TrajectorySeparation's order -- the same bits per pair and query
+                share_first, share_second = per_pair(tau_bar)
+                time_bar = share_first if time_bar is None else time_bar + share_first
+                time_bar = time_bar + share_second
+                shift_bar = share_second if shift_bar is None else shift_bar + share_second
+        start_bar = lo_bar = hi_bar = None
+        if want_time:
+            zero = torch.zeros_like(time_bar)
+            routed = lambda mask: torch.where(mask, time_bar, zero)      # noqa: E731
+            for c in range(d):
+                if need[8 * c + 6] or need[8 * c + 7]:      # a vehicle's pairs: through the slot table, then a plain sum
+                    mine = torch.where(signs > 0, through(routed(end_first[c])), through(routed(end_second[c]))).sum(dim=(2, 3)).reshape(n * m)
+                    for f in (6, 7):
+                        if need[8 * c + f]:
+                            bars[8 * c + f] = bars[8 * c + f] + mine
+            lo_pair, hi_pair = routed(is_lo), routed(is_hi)
+            if need[8 * d + 1]:
+                lo_bar = lo_pair.sum(dim=1)
+            if need[8 * d + 2]:
+                hi_bar = hi_pair.sum(dim=1)
+            if need[8 * d]:      # the second vehicle is at t' - delay, and the times that hold the delay move with it
+                holds = is_start
+                for mask in end_second:
+                    holds = holds | mask
+                delay_bar = routed(holds) - shift_bar
+                start_bar = torch.where(signs > 0, through(-((delay_bar + lo_pair) + hi_pair)), through(delay_bar)).sum(dim=(2, 3))
+        return (None, None) + tuple(bars) + (start_bar, lo_bar, hi_bar)
+
+    @staticmethod
+    def jvp(ctx, _t_d, _t_m, *tangents):
+        d, m = ctx.d, ctx.m
+        fleet, slots, tau, missing, gaps, per_pair, through, (is_lo, is_hi, end_first, end_second, is_start) = _TrajectoryStaggeredSeparation._saved(ctx)
+        sign, first, second = slots[1], slots[4], slots[5]
+        n, pairs, k = missing.shape
+        dots = [_dense(t) for t in tangents[:8 * d]]
+        zero = torch.zeros(missing.shape, dtype=torch.float64, device=tau.device)
+        wide = lambda t: t.unsqueeze(1) if t is not None else zero      # noqa: E731
+        start_dot = tangents[8 * d]
+        first_dot = start_dot[:, first].unsqueeze(2) if start_dot is not None else zero
+        delay_dot = (start_dot[:, second] - start_dot[:, first]).unsqueeze(2) + zero if start_dot is not None else zero
+        time_dot = torch.where(is_lo, wide(tangents[8 * d + 1]) - first_dot, zero)
+        time_dot = torch.where(is_hi, wide(tangents[8 * d + 2]) - first_dot, time_dot)
+        for which, ends, shift in ((first, end_first, zero), (second, end_second, delay_dot)):
+            for c in range(d):
+                total = shift
+                for t in (dots[8 * c + 6], dots[8 * c + 7]):
+                    if t is not None:
+                        total = total + t.reshape(n, m)[:, which].unsqueeze(2)
+                time_dot = torch.where(ends[c], total, time_dot)
+        time_dot = torch.where(is_start, delay_dot, time_dot)
+        signs = sign.reshape(1, m, m - 1, 1)
+        tau_dot = torch.where(signs > 0, through(time_dot), through(time_dot - delay_dot)).reshape(tau.shape).contiguous()
+        value_dot = zero
+        for c in range(d):
+            pos_dot = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
+            _trajectory_launch(capi.trajectory_eval_jvp, tau.device, fleet[c], tau, dots[8 * c:8 * c + 8], tau_dot, pos_dot, None, None)
+            dot_first, dot_second = per_pair(pos_dot)
+            value_dot = value_dot + (2.0 * gaps[c]) * (dot_first - dot_second)
+        return torch.where(missing, torch.full_like(zero, float("nan")), value_dot), None, None
+
+
+def _check_fleet_start(n, m, start, who):
+    """start: float64, (n, m) -- shape and type; the device comes after the windows' shapes (_check_fleet_start_device)."""
+    _check_is_tensor("start", start, who)
+    if start.dim() != 2 or tuple(start.shape) != (n, m):
+        raise ValueError("%s: start must have shape (%d, %d) -- one start time per vehicle -- got %s" % (who, n, m, tuple(start.shape)))
+    _check_is_float64("start", start, who)
+
+
+def _check_fleet_start_device(start, device, who):
+    if start.device != device:
+        raise TypeError("%s: start is on %s; it must be on the fleet's device %s" % (who, start.device, device))
+
+
 def _check_fleet(fleet, who):
     """A fleet as trajectory_fleet_separation takes it: six or eight float64 tensors (n, m, d): shapes and types (the devices come after
     the windows' shapes: _check_fleet_devices).  Returns (n, m, d, the d splines as lists of eight (n m,) tensors in the table's order)."""
@@ -1733,7 +1926,7 @@ def _check_fleet_windows(n, device, lo, hi, who):
     return out
 
 
-def trajectory_fleet_separation(fleet, lo=None, hi=None):
+def trajectory_fleet_separation(fleet, lo=None, hi=None, *, start=None):
     """trajectory_separation for every pair of a fleet, in one launch: n scenes of m vehicles (2..256) that move in d = 1, 2 or 3 axes, all
     vehicles of a scene on one clock.  fleet: a sequence of six tensors (pos0, pos1, pos2, vel1, duration0, duration1), or of eight with
     (vel0, vel2) appended, each (n, m, d) -- always three-dimensional -- float64 on one ROCm device.  lo, hi: (n, k), the windows of a
@@ -1747,21 +1940,35 @@ def trajectory_fleet_separation(fleet, lo=None, hi=None):
     or rp_trajectory_eval_jvp (forward) launch on the n m splines at the returned times; every sum over pairs is a
     gather and a sum, so a gradient is the same bits in every run; a double backward raises torch's once_differentiable error.  At ties
     the derivative is that of the branch the forward pass found.  A NaN value has gradient 0 (forward mode: NaN).  The time is not
-    differentiable.  Does not synchronise the host."""
+    differentiable.  Does not synchronise the host.
+
+    start= (n, m), float64 on the fleet's device, gives every vehicle a start time of its own: vehicle v runs its
+    spline over [start, start + T] of the scene's clock, on which lo, hi and t_closest then are.  [s, (i, j), q] is bit for bit
+    trajectory_separation's value for vehicles i and j with delay = start_j - start_i over the window [lo - start_i, hi - start_i], and
+    t_closest its time plus start_i; a NaN or infinite start makes exactly its vehicle's m - 1 pairs NaN, pairs never under way together
+    are NaN.  One rp_trajectory_fleet_separation_staggered launch; sep_sq is differentiable in start as well, by the pair entry's rule
+    for its delay, lo and hi.  start=None is the call without it: the same launches and the same bits."""
     who = "trajectory_fleet_separation"
     n, m, d, tables = _check_fleet(fleet, who)
+    if start is not None:
+        _check_fleet_start(n, m, start, who)
     lo, hi = _check_fleet_windows(n, fleet[0].device, lo, hi, who)
+    if start is not None:
+        _check_fleet_start_device(start, fleet[0].device, who)
     _check_fleet_devices(fleet, who)
-    return _TrajectoryFleetSeparation.apply(d, m, *[t for table in tables for t in table], lo, hi)
+    if start is None:
+        return _TrajectoryFleetSeparation.apply(d, m, *[t for table in tables for t in table], lo, hi)
+    return _TrajectoryStaggeredSeparation.apply(d, m, *[t for table in tables for t in table], start, lo, hi)[:2]
 
 
-def min_time_fleet_separation(pos, lo=None, hi=None, *, vel=None, synchronize=True, gap_tol=1e-8, max_iter=200, params=None):
+def min_time_fleet_separation(pos, lo=None, hi=None, *, vel=None, synchronize=True, gap_tol=1e-8, max_iter=200, params=None, start=None):
     """min_time_solve of a fleet's axes, then trajectory_fleet_separation of the solutions.  pos: (pos0, pos1, pos2), (n, m, d) each: one
     solve over the n m d axis problems.  vel: (vel0, vel2), (n, m, d) each (None: rest to rest).  synchronize (the default): each
     vehicle's axes are stretched to its slowest first (synchronize_axes on (n m, d); rest to rest only: with end velocities given it
     raises ValueError).  lo, hi as trajectory_fleet_separation's.  Returns (sep_sq, t_closest, solution) with the solution
     min_time_solve's (vel1, duration0, duration1, iters, status) as (n, m, d), as the solve left them (before the stretch).  Plain
-    composition: sep_sq is differentiable to first order in the positions, the end velocities, lo and hi, in both modes."""
+    composition: sep_sq is differentiable to first order in the positions, the end velocities, lo and hi, in both modes.  start= (n, m):
+    trajectory_fleet_separation's start times, checked before the solve and differentiable like lo and hi."""
     who = "min_time_fleet_separation"
     if synchronize and vel is not None:
         raise ValueError(who + ": synchronize=True needs rest-to-rest vehicles; pass synchronize=False with end velocities")
@@ -1775,7 +1982,11 @@ def min_time_fleet_separation(pos, lo=None, hi=None, *, vel=None, synchronize=Tr
             raise ValueError("%s: every tensor must have one shape (n, m, d) with d in 1..3, got %s" % (who, tuple(t.shape)))
     n, m, d = pos[0].shape
     _check_fleet_size(int(m), who)
+    if start is not None:
+        _check_fleet_start(n, int(m), start, who)
     lo, hi = _check_fleet_windows(n, pos[0].device, lo, hi, who)      # before the solve: a bad query costs none
+    if start is not None:
+        _check_fleet_start_device(start, pos[0].device, who)
     flat = lambda t: t.reshape(-1) if t is not None else None      # noqa: E731
     vel0, vel2 = (flat(v) for v in vel) if vel is not None else (None, None)
     solution = min_time_solve(*[flat(t) for t in pos], gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
@@ -1785,7 +1996,7 @@ def min_time_fleet_separation(pos, lo=None, hi=None, *, vel=None, synchronize=Tr
         spline = [t.reshape(n, m, d) for t in spline]
     elif vel is not None:
         spline = spline + list(vel)
-    return tuple(trajectory_fleet_separation(spline, lo, hi)) + (tuple(t.reshape(n, m, d) for t in solution),)
+    return tuple(trajectory_fleet_separation(spline, lo, hi, start=start)) + (tuple(t.reshape(n, m, d) for t in solution),)
 
 
 # ---- when two vehicles moving in several axes first come within a distance ----
@@ -2062,6 +2273,113 @@ class _TrajectoryFleetContact(torch.autograd.Function):
         return torch.where(missing, torch.full_like(rate, float("nan")), total / rate), None
 
 
+class _TrajectoryStaggeredContact(torch.autograd.Function):
+    """_TrajectoryFleetContact with a start time per vehicle: (the time on the scene's clock, the time on the clock of the pair's first
+    vehicle, rate), (n, pairs, k) each.  Inputs: d, m, the fleet's 8 d tensors, start (n, m), level_sq, lo, hi.  Pair (i, j) is
+    _TrajectoryContact's query with delay = start_j - start_i over [lo - start_i, hi - start_i]; the scene-clock time is its time t' plus
+    start_i and is differentiable by its implicit-function formula routed per vehicle: vehicle i is evaluated at t', vehicle j at
+    t' - delay, delay_bar is minus the second vehicle's tau_bar, start_j gets delay_bar and start_i minus delay_bar plus the time's own
+    +1.  lo and hi only choose the branch; the local time and the rate are not differentiable."""
+
+    @staticmethod
+    def forward(d, m, *inputs):
+        fleet = [_dense(t) for t in inputs[:8 * d]]
+        start, level, lo, hi = (_dense(t) for t in inputs[8 * d:])
+        per_pair = level.dim() == 3
+        if per_pair and _plain(level).data_ptr() % 16:      # a view that starts in the middle of a 16-byte vector
+            level = level.clone()
+        n, k = level.shape[0], level.shape[-1]
+        device = inputs[0].device
+        time, local, rate = (torch.empty((n, m * (m - 1) // 2, k), dtype=torch.float64, device=device) for _ in range(3))
+        with torch.cuda.device(device):      # as _trajectory_launch
+            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_fleet_contact_staggered(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d,
+                                                    [addr(t) for t in fleet], addr(start), addr(level), int(per_pair), addr(lo), addr(hi),
+                                                    addr(time), addr(local), addr(rate))
+        return time, local, rate
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(output[1], output[2])
+        d, ctx.m = inputs[0], inputs[1]
+        ctx.d = d
+        ctx.per_pair = inputs[3 + 8 * d].dim() == 3
+        ctx.given = [t is not None for t in inputs[2:2 + 8 * d]]      # neither derivative reads the level, lo or hi
+        kept = [t for t in inputs[2:2 + 8 * d] if t is not None] + [inputs[2 + 8 * d], output[1], output[2]]
+        ctx.save_for_backward(*kept)
+        ctx.save_for_forward(*kept)
+
+    @staticmethod
+    def _saved(ctx):
+        d, m = ctx.d, ctx.m
+        kept = iter(ctx.saved_tensors)
+        inputs = [next(kept) if given else None for given in ctx.given]
+        start, local, rate = list(kept)
+        fleet = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
+        missing = torch.isnan(local)
+        slots, _, _, tau, per_pair, through = _staggered_times(m, start, local, missing)
+        return fleet, slots, tau, rate, missing, _fleet_gaps(fleet, tau, per_pair), per_pair, through
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_time, _g_local, _g_rate):
+        d, m = ctx.d, ctx.m
+        if g_time is None:
+            return (None,) * (8 * d + 6)
+        fleet, slots, tau, rate, missing, gaps, per_pair, through = _TrajectoryStaggeredContact._saved(ctx)
+        n, pairs, k = missing.shape
+        need = ctx.needs_input_grad[2:]
+        zero = torch.zeros_like(rate)
+        own = torch.where(missing, zero, g_time)      # time = t' + start_i
+        w = torch.where(missing, zero, g_time / rate)      # an unreached level: gradient 0
+        signs = slots[1].reshape(1, m, m - 1, 1)
+        bars, delay_bar = [None] * (8 * d), None
+        for c in range(d):
+            bar = [torch.empty(n * m, dtype=torch.float64, device=tau.device) if need[8 * c + f] else None for f in range(8)]
+            tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if need[8 * d] else None
+            if tau_bar is not None or any(x is not None for x in bar):
+                g_pos = torch.where(missing, zero, -((2.0 * w) * gaps[c]))      # (a bad vehicle's gap is NaN: not into its partners)
+                upstream = (signs * through(g_pos)).reshape(tau.shape).contiguous()
+                _trajectory_launch(capi.trajectory_eval_vjp, tau.device, fleet[c], tau, upstream, None, None, bar, tau_bar)
+            bars[8 * c:8 * c + 8] = bar
+            if tau_bar is not None:      # the second vehicle is at t' - delay
+                share = per_pair(tau_bar)[1]
+                delay_bar = -share if delay_bar is None else delay_bar - share
+        start_bar = level_bar = None
+        if need[8 * d]:
+            start_bar = torch.where(signs > 0, through(own - delay_bar), through(delay_bar)).sum(dim=(2, 3))
+        if need[8 * d + 1]:
+            level_bar = w if ctx.per_pair else w.sum(dim=1)
+        return (None, None) + tuple(bars) + (start_bar, level_bar, None, None)
+
+    @staticmethod
+    def jvp(ctx, _t_d, _t_m, *tangents):
+        d, m = ctx.d, ctx.m
+        fleet, slots, tau, rate, missing, gaps, per_pair, through = _TrajectoryStaggeredContact._saved(ctx)
+        sign, first, second = slots[1], slots[4], slots[5]
+        dots = [_dense(t) for t in tangents[:8 * d]]
+        start_dot, level_dot = tangents[8 * d], tangents[8 * d + 1]
+        zero = torch.zeros_like(rate)
+        if level_dot is None:
+            total = zero
+        else:
+            total = level_dot if ctx.per_pair else level_dot.unsqueeze(1)
+        tau_dot = None
+        if start_dot is not None:      # the second vehicle's time moves against the delay
+            delay_dot = (start_dot[:, second] - start_dot[:, first]).unsqueeze(2) + zero
+            tau_dot = torch.where(sign.reshape(1, m, m - 1, 1) > 0, through(zero), through(-delay_dot)).reshape(tau.shape).contiguous()
+        for c in range(d):
+            pos_dot = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
+            _trajectory_launch(capi.trajectory_eval_jvp, tau.device, fleet[c], tau, dots[8 * c:8 * c + 8], tau_dot, pos_dot, None, None)
+            dot_first, dot_second = per_pair(pos_dot)
+            total = total - (2.0 * gaps[c]) * (dot_first - dot_second)
+        time_dot = total / rate
+        if start_dot is not None:
+            time_dot = time_dot + start_dot[:, first].unsqueeze(2)
+        return torch.where(missing, torch.full_like(rate, float("nan")), time_dot), None, None
+
+
 def _check_fleet_level(n, pairs, radius, level_sq, who):
     """The level of trajectory_fleet_contact, shape and type (the device comes after the windows' shapes): radius or level_sq, float64,
     (n, k), (k,) -- one level for all pairs of a scene -- or (n, pairs, k) -- one per pair.  Returns (its name, the level in units of
@@ -2089,7 +2407,7 @@ def _check_fleet_queries(n, m, device, radius, level_sq, lo, hi, who):
     return level, lo, hi
 
 
-def trajectory_fleet_contact(fleet, radius=None, lo=None, hi=None, *, level_sq=None):
+def trajectory_fleet_contact(fleet, radius=None, lo=None, hi=None, *, level_sq=None, start=None):
     """trajectory_contact for every pair of a fleet, in one launch: the first time in a scene's windows [lo, hi] at which two of its
     vehicles come within `radius` of each other.  fleet, lo, hi: exactly trajectory_fleet_separation's.  radius: (n, k), or (k,) for the
     same in every scene -- one radius for all pairs of a scene --, or (n, pairs, k) -- one per pair, what vehicles of different sizes need:
@@ -2105,22 +2423,33 @@ def trajectory_fleet_contact(fleet, radius=None, lo=None, hi=None, *, level_sq=N
     the returned times; every sum over pairs is a gather and a sum, so a gradient is the same bits in every run; a
     double backward raises torch's once_differentiable error.  lo and hi get no gradient.  An unreached level has gradient 0 (forward
     mode: NaN, as the time); where rate is 0 (a touch) the result is inf or NaN.  fleet_first_contact gives the scene's first contact and
-    its pair.  Does not synchronise the host."""
+    its pair.  Does not synchronise the host.
+
+    start= (n, m), float64 on the fleet's device: trajectory_fleet_separation's start times.  lo, hi and t_contact
+    are then on the scene's clock: [s, (i, j), q] is trajectory_contact's time, bit for bit, for vehicles i and j with delay = start_j -
+    start_i over the window [lo - start_i, hi - start_i], plus start_i.  One rp_trajectory_fleet_contact_staggered launch; the time is
+    differentiable in start as well.  start=None is the call without it: the same launches and the same bits."""
     who = "trajectory_fleet_contact"
     if (radius is None) == (level_sq is None):
         raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
     n, m, d, tables = _check_fleet(fleet, who)
+    if start is not None:
+        _check_fleet_start(n, m, start, who)
     level, lo, hi = _check_fleet_queries(n, m, fleet[0].device, radius, level_sq, lo, hi, who)
+    if start is not None:
+        _check_fleet_start_device(start, fleet[0].device, who)
     _check_fleet_devices(fleet, who)
-    return _TrajectoryFleetContact.apply(d, m, *[t for table in tables for t in table], level, lo, hi)[0]
+    if start is None:
+        return _TrajectoryFleetContact.apply(d, m, *[t for table in tables for t in table], level, lo, hi)[0]
+    return _TrajectoryStaggeredContact.apply(d, m, *[t for table in tables for t in table], start, level, lo, hi)[0]
 
 
 def min_time_fleet_contact(pos, radius=None, lo=None, hi=None, *, level_sq=None, vel=None, synchronize=True, gap_tol=1e-8, max_iter=200,
-                           params=None):
+                           params=None, start=None):
     """min_time_solve of a fleet's axes, then trajectory_fleet_contact of the solutions: min_time_fleet_separation's composition -- pos,
     vel, synchronize and the solution returned are its -- with trajectory_fleet_contact's radius (or level_sq=), lo and hi.  Returns
     (t_contact, solution).  Plain composition: the times are differentiable to first order in the positions, the end velocities and the
-    radius, in both modes."""
+    radius, in both modes.  start= (n, m): trajectory_fleet_contact's start times, checked before the solve and differentiable."""
     who = "min_time_fleet_contact"
     if (radius is None) == (level_sq is None):
         raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
@@ -2136,7 +2465,11 @@ def min_time_fleet_contact(pos, radius=None, lo=None, hi=None, *, level_sq=None,
             raise ValueError("%s: every tensor must have one shape (n, m, d) with d in 1..3, got %s" % (who, tuple(t.shape)))
     n, m, d = pos[0].shape
     _check_fleet_size(int(m), who)
+    if start is not None:
+        _check_fleet_start(n, int(m), start, who)
     level, lo, hi = _check_fleet_queries(n, int(m), pos[0].device, radius, level_sq, lo, hi, who)      # before the solve: a bad query costs none
+    if start is not None:
+        _check_fleet_start_device(start, pos[0].device, who)
     flat = lambda t: t.reshape(-1) if t is not None else None      # noqa: E731
     vel0, vel2 = (flat(v) for v in vel) if vel is not None else (None, None)
     solution = min_time_solve(*[flat(t) for t in pos], gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
@@ -2146,7 +2479,7 @@ def min_time_fleet_contact(pos, radius=None, lo=None, hi=None, *, level_sq=None,
         spline = [t.reshape(n, m, d) for t in spline]
     elif vel is not None:
         spline = spline + list(vel)
-    return trajectory_fleet_contact(spline, None, lo, hi, level_sq=level), tuple(t.reshape(n, m, d) for t in solution)
+    return trajectory_fleet_contact(spline, None, lo, hi, level_sq=level, start=start), tuple(t.reshape(n, m, d) for t in solution)
 
 
 def fleet_first_contact(t_contact):

@@ -124,6 +124,10 @@ SIGNATURES = {
                                                       ctypes.POINTER(_vp), _vp, _vp, _vp, _vp]),
     "rp_trajectory_fleet_contact": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
                                                    ctypes.POINTER(_vp), _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "rp_trajectory_fleet_separation_staggered": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                                ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rp_trajectory_fleet_contact_staggered": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                             ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "rp_trajectory_tracking": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
                                               _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_tracking_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
@@ -363,6 +367,39 @@ def trajectory_fleet_contact(device, stream, n, m, k, d, fleet, d_level_sq, leve
         raise ValueError("trajectory_fleet_contact: m must be 2..256 vehicles per scene, got %d" % m)
     check(load_library().rp_trajectory_fleet_contact(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_level_sq),
                                                      int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_time), vp(d_rate)))
+
+
+def trajectory_fleet_separation_staggered(device, stream, n, m, k, d, fleet, d_start, d_lo=None, d_hi=None, d_value=None, d_time=None,
+                                         d_time_local=None):
+    """rp_trajectory_fleet_separation_staggered: trajectory_fleet_separation with a start time per vehicle, d_start (n, m), required, on
+    the scene's clock, on which d_lo, d_hi and d_time are.  Pair (i, j) is trajectory_separation's query, bit for bit, with the delay
+    start_j - start_i over the window [lo - start_i, hi - start_i]; d_time_local is its time (vehicle i's clock), d_time that plus start_i.
+    d_value, d_time, d_time_local: (n, m (m - 1) / 2, k) (None / 0: not wanted; not all three)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = int(d), int(m)
+    if not 1 <= d <= 3:
+        raise ValueError("trajectory_fleet_separation_staggered: d must be 1, 2 or 3, got %d" % d)
+    if not 2 <= m <= 256:
+        raise ValueError("trajectory_fleet_separation_staggered: m must be 2..256 vehicles per scene, got %d" % m)
+    check(load_library().rp_trajectory_fleet_separation_staggered(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_start),
+                                                                  vp(d_lo), vp(d_hi), vp(d_value), vp(d_time), vp(d_time_local)))
+
+
+def trajectory_fleet_contact_staggered(device, stream, n, m, k, d, fleet, d_start, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None, d_time=None,
+                                       d_time_local=None, d_rate=None):
+    """rp_trajectory_fleet_contact_staggered: trajectory_fleet_contact with a start time per vehicle, d_start (n, m), required: pair (i, j)
+    is trajectory_contact's query, bit for bit, with the delay start_j - start_i over the window [lo - start_i, hi - start_i] at the same
+    level; d_time_local is its time (vehicle i's clock), d_time that plus start_i, d_rate its rate.  The three outputs are
+    (n, m (m - 1) / 2, k) (None / 0: not wanted; not all three)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = int(d), int(m)
+    if not 1 <= d <= 3:
+        raise ValueError("trajectory_fleet_contact_staggered: d must be 1, 2 or 3, got %d" % d)
+    if not 2 <= m <= 256:
+        raise ValueError("trajectory_fleet_contact_staggered: m must be 2..256 vehicles per scene, got %d" % m)
+    check(load_library().rp_trajectory_fleet_contact_staggered(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_start),
+                                                               vp(d_level_sq), int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_time),
+                                                               vp(d_time_local), vp(d_rate)))
 
 
 def tracking_table(addresses):

@@ -221,5 +221,13 @@ hipError_t launch_fleet_separation(size_t n, size_t m, size_t k, int d, const do
 // all pairs of a scene) or n x m (m - 1) / 2 x k (1); d_time required, d_rate may be null; both n x m (m - 1) / 2 x k
 hipError_t launch_fleet_contact(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq, int level_per_pair,
                                 const double *d_lo, const double *d_hi, double *d_time, double *d_rate, hipStream_t stream);
+// the two fleet queries with a start time per vehicle, d_start n x m (required) on the scene's clock, on which d_lo, d_hi and d_time are;
+// d_time_local is the same time on the clock of the pair's first vehicle (any output may be null, not all)
+hipError_t launch_fleet_separation_staggered(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
+                                             const double *d_lo, const double *d_hi, double *d_value, double *d_time, double *d_time_local,
+                                             hipStream_t stream);
+hipError_t launch_fleet_contact_staggered(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
+                                          const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
+                                          double *d_time_local, double *d_rate, hipStream_t stream);
 
 }  // namespace rp

@@ -1567,6 +1567,55 @@ int rp_trajectory_fleet_contact(int device, void *stream, size_t n, size_t m, si
     return RP_OK;
 }
 
+// the two fleet entries with a start time per vehicle (n x m, read as single values): the refusals of the entries they extend, a start that is
+// required, and three outputs of which any may be left out but not all
+int rp_trajectory_fleet_separation_staggered(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                                             const double *d_start, const double *d_lo, const double *d_hi, double *d_value, double *d_time,
+                                             double *d_time_local)
+{
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
+    if (m < 2 || m > 256) return fail(RP_ERR_INVALID, "%s: m must be 2..256 vehicles per scene, got %zu", __func__, m);
+    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
+    if (!d_fleet) return fail(RP_ERR_INVALID, "%s: d_fleet is null", __func__);
+    int st = RP_OK;
+    for (int x = 0; x < d && st == RP_OK; ++x) st = check_spline(__func__, "d_fleet", d_fleet + 8 * x);
+    const size_t pairs = m * (m - 1) / 2;
+    if (st == RP_OK && !d_start) st = fail(RP_ERR_INVALID, "%s: d_start is null", __func__);
+    if (st == RP_OK && n > SIZE_MAX / sizeof(double) / pairs) st = fail(RP_ERR_INVALID, "%s: n x pairs does not fit", __func__);
+    if (st == RP_OK)
+        st = check_queries(__func__, n == 0 ? 0 : n * pairs, k, nullptr, nullptr, {d_value, d_time, d_time_local}, d_value || d_time || d_time_local);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_fleet_separation_staggered(n, m, k, d, d_fleet, d_start, d_lo, d_hi, d_value, d_time, d_time_local, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_trajectory_fleet_contact_staggered(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                                          const double *d_start, const double *d_level_sq, int level_per_pair, const double *d_lo,
+                                          const double *d_hi, double *d_time, double *d_time_local, double *d_rate)
+{
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
+    if (m < 2 || m > 256) return fail(RP_ERR_INVALID, "%s: m must be 2..256 vehicles per scene, got %zu", __func__, m);
+    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
+    if (level_per_pair != 0 && level_per_pair != 1)
+        return fail(RP_ERR_INVALID, "%s: level_per_pair must be 0 (n x k) or 1 (n x pairs x k), got %d", __func__, level_per_pair);
+    if (!d_fleet) return fail(RP_ERR_INVALID, "%s: d_fleet is null", __func__);
+    int st = RP_OK;
+    for (int x = 0; x < d && st == RP_OK; ++x) st = check_spline(__func__, "d_fleet", d_fleet + 8 * x);
+    const size_t pairs = m * (m - 1) / 2;
+    if (st == RP_OK && !d_start) st = fail(RP_ERR_INVALID, "%s: d_start is null", __func__);
+    if (st == RP_OK && !d_level_sq) st = fail(RP_ERR_INVALID, "%s: d_level_sq is null", __func__);
+    if (st == RP_OK && n > SIZE_MAX / sizeof(double) / pairs) st = fail(RP_ERR_INVALID, "%s: n x pairs does not fit", __func__);
+    if (st == RP_OK)
+        st = check_queries(__func__, n == 0 ? 0 : n * pairs, k, nullptr, nullptr, {level_per_pair ? d_level_sq : nullptr, d_time, d_time_local, d_rate},
+                           d_time || d_time_local || d_rate);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_fleet_contact_staggered(n, m, k, d, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate,
+                                              (hipStream_t)stream));
+    return RP_OK;
+}
+
 // the integrals over a window, their first derivatives and the reverse rule's derivative along a direction
 int rp_trajectory_integrals(int device, void *stream, size_t n, size_t k, const double *const d_spline[8], const double *d_lo, const double *d_hi,
                             double *const d_value[4])

@@ -16,6 +16,7 @@
 //   the first time they come within a distance k_contact                                        section 25
 //   the closest approach of a fleet's pairs    k_fleet                                          section 26
 //   the first contact of a fleet's pairs       k_encounter                                      section 27
+//   ... both with a start time per vehicle     k_stagger, k_rendezvous                          section 28
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
 // rp_batch_integrals_device and rp_batch_sample*; the launchers are at the end of the file.
@@ -2811,6 +2812,138 @@ k_encounter(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, co
     });
 }
 
+// ---- a fleet whose vehicles start at times of their own (rp_trajectory_fleet_separation_staggered, rp_trajectory_fleet_contact_staggered;
+// DESIGN.md section 28) ----
+// start is n x m: vehicle v of scene s runs its spline over [start, start + T] of the scene's clock, on which lo, hi and the returned time
+// are.  Pair (i, j) is the pair entry's query on vehicle i's clock, each number one fp64 operation: delay = s_j - s_i, the window
+// [lo - s_i, hi - s_i] (a null end is -inf / +inf before the subtraction), and the time that comes back plus s_i.  k_fleet's / k_encounter's
+// staging and scene arithmetic; SepLds has no spare word and nothing may stand next to it (section 26), so the two starts of a query do
+// not go through LDS: the streaming part decodes (i, j) again from the query's own problem number -- fleet_pair, at most m - 1 integer
+// subtractions -- and loads the two starts as plain 8-byte loads, which L2 serves.  One query at a time does so, inside the loop over the
+// pair's halves, so that one delay and one s_i are live across a query's searches and not two.  A NaN or infinite start makes the
+// delay NaN or infinite (inf - inf: NaN), which is the pair entry's NaN rule for exactly that vehicle's m - 1 pairs.
+struct StartOf {
+    const double *__restrict__ start, *__restrict__ lo, *__restrict__ hi;
+    unsigned m, pairs;
+
+    // the query of problem r_first + q (from the trip's first scene on) at window element w: its s_i, delay and window on i's clock
+    __device__ __forceinline__ void load(size_t s, unsigned r, size_t w, double &s_i, double &delay, double &l, double &h) const
+    {
+        const double inf = __builtin_inf();
+        unsigned i, j;
+        fleet_pair(r, m, i, j);
+        s_i = start[s * m + i];
+        delay = start[s * m + j] - s_i;
+        l = (lo ? lo[w] : -inf) - s_i;
+        h = (hi ? hi[w] : inf) - s_i;
+    }
+};
+
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
+k_stagger(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const double *__restrict__ start, const double *__restrict__ lo,
+          const double *__restrict__ hi, double *__restrict__ value, double *__restrict__ time, double *__restrict__ time_local)
+{
+    __shared__ SepLds<D> L;
+    const unsigned pairs = fleet_pair_count(m);
+    const StartOf clock{start, lo, hi, m, pairs};
+    auto stage_problem = [&](int q, size_t p) {
+        const size_t p_first = p - (size_t)q, s_first = p_first / pairs;
+        const unsigned r = (unsigned)(p_first - s_first * pairs) + (unsigned)q;      // < pairs + kTrajProblems
+        const size_t s = s_first + r / pairs;
+        unsigned i, j;
+        fleet_pair(r % pairs, m, i, j);
+        const size_t first = s * m + i, second = s * m + j;
+#pragma unroll
+        for (int x = 0; x < D; ++x) {
+            Knots ka = in.v[x].load(first), kb = in.v[x].load(second);
+            ka.check();
+            kb.check();
+            stage_eval(L.a[x], q, ka);
+            stage_eval(L.b[x], q, kb);
+            L.Ta[x][q] = ka.t0 + ka.t1;
+            L.Tb[x][q] = kb.t0 + kb.t1;
+        }
+    };
+    for_each_trip(problems, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k, s_first = p_first / pairs;
+        const unsigned r_first = (unsigned)(p_first - s_first * pairs);
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double va = 0.0, vb = 0.0, ta = 0.0, tb = 0.0, ua = 0.0, ub = 0.0;      // value, scene-clock time, local time
+#pragma nounroll
+            for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_fleet: each query's searches have their own trip counts
+                const int q = half ? qb : qa;
+                const unsigned r = r_first + (unsigned)q;
+                const size_t s = s_first + r / pairs;
+                double s_i, delay, l, h, v, t;
+                clock.load(s, r % pairs, s * k + (e + (size_t)half - (size_t)q * k), s_i, delay, l, h);
+                int trips = 0;
+                separation_query(L, q, l, h, delay, v, t, trips);
+                const double scene = t + s_i;
+                va = half ? va : v; ua = half ? ua : t; ta = half ? ta : scene;
+                vb = half ? v : vb; ub = half ? t : ub; tb = half ? scene : tb;
+            }
+            if (value) store_pair(value, e_first + e, va, vb, two);
+            if (time) store_pair(time, e_first + e, ta, tb, two);
+            if (time_local) store_pair(time_local, e_first + e, ua, ub, two);
+        });
+    });
+}
+
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
+k_rendezvous(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const double *__restrict__ start,
+             const double *__restrict__ level, int level_per_pair, const double *__restrict__ lo, const double *__restrict__ hi,
+             double *__restrict__ time, double *__restrict__ time_local, double *__restrict__ rate)
+{
+    __shared__ SepLds<D> L;
+    const unsigned pairs = fleet_pair_count(m);
+    const StartOf clock{start, lo, hi, m, pairs};
+    auto stage_problem = [&](int q, size_t p) {
+        const size_t p_first = p - (size_t)q, s_first = p_first / pairs;
+        const unsigned r = (unsigned)(p_first - s_first * pairs) + (unsigned)q;      // < pairs + kTrajProblems
+        const size_t s = s_first + r / pairs;
+        unsigned i, j;
+        fleet_pair(r % pairs, m, i, j);
+        const size_t first = s * m + i, second = s * m + j;
+#pragma unroll
+        for (int x = 0; x < D; ++x) {
+            Knots ka = in.v[x].load(first), kb = in.v[x].load(second);
+            ka.check();
+            kb.check();
+            stage_eval(L.a[x], q, ka);
+            stage_eval(L.b[x], q, kb);
+            L.Ta[x][q] = ka.t0 + ka.t1;
+            L.Tb[x][q] = kb.t0 + kb.t1;
+        }
+    };
+    for_each_trip(problems, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k, s_first = p_first / pairs;
+        const unsigned r_first = (unsigned)(p_first - s_first * pairs);
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            double ta = 0.0, tb = 0.0, ua = 0.0, ub = 0.0, ra = 0.0, rb = 0.0;      // scene-clock time, local time, rate
+#pragma nounroll
+            for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_encounter: each query's searches have their own trip counts
+                const int q = half ? qb : qa;
+                const unsigned r = r_first + (unsigned)q;
+                const size_t s = s_first + r / pairs;
+                const size_t w = s * k + (e + (size_t)half - (size_t)q * k);      // the scene's row, the query's column
+                double s_i, delay, l, h, t, rt;
+                clock.load(s, r % pairs, w, s_i, delay, l, h);
+                const double p = level[level_per_pair ? e_first + e + (size_t)half : w];
+                int trips = 0;
+                contact_query<D>(L, q, p, l, h, delay, t, rt, trips);
+                const double scene = t + s_i;
+                ua = half ? ua : t; ta = half ? ta : scene; ra = half ? ra : rt;
+                ub = half ? t : ub; tb = half ? scene : tb; rb = half ? rt : rb;
+            }
+            if (time) store_pair(time, e_first + e, ta, tb, two);
+            if (time_local) store_pair(time_local, e_first + e, ua, ub, two);
+            if (rate) store_pair(rate, e_first + e, ra, rb, two);
+        });
+    });
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -3242,6 +3375,61 @@ hipError_t launch_fleet_contact(size_t n, size_t m, size_t k, int d, const doubl
     case 1: return launch_fleet_contact_axes<1>(n, (unsigned)m, k, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, stream);
     case 2: return launch_fleet_contact_axes<2>(n, (unsigned)m, k, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, stream);
     case 3: return launch_fleet_contact_axes<3>(n, (unsigned)m, k, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <int D>
+hipError_t launch_stagger_axes(size_t n, unsigned m, size_t k, const double *const *d_fleet, const double *d_start, const double *d_lo,
+                               const double *d_hi, double *d_value, double *d_time, double *d_time_local, hipStream_t stream)
+{
+    FleetSplines<D> in;
+    for (int x = 0; x < D; ++x) in.v[x] = FromArrays{table_of<8>(d_fleet + 8 * x)};
+    const size_t problems = n * fleet_pair_count(m);
+    return launch_stateless<false>(problems, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_stagger<D>, grid, block, 0, stream, in, problems, m, k, P, d_start, d_lo, d_hi, d_value, d_time, d_time_local);
+    });
+}
+
+hipError_t launch_fleet_separation_staggered(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
+                                             const double *d_lo, const double *d_hi, double *d_value, double *d_time, double *d_time_local,
+                                             hipStream_t stream)
+{
+    if (m < 2 || m > kFleetMost || !d_start) return hipErrorInvalidValue;
+    switch (d) {
+    case 1: return launch_stagger_axes<1>(n, (unsigned)m, k, d_fleet, d_start, d_lo, d_hi, d_value, d_time, d_time_local, stream);
+    case 2: return launch_stagger_axes<2>(n, (unsigned)m, k, d_fleet, d_start, d_lo, d_hi, d_value, d_time, d_time_local, stream);
+    case 3: return launch_stagger_axes<3>(n, (unsigned)m, k, d_fleet, d_start, d_lo, d_hi, d_value, d_time, d_time_local, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <int D>
+hipError_t launch_rendezvous_axes(size_t n, unsigned m, size_t k, const double *const *d_fleet, const double *d_start, const double *d_level_sq,
+                                  int level_per_pair, const double *d_lo, const double *d_hi, double *d_time, double *d_time_local,
+                                  double *d_rate, hipStream_t stream)
+{
+    FleetSplines<D> in;
+    for (int x = 0; x < D; ++x) in.v[x] = FromArrays{table_of<8>(d_fleet + 8 * x)};
+    const size_t problems = n * fleet_pair_count(m);
+    return launch_stateless<false>(problems, k, [&](dim3 grid, dim3 block, int P, int) {
+        hipLaunchKernelGGL(k_rendezvous<D>, grid, block, 0, stream, in, problems, m, k, P, d_start, d_level_sq, level_per_pair, d_lo, d_hi,
+                           d_time, d_time_local, d_rate);
+    });
+}
+
+hipError_t launch_fleet_contact_staggered(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
+                                          const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
+                                          double *d_time_local, double *d_rate, hipStream_t stream)
+{
+    if (m < 2 || m > kFleetMost || !d_start || !d_level_sq) return hipErrorInvalidValue;
+    switch (d) {
+    case 1:
+        return launch_rendezvous_axes<1>(n, (unsigned)m, k, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, stream);
+    case 2:
+        return launch_rendezvous_axes<2>(n, (unsigned)m, k, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, stream);
+    case 3:
+        return launch_rendezvous_axes<3>(n, (unsigned)m, k, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, stream);
     }
     return hipErrorInvalidValue;
 }
