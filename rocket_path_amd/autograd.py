@@ -62,6 +62,7 @@ start= on those four (section 28) gives every vehicle a start time of its own on
 delay start_j - start_i over the window shifted by start_i, bit for bit, in one rp_trajectory_fleet_separation_staggered or
 rp_trajectory_fleet_contact_staggered launch, differentiable in start through the same slot table; start=None is the call without it.
 """
+import collections
 import ctypes
 import functools
 import threading
@@ -1541,111 +1542,186 @@ def fleet_slots(m, device=None):
     return tuple(t.to(device) if device is not None else t.clone() for t in _fleet_slots_cpu(m))
 
 
+# What the four fleet Functions share: one forward launch each; for the derivatives the pair entry's rule done per
+# vehicle -- the times gathered through the slot table to (n m, (m - 1) k), per axis one evaluator launch and one launch of its derivative
+# on the n m splines, every sum over a vehicle's pairs a gather through the slot table and a sum.
+def _fleet_forward(entry, d, m, inputs, n, k, outputs, middle):
+    """One launch of a fleet entry on the current stream: the fleet's 8 d tensors (inputs[:8 d]; axis-major, each axis in the table's
+    order, each n m values with vehicle v of scene s at s m + v), middle(addr)'s arguments, then `outputs` fresh (n, pairs, k) tensors,
+    which it returns."""
+    fleet = [_dense(t) for t in inputs[:8 * d]]
+    device = inputs[0].device
+    out = tuple(torch.empty((n, m * (m - 1) // 2, k), dtype=torch.float64, device=device) for _ in range(outputs))
+    with torch.cuda.device(device):      # as _trajectory_launch
+        addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
+        entry(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in fleet], *middle(addr),
+              *[addr(t) for t in out])
+    return out
+
+
+def _fleet_setup(ctx, inputs, count, dead, outputs):
+    """Keeps d, m, those of the first `count` inputs after them that were given, and `outputs`, for both modes; `dead` are the outputs
+    that are not differentiable."""
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(*dead)
+    ctx.d, ctx.m = inputs[0], inputs[1]
+    ctx.given = [t is not None for t in inputs[2:2 + count]]
+    kept = [t for t in inputs[2:2 + count] if t is not None] + list(outputs)
+    ctx.save_for_backward(*kept)
+    ctx.save_for_forward(*kept)
+
+
+def _fleet_kept(ctx):
+    """What _fleet_setup kept: (the d lists of eight fleet tensors, the other inputs among the `count`, the outputs)"""
+    kept = iter(ctx.saved_tensors)
+    inputs = [next(kept) if given else None for given in ctx.given]
+    return [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(ctx.d)], inputs[8 * ctx.d:], list(kept)
+
+
+_FleetTimes = collections.namedtuple("_FleetTimes", "slots signs delay t tau per_pair through")
+
+
+def _fleet_times(m, time, missing, start=None):
+    """Where the derivatives evaluate the n m splines.  time: each pair's time on the clock of its first vehicle, (n, pairs, k).  Returns
+    slots: the slot tables; signs: +1 / -1 as (1, m, m - 1, 1); delay: start_j - start_i, (n, pairs, 1), the kernel's bits (None without
+    start); t: the time, 0 where missing; tau: the times through the slot table, (n m, (m - 1) k) -- t in both vehicles' rows or, with
+    start (DESIGN.md section 28), t in the row of the pair's first vehicle and t - delay, the pair entry's t_b, in the row of its second;
+    per_pair: a pair's view of a per-slot array; through: (n, pairs, k) -> per vehicle and slot, (n, m, m - 1, k)."""
+    n, pairs, k = time.shape
+    slots = _fleet_slots_on(m, time.device)
+    pair, sign, at_first, at_second, first, second = slots
+    through = lambda x: x[:, pair.reshape(-1), :].reshape(n, m, m - 1, k)      # noqa: E731
+    signs = sign.reshape(1, m, m - 1, 1)
+    zero = torch.zeros_like(time)
+    t = torch.where(missing, zero, time)
+    if start is None:
+        delay, rows = None, through(t)
+    else:
+        delay = (start[:, second] - start[:, first]).unsqueeze(2)
+        rows = torch.where(signs > 0, through(t), through(torch.where(missing, zero, t - delay)))
+    tau = rows.reshape(n * m, (m - 1) * k).contiguous()
+
+    def per_pair(x):      # (n m, (m - 1) k) -> the pair's entry in its first vehicle's row and in its second's, (n, pairs, k) each
+        x = x.reshape(n, m * (m - 1), k)
+        return x[:, at_first, :], x[:, at_second, :]
+
+    return _FleetTimes(slots, signs, delay, t, tau, per_pair, through)
+
+
+def _fleet_gaps(fleet, at):
+    """The d gaps D_c at the pairs' times, (n, pairs, k) each: one evaluator launch per axis"""
+    gaps = []
+    for s in fleet:
+        pos = torch.empty(at.tau.shape, dtype=torch.float64, device=at.tau.device)
+        _trajectory_launch(capi.trajectory_eval, at.tau.device, s, at.tau, pos, None, None)
+        pos_first, pos_second = at.per_pair(pos)
+        gaps.append(pos_first - pos_second)
+    return gaps
+
+
+def _class_masks(t, missing, tests, last_only=None):
+    """The class of each time: where t equals tests[0], else tests[1], ... (None: nowhere) -- exclusive, in that priority, never where
+    missing; the last class only where last_only holds."""
+    masks, taken = [], missing
+    for at, ref in enumerate(tests):
+        mask = (t == ref) & ~taken if ref is not None else torch.zeros_like(missing)
+        if last_only is not None and at == len(tests) - 1:
+            mask = mask & last_only
+        masks.append(mask)
+        taken = taken | mask
+    return masks
+
+
+def _fleet_vjp(fleet, at, need, want_tau, g_gap):
+    """Axis by axis, the evaluator's reverse launch on the n m splines at at.tau, upstream g_gap(c) -- the gradient on the gap D_c,
+    (n, pairs, k) -- with its sign through the slot table; yields (the axis' eight bars, None where need has none; tau_bar, None unless
+    want_tau).  An axis that needs neither is not launched."""
+    tau = at.tau
+    for c, s in enumerate(fleet):
+        bar = [torch.empty(tau.shape[0], dtype=torch.float64, device=tau.device) if need[8 * c + f] else None for f in range(8)]
+        tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if want_tau else None
+        if want_tau or any(x is not None for x in bar):
+            upstream = (at.signs * at.through(g_gap(c))).reshape(tau.shape).contiguous()
+            _trajectory_launch(capi.trajectory_eval_vjp, tau.device, s, tau, upstream, None, None, bar, tau_bar)
+        yield bar, tau_bar
+
+
+def _fleet_jvp(fleet, at, gaps, dots, tau_dot):
+    """Axis by axis, the evaluator's forward launch on the n m splines at at.tau; yields the axis' share of the tangent of the squared
+    distance, 2 D_c (d pos_first,c - d pos_second,c), (n, pairs, k)."""
+    for c, s in enumerate(fleet):
+        pos_dot = torch.empty(at.tau.shape, dtype=torch.float64, device=at.tau.device)
+        _trajectory_launch(capi.trajectory_eval_jvp, at.tau.device, s, at.tau, dots[8 * c:8 * c + 8], tau_dot, pos_dot, None, None)
+        dot_first, dot_second = at.per_pair(pos_dot)
+        yield (2.0 * gaps[c]) * (dot_first - dot_second)
+
+
+def _route_end_bars(bars, need, at, routed, end_first, end_second):
+    """Adds to the duration bars what the times that sit on a vehicle's end carry: a vehicle's pairs through the slot table, then a
+    plain sum."""
+    for c in range(len(end_first)):
+        if need[8 * c + 6] or need[8 * c + 7]:
+            mine = torch.where(at.signs > 0, at.through(routed(end_first[c])), at.through(routed(end_second[c]))).sum(dim=(2, 3)).reshape(-1)
+            for f in (6, 7):
+                if need[8 * c + f]:
+                    bars[8 * c + f] = bars[8 * c + f] + mine
+
+
 class _TrajectoryFleetSeparation(torch.autograd.Function):
     """(sep_sq, t_closest), (n, pairs, k) each, of every pair of n scenes of m vehicles of d axes over the scenes' windows.  Inputs: d, m,
-    the fleet's 8 d tensors (axis-major, each axis in the table's order, each n m values with vehicle v of scene s at s m + v), lo, hi
-    (n, k).  The value is differentiable to first order in all 8 d fleet inputs, lo and hi by _TrajectorySeparation's envelope routing
-    done per vehicle: the returned times gathered through the slot table to (n m, (m - 1) k), per axis one evaluator launch and one
-    launch of its derivative on the n m splines, the time's own derivative routed by the class of the time -- lo, hi, the end of an
-    axis of the pair's first vehicle, of its second; dropped otherwise.  The time is not differentiable."""
+    the fleet's 8 d tensors, lo, hi (n, k).  The value is differentiable to first order in all 8 d fleet inputs, lo and hi by
+    _TrajectorySeparation's envelope routing done per vehicle, the time's own derivative routed by the class of the time -- lo, hi, the
+    end of an axis of the pair's first vehicle, of its second; dropped otherwise.  The time is not differentiable."""
 
     @staticmethod
     def forward(d, m, *inputs):
-        fleet = [_dense(t) for t in inputs[:8 * d]]
         lo, hi = (_dense(t) for t in inputs[8 * d:])
         given = lo if lo is not None else hi
         n = inputs[0].shape[0] // m
         k = given.shape[1] if given is not None else 1
-        device = inputs[0].device
-        value, time = (torch.empty((n, m * (m - 1) // 2, k), dtype=torch.float64, device=device) for _ in range(2))
-        with torch.cuda.device(device):      # as _trajectory_launch
-            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_fleet_separation(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in fleet],
-                                             addr(lo), addr(hi), addr(value), addr(time))
-        return value, time
+        return _fleet_forward(capi.trajectory_fleet_separation, d, m, inputs, n, k, 2, lambda addr: (addr(lo), addr(hi)))
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(output[1])
-        ctx.d, ctx.m = inputs[0], inputs[1]
-        ctx.given = [t is not None for t in inputs[2:]]
-        kept = [t for t in inputs[2:] if t is not None] + list(output)
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _fleet_setup(ctx, inputs, 8 * inputs[0] + 2, output[1:], output)
 
     @staticmethod
     def _saved(ctx):
-        """(the d lists of eight tensors; the slot tables; the times through the slot table, 0 where the value is NaN, (n m, (m - 1) k);
-        where the value is NaN, (n, pairs, k); the d gaps D_c there; a pair's view of a per-slot array; the class masks LO, HI, [END of
-        the first vehicle's axis c], [END of the second's], exclusive and in that priority)"""
+        """(the d lists of eight tensors; _fleet_times; where the value is NaN, (n, pairs, k); the d gaps D_c; the class masks LO, HI,
+        [END of the first vehicle's axis c], [END of the second's], exclusive and in that priority)"""
         d, m = ctx.d, ctx.m
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        value, time = list(kept)
-        fleet = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
-        lo, hi = inputs[8 * d:]
-        n, pairs, k = time.shape
-        slots = _fleet_slots_on(m, time.device)
-        pair, _, at_first, at_second, first, second = slots
+        fleet, (lo, hi), (value, time) = _fleet_kept(ctx)
         missing = torch.isnan(value) | torch.isnan(time)
-        t = torch.where(missing, torch.zeros_like(time), time)
-        tau = t[:, pair.reshape(-1), :].reshape(n * m, (m - 1) * k).contiguous()
-
-        def per_pair(x):      # (n m, (m - 1) k) -> the pair's entry in its first vehicle's row and in its second's, (n, pairs, k) each
-            x = x.reshape(n, m * (m - 1), k)
-            return x[:, at_first, :], x[:, at_second, :]
-
-        ends = [(s[6] + s[7]).reshape(n, m) for s in fleet]
+        at = _fleet_times(m, time, missing)
+        first, second = at.slots[4], at.slots[5]
+        ends = [(s[6] + s[7]).reshape(-1, m) for s in fleet]
         tests = [lo.unsqueeze(1) if lo is not None else None, hi.unsqueeze(1) if hi is not None else None]
         tests += [e[:, first].unsqueeze(2) for e in ends] + [e[:, second].unsqueeze(2) for e in ends]
-        masks, taken = [], missing
-        for ref in tests:
-            mask = (t == ref) & ~taken if ref is not None else torch.zeros_like(missing)
-            masks.append(mask)
-            taken = taken | mask
-        gaps = []
-        for s in fleet:
-            pos = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
-            _trajectory_launch(capi.trajectory_eval, tau.device, s, tau, pos, None, None)
-            pos_first, pos_second = per_pair(pos)
-            gaps.append(pos_first - pos_second)
-        return fleet, slots, tau, missing, gaps, per_pair, (masks[0], masks[1], masks[2:2 + d], masks[2 + d:])
+        masks = _class_masks(at.t, missing, tests)
+        return fleet, at, missing, _fleet_gaps(fleet, at), (masks[0], masks[1], masks[2:2 + d], masks[2 + d:])
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_value, _g_time):
-        d, m = ctx.d, ctx.m
+        d = ctx.d
         if g_value is None:
             return (None,) * (8 * d + 4)
-        fleet, (pair, sign, _, _, _, _), tau, missing, gaps, per_pair, (is_lo, is_hi, end_first, end_second) = _TrajectoryFleetSeparation._saved(ctx)
-        n, pairs, k = missing.shape
+        fleet, at, missing, gaps, (is_lo, is_hi, end_first, end_second) = _TrajectoryFleetSeparation._saved(ctx)
         g = torch.where(missing, torch.zeros_like(g_value), g_value)      # a NaN value: gradient 0
         need = ctx.needs_input_grad[2:]
         want_time = any(need[8 * c + 6] or need[8 * c + 7] for c in range(d)) or any(need[8 * d:])
-        through = lambda x: x[:, pair.reshape(-1), :].reshape(n, m, m - 1, k)      # noqa: E731  (n, pairs, k) -> per vehicle and slot
-        signs = sign.reshape(1, m, m - 1, 1)
-        bars, time_bar = [None] * (8 * d), None
-        for c in range(d):
-            g_pos = torch.where(missing, torch.zeros_like(g), (2.0 * g) * gaps[c])      # (a bad vehicle's gap is NaN: not into its partners)
-            upstream = (signs * through(g_pos)).reshape(tau.shape).contiguous()
-            bar = [torch.empty(n * m, dtype=torch.float64, device=tau.device) if need[8 * c + f] else None for f in range(8)]
-            tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if want_time else None
-            if want_time or any(x is not None for x in bar):
-                _trajectory_launch(capi.trajectory_eval_vjp, tau.device, fleet[c], tau, upstream, None, None, bar, tau_bar)
-            bars[8 * c:8 * c + 8] = bar
+        # (a bad vehicle's gap is NaN: not into its partners)
+        g_gap = lambda c: torch.where(missing, torch.zeros_like(g), (2.0 * g) * gaps[c])      # noqa: E731
+        bars, time_bar = [], None
+        for bar, tau_bar in _fleet_vjp(fleet, at, need, want_time, g_gap):
+            bars += bar
             if want_time:      # the pair's: its two vehicles', added in _TrajectorySeparation's order -- the same bits per pair and query
-                for share in per_pair(tau_bar):
+                for share in at.per_pair(tau_bar):
                     time_bar = share if time_bar is None else time_bar + share
         lo_bar = hi_bar = None
         if want_time:
             routed = lambda mask: torch.where(mask, time_bar, torch.zeros_like(time_bar))      # noqa: E731
-            for c in range(d):
-                if need[8 * c + 6] or need[8 * c + 7]:      # a vehicle's pairs: through the slot table, then a plain sum
-                    mine = torch.where(signs > 0, through(routed(end_first[c])), through(routed(end_second[c]))).sum(dim=(2, 3)).reshape(n * m)
-                    for f in (6, 7):
-                        if need[8 * c + f]:
-                            bars[8 * c + f] = bars[8 * c + f] + mine
+            _route_end_bars(bars, need, at, routed, end_first, end_second)
             if need[8 * d]:
                 lo_bar = routed(is_lo).sum(dim=1)
             if need[8 * d + 1]:
@@ -1655,10 +1731,10 @@ class _TrajectoryFleetSeparation(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, _t_d, _t_m, *tangents):
         d, m = ctx.d, ctx.m
-        fleet, (pair, _, _, _, first, second), tau, missing, gaps, per_pair, (is_lo, is_hi, end_first, end_second) = _TrajectoryFleetSeparation._saved(ctx)
-        n, pairs, k = missing.shape
+        fleet, at, missing, gaps, (is_lo, is_hi, end_first, end_second) = _TrajectoryFleetSeparation._saved(ctx)
+        pair, first, second = at.slots[0], at.slots[4], at.slots[5]
         dots = [_dense(t) for t in tangents[:8 * d]]
-        zero = torch.zeros(missing.shape, dtype=torch.float64, device=tau.device)
+        zero = torch.zeros(missing.shape, dtype=torch.float64, device=at.tau.device)
         wide = lambda t: t.unsqueeze(1) if t is not None else zero      # noqa: E731
         time_dot = torch.where(is_lo, wide(tangents[8 * d]), zero)
         time_dot = torch.where(is_hi, wide(tangents[8 * d + 1]), time_dot)
@@ -1669,48 +1745,12 @@ class _TrajectoryFleetSeparation(torch.autograd.Function):
                     if t is not None:
                         total = t if total is None else total + t
                 if total is not None:
-                    time_dot = torch.where(ends[c], total.reshape(n, m)[:, which].unsqueeze(2), time_dot)
-        tau_dot = time_dot[:, pair.reshape(-1), :].reshape(tau.shape).contiguous()
+                    time_dot = torch.where(ends[c], total.reshape(-1, m)[:, which].unsqueeze(2), time_dot)
+        tau_dot = time_dot[:, pair.reshape(-1), :].reshape(at.tau.shape).contiguous()
         value_dot = zero
-        for c in range(d):
-            pos_dot = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
-            _trajectory_launch(capi.trajectory_eval_jvp, tau.device, fleet[c], tau, dots[8 * c:8 * c + 8], tau_dot, pos_dot, None, None)
-            dot_first, dot_second = per_pair(pos_dot)
-            value_dot = value_dot + (2.0 * gaps[c]) * (dot_first - dot_second)
+        for share in _fleet_jvp(fleet, at, gaps, dots, tau_dot):
+            value_dot = value_dot + share
         return torch.where(missing, torch.full_like(zero, float("nan")), value_dot), None
-
-
-def _staggered_times(m, start, time_local, missing):
-    """What both staggered fleet functions evaluate at: (the slot tables; the pair's delay start_j - start_i,
-    (n, pairs, 1), the kernel's bits; the pair's local time t', 0 where missing, (n, pairs, k); the times through the slot table,
-    (n m, (m - 1) k): t' in the row of the pair's first vehicle and t' - delay, the pair entry's t_b, in the row of its second; a pair's
-    view of a per-slot array; (n, pairs, k) -> per vehicle and slot, (n, m, m - 1, k))"""
-    n, pairs, k = time_local.shape
-    slots = _fleet_slots_on(m, time_local.device)
-    pair, sign, at_first, at_second, first, second = slots
-    delay = (start[:, second] - start[:, first]).unsqueeze(2)
-    zero = torch.zeros_like(time_local)
-    t_first = torch.where(missing, zero, time_local)
-    t_second = torch.where(missing, zero, t_first - delay)
-    through = lambda x: x[:, pair.reshape(-1), :].reshape(n, m, m - 1, k)      # noqa: E731
-    signs = sign.reshape(1, m, m - 1, 1)
-    tau = torch.where(signs > 0, through(t_first), through(t_second)).reshape(n * m, (m - 1) * k).contiguous()
-
-    def per_pair(x):      # (n m, (m - 1) k) -> the pair's entry in its first vehicle's row and in its second's, (n, pairs, k) each
-        x = x.reshape(n, m * (m - 1), k)
-        return x[:, at_first, :], x[:, at_second, :]
-
-    return slots, delay, t_first, tau, per_pair, through
-
-
-def _fleet_gaps(fleet, tau, per_pair):
-    gaps = []
-    for s in fleet:
-        pos = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
-        _trajectory_launch(capi.trajectory_eval, tau.device, s, tau, pos, None, None)
-        pos_first, pos_second = per_pair(pos)
-        gaps.append(pos_first - pos_second)
-    return gaps
 
 
 class _TrajectoryStaggeredSeparation(torch.autograd.Function):
@@ -1724,80 +1764,49 @@ class _TrajectoryStaggeredSeparation(torch.autograd.Function):
 
     @staticmethod
     def forward(d, m, *inputs):
-        fleet = [_dense(t) for t in inputs[:8 * d]]
         start, lo, hi = (_dense(t) for t in inputs[8 * d:])
         given = lo if lo is not None else hi
         n = start.shape[0]
         k = given.shape[1] if given is not None else 1
-        device = inputs[0].device
-        value, time, local = (torch.empty((n, m * (m - 1) // 2, k), dtype=torch.float64, device=device) for _ in range(3))
-        with torch.cuda.device(device):      # as _trajectory_launch
-            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_fleet_separation_staggered(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d,
-                                                       [addr(t) for t in fleet], addr(start), addr(lo), addr(hi), addr(value), addr(time),
-                                                       addr(local))
-        return value, time, local
+        return _fleet_forward(capi.trajectory_fleet_separation_staggered, d, m, inputs, n, k, 3,
+                              lambda addr: (addr(start), addr(lo), addr(hi)))
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(output[1], output[2])
-        ctx.d, ctx.m = inputs[0], inputs[1]
-        ctx.given = [t is not None for t in inputs[2:]]
-        kept = [t for t in inputs[2:] if t is not None] + [output[0], output[2]]
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _fleet_setup(ctx, inputs, 8 * inputs[0] + 3, output[1:], (output[0], output[2]))
 
     @staticmethod
     def _saved(ctx):
+        """_TrajectoryFleetSeparation._saved's, the times the local ones, with the class mask START after the others"""
         d, m = ctx.d, ctx.m
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        value, local = list(kept)
-        fleet = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
-        start, lo, hi = inputs[8 * d:]
-        n = start.shape[0]
+        fleet, (start, lo, hi), (value, local) = _fleet_kept(ctx)
         missing = torch.isnan(value) | torch.isnan(local)
-        slots, delay, t, tau, per_pair, through = _staggered_times(m, start, local, missing)
-        first, second = slots[4], slots[5]
+        at = _fleet_times(m, local, missing, start)
+        first, second = at.slots[4], at.slots[5]
         s_first = start[:, first].unsqueeze(2)
-        ends = [(s[6] + s[7]).reshape(n, m) for s in fleet]
+        ends = [(s[6] + s[7]).reshape(-1, m) for s in fleet]
         tests = [lo.unsqueeze(1) - s_first if lo is not None else None, hi.unsqueeze(1) - s_first if hi is not None else None]
-        tests += [e[:, first].unsqueeze(2) for e in ends] + [delay + e[:, second].unsqueeze(2) for e in ends] + [delay]
-        masks, taken = [], missing
-        for at, ref in enumerate(tests):
-            mask = (t == ref) & ~taken if ref is not None else torch.zeros_like(missing)
-            if at == len(tests) - 1:
-                mask = mask & (delay > 0)      # a start clamped to +0.0 is a constant
-            masks.append(mask)
-            taken = taken | mask
-        gaps = _fleet_gaps(fleet, tau, per_pair)
-        return fleet, slots, tau, missing, gaps, per_pair, through, (masks[0], masks[1], masks[2:2 + d], masks[2 + d:2 + 2 * d], masks[-1])
+        tests += [e[:, first].unsqueeze(2) for e in ends] + [at.delay + e[:, second].unsqueeze(2) for e in ends] + [at.delay]
+        masks = _class_masks(at.t, missing, tests, at.delay > 0)      # a start clamped to +0.0 is a constant
+        return fleet, at, missing, _fleet_gaps(fleet, at), (masks[0], masks[1], masks[2:2 + d], masks[2 + d:2 + 2 * d], masks[-1])
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_value, _g_time, _g_local):
-        d, m = ctx.d, ctx.m
+        d = ctx.d
         if g_value is None:
             return (None,) * (8 * d + 5)
-        fleet, slots, tau, missing, gaps, per_pair, through, (is_lo, is_hi, end_first, end_second, is_start) = _TrajectoryStaggeredSeparation._saved(ctx)
-        sign = slots[1]
-        n, pairs, k = missing.shape
+        fleet, at, missing, gaps, (is_lo, is_hi, end_first, end_second, is_start) = _TrajectoryStaggeredSeparation._saved(ctx)
         g = torch.where(missing, torch.zeros_like(g_value), g_value)      # a NaN value: gradient 0
         need = ctx.needs_input_grad[2:]
         want_time = any(need[8 * c + 6] or need[8 * c + 7] for c in range(d)) or any(need[8 * d:])
-        signs = sign.reshape(1, m, m - 1, 1)
-        bars, time_bar, shift_bar = [None] * (8 * d), None, None
-        for c in range(d):
-            g_pos = torch.where(missing, torch.zeros_like(g), (2.0 * g) * gaps[c])      # (a bad vehicle's gap is NaN: not into its partners)
-            upstream = (signs * through(g_pos)).reshape(tau.shape).contiguous()
-            bar = [torch.empty(n * m, dtype=torch.float64, device=tau.device) if need[8 * c + f] else None for f in range(8)]
-            tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if want_time else None
-            if want_time or any(x is not None for x in bar):
-                _trajectory_launch(capi.trajectory_eval_vjp, tau.device, fleet[c], tau, upstream, None, None, bar, tau_bar)
-            bars[8 * c:8 * c + 8] = bar
+        # (a bad vehicle's gap is NaN: not into its partners)
+        g_gap = lambda c: torch.where(missing, torch.zeros_like(g), (2.0 * g) * gaps[c])      # noqa: E731
+        bars, time_bar, shift_bar = [], None, None
+        for bar, tau_bar in _fleet_vjp(fleet, at, need, want_time, g_gap):
+            bars += bar
             if want_time:      # the pair's: its two vehicles', added in _TrajectorySeparation's order -- the same bits per pair and query
-                share_first, share_second = per_pair(tau_bar)
+                share_first, share_second = at.per_pair(tau_bar)
                 time_bar = share_first if time_bar is None else time_bar + share_first
                 time_bar = time_bar + share_second
                 shift_bar = share_second if shift_bar is None else shift_bar + share_second
@@ -1805,12 +1814,7 @@ class _TrajectoryStaggeredSeparation(torch.autograd.Function):
         if want_time:
             zero = torch.zeros_like(time_bar)
             routed = lambda mask: torch.where(mask, time_bar, zero)      # noqa: E731
-            for c in range(d):
-                if need[8 * c + 6] or need[8 * c + 7]:      # a vehicle's pairs: through the slot table, then a plain sum
-                    mine = torch.where(signs > 0, through(routed(end_first[c])), through(routed(end_second[c]))).sum(dim=(2, 3)).reshape(n * m)
-                    for f in (6, 7):
-                        if need[8 * c + f]:
-                            bars[8 * c + f] = bars[8 * c + f] + mine
+            _route_end_bars(bars, need, at, routed, end_first, end_second)
             lo_pair, hi_pair = routed(is_lo), routed(is_hi)
             if need[8 * d + 1]:
                 lo_bar = lo_pair.sum(dim=1)
@@ -1821,17 +1825,16 @@ class _TrajectoryStaggeredSeparation(torch.autograd.Function):
                 for mask in end_second:
                     holds = holds | mask
                 delay_bar = routed(holds) - shift_bar
-                start_bar = torch.where(signs > 0, through(-((delay_bar + lo_pair) + hi_pair)), through(delay_bar)).sum(dim=(2, 3))
+                start_bar = torch.where(at.signs > 0, at.through(-((delay_bar + lo_pair) + hi_pair)), at.through(delay_bar)).sum(dim=(2, 3))
         return (None, None) + tuple(bars) + (start_bar, lo_bar, hi_bar)
 
     @staticmethod
     def jvp(ctx, _t_d, _t_m, *tangents):
         d, m = ctx.d, ctx.m
-        fleet, slots, tau, missing, gaps, per_pair, through, (is_lo, is_hi, end_first, end_second, is_start) = _TrajectoryStaggeredSeparation._saved(ctx)
-        sign, first, second = slots[1], slots[4], slots[5]
-        n, pairs, k = missing.shape
+        fleet, at, missing, gaps, (is_lo, is_hi, end_first, end_second, is_start) = _TrajectoryStaggeredSeparation._saved(ctx)
+        first, second = at.slots[4], at.slots[5]
         dots = [_dense(t) for t in tangents[:8 * d]]
-        zero = torch.zeros(missing.shape, dtype=torch.float64, device=tau.device)
+        zero = torch.zeros(missing.shape, dtype=torch.float64, device=at.tau.device)
         wide = lambda t: t.unsqueeze(1) if t is not None else zero      # noqa: E731
         start_dot = tangents[8 * d]
         first_dot = start_dot[:, first].unsqueeze(2) if start_dot is not None else zero
@@ -1843,17 +1846,13 @@ class _TrajectoryStaggeredSeparation(torch.autograd.Function):
                 total = shift
                 for t in (dots[8 * c + 6], dots[8 * c + 7]):
                     if t is not None:
-                        total = total + t.reshape(n, m)[:, which].unsqueeze(2)
+                        total = total + t.reshape(-1, m)[:, which].unsqueeze(2)
                 time_dot = torch.where(ends[c], total, time_dot)
         time_dot = torch.where(is_start, delay_dot, time_dot)
-        signs = sign.reshape(1, m, m - 1, 1)
-        tau_dot = torch.where(signs > 0, through(time_dot), through(time_dot - delay_dot)).reshape(tau.shape).contiguous()
+        tau_dot = torch.where(at.signs > 0, at.through(time_dot), at.through(time_dot - delay_dot)).reshape(at.tau.shape).contiguous()
         value_dot = zero
-        for c in range(d):
-            pos_dot = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
-            _trajectory_launch(capi.trajectory_eval_jvp, tau.device, fleet[c], tau, dots[8 * c:8 * c + 8], tau_dot, pos_dot, None, None)
-            dot_first, dot_second = per_pair(pos_dot)
-            value_dot = value_dot + (2.0 * gaps[c]) * (dot_first - dot_second)
+        for share in _fleet_jvp(fleet, at, gaps, dots, tau_dot):
+            value_dot = value_dot + share
         return torch.where(missing, torch.full_like(zero, float("nan")), value_dot), None, None
 
 
@@ -1868,6 +1867,50 @@ def _check_fleet_start(n, m, start, who):
 def _check_fleet_start_device(start, device, who):
     if start.device != device:
         raise TypeError("%s: start is on %s; it must be on the fleet's device %s" % (who, start.device, device))
+
+
+def _check_fleet_arguments(n, m, device, start, queries, who):
+    """What comes after the fleet's own shapes and types: start's shape and type, queries() -- the checks of the windows (and the level),
+    whose result is returned --, then start's device."""
+    if start is not None:
+        _check_fleet_start(n, m, start, who)
+    checked = queries()
+    if start is not None:
+        _check_fleet_start_device(start, device, who)
+    return checked
+
+
+def _check_fleet_problem(pos, vel, synchronize, who):
+    """pos and vel of a fleet pipeline, shapes and types; returns (n, m, d)."""
+    if synchronize and vel is not None:
+        raise ValueError(who + ": synchronize=True needs rest-to-rest vehicles; pass synchronize=False with end velocities")
+    if not isinstance(pos, (list, tuple)) or len(pos) != 3:
+        raise TypeError("%s: pos must be a list or tuple of three tensors (pos0, pos1, pos2)" % who)
+    if vel is not None and (not isinstance(vel, (list, tuple)) or len(vel) != 2):
+        raise TypeError("%s: vel must be None or a pair (vel0, vel2)" % who)
+    for name, t in [("pos", t) for t in pos] + [("vel", v) for v in (vel or ()) if v is not None]:
+        _check_is_tensor(name, t, who)
+        if t.dim() != 3 or t.shape != pos[0].shape or not 1 <= t.shape[2] <= 3:
+            raise ValueError("%s: every tensor must have one shape (n, m, d) with d in 1..3, got %s" % (who, tuple(t.shape)))
+    n, m, d = pos[0].shape
+    _check_fleet_size(int(m), who)
+    return n, int(m), d
+
+
+def _solve_fleet(pos, vel, synchronize, gap_tol, max_iter, params):
+    """One min_time_solve over the n m d axis problems of a fleet: (the fleet as trajectory_fleet_separation takes it, stretched where
+    synchronize; the solution as (n, m, d), as the solve left it)"""
+    n, m, d = pos[0].shape
+    flat = lambda t: t.reshape(-1) if t is not None else None      # noqa: E731
+    vel0, vel2 = (flat(v) for v in vel) if vel is not None else (None, None)
+    solution = min_time_solve(*[flat(t) for t in pos], gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
+    spline = list(pos) + [t.reshape(n, m, d) for t in solution[:3]]
+    if synchronize:
+        spline, _ = synchronize_axes([t.reshape(n * m, d) for t in spline])
+        spline = [t.reshape(n, m, d) for t in spline]
+    elif vel is not None:
+        spline = spline + list(vel)
+    return spline, tuple(t.reshape(n, m, d) for t in solution)
 
 
 def _check_fleet(fleet, who):
@@ -1950,11 +1993,7 @@ def trajectory_fleet_separation(fleet, lo=None, hi=None, *, start=None):
     for its delay, lo and hi.  start=None is the call without it: the same launches and the same bits."""
     who = "trajectory_fleet_separation"
     n, m, d, tables = _check_fleet(fleet, who)
-    if start is not None:
-        _check_fleet_start(n, m, start, who)
-    lo, hi = _check_fleet_windows(n, fleet[0].device, lo, hi, who)
-    if start is not None:
-        _check_fleet_start_device(start, fleet[0].device, who)
+    lo, hi = _check_fleet_arguments(n, m, fleet[0].device, start, lambda: _check_fleet_windows(n, fleet[0].device, lo, hi, who), who)
     _check_fleet_devices(fleet, who)
     if start is None:
         return _TrajectoryFleetSeparation.apply(d, m, *[t for table in tables for t in table], lo, hi)
@@ -1970,33 +2009,11 @@ def min_time_fleet_separation(pos, lo=None, hi=None, *, vel=None, synchronize=Tr
     composition: sep_sq is differentiable to first order in the positions, the end velocities, lo and hi, in both modes.  start= (n, m):
     trajectory_fleet_separation's start times, checked before the solve and differentiable like lo and hi."""
     who = "min_time_fleet_separation"
-    if synchronize and vel is not None:
-        raise ValueError(who + ": synchronize=True needs rest-to-rest vehicles; pass synchronize=False with end velocities")
-    if not isinstance(pos, (list, tuple)) or len(pos) != 3:
-        raise TypeError("%s: pos must be a list or tuple of three tensors (pos0, pos1, pos2)" % who)
-    if vel is not None and (not isinstance(vel, (list, tuple)) or len(vel) != 2):
-        raise TypeError("%s: vel must be None or a pair (vel0, vel2)" % who)
-    for name, t in [("pos", t) for t in pos] + [("vel", v) for v in (vel or ()) if v is not None]:
-        _check_is_tensor(name, t, who)
-        if t.dim() != 3 or t.shape != pos[0].shape or not 1 <= t.shape[2] <= 3:
-            raise ValueError("%s: every tensor must have one shape (n, m, d) with d in 1..3, got %s" % (who, tuple(t.shape)))
-    n, m, d = pos[0].shape
-    _check_fleet_size(int(m), who)
-    if start is not None:
-        _check_fleet_start(n, int(m), start, who)
-    lo, hi = _check_fleet_windows(n, pos[0].device, lo, hi, who)      # before the solve: a bad query costs none
-    if start is not None:
-        _check_fleet_start_device(start, pos[0].device, who)
-    flat = lambda t: t.reshape(-1) if t is not None else None      # noqa: E731
-    vel0, vel2 = (flat(v) for v in vel) if vel is not None else (None, None)
-    solution = min_time_solve(*[flat(t) for t in pos], gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
-    spline = list(pos) + [t.reshape(n, m, d) for t in solution[:3]]
-    if synchronize:
-        spline, _ = synchronize_axes([t.reshape(n * m, d) for t in spline])
-        spline = [t.reshape(n, m, d) for t in spline]
-    elif vel is not None:
-        spline = spline + list(vel)
-    return tuple(trajectory_fleet_separation(spline, lo, hi, start=start)) + (tuple(t.reshape(n, m, d) for t in solution),)
+    n, m, d = _check_fleet_problem(pos, vel, synchronize, who)
+    # before the solve: a bad query costs none
+    lo, hi = _check_fleet_arguments(n, m, pos[0].device, start, lambda: _check_fleet_windows(n, pos[0].device, lo, hi, who), who)
+    spline, solution = _solve_fleet(pos, vel, synchronize, gap_tol, max_iter, params)
+    return tuple(trajectory_fleet_separation(spline, lo, hi, start=start)) + (solution,)
 
 
 # ---- when two vehicles moving in several axes first come within a distance ----
@@ -2164,112 +2181,76 @@ def min_time_contact(pos_a, pos_b, radius=None, lo=None, hi=None, delay=None, *,
 
 
 # ---- the first contact of every pair of a fleet ----
+def _fleet_level(level):
+    """(the level as the entry reads it, whether it is one per pair): (n, k) or (n, pairs, k)"""
+    per_pair = level.dim() == 3
+    if per_pair and _plain(level).data_ptr() % 16:      # a view that starts in the middle of a 16-byte vector
+        level = level.clone()
+    return level, per_pair
+
+
+def _level_bar(ctx, w):
+    return w if ctx.per_pair else w.sum(dim=1)
+
+
+def _level_dot(ctx, level_dot, rate):
+    if level_dot is None:
+        return torch.zeros_like(rate)
+    return level_dot if ctx.per_pair else level_dot.unsqueeze(1)
+
+
 class _TrajectoryFleetContact(torch.autograd.Function):
     """(time, rate), (n, pairs, k) each, of the first time in the scene's window at which a pair's squared distance is at the level.  Inputs:
-    d, m, the fleet's 8 d tensors as _TrajectoryFleetSeparation takes them, level_sq -- (n, k): one level for all pairs of a scene, or
-    (n, pairs, k): one per pair --, lo, hi (n, k).  The time is differentiable to first order in all 8 d fleet inputs and the level by
-    _TrajectoryContact's implicit-function formula, d time = (d level - sum of 2 D_c (d pos_first,c - d pos_second,c)) / rate, routed per
-    vehicle as _TrajectoryFleetSeparation routes: the times gathered through the slot table to (n m, (m - 1) k), per axis one evaluator
-    launch and one launch of its derivative on the n m splines.  lo and hi only choose the branch.  rate is for the
-    backward and is not differentiable."""
+    d, m, the fleet's 8 d tensors, level_sq -- (n, k): one level for all pairs of a scene, or (n, pairs, k): one per pair --, lo, hi
+    (n, k).  The time is differentiable to first order in all 8 d fleet inputs and the level by _TrajectoryContact's implicit-function
+    formula, d time = (d level - sum of 2 D_c (d pos_first,c - d pos_second,c)) / rate, routed per vehicle.  lo and
+    hi only choose the branch.  rate is for the backward and is not differentiable."""
 
     @staticmethod
     def forward(d, m, *inputs):
-        fleet = [_dense(t) for t in inputs[:8 * d]]
         level, lo, hi = (_dense(t) for t in inputs[8 * d:])
-        per_pair = level.dim() == 3
-        if per_pair and _plain(level).data_ptr() % 16:      # a view that starts in the middle of a 16-byte vector
-            level = level.clone()
-        n, k = level.shape[0], level.shape[-1]
-        device = inputs[0].device
-        time, rate = (torch.empty((n, m * (m - 1) // 2, k), dtype=torch.float64, device=device) for _ in range(2))
-        with torch.cuda.device(device):      # as _trajectory_launch
-            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_fleet_contact(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in fleet],
-                                          addr(level), int(per_pair), addr(lo), addr(hi), addr(time), addr(rate))
-        return time, rate
+        level, per_pair = _fleet_level(level)
+        return _fleet_forward(capi.trajectory_fleet_contact, d, m, inputs, level.shape[0], level.shape[-1], 2,
+                              lambda addr: (addr(level), int(per_pair), addr(lo), addr(hi)))
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(output[1])
-        d, ctx.m = inputs[0], inputs[1]
-        ctx.d = d
+        d = inputs[0]
         ctx.per_pair = inputs[2 + 8 * d].dim() == 3
-        ctx.given = [t is not None for t in inputs[2:2 + 8 * d]]      # neither derivative reads the level, lo or hi
-        kept = [t for t in inputs[2:2 + 8 * d] if t is not None] + list(output)
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _fleet_setup(ctx, inputs, 8 * d, output[1:], output)      # neither derivative reads the level, lo or hi
 
     @staticmethod
     def _saved(ctx):
-        """(the d lists of eight tensors; the slot tables; the times through the slot table, 0 where there is no contact,
-        (n m, (m - 1) k); rate; where there is no contact, (n, pairs, k); the d gaps D_c there; a pair's view of a per-slot array)"""
-        d, m = ctx.d, ctx.m
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        time, rate = list(kept)
-        fleet = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
-        n, pairs, k = time.shape
-        slots = _fleet_slots_on(m, time.device)
-        pair, _, at_first, at_second, _, _ = slots
+        """(the d lists of eight tensors; _fleet_times; rate; where there is no contact, (n, pairs, k); the d gaps D_c)"""
+        fleet, _, (time, rate) = _fleet_kept(ctx)
         missing = torch.isnan(time)
-        t = torch.where(missing, torch.zeros_like(time), time)
-        tau = t[:, pair.reshape(-1), :].reshape(n * m, (m - 1) * k).contiguous()
-
-        def per_pair(x):      # (n m, (m - 1) k) -> the pair's entry in its first vehicle's row and in its second's, (n, pairs, k) each
-            x = x.reshape(n, m * (m - 1), k)
-            return x[:, at_first, :], x[:, at_second, :]
-
-        gaps = []
-        for s in fleet:
-            pos = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
-            _trajectory_launch(capi.trajectory_eval, tau.device, s, tau, pos, None, None)
-            pos_first, pos_second = per_pair(pos)
-            gaps.append(pos_first - pos_second)
-        return fleet, slots, tau, rate, missing, gaps, per_pair
+        at = _fleet_times(ctx.m, time, missing)
+        return fleet, at, rate, missing, _fleet_gaps(fleet, at)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_time, _g_rate):
-        d, m = ctx.d, ctx.m
+        d = ctx.d
         if g_time is None:
             return (None,) * (8 * d + 5)
-        fleet, (pair, sign, _, _, _, _), tau, rate, missing, gaps, _ = _TrajectoryFleetContact._saved(ctx)
-        n, pairs, k = missing.shape
+        fleet, at, rate, missing, gaps = _TrajectoryFleetContact._saved(ctx)
         need = ctx.needs_input_grad[2:]
         zero = torch.zeros_like(rate)
         w = torch.where(missing, zero, g_time / rate)      # an unreached level: gradient 0
-        through = lambda x: x[:, pair.reshape(-1), :].reshape(n, m, m - 1, k)      # noqa: E731  (n, pairs, k) -> per vehicle and slot
-        signs = sign.reshape(1, m, m - 1, 1)
-        bars = [None] * (8 * d)
-        for c in range(d):
-            bar = [torch.empty(n * m, dtype=torch.float64, device=tau.device) if need[8 * c + f] else None for f in range(8)]
-            if any(x is not None for x in bar):
-                g_pos = torch.where(missing, zero, -((2.0 * w) * gaps[c]))      # (a bad vehicle's gap is NaN: not into its partners)
-                upstream = (signs * through(g_pos)).reshape(tau.shape).contiguous()
-                _trajectory_launch(capi.trajectory_eval_vjp, tau.device, fleet[c], tau, upstream, None, None, bar, None)
-            bars[8 * c:8 * c + 8] = bar
-        level_bar = None
-        if need[8 * d]:
-            level_bar = w if ctx.per_pair else w.sum(dim=1)
+        # (a bad vehicle's gap is NaN: not into its partners)
+        g_gap = lambda c: torch.where(missing, zero, -((2.0 * w) * gaps[c]))      # noqa: E731
+        bars = [x for bar, _ in _fleet_vjp(fleet, at, need, False, g_gap) for x in bar]
+        level_bar = _level_bar(ctx, w) if need[8 * d] else None
         return (None, None) + tuple(bars) + (level_bar, None, None)
 
     @staticmethod
     def jvp(ctx, _t_d, _t_m, *tangents):
         d = ctx.d
-        fleet, _, tau, rate, missing, gaps, per_pair = _TrajectoryFleetContact._saved(ctx)
+        fleet, at, rate, missing, gaps = _TrajectoryFleetContact._saved(ctx)
         dots = [_dense(t) for t in tangents[:8 * d]]
-        level_dot = tangents[8 * d]
-        if level_dot is None:
-            total = torch.zeros_like(rate)
-        else:
-            total = level_dot if ctx.per_pair else level_dot.unsqueeze(1)
-        for c in range(d):
-            pos_dot = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
-            _trajectory_launch(capi.trajectory_eval_jvp, tau.device, fleet[c], tau, dots[8 * c:8 * c + 8], None, pos_dot, None, None)
-            dot_first, dot_second = per_pair(pos_dot)
-            total = total - (2.0 * gaps[c]) * (dot_first - dot_second)
+        total = _level_dot(ctx, tangents[8 * d], rate)
+        for share in _fleet_jvp(fleet, at, gaps, dots, None):
+            total = total - share
         return torch.where(missing, torch.full_like(rate, float("nan")), total / rate), None
 
 
@@ -2283,97 +2264,65 @@ class _TrajectoryStaggeredContact(torch.autograd.Function):
 
     @staticmethod
     def forward(d, m, *inputs):
-        fleet = [_dense(t) for t in inputs[:8 * d]]
         start, level, lo, hi = (_dense(t) for t in inputs[8 * d:])
-        per_pair = level.dim() == 3
-        if per_pair and _plain(level).data_ptr() % 16:      # a view that starts in the middle of a 16-byte vector
-            level = level.clone()
-        n, k = level.shape[0], level.shape[-1]
-        device = inputs[0].device
-        time, local, rate = (torch.empty((n, m * (m - 1) // 2, k), dtype=torch.float64, device=device) for _ in range(3))
-        with torch.cuda.device(device):      # as _trajectory_launch
-            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_fleet_contact_staggered(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d,
-                                                    [addr(t) for t in fleet], addr(start), addr(level), int(per_pair), addr(lo), addr(hi),
-                                                    addr(time), addr(local), addr(rate))
-        return time, local, rate
+        level, per_pair = _fleet_level(level)
+        return _fleet_forward(capi.trajectory_fleet_contact_staggered, d, m, inputs, level.shape[0], level.shape[-1], 3,
+                              lambda addr: (addr(start), addr(level), int(per_pair), addr(lo), addr(hi)))
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(output[1], output[2])
-        d, ctx.m = inputs[0], inputs[1]
-        ctx.d = d
+        d = inputs[0]
         ctx.per_pair = inputs[3 + 8 * d].dim() == 3
-        ctx.given = [t is not None for t in inputs[2:2 + 8 * d]]      # neither derivative reads the level, lo or hi
-        kept = [t for t in inputs[2:2 + 8 * d] if t is not None] + [inputs[2 + 8 * d], output[1], output[2]]
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _fleet_setup(ctx, inputs, 8 * d, output[1:], (inputs[2 + 8 * d], output[1], output[2]))      # as _TrajectoryFleetContact, and the start
 
     @staticmethod
     def _saved(ctx):
-        d, m = ctx.d, ctx.m
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        start, local, rate = list(kept)
-        fleet = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
+        fleet, _, (start, local, rate) = _fleet_kept(ctx)
         missing = torch.isnan(local)
-        slots, _, _, tau, per_pair, through = _staggered_times(m, start, local, missing)
-        return fleet, slots, tau, rate, missing, _fleet_gaps(fleet, tau, per_pair), per_pair, through
+        at = _fleet_times(ctx.m, local, missing, start)
+        return fleet, at, rate, missing, _fleet_gaps(fleet, at)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_time, _g_local, _g_rate):
-        d, m = ctx.d, ctx.m
+        d = ctx.d
         if g_time is None:
             return (None,) * (8 * d + 6)
-        fleet, slots, tau, rate, missing, gaps, per_pair, through = _TrajectoryStaggeredContact._saved(ctx)
-        n, pairs, k = missing.shape
+        fleet, at, rate, missing, gaps = _TrajectoryStaggeredContact._saved(ctx)
         need = ctx.needs_input_grad[2:]
         zero = torch.zeros_like(rate)
         own = torch.where(missing, zero, g_time)      # time = t' + start_i
         w = torch.where(missing, zero, g_time / rate)      # an unreached level: gradient 0
-        signs = slots[1].reshape(1, m, m - 1, 1)
-        bars, delay_bar = [None] * (8 * d), None
-        for c in range(d):
-            bar = [torch.empty(n * m, dtype=torch.float64, device=tau.device) if need[8 * c + f] else None for f in range(8)]
-            tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if need[8 * d] else None
-            if tau_bar is not None or any(x is not None for x in bar):
-                g_pos = torch.where(missing, zero, -((2.0 * w) * gaps[c]))      # (a bad vehicle's gap is NaN: not into its partners)
-                upstream = (signs * through(g_pos)).reshape(tau.shape).contiguous()
-                _trajectory_launch(capi.trajectory_eval_vjp, tau.device, fleet[c], tau, upstream, None, None, bar, tau_bar)
-            bars[8 * c:8 * c + 8] = bar
+        # (a bad vehicle's gap is NaN: not into its partners)
+        g_gap = lambda c: torch.where(missing, zero, -((2.0 * w) * gaps[c]))      # noqa: E731
+        bars, delay_bar = [], None
+        for bar, tau_bar in _fleet_vjp(fleet, at, need, need[8 * d], g_gap):
+            bars += bar
             if tau_bar is not None:      # the second vehicle is at t' - delay
-                share = per_pair(tau_bar)[1]
+                share = at.per_pair(tau_bar)[1]
                 delay_bar = -share if delay_bar is None else delay_bar - share
         start_bar = level_bar = None
         if need[8 * d]:
-            start_bar = torch.where(signs > 0, through(own - delay_bar), through(delay_bar)).sum(dim=(2, 3))
+            start_bar = torch.where(at.signs > 0, at.through(own - delay_bar), at.through(delay_bar)).sum(dim=(2, 3))
         if need[8 * d + 1]:
-            level_bar = w if ctx.per_pair else w.sum(dim=1)
+            level_bar = _level_bar(ctx, w)
         return (None, None) + tuple(bars) + (start_bar, level_bar, None, None)
 
     @staticmethod
     def jvp(ctx, _t_d, _t_m, *tangents):
-        d, m = ctx.d, ctx.m
-        fleet, slots, tau, rate, missing, gaps, per_pair, through = _TrajectoryStaggeredContact._saved(ctx)
-        sign, first, second = slots[1], slots[4], slots[5]
+        d = ctx.d
+        fleet, at, rate, missing, gaps = _TrajectoryStaggeredContact._saved(ctx)
+        first, second = at.slots[4], at.slots[5]
         dots = [_dense(t) for t in tangents[:8 * d]]
-        start_dot, level_dot = tangents[8 * d], tangents[8 * d + 1]
-        zero = torch.zeros_like(rate)
-        if level_dot is None:
-            total = zero
-        else:
-            total = level_dot if ctx.per_pair else level_dot.unsqueeze(1)
+        start_dot = tangents[8 * d]
+        total = _level_dot(ctx, tangents[8 * d + 1], rate)
         tau_dot = None
         if start_dot is not None:      # the second vehicle's time moves against the delay
+            zero = torch.zeros_like(rate)
             delay_dot = (start_dot[:, second] - start_dot[:, first]).unsqueeze(2) + zero
-            tau_dot = torch.where(sign.reshape(1, m, m - 1, 1) > 0, through(zero), through(-delay_dot)).reshape(tau.shape).contiguous()
-        for c in range(d):
-            pos_dot = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
-            _trajectory_launch(capi.trajectory_eval_jvp, tau.device, fleet[c], tau, dots[8 * c:8 * c + 8], tau_dot, pos_dot, None, None)
-            dot_first, dot_second = per_pair(pos_dot)
-            total = total - (2.0 * gaps[c]) * (dot_first - dot_second)
+            tau_dot = torch.where(at.signs > 0, at.through(zero), at.through(-delay_dot)).reshape(at.tau.shape).contiguous()
+        for share in _fleet_jvp(fleet, at, gaps, dots, tau_dot):
+            total = total - share
         time_dot = total / rate
         if start_dot is not None:
             time_dot = time_dot + start_dot[:, first].unsqueeze(2)
@@ -2433,11 +2382,8 @@ def trajectory_fleet_contact(fleet, radius=None, lo=None, hi=None, *, level_sq=N
     if (radius is None) == (level_sq is None):
         raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
     n, m, d, tables = _check_fleet(fleet, who)
-    if start is not None:
-        _check_fleet_start(n, m, start, who)
-    level, lo, hi = _check_fleet_queries(n, m, fleet[0].device, radius, level_sq, lo, hi, who)
-    if start is not None:
-        _check_fleet_start_device(start, fleet[0].device, who)
+    level, lo, hi = _check_fleet_arguments(n, m, fleet[0].device, start,
+                                           lambda: _check_fleet_queries(n, m, fleet[0].device, radius, level_sq, lo, hi, who), who)
     _check_fleet_devices(fleet, who)
     if start is None:
         return _TrajectoryFleetContact.apply(d, m, *[t for table in tables for t in table], level, lo, hi)[0]
@@ -2453,33 +2399,12 @@ def min_time_fleet_contact(pos, radius=None, lo=None, hi=None, *, level_sq=None,
     who = "min_time_fleet_contact"
     if (radius is None) == (level_sq is None):
         raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
-    if synchronize and vel is not None:
-        raise ValueError(who + ": synchronize=True needs rest-to-rest vehicles; pass synchronize=False with end velocities")
-    if not isinstance(pos, (list, tuple)) or len(pos) != 3:
-        raise TypeError("%s: pos must be a list or tuple of three tensors (pos0, pos1, pos2)" % who)
-    if vel is not None and (not isinstance(vel, (list, tuple)) or len(vel) != 2):
-        raise TypeError("%s: vel must be None or a pair (vel0, vel2)" % who)
-    for name, t in [("pos", t) for t in pos] + [("vel", v) for v in (vel or ()) if v is not None]:
-        _check_is_tensor(name, t, who)
-        if t.dim() != 3 or t.shape != pos[0].shape or not 1 <= t.shape[2] <= 3:
-            raise ValueError("%s: every tensor must have one shape (n, m, d) with d in 1..3, got %s" % (who, tuple(t.shape)))
-    n, m, d = pos[0].shape
-    _check_fleet_size(int(m), who)
-    if start is not None:
-        _check_fleet_start(n, int(m), start, who)
-    level, lo, hi = _check_fleet_queries(n, int(m), pos[0].device, radius, level_sq, lo, hi, who)      # before the solve: a bad query costs none
-    if start is not None:
-        _check_fleet_start_device(start, pos[0].device, who)
-    flat = lambda t: t.reshape(-1) if t is not None else None      # noqa: E731
-    vel0, vel2 = (flat(v) for v in vel) if vel is not None else (None, None)
-    solution = min_time_solve(*[flat(t) for t in pos], gap_tol=gap_tol, max_iter=max_iter, params=params, vel0=vel0, vel2=vel2)
-    spline = list(pos) + [t.reshape(n, m, d) for t in solution[:3]]
-    if synchronize:
-        spline, _ = synchronize_axes([t.reshape(n * m, d) for t in spline])
-        spline = [t.reshape(n, m, d) for t in spline]
-    elif vel is not None:
-        spline = spline + list(vel)
-    return trajectory_fleet_contact(spline, None, lo, hi, level_sq=level, start=start), tuple(t.reshape(n, m, d) for t in solution)
+    n, m, d = _check_fleet_problem(pos, vel, synchronize, who)
+    # before the solve: a bad query costs none
+    level, lo, hi = _check_fleet_arguments(n, m, pos[0].device, start,
+                                           lambda: _check_fleet_queries(n, m, pos[0].device, radius, level_sq, lo, hi, who), who)
+    spline, solution = _solve_fleet(pos, vel, synchronize, gap_tol, max_iter, params)
+    return trajectory_fleet_contact(spline, None, lo, hi, level_sq=level, start=start), solution
 
 
 def fleet_first_contact(t_contact):

@@ -338,17 +338,23 @@ def trajectory_contact(device, stream, n, k, d, spline_a, spline_b, d_level_sq, 
                                                vp(d_level_sq), vp(d_lo), vp(d_hi), vp(d_delay), vp(d_time), vp(d_rate)))
 
 
+def _fleet_sizes(who, d, m):
+    """(d, m) as ints, refused here where the C entry would refuse them"""
+    d, m = int(d), int(m)
+    if not 1 <= d <= 3:
+        raise ValueError("%s: d must be 1, 2 or 3, got %d" % (who, d))
+    if not 2 <= m <= 256:
+        raise ValueError("%s: m must be 2..256 vehicles per scene, got %d" % (who, m))
+    return d, m
+
+
 def trajectory_fleet_separation(device, stream, n, m, k, d, fleet, d_lo=None, d_hi=None, d_value=None, d_time=None):
     """rp_trajectory_fleet_separation: trajectory_separation's two outputs, bit for bit with no delay, for every pair (i, j), i < j
     (lexicographic), of `n` scenes of `m` vehicles (2..256) of `d` axes (1..3) on one clock.  `fleet`: 8 d addresses, axis-major, each axis
     as for trajectory_eval, every array n m values with vehicle v of scene s at s m + v.  d_lo, d_hi: (n, k), the scene's windows for all
     its pairs (None / 0: -inf, +inf).  d_value, d_time: (n, m (m - 1) / 2, k) (None / 0: not wanted; not both)."""
     vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
-    d, m = int(d), int(m)
-    if not 1 <= d <= 3:
-        raise ValueError("trajectory_fleet_separation: d must be 1, 2 or 3, got %d" % d)
-    if not 2 <= m <= 256:
-        raise ValueError("trajectory_fleet_separation: m must be 2..256 vehicles per scene, got %d" % m)
+    d, m = _fleet_sizes("trajectory_fleet_separation", d, m)
     check(load_library().rp_trajectory_fleet_separation(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_lo), vp(d_hi),
                                                         vp(d_value), vp(d_time)))
 
@@ -360,11 +366,7 @@ def trajectory_fleet_contact(device, stream, n, m, k, d, fleet, d_level_sq, leve
     (level_per_pair 0), or (n, m (m - 1) / 2, k), 16-byte aligned (level_per_pair 1).  d_time (required), d_rate (None / 0: not wanted):
     (n, m (m - 1) / 2, k)."""
     vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
-    d, m = int(d), int(m)
-    if not 1 <= d <= 3:
-        raise ValueError("trajectory_fleet_contact: d must be 1, 2 or 3, got %d" % d)
-    if not 2 <= m <= 256:
-        raise ValueError("trajectory_fleet_contact: m must be 2..256 vehicles per scene, got %d" % m)
+    d, m = _fleet_sizes("trajectory_fleet_contact", d, m)
     check(load_library().rp_trajectory_fleet_contact(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_level_sq),
                                                      int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_time), vp(d_rate)))
 
@@ -376,11 +378,7 @@ def trajectory_fleet_separation_staggered(device, stream, n, m, k, d, fleet, d_s
     start_j - start_i over the window [lo - start_i, hi - start_i]; d_time_local is its time (vehicle i's clock), d_time that plus start_i.
     d_value, d_time, d_time_local: (n, m (m - 1) / 2, k) (None / 0: not wanted; not all three)."""
     vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
-    d, m = int(d), int(m)
-    if not 1 <= d <= 3:
-        raise ValueError("trajectory_fleet_separation_staggered: d must be 1, 2 or 3, got %d" % d)
-    if not 2 <= m <= 256:
-        raise ValueError("trajectory_fleet_separation_staggered: m must be 2..256 vehicles per scene, got %d" % m)
+    d, m = _fleet_sizes("trajectory_fleet_separation_staggered", d, m)
     check(load_library().rp_trajectory_fleet_separation_staggered(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_start),
                                                                   vp(d_lo), vp(d_hi), vp(d_value), vp(d_time), vp(d_time_local)))
 
@@ -392,11 +390,7 @@ def trajectory_fleet_contact_staggered(device, stream, n, m, k, d, fleet, d_star
     level; d_time_local is its time (vehicle i's clock), d_time that plus start_i, d_rate its rate.  The three outputs are
     (n, m (m - 1) / 2, k) (None / 0: not wanted; not all three)."""
     vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
-    d, m = int(d), int(m)
-    if not 1 <= d <= 3:
-        raise ValueError("trajectory_fleet_contact_staggered: d must be 1, 2 or 3, got %d" % d)
-    if not 2 <= m <= 256:
-        raise ValueError("trajectory_fleet_contact_staggered: m must be 2..256 vehicles per scene, got %d" % m)
+    d, m = _fleet_sizes("trajectory_fleet_contact_staggered", d, m)
     check(load_library().rp_trajectory_fleet_contact_staggered(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_start),
                                                                vp(d_level_sq), int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_time),
                                                                vp(d_time_local), vp(d_rate)))

@@ -1482,19 +1482,53 @@ int rp_trajectory_meeting(int device, void *stream, size_t n, size_t k, const do
     return RP_OK;
 }
 
+// What the two pair entries in d axes check first: the device, d, and the two tables of 8 d pointers, axis-major (A's before B's per axis).
+static int check_vehicles(const char *who, int device, int d, const double *const *d_spline_a, const double *const *d_spline_b)
+{
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", who, device);
+    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", who, d);
+    if (!d_spline_a) return fail(RP_ERR_INVALID, "%s: d_spline_a is null", who);
+    if (!d_spline_b) return fail(RP_ERR_INVALID, "%s: d_spline_b is null", who);
+    int st = RP_OK;
+    for (int x = 0; x < d && st == RP_OK; ++x) {
+        st = check_spline(who, "d_spline_a", d_spline_a + 8 * x);
+        if (st == RP_OK) st = check_spline(who, "d_spline_b", d_spline_b + 8 * x);
+    }
+    return st;
+}
+
+struct Required {
+    const char *name;
+    const void *given;
+};
+
+// What the four fleet entries check, in this order: the device, m, d, level_per_pair (null: the entry has none), the table of 8 d pointers,
+// the entry's own required arrays under their names, that n x pairs fits, and check_queries of the n x pairs x k arrays.
+static int check_fleet(const char *who, int device, size_t n, size_t m, size_t k, int d, const int *level_per_pair, const double *const *d_fleet,
+                       std::initializer_list<Required> required, std::initializer_list<const void *> per_query, bool any_output)
+{
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", who, device);
+    if (m < 2 || m > 256) return fail(RP_ERR_INVALID, "%s: m must be 2..256 vehicles per scene, got %zu", who, m);
+    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", who, d);
+    if (level_per_pair && *level_per_pair != 0 && *level_per_pair != 1)
+        return fail(RP_ERR_INVALID, "%s: level_per_pair must be 0 (n x k) or 1 (n x pairs x k), got %d", who, *level_per_pair);
+    if (!d_fleet) return fail(RP_ERR_INVALID, "%s: d_fleet is null", who);
+    for (int x = 0; x < d; ++x) {
+        const int st = check_spline(who, "d_fleet", d_fleet + 8 * x);
+        if (st != RP_OK) return st;
+    }
+    for (const Required &r : required)
+        if (!r.given) return fail(RP_ERR_INVALID, "%s: %s is null", who, r.name);
+    const size_t pairs = m * (m - 1) / 2;
+    if (n > SIZE_MAX / sizeof(double) / pairs) return fail(RP_ERR_INVALID, "%s: n x pairs does not fit", who);
+    return check_queries(who, n == 0 ? 0 : n * pairs, k, nullptr, nullptr, per_query, any_output);
+}
+
 // the least squared distance of two vehicles moving in d axes: two tables of 8 d pointers, axis-major; rp_trajectory_gap's argument rules
 int rp_trajectory_separation(int device, void *stream, size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b,
                              const double *d_lo, const double *d_hi, const double *d_delay, double *d_value, double *d_time)
 {
-    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
-    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
-    if (!d_spline_a) return fail(RP_ERR_INVALID, "%s: d_spline_a is null", __func__);
-    if (!d_spline_b) return fail(RP_ERR_INVALID, "%s: d_spline_b is null", __func__);
-    int st = RP_OK;
-    for (int x = 0; x < d && st == RP_OK; ++x) {
-        st = check_spline(__func__, "d_spline_a", d_spline_a + 8 * x);
-        if (st == RP_OK) st = check_spline(__func__, "d_spline_b", d_spline_b + 8 * x);
-    }
+    int st = check_vehicles(__func__, device, d, d_spline_a, d_spline_b);
     if (st == RP_OK) st = check_queries(__func__, n, k, nullptr, nullptr, {d_lo, d_hi, d_delay, d_value, d_time}, d_value || d_time);
     if (st != RP_OK) return st;
     RP_HIP(hipSetDevice(device));
@@ -1507,15 +1541,7 @@ int rp_trajectory_separation(int device, void *stream, size_t n, size_t k, int d
 int rp_trajectory_fleet_separation(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo,
                                    const double *d_hi, double *d_value, double *d_time)
 {
-    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
-    if (m < 2 || m > 256) return fail(RP_ERR_INVALID, "%s: m must be 2..256 vehicles per scene, got %zu", __func__, m);
-    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
-    if (!d_fleet) return fail(RP_ERR_INVALID, "%s: d_fleet is null", __func__);
-    int st = RP_OK;
-    for (int x = 0; x < d && st == RP_OK; ++x) st = check_spline(__func__, "d_fleet", d_fleet + 8 * x);
-    const size_t pairs = m * (m - 1) / 2;
-    if (st == RP_OK && n > SIZE_MAX / sizeof(double) / pairs) st = fail(RP_ERR_INVALID, "%s: n x pairs does not fit", __func__);
-    if (st == RP_OK) st = check_queries(__func__, n == 0 ? 0 : n * pairs, k, nullptr, nullptr, {d_value, d_time}, d_value || d_time);
+    const int st = check_fleet(__func__, device, n, m, k, d, nullptr, d_fleet, {}, {d_value, d_time}, d_value || d_time);
     if (st != RP_OK) return st;
     RP_HIP(hipSetDevice(device));
     RP_HIP(rp::launch_fleet_separation(n, m, k, d, d_fleet, d_lo, d_hi, d_value, d_time, (hipStream_t)stream));
@@ -1526,15 +1552,7 @@ int rp_trajectory_fleet_separation(int device, void *stream, size_t n, size_t m,
 int rp_trajectory_contact(int device, void *stream, size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b,
                           const double *d_level_sq, const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_rate)
 {
-    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
-    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
-    if (!d_spline_a) return fail(RP_ERR_INVALID, "%s: d_spline_a is null", __func__);
-    if (!d_spline_b) return fail(RP_ERR_INVALID, "%s: d_spline_b is null", __func__);
-    int st = RP_OK;
-    for (int x = 0; x < d && st == RP_OK; ++x) {
-        st = check_spline(__func__, "d_spline_a", d_spline_a + 8 * x);
-        if (st == RP_OK) st = check_spline(__func__, "d_spline_b", d_spline_b + 8 * x);
-    }
+    int st = check_vehicles(__func__, device, d, d_spline_a, d_spline_b);
     if (st == RP_OK && !d_time) st = fail(RP_ERR_INVALID, "%s: d_time is null", __func__);
     if (st == RP_OK) st = check_queries(__func__, n, k, d_level_sq, "d_level_sq", {d_lo, d_hi, d_delay, d_time, d_rate}, true);
     if (st != RP_OK) return st;
@@ -1548,19 +1566,8 @@ int rp_trajectory_contact(int device, void *stream, size_t n, size_t k, int d, c
 int rp_trajectory_fleet_contact(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq,
                                 int level_per_pair, const double *d_lo, const double *d_hi, double *d_time, double *d_rate)
 {
-    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
-    if (m < 2 || m > 256) return fail(RP_ERR_INVALID, "%s: m must be 2..256 vehicles per scene, got %zu", __func__, m);
-    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
-    if (level_per_pair != 0 && level_per_pair != 1)
-        return fail(RP_ERR_INVALID, "%s: level_per_pair must be 0 (n x k) or 1 (n x pairs x k), got %d", __func__, level_per_pair);
-    if (!d_fleet) return fail(RP_ERR_INVALID, "%s: d_fleet is null", __func__);
-    int st = RP_OK;
-    for (int x = 0; x < d && st == RP_OK; ++x) st = check_spline(__func__, "d_fleet", d_fleet + 8 * x);
-    const size_t pairs = m * (m - 1) / 2;
-    if (st == RP_OK && !d_level_sq) st = fail(RP_ERR_INVALID, "%s: d_level_sq is null", __func__);
-    if (st == RP_OK && !d_time) st = fail(RP_ERR_INVALID, "%s: d_time is null", __func__);
-    if (st == RP_OK && n > SIZE_MAX / sizeof(double) / pairs) st = fail(RP_ERR_INVALID, "%s: n x pairs does not fit", __func__);
-    if (st == RP_OK) st = check_queries(__func__, n == 0 ? 0 : n * pairs, k, nullptr, nullptr, {level_per_pair ? d_level_sq : nullptr, d_time, d_rate}, true);
+    const int st = check_fleet(__func__, device, n, m, k, d, &level_per_pair, d_fleet, {{"d_level_sq", d_level_sq}, {"d_time", d_time}},
+                               {level_per_pair ? d_level_sq : nullptr, d_time, d_rate}, true);
     if (st != RP_OK) return st;
     RP_HIP(hipSetDevice(device));
     RP_HIP(rp::launch_fleet_contact(n, m, k, d, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, (hipStream_t)stream));
@@ -1573,17 +1580,8 @@ int rp_trajectory_fleet_separation_staggered(int device, void *stream, size_t n,
                                              const double *d_start, const double *d_lo, const double *d_hi, double *d_value, double *d_time,
                                              double *d_time_local)
 {
-    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
-    if (m < 2 || m > 256) return fail(RP_ERR_INVALID, "%s: m must be 2..256 vehicles per scene, got %zu", __func__, m);
-    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
-    if (!d_fleet) return fail(RP_ERR_INVALID, "%s: d_fleet is null", __func__);
-    int st = RP_OK;
-    for (int x = 0; x < d && st == RP_OK; ++x) st = check_spline(__func__, "d_fleet", d_fleet + 8 * x);
-    const size_t pairs = m * (m - 1) / 2;
-    if (st == RP_OK && !d_start) st = fail(RP_ERR_INVALID, "%s: d_start is null", __func__);
-    if (st == RP_OK && n > SIZE_MAX / sizeof(double) / pairs) st = fail(RP_ERR_INVALID, "%s: n x pairs does not fit", __func__);
-    if (st == RP_OK)
-        st = check_queries(__func__, n == 0 ? 0 : n * pairs, k, nullptr, nullptr, {d_value, d_time, d_time_local}, d_value || d_time || d_time_local);
+    const int st = check_fleet(__func__, device, n, m, k, d, nullptr, d_fleet, {{"d_start", d_start}}, {d_value, d_time, d_time_local},
+                               d_value || d_time || d_time_local);
     if (st != RP_OK) return st;
     RP_HIP(hipSetDevice(device));
     RP_HIP(rp::launch_fleet_separation_staggered(n, m, k, d, d_fleet, d_start, d_lo, d_hi, d_value, d_time, d_time_local, (hipStream_t)stream));
@@ -1594,21 +1592,8 @@ int rp_trajectory_fleet_contact_staggered(int device, void *stream, size_t n, si
                                           const double *d_start, const double *d_level_sq, int level_per_pair, const double *d_lo,
                                           const double *d_hi, double *d_time, double *d_time_local, double *d_rate)
 {
-    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", __func__, device);
-    if (m < 2 || m > 256) return fail(RP_ERR_INVALID, "%s: m must be 2..256 vehicles per scene, got %zu", __func__, m);
-    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", __func__, d);
-    if (level_per_pair != 0 && level_per_pair != 1)
-        return fail(RP_ERR_INVALID, "%s: level_per_pair must be 0 (n x k) or 1 (n x pairs x k), got %d", __func__, level_per_pair);
-    if (!d_fleet) return fail(RP_ERR_INVALID, "%s: d_fleet is null", __func__);
-    int st = RP_OK;
-    for (int x = 0; x < d && st == RP_OK; ++x) st = check_spline(__func__, "d_fleet", d_fleet + 8 * x);
-    const size_t pairs = m * (m - 1) / 2;
-    if (st == RP_OK && !d_start) st = fail(RP_ERR_INVALID, "%s: d_start is null", __func__);
-    if (st == RP_OK && !d_level_sq) st = fail(RP_ERR_INVALID, "%s: d_level_sq is null", __func__);
-    if (st == RP_OK && n > SIZE_MAX / sizeof(double) / pairs) st = fail(RP_ERR_INVALID, "%s: n x pairs does not fit", __func__);
-    if (st == RP_OK)
-        st = check_queries(__func__, n == 0 ? 0 : n * pairs, k, nullptr, nullptr, {level_per_pair ? d_level_sq : nullptr, d_time, d_time_local, d_rate},
-                           d_time || d_time_local || d_rate);
+    const int st = check_fleet(__func__, device, n, m, k, d, &level_per_pair, d_fleet, {{"d_start", d_start}, {"d_level_sq", d_level_sq}},
+                               {level_per_pair ? d_level_sq : nullptr, d_time, d_time_local, d_rate}, d_time || d_time_local || d_rate);
     if (st != RP_OK) return st;
     RP_HIP(hipSetDevice(device));
     RP_HIP(rp::launch_fleet_contact_staggered(n, m, k, d, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate,

@@ -47,6 +47,8 @@
 // expression, so that null and explicit zeros give the same bits; a null window end is -inf or +inf (load_window).
 #include "ip_kernels.h"
 
+#include <type_traits>
+
 #include "../../include/rp_batch.h"
 #include "batch_dispatch.h"
 #include "fleet_index.h"
@@ -2485,7 +2487,38 @@ __device__ __forceinline__ void separation_query(const SepLds<D> &L, int q, doub
     time = best_t;
 }
 
-template <int D> struct SepSplines { FromArrays a[D], b[D]; };
+template <int D> struct SepSplines { FromArrays a[D], b[D]; };      // a pair entry's tables: vehicle A's D splines and vehicle B's
+template <int D> struct FleetSplines { FromArrays v[D]; };          // a fleet entry's: vehicle v of scene s at s m + v of every array
+
+// The one staging of a pair (sections 24-28): problem ia of a's D splines as vehicle A and problem ib of b's as vehicle B into place q,
+// under the NaN rule, each axis' evaluator constants and total time.
+template <int D>
+__device__ __forceinline__ void stage_vehicles(SepLds<D> &L, int q, const FromArrays (&a)[D], size_t ia, const FromArrays (&b)[D], size_t ib)
+{
+#pragma unroll
+    for (int x = 0; x < D; ++x) {
+        Knots ka = a[x].load(ia), kb = b[x].load(ib);
+        ka.check();
+        kb.check();
+        stage_eval(L.a[x], q, ka);
+        stage_eval(L.b[x], q, kb);
+        L.Ta[x][q] = ka.t0 + ka.t1;
+        L.Tb[x][q] = kb.t0 + kb.t1;
+    }
+}
+
+// The one decode of a fleet launch's problem p, staged by thread q of its trip, into (scene, i, j) (section 26: one 64-bit division for
+// the trip's first scene, 32-bit ones from there), and the staging of vehicles i and j of that scene as A and B.
+template <int D>
+__device__ __forceinline__ void stage_fleet_pair(SepLds<D> &L, int q, const FleetSplines<D> &in, unsigned m, unsigned pairs, size_t p)
+{
+    const size_t p_first = p - (size_t)q, s_first = p_first / pairs;
+    const unsigned r = (unsigned)(p_first - s_first * pairs) + (unsigned)q;      // < pairs + kTrajProblems
+    const size_t s = s_first + r / pairs;
+    unsigned i, j;
+    fleet_pair(r % pairs, m, i, j);
+    stage_vehicles(L, q, in.v, s * m + i, in.v, s * m + j);
+}
 
 template <int D>
 __global__ void __launch_bounds__(kTrajBlock) 
@@ -2493,18 +2526,7 @@ k_separation(SepSplines<D> in, size_t n, size_t k, int P, const double *__restri
              const double *__restrict__ delay, double *__restrict__ value, double *__restrict__ time)
 {
     __shared__ SepLds<D> L;
-    auto stage_problem = [&](int q, size_t i) {
-#pragma unroll
-        for (int x = 0; x < D; ++x) {
-            Knots ka = in.a[x].load(i), kb = in.b[x].load(i);
-            ka.check();
-            kb.check();
-            stage_eval(L.a[x], q, ka);
-            stage_eval(L.b[x], q, kb);
-            L.Ta[x][q] = ka.t0 + ka.t1;
-            L.Tb[x][q] = kb.t0 + kb.t1;
-        }
-    };
+    auto stage_problem = [&](int q, size_t i) { stage_vehicles(L, q, in.a, i, in.b, i); };
     for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
         const size_t e_first = p_first * k;
         stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
@@ -2534,8 +2556,6 @@ k_separation(SepSplines<D> in, size_t n, size_t k, int P, const double *__restri
 // 133 VGPRs).  Instead one 64-bit division per trip gives the trip's first (scene, pair), and place q's are a 32-bit division on from there.
 // Every query is separation_query with a delay of 0.0: k_separation's bits for the gathered pair with a null delay.  Without the hint the
 // allocator takes 127 / 133 / 142 VGPRs.
-template <int D> struct FleetSplines { FromArrays v[D]; };
-
 template <int D>
 __global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
 k_fleet(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
@@ -2543,24 +2563,7 @@ k_fleet(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const 
 {
     __shared__ SepLds<D> L;
     const unsigned pairs = fleet_pair_count(m);
-    auto stage_problem = [&](int q, size_t p) {
-        const size_t p_first = p - (size_t)q, s_first = p_first / pairs;
-        const unsigned r = (unsigned)(p_first - s_first * pairs) + (unsigned)q;      // < pairs + kTrajProblems
-        const size_t s = s_first + r / pairs;
-        unsigned i, j;
-        fleet_pair(r % pairs, m, i, j);
-        const size_t first = s * m + i, second = s * m + j;
-#pragma unroll
-        for (int x = 0; x < D; ++x) {
-            Knots ka = in.v[x].load(first), kb = in.v[x].load(second);
-            ka.check();
-            kb.check();
-            stage_eval(L.a[x], q, ka);
-            stage_eval(L.b[x], q, kb);
-            L.Ta[x][q] = ka.t0 + ka.t1;
-            L.Tb[x][q] = kb.t0 + kb.t1;
-        }
-    };
+    auto stage_problem = [&](int q, size_t p) { stage_fleet_pair(L, q, in, m, pairs, p); };
     for_each_trip(problems, P, stage_problem, [&](size_t p_first, int here) {
         const size_t e_first = p_first * k, s_first = p_first / pairs;
         const unsigned r_first = (unsigned)(p_first - s_first * pairs);
@@ -2719,18 +2722,7 @@ k_contact(SepSplines<D> in, size_t n, size_t k, int P, const double *__restrict_
           const double *__restrict__ hi, const double *__restrict__ delay, double *__restrict__ time, double *__restrict__ rate)
 {
     __shared__ SepLds<D> L;
-    auto stage_problem = [&](int q, size_t i) {
-#pragma unroll
-        for (int x = 0; x < D; ++x) {
-            Knots ka = in.a[x].load(i), kb = in.b[x].load(i);
-            ka.check();
-            kb.check();
-            stage_eval(L.a[x], q, ka);
-            stage_eval(L.b[x], q, kb);
-            L.Ta[x][q] = ka.t0 + ka.t1;
-            L.Tb[x][q] = kb.t0 + kb.t1;
-        }
-    };
+    auto stage_problem = [&](int q, size_t i) { stage_vehicles(L, q, in.a, i, in.b, i); };
     for_each_trip(n, P, stage_problem, [&](size_t p_first, int here) {
         const size_t e_first = p_first * k;
         stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
@@ -2766,24 +2758,7 @@ k_encounter(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, co
 {
     __shared__ SepLds<D> L;
     const unsigned pairs = fleet_pair_count(m);
-    auto stage_problem = [&](int q, size_t p) {
-        const size_t p_first = p - (size_t)q, s_first = p_first / pairs;
-        const unsigned r = (unsigned)(p_first - s_first * pairs) + (unsigned)q;      // < pairs + kTrajProblems
-        const size_t s = s_first + r / pairs;
-        unsigned i, j;
-        fleet_pair(r % pairs, m, i, j);
-        const size_t first = s * m + i, second = s * m + j;
-#pragma unroll
-        for (int x = 0; x < D; ++x) {
-            Knots ka = in.v[x].load(first), kb = in.v[x].load(second);
-            ka.check();
-            kb.check();
-            stage_eval(L.a[x], q, ka);
-            stage_eval(L.b[x], q, kb);
-            L.Ta[x][q] = ka.t0 + ka.t1;
-            L.Tb[x][q] = kb.t0 + kb.t1;
-        }
-    };
+    auto stage_problem = [&](int q, size_t p) { stage_fleet_pair(L, q, in, m, pairs, p); };
     for_each_trip(problems, P, stage_problem, [&](size_t p_first, int here) {
         const size_t e_first = p_first * k, s_first = p_first / pairs;
         const unsigned r_first = (unsigned)(p_first - s_first * pairs);
@@ -2847,24 +2822,7 @@ k_stagger(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, cons
     __shared__ SepLds<D> L;
     const unsigned pairs = fleet_pair_count(m);
     const StartOf clock{start, lo, hi, m, pairs};
-    auto stage_problem = [&](int q, size_t p) {
-        const size_t p_first = p - (size_t)q, s_first = p_first / pairs;
-        const unsigned r = (unsigned)(p_first - s_first * pairs) + (unsigned)q;      // < pairs + kTrajProblems
-        const size_t s = s_first + r / pairs;
-        unsigned i, j;
-        fleet_pair(r % pairs, m, i, j);
-        const size_t first = s * m + i, second = s * m + j;
-#pragma unroll
-        for (int x = 0; x < D; ++x) {
-            Knots ka = in.v[x].load(first), kb = in.v[x].load(second);
-            ka.check();
-            kb.check();
-            stage_eval(L.a[x], q, ka);
-            stage_eval(L.b[x], q, kb);
-            L.Ta[x][q] = ka.t0 + ka.t1;
-            L.Tb[x][q] = kb.t0 + kb.t1;
-        }
-    };
+    auto stage_problem = [&](int q, size_t p) { stage_fleet_pair(L, q, in, m, pairs, p); };
     for_each_trip(problems, P, stage_problem, [&](size_t p_first, int here) {
         const size_t e_first = p_first * k, s_first = p_first / pairs;
         const unsigned r_first = (unsigned)(p_first - s_first * pairs);
@@ -2899,24 +2857,7 @@ k_rendezvous(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, c
     __shared__ SepLds<D> L;
     const unsigned pairs = fleet_pair_count(m);
     const StartOf clock{start, lo, hi, m, pairs};
-    auto stage_problem = [&](int q, size_t p) {
-        const size_t p_first = p - (size_t)q, s_first = p_first / pairs;
-        const unsigned r = (unsigned)(p_first - s_first * pairs) + (unsigned)q;      // < pairs + kTrajProblems
-        const size_t s = s_first + r / pairs;
-        unsigned i, j;
-        fleet_pair(r % pairs, m, i, j);
-        const size_t first = s * m + i, second = s * m + j;
-#pragma unroll
-        for (int x = 0; x < D; ++x) {
-            Knots ka = in.v[x].load(first), kb = in.v[x].load(second);
-            ka.check();
-            kb.check();
-            stage_eval(L.a[x], q, ka);
-            stage_eval(L.b[x], q, kb);
-            L.Ta[x][q] = ka.t0 + ka.t1;
-            L.Tb[x][q] = kb.t0 + kb.t1;
-        }
-    };
+    auto stage_problem = [&](int q, size_t p) { stage_fleet_pair(L, q, in, m, pairs, p); };
     for_each_trip(problems, P, stage_problem, [&](size_t p_first, int here) {
         const size_t e_first = p_first * k, s_first = p_first / pairs;
         const unsigned r_first = (unsigned)(p_first - s_first * pairs);
@@ -3066,6 +3007,51 @@ template <class Launch> hipError_t launch_on_batch(const BatchView &b, size_t k,
     const int P = problems_per_trip(k, true);
     RP_DISPATCH(kVariant | kZeroVel, b, launch(FromBatch<S, V, Z>{(const S *)b.base, b.stride, slots(b)}, dim3(trajectory_grid(b.n, P)), dim3(kTrajBlock), P));
     return hipGetLastError();
+}
+
+// The run-time number of axes as a compile-time one: f(std::integral_constant<int, D>) for d = 1, 2, 3, a refusal for any other d.
+template <class F> hipError_t with_axes(int d, F f)
+{
+    switch (d) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+// the kernels' tables from the entries': d_spline_a, d_spline_b and d_fleet are 8 d pointers each, axis x at 8 x
+template <int D> SepSplines<D> sep_splines(const double *const *d_spline_a, const double *const *d_spline_b)
+{
+    SepSplines<D> in;
+    for (int x = 0; x < D; ++x) {
+        in.a[x] = FromArrays{table_of<8>(d_spline_a + 8 * x)};
+        in.b[x] = FromArrays{table_of<8>(d_spline_b + 8 * x)};
+    }
+    return in;
+}
+
+template <int D> FleetSplines<D> fleet_splines(const double *const *d_fleet)
+{
+    FleetSplines<D> in;
+    for (int x = 0; x < D; ++x) in.v[x] = FromArrays{table_of<8>(d_fleet + 8 * x)};
+    return in;
+}
+
+// A pointwise launch over n pairs of vehicles in d axes: launch(axes, grid, block, P), D = decltype(axes)::value.
+template <class Launch> hipError_t launch_on_pairs(size_t n, size_t k, int d, Launch launch)
+{
+    return with_axes(d, [&](auto axes) {
+        return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) { launch(axes, grid, block, P); });
+    });
+}
+
+// The same over the n m (m - 1) / 2 (scene, pair) problems of n scenes of m vehicles: launch(axes, problems, grid, block, P).
+template <class Launch> hipError_t launch_on_fleet(size_t n, size_t m, size_t k, int d, Launch launch)
+{
+    if (m < 2 || m > kFleetMost) return hipErrorInvalidValue;
+    const size_t problems = n * fleet_pair_count((unsigned)m);
+    return launch_on_pairs(problems, k, d, [&](auto axes, dim3 grid, dim3 block, int P) { launch(axes, problems, grid, block, P); });
 }
 
 }  // namespace
@@ -3281,113 +3267,43 @@ hipError_t launch_meeting(size_t n, size_t k, const double *const d_spline_a[8],
     });
 }
 
-template <int D>
-hipError_t launch_separation_axes(size_t n, size_t k, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_lo,
-                                  const double *d_hi, const double *d_delay, double *d_value, double *d_time, hipStream_t stream)
-{
-    SepSplines<D> in;
-    for (int x = 0; x < D; ++x) {
-        in.a[x] = FromArrays{table_of<8>(d_spline_a + 8 * x)};
-        in.b[x] = FromArrays{table_of<8>(d_spline_b + 8 * x)};
-    }
-    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
-        hipLaunchKernelGGL(k_separation<D>, grid, block, 0, stream, in, n, k, P, d_lo, d_hi, d_delay, d_value, d_time);
-    });
-}
-
 hipError_t launch_separation(size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_lo,
                              const double *d_hi, const double *d_delay, double *d_value, double *d_time, hipStream_t stream)
 {
-    switch (d) {
-    case 1: return launch_separation_axes<1>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
-    case 2: return launch_separation_axes<2>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
-    case 3: return launch_separation_axes<3>(n, k, d_spline_a, d_spline_b, d_lo, d_hi, d_delay, d_value, d_time, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <int D>
-hipError_t launch_fleet_axes(size_t n, unsigned m, size_t k, const double *const *d_fleet, const double *d_lo, const double *d_hi, double *d_value,
-                             double *d_time, hipStream_t stream)
-{
-    FleetSplines<D> in;
-    for (int x = 0; x < D; ++x) in.v[x] = FromArrays{table_of<8>(d_fleet + 8 * x)};
-    const size_t problems = n * fleet_pair_count(m);
-    return launch_stateless<false>(problems, k, [&](dim3 grid, dim3 block, int P, int) {
-        hipLaunchKernelGGL(k_fleet<D>, grid, block, 0, stream, in, problems, m, k, P, d_lo, d_hi, d_value, d_time);
-    });
-}
-
-hipError_t launch_fleet_separation(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo, const double *d_hi,
-                                   double *d_value, double *d_time, hipStream_t stream)
-{
-    if (m < 2 || m > kFleetMost) return hipErrorInvalidValue;
-    switch (d) {
-    case 1: return launch_fleet_axes<1>(n, (unsigned)m, k, d_fleet, d_lo, d_hi, d_value, d_time, stream);
-    case 2: return launch_fleet_axes<2>(n, (unsigned)m, k, d_fleet, d_lo, d_hi, d_value, d_time, stream);
-    case 3: return launch_fleet_axes<3>(n, (unsigned)m, k, d_fleet, d_lo, d_hi, d_value, d_time, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <int D>
-hipError_t launch_contact_axes(size_t n, size_t k, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_level_sq,
-                               const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_rate, hipStream_t stream)
-{
-    SepSplines<D> in;
-    for (int x = 0; x < D; ++x) {
-        in.a[x] = FromArrays{table_of<8>(d_spline_a + 8 * x)};
-        in.b[x] = FromArrays{table_of<8>(d_spline_b + 8 * x)};
-    }
-    return launch_stateless<false>(n, k, [&](dim3 grid, dim3 block, int P, int) {
-        hipLaunchKernelGGL(k_contact<D>, grid, block, 0, stream, in, n, k, P, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate);
+    return launch_on_pairs(n, k, d, [&](auto axes, dim3 grid, dim3 block, int P) {
+        constexpr int D = decltype(axes)::value;
+        hipLaunchKernelGGL(k_separation<D>, grid, block, 0, stream, sep_splines<D>(d_spline_a, d_spline_b), n, k, P, d_lo, d_hi, d_delay, d_value,
+                           d_time);
     });
 }
 
 hipError_t launch_contact(size_t n, size_t k, int d, const double *const *d_spline_a, const double *const *d_spline_b, const double *d_level_sq,
                           const double *d_lo, const double *d_hi, const double *d_delay, double *d_time, double *d_rate, hipStream_t stream)
 {
-    switch (d) {
-    case 1: return launch_contact_axes<1>(n, k, d_spline_a, d_spline_b, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate, stream);
-    case 2: return launch_contact_axes<2>(n, k, d_spline_a, d_spline_b, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate, stream);
-    case 3: return launch_contact_axes<3>(n, k, d_spline_a, d_spline_b, d_level_sq, d_lo, d_hi, d_delay, d_time, d_rate, stream);
-    }
-    return hipErrorInvalidValue;
+    return launch_on_pairs(n, k, d, [&](auto axes, dim3 grid, dim3 block, int P) {
+        constexpr int D = decltype(axes)::value;
+        hipLaunchKernelGGL(k_contact<D>, grid, block, 0, stream, sep_splines<D>(d_spline_a, d_spline_b), n, k, P, d_level_sq, d_lo, d_hi, d_delay,
+                           d_time, d_rate);
+    });
 }
 
-template <int D>
-hipError_t launch_fleet_contact_axes(size_t n, unsigned m, size_t k, const double *const *d_fleet, const double *d_level_sq, int level_per_pair,
-                                     const double *d_lo, const double *d_hi, double *d_time, double *d_rate, hipStream_t stream)
+hipError_t launch_fleet_separation(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo, const double *d_hi,
+                                   double *d_value, double *d_time, hipStream_t stream)
 {
-    FleetSplines<D> in;
-    for (int x = 0; x < D; ++x) in.v[x] = FromArrays{table_of<8>(d_fleet + 8 * x)};
-    const size_t problems = n * fleet_pair_count(m);
-    return launch_stateless<false>(problems, k, [&](dim3 grid, dim3 block, int P, int) {
-        hipLaunchKernelGGL(k_encounter<D>, grid, block, 0, stream, in, problems, m, k, P, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate);
+    return launch_on_fleet(n, m, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
+        constexpr int D = decltype(axes)::value;
+        hipLaunchKernelGGL(k_fleet<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_lo, d_hi, d_value, d_time);
     });
 }
 
 hipError_t launch_fleet_contact(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq, int level_per_pair,
                                 const double *d_lo, const double *d_hi, double *d_time, double *d_rate, hipStream_t stream)
 {
-    if (m < 2 || m > kFleetMost || !d_level_sq || !d_time) return hipErrorInvalidValue;
-    switch (d) {
-    case 1: return launch_fleet_contact_axes<1>(n, (unsigned)m, k, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, stream);
-    case 2: return launch_fleet_contact_axes<2>(n, (unsigned)m, k, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, stream);
-    case 3: return launch_fleet_contact_axes<3>(n, (unsigned)m, k, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <int D>
-hipError_t launch_stagger_axes(size_t n, unsigned m, size_t k, const double *const *d_fleet, const double *d_start, const double *d_lo,
-                               const double *d_hi, double *d_value, double *d_time, double *d_time_local, hipStream_t stream)
-{
-    FleetSplines<D> in;
-    for (int x = 0; x < D; ++x) in.v[x] = FromArrays{table_of<8>(d_fleet + 8 * x)};
-    const size_t problems = n * fleet_pair_count(m);
-    return launch_stateless<false>(problems, k, [&](dim3 grid, dim3 block, int P, int) {
-        hipLaunchKernelGGL(k_stagger<D>, grid, block, 0, stream, in, problems, m, k, P, d_start, d_lo, d_hi, d_value, d_time, d_time_local);
+    if (!d_level_sq || !d_time) return hipErrorInvalidValue;
+    return launch_on_fleet(n, m, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
+        constexpr int D = decltype(axes)::value;
+        hipLaunchKernelGGL(k_encounter<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_level_sq,
+                           level_per_pair, d_lo, d_hi, d_time, d_rate);
     });
 }
 
@@ -3395,26 +3311,11 @@ hipError_t launch_fleet_separation_staggered(size_t n, size_t m, size_t k, int d
                                              const double *d_lo, const double *d_hi, double *d_value, double *d_time, double *d_time_local,
                                              hipStream_t stream)
 {
-    if (m < 2 || m > kFleetMost || !d_start) return hipErrorInvalidValue;
-    switch (d) {
-    case 1: return launch_stagger_axes<1>(n, (unsigned)m, k, d_fleet, d_start, d_lo, d_hi, d_value, d_time, d_time_local, stream);
-    case 2: return launch_stagger_axes<2>(n, (unsigned)m, k, d_fleet, d_start, d_lo, d_hi, d_value, d_time, d_time_local, stream);
-    case 3: return launch_stagger_axes<3>(n, (unsigned)m, k, d_fleet, d_start, d_lo, d_hi, d_value, d_time, d_time_local, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <int D>
-hipError_t launch_rendezvous_axes(size_t n, unsigned m, size_t k, const double *const *d_fleet, const double *d_start, const double *d_level_sq,
-                                  int level_per_pair, const double *d_lo, const double *d_hi, double *d_time, double *d_time_local,
-                                  double *d_rate, hipStream_t stream)
-{
-    FleetSplines<D> in;
-    for (int x = 0; x < D; ++x) in.v[x] = FromArrays{table_of<8>(d_fleet + 8 * x)};
-    const size_t problems = n * fleet_pair_count(m);
-    return launch_stateless<false>(problems, k, [&](dim3 grid, dim3 block, int P, int) {
-        hipLaunchKernelGGL(k_rendezvous<D>, grid, block, 0, stream, in, problems, m, k, P, d_start, d_level_sq, level_per_pair, d_lo, d_hi,
-                           d_time, d_time_local, d_rate);
+    if (!d_start) return hipErrorInvalidValue;
+    return launch_on_fleet(n, m, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
+        constexpr int D = decltype(axes)::value;
+        hipLaunchKernelGGL(k_stagger<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_start, d_lo, d_hi,
+                           d_value, d_time, d_time_local);
     });
 }
 
@@ -3422,16 +3323,12 @@ hipError_t launch_fleet_contact_staggered(size_t n, size_t m, size_t k, int d, c
                                           const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
                                           double *d_time_local, double *d_rate, hipStream_t stream)
 {
-    if (m < 2 || m > kFleetMost || !d_start || !d_level_sq) return hipErrorInvalidValue;
-    switch (d) {
-    case 1:
-        return launch_rendezvous_axes<1>(n, (unsigned)m, k, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, stream);
-    case 2:
-        return launch_rendezvous_axes<2>(n, (unsigned)m, k, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, stream);
-    case 3:
-        return launch_rendezvous_axes<3>(n, (unsigned)m, k, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, stream);
-    }
-    return hipErrorInvalidValue;
+    if (!d_start || !d_level_sq) return hipErrorInvalidValue;
+    return launch_on_fleet(n, m, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
+        constexpr int D = decltype(axes)::value;
+        hipLaunchKernelGGL(k_rendezvous<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_start, d_level_sq,
+                           level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate);
+    });
 }
 
 // ---- plot data by problem index: a range [first, first + count) of problems, wherever they lie in the batch ----
