@@ -81,7 +81,9 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      approach for every pair of a fleet in one launch; a new entry only, the revision stays); rp_trajectory_fleet_contact (that first time
  *      within a distance for every pair of a fleet in one launch; a new entry only, the revision stays);
  *      rp_trajectory_fleet_separation_staggered and rp_trajectory_fleet_contact_staggered (those two with a start time per vehicle; new
- *      entries only, the revision stays) */
+ *      entries only, the revision stays); rp_trajectory_fleet_reach, rp_trajectory_fleet_contact_culled(_workspace) and
+ *      rp_trajectory_fleet_contact_candidates (the fleet's position boxes, and the fleet's first contacts with a broad phase that skips
+ *      the pairs whose boxes prove them apart; new entries only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -804,6 +806,38 @@ RP_API int rp_trajectory_fleet_separation_staggered(int device, void *stream, si
 RP_API int rp_trajectory_fleet_contact_staggered(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
                                                  const double *d_start, const double *d_level_sq, int level_per_pair, const double *d_lo,
                                                  const double *d_hi, double *d_time, double *d_time_local, double *d_rate);
+
+/* ---- the fleet's first contacts with a broad phase in front (new entries only, the revision stays) ----
+ * rp_trajectory_fleet_reach: for vehicle v of scene s, axis c and query q the least and greatest position of that spline over the scene's
+ * window [lo, hi][s, q]: rp_trajectory_extrema's pos_min and pos_max of that spline and window, bit for bit -- its clamp to [0, T] and its
+ * NaN for an empty clamped window and under the NaN rule.  n, m, k, d, d_fleet, d_lo and d_hi are rp_trajectory_fleet_separation's; d_min,
+ * d_max: d pointers each, axis c's to n x m x k doubles, 16-byte aligned; a NULL table or entry is not written, at least one must be.
+ *
+ * rp_trajectory_fleet_contact_culled: rp_trajectory_fleet_contact's outputs, bit for bit in d_time and d_rate, NaN bits included, for
+ * the same first thirteen arguments, which it refuses as that entry does and in its order.  In front of the search: the boxes above;
+ * per pair and query a lower bound of the squared distance of the two vehicles' boxes, made smaller by a slack per vehicle and axis and
+ * a margin (section 30 proves that a pair whose bound is above the level in all k queries has k NaN outputs); those pairs get the NaN
+ * written directly and the search runs over the list of the others, so that the time goes with the number of pairs that are near and
+ * not with m^2.  A NaN or infinite box end, slack or level keeps the pair.  Every element of d_time and d_rate is written exactly once.
+ * d_workspace: caller-owned, 16-byte aligned, at least the bytes rp_trajectory_fleet_contact_culled_workspace gives for (n, m, k, d);
+ * its contents before the call do not matter and after it are unspecified.  d_kept (n x pairs bytes: 1 the pair went to the search, 0 it
+ * was culled), d_list (n x pairs uint32_t: the kept problems s pairs + pair in increasing order in its first *d_count entries, the rest
+ * unspecified) and d_count (one uint32_t) are copies for callers and tests, NULL: not written; the host never reads them.  Beyond
+ * rp_trajectory_fleet_contact's refusals: n x pairs >= 2^32, a NULL or misaligned workspace, workspace_bytes below the size asked for --
+ * RP_ERR_INVALID before any device call.  No block of any of its kernels waits for another; no atomics: the same list and bits in every run.
+ *
+ * rp_trajectory_fleet_contact_candidates: the broad phase alone -- boxes, sieve, no search: d_kept, required, as above.
+ * All asynchronous on `stream`; none throws. */
+RP_API int rp_trajectory_fleet_reach(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                                     const double *d_lo, const double *d_hi, double *const *d_min, double *const *d_max);
+RP_API int rp_trajectory_fleet_contact_culled_workspace(size_t n, size_t m, size_t k, int d, size_t *bytes);
+RP_API int rp_trajectory_fleet_contact_culled(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                                              const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi,
+                                              double *d_time, double *d_rate, void *d_workspace, size_t workspace_bytes,
+                                              unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count);
+RP_API int rp_trajectory_fleet_contact_candidates(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                                                  const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi,
+                                                  void *d_workspace, size_t workspace_bytes, unsigned char *d_kept);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

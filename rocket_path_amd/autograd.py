@@ -2254,6 +2254,30 @@ class _TrajectoryFleetContact(torch.autograd.Function):
         return torch.where(missing, torch.full_like(rate, float("nan")), total / rate), None
 
 
+def _cull_workspace(n, m, k, d, device):
+    """The culled entries' workspace as a torch allocation on the current stream: (tensor, bytes)"""
+    size = capi.trajectory_fleet_contact_culled_workspace(n, m, k, d)
+    return torch.empty(size, dtype=torch.uint8, device=device), size
+
+
+class _TrajectoryFleetContactCulled(_TrajectoryFleetContact):
+    """_TrajectoryFleetContact with the broad phase in front of the forward: rp_trajectory_fleet_contact_culled gives
+    the same bits in time and rate, so what is saved and both derivative rules are the parent's, unchanged."""
+
+    @staticmethod
+    def forward(d, m, *inputs):
+        level, lo, hi = (_dense(t) for t in inputs[8 * d:])
+        level, per_pair = _fleet_level(level)
+        n, k = level.shape[0], level.shape[-1]
+        with torch.cuda.device(inputs[0].device):
+            work, size = _cull_workspace(n, m, k, d, inputs[0].device)
+
+        def entry(*args):
+            capi.trajectory_fleet_contact_culled(*args, _plain(work).data_ptr(), size)
+
+        return _fleet_forward(entry, d, m, inputs, n, k, 2, lambda addr: (addr(level), int(per_pair), addr(lo), addr(hi)))
+
+
 class _TrajectoryStaggeredContact(torch.autograd.Function):
     """_TrajectoryFleetContact with a start time per vehicle: (the time on the scene's clock, the time on the clock of the pair's first
     vehicle, rate), (n, pairs, k) each.  Inputs: d, m, the fleet's 8 d tensors, start (n, m), level_sq, lo, hi.  Pair (i, j) is
@@ -2356,7 +2380,7 @@ def _check_fleet_queries(n, m, device, radius, level_sq, lo, hi, who):
     return level, lo, hi
 
 
-def trajectory_fleet_contact(fleet, radius=None, lo=None, hi=None, *, level_sq=None, start=None):
+def trajectory_fleet_contact(fleet, radius=None, lo=None, hi=None, *, level_sq=None, start=None, broad_phase=False):
     """trajectory_contact for every pair of a fleet, in one launch: the first time in a scene's windows [lo, hi] at which two of its
     vehicles come within `radius` of each other.  fleet, lo, hi: exactly trajectory_fleet_separation's.  radius: (n, k), or (k,) for the
     same in every scene -- one radius for all pairs of a scene --, or (n, pairs, k) -- one per pair, what vehicles of different sizes need:
@@ -2377,34 +2401,101 @@ def trajectory_fleet_contact(fleet, radius=None, lo=None, hi=None, *, level_sq=N
     start= (n, m), float64 on the fleet's device: trajectory_fleet_separation's start times.  lo, hi and t_contact
     are then on the scene's clock: [s, (i, j), q] is trajectory_contact's time, bit for bit, for vehicles i and j with delay = start_j -
     start_i over the window [lo - start_i, hi - start_i], plus start_i.  One rp_trajectory_fleet_contact_staggered launch; the time is
-    differentiable in start as well.  start=None is the call without it: the same launches and the same bits."""
+    differentiable in start as well.  start=None is the call without it: the same launches and the same bits.
+
+    broad_phase=True puts a bounding-box cull in front of the search: one rp_trajectory_fleet_contact_culled call
+    -- per vehicle, axis and query the position's box over the window, per pair a lower bound of the boxes' distance with a proved margin,
+    NaN written directly for the pairs whose bound is above the level in all k queries, and the search over a device-side list of the
+    rest.  The same bits out, NaN included, hence the same gradients; the time goes with the number of near pairs and not with m^2.  The
+    workspace is a torch allocation on the current stream.  Not with start= (ValueError).  False is the call without it: the same
+    launches and the same bits as before."""
     who = "trajectory_fleet_contact"
     if (radius is None) == (level_sq is None):
         raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
+    if broad_phase and start is not None:
+        raise ValueError(who + ": broad_phase=True does not take start=; the staggered entries have no broad phase")
     n, m, d, tables = _check_fleet(fleet, who)
     level, lo, hi = _check_fleet_arguments(n, m, fleet[0].device, start,
                                            lambda: _check_fleet_queries(n, m, fleet[0].device, radius, level_sq, lo, hi, who), who)
     _check_fleet_devices(fleet, who)
     if start is None:
-        return _TrajectoryFleetContact.apply(d, m, *[t for table in tables for t in table], level, lo, hi)[0]
+        function = _TrajectoryFleetContactCulled if broad_phase else _TrajectoryFleetContact
+        return function.apply(d, m, *[t for table in tables for t in table], level, lo, hi)[0]
     return _TrajectoryStaggeredContact.apply(d, m, *[t for table in tables for t in table], start, level, lo, hi)[0]
 
 
 def min_time_fleet_contact(pos, radius=None, lo=None, hi=None, *, level_sq=None, vel=None, synchronize=True, gap_tol=1e-8, max_iter=200,
-                           params=None, start=None):
+                           params=None, start=None, broad_phase=False):
     """min_time_solve of a fleet's axes, then trajectory_fleet_contact of the solutions: min_time_fleet_separation's composition -- pos,
     vel, synchronize and the solution returned are its -- with trajectory_fleet_contact's radius (or level_sq=), lo and hi.  Returns
     (t_contact, solution).  Plain composition: the times are differentiable to first order in the positions, the end velocities and the
-    radius, in both modes.  start= (n, m): trajectory_fleet_contact's start times, checked before the solve and differentiable."""
+    radius, in both modes.  start= (n, m): trajectory_fleet_contact's start times, checked before the solve and differentiable.
+    broad_phase=True: trajectory_fleet_contact's bounding-box cull in front of the search; the same bits; not with start=."""
     who = "min_time_fleet_contact"
     if (radius is None) == (level_sq is None):
         raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
+    if broad_phase and start is not None:
+        raise ValueError(who + ": broad_phase=True does not take start=; the staggered entries have no broad phase")
     n, m, d = _check_fleet_problem(pos, vel, synchronize, who)
     # before the solve: a bad query costs none
     level, lo, hi = _check_fleet_arguments(n, m, pos[0].device, start,
                                            lambda: _check_fleet_queries(n, m, pos[0].device, radius, level_sq, lo, hi, who), who)
     spline, solution = _solve_fleet(pos, vel, synchronize, gap_tol, max_iter, params)
-    return trajectory_fleet_contact(spline, None, lo, hi, level_sq=level, start=start), solution
+    return trajectory_fleet_contact(spline, None, lo, hi, level_sq=level, start=start, broad_phase=broad_phase), solution
+
+
+def fleet_contact_candidates(fleet, radius=None, lo=None, hi=None, *, level_sq=None):
+    """The broad phase of trajectory_fleet_contact(..., broad_phase=True) alone: a (n, pairs) bool tensor, in fleet_pairs(m)'s order, True
+    where the pair would go to the search and False where its position boxes over the window prove, with the margin of DESIGN.md section
+    30, that it is further apart than the level in all k queries -- trajectory_fleet_contact's times of such a pair are NaN.  A kept pair
+    need not have a contact.  fleet, radius (or level_sq=), lo and hi: exactly trajectory_fleet_contact's.  One
+    rp_trajectory_fleet_contact_candidates call on the current stream: boxes, sieve, no search.  Not differentiable."""
+    who = "fleet_contact_candidates"
+    if (radius is None) == (level_sq is None):
+        raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
+    n, m, d, tables = _check_fleet(fleet, who)
+    device = fleet[0].device
+    level, lo, hi = _check_fleet_queries(n, m, device, radius, level_sq, lo, hi, who)
+    _check_fleet_devices(fleet, who)
+    with torch.no_grad():
+        level, per_pair = _fleet_level(_dense(level.detach()))
+        lo, hi = (_dense(t.detach()) if t is not None else None for t in (lo, hi))
+        k = level.shape[-1]
+        splines = [_dense(t.detach()) if t is not None else None for table in tables for t in table]
+        kept = torch.empty((n, m * (m - 1) // 2), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            work, size = _cull_workspace(n, m, k, d, device)
+            addr = lambda t: t.data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_fleet_contact_candidates(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d,
+                                                     [addr(t) for t in splines], addr(level), int(per_pair), addr(lo), addr(hi),
+                                                     work.data_ptr(), size, kept.data_ptr())
+    return kept != 0
+
+
+def trajectory_fleet_reach(fleet, lo=None, hi=None):
+    """How far every vehicle of a fleet gets in every axis: (box_min, box_max), (n, m, k, d) each -- the least and greatest position of
+    vehicle v of scene s in axis c over the scene's window [lo, hi][s, q], bit for bit trajectory_extrema's pos_min and pos_max of that
+    spline and window (its clamp to [0, T]; NaN for an empty clamped window and for a vehicle with a bad duration).  fleet, lo, hi:
+    exactly trajectory_fleet_separation's; both windows None: k = 1, each spline's whole time.  One rp_trajectory_fleet_reach launch on
+    the current stream; no window tensor repeated per vehicle is made.  These are the boxes of trajectory_fleet_contact's broad phase
+    (DESIGN.md section 30).  Not differentiable: trajectory_extrema is the differentiable form."""
+    who = "trajectory_fleet_reach"
+    n, m, d, tables = _check_fleet(fleet, who)
+    device = fleet[0].device
+    lo, hi = _check_fleet_windows(n, device, lo, hi, who)
+    _check_fleet_devices(fleet, who)
+    with torch.no_grad():
+        lo, hi = (_dense(t.detach()) if t is not None else None for t in (lo, hi))
+        k = next((t.shape[1] for t in (lo, hi) if t is not None), 1)
+        splines = [_dense(t.detach()) if t is not None else None for table in tables for t in table]
+        size = n * m * k
+        flat = torch.empty((2, d, size + (size & 1)), dtype=torch.float64, device=device)      # every array starts on a 16-byte boundary
+        box = flat[:, :, :size].unflatten(2, (n, m, k))      # a view: axis c's (n, m, k) array is contiguous
+        with torch.cuda.device(device):
+            addr = lambda t: t.data_ptr() if t is not None else 0      # noqa: E731
+            capi.trajectory_fleet_reach(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in splines],
+                                        addr(lo), addr(hi), [box[0, c].data_ptr() for c in range(d)], [box[1, c].data_ptr() for c in range(d)])
+    return box[0].permute(1, 2, 3, 0), box[1].permute(1, 2, 3, 0)
 
 
 def fleet_first_contact(t_contact):

@@ -128,6 +128,15 @@ SIGNATURES = {
                                                                 ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_trajectory_fleet_contact_staggered": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
                                                              ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "rp_trajectory_fleet_reach": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                 ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rp_trajectory_fleet_contact_culled_workspace": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                                    ctypes.POINTER(ctypes.c_size_t)]),
+    "rp_trajectory_fleet_contact_culled": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                          ctypes.POINTER(_vp), _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t,
+                                                          _vp, _vp, _vp]),
+    "rp_trajectory_fleet_contact_candidates": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                              ctypes.POINTER(_vp), _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "rp_trajectory_tracking": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
                                               _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_tracking_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
@@ -394,6 +403,58 @@ def trajectory_fleet_contact_staggered(device, stream, n, m, k, d, fleet, d_star
     check(load_library().rp_trajectory_fleet_contact_staggered(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_start),
                                                                vp(d_level_sq), int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_time),
                                                                vp(d_time_local), vp(d_rate)))
+
+
+def _axis_outputs(addresses, d, name):
+    """d device addresses (ints; None / 0: NULL) as a `double *const [d]` table; None gives a NULL table."""
+    if addresses is None:
+        return None
+    addresses = list(addresses)
+    if len(addresses) != d:
+        raise ValueError("%s: a table of %d axes has %d entries, got %d" % (name, d, d, len(addresses)))
+    return (_vp * d)(*[a if a else None for a in addresses])
+
+
+def trajectory_fleet_reach(device, stream, n, m, k, d, fleet, d_lo=None, d_hi=None, d_min=None, d_max=None):
+    """rp_trajectory_fleet_reach: per vehicle, axis and query the least and greatest position over the scene's window [lo, hi] (n, k;
+    None / 0: -inf, +inf) -- trajectory_extrema's pos_min and pos_max of that spline and window, bit for bit.  `fleet` as for
+    trajectory_fleet_separation.  d_min, d_max: d addresses each, axis c's to (n, m, k), 16-byte aligned (None / 0: not wanted; not all)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = _fleet_sizes("trajectory_fleet_reach", d, m)
+    check(load_library().rp_trajectory_fleet_reach(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_lo), vp(d_hi),
+                                                   _axis_outputs(d_min, d, "d_min"), _axis_outputs(d_max, d, "d_max")))
+
+
+def trajectory_fleet_contact_culled_workspace(n, m, k, d):
+    """rp_trajectory_fleet_contact_culled_workspace: the bytes of workspace the culled entries need for (n, m, k, d)."""
+    d, m = _fleet_sizes("trajectory_fleet_contact_culled_workspace", d, m)
+    size = ctypes.c_size_t(0)
+    check(load_library().rp_trajectory_fleet_contact_culled_workspace(int(n), m, int(k), d, ctypes.byref(size)))
+    return size.value
+
+
+def trajectory_fleet_contact_culled(device, stream, n, m, k, d, fleet, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None, d_time=None,
+                                    d_rate=None, d_workspace=None, workspace_bytes=0, d_kept=None, d_list=None, d_count=None):
+    """rp_trajectory_fleet_contact_culled: trajectory_fleet_contact's outputs, bit for bit, for the same first thirteen arguments, with the
+    broad phase in front: pairs whose position boxes prove them further apart than the level in all k queries get their NaN without a
+    search.  d_workspace: workspace_bytes >= trajectory_fleet_contact_culled_workspace(n, m, k, d) bytes, 16-byte aligned.  d_kept
+    (n pairs bytes), d_list (n pairs uint32), d_count (one uint32): copies of the keep-flags, the list and its length (None / 0: none)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = _fleet_sizes("trajectory_fleet_contact_culled", d, m)
+    check(load_library().rp_trajectory_fleet_contact_culled(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_level_sq),
+                                                            int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_time), vp(d_rate), vp(d_workspace),
+                                                            int(workspace_bytes), vp(d_kept), vp(d_list), vp(d_count)))
+
+
+def trajectory_fleet_contact_candidates(device, stream, n, m, k, d, fleet, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None, d_workspace=None,
+                                        workspace_bytes=0, d_kept=None):
+    """rp_trajectory_fleet_contact_candidates: the broad phase of trajectory_fleet_contact_culled alone: d_kept (n pairs bytes, required),
+    1 where the pair would go to the search.  The workspace as there."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = _fleet_sizes("trajectory_fleet_contact_candidates", d, m)
+    check(load_library().rp_trajectory_fleet_contact_candidates(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d),
+                                                                vp(d_level_sq), int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_workspace),
+                                                                int(workspace_bytes), vp(d_kept)))
 
 
 def tracking_table(addresses):

@@ -229,5 +229,16 @@ hipError_t launch_fleet_separation_staggered(size_t n, size_t m, size_t k, int d
 hipError_t launch_fleet_contact_staggered(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
                                           const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
                                           double *d_time_local, double *d_rate, hipStream_t stream);
+// the fleet's position boxes over the scenes' windows: d_min, d_max d pointers each to n x m x k (null table or entry: not wanted),
+// d_slack d pointers to n x m (null table: not wanted)
+hipError_t launch_fleet_reach(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo, const double *d_hi,
+                              double *const *d_min, double *const *d_max, double *const *d_slack, hipStream_t stream);
+// launch_fleet_contact with the broad phase in front: the bytes of workspace it needs (0: n x pairs does not fit
+// 32 bits), and the launch -- boxes, sieve, list and, where d_time is given, the search over the list.  d_time null: the broad phase alone.
+// d_kept (n x pairs bytes), d_list (n x pairs uint32) and d_count (one uint32) are copies for the caller (null: none).
+size_t fleet_cull_workspace_bytes(size_t n, size_t m, size_t k, int d);
+hipError_t launch_fleet_contact_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq,
+                                       int level_per_pair, const double *d_lo, const double *d_hi, double *d_time, double *d_rate,
+                                       void *d_workspace, unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count, hipStream_t stream);
 
 }  // namespace rp

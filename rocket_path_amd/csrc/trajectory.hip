@@ -51,6 +51,7 @@
 
 #include "../../include/rp_batch.h"
 #include "batch_dispatch.h"
+#include "fleet_cull.h"
 #include "fleet_index.h"
 #include "ip_core.h"
 #include "spline_core.h"
@@ -2885,6 +2886,204 @@ k_rendezvous(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, c
     });
 }
 
+// ---- the fleet's first contacts with a broad phase in front (rp_trajectory_fleet_contact_culled, rp_trajectory_fleet_reach; DESIGN.md
+// section 30) ----
+// Four passes on one stream, none of which waits for another block.  k_reach: per vehicle, axis and query the least and greatest position
+// over the scene's window -- stage_extrema and the position half of extrema_query, rp_trajectory_extrema's bits -- and per (vehicle, axis)
+// a slack (fleet_cull.h).  k_sieve: one thread per (scene, pair); a query is far when the boxes' distance, less the slacks and the margin,
+// is above its level (cull_far); a pair all of whose k queries are far is culled: its k times and rates are quiet_nan() -- what
+// contact_query would have returned, section 30 has the proof -- and its keep-flag is 0.  k_shortlist_count / _scan / _scatter: the kept
+// problems' indices in increasing order and their number, by a count per chunk of kShortChunk flags, one block's exclusive scan over the
+// chunks' counts and a scatter in which every chunk knows where it starts: no atomics, the same list in every run.  k_shortlisted:
+// k_encounter's staging and query around that list -- a trip stages up to P consecutive list entries, each through stage_fleet_pair at
+// its listed problem (the list is strictly increasing, so an entry is never below its place and the decode's p - q holds), and a query
+// finds its problem by loading the list entry again: SepLds has no spare word (section 26).  Its k outputs go to the problem's own place,
+// one 8-byte store per query: neighbouring places are no neighbours in the output.
+constexpr int kShortBlock = 256;
+constexpr int kShortEach = 8;                                  // flags per thread: one 8-byte load
+constexpr unsigned kShortChunk = kShortBlock * kShortEach;     // flags per chunk
+
+template <int D> struct ReachOut { double *lo[D], *hi[D], *slack[D]; };      // per axis: n m k, n m k, n m (null: not written)
+
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock)
+k_reach(FleetSplines<D> in, size_t vehicles, unsigned m, size_t k, int P, const double *__restrict__ lo, const double *__restrict__ hi,
+        ReachOut<D> out)
+{
+    __shared__ ExtLds L;
+#pragma unroll
+    for (int x = 0; x < D; ++x) {
+        double *__restrict__ const box_lo = out.lo[x], *__restrict__ const box_hi = out.hi[x], *__restrict__ const slack = out.slack[x];
+        auto stage_problem = [&](int q, size_t i) {
+            Knots kn = in.v[x].load(i);
+            stage_extrema(L, q, kn);
+            kn.check();
+            if (slack) slack[i] = cull_slack(kn.p0, kn.p1, kn.p2, kn.v0, kn.v1, kn.v2, kn.t0, kn.t1);
+        };
+        for_each_trip(vehicles, P, stage_problem, [&](size_t p_first, int here) {
+            const size_t e_first = p_first * k, s_first = p_first / m;
+            const unsigned r_first = (unsigned)(p_first - s_first * m);
+            stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+                const double inf = __builtin_inf();
+                const size_t sa = s_first + (r_first + (unsigned)qa) / m, sb = s_first + (r_first + (unsigned)qb) / m;
+                const size_t wa = sa * k + (e - (size_t)qa * k);                            // the scene's row, the query's column
+                const size_t wb = two ? sb * k + (e + 1 - (size_t)qb * k) : wa;
+                const double la = lo ? lo[wa] : -inf, lb = lo ? lo[wb] : -inf, ha = hi ? hi[wa] : inf, hb = hi ? hi[wb] : inf;
+                Extreme Pa, Va, Pb, Vb;
+                extrema_query<true, false>(L, qa, la, ha, Pa, Va);
+                extrema_query<true, false>(L, qb, lb, hb, Pb, Vb);
+                if (box_lo) store_pair(box_lo, e_first + e, Pa.lo_v, Pb.lo_v, two);
+                if (box_hi) store_pair(box_hi, e_first + e, Pa.hi_v, Pb.hi_v, two);
+            });
+        });
+    }
+}
+
+template <int D> struct SieveIn { const double *lo[D], *hi[D], *slack[D]; };
+
+template <int D>
+__global__ void __launch_bounds__(kShortBlock)
+k_sieve(SieveIn<D> box, size_t problems, unsigned m, size_t k, const double *__restrict__ level, int level_per_pair,
+        double *__restrict__ time, double *__restrict__ rate, unsigned char *__restrict__ kept)
+{
+    const size_t p = (size_t)blockIdx.x * kShortBlock + threadIdx.x;
+    if (p >= problems) return;
+    const unsigned pairs = fleet_pair_count(m);
+    const size_t s = p / pairs;
+    unsigned i, j;
+    fleet_pair((unsigned)(p - s * pairs), m, i, j);
+    const size_t vi = s * m + i, vj = s * m + j;
+    bool culled = true;
+    for (size_t q = 0; q < k && culled; ++q) {
+        CullBound b = cull_begin();
+#pragma unroll
+        for (int x = 0; x < D; ++x)
+            cull_add(b, box.lo[x][vi * k + q], box.hi[x][vi * k + q], box.lo[x][vj * k + q], box.hi[x][vj * k + q], box.slack[x][vi],
+                     box.slack[x][vj]);
+        culled = cull_far(b, level[level_per_pair ? p * k + q : s * k + q]);
+    }
+    kept[p] = culled ? 0 : 1;
+    if (!culled) return;
+    const double nan = quiet_nan();
+    for (size_t q = 0; q < k; ++q) {
+        if (time) time[p * k + q] = nan;
+        if (rate) rate[p * k + q] = nan;
+    }
+}
+
+// the kShortEach flags of this thread (those at or beyond `problems` count as 0), one bit each, lowest first
+__device__ __forceinline__ unsigned shortlist_flags(const unsigned char *__restrict__ kept, size_t problems, size_t first)
+{
+    unsigned bits = 0;
+    if (first + kShortEach <= problems) {      // (kept is 16-byte aligned and first a multiple of 8)
+        const uint64_t w = *reinterpret_cast<const uint64_t *>(kept + first);
+#pragma unroll
+        for (int b = 0; b < kShortEach; ++b) bits |= ((unsigned)(w >> (8 * b)) & 0xffu) ? 1u << b : 0u;
+    } else {
+        for (int b = 0; b < kShortEach; ++b)
+            if (first + (size_t)b < problems && kept[first + (size_t)b]) bits |= 1u << b;
+    }
+    return bits;
+}
+
+// the exclusive prefix sums of one value per thread over the block, and their total: kShortBlock threads, Hillis-Steele in LDS
+__device__ __forceinline__ unsigned shortlist_block_scan(unsigned (&s)[kShortBlock], unsigned mine, unsigned &total)
+{
+    const int t = (int)threadIdx.x;
+    s[t] = mine;
+    __syncthreads();
+    for (int step = 1; step < kShortBlock; step <<= 1) {
+        const unsigned add = t >= step ? s[t - step] : 0u;
+        __syncthreads();
+        s[t] += add;
+        __syncthreads();
+    }
+    total = s[kShortBlock - 1];
+    const unsigned before = s[t] - mine;
+    __syncthreads();
+    return before;
+}
+
+__global__ void __launch_bounds__(kShortBlock)
+k_shortlist_count(const unsigned char *__restrict__ kept, size_t problems, uint32_t *__restrict__ chunk_count)
+{
+    __shared__ unsigned s[kShortBlock];
+    const size_t first = ((size_t)blockIdx.x * kShortBlock + threadIdx.x) * kShortEach;
+    unsigned total;
+    shortlist_block_scan(s, (unsigned)__builtin_popcount(shortlist_flags(kept, problems, first)), total);
+    if (threadIdx.x == 0) chunk_count[blockIdx.x] = total;
+}
+
+// one block: chunk_count becomes where each chunk's entries start, *count their number.  Thread t takes the chunks [t each, (t + 1) each).
+__global__ void __launch_bounds__(kShortBlock)
+k_shortlist_scan(uint32_t *__restrict__ chunk_count, size_t chunks, uint32_t *__restrict__ count)
+{
+    __shared__ unsigned s[kShortBlock];
+    const size_t each = (chunks + kShortBlock - 1) / kShortBlock;
+    const size_t from = (size_t)threadIdx.x * each < chunks ? (size_t)threadIdx.x * each : chunks;
+    const size_t to = from + each < chunks ? from + each : chunks;
+    unsigned mine = 0;
+    for (size_t c = from; c < to; ++c) mine += chunk_count[c];
+    unsigned total;
+    unsigned at = shortlist_block_scan(s, mine, total);
+    for (size_t c = from; c < to; ++c) {
+        const unsigned here = chunk_count[c];
+        chunk_count[c] = at;
+        at += here;
+    }
+    if (threadIdx.x == 0) *count = total;
+}
+
+__global__ void __launch_bounds__(kShortBlock)
+k_shortlist_scatter(const unsigned char *__restrict__ kept, size_t problems, const uint32_t *__restrict__ chunk_start, uint32_t *__restrict__ list)
+{
+    __shared__ unsigned s[kShortBlock];
+    const size_t first = ((size_t)blockIdx.x * kShortBlock + threadIdx.x) * kShortEach;
+    const unsigned bits = shortlist_flags(kept, problems, first);
+    unsigned total;
+    size_t at = (size_t)chunk_start[blockIdx.x] + shortlist_block_scan(s, (unsigned)__builtin_popcount(bits), total);
+    for (int b = 0; b < kShortEach; ++b)
+        if (bits >> b & 1u) {
+            if (at < problems) list[at] = (uint32_t)(first + (size_t)b);      // (always: there are no more kept flags than problems)
+            ++at;
+        }
+}
+
+// Budgets as k_encounter's (section 27); the hint and what the allocator does without it are in section 30.
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
+k_shortlisted(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const double *__restrict__ level, int level_per_pair,
+              const double *__restrict__ lo, const double *__restrict__ hi, double *__restrict__ time, double *__restrict__ rate,
+              const uint32_t *__restrict__ list, const uint32_t *__restrict__ count)
+{
+    __shared__ SepLds<D> L;
+    const unsigned pairs = fleet_pair_count(m);
+    const size_t listed = *count < problems ? (size_t)*count : problems;      // the device's own count, never beyond the list
+    const size_t last = problems - 1;
+    auto stage_problem = [&](int q, size_t at) {
+        const size_t p = list[at];
+        stage_fleet_pair(L, q, in, m, pairs, p < last ? p : last);      // (an entry is a problem: the clamp never acts)
+    };
+    for_each_trip(listed, P, stage_problem, [&](size_t at_first, int here) {
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            const double inf = __builtin_inf();
+#pragma nounroll
+            for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_encounter: each query's searches have their own trip counts
+                const int q = half ? qb : qa;
+                const size_t entry = list[at_first + (size_t)q], p = entry < last ? entry : last;
+                const size_t col = e + (size_t)half - (size_t)q * k;
+                const size_t w = (size_t)((uint32_t)p / pairs) * k + col;      // the scene's row, the query's column
+                const size_t o = p * k + col;                                  // the problem's own place
+                double t, r;
+                int trips = 0;
+                contact_query<D>(L, q, level[level_per_pair ? o : w], lo ? lo[w] : -inf, hi ? hi[w] : inf, 0.0, t, r, trips);
+                time[o] = t;
+                if (rate) rate[o] = r;
+            }
+        });
+    });
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -3329,6 +3528,105 @@ hipError_t launch_fleet_contact_staggered(size_t n, size_t m, size_t k, int d, c
         hipLaunchKernelGGL(k_rendezvous<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_start, d_level_sq,
                            level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate);
     });
+}
+
+hipError_t launch_fleet_reach(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo, const double *d_hi,
+                              double *const *d_min, double *const *d_max, double *const *d_slack, hipStream_t stream)
+{
+    if (m < 2 || m > kFleetMost) return hipErrorInvalidValue;
+    return launch_on_pairs(n * m, k, d, [&](auto axes, dim3 grid, dim3 block, int P) {
+        constexpr int D = decltype(axes)::value;
+        ReachOut<D> out;
+        for (int x = 0; x < D; ++x) {
+            out.lo[x] = d_min ? d_min[x] : nullptr;
+            out.hi[x] = d_max ? d_max[x] : nullptr;
+            out.slack[x] = d_slack ? d_slack[x] : nullptr;
+        }
+        hipLaunchKernelGGL(k_reach<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), n * m, (unsigned)m, k, P, d_lo, d_hi, out);
+    });
+}
+
+namespace {
+
+// The culled entry's workspace, every part on a 16-byte boundary: per axis the boxes' two n m k arrays and the n m slacks, the n x pairs
+// keep-flags, the list, the chunks' counts, the count.
+struct CullWorkspace {
+    size_t box, slack, kept, list, chunk, count, bytes;      // offsets in bytes; box and slack: of axis 0's, the axes follow each other
+    size_t box_each, slack_each, problems, chunks;
+};
+
+size_t round16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+CullWorkspace cull_workspace(size_t n, size_t m, size_t k, int d)
+{
+    CullWorkspace w{};
+    w.problems = n * fleet_pair_count((unsigned)m);
+    w.chunks = (w.problems + kShortChunk - 1) / kShortChunk;
+    w.box_each = round16(n * m * k * sizeof(double));
+    w.slack_each = round16(n * m * sizeof(double));
+    w.box = 0;
+    w.slack = w.box + 2 * (size_t)d * w.box_each;
+    w.kept = w.slack + (size_t)d * w.slack_each;
+    w.list = w.kept + round16(w.problems);
+    w.chunk = w.list + round16(w.problems * sizeof(uint32_t));
+    w.count = w.chunk + round16(w.chunks * sizeof(uint32_t));
+    w.bytes = w.count + 16;
+    return w;
+}
+
+}  // namespace
+
+size_t fleet_cull_workspace_bytes(size_t n, size_t m, size_t k, int d)
+{
+    if (m < 2 || m > kFleetMost || d < 1 || d > 3 || n == 0 || k == 0) return 0;
+    if (n > (((size_t)1 << 32) - 1) / fleet_pair_count((unsigned)m)) return 0;      // a list entry is 32 bits
+    if (k > SIZE_MAX / 64 / (n * m)) return 0;                                       // the boxes' bytes fit
+    return cull_workspace(n, m, k, d).bytes;
+}
+
+hipError_t launch_fleet_contact_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq,
+                                       int level_per_pair, const double *d_lo, const double *d_hi, double *d_time, double *d_rate,
+                                       void *d_workspace, unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count, hipStream_t stream)
+{
+    if (!d_level_sq || !d_workspace || fleet_cull_workspace_bytes(n, m, k, d) == 0) return hipErrorInvalidValue;
+    const CullWorkspace w = cull_workspace(n, m, k, d);
+    char *const base = (char *)d_workspace;
+    double *box_lo[3], *box_hi[3], *slack[3];
+    for (int x = 0; x < d; ++x) {
+        box_lo[x] = (double *)(base + w.box + (size_t)(2 * x) * w.box_each);
+        box_hi[x] = (double *)(base + w.box + (size_t)(2 * x + 1) * w.box_each);
+        slack[x] = (double *)(base + w.slack + (size_t)x * w.slack_each);
+    }
+    unsigned char *const kept = (unsigned char *)(base + w.kept);
+    uint32_t *const list = (uint32_t *)(base + w.list), *const chunk = (uint32_t *)(base + w.chunk), *const count = (uint32_t *)(base + w.count);
+    hipError_t e = launch_fleet_reach(n, m, k, d, d_fleet, d_lo, d_hi, box_lo, box_hi, slack, stream);
+    if (e != hipSuccess) return e;
+    e = with_axes(d, [&](auto axes) {
+        constexpr int D = decltype(axes)::value;
+        SieveIn<D> box;
+        for (int x = 0; x < D; ++x) { box.lo[x] = box_lo[x]; box.hi[x] = box_hi[x]; box.slack[x] = slack[x]; }
+        hipLaunchKernelGGL(k_sieve<D>, dim3((unsigned)((w.problems + kShortBlock - 1) / kShortBlock)), dim3(kShortBlock), 0, stream, box,
+                           w.problems, (unsigned)m, k, d_level_sq, level_per_pair, d_time, d_rate, kept);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_shortlist_count, dim3((unsigned)w.chunks), dim3(kShortBlock), 0, stream, kept, w.problems, chunk);
+    hipLaunchKernelGGL(k_shortlist_scan, dim3(1), dim3(kShortBlock), 0, stream, chunk, w.chunks, count);
+    hipLaunchKernelGGL(k_shortlist_scatter, dim3((unsigned)w.chunks), dim3(kShortBlock), 0, stream, kept, w.problems, chunk, list);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (d_time) {
+        e = launch_on_fleet(n, m, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
+            constexpr int D = decltype(axes)::value;
+            hipLaunchKernelGGL(k_shortlisted<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_level_sq,
+                               level_per_pair, d_lo, d_hi, d_time, d_rate, list, count);
+        });
+        if (e != hipSuccess) return e;
+    }
+    if (d_kept) e = hipMemcpyAsync(d_kept, kept, w.problems, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && d_list) e = hipMemcpyAsync(d_list, list, w.problems * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && d_count) e = hipMemcpyAsync(d_count, count, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
+    return e;
 }
 
 // ---- plot data by problem index: a range [first, first + count) of problems, wherever they lie in the batch ----
