@@ -26,7 +26,10 @@ KS = (1, 2, 33, 63, 64, 65, 200)
 BIG = 4097
 # beyond the grid's cap: at k = 1 and 2 a block takes 128 problems per trip, so 300,001 problems are 2,344 trips for the grid's 2,048 blocks,
 # the last one partial and the total odd; the rows looked at are the first 257, those around problem 2,048 x 128 = 262,144, where the
-# blocks start their second trip, and the last 257
+# blocks start their second trip, and the last 257.  The kernels of the later sections -- k_gap, k_tracking with its vjp and jvp, k_meeting,
+# k_separation, k_contact, k_fleet, k_encounter, k_stagger, k_rendezvous, k_reach (GRID_N pair problems; 100,001 scenes of three vehicles,
+# 300,003 problems, the rows whole scenes) and k_shortlisted (a list longer than 262,144) -- have their cases on these rows in
+# grid_cap_gpu_cases.py and shortlist_gpu_cases.py
 GRID_N, GRID_KS = 300001, (1, 2)
 GRID_ROWS = (slice(0, 257), slice(262016, 262401), slice(GRID_N - 257, GRID_N))
 PAD, SENTINEL = 16, 7.0      # doubles behind every output buffer, and what they hold
