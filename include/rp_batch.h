@@ -83,7 +83,9 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      rp_trajectory_fleet_separation_staggered and rp_trajectory_fleet_contact_staggered (those two with a start time per vehicle; new
  *      entries only, the revision stays); rp_trajectory_fleet_reach, rp_trajectory_fleet_contact_culled(_workspace) and
  *      rp_trajectory_fleet_contact_candidates (the fleet's position boxes, and the fleet's first contacts with a broad phase that skips
- *      the pairs whose boxes prove them apart; new entries only, the revision stays) */
+ *      the pairs whose boxes prove them apart; new entries only, the revision stays); rp_trajectory_fleet_reach_staggered,
+ *      rp_trajectory_fleet_contact_staggered_culled(_workspace) and rp_trajectory_fleet_contact_staggered_candidates (that broad phase
+ *      with a start time per vehicle: a query is out when it is refused or box-far; new entries only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -838,6 +840,39 @@ RP_API int rp_trajectory_fleet_contact_culled(int device, void *stream, size_t n
 RP_API int rp_trajectory_fleet_contact_candidates(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
                                                   const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi,
                                                   void *d_workspace, size_t workspace_bytes, unsigned char *d_kept);
+
+/* ---- that broad phase with a start time per vehicle (new entries only, the revision stays) ----
+ * rp_trajectory_fleet_reach_staggered: rp_trajectory_fleet_reach with d_start (n x m, required, as rp_trajectory_fleet_contact_staggered's):
+ * the window of vehicle v is taken on v's own clock, [lo - start_v, hi - start_v], one fp64 subtraction each (a NULL end is the infinity
+ * before the subtraction), and the box is rp_trajectory_extrema's pos_min and pos_max of that spline over that window, bit for bit.
+ *
+ * rp_trajectory_fleet_contact_staggered_culled: rp_trajectory_fleet_contact_staggered's outputs, bit for bit in d_time, d_time_local and
+ * d_rate, NaN bits included, for the same first fifteen arguments, which it refuses as that entry does and in its order (any output may
+ * be NULL but not all).  In front of the search, per pair and query two tests: refused -- the query's window on the first vehicle's clock
+ * does not meet the two vehicles' common domain, decided by the search's own fp64 operations on the same numbers, exactly -- or far --
+ * the boxes above are further apart than the level, with section 30's slacks and margin and an allowance for the time error of the
+ * second vehicle's clock (section 31 proves that either gives NaN outputs).  A pair whose k queries are each refused or far gets its NaN
+ * written directly; the search runs over the list of the others.  A pair with a NaN or infinite start is kept; so is a query with a NaN or
+ * infinite box end, slack, speed bound or total time that is not refused.  Every element of each non-NULL output is written exactly once.
+ * d_workspace: as rp_trajectory_fleet_contact_culled's, of rp_trajectory_fleet_contact_staggered_culled_workspace's size; d_kept, d_list,
+ * d_count and the refusals beyond rp_trajectory_fleet_contact_staggered's: as there, before any device call.  No block waits for another,
+ * no atomics: the same list and bits in every run.
+ *
+ * rp_trajectory_fleet_contact_staggered_candidates: the broad phase alone -- boxes, the two tests, no search: d_kept, required.
+ * All asynchronous on `stream`; none throws. */
+RP_API int rp_trajectory_fleet_reach_staggered(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                                               const double *d_start, const double *d_lo, const double *d_hi, double *const *d_min,
+                                               double *const *d_max);
+RP_API int rp_trajectory_fleet_contact_staggered_culled_workspace(size_t n, size_t m, size_t k, int d, size_t *bytes);
+RP_API int rp_trajectory_fleet_contact_staggered_culled(int device, void *stream, size_t n, size_t m, size_t k, int d,
+                                                        const double *const *d_fleet, const double *d_start, const double *d_level_sq,
+                                                        int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
+                                                        double *d_time_local, double *d_rate, void *d_workspace, size_t workspace_bytes,
+                                                        unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count);
+RP_API int rp_trajectory_fleet_contact_staggered_candidates(int device, void *stream, size_t n, size_t m, size_t k, int d,
+                                                            const double *const *d_fleet, const double *d_start, const double *d_level_sq,
+                                                            int level_per_pair, const double *d_lo, const double *d_hi, void *d_workspace,
+                                                            size_t workspace_bytes, unsigned char *d_kept);
 
 /* The same as rp_batch_sample_device for problems [first, first + count) only (what onDraw needs for the watched problem). Synchronous. */
 RP_API int rp_batch_sample_range(rp_batch *b, size_t first, size_t count, double *pos66, double *acc4);

@@ -2353,6 +2353,37 @@ class _TrajectoryStaggeredContact(torch.autograd.Function):
         return torch.where(missing, torch.full_like(rate, float("nan")), time_dot), None, None
 
 
+class _TrajectoryStaggeredContactCulled(_TrajectoryStaggeredContact):
+    """_TrajectoryStaggeredContact with the broad phase in front of the forward:
+    rp_trajectory_fleet_contact_staggered_culled gives the same bits in the three outputs, so what is saved and both derivative rules are
+    the parent's, unchanged."""
+
+    @staticmethod
+    def forward(d, m, *inputs):
+        start, level, lo, hi = (_dense(t) for t in inputs[8 * d:])
+        level, per_pair = _fleet_level(level)
+        n, k = level.shape[0], level.shape[-1]
+        with torch.cuda.device(inputs[0].device):
+            size = capi.trajectory_fleet_contact_staggered_culled_workspace(n, m, k, d)
+            work = torch.empty(size, dtype=torch.uint8, device=inputs[0].device)
+
+        def entry(*args):
+            capi.trajectory_fleet_contact_staggered_culled(*args, _plain(work).data_ptr(), size)
+
+        return _fleet_forward(entry, d, m, inputs, n, k, 3, lambda addr: (addr(start), addr(level), int(per_pair), addr(lo), addr(hi)))
+
+
+def _check_broad_phase(broad_phase, start, who):
+    """broad_phase: False, True (not with start=) or "staggered" (only with start=)."""
+    if isinstance(broad_phase, str):
+        if broad_phase != "staggered":
+            raise ValueError('%s: broad_phase must be False, True or "staggered", got %r' % (who, broad_phase))
+        if start is None:
+            raise ValueError('%s: broad_phase="staggered" needs start=; without start times broad_phase=True is the broad phase' % who)
+    elif broad_phase and start is not None:
+        raise ValueError(who + ': broad_phase=True does not take start=; broad_phase="staggered" is the broad phase of the staggered entries')
+
+
 def _check_fleet_level(n, pairs, radius, level_sq, who):
     """The level of trajectory_fleet_contact, shape and type (the device comes after the windows' shapes): radius or level_sq, float64,
     (n, k), (k,) -- one level for all pairs of a scene -- or (n, pairs, k) -- one per pair.  Returns (its name, the level in units of
@@ -2408,12 +2439,16 @@ def trajectory_fleet_contact(fleet, radius=None, lo=None, hi=None, *, level_sq=N
     NaN written directly for the pairs whose bound is above the level in all k queries, and the search over a device-side list of the
     rest.  The same bits out, NaN included, hence the same gradients; the time goes with the number of near pairs and not with m^2.  The
     workspace is a torch allocation on the current stream.  Not with start= (ValueError).  False is the call without it: the same
-    launches and the same bits as before."""
+    launches and the same bits as before.
+
+    broad_phase="staggered" is the broad phase with start= (without start= a ValueError): one
+    rp_trajectory_fleet_contact_staggered_culled call.  A query is out when the two vehicles are never under way together in its window
+    -- decided exactly, by the search's own operations -- or when their boxes, each over the window on its own clock, are far; a pair all
+    of whose queries are out gets its NaN without a search.  The same bits out, hence the same gradients, start's included."""
     who = "trajectory_fleet_contact"
     if (radius is None) == (level_sq is None):
         raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
-    if broad_phase and start is not None:
-        raise ValueError(who + ": broad_phase=True does not take start=; the staggered entries have no broad phase")
+    _check_broad_phase(broad_phase, start, who)
     n, m, d, tables = _check_fleet(fleet, who)
     level, lo, hi = _check_fleet_arguments(n, m, fleet[0].device, start,
                                            lambda: _check_fleet_queries(n, m, fleet[0].device, radius, level_sq, lo, hi, who), who)
@@ -2421,7 +2456,8 @@ def trajectory_fleet_contact(fleet, radius=None, lo=None, hi=None, *, level_sq=N
     if start is None:
         function = _TrajectoryFleetContactCulled if broad_phase else _TrajectoryFleetContact
         return function.apply(d, m, *[t for table in tables for t in table], level, lo, hi)[0]
-    return _TrajectoryStaggeredContact.apply(d, m, *[t for table in tables for t in table], start, level, lo, hi)[0]
+    function = _TrajectoryStaggeredContactCulled if broad_phase else _TrajectoryStaggeredContact      # (with start=: "staggered" or False)
+    return function.apply(d, m, *[t for table in tables for t in table], start, level, lo, hi)[0]
 
 
 def min_time_fleet_contact(pos, radius=None, lo=None, hi=None, *, level_sq=None, vel=None, synchronize=True, gap_tol=1e-8, max_iter=200,
@@ -2430,12 +2466,12 @@ def min_time_fleet_contact(pos, radius=None, lo=None, hi=None, *, level_sq=None,
     vel, synchronize and the solution returned are its -- with trajectory_fleet_contact's radius (or level_sq=), lo and hi.  Returns
     (t_contact, solution).  Plain composition: the times are differentiable to first order in the positions, the end velocities and the
     radius, in both modes.  start= (n, m): trajectory_fleet_contact's start times, checked before the solve and differentiable.
-    broad_phase=True: trajectory_fleet_contact's bounding-box cull in front of the search; the same bits; not with start=."""
+    broad_phase=True: trajectory_fleet_contact's bounding-box cull in front of the search; the same bits; not with start=.
+    broad_phase="staggered": its broad phase with start=; the same bits."""
     who = "min_time_fleet_contact"
     if (radius is None) == (level_sq is None):
         raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
-    if broad_phase and start is not None:
-        raise ValueError(who + ": broad_phase=True does not take start=; the staggered entries have no broad phase")
+    _check_broad_phase(broad_phase, start, who)
     n, m, d = _check_fleet_problem(pos, vel, synchronize, who)
     # before the solve: a bad query costs none
     level, lo, hi = _check_fleet_arguments(n, m, pos[0].device, start,
@@ -2444,18 +2480,20 @@ def min_time_fleet_contact(pos, radius=None, lo=None, hi=None, *, level_sq=None,
     return trajectory_fleet_contact(spline, None, lo, hi, level_sq=level, start=start, broad_phase=broad_phase), solution
 
 
-def fleet_contact_candidates(fleet, radius=None, lo=None, hi=None, *, level_sq=None):
+def fleet_contact_candidates(fleet, radius=None, lo=None, hi=None, *, level_sq=None, start=None):
     """The broad phase of trajectory_fleet_contact(..., broad_phase=True) alone: a (n, pairs) bool tensor, in fleet_pairs(m)'s order, True
     where the pair would go to the search and False where its position boxes over the window prove, with the margin of DESIGN.md section
     30, that it is further apart than the level in all k queries -- trajectory_fleet_contact's times of such a pair are NaN.  A kept pair
     need not have a contact.  fleet, radius (or level_sq=), lo and hi: exactly trajectory_fleet_contact's.  One
-    rp_trajectory_fleet_contact_candidates call on the current stream: boxes, sieve, no search.  Not differentiable."""
+    rp_trajectory_fleet_contact_candidates call on the current stream: boxes, sieve, no search.  Not differentiable.  start= (n, m):
+    trajectory_fleet_contact's start times; the flags are then those of broad_phase="staggered" (DESIGN.md section 31), one
+    rp_trajectory_fleet_contact_staggered_candidates call.  start=None: exactly the call without it."""
     who = "fleet_contact_candidates"
     if (radius is None) == (level_sq is None):
         raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
     n, m, d, tables = _check_fleet(fleet, who)
     device = fleet[0].device
-    level, lo, hi = _check_fleet_queries(n, m, device, radius, level_sq, lo, hi, who)
+    level, lo, hi = _check_fleet_arguments(n, m, device, start, lambda: _check_fleet_queries(n, m, device, radius, level_sq, lo, hi, who), who)
     _check_fleet_devices(fleet, who)
     with torch.no_grad():
         level, per_pair = _fleet_level(_dense(level.detach()))
@@ -2464,25 +2502,34 @@ def fleet_contact_candidates(fleet, radius=None, lo=None, hi=None, *, level_sq=N
         splines = [_dense(t.detach()) if t is not None else None for table in tables for t in table]
         kept = torch.empty((n, m * (m - 1) // 2), dtype=torch.uint8, device=device)
         with torch.cuda.device(device):
-            work, size = _cull_workspace(n, m, k, d, device)
             addr = lambda t: t.data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_fleet_contact_candidates(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d,
-                                                     [addr(t) for t in splines], addr(level), int(per_pair), addr(lo), addr(hi),
-                                                     work.data_ptr(), size, kept.data_ptr())
+            if start is None:
+                work, size = _cull_workspace(n, m, k, d, device)
+                capi.trajectory_fleet_contact_candidates(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d,
+                                                         [addr(t) for t in splines], addr(level), int(per_pair), addr(lo), addr(hi),
+                                                         work.data_ptr(), size, kept.data_ptr())
+            else:
+                size = capi.trajectory_fleet_contact_staggered_culled_workspace(n, m, k, d)
+                work = torch.empty(size, dtype=torch.uint8, device=device)
+                capi.trajectory_fleet_contact_staggered_candidates(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d,
+                                                                   [addr(t) for t in splines], addr(_dense(start.detach())), addr(level),
+                                                                   int(per_pair), addr(lo), addr(hi), work.data_ptr(), size, kept.data_ptr())
     return kept != 0
 
 
-def trajectory_fleet_reach(fleet, lo=None, hi=None):
+def trajectory_fleet_reach(fleet, lo=None, hi=None, *, start=None):
     """How far every vehicle of a fleet gets in every axis: (box_min, box_max), (n, m, k, d) each -- the least and greatest position of
     vehicle v of scene s in axis c over the scene's window [lo, hi][s, q], bit for bit trajectory_extrema's pos_min and pos_max of that
     spline and window (its clamp to [0, T]; NaN for an empty clamped window and for a vehicle with a bad duration).  fleet, lo, hi:
     exactly trajectory_fleet_separation's; both windows None: k = 1, each spline's whole time.  One rp_trajectory_fleet_reach launch on
     the current stream; no window tensor repeated per vehicle is made.  These are the boxes of trajectory_fleet_contact's broad phase
-    (DESIGN.md section 30).  Not differentiable: trajectory_extrema is the differentiable form."""
+    (DESIGN.md section 30).  Not differentiable: trajectory_extrema is the differentiable form.  start= (n, m): trajectory_fleet_contact's
+    start times; vehicle v's window is then [lo - start_v, hi - start_v], on its own clock, one
+    rp_trajectory_fleet_reach_staggered launch.  start=None: exactly the call without it."""
     who = "trajectory_fleet_reach"
     n, m, d, tables = _check_fleet(fleet, who)
     device = fleet[0].device
-    lo, hi = _check_fleet_windows(n, device, lo, hi, who)
+    lo, hi = _check_fleet_arguments(n, m, device, start, lambda: _check_fleet_windows(n, device, lo, hi, who), who)
     _check_fleet_devices(fleet, who)
     with torch.no_grad():
         lo, hi = (_dense(t.detach()) if t is not None else None for t in (lo, hi))
@@ -2493,8 +2540,12 @@ def trajectory_fleet_reach(fleet, lo=None, hi=None):
         box = flat[:, :, :size].unflatten(2, (n, m, k))      # a view: axis c's (n, m, k) array is contiguous
         with torch.cuda.device(device):
             addr = lambda t: t.data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_fleet_reach(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in splines],
-                                        addr(lo), addr(hi), [box[0, c].data_ptr() for c in range(d)], [box[1, c].data_ptr() for c in range(d)])
+            tail = (addr(lo), addr(hi), [box[0, c].data_ptr() for c in range(d)], [box[1, c].data_ptr() for c in range(d)])
+            head = (device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in splines])
+            if start is None:
+                capi.trajectory_fleet_reach(*head, *tail)
+            else:
+                capi.trajectory_fleet_reach_staggered(*head, addr(_dense(start.detach())), *tail)
     return box[0].permute(1, 2, 3, 0), box[1].permute(1, 2, 3, 0)
 
 

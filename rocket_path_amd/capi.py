@@ -137,6 +137,16 @@ SIGNATURES = {
                                                           _vp, _vp, _vp]),
     "rp_trajectory_fleet_contact_candidates": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
                                                               ctypes.POINTER(_vp), _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "rp_trajectory_fleet_reach_staggered": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                           ctypes.POINTER(_vp), _vp, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rp_trajectory_fleet_contact_staggered_culled_workspace": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
+                                                                              ctypes.POINTER(ctypes.c_size_t)]),
+    "rp_trajectory_fleet_contact_staggered_culled": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                                                    ctypes.c_int, ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int, _vp, _vp, _vp,
+                                                                    _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "rp_trajectory_fleet_contact_staggered_candidates": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                                                        ctypes.c_int, ctypes.POINTER(_vp), _vp, _vp, ctypes.c_int, _vp, _vp,
+                                                                        _vp, ctypes.c_size_t, _vp]),
     "rp_trajectory_tracking": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp,
                                               _vp, ctypes.POINTER(_vp)]),
     "rp_trajectory_tracking_vjp": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp,
@@ -455,6 +465,50 @@ def trajectory_fleet_contact_candidates(device, stream, n, m, k, d, fleet, d_lev
     check(load_library().rp_trajectory_fleet_contact_candidates(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d),
                                                                 vp(d_level_sq), int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_workspace),
                                                                 int(workspace_bytes), vp(d_kept)))
+
+
+def trajectory_fleet_reach_staggered(device, stream, n, m, k, d, fleet, d_start, d_lo=None, d_hi=None, d_min=None, d_max=None):
+    """rp_trajectory_fleet_reach_staggered: trajectory_fleet_reach with a start time per vehicle, d_start (n, m), required: vehicle v's
+    window is [lo - start_v, hi - start_v], on its own clock."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = _fleet_sizes("trajectory_fleet_reach_staggered", d, m)
+    check(load_library().rp_trajectory_fleet_reach_staggered(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_start),
+                                                             vp(d_lo), vp(d_hi), _axis_outputs(d_min, d, "d_min"),
+                                                             _axis_outputs(d_max, d, "d_max")))
+
+
+def trajectory_fleet_contact_staggered_culled_workspace(n, m, k, d):
+    """rp_trajectory_fleet_contact_staggered_culled_workspace: the bytes of workspace the staggered culled entries need for (n, m, k, d)."""
+    d, m = _fleet_sizes("trajectory_fleet_contact_staggered_culled_workspace", d, m)
+    size = ctypes.c_size_t(0)
+    check(load_library().rp_trajectory_fleet_contact_staggered_culled_workspace(int(n), m, int(k), d, ctypes.byref(size)))
+    return size.value
+
+
+def trajectory_fleet_contact_staggered_culled(device, stream, n, m, k, d, fleet, d_start, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None,
+                                              d_time=None, d_time_local=None, d_rate=None, d_workspace=None, workspace_bytes=0, d_kept=None,
+                                              d_list=None, d_count=None):
+    """rp_trajectory_fleet_contact_staggered_culled: trajectory_fleet_contact_staggered's outputs, bit for bit, for the same first fifteen
+    arguments, with the broad phase in front: a pair each of whose k queries is refused (no common time in the window) or box-far gets its
+    NaN without a search.  The workspace (trajectory_fleet_contact_staggered_culled_workspace), d_kept, d_list and d_count as
+    trajectory_fleet_contact_culled's."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = _fleet_sizes("trajectory_fleet_contact_staggered_culled", d, m)
+    check(load_library().rp_trajectory_fleet_contact_staggered_culled(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d),
+                                                                      vp(d_start), vp(d_level_sq), int(level_per_pair), vp(d_lo), vp(d_hi),
+                                                                      vp(d_time), vp(d_time_local), vp(d_rate), vp(d_workspace),
+                                                                      int(workspace_bytes), vp(d_kept), vp(d_list), vp(d_count)))
+
+
+def trajectory_fleet_contact_staggered_candidates(device, stream, n, m, k, d, fleet, d_start, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None,
+                                                  d_workspace=None, workspace_bytes=0, d_kept=None):
+    """rp_trajectory_fleet_contact_staggered_candidates: the broad phase of trajectory_fleet_contact_staggered_culled alone: d_kept
+    (n pairs bytes, required), 1 where the pair would go to the search.  The workspace as there."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = _fleet_sizes("trajectory_fleet_contact_staggered_candidates", d, m)
+    check(load_library().rp_trajectory_fleet_contact_staggered_candidates(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d),
+                                                                          vp(d_start), vp(d_level_sq), int(level_per_pair), vp(d_lo),
+                                                                          vp(d_hi), vp(d_workspace), int(workspace_bytes), vp(d_kept)))
 
 
 def tracking_table(addresses):

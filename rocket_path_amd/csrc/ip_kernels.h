@@ -240,5 +240,16 @@ size_t fleet_cull_workspace_bytes(size_t n, size_t m, size_t k, int d);
 hipError_t launch_fleet_contact_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq,
                                        int level_per_pair, const double *d_lo, const double *d_hi, double *d_time, double *d_rate,
                                        void *d_workspace, unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count, hipStream_t stream);
+// the same with a start time per vehicle: the boxes on each vehicle's own clock, with d_total and d_speed, d pointers
+// to n x m each, next to the slacks (null table: not wanted); the workspace; and launch_fleet_contact_staggered with the broad phase in
+// front -- all three outputs null: the broad phase alone
+hipError_t launch_fleet_reach_staggered(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
+                                        const double *d_lo, const double *d_hi, double *const *d_min, double *const *d_max,
+                                        double *const *d_slack, double *const *d_total, double *const *d_speed, hipStream_t stream);
+size_t fleet_stagger_cull_workspace_bytes(size_t n, size_t m, size_t k, int d);
+hipError_t launch_fleet_contact_staggered_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
+                                                 const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi,
+                                                 double *d_time, double *d_time_local, double *d_rate, void *d_workspace,
+                                                 unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count, hipStream_t stream);
 
 }  // namespace rp

@@ -3084,6 +3084,142 @@ k_shortlisted(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, 
     });
 }
 
+// ---- the broad phase with a start time per vehicle (rp_trajectory_fleet_contact_staggered_culled, rp_trajectory_fleet_reach_staggered;
+// DESIGN.md section 31) ----
+// The same four passes around k_rendezvous' query.  k_span: k_reach with the window of vehicle v taken on v's own clock,
+// [lo - s_v, hi - s_v], StartOf::load's subtraction, so the box window of a pair's first vehicle is the search's window bit for bit; per
+// (vehicle, axis) it also leaves the checked total time -- stage_vehicles' Ta / Tb -- and a bound of the spline's speed.  k_winnow: one
+// thread per (scene, pair); a pair with a start that is not finite is kept; a query is out when contact_query would refuse it before its
+// walk (cull_refused: its own operations on the stored totals) or when the boxes are far with the time error of t - delay allowed for
+// (cull_add_staggered); a pair all of whose queries are out is culled and gets quiet_nan() in its k times, local times and rates.  The
+// list kernels are section 30's.  k_appointed: k_shortlisted's staging and stores around StartOf::load and contact_query with a delay.
+template <int D> struct SpanOut { double *lo[D], *hi[D], *slack[D], *total[D], *speed[D]; };      // n m k, n m k, n m, n m, n m (null: not written)
+
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock)
+k_span(FleetSplines<D> in, size_t vehicles, unsigned m, size_t k, int P, const double *__restrict__ start, const double *__restrict__ lo,
+       const double *__restrict__ hi, SpanOut<D> out)
+{
+    __shared__ ExtLds L;
+#pragma unroll
+    for (int x = 0; x < D; ++x) {
+        double *__restrict__ const box_lo = out.lo[x], *__restrict__ const box_hi = out.hi[x], *__restrict__ const slack = out.slack[x];
+        double *__restrict__ const total = out.total[x], *__restrict__ const speed = out.speed[x];
+        auto stage_problem = [&](int q, size_t i) {
+            Knots kn = in.v[x].load(i);
+            stage_extrema(L, q, kn);
+            kn.check();
+            const double T = kn.t0 + kn.t1;      // stage_vehicles' Ta / Tb
+            if (slack) slack[i] = cull_slack(kn.p0, kn.p1, kn.p2, kn.v0, kn.v1, kn.v2, kn.t0, kn.t1);
+            if (total) total[i] = T;
+            if (speed)
+                speed[i] = cull_speed(L.e.c[0][1][q], L.e.c[0][2][q], L.e.c[0][3][q], kn.t0, L.e.c[1][1][q], L.e.c[1][2][q], L.e.c[1][3][q], kn.t1, T);
+        };
+        for_each_trip(vehicles, P, stage_problem, [&](size_t p_first, int here) {
+            const size_t e_first = p_first * k, s_first = p_first / m;
+            const unsigned r_first = (unsigned)(p_first - s_first * m);
+            stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+                const double inf = __builtin_inf();
+                const size_t sa = s_first + (r_first + (unsigned)qa) / m, sb = s_first + (r_first + (unsigned)qb) / m;
+                const size_t wa = sa * k + (e - (size_t)qa * k);                            // the scene's row, the query's column
+                const size_t wb = two ? sb * k + (e + 1 - (size_t)qb * k) : wa;
+                const double start_a = start[p_first + (size_t)qa], start_b = start[p_first + (size_t)qb];      // a problem is a vehicle
+                const double la = (lo ? lo[wa] : -inf) - start_a, lb = (lo ? lo[wb] : -inf) - start_b;
+                const double ha = (hi ? hi[wa] : inf) - start_a, hb = (hi ? hi[wb] : inf) - start_b;
+                Extreme Pa, Va, Pb, Vb;
+                extrema_query<true, false>(L, qa, la, ha, Pa, Va);
+                extrema_query<true, false>(L, qb, lb, hb, Pb, Vb);
+                if (box_lo) store_pair(box_lo, e_first + e, Pa.lo_v, Pb.lo_v, two);
+                if (box_hi) store_pair(box_hi, e_first + e, Pa.hi_v, Pb.hi_v, two);
+            });
+        });
+    }
+}
+
+template <int D> struct WinnowIn { const double *lo[D], *hi[D], *slack[D], *total[D], *speed[D]; };
+
+template <int D>
+__global__ void __launch_bounds__(kShortBlock)
+k_winnow(WinnowIn<D> box, size_t problems, unsigned m, size_t k, const double *__restrict__ start, const double *__restrict__ level,
+         int level_per_pair, const double *__restrict__ lo, const double *__restrict__ hi, double *__restrict__ time,
+         double *__restrict__ time_local, double *__restrict__ rate, unsigned char *__restrict__ kept)
+{
+    const size_t p = (size_t)blockIdx.x * kShortBlock + threadIdx.x;
+    if (p >= problems) return;
+    const double inf = __builtin_inf();
+    const unsigned pairs = fleet_pair_count(m);
+    const size_t s = p / pairs;
+    unsigned i, j;
+    fleet_pair((unsigned)(p - s * pairs), m, i, j);
+    const size_t vi = s * m + i, vj = s * m + j;
+    const double s_i = start[vi], s_j = start[vj];
+    const double delay = s_j - s_i;      // StartOf::load's
+    bool culled = cull_finite(s_i) && cull_finite(s_j);      // a start that is not finite: the search makes the NaNs
+    CullDomain domain = cull_domain_begin();
+#pragma unroll
+    for (int x = 0; x < D; ++x) cull_domain_first(domain, box.total[x][vi]);
+#pragma unroll
+    for (int x = 0; x < D; ++x) cull_domain_second(domain, delay, box.total[x][vj]);
+    for (size_t q = 0; q < k && culled; ++q) {
+        const double l = (lo ? lo[s * k + q] : -inf) - s_i, h = (hi ? hi[s * k + q] : inf) - s_i;
+        const double reach = level[level_per_pair ? p * k + q : s * k + q];
+        if (cull_refused(domain, delay, reach, l, h)) continue;
+        CullBound b = cull_begin();
+#pragma unroll
+        for (int x = 0; x < D; ++x)
+            cull_add_staggered(b, box.lo[x][vi * k + q], box.hi[x][vi * k + q], box.lo[x][vj * k + q], box.hi[x][vj * k + q], box.slack[x][vi],
+                               box.slack[x][vj], box.speed[x][vi], box.speed[x][vj], box.total[x][vi], box.total[x][vj]);
+        culled = cull_far(b, reach);
+    }
+    kept[p] = culled ? 0 : 1;
+    if (!culled) return;
+    const double nan = quiet_nan();
+    for (size_t q = 0; q < k; ++q) {
+        if (time) time[p * k + q] = nan;
+        if (time_local) time_local[p * k + q] = nan;
+        if (rate) rate[p * k + q] = nan;
+    }
+}
+
+// Budgets as k_rendezvous' (section 28).
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
+k_appointed(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const double *__restrict__ start,
+            const double *__restrict__ level, int level_per_pair, const double *__restrict__ lo, const double *__restrict__ hi,
+            double *__restrict__ time, double *__restrict__ time_local, double *__restrict__ rate, const uint32_t *__restrict__ list,
+            const uint32_t *__restrict__ count)
+{
+    __shared__ SepLds<D> L;
+    const unsigned pairs = fleet_pair_count(m);
+    const StartOf clock{start, lo, hi, m, pairs};
+    const size_t listed = *count < problems ? (size_t)*count : problems;      // the device's own count, never beyond the list
+    const size_t last = problems - 1;
+    auto stage_problem = [&](int q, size_t at) {
+        const size_t p = list[at];
+        stage_fleet_pair(L, q, in, m, pairs, p < last ? p : last);      // (an entry is a problem: the clamp never acts)
+    };
+    for_each_trip(listed, P, stage_problem, [&](size_t at_first, int here) {
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+#pragma nounroll
+            for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_rendezvous: each query's searches have their own trip counts
+                const int q = half ? qb : qa;
+                const size_t entry = list[at_first + (size_t)q], p = entry < last ? entry : last;
+                const size_t col = e + (size_t)half - (size_t)q * k;
+                const uint32_t s = (uint32_t)p / pairs;
+                const size_t w = (size_t)s * k + col;      // the scene's row, the query's column
+                const size_t o = p * k + col;              // the problem's own place
+                double s_i, delay, l, h, t, rt;
+                clock.load(s, (uint32_t)p - s * pairs, w, s_i, delay, l, h);
+                int trips = 0;
+                contact_query<D>(L, q, level[level_per_pair ? o : w], l, h, delay, t, rt, trips);
+                if (time) time[o] = t + s_i;
+                if (time_local) time_local[o] = t;
+                if (rate) rate[o] = rt;
+            }
+        });
+    });
+}
+
 // ---- plot data ----
 // Per problem 66 positions (drawSegment, onedpath_ip.cpp:1065-1088, 33 per segment) and 4 end accelerations
 // (plotAcceleration, 1024-1027).  The launch moves 64 B of state in and 560 B out per problem: it has to be an HBM-write
@@ -3557,7 +3693,8 @@ struct CullWorkspace {
 
 size_t round16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
-CullWorkspace cull_workspace(size_t n, size_t m, size_t k, int d)
+// per_vehicle: the n m arrays per axis -- the slacks; with a start per vehicle (section 31) the totals and the speed bounds behind them
+CullWorkspace cull_workspace(size_t n, size_t m, size_t k, int d, int per_vehicle = 1)
 {
     CullWorkspace w{};
     w.problems = n * fleet_pair_count((unsigned)m);
@@ -3566,12 +3703,21 @@ CullWorkspace cull_workspace(size_t n, size_t m, size_t k, int d)
     w.slack_each = round16(n * m * sizeof(double));
     w.box = 0;
     w.slack = w.box + 2 * (size_t)d * w.box_each;
-    w.kept = w.slack + (size_t)d * w.slack_each;
+    w.kept = w.slack + (size_t)per_vehicle * (size_t)d * w.slack_each;
     w.list = w.kept + round16(w.problems);
     w.chunk = w.list + round16(w.problems * sizeof(uint32_t));
     w.count = w.chunk + round16(w.chunks * sizeof(uint32_t));
     w.bytes = w.count + 16;
     return w;
+}
+
+// the list of the kept problems and its length from the flags (section 30's third pass)
+hipError_t launch_shortlist(const CullWorkspace &w, const unsigned char *kept, uint32_t *chunk, uint32_t *count, uint32_t *list, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_shortlist_count, dim3((unsigned)w.chunks), dim3(kShortBlock), 0, stream, kept, w.problems, chunk);
+    hipLaunchKernelGGL(k_shortlist_scan, dim3(1), dim3(kShortBlock), 0, stream, chunk, w.chunks, count);
+    hipLaunchKernelGGL(k_shortlist_scatter, dim3((unsigned)w.chunks), dim3(kShortBlock), 0, stream, kept, w.problems, chunk, list);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -3610,16 +3756,84 @@ hipError_t launch_fleet_contact_culled(size_t n, size_t m, size_t k, int d, cons
         return hipGetLastError();
     });
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_shortlist_count, dim3((unsigned)w.chunks), dim3(kShortBlock), 0, stream, kept, w.problems, chunk);
-    hipLaunchKernelGGL(k_shortlist_scan, dim3(1), dim3(kShortBlock), 0, stream, chunk, w.chunks, count);
-    hipLaunchKernelGGL(k_shortlist_scatter, dim3((unsigned)w.chunks), dim3(kShortBlock), 0, stream, kept, w.problems, chunk, list);
-    e = hipGetLastError();
+    e = launch_shortlist(w, kept, chunk, count, list, stream);
     if (e != hipSuccess) return e;
     if (d_time) {
         e = launch_on_fleet(n, m, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
             constexpr int D = decltype(axes)::value;
             hipLaunchKernelGGL(k_shortlisted<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_level_sq,
                                level_per_pair, d_lo, d_hi, d_time, d_rate, list, count);
+        });
+        if (e != hipSuccess) return e;
+    }
+    if (d_kept) e = hipMemcpyAsync(d_kept, kept, w.problems, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && d_list) e = hipMemcpyAsync(d_list, list, w.problems * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && d_count) e = hipMemcpyAsync(d_count, count, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
+    return e;
+}
+
+// ---- the same with a start time per vehicle (section 31) ----
+hipError_t launch_fleet_reach_staggered(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
+                                        const double *d_lo, const double *d_hi, double *const *d_min, double *const *d_max,
+                                        double *const *d_slack, double *const *d_total, double *const *d_speed, hipStream_t stream)
+{
+    if (m < 2 || m > kFleetMost || !d_start) return hipErrorInvalidValue;
+    return launch_on_pairs(n * m, k, d, [&](auto axes, dim3 grid, dim3 block, int P) {
+        constexpr int D = decltype(axes)::value;
+        SpanOut<D> out;
+        for (int x = 0; x < D; ++x) {
+            out.lo[x] = d_min ? d_min[x] : nullptr;
+            out.hi[x] = d_max ? d_max[x] : nullptr;
+            out.slack[x] = d_slack ? d_slack[x] : nullptr;
+            out.total[x] = d_total ? d_total[x] : nullptr;
+            out.speed[x] = d_speed ? d_speed[x] : nullptr;
+        }
+        hipLaunchKernelGGL(k_span<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), n * m, (unsigned)m, k, P, d_start, d_lo, d_hi, out);
+    });
+}
+
+size_t fleet_stagger_cull_workspace_bytes(size_t n, size_t m, size_t k, int d)
+{
+    if (fleet_cull_workspace_bytes(n, m, k, d) == 0) return 0;
+    return cull_workspace(n, m, k, d, 3).bytes;
+}
+
+hipError_t launch_fleet_contact_staggered_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
+                                                 const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi,
+                                                 double *d_time, double *d_time_local, double *d_rate, void *d_workspace,
+                                                 unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count, hipStream_t stream)
+{
+    if (!d_start || !d_level_sq || !d_workspace || fleet_stagger_cull_workspace_bytes(n, m, k, d) == 0) return hipErrorInvalidValue;
+    const CullWorkspace w = cull_workspace(n, m, k, d, 3);
+    char *const base = (char *)d_workspace;
+    double *box_lo[3], *box_hi[3], *slack[3], *total[3], *speed[3];
+    for (int x = 0; x < d; ++x) {
+        box_lo[x] = (double *)(base + w.box + (size_t)(2 * x) * w.box_each);
+        box_hi[x] = (double *)(base + w.box + (size_t)(2 * x + 1) * w.box_each);
+        slack[x] = (double *)(base + w.slack + (size_t)(3 * x) * w.slack_each);
+        total[x] = (double *)(base + w.slack + (size_t)(3 * x + 1) * w.slack_each);
+        speed[x] = (double *)(base + w.slack + (size_t)(3 * x + 2) * w.slack_each);
+    }
+    unsigned char *const kept = (unsigned char *)(base + w.kept);
+    uint32_t *const list = (uint32_t *)(base + w.list), *const chunk = (uint32_t *)(base + w.chunk), *const count = (uint32_t *)(base + w.count);
+    hipError_t e = launch_fleet_reach_staggered(n, m, k, d, d_fleet, d_start, d_lo, d_hi, box_lo, box_hi, slack, total, speed, stream);
+    if (e != hipSuccess) return e;
+    e = with_axes(d, [&](auto axes) {
+        constexpr int D = decltype(axes)::value;
+        WinnowIn<D> box;
+        for (int x = 0; x < D; ++x) { box.lo[x] = box_lo[x]; box.hi[x] = box_hi[x]; box.slack[x] = slack[x]; box.total[x] = total[x]; box.speed[x] = speed[x]; }
+        hipLaunchKernelGGL(k_winnow<D>, dim3((unsigned)((w.problems + kShortBlock - 1) / kShortBlock)), dim3(kShortBlock), 0, stream, box,
+                           w.problems, (unsigned)m, k, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, kept);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
+    e = launch_shortlist(w, kept, chunk, count, list, stream);
+    if (e != hipSuccess) return e;
+    if (d_time || d_time_local || d_rate) {
+        e = launch_on_fleet(n, m, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
+            constexpr int D = decltype(axes)::value;
+            hipLaunchKernelGGL(k_appointed<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_start, d_level_sq,
+                               level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, list, count);
         });
         if (e != hipSuccess) return e;
     }
