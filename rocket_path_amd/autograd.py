@@ -2254,10 +2254,27 @@ class _TrajectoryFleetContact(torch.autograd.Function):
         return torch.where(missing, torch.full_like(rate, float("nan")), total / rate), None
 
 
-def _cull_workspace(n, m, k, d, device):
-    """The culled entries' workspace as a torch allocation on the current stream: (tensor, bytes)"""
-    size = capi.trajectory_fleet_contact_culled_workspace(n, m, k, d)
+def _cull_workspace(n, m, k, d, device, staggered):
+    """The culled entries' workspace (staggered: of those with start times) as a torch allocation on the current stream: (tensor, bytes)"""
+    ask = capi.trajectory_fleet_contact_staggered_culled_workspace if staggered else capi.trajectory_fleet_contact_culled_workspace
+    size = ask(n, m, k, d)
     return torch.empty(size, dtype=torch.uint8, device=device), size
+
+
+def _culled_forward(entry, d, m, inputs):
+    """The forward of the two functions with the broad phase in front: behind the fleet's tensors the inputs are (level_sq, lo, hi), or
+    (start, level_sq, lo, hi) and one output more; the workspace's address and size follow the entry's other arguments."""
+    *start, level, lo, hi = (_dense(t) for t in inputs[8 * d:])
+    level, per_pair = _fleet_level(level)
+    n, k = level.shape[0], level.shape[-1]
+    with torch.cuda.device(inputs[0].device):
+        work, size = _cull_workspace(n, m, k, d, inputs[0].device, bool(start))
+
+    def culled(*args):
+        entry(*args, _plain(work).data_ptr(), size)
+
+    return _fleet_forward(culled, d, m, inputs, n, k, 2 + len(start),
+                          lambda addr: (*map(addr, start), addr(level), int(per_pair), addr(lo), addr(hi)))
 
 
 class _TrajectoryFleetContactCulled(_TrajectoryFleetContact):
@@ -2266,16 +2283,7 @@ class _TrajectoryFleetContactCulled(_TrajectoryFleetContact):
 
     @staticmethod
     def forward(d, m, *inputs):
-        level, lo, hi = (_dense(t) for t in inputs[8 * d:])
-        level, per_pair = _fleet_level(level)
-        n, k = level.shape[0], level.shape[-1]
-        with torch.cuda.device(inputs[0].device):
-            work, size = _cull_workspace(n, m, k, d, inputs[0].device)
-
-        def entry(*args):
-            capi.trajectory_fleet_contact_culled(*args, _plain(work).data_ptr(), size)
-
-        return _fleet_forward(entry, d, m, inputs, n, k, 2, lambda addr: (addr(level), int(per_pair), addr(lo), addr(hi)))
+        return _culled_forward(capi.trajectory_fleet_contact_culled, d, m, inputs)
 
 
 class _TrajectoryStaggeredContact(torch.autograd.Function):
@@ -2360,17 +2368,7 @@ class _TrajectoryStaggeredContactCulled(_TrajectoryStaggeredContact):
 
     @staticmethod
     def forward(d, m, *inputs):
-        start, level, lo, hi = (_dense(t) for t in inputs[8 * d:])
-        level, per_pair = _fleet_level(level)
-        n, k = level.shape[0], level.shape[-1]
-        with torch.cuda.device(inputs[0].device):
-            size = capi.trajectory_fleet_contact_staggered_culled_workspace(n, m, k, d)
-            work = torch.empty(size, dtype=torch.uint8, device=inputs[0].device)
-
-        def entry(*args):
-            capi.trajectory_fleet_contact_staggered_culled(*args, _plain(work).data_ptr(), size)
-
-        return _fleet_forward(entry, d, m, inputs, n, k, 3, lambda addr: (addr(start), addr(level), int(per_pair), addr(lo), addr(hi)))
+        return _culled_forward(capi.trajectory_fleet_contact_staggered_culled, d, m, inputs)
 
 
 def _check_broad_phase(broad_phase, start, who):
@@ -2480,6 +2478,11 @@ def min_time_fleet_contact(pos, radius=None, lo=None, hi=None, *, level_sq=None,
     return trajectory_fleet_contact(spline, None, lo, hi, level_sq=level, start=start, broad_phase=broad_phase), solution
 
 
+def _with_start(entry, staggered_entry, start):
+    """(the entry to call, what to put behind its fleet table): the plain one and nothing, or with start= the staggered one and the start's address"""
+    return (entry, ()) if start is None else (staggered_entry, (_dense(start.detach()).data_ptr(),))
+
+
 def fleet_contact_candidates(fleet, radius=None, lo=None, hi=None, *, level_sq=None, start=None):
     """The broad phase of trajectory_fleet_contact(..., broad_phase=True) alone: a (n, pairs) bool tensor, in fleet_pairs(m)'s order, True
     where the pair would go to the search and False where its position boxes over the window prove, with the margin of DESIGN.md section
@@ -2503,17 +2506,11 @@ def fleet_contact_candidates(fleet, radius=None, lo=None, hi=None, *, level_sq=N
         kept = torch.empty((n, m * (m - 1) // 2), dtype=torch.uint8, device=device)
         with torch.cuda.device(device):
             addr = lambda t: t.data_ptr() if t is not None else 0      # noqa: E731
-            if start is None:
-                work, size = _cull_workspace(n, m, k, d, device)
-                capi.trajectory_fleet_contact_candidates(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d,
-                                                         [addr(t) for t in splines], addr(level), int(per_pair), addr(lo), addr(hi),
-                                                         work.data_ptr(), size, kept.data_ptr())
-            else:
-                size = capi.trajectory_fleet_contact_staggered_culled_workspace(n, m, k, d)
-                work = torch.empty(size, dtype=torch.uint8, device=device)
-                capi.trajectory_fleet_contact_staggered_candidates(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d,
-                                                                   [addr(t) for t in splines], addr(_dense(start.detach())), addr(level),
-                                                                   int(per_pair), addr(lo), addr(hi), work.data_ptr(), size, kept.data_ptr())
+            work, size = _cull_workspace(n, m, k, d, device, start is not None)
+            head = (device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in splines])
+            tail = (addr(level), int(per_pair), addr(lo), addr(hi), work.data_ptr(), size, kept.data_ptr())
+            entry, with_start = _with_start(capi.trajectory_fleet_contact_candidates, capi.trajectory_fleet_contact_staggered_candidates, start)
+            entry(*head, *with_start, *tail)
     return kept != 0
 
 
@@ -2542,10 +2539,8 @@ def trajectory_fleet_reach(fleet, lo=None, hi=None, *, start=None):
             addr = lambda t: t.data_ptr() if t is not None else 0      # noqa: E731
             tail = (addr(lo), addr(hi), [box[0, c].data_ptr() for c in range(d)], [box[1, c].data_ptr() for c in range(d)])
             head = (device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in splines])
-            if start is None:
-                capi.trajectory_fleet_reach(*head, *tail)
-            else:
-                capi.trajectory_fleet_reach_staggered(*head, addr(_dense(start.detach())), *tail)
+            entry, with_start = _with_start(capi.trajectory_fleet_reach, capi.trajectory_fleet_reach_staggered, start)
+            entry(*head, *with_start, *tail)
     return box[0].permute(1, 2, 3, 0), box[1].permute(1, 2, 3, 0)
 
 

@@ -425,22 +425,42 @@ def _axis_outputs(addresses, d, name):
     return (_vp * d)(*[a if a else None for a in addresses])
 
 
+def _fleet_reach(who, start, device, stream, n, m, k, d, fleet, d_lo, d_hi, d_min, d_max):
+    """rp_<who> for the two reach mirrors; `start`: () or (d_start,), which follows the fleet's table"""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = _fleet_sizes(who, d, m)
+    check(getattr(load_library(), "rp_" + who)(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), *map(vp, start), vp(d_lo),
+                                               vp(d_hi), _axis_outputs(d_min, d, "d_min"), _axis_outputs(d_max, d, "d_max")))
+
+
+def _culled_workspace(who, n, m, k, d):
+    """rp_<who> for the two workspace mirrors"""
+    d, m = _fleet_sizes(who, d, m)
+    size = ctypes.c_size_t(0)
+    check(getattr(load_library(), "rp_" + who)(int(n), m, int(k), d, ctypes.byref(size)))
+    return size.value
+
+
+def _fleet_broad_phase(who, start, outputs, copies, device, stream, n, m, k, d, fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_workspace,
+                       workspace_bytes):
+    """rp_<who> for the culled and candidates mirrors; start: () or (d_start,); outputs: its times and rate; copies: d_kept, its d_list, d_count"""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m = _fleet_sizes(who, d, m)
+    check(getattr(load_library(), "rp_" + who)(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), *map(vp, start),
+                                               vp(d_level_sq), int(level_per_pair), vp(d_lo), vp(d_hi), *map(vp, outputs), vp(d_workspace),
+                                               int(workspace_bytes), *map(vp, copies)))
+
+
 def trajectory_fleet_reach(device, stream, n, m, k, d, fleet, d_lo=None, d_hi=None, d_min=None, d_max=None):
     """rp_trajectory_fleet_reach: per vehicle, axis and query the least and greatest position over the scene's window [lo, hi] (n, k;
     None / 0: -inf, +inf) -- trajectory_extrema's pos_min and pos_max of that spline and window, bit for bit.  `fleet` as for
     trajectory_fleet_separation.  d_min, d_max: d addresses each, axis c's to (n, m, k), 16-byte aligned (None / 0: not wanted; not all)."""
-    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
-    d, m = _fleet_sizes("trajectory_fleet_reach", d, m)
-    check(load_library().rp_trajectory_fleet_reach(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_lo), vp(d_hi),
-                                                   _axis_outputs(d_min, d, "d_min"), _axis_outputs(d_max, d, "d_max")))
+    _fleet_reach("trajectory_fleet_reach", (), device, stream, n, m, k, d, fleet, d_lo, d_hi, d_min, d_max)
 
 
 def trajectory_fleet_contact_culled_workspace(n, m, k, d):
     """rp_trajectory_fleet_contact_culled_workspace: the bytes of workspace the culled entries need for (n, m, k, d)."""
-    d, m = _fleet_sizes("trajectory_fleet_contact_culled_workspace", d, m)
-    size = ctypes.c_size_t(0)
-    check(load_library().rp_trajectory_fleet_contact_culled_workspace(int(n), m, int(k), d, ctypes.byref(size)))
-    return size.value
+    return _culled_workspace("trajectory_fleet_contact_culled_workspace", n, m, k, d)
 
 
 def trajectory_fleet_contact_culled(device, stream, n, m, k, d, fleet, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None, d_time=None,
@@ -449,40 +469,27 @@ def trajectory_fleet_contact_culled(device, stream, n, m, k, d, fleet, d_level_s
     broad phase in front: pairs whose position boxes prove them further apart than the level in all k queries get their NaN without a
     search.  d_workspace: workspace_bytes >= trajectory_fleet_contact_culled_workspace(n, m, k, d) bytes, 16-byte aligned.  d_kept
     (n pairs bytes), d_list (n pairs uint32), d_count (one uint32): copies of the keep-flags, the list and its length (None / 0: none)."""
-    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
-    d, m = _fleet_sizes("trajectory_fleet_contact_culled", d, m)
-    check(load_library().rp_trajectory_fleet_contact_culled(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_level_sq),
-                                                            int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_time), vp(d_rate), vp(d_workspace),
-                                                            int(workspace_bytes), vp(d_kept), vp(d_list), vp(d_count)))
+    _fleet_broad_phase("trajectory_fleet_contact_culled", (), (d_time, d_rate), (d_kept, d_list, d_count), device, stream, n, m, k, d, fleet,
+                       d_level_sq, level_per_pair, d_lo, d_hi, d_workspace, workspace_bytes)
 
 
 def trajectory_fleet_contact_candidates(device, stream, n, m, k, d, fleet, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None, d_workspace=None,
                                         workspace_bytes=0, d_kept=None):
     """rp_trajectory_fleet_contact_candidates: the broad phase of trajectory_fleet_contact_culled alone: d_kept (n pairs bytes, required),
     1 where the pair would go to the search.  The workspace as there."""
-    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
-    d, m = _fleet_sizes("trajectory_fleet_contact_candidates", d, m)
-    check(load_library().rp_trajectory_fleet_contact_candidates(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d),
-                                                                vp(d_level_sq), int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_workspace),
-                                                                int(workspace_bytes), vp(d_kept)))
+    _fleet_broad_phase("trajectory_fleet_contact_candidates", (), (), (d_kept,), device, stream, n, m, k, d, fleet, d_level_sq, level_per_pair,
+                       d_lo, d_hi, d_workspace, workspace_bytes)
 
 
 def trajectory_fleet_reach_staggered(device, stream, n, m, k, d, fleet, d_start, d_lo=None, d_hi=None, d_min=None, d_max=None):
     """rp_trajectory_fleet_reach_staggered: trajectory_fleet_reach with a start time per vehicle, d_start (n, m), required: vehicle v's
     window is [lo - start_v, hi - start_v], on its own clock."""
-    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
-    d, m = _fleet_sizes("trajectory_fleet_reach_staggered", d, m)
-    check(load_library().rp_trajectory_fleet_reach_staggered(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_start),
-                                                             vp(d_lo), vp(d_hi), _axis_outputs(d_min, d, "d_min"),
-                                                             _axis_outputs(d_max, d, "d_max")))
+    _fleet_reach("trajectory_fleet_reach_staggered", (d_start,), device, stream, n, m, k, d, fleet, d_lo, d_hi, d_min, d_max)
 
 
 def trajectory_fleet_contact_staggered_culled_workspace(n, m, k, d):
     """rp_trajectory_fleet_contact_staggered_culled_workspace: the bytes of workspace the staggered culled entries need for (n, m, k, d)."""
-    d, m = _fleet_sizes("trajectory_fleet_contact_staggered_culled_workspace", d, m)
-    size = ctypes.c_size_t(0)
-    check(load_library().rp_trajectory_fleet_contact_staggered_culled_workspace(int(n), m, int(k), d, ctypes.byref(size)))
-    return size.value
+    return _culled_workspace("trajectory_fleet_contact_staggered_culled_workspace", n, m, k, d)
 
 
 def trajectory_fleet_contact_staggered_culled(device, stream, n, m, k, d, fleet, d_start, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None,
@@ -492,23 +499,16 @@ def trajectory_fleet_contact_staggered_culled(device, stream, n, m, k, d, fleet,
     arguments, with the broad phase in front: a pair each of whose k queries is refused (no common time in the window) or box-far gets its
     NaN without a search.  The workspace (trajectory_fleet_contact_staggered_culled_workspace), d_kept, d_list and d_count as
     trajectory_fleet_contact_culled's."""
-    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
-    d, m = _fleet_sizes("trajectory_fleet_contact_staggered_culled", d, m)
-    check(load_library().rp_trajectory_fleet_contact_staggered_culled(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d),
-                                                                      vp(d_start), vp(d_level_sq), int(level_per_pair), vp(d_lo), vp(d_hi),
-                                                                      vp(d_time), vp(d_time_local), vp(d_rate), vp(d_workspace),
-                                                                      int(workspace_bytes), vp(d_kept), vp(d_list), vp(d_count)))
+    _fleet_broad_phase("trajectory_fleet_contact_staggered_culled", (d_start,), (d_time, d_time_local, d_rate), (d_kept, d_list, d_count), device,
+                       stream, n, m, k, d, fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_workspace, workspace_bytes)
 
 
 def trajectory_fleet_contact_staggered_candidates(device, stream, n, m, k, d, fleet, d_start, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None,
                                                   d_workspace=None, workspace_bytes=0, d_kept=None):
     """rp_trajectory_fleet_contact_staggered_candidates: the broad phase of trajectory_fleet_contact_staggered_culled alone: d_kept
     (n pairs bytes, required), 1 where the pair would go to the search.  The workspace as there."""
-    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
-    d, m = _fleet_sizes("trajectory_fleet_contact_staggered_candidates", d, m)
-    check(load_library().rp_trajectory_fleet_contact_staggered_candidates(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d),
-                                                                          vp(d_start), vp(d_level_sq), int(level_per_pair), vp(d_lo),
-                                                                          vp(d_hi), vp(d_workspace), int(workspace_bytes), vp(d_kept)))
+    _fleet_broad_phase("trajectory_fleet_contact_staggered_candidates", (d_start,), (), (d_kept,), device, stream, n, m, k, d, fleet, d_level_sq,
+                       level_per_pair, d_lo, d_hi, d_workspace, workspace_bytes)
 
 
 def tracking_table(addresses):

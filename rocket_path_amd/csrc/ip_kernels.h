@@ -230,26 +230,20 @@ hipError_t launch_fleet_contact_staggered(size_t n, size_t m, size_t k, int d, c
                                           const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
                                           double *d_time_local, double *d_rate, hipStream_t stream);
 // the fleet's position boxes over the scenes' windows: d_min, d_max d pointers each to n x m x k (null table or entry: not wanted),
-// d_slack d pointers to n x m (null table: not wanted)
-hipError_t launch_fleet_reach(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo, const double *d_hi,
-                              double *const *d_min, double *const *d_max, double *const *d_slack, hipStream_t stream);
-// launch_fleet_contact with the broad phase in front: the bytes of workspace it needs (0: n x pairs does not fit
-// 32 bits), and the launch -- boxes, sieve, list and, where d_time is given, the search over the list.  d_time null: the broad phase alone.
-// d_kept (n x pairs bytes), d_list (n x pairs uint32) and d_count (one uint32) are copies for the caller (null: none).
-size_t fleet_cull_workspace_bytes(size_t n, size_t m, size_t k, int d);
-hipError_t launch_fleet_contact_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq,
-                                       int level_per_pair, const double *d_lo, const double *d_hi, double *d_time, double *d_rate,
-                                       void *d_workspace, unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count, hipStream_t stream);
-// the same with a start time per vehicle: the boxes on each vehicle's own clock, with d_total and d_speed, d pointers
-// to n x m each, next to the slacks (null table: not wanted); the workspace; and launch_fleet_contact_staggered with the broad phase in
-// front -- all three outputs null: the broad phase alone
-hipError_t launch_fleet_reach_staggered(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
-                                        const double *d_lo, const double *d_hi, double *const *d_min, double *const *d_max,
-                                        double *const *d_slack, double *const *d_total, double *const *d_speed, hipStream_t stream);
-size_t fleet_stagger_cull_workspace_bytes(size_t n, size_t m, size_t k, int d);
-hipError_t launch_fleet_contact_staggered_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
-                                                 const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi,
-                                                 double *d_time, double *d_time_local, double *d_rate, void *d_workspace,
-                                                 unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count, hipStream_t stream);
+// d_slack d pointers to n x m (null table: not wanted).  d_start (n x m) given: the window of vehicle v on its own clock (DESIGN.md
+// section 31), and d_total and d_speed, d pointers to n x m each, next to the slacks; d_start null: one clock, and neither is looked at
+hipError_t launch_fleet_reach(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start, const double *d_lo,
+                              const double *d_hi, double *const *d_min, double *const *d_max, double *const *d_slack, double *const *d_total,
+                              double *const *d_speed, hipStream_t stream);
+// launch_fleet_contact (d_start null; section 30) or launch_fleet_contact_staggered (d_start given; section 31) with the broad phase in
+// front (section 32): the bytes of workspace it needs (0: n x pairs does not fit 32 bits), and the launch -- boxes, sieve, list and the
+// search over the list: on one clock where d_time is given (d_time_local is not looked at), with starts where any of the three outputs is.
+// Otherwise: the broad phase alone.  d_kept (n x pairs bytes), d_list (n x pairs uint32) and d_count (one uint32) are copies for the
+// caller (null: none).
+size_t fleet_cull_workspace_bytes(size_t n, size_t m, size_t k, int d, bool staggered);
+hipError_t launch_fleet_contact_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
+                                       const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
+                                       double *d_time_local, double *d_rate, void *d_workspace, unsigned char *d_kept, uint32_t *d_list,
+                                       uint32_t *d_count, hipStream_t stream);
 
 }  // namespace rp

@@ -1602,9 +1602,11 @@ int rp_trajectory_fleet_contact_staggered(int device, void *stream, size_t n, si
 }
 
 // the fleet's position boxes over the scenes' windows: two tables of d pointers to n x m x k, of which at least one
-// array must be given; the fleet entries' first refusals
-static int check_reach(const char *who, int device, size_t n, size_t m, size_t k, int d, const double *const *d_fleet, double *const *d_min,
-                       double *const *d_max)
+// array must be given; the fleet entries' first refusals, then the entry's own required arrays.  d_start given: the window of vehicle v on
+// its own clock, [lo - start_v, hi - start_v] (section 31).
+static int fleet_reach(const char *who, int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                       const double *d_start, std::initializer_list<Required> required, const double *d_lo, const double *d_hi,
+                       double *const *d_min, double *const *d_max)
 {
     if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", who, device);
     if (m < 2 || m > 256) return fail(RP_ERR_INVALID, "%s: m must be 2..256 vehicles per scene, got %zu", who, m);
@@ -1617,50 +1619,29 @@ static int check_reach(const char *who, int device, size_t n, size_t m, size_t k
     if (n > SIZE_MAX / sizeof(double) / m) return fail(RP_ERR_INVALID, "%s: n x m does not fit", who);
     bool any = false;
     for (int x = 0; x < d; ++x) any = any || (d_min && d_min[x]) || (d_max && d_max[x]);
-    int st = check_queries(who, n == 0 ? 0 : n * m, k, nullptr, nullptr, {}, any);      // (the windows are read as single values)
-    for (int x = 0; x < d && st == RP_OK; ++x)
+    const int st = check_queries(who, n == 0 ? 0 : n * m, k, nullptr, nullptr, {}, any);      // (the windows are read as single values)
+    if (st != RP_OK) return st;
+    for (int x = 0; x < d; ++x)
         if ((d_min && misaligned16(d_min[x])) || (d_max && misaligned16(d_max[x])))
-            st = fail(RP_ERR_INVALID, "%s: every n x m x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
-    return st;
+            return fail(RP_ERR_INVALID, "%s: every n x m x k array must be 16-byte aligned (the queries move as 16-byte vectors)", who);
+    for (const Required &r : required)
+        if (!r.given) return fail(RP_ERR_INVALID, "%s: %s is null", who, r.name);
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_fleet_reach(n, m, k, d, d_fleet, d_start, d_lo, d_hi, d_min, d_max, nullptr, nullptr, nullptr, (hipStream_t)stream));
+    return RP_OK;
 }
 
 int rp_trajectory_fleet_reach(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo,
                               const double *d_hi, double *const *d_min, double *const *d_max)
 {
-    const int st = check_reach(__func__, device, n, m, k, d, d_fleet, d_min, d_max);
-    if (st != RP_OK) return st;
-    RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_fleet_reach(n, m, k, d, d_fleet, d_lo, d_hi, d_min, d_max, nullptr, (hipStream_t)stream));
-    return RP_OK;
+    return fleet_reach(__func__, device, stream, n, m, k, d, d_fleet, nullptr, {}, d_lo, d_hi, d_min, d_max);
 }
 
-// the same boxes with the window of vehicle v on its own clock, [lo - start_v, hi - start_v]: rp_trajectory_fleet_reach's
-// refusals in its order, then a start that is required
 int rp_trajectory_fleet_reach_staggered(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
                                         const double *d_start, const double *d_lo, const double *d_hi, double *const *d_min,
                                         double *const *d_max)
 {
-    int st = check_reach(__func__, device, n, m, k, d, d_fleet, d_min, d_max);
-    if (st == RP_OK && !d_start) st = fail(RP_ERR_INVALID, "%s: d_start is null", __func__);
-    if (st != RP_OK) return st;
-    RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_fleet_reach_staggered(n, m, k, d, d_fleet, d_start, d_lo, d_hi, d_min, d_max, nullptr, nullptr, nullptr, (hipStream_t)stream));
-    return RP_OK;
-}
-
-// What the culled entries add to rp_trajectory_fleet_contact's refusals: n x pairs below 2^32 (a list entry is 32 bits) and a workspace
-// that is given, 16-byte aligned and large enough.
-static int check_cull_workspace(const char *who, size_t n, size_t m, size_t k, int d, const void *d_workspace, size_t workspace_bytes,
-                                bool staggered = false)
-{
-    const size_t need = staggered ? rp::fleet_stagger_cull_workspace_bytes(n, m, k, d) : rp::fleet_cull_workspace_bytes(n, m, k, d);
-    if (need == 0) return fail(RP_ERR_INVALID, "%s: n x pairs must be below 2^32 and the boxes must fit", who);
-    if (!d_workspace) return fail(RP_ERR_INVALID, "%s: d_workspace is null", who);
-    if (misaligned16(d_workspace)) return fail(RP_ERR_INVALID, "%s: d_workspace must be 16-byte aligned", who);
-    if (workspace_bytes < need)
-        return fail(RP_ERR_INVALID, "%s: the workspace holds %zu bytes, rp_trajectory_fleet_contact_%sculled_workspace asks for %zu", who,
-                    workspace_bytes, staggered ? "staggered_" : "", need);
-    return RP_OK;
+    return fleet_reach(__func__, device, stream, n, m, k, d, d_fleet, d_start, {{"d_start", d_start}}, d_lo, d_hi, d_min, d_max);
 }
 
 static int cull_workspace_size(const char *who, size_t n, size_t m, size_t k, int d, size_t *bytes, bool staggered)
@@ -1671,7 +1652,7 @@ static int cull_workspace_size(const char *who, size_t n, size_t m, size_t k, in
     if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", who, d);
     if (n == 0 || k == 0) return fail(RP_ERR_INVALID, "%s: n and k must be positive", who);
     if (k >= ((size_t)1 << 31)) return fail(RP_ERR_INVALID, "%s: k must be below 2^31", who);
-    const size_t need = staggered ? rp::fleet_stagger_cull_workspace_bytes(n, m, k, d) : rp::fleet_cull_workspace_bytes(n, m, k, d);
+    const size_t need = rp::fleet_cull_workspace_bytes(n, m, k, d, staggered);
     if (need == 0) return fail(RP_ERR_INVALID, "%s: n x pairs must be below 2^32 and the boxes must fit", who);
     *bytes = need;
     return RP_OK;
@@ -1687,20 +1668,40 @@ int rp_trajectory_fleet_contact_staggered_culled_workspace(size_t n, size_t m, s
     return cull_workspace_size(__func__, n, m, k, d, bytes, true);
 }
 
-// rp_trajectory_fleet_contact with the broad phase in front: its refusals in its order, then the workspace's
+// The culled and the candidates entries (DESIGN.md sections 30 to 32): the refusals of rp_trajectory_fleet_contact (d_start null) or
+// rp_trajectory_fleet_contact_staggered in their order, with the entry's own required arrays; then n x pairs below 2^32 (a list entry is 32
+// bits) and a workspace that is given, 16-byte aligned and large enough.  All three outputs null: the broad phase alone.
+static int fleet_culled(const char *who, int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
+                        const double *d_start, const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi,
+                        std::initializer_list<Required> required, double *d_time, double *d_time_local, double *d_rate, bool any_output,
+                        void *d_workspace, size_t workspace_bytes, unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count)
+{
+    const int st = check_fleet(who, device, n, m, k, d, &level_per_pair, d_fleet, required,
+                               {level_per_pair ? d_level_sq : nullptr, d_time, d_time_local, d_rate}, any_output);
+    if (st != RP_OK) return st;
+    const bool staggered = d_start != nullptr;      // (an entry with starts has them among its required arrays)
+    const size_t need = rp::fleet_cull_workspace_bytes(n, m, k, d, staggered);
+    if (need == 0) return fail(RP_ERR_INVALID, "%s: n x pairs must be below 2^32 and the boxes must fit", who);
+    if (!d_workspace) return fail(RP_ERR_INVALID, "%s: d_workspace is null", who);
+    if (misaligned16(d_workspace)) return fail(RP_ERR_INVALID, "%s: d_workspace must be 16-byte aligned", who);
+    if (workspace_bytes < need)
+        return fail(RP_ERR_INVALID, "%s: the workspace holds %zu bytes, rp_trajectory_fleet_contact_%sculled_workspace asks for %zu", who,
+                    workspace_bytes, staggered ? "staggered_" : "", need);
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_fleet_contact_culled(n, m, k, d, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate,
+                                           d_workspace, d_kept, d_list, d_count, (hipStream_t)stream));
+    return RP_OK;
+}
+
+// rp_trajectory_fleet_contact with the broad phase in front
 int rp_trajectory_fleet_contact_culled(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
                                        const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
                                        double *d_rate, void *d_workspace, size_t workspace_bytes, unsigned char *d_kept, uint32_t *d_list,
                                        uint32_t *d_count)
 {
-    int st = check_fleet(__func__, device, n, m, k, d, &level_per_pair, d_fleet, {{"d_level_sq", d_level_sq}, {"d_time", d_time}},
-                         {level_per_pair ? d_level_sq : nullptr, d_time, d_rate}, true);
-    if (st == RP_OK) st = check_cull_workspace(__func__, n, m, k, d, d_workspace, workspace_bytes);
-    if (st != RP_OK) return st;
-    RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_fleet_contact_culled(n, m, k, d, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate, d_workspace, d_kept,
-                                           d_list, d_count, (hipStream_t)stream));
-    return RP_OK;
+    return fleet_culled(__func__, device, stream, n, m, k, d, d_fleet, nullptr, d_level_sq, level_per_pair, d_lo, d_hi,
+                        {{"d_level_sq", d_level_sq}, {"d_time", d_time}}, d_time, nullptr, d_rate, true, d_workspace, workspace_bytes, d_kept,
+                        d_list, d_count);
 }
 
 // the broad phase alone: the keep-flags of rp_trajectory_fleet_contact_culled's sieve, and no search
@@ -1708,30 +1709,20 @@ int rp_trajectory_fleet_contact_candidates(int device, void *stream, size_t n, s
                                            const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi,
                                            void *d_workspace, size_t workspace_bytes, unsigned char *d_kept)
 {
-    int st = check_fleet(__func__, device, n, m, k, d, &level_per_pair, d_fleet, {{"d_level_sq", d_level_sq}, {"d_kept", d_kept}},
-                         {level_per_pair ? d_level_sq : nullptr}, true);
-    if (st == RP_OK) st = check_cull_workspace(__func__, n, m, k, d, d_workspace, workspace_bytes);
-    if (st != RP_OK) return st;
-    RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_fleet_contact_culled(n, m, k, d, d_fleet, d_level_sq, level_per_pair, d_lo, d_hi, nullptr, nullptr, d_workspace, d_kept,
-                                           nullptr, nullptr, (hipStream_t)stream));
-    return RP_OK;
+    return fleet_culled(__func__, device, stream, n, m, k, d, d_fleet, nullptr, d_level_sq, level_per_pair, d_lo, d_hi,
+                        {{"d_level_sq", d_level_sq}, {"d_kept", d_kept}}, nullptr, nullptr, nullptr, true, d_workspace, workspace_bytes, d_kept,
+                        nullptr, nullptr);
 }
 
-// rp_trajectory_fleet_contact_staggered with the broad phase in front: its refusals in its order, then the workspace's
+// rp_trajectory_fleet_contact_staggered with the broad phase in front
 int rp_trajectory_fleet_contact_staggered_culled(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
                                                  const double *d_start, const double *d_level_sq, int level_per_pair, const double *d_lo,
                                                  const double *d_hi, double *d_time, double *d_time_local, double *d_rate, void *d_workspace,
                                                  size_t workspace_bytes, unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count)
 {
-    int st = check_fleet(__func__, device, n, m, k, d, &level_per_pair, d_fleet, {{"d_start", d_start}, {"d_level_sq", d_level_sq}},
-                         {level_per_pair ? d_level_sq : nullptr, d_time, d_time_local, d_rate}, d_time || d_time_local || d_rate);
-    if (st == RP_OK) st = check_cull_workspace(__func__, n, m, k, d, d_workspace, workspace_bytes, true);
-    if (st != RP_OK) return st;
-    RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_fleet_contact_staggered_culled(n, m, k, d, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local,
-                                                     d_rate, d_workspace, d_kept, d_list, d_count, (hipStream_t)stream));
-    return RP_OK;
+    return fleet_culled(__func__, device, stream, n, m, k, d, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi,
+                        {{"d_start", d_start}, {"d_level_sq", d_level_sq}}, d_time, d_time_local, d_rate, d_time || d_time_local || d_rate,
+                        d_workspace, workspace_bytes, d_kept, d_list, d_count);
 }
 
 // its broad phase alone: the keep-flags, and no search
@@ -1739,14 +1730,9 @@ int rp_trajectory_fleet_contact_staggered_candidates(int device, void *stream, s
                                                      const double *d_start, const double *d_level_sq, int level_per_pair, const double *d_lo,
                                                      const double *d_hi, void *d_workspace, size_t workspace_bytes, unsigned char *d_kept)
 {
-    int st = check_fleet(__func__, device, n, m, k, d, &level_per_pair, d_fleet,
-                         {{"d_start", d_start}, {"d_level_sq", d_level_sq}, {"d_kept", d_kept}}, {level_per_pair ? d_level_sq : nullptr}, true);
-    if (st == RP_OK) st = check_cull_workspace(__func__, n, m, k, d, d_workspace, workspace_bytes, true);
-    if (st != RP_OK) return st;
-    RP_HIP(hipSetDevice(device));
-    RP_HIP(rp::launch_fleet_contact_staggered_culled(n, m, k, d, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi, nullptr, nullptr, nullptr,
-                                                     d_workspace, d_kept, nullptr, nullptr, (hipStream_t)stream));
-    return RP_OK;
+    return fleet_culled(__func__, device, stream, n, m, k, d, d_fleet, d_start, d_level_sq, level_per_pair, d_lo, d_hi,
+                        {{"d_start", d_start}, {"d_level_sq", d_level_sq}, {"d_kept", d_kept}}, nullptr, nullptr, nullptr, true, d_workspace,
+                        workspace_bytes, d_kept, nullptr, nullptr);
 }
 
 // the integrals over a window, their first derivatives and the reverse rule's derivative along a direction

@@ -2904,6 +2904,7 @@ constexpr int kShortEach = 8;                                  // flags per thre
 constexpr unsigned kShortChunk = kShortBlock * kShortEach;     // flags per chunk
 
 template <int D> struct ReachOut { double *lo[D], *hi[D], *slack[D]; };      // per axis: n m k, n m k, n m (null: not written)
+template <int D> struct SpanOut : ReachOut<D> { double *total[D], *speed[D]; };      // and n m, n m (null: not written)
 
 template <int D>
 __global__ void __launch_bounds__(kTrajBlock)
@@ -2941,18 +2942,40 @@ k_reach(FleetSplines<D> in, size_t vehicles, unsigned m, size_t k, int P, const 
 
 template <int D> struct SieveIn { const double *lo[D], *hi[D], *slack[D]; };
 
+// a sieve thread's problem p (false: none), its scene s and its two vehicles' places
+__device__ __forceinline__ bool sieve_pair(size_t problems, unsigned m, size_t &p, size_t &s, size_t &vi, size_t &vj)
+{
+    p = (size_t)blockIdx.x * kShortBlock + threadIdx.x;
+    if (p >= problems) return false;
+    const unsigned pairs = fleet_pair_count(m);
+    s = p / pairs;
+    unsigned i, j;
+    fleet_pair((unsigned)(p - s * pairs), m, i, j);
+    vi = s * m + i, vj = s * m + j;
+    return true;
+}
+
+// its keep-flag, and a culled pair's NaNs in the outputs that are wanted
+__device__ __forceinline__ void sieve_verdict(bool culled, size_t p, size_t k, double *__restrict__ time, double *__restrict__ time_local,
+                                              double *__restrict__ rate, unsigned char *__restrict__ kept)
+{
+    kept[p] = culled ? 0 : 1;
+    if (!culled) return;
+    const double nan = quiet_nan();
+    for (size_t q = 0; q < k; ++q) {
+        if (time) time[p * k + q] = nan;
+        if (time_local) time_local[p * k + q] = nan;
+        if (rate) rate[p * k + q] = nan;
+    }
+}
+
 template <int D>
 __global__ void __launch_bounds__(kShortBlock)
 k_sieve(SieveIn<D> box, size_t problems, unsigned m, size_t k, const double *__restrict__ level, int level_per_pair,
         double *__restrict__ time, double *__restrict__ rate, unsigned char *__restrict__ kept)
 {
-    const size_t p = (size_t)blockIdx.x * kShortBlock + threadIdx.x;
-    if (p >= problems) return;
-    const unsigned pairs = fleet_pair_count(m);
-    const size_t s = p / pairs;
-    unsigned i, j;
-    fleet_pair((unsigned)(p - s * pairs), m, i, j);
-    const size_t vi = s * m + i, vj = s * m + j;
+    size_t p, s, vi, vj;
+    if (!sieve_pair(problems, m, p, s, vi, vj)) return;
     bool culled = true;
     for (size_t q = 0; q < k && culled; ++q) {
         CullBound b = cull_begin();
@@ -2962,13 +2985,7 @@ k_sieve(SieveIn<D> box, size_t problems, unsigned m, size_t k, const double *__r
                      box.slack[x][vj]);
         culled = cull_far(b, level[level_per_pair ? p * k + q : s * k + q]);
     }
-    kept[p] = culled ? 0 : 1;
-    if (!culled) return;
-    const double nan = quiet_nan();
-    for (size_t q = 0; q < k; ++q) {
-        if (time) time[p * k + q] = nan;
-        if (rate) rate[p * k + q] = nan;
-    }
+    sieve_verdict(culled, p, k, time, nullptr, rate, kept);
 }
 
 // the kShortEach flags of this thread (those at or beyond `problems` count as 0), one bit each, lowest first
@@ -3049,12 +3066,13 @@ k_shortlist_scatter(const unsigned char *__restrict__ kept, size_t problems, con
         }
 }
 
-// Budgets as k_encounter's (section 27); the hint and what the allocator does without it are in section 30.
-template <int D>
-__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
-k_shortlisted(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const double *__restrict__ level, int level_per_pair,
-              const double *__restrict__ lo, const double *__restrict__ hi, double *__restrict__ time, double *__restrict__ rate,
-              const uint32_t *__restrict__ list, const uint32_t *__restrict__ count)
+// k_shortlisted (one clock) and k_appointed (STAGGERED: StartOf::load, a delay and a third output); section 32.  One clock is not a zero
+// start: t + 0.0 would make a -0.0 time +0.0, so that branch has its literal 0.0 delay and stores t as it is, unasked.
+template <int D, bool STAGGERED>
+__device__ __forceinline__ void search_listed(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const double *__restrict__ start,
+                                              const double *__restrict__ level, int level_per_pair, const double *__restrict__ lo,
+                                              const double *__restrict__ hi, double *__restrict__ time, double *__restrict__ time_local,
+                                              double *__restrict__ rate, const uint32_t *__restrict__ list, const uint32_t *__restrict__ count)
 {
     __shared__ SepLds<D> L;
     const unsigned pairs = fleet_pair_count(m);
@@ -3066,22 +3084,42 @@ k_shortlisted(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, 
     };
     for_each_trip(listed, P, stage_problem, [&](size_t at_first, int here) {
         stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
-            const double inf = __builtin_inf();
 #pragma nounroll
             for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_encounter: each query's searches have their own trip counts
                 const int q = half ? qb : qa;
                 const size_t entry = list[at_first + (size_t)q], p = entry < last ? entry : last;
                 const size_t col = e + (size_t)half - (size_t)q * k;
-                const size_t w = (size_t)((uint32_t)p / pairs) * k + col;      // the scene's row, the query's column
-                const size_t o = p * k + col;                                  // the problem's own place
+                const uint32_t s = (uint32_t)p / pairs;
+                const size_t w = (size_t)s * k + col;      // the scene's row, the query's column
+                const size_t o = p * k + col;              // the problem's own place
                 double t, r;
                 int trips = 0;
-                contact_query<D>(L, q, level[level_per_pair ? o : w], lo ? lo[w] : -inf, hi ? hi[w] : inf, 0.0, t, r, trips);
-                time[o] = t;
+                if constexpr (STAGGERED) {
+                    const StartOf clock{start, lo, hi, m, pairs};
+                    double s_i, delay, l, h;
+                    clock.load(s, (uint32_t)p - s * pairs, w, s_i, delay, l, h);
+                    contact_query<D>(L, q, level[level_per_pair ? o : w], l, h, delay, t, r, trips);
+                    if (time) time[o] = t + s_i;
+                    if (time_local) time_local[o] = t;
+                } else {
+                    const double inf = __builtin_inf();
+                    contact_query<D>(L, q, level[level_per_pair ? o : w], lo ? lo[w] : -inf, hi ? hi[w] : inf, 0.0, t, r, trips);
+                    time[o] = t;
+                }
                 if (rate) rate[o] = r;
             }
         });
     });
+}
+
+// Budgets as k_encounter's (section 27); the hint and what the allocator does without it are in section 30.
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
+k_shortlisted(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const double *__restrict__ level, int level_per_pair,
+              const double *__restrict__ lo, const double *__restrict__ hi, double *__restrict__ time, double *__restrict__ rate,
+              const uint32_t *__restrict__ list, const uint32_t *__restrict__ count)
+{
+    search_listed<D, false>(in, problems, m, k, P, nullptr, level, level_per_pair, lo, hi, time, nullptr, rate, list, count);
 }
 
 // ---- the broad phase with a start time per vehicle (rp_trajectory_fleet_contact_staggered_culled, rp_trajectory_fleet_reach_staggered;
@@ -3093,8 +3131,6 @@ k_shortlisted(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, 
 // walk (cull_refused: its own operations on the stored totals) or when the boxes are far with the time error of t - delay allowed for
 // (cull_add_staggered); a pair all of whose queries are out is culled and gets quiet_nan() in its k times, local times and rates.  The
 // list kernels are section 30's.  k_appointed: k_shortlisted's staging and stores around StartOf::load and contact_query with a delay.
-template <int D> struct SpanOut { double *lo[D], *hi[D], *slack[D], *total[D], *speed[D]; };      // n m k, n m k, n m, n m, n m (null: not written)
-
 template <int D>
 __global__ void __launch_bounds__(kTrajBlock)
 k_span(FleetSplines<D> in, size_t vehicles, unsigned m, size_t k, int P, const double *__restrict__ start, const double *__restrict__ lo,
@@ -3136,7 +3172,7 @@ k_span(FleetSplines<D> in, size_t vehicles, unsigned m, size_t k, int P, const d
     }
 }
 
-template <int D> struct WinnowIn { const double *lo[D], *hi[D], *slack[D], *total[D], *speed[D]; };
+template <int D> struct WinnowIn : SieveIn<D> { const double *total[D], *speed[D]; };
 
 template <int D>
 __global__ void __launch_bounds__(kShortBlock)
@@ -3144,14 +3180,9 @@ k_winnow(WinnowIn<D> box, size_t problems, unsigned m, size_t k, const double *_
          int level_per_pair, const double *__restrict__ lo, const double *__restrict__ hi, double *__restrict__ time,
          double *__restrict__ time_local, double *__restrict__ rate, unsigned char *__restrict__ kept)
 {
-    const size_t p = (size_t)blockIdx.x * kShortBlock + threadIdx.x;
-    if (p >= problems) return;
+    size_t p, s, vi, vj;
+    if (!sieve_pair(problems, m, p, s, vi, vj)) return;
     const double inf = __builtin_inf();
-    const unsigned pairs = fleet_pair_count(m);
-    const size_t s = p / pairs;
-    unsigned i, j;
-    fleet_pair((unsigned)(p - s * pairs), m, i, j);
-    const size_t vi = s * m + i, vj = s * m + j;
     const double s_i = start[vi], s_j = start[vj];
     const double delay = s_j - s_i;      // StartOf::load's
     bool culled = cull_finite(s_i) && cull_finite(s_j);      // a start that is not finite: the search makes the NaNs
@@ -3171,14 +3202,7 @@ k_winnow(WinnowIn<D> box, size_t problems, unsigned m, size_t k, const double *_
                                box.slack[x][vj], box.speed[x][vi], box.speed[x][vj], box.total[x][vi], box.total[x][vj]);
         culled = cull_far(b, reach);
     }
-    kept[p] = culled ? 0 : 1;
-    if (!culled) return;
-    const double nan = quiet_nan();
-    for (size_t q = 0; q < k; ++q) {
-        if (time) time[p * k + q] = nan;
-        if (time_local) time_local[p * k + q] = nan;
-        if (rate) rate[p * k + q] = nan;
-    }
+    sieve_verdict(culled, p, k, time, time_local, rate, kept);
 }
 
 // Budgets as k_rendezvous' (section 28).
@@ -3189,35 +3213,7 @@ k_appointed(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, co
             double *__restrict__ time, double *__restrict__ time_local, double *__restrict__ rate, const uint32_t *__restrict__ list,
             const uint32_t *__restrict__ count)
 {
-    __shared__ SepLds<D> L;
-    const unsigned pairs = fleet_pair_count(m);
-    const StartOf clock{start, lo, hi, m, pairs};
-    const size_t listed = *count < problems ? (size_t)*count : problems;      // the device's own count, never beyond the list
-    const size_t last = problems - 1;
-    auto stage_problem = [&](int q, size_t at) {
-        const size_t p = list[at];
-        stage_fleet_pair(L, q, in, m, pairs, p < last ? p : last);      // (an entry is a problem: the clamp never acts)
-    };
-    for_each_trip(listed, P, stage_problem, [&](size_t at_first, int here) {
-        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
-#pragma nounroll
-            for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_rendezvous: each query's searches have their own trip counts
-                const int q = half ? qb : qa;
-                const size_t entry = list[at_first + (size_t)q], p = entry < last ? entry : last;
-                const size_t col = e + (size_t)half - (size_t)q * k;
-                const uint32_t s = (uint32_t)p / pairs;
-                const size_t w = (size_t)s * k + col;      // the scene's row, the query's column
-                const size_t o = p * k + col;              // the problem's own place
-                double s_i, delay, l, h, t, rt;
-                clock.load(s, (uint32_t)p - s * pairs, w, s_i, delay, l, h);
-                int trips = 0;
-                contact_query<D>(L, q, level[level_per_pair ? o : w], l, h, delay, t, rt, trips);
-                if (time) time[o] = t + s_i;
-                if (time_local) time_local[o] = t;
-                if (rate) rate[o] = rt;
-            }
-        });
-    });
+    search_listed<D, true>(in, problems, m, k, P, start, level, level_per_pair, lo, hi, time, time_local, rate, list, count);
 }
 
 // ---- plot data ----
@@ -3666,118 +3662,12 @@ hipError_t launch_fleet_contact_staggered(size_t n, size_t m, size_t k, int d, c
     });
 }
 
-hipError_t launch_fleet_reach(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_lo, const double *d_hi,
-                              double *const *d_min, double *const *d_max, double *const *d_slack, hipStream_t stream)
+// the boxes of either clock: d_start null, k_reach (which has no totals and no speed bounds: d_total and d_speed are not looked at); given, k_span
+hipError_t launch_fleet_reach(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start, const double *d_lo,
+                              const double *d_hi, double *const *d_min, double *const *d_max, double *const *d_slack, double *const *d_total,
+                              double *const *d_speed, hipStream_t stream)
 {
     if (m < 2 || m > kFleetMost) return hipErrorInvalidValue;
-    return launch_on_pairs(n * m, k, d, [&](auto axes, dim3 grid, dim3 block, int P) {
-        constexpr int D = decltype(axes)::value;
-        ReachOut<D> out;
-        for (int x = 0; x < D; ++x) {
-            out.lo[x] = d_min ? d_min[x] : nullptr;
-            out.hi[x] = d_max ? d_max[x] : nullptr;
-            out.slack[x] = d_slack ? d_slack[x] : nullptr;
-        }
-        hipLaunchKernelGGL(k_reach<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), n * m, (unsigned)m, k, P, d_lo, d_hi, out);
-    });
-}
-
-namespace {
-
-// The culled entry's workspace, every part on a 16-byte boundary: per axis the boxes' two n m k arrays and the n m slacks, the n x pairs
-// keep-flags, the list, the chunks' counts, the count.
-struct CullWorkspace {
-    size_t box, slack, kept, list, chunk, count, bytes;      // offsets in bytes; box and slack: of axis 0's, the axes follow each other
-    size_t box_each, slack_each, problems, chunks;
-};
-
-size_t round16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
-// per_vehicle: the n m arrays per axis -- the slacks; with a start per vehicle (section 31) the totals and the speed bounds behind them
-CullWorkspace cull_workspace(size_t n, size_t m, size_t k, int d, int per_vehicle = 1)
-{
-    CullWorkspace w{};
-    w.problems = n * fleet_pair_count((unsigned)m);
-    w.chunks = (w.problems + kShortChunk - 1) / kShortChunk;
-    w.box_each = round16(n * m * k * sizeof(double));
-    w.slack_each = round16(n * m * sizeof(double));
-    w.box = 0;
-    w.slack = w.box + 2 * (size_t)d * w.box_each;
-    w.kept = w.slack + (size_t)per_vehicle * (size_t)d * w.slack_each;
-    w.list = w.kept + round16(w.problems);
-    w.chunk = w.list + round16(w.problems * sizeof(uint32_t));
-    w.count = w.chunk + round16(w.chunks * sizeof(uint32_t));
-    w.bytes = w.count + 16;
-    return w;
-}
-
-// the list of the kept problems and its length from the flags (section 30's third pass)
-hipError_t launch_shortlist(const CullWorkspace &w, const unsigned char *kept, uint32_t *chunk, uint32_t *count, uint32_t *list, hipStream_t stream)
-{
-    hipLaunchKernelGGL(k_shortlist_count, dim3((unsigned)w.chunks), dim3(kShortBlock), 0, stream, kept, w.problems, chunk);
-    hipLaunchKernelGGL(k_shortlist_scan, dim3(1), dim3(kShortBlock), 0, stream, chunk, w.chunks, count);
-    hipLaunchKernelGGL(k_shortlist_scatter, dim3((unsigned)w.chunks), dim3(kShortBlock), 0, stream, kept, w.problems, chunk, list);
-    return hipGetLastError();
-}
-
-}  // namespace
-
-size_t fleet_cull_workspace_bytes(size_t n, size_t m, size_t k, int d)
-{
-    if (m < 2 || m > kFleetMost || d < 1 || d > 3 || n == 0 || k == 0) return 0;
-    if (n > (((size_t)1 << 32) - 1) / fleet_pair_count((unsigned)m)) return 0;      // a list entry is 32 bits
-    if (k > SIZE_MAX / 64 / (n * m)) return 0;                                       // the boxes' bytes fit
-    return cull_workspace(n, m, k, d).bytes;
-}
-
-hipError_t launch_fleet_contact_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq,
-                                       int level_per_pair, const double *d_lo, const double *d_hi, double *d_time, double *d_rate,
-                                       void *d_workspace, unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count, hipStream_t stream)
-{
-    if (!d_level_sq || !d_workspace || fleet_cull_workspace_bytes(n, m, k, d) == 0) return hipErrorInvalidValue;
-    const CullWorkspace w = cull_workspace(n, m, k, d);
-    char *const base = (char *)d_workspace;
-    double *box_lo[3], *box_hi[3], *slack[3];
-    for (int x = 0; x < d; ++x) {
-        box_lo[x] = (double *)(base + w.box + (size_t)(2 * x) * w.box_each);
-        box_hi[x] = (double *)(base + w.box + (size_t)(2 * x + 1) * w.box_each);
-        slack[x] = (double *)(base + w.slack + (size_t)x * w.slack_each);
-    }
-    unsigned char *const kept = (unsigned char *)(base + w.kept);
-    uint32_t *const list = (uint32_t *)(base + w.list), *const chunk = (uint32_t *)(base + w.chunk), *const count = (uint32_t *)(base + w.count);
-    hipError_t e = launch_fleet_reach(n, m, k, d, d_fleet, d_lo, d_hi, box_lo, box_hi, slack, stream);
-    if (e != hipSuccess) return e;
-    e = with_axes(d, [&](auto axes) {
-        constexpr int D = decltype(axes)::value;
-        SieveIn<D> box;
-        for (int x = 0; x < D; ++x) { box.lo[x] = box_lo[x]; box.hi[x] = box_hi[x]; box.slack[x] = slack[x]; }
-        hipLaunchKernelGGL(k_sieve<D>, dim3((unsigned)((w.problems + kShortBlock - 1) / kShortBlock)), dim3(kShortBlock), 0, stream, box,
-                           w.problems, (unsigned)m, k, d_level_sq, level_per_pair, d_time, d_rate, kept);
-        return hipGetLastError();
-    });
-    if (e != hipSuccess) return e;
-    e = launch_shortlist(w, kept, chunk, count, list, stream);
-    if (e != hipSuccess) return e;
-    if (d_time) {
-        e = launch_on_fleet(n, m, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
-            constexpr int D = decltype(axes)::value;
-            hipLaunchKernelGGL(k_shortlisted<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_level_sq,
-                               level_per_pair, d_lo, d_hi, d_time, d_rate, list, count);
-        });
-        if (e != hipSuccess) return e;
-    }
-    if (d_kept) e = hipMemcpyAsync(d_kept, kept, w.problems, hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess && d_list) e = hipMemcpyAsync(d_list, list, w.problems * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess && d_count) e = hipMemcpyAsync(d_count, count, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
-    return e;
-}
-
-// ---- the same with a start time per vehicle (section 31) ----
-hipError_t launch_fleet_reach_staggered(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
-                                        const double *d_lo, const double *d_hi, double *const *d_min, double *const *d_max,
-                                        double *const *d_slack, double *const *d_total, double *const *d_speed, hipStream_t stream)
-{
-    if (m < 2 || m > kFleetMost || !d_start) return hipErrorInvalidValue;
     return launch_on_pairs(n * m, k, d, [&](auto axes, dim3 grid, dim3 block, int P) {
         constexpr int D = decltype(axes)::value;
         SpanOut<D> out;
@@ -3788,58 +3678,115 @@ hipError_t launch_fleet_reach_staggered(size_t n, size_t m, size_t k, int d, con
             out.total[x] = d_total ? d_total[x] : nullptr;
             out.speed[x] = d_speed ? d_speed[x] : nullptr;
         }
-        hipLaunchKernelGGL(k_span<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), n * m, (unsigned)m, k, P, d_start, d_lo, d_hi, out);
+        if (d_start)
+            hipLaunchKernelGGL(k_span<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), n * m, (unsigned)m, k, P, d_start, d_lo, d_hi, out);
+        else
+            hipLaunchKernelGGL(k_reach<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), n * m, (unsigned)m, k, P, d_lo, d_hi,
+                               ReachOut<D>(out));
     });
 }
 
-size_t fleet_stagger_cull_workspace_bytes(size_t n, size_t m, size_t k, int d)
+namespace {
+
+// The n m arrays the broad phase keeps per axis: the slacks; with a start per vehicle (section 31) the totals and the speed bounds too.
+constexpr int cull_per_vehicle(bool staggered) { return staggered ? 3 : 1; }
+
+// The culled entries' workspace, every part on a 16-byte boundary: per axis the boxes' two n m k arrays; per axis the n m slacks and,
+// staggered, totals and speed bounds (null otherwise); the n x pairs keep-flags, the list, the chunks' counts, the count.
+struct CullWorkspace {
+    double *box_lo[3], *box_hi[3], *slack[3], *total[3], *speed[3];      // (axes at or beyond d: null)
+    unsigned char *kept;
+    uint32_t *list, *chunk, *count;
+    size_t problems, chunks, bytes;
+};
+
+size_t round16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// the parts of a workspace at d_workspace; a null d_workspace gives the sizes, and pointers that are only offsets
+CullWorkspace cull_workspace(size_t n, size_t m, size_t k, int d, bool staggered, void *d_workspace)
 {
-    if (fleet_cull_workspace_bytes(n, m, k, d) == 0) return 0;
-    return cull_workspace(n, m, k, d, 3).bytes;
+    CullWorkspace w{};
+    w.problems = n * fleet_pair_count((unsigned)m);
+    w.chunks = (w.problems + kShortChunk - 1) / kShortChunk;
+    const size_t box_each = round16(n * m * k * sizeof(double)), slack_each = round16(n * m * sizeof(double));
+    double **const per_vehicle[3] = {w.slack, w.total, w.speed};
+    uintptr_t at = (uintptr_t)d_workspace;
+    auto take = [&](size_t bytes) { void *const here = (void *)at; at += bytes; return here; };
+    for (int x = 0; x < d; ++x) {
+        w.box_lo[x] = (double *)take(box_each);
+        w.box_hi[x] = (double *)take(box_each);
+    }
+    for (int x = 0; x < d; ++x)
+        for (int a = 0; a < cull_per_vehicle(staggered); ++a) per_vehicle[a][x] = (double *)take(slack_each);
+    w.kept = (unsigned char *)take(round16(w.problems));
+    w.list = (uint32_t *)take(round16(w.problems * sizeof(uint32_t)));
+    w.chunk = (uint32_t *)take(round16(w.chunks * sizeof(uint32_t)));
+    w.count = (uint32_t *)take(16);
+    w.bytes = (size_t)(at - (uintptr_t)d_workspace);
+    return w;
 }
 
-hipError_t launch_fleet_contact_staggered_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
-                                                 const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi,
-                                                 double *d_time, double *d_time_local, double *d_rate, void *d_workspace,
-                                                 unsigned char *d_kept, uint32_t *d_list, uint32_t *d_count, hipStream_t stream)
+// the list of the kept problems and its length from the flags (section 30's third pass)
+hipError_t launch_shortlist(const CullWorkspace &w, hipStream_t stream)
 {
-    if (!d_start || !d_level_sq || !d_workspace || fleet_stagger_cull_workspace_bytes(n, m, k, d) == 0) return hipErrorInvalidValue;
-    const CullWorkspace w = cull_workspace(n, m, k, d, 3);
-    char *const base = (char *)d_workspace;
-    double *box_lo[3], *box_hi[3], *slack[3], *total[3], *speed[3];
-    for (int x = 0; x < d; ++x) {
-        box_lo[x] = (double *)(base + w.box + (size_t)(2 * x) * w.box_each);
-        box_hi[x] = (double *)(base + w.box + (size_t)(2 * x + 1) * w.box_each);
-        slack[x] = (double *)(base + w.slack + (size_t)(3 * x) * w.slack_each);
-        total[x] = (double *)(base + w.slack + (size_t)(3 * x + 1) * w.slack_each);
-        speed[x] = (double *)(base + w.slack + (size_t)(3 * x + 2) * w.slack_each);
-    }
-    unsigned char *const kept = (unsigned char *)(base + w.kept);
-    uint32_t *const list = (uint32_t *)(base + w.list), *const chunk = (uint32_t *)(base + w.chunk), *const count = (uint32_t *)(base + w.count);
-    hipError_t e = launch_fleet_reach_staggered(n, m, k, d, d_fleet, d_start, d_lo, d_hi, box_lo, box_hi, slack, total, speed, stream);
+    hipLaunchKernelGGL(k_shortlist_count, dim3((unsigned)w.chunks), dim3(kShortBlock), 0, stream, w.kept, w.problems, w.chunk);
+    hipLaunchKernelGGL(k_shortlist_scan, dim3(1), dim3(kShortBlock), 0, stream, w.chunk, w.chunks, w.count);
+    hipLaunchKernelGGL(k_shortlist_scatter, dim3((unsigned)w.chunks), dim3(kShortBlock), 0, stream, w.kept, w.problems, w.chunk, w.list);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+size_t fleet_cull_workspace_bytes(size_t n, size_t m, size_t k, int d, bool staggered)
+{
+    if (m < 2 || m > kFleetMost || d < 1 || d > 3 || n == 0 || k == 0) return 0;
+    if (n > (((size_t)1 << 32) - 1) / fleet_pair_count((unsigned)m)) return 0;      // a list entry is 32 bits
+    if (k > SIZE_MAX / 64 / (n * m)) return 0;                                       // the boxes' bytes fit
+    return cull_workspace(n, m, k, d, staggered, nullptr).bytes;
+}
+
+// The four passes of sections 30 and 31.  d_start null: one clock, k_sieve and k_shortlisted, and d_time_local is not looked at.
+hipError_t launch_fleet_contact_culled(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,
+                                       const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
+                                       double *d_time_local, double *d_rate, void *d_workspace, unsigned char *d_kept, uint32_t *d_list,
+                                       uint32_t *d_count, hipStream_t stream)
+{
+    const bool staggered = d_start != nullptr;
+    if (!d_level_sq || !d_workspace || fleet_cull_workspace_bytes(n, m, k, d, staggered) == 0) return hipErrorInvalidValue;
+    const CullWorkspace w = cull_workspace(n, m, k, d, staggered, d_workspace);
+    hipError_t e = launch_fleet_reach(n, m, k, d, d_fleet, d_start, d_lo, d_hi, w.box_lo, w.box_hi, w.slack, w.total, w.speed, stream);
     if (e != hipSuccess) return e;
     e = with_axes(d, [&](auto axes) {
         constexpr int D = decltype(axes)::value;
+        const dim3 grid((unsigned)((w.problems + kShortBlock - 1) / kShortBlock)), block(kShortBlock);
         WinnowIn<D> box;
-        for (int x = 0; x < D; ++x) { box.lo[x] = box_lo[x]; box.hi[x] = box_hi[x]; box.slack[x] = slack[x]; box.total[x] = total[x]; box.speed[x] = speed[x]; }
-        hipLaunchKernelGGL(k_winnow<D>, dim3((unsigned)((w.problems + kShortBlock - 1) / kShortBlock)), dim3(kShortBlock), 0, stream, box,
-                           w.problems, (unsigned)m, k, d_start, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, kept);
+        for (int x = 0; x < D; ++x) { box.lo[x] = w.box_lo[x]; box.hi[x] = w.box_hi[x]; box.slack[x] = w.slack[x]; box.total[x] = w.total[x]; box.speed[x] = w.speed[x]; }
+        if (staggered)
+            hipLaunchKernelGGL(k_winnow<D>, grid, block, 0, stream, box, w.problems, (unsigned)m, k, d_start, d_level_sq, level_per_pair, d_lo, d_hi,
+                               d_time, d_time_local, d_rate, w.kept);
+        else
+            hipLaunchKernelGGL(k_sieve<D>, grid, block, 0, stream, SieveIn<D>(box), w.problems, (unsigned)m, k, d_level_sq, level_per_pair, d_time,
+                               d_rate, w.kept);
         return hipGetLastError();
     });
     if (e != hipSuccess) return e;
-    e = launch_shortlist(w, kept, chunk, count, list, stream);
+    e = launch_shortlist(w, stream);
     if (e != hipSuccess) return e;
-    if (d_time || d_time_local || d_rate) {
+    if (staggered ? d_time || d_time_local || d_rate : d_time != nullptr) {      // (k_shortlisted stores its time unasked)
         e = launch_on_fleet(n, m, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
             constexpr int D = decltype(axes)::value;
-            hipLaunchKernelGGL(k_appointed<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_start, d_level_sq,
-                               level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, list, count);
+            if (staggered)
+                hipLaunchKernelGGL(k_appointed<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_start,
+                                   d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_time_local, d_rate, w.list, w.count);
+            else
+                hipLaunchKernelGGL(k_shortlisted<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_level_sq,
+                                   level_per_pair, d_lo, d_hi, d_time, d_rate, w.list, w.count);
         });
         if (e != hipSuccess) return e;
     }
-    if (d_kept) e = hipMemcpyAsync(d_kept, kept, w.problems, hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess && d_list) e = hipMemcpyAsync(d_list, list, w.problems * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess && d_count) e = hipMemcpyAsync(d_count, count, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
+    if (d_kept) e = hipMemcpyAsync(d_kept, w.kept, w.problems, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && d_list) e = hipMemcpyAsync(d_list, w.list, w.problems * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && d_count) e = hipMemcpyAsync(d_count, w.count, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
     return e;
 }
 
