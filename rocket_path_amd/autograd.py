@@ -489,19 +489,104 @@ def _check_tau(pos0, tau, who, name="tau"):
     return tau
 
 
-def _trajectory_launch(entry, device, spline, tau, *rest):
-    """One rp_trajectory_* launch on the current stream of `device`, no host synchronisation.  spline: the eight tensors (None: NULL);
-    rest: the entry's remaining arguments, tensors, None or lists of eight of them (tables)."""
+# What the query Functions below share: _enqueue is the one launch, _keep and _kept what a ctx holds, _query_shape
+# the shape of the outputs, _empty and _bars the buffers a launch writes, _class_masks the class of a time.
+def _enqueue(entry, device, *args):
+    """One launch of a capi entry on the current stream of `device`, no host synchronisation.  args: what the entry takes behind the
+    device and the stream, in its order (the sizes n, k[, m, d] included) -- an int goes as it is, a tensor as its address (the one
+    under torch.func's wrappers: _plain), None as NULL, a list or tuple of tensors and Nones as a table of addresses."""
     addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-    n, k = tau.shape
     with torch.cuda.device(device):      # the entry selects the device for its thread: put torch's choice back afterwards
-        stream = torch.cuda.current_stream(device).cuda_stream
-        entry(device.index, stream, n, k, [addr(t) for t in spline], addr(tau),
-              *[[addr(t) for t in a] if isinstance(a, (list, tuple)) else addr(a) for a in rest])
+        entry(device.index, torch.cuda.current_stream(device).cuda_stream,
+              *[a if isinstance(a, int) else [addr(t) for t in a] if isinstance(a, (list, tuple)) else addr(a) for a in args])
 
 
 def _dense(t):
     return t.contiguous() if t is not None else None
+
+
+def _empty(shape, device):
+    return torch.empty(shape, dtype=torch.float64, device=device)
+
+
+def _bars(need, shape, device):
+    """A buffer of `shape` for every flag of `need` that holds, None for the others: what a derivative launch is asked to form."""
+    return [_empty(shape, device) if wanted else None for wanted in need]
+
+
+def _query_shape(n, *queries):
+    """(n, k) of a query's outputs: the shape of the first per-query argument that was given, (n, 1) if none was."""
+    for t in queries:
+        if t is not None:
+            return t.shape
+    return (n, 1)
+
+
+def _keep(ctx, inputs, outputs=(), dead=(), given=None, forward=True):
+    """setup_context of the query Functions: keeps those of `inputs` that `given` flags (None: those that are not None) and `outputs`, for
+    backward and, unless forward=False, for jvp; `dead` are the outputs that are not differentiable.  Gradients are not materialised: an
+    output the loss does not use arrives in backward as None and goes to the kernel as NULL, which it does not read."""
+    ctx.set_materialize_grads(False)
+    if dead:
+        ctx.mark_non_differentiable(*dead)
+    ctx.given = given if given is not None else [t is not None for t in inputs]
+    kept = [t for t, has in zip(inputs, ctx.given) if has] + list(outputs)
+    ctx.save_for_backward(*kept)
+    if forward:
+        ctx.save_for_forward(*kept)
+
+
+def _kept(ctx):
+    """What _keep kept: (the inputs, None back in the places of those not kept; the outputs)"""
+    kept = iter(ctx.saved_tensors)
+    return [next(kept) if has else None for has in ctx.given], list(kept)
+
+
+def _class_masks(t, missing, tests, last_only=None):
+    """The class of each time: where t equals tests[0], else tests[1], ... (None: nowhere) -- exclusive, in that priority, never where
+    missing; the last class only where last_only holds."""
+    masks, taken = [], missing
+    for at, ref in enumerate(tests):
+        mask = (t == ref) & ~taken if ref is not None else torch.zeros_like(missing)
+        if last_only is not None and at == len(tests) - 1:
+            mask = mask & last_only
+        masks.append(mask)
+        taken = taken | mask
+    return masks
+
+
+def _axis_tables(inputs, d, vehicles=2):
+    """inputs[:8 d vehicles] -- vehicle-major, then axis-major, each axis in the table's order -- as one list per vehicle of its d lists of
+    eight dense tensors."""
+    return [[[_dense(t) for t in inputs[8 * (v * d + c):8 * (v * d + c) + 8]] for c in range(d)] for v in range(vehicles)]
+
+
+def _pair_gaps(a, b, t_a, t_b):
+    """The d gaps D_c = pos_Ac(t_a) - pos_Bc(t_b) of two vehicles of d axes: one evaluator launch on each axis' two splines"""
+    gaps = []
+    for sa, sb in zip(a, b):
+        pa, pb = _empty(t_a.shape, t_a.device), _empty(t_a.shape, t_a.device)
+        _enqueue(capi.trajectory_eval, t_a.device, *t_a.shape, sa, t_a, pa, None, None)
+        _enqueue(capi.trajectory_eval, t_a.device, *t_a.shape, sb, t_b, pb, None, None)
+        gaps.append(pa - pb)
+    return gaps
+
+
+def _eval_vjp(spline, tau, g, need):
+    """The one rp_trajectory_eval_vjp launch of _TrajectoryEval.backward and _TrajectoryVJP.forward: the eight bars and tau_bar that
+    `need` names, None for the others."""
+    bars = _bars(need[:8], tau.shape[0], tau.device)
+    tau_bar = _empty(tau.shape, tau.device) if need[8] else None
+    _enqueue(capi.trajectory_eval_vjp, tau.device, *tau.shape, spline, tau, *[_dense(x) for x in g], bars, tau_bar)
+    return tuple(bars) + (tau_bar,)
+
+
+def _backward2(ctx, vjp, g, *more):
+    """backward of the three order=2 Functions: the first-order launch made through `vjp`, so that a create_graph backward records it."""
+    count = len(ctx.given)
+    if all(x is None for x in g):
+        return (None,) * count
+    return vjp.apply(*_kept(ctx)[0], *g, tuple(ctx.needs_input_grad[:count]), *more)
 
 
 class _TrajectoryEval(torch.autograd.Function):
@@ -511,42 +596,33 @@ class _TrajectoryEval(torch.autograd.Function):
     def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, tau):
         spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
         tau = tau.contiguous()
-        outs = [torch.empty(tau.shape, dtype=torch.float64, device=tau.device) for _ in range(3)]
-        _trajectory_launch(capi.trajectory_eval, tau.device, spline, tau, *outs)
+        outs = [_empty(tau.shape, tau.device) for _ in range(3)]
+        _enqueue(capi.trajectory_eval, tau.device, *tau.shape, spline, tau, *outs)
         return tuple(outs)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None and goes to the kernel as NULL: not read
-        ctx.given = [t is not None for t in inputs]
-        kept = [t for t in inputs if t is not None]
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _keep(ctx, inputs)
 
     @staticmethod
     def _inputs(ctx):
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
+        inputs, _ = _kept(ctx)
         return [_dense(t) for t in inputs[:8]], inputs[8].contiguous()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, g_pos, g_vel, g_acc):
-        if g_pos is None and g_vel is None and g_acc is None:
+    def backward(ctx, *g):
+        if all(x is None for x in g):
             return (None,) * 9
         spline, tau = _TrajectoryEval._inputs(ctx)
-        n = tau.shape[0]
-        bars = [torch.empty(n, dtype=torch.float64, device=tau.device) if need else None for need in ctx.needs_input_grad[:8]]
-        tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if ctx.needs_input_grad[8] else None
-        _trajectory_launch(capi.trajectory_eval_vjp, tau.device, spline, tau, _dense(g_pos), _dense(g_vel), _dense(g_acc), bars, tau_bar)
-        return tuple(bars) + (tau_bar,)
+        return _eval_vjp(spline, tau, g, ctx.needs_input_grad)
 
     @staticmethod
     def jvp(ctx, *tangents):
         spline, tau = _TrajectoryEval._inputs(ctx)
         dots = [_dense(t) for t in tangents]
-        outs = [torch.empty(tau.shape, dtype=torch.float64, device=tau.device) for _ in range(3)]
-        _trajectory_launch(capi.trajectory_eval_jvp, tau.device, spline, tau, dots[:8], dots[8], *outs)
+        outs = [_empty(tau.shape, tau.device) for _ in range(3)]
+        _enqueue(capi.trajectory_eval_jvp, tau.device, *tau.shape, spline, tau, dots[:8], dots[8], *outs)
         return tuple(outs)
 
 
@@ -555,12 +631,8 @@ class _TrajectoryEval2(_TrajectoryEval):
     the same one rp_trajectory_eval_vjp launch in backward, made through _TrajectoryVJP so that a create_graph backward records it."""
 
     @staticmethod
-    def backward(ctx, g_pos, g_vel, g_acc):
-        if g_pos is None and g_vel is None and g_acc is None:
-            return (None,) * 9
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        return _TrajectoryVJP.apply(*inputs, g_pos, g_vel, g_acc, tuple(ctx.needs_input_grad[:9]))
+    def backward(ctx, *g):
+        return _backward2(ctx, _TrajectoryVJP, g)
 
 
 class _TrajectoryVJP(torch.autograd.Function):
@@ -573,18 +645,11 @@ class _TrajectoryVJP(torch.autograd.Function):
     @staticmethod
     def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, tau, g_pos, g_vel, g_acc, need):
         spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
-        tau = tau.contiguous()
-        n = tau.shape[0]
-        bars = [torch.empty(n, dtype=torch.float64, device=tau.device) if need[f] else None for f in range(8)]
-        tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if need[8] else None
-        _trajectory_launch(capi.trajectory_eval_vjp, tau.device, spline, tau, _dense(g_pos), _dense(g_vel), _dense(g_acc), bars, tau_bar)
-        return tuple(bars) + (tau_bar,)
+        return _eval_vjp(spline, tau.contiguous(), (g_pos, g_vel, g_acc), need)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)      # a bar nothing downstream uses arrives as None and goes to the kernels as NULL: not read
-        ctx.given = [t is not None for t in inputs[:12]]
-        ctx.save_for_backward(*[t for t in inputs[:12] if t is not None])
+        _keep(ctx, inputs[:12], forward=False)      # (a bar nothing downstream uses arrives as None too)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -592,19 +657,18 @@ class _TrajectoryVJP(torch.autograd.Function):
         out = [None] * 13
         if all(x is None for x in u):
             return tuple(out)
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
+        inputs, _ = _kept(ctx)
         spline, tau, g = [_dense(t) for t in inputs[:8]], inputs[8].contiguous(), [_dense(t) for t in inputs[9:12]]
-        need, n, dev = ctx.needs_input_grad, tau.shape[0], tau.device
+        need, dev = ctx.needs_input_grad, tau.device
         dots, tau_dot = [_dense(x) for x in u[:8]], _dense(u[8])
         if any(need[9:12]):
-            outs = [torch.empty(tau.shape, dtype=torch.float64, device=dev) if need[9 + c] else None for c in range(3)]
-            _trajectory_launch(capi.trajectory_eval_jvp, dev, spline, tau, dots, tau_dot, *outs)
+            outs = _bars(need[9:12], tau.shape, dev)
+            _enqueue(capi.trajectory_eval_jvp, dev, *tau.shape, spline, tau, dots, tau_dot, *outs)
             out[9:12] = outs
         if any(need[:9]) and any(x is not None for x in g):
-            bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(8)]
-            tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=dev) if need[8] else None
-            _trajectory_launch(capi.trajectory_eval_hvp, dev, spline, tau, *g, dots, tau_dot, bars, tau_bar)
+            bars = _bars(need[:8], tau.shape[0], dev)
+            tau_bar = _empty(tau.shape, dev) if need[8] else None
+            _enqueue(capi.trajectory_eval_hvp, dev, *tau.shape, spline, tau, *g, dots, tau_dot, bars, tau_bar)
             out[:9] = bars + [tau_bar]
         return tuple(out)
 
@@ -666,27 +730,20 @@ class _TrajectoryCrossing(torch.autograd.Function):
     def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, level):
         spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
         level = level.contiguous()
-        time, vel = (torch.empty(level.shape, dtype=torch.float64, device=level.device) for _ in range(2))
-        _trajectory_launch(capi.trajectory_crossing, level.device, spline, level, time, vel)
+        time, vel = _empty(level.shape, level.device), _empty(level.shape, level.device)
+        _enqueue(capi.trajectory_crossing, level.device, *level.shape, spline, level, time, vel)
         return time, vel
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(output[1])
-        ctx.given = [t is not None for t in inputs[:8]]
-        kept = [t for t in inputs[:8] if t is not None] + list(output)      # the level itself is in neither derivative
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _keep(ctx, inputs[:8], output, dead=output[1:])      # the level itself is in neither derivative
 
     @staticmethod
     def _saved(ctx):
         """(the eight spline tensors, the times with 0 where no crossing exists, vel, where no crossing exists)"""
-        kept = iter(ctx.saved_tensors)
-        spline = [_dense(next(kept)) if given else None for given in ctx.given]
-        time, vel = next(kept), next(kept)
+        spline, (time, vel) = _kept(ctx)
         missing = torch.isnan(time)
-        return spline, torch.where(missing, torch.zeros_like(time), time), vel, missing
+        return [_dense(t) for t in spline], torch.where(missing, torch.zeros_like(time), time), vel, missing
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -695,17 +752,17 @@ class _TrajectoryCrossing(torch.autograd.Function):
             return (None,) * 9
         spline, tau, vel, missing = _TrajectoryCrossing._saved(ctx)
         w = torch.where(missing, torch.zeros_like(tau), g_time / vel)      # an unreached level: gradient 0
-        bars = [torch.empty(tau.shape[0], dtype=torch.float64, device=tau.device) if need else None for need in ctx.needs_input_grad[:8]]
+        bars = _bars(ctx.needs_input_grad[:8], tau.shape[0], tau.device)
         if any(b is not None for b in bars):
-            _trajectory_launch(capi.trajectory_eval_vjp, tau.device, spline, tau, -w, None, None, bars, None)
+            _enqueue(capi.trajectory_eval_vjp, tau.device, *tau.shape, spline, tau, -w, None, None, bars, None)
         return tuple(bars) + (w if ctx.needs_input_grad[8] else None,)
 
     @staticmethod
     def jvp(ctx, *tangents):
         spline, tau, vel, missing = _TrajectoryCrossing._saved(ctx)
         dots = [_dense(t) for t in tangents[:8]]
-        pos_dot = torch.empty(tau.shape, dtype=torch.float64, device=tau.device)
-        _trajectory_launch(capi.trajectory_eval_jvp, tau.device, spline, tau, dots, None, pos_dot, None, None)
+        pos_dot = _empty(tau.shape, tau.device)
+        _enqueue(capi.trajectory_eval_jvp, tau.device, *tau.shape, spline, tau, dots, None, pos_dot, None, None)
         level_dot = tangents[8] if tangents[8] is not None else torch.zeros_like(tau)
         time_dot = torch.where(missing, torch.full_like(tau, float("nan")), (level_dot - pos_dot) / vel)
         return time_dot, None
@@ -751,42 +808,27 @@ class _TrajectoryExtrema(torch.autograd.Function):
     def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, lo, hi):
         spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
         lo, hi = _dense(lo), _dense(hi)
-        shape = lo.shape if lo is not None else hi.shape if hi is not None else (pos0.shape[0], 1)
-        outs = [torch.empty(shape, dtype=torch.float64, device=pos0.device) for _ in range(8)]
-        n, k = shape
-        with torch.cuda.device(pos0.device):      # as _trajectory_launch
-            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_extrema(pos0.device.index, torch.cuda.current_stream(pos0.device).cuda_stream, n, k, [addr(t) for t in spline],
-                                    addr(lo), addr(hi), [addr(t) for t in outs[:4]], [addr(t) for t in outs[4:]])
+        n, k = _query_shape(pos0.shape[0], lo, hi)
+        outs = [_empty((n, k), pos0.device) for _ in range(8)]
+        _enqueue(capi.trajectory_extrema, pos0.device, n, k, spline, lo, hi, outs[:4], outs[4:])
         return tuple(outs)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(*output[4:])
-        ctx.given = [t is not None for t in inputs]
-        kept = [t for t in inputs if t is not None] + list(output)
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _keep(ctx, inputs, output, dead=output[4:])
 
     @staticmethod
     def _saved(ctx):
         """(the eight spline tensors; the four times side by side, (n, 4 k), 0 where the value is NaN; where it is NaN; the class masks
         LO, HI, END, KNOT of each time, exclusive and in that priority)"""
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        outs = list(kept)
+        inputs, outs = _kept(ctx)
         spline, lo, hi = [_dense(t) for t in inputs[:8]], inputs[8], inputs[9]
         time = torch.cat(outs[4:], dim=1)
         missing = torch.isnan(torch.cat(outs[:4], dim=1)) | torch.isnan(time)
         t0 = torch.where(missing, torch.zeros_like(time), time)
         d0, T = spline[6].unsqueeze(1), (spline[6] + spline[7]).unsqueeze(1)
-        none = torch.zeros_like(missing)
-        is_lo = (t0 == lo.repeat(1, 4)) & ~missing if lo is not None else none
-        is_hi = (t0 == hi.repeat(1, 4)) & ~missing & ~is_lo if hi is not None else none
-        is_end = (t0 == T) & ~missing & ~is_lo & ~is_hi
-        is_knot = (t0 == d0) & ~missing & ~is_lo & ~is_hi & ~is_end
-        return spline, t0, missing, (is_lo, is_hi, is_end, is_knot)
+        wide = lambda t: t.repeat(1, 4) if t is not None else None      # noqa: E731
+        return spline, t0, missing, _class_masks(t0, missing, [wide(lo), wide(hi), T, d0])
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -802,10 +844,10 @@ class _TrajectoryExtrema(torch.autograd.Function):
         g_pos = torch.where(missing, torch.zeros_like(g_pos), g_pos)      # a NaN value: gradient 0
         g_vel = torch.where(missing, torch.zeros_like(g_vel), g_vel)
         need = ctx.needs_input_grad
-        bars = [torch.empty(n, dtype=torch.float64, device=t0.device) if need[f] else None for f in range(8)]
+        bars = _bars(need[:8], n, t0.device)
         want_tau = need[6] or need[7] or need[8] or need[9]
-        tau_bar = torch.empty(t0.shape, dtype=torch.float64, device=t0.device) if want_tau else None
-        _trajectory_launch(capi.trajectory_eval_vjp, t0.device, spline, t0, g_pos, g_vel, None, bars, tau_bar)
+        tau_bar = _empty(t0.shape, t0.device) if want_tau else None
+        _enqueue(capi.trajectory_eval_vjp, t0.device, *t0.shape, spline, t0, g_pos, g_vel, None, bars, tau_bar)
         lo_bar = hi_bar = None
         if want_tau:
             routed = lambda mask: torch.where(mask, tau_bar, torch.zeros_like(tau_bar))      # noqa: E731
@@ -837,8 +879,8 @@ class _TrajectoryExtrema(torch.autograd.Function):
             tau_dot = torch.where(is_end | is_knot, d0_dot, tau_dot)
         if d1_dot is not None:
             tau_dot = torch.where(is_end, tau_dot + d1_dot, tau_dot)
-        pos_dot, vel_dot = (torch.empty(t0.shape, dtype=torch.float64, device=t0.device) for _ in range(2))
-        _trajectory_launch(capi.trajectory_eval_jvp, t0.device, spline, t0, dots, tau_dot.contiguous(), pos_dot, vel_dot, None)
+        pos_dot, vel_dot = _empty(t0.shape, t0.device), _empty(t0.shape, t0.device)
+        _enqueue(capi.trajectory_eval_jvp, t0.device, *t0.shape, spline, t0, dots, tau_dot.contiguous(), pos_dot, vel_dot, None)
         nan = torch.full_like(t0, float("nan"))
         pos_dot, vel_dot = torch.where(missing, nan, pos_dot), torch.where(missing, nan, vel_dot)
         return tuple(x.clone() for x in (pos_dot[:, :k], pos_dot[:, k:2 * k], vel_dot[:, 2 * k:3 * k], vel_dot[:, 3 * k:])) + (None,) * 4
@@ -896,34 +938,21 @@ class _TrajectoryGap(torch.autograd.Function):
     def forward(*inputs):
         a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
         lo, hi, delay = (_dense(t) for t in inputs[16:19])
-        given = lo if lo is not None else hi if hi is not None else delay
-        shape = given.shape if given is not None else (inputs[0].shape[0], 1)
+        n, k = _query_shape(inputs[0].shape[0], lo, hi, delay)
         device = inputs[0].device
-        outs = [torch.empty(shape, dtype=torch.float64, device=device) for _ in range(4)]
-        n, k = shape
-        with torch.cuda.device(device):      # as _trajectory_launch
-            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_gap(device.index, torch.cuda.current_stream(device).cuda_stream, n, k, [addr(t) for t in a], [addr(t) for t in b],
-                                addr(lo), addr(hi), addr(delay), [addr(t) for t in outs[:2]], [addr(t) for t in outs[2:]])
+        outs = [_empty((n, k), device) for _ in range(4)]
+        _enqueue(capi.trajectory_gap, device, n, k, a, b, lo, hi, delay, outs[:2], outs[2:])
         return tuple(outs)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(*output[2:])
-        ctx.given = [t is not None for t in inputs]
-        kept = [t for t in inputs if t is not None] + list(output)
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _keep(ctx, inputs, output, dead=output[2:])
 
     @staticmethod
     def _saved(ctx):
-        """(A's and B's eight tensors; the delay side by side, (n, 2 k), zeros for None; the two times side by side, 0 where the value is
-        NaN, and B's, those minus the delay; where it is NaN; the class masks LO, HI, END_A, END_B, KNOT_A, KNOT_B, START of each time,
-        exclusive and in that priority)"""
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        outs = list(kept)
+        """(A's and B's eight tensors; the two times side by side, (n, 2 k), 0 where the value is NaN, and B's, those minus the delay;
+        where it is NaN; the class masks LO, HI, END_A, END_B, KNOT_A, KNOT_B, START of each time, exclusive and in that priority)"""
+        inputs, outs = _kept(ctx)
         a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
         lo, hi, delay = inputs[16:19]
         time = torch.cat(outs[2:], dim=1)
@@ -932,15 +961,9 @@ class _TrajectoryGap(torch.autograd.Function):
         t_a = torch.where(missing, zero, time)
         shift = delay.repeat(1, 2) if delay is not None else zero
         t_b = torch.where(missing, zero, t_a - shift)
-        masks, taken = [], missing
         tests = ((lo.repeat(1, 2) if lo is not None else None), (hi.repeat(1, 2) if hi is not None else None),
                  (a[6] + a[7]).unsqueeze(1), shift + (b[6] + b[7]).unsqueeze(1), a[6].unsqueeze(1), shift + b[6].unsqueeze(1), shift)
-        for at, ref in enumerate(tests):
-            mask = (t_a == ref) & ~taken if ref is not None else torch.zeros_like(missing)
-            if at == 6:
-                mask = mask & (shift > 0)      # a start clamped to +0.0 is a constant
-            masks.append(mask)
-            taken = taken | mask
+        masks = _class_masks(t_a, missing, tests, last_only=shift > 0)      # a start clamped to +0.0 is a constant
         return a, b, t_a.contiguous(), t_b.contiguous(), missing, masks
 
     @staticmethod
@@ -957,10 +980,10 @@ class _TrajectoryGap(torch.autograd.Function):
         want_time = need[6] or need[7] or need[14] or need[15] or need[16] or need[17] or need[18]
         bars, tau_bars = [], []
         for first, spline, tau, g_pos in ((0, a, t_a, g), (8, b, t_b, -g)):
-            bar = [torch.empty(n, dtype=torch.float64, device=tau.device) if need[first + f] else None for f in range(8)]
-            tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if want_time else None
+            bar = _bars(need[first:first + 8], n, tau.device)
+            tau_bar = _empty(tau.shape, tau.device) if want_time else None
             if want_time or any(x is not None for x in bar):
-                _trajectory_launch(capi.trajectory_eval_vjp, tau.device, spline, tau, g_pos.contiguous(), None, None, bar, tau_bar)
+                _enqueue(capi.trajectory_eval_vjp, tau.device, *tau.shape, spline, tau, g_pos.contiguous(), None, None, bar, tau_bar)
             bars += bar
             tau_bars.append(tau_bar)
         lo_bar = hi_bar = delay_bar = None
@@ -995,9 +1018,9 @@ class _TrajectoryGap(torch.autograd.Function):
         time_dot = torch.where(knot_a, col(dots[6]), time_dot)
         time_dot = torch.where(knot_b, delay_dot + col(dots[14]), time_dot)
         time_dot = torch.where(start, delay_dot, time_dot)
-        pos_a, pos_b = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
-        _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, a, t_a, dots[:8], time_dot.contiguous(), pos_a, None, None)
-        _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, b, t_b, dots[8:], (time_dot - delay_dot).contiguous(), pos_b, None, None)
+        pos_a, pos_b = _empty(t_a.shape, t_a.device), _empty(t_a.shape, t_a.device)
+        _enqueue(capi.trajectory_eval_jvp, t_a.device, *t_a.shape, a, t_a, dots[:8], time_dot.contiguous(), pos_a, None, None)
+        _enqueue(capi.trajectory_eval_jvp, t_a.device, *t_a.shape, b, t_b, dots[8:], (time_dot - delay_dot).contiguous(), pos_b, None, None)
         gap_dot = torch.where(missing, torch.full_like(t_a, float("nan")), pos_a - pos_b)
         return gap_dot[:, :k].clone(), gap_dot[:, k:].clone(), None, None
 
@@ -1117,33 +1140,22 @@ class _TrajectoryMeeting(torch.autograd.Function):
     def forward(*inputs):
         a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
         level, lo, hi, delay = (_dense(t) for t in inputs[16:20])
-        given = next((t for t in (level, lo, hi, delay) if t is not None), None)
-        shape = given.shape if given is not None else (inputs[0].shape[0], 1)
+        n, k = _query_shape(inputs[0].shape[0], level, lo, hi, delay)
         device = inputs[0].device
-        time, relvel = (torch.empty(shape, dtype=torch.float64, device=device) for _ in range(2))
-        n, k = shape
-        with torch.cuda.device(device):      # as _trajectory_launch
-            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_meeting(device.index, torch.cuda.current_stream(device).cuda_stream, n, k, [addr(t) for t in a],
-                                    [addr(t) for t in b], addr(level), addr(lo), addr(hi), addr(delay), addr(time), addr(relvel))
+        time, relvel = _empty((n, k), device), _empty((n, k), device)
+        _enqueue(capi.trajectory_meeting, device, n, k, a, b, level, lo, hi, delay, time, relvel)
         return time, relvel
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(output[1])
-        ctx.given = [t is not None for t in inputs[:16]] + [False, False, False, inputs[19] is not None]      # neither derivative reads
-        kept = [t for t, given in zip(inputs, ctx.given) if given] + list(output)                             # the level, lo or hi
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        # neither derivative reads the level, lo or hi
+        _keep(ctx, inputs, output, dead=output[1:], given=[t is not None for t in inputs[:16]] + [False, False, False, inputs[19] is not None])
 
     @staticmethod
     def _saved(ctx):
         """(A's and B's eight tensors; A's times, 0 where there is no meeting, and B's, those minus the delay; relvel; where there is no
         meeting)"""
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        time, relvel = next(kept), next(kept)
+        inputs, (time, relvel) = _kept(ctx)
         a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
         delay = inputs[19]
         missing = torch.isnan(time)
@@ -1159,13 +1171,12 @@ class _TrajectoryMeeting(torch.autograd.Function):
         a, b, t_a, t_b, relvel, missing = _TrajectoryMeeting._saved(ctx)
         need = ctx.needs_input_grad
         w = torch.where(missing, torch.zeros_like(t_a), g_time / relvel)      # an unreached level: gradient 0
-        n = t_a.shape[0]
-        bars = [torch.empty(n, dtype=torch.float64, device=t_a.device) if need[f] else None for f in range(16)]
-        tau_bar = torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) if need[19] else None
+        bars = _bars(need[:16], t_a.shape[0], t_a.device)
+        tau_bar = _empty(t_a.shape, t_a.device) if need[19] else None
         if any(x is not None for x in bars[:8]):
-            _trajectory_launch(capi.trajectory_eval_vjp, t_a.device, a, t_a, -w, None, None, bars[:8], None)
+            _enqueue(capi.trajectory_eval_vjp, t_a.device, *t_a.shape, a, t_a, -w, None, None, bars[:8], None)
         if tau_bar is not None or any(x is not None for x in bars[8:]):      # B is at time - delay
-            _trajectory_launch(capi.trajectory_eval_vjp, t_a.device, b, t_b, w, None, None, bars[8:], tau_bar)
+            _enqueue(capi.trajectory_eval_vjp, t_a.device, *t_a.shape, b, t_b, w, None, None, bars[8:], tau_bar)
         return tuple(bars) + (w if need[16] else None, None, None, -tau_bar if tau_bar is not None else None)
 
     @staticmethod
@@ -1173,10 +1184,10 @@ class _TrajectoryMeeting(torch.autograd.Function):
         a, b, t_a, t_b, relvel, missing = _TrajectoryMeeting._saved(ctx)
         dots = [_dense(t) for t in tangents[:16]]
         level_dot, delay_dot = tangents[16], tangents[19]
-        pos_a, pos_b = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
-        _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, a, t_a, dots[:8], None, pos_a, None, None)
-        _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, b, t_b, dots[8:], (-delay_dot).contiguous() if delay_dot is not None else None,
-                           pos_b, None, None)
+        pos_a, pos_b = _empty(t_a.shape, t_a.device), _empty(t_a.shape, t_a.device)
+        _enqueue(capi.trajectory_eval_jvp, t_a.device, *t_a.shape, a, t_a, dots[:8], None, pos_a, None, None)
+        _enqueue(capi.trajectory_eval_jvp, t_a.device, *t_a.shape, b, t_b, dots[8:], (-delay_dot).contiguous() if delay_dot is not None else None,
+                 pos_b, None, None)
         if level_dot is None:
             level_dot = torch.zeros_like(t_a)
         time_dot = torch.where(missing, torch.full_like(t_a, float("nan")), (level_dot - pos_a + pos_b) / relvel)
@@ -1240,26 +1251,16 @@ class _TrajectorySeparation(torch.autograd.Function):
     def forward(d, *inputs):
         a, b = [_dense(t) for t in inputs[:8 * d]], [_dense(t) for t in inputs[8 * d:16 * d]]
         lo, hi, delay = (_dense(t) for t in inputs[16 * d:])
-        given = lo if lo is not None else hi if hi is not None else delay
-        shape = given.shape if given is not None else (inputs[0].shape[0], 1)
+        n, k = _query_shape(inputs[0].shape[0], lo, hi, delay)
         device = inputs[0].device
-        value, time = (torch.empty(shape, dtype=torch.float64, device=device) for _ in range(2))
-        n, k = shape
-        with torch.cuda.device(device):      # as _trajectory_launch
-            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_separation(device.index, torch.cuda.current_stream(device).cuda_stream, n, k, d, [addr(t) for t in a],
-                                       [addr(t) for t in b], addr(lo), addr(hi), addr(delay), addr(value), addr(time))
+        value, time = _empty((n, k), device), _empty((n, k), device)
+        _enqueue(capi.trajectory_separation, device, n, k, d, a, b, lo, hi, delay, value, time)
         return value, time
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(output[1])
         ctx.d = inputs[0]
-        ctx.given = [t is not None for t in inputs[1:]]
-        kept = [t for t in inputs[1:] if t is not None] + list(output)
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _keep(ctx, inputs[1:], output, dead=output[1:])
 
     @staticmethod
     def _saved(ctx):
@@ -1267,11 +1268,8 @@ class _TrajectorySeparation(torch.autograd.Function):
         delay; where it is NaN; the d gaps D_c there; the class masks LO, HI, [END of A_c], [END of B_c], START, exclusive and in that
         priority)"""
         d = ctx.d
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        value, time = list(kept)
-        a = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
-        b = [[_dense(t) for t in inputs[8 * (d + c):8 * (d + c) + 8]] for c in range(d)]
+        inputs, (value, time) = _kept(ctx)
+        a, b = _axis_tables(inputs, d)
         lo, hi, delay = inputs[16 * d:]
         missing = torch.isnan(value) | torch.isnan(time)
         zero = torch.zeros_like(time)
@@ -1279,20 +1277,8 @@ class _TrajectorySeparation(torch.autograd.Function):
         shift = delay if delay is not None else zero
         t_b = torch.where(missing, zero, t_a - shift).contiguous()
         tests = [lo, hi] + [(s[6] + s[7]).unsqueeze(1) for s in a] + [shift + (s[6] + s[7]).unsqueeze(1) for s in b] + [shift]
-        masks, taken = [], missing
-        for at, ref in enumerate(tests):
-            mask = (t_a == ref) & ~taken if ref is not None else torch.zeros_like(missing)
-            if at == len(tests) - 1:
-                mask = mask & (shift > 0)      # a start clamped to +0.0 is a constant
-            masks.append(mask)
-            taken = taken | mask
-        gaps = []
-        for sa, sb in zip(a, b):
-            pa, pb = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
-            _trajectory_launch(capi.trajectory_eval, t_a.device, sa, t_a, pa, None, None)
-            _trajectory_launch(capi.trajectory_eval, t_a.device, sb, t_b, pb, None, None)
-            gaps.append(pa - pb)
-        return a, b, shift, t_a, t_b, missing, gaps, (masks[0], masks[1], masks[2:2 + d], masks[2 + d:2 + 2 * d], masks[-1])
+        masks = _class_masks(t_a, missing, tests, last_only=shift > 0)      # a start clamped to +0.0 is a constant
+        return a, b, shift, t_a, t_b, missing, _pair_gaps(a, b, t_a, t_b), (masks[0], masks[1], masks[2:2 + d], masks[2 + d:2 + 2 * d], masks[-1])
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -1310,10 +1296,10 @@ class _TrajectorySeparation(torch.autograd.Function):
             g_pos = ((2.0 * g) * gaps[c]).contiguous()
             for side, spline, tau, upstream in ((0, a[c], t_a, g_pos), (1, b[c], t_b, -g_pos)):
                 first = 8 * (side * d + c)
-                bar = [torch.empty(n, dtype=torch.float64, device=tau.device) if need[first + f] else None for f in range(8)]
-                tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if want_time else None
+                bar = _bars(need[first:first + 8], n, tau.device)
+                tau_bar = _empty(tau.shape, tau.device) if want_time else None
                 if want_time or any(x is not None for x in bar):
-                    _trajectory_launch(capi.trajectory_eval_vjp, tau.device, spline, tau, upstream, None, None, bar, tau_bar)
+                    _enqueue(capi.trajectory_eval_vjp, tau.device, *tau.shape, spline, tau, upstream, None, None, bar, tau_bar)
                 bars[first:first + 8] = bar
                 if want_time:
                     time_bar = tau_bar if time_bar is None else time_bar + tau_bar
@@ -1357,10 +1343,10 @@ class _TrajectorySeparation(torch.autograd.Function):
         time_dot = torch.where(start, delay_dot, time_dot)
         value_dot = zero
         for c in range(d):
-            pos_a, pos_b = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
-            _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, a[c], t_a, dots[8 * c:8 * c + 8], time_dot.contiguous(), pos_a, None, None)
-            _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, b[c], t_b, dots[8 * (d + c):8 * (d + c) + 8],
-                               (time_dot - delay_dot).contiguous(), pos_b, None, None)
+            pos_a, pos_b = _empty(t_a.shape, t_a.device), _empty(t_a.shape, t_a.device)
+            _enqueue(capi.trajectory_eval_jvp, t_a.device, n, k, a[c], t_a, dots[8 * c:8 * c + 8], time_dot.contiguous(), pos_a, None, None)
+            _enqueue(capi.trajectory_eval_jvp, t_a.device, n, k, b[c], t_b, dots[8 * (d + c):8 * (d + c) + 8],
+                     (time_dot - delay_dot).contiguous(), pos_b, None, None)
             value_dot = value_dot + (2.0 * gaps[c]) * (pos_a - pos_b)
         return torch.where(missing, torch.full_like(t_a, float("nan")), value_dot), None
 
@@ -1545,37 +1531,27 @@ def fleet_slots(m, device=None):
 # What the four fleet Functions share: one forward launch each; for the derivatives the pair entry's rule done per
 # vehicle -- the times gathered through the slot table to (n m, (m - 1) k), per axis one evaluator launch and one launch of its derivative
 # on the n m splines, every sum over a vehicle's pairs a gather through the slot table and a sum.
-def _fleet_forward(entry, d, m, inputs, n, k, outputs, middle):
+def _fleet_forward(entry, d, m, inputs, n, k, outputs, *middle, tail=()):
     """One launch of a fleet entry on the current stream: the fleet's 8 d tensors (inputs[:8 d]; axis-major, each axis in the table's
-    order, each n m values with vehicle v of scene s at s m + v), middle(addr)'s arguments, then `outputs` fresh (n, pairs, k) tensors,
-    which it returns."""
+    order, each n m values with vehicle v of scene s at s m + v), `middle`, then `outputs` fresh (n, pairs, k) tensors, which it returns,
+    then `tail`."""
     fleet = [_dense(t) for t in inputs[:8 * d]]
-    device = inputs[0].device
-    out = tuple(torch.empty((n, m * (m - 1) // 2, k), dtype=torch.float64, device=device) for _ in range(outputs))
-    with torch.cuda.device(device):      # as _trajectory_launch
-        addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-        entry(device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in fleet], *middle(addr),
-              *[addr(t) for t in out])
+    out = tuple(_empty((n, m * (m - 1) // 2, k), inputs[0].device) for _ in range(outputs))
+    _enqueue(entry, inputs[0].device, n, m, k, d, fleet, *middle, *out, *tail)
     return out
 
 
 def _fleet_setup(ctx, inputs, count, dead, outputs):
-    """Keeps d, m, those of the first `count` inputs after them that were given, and `outputs`, for both modes; `dead` are the outputs
-    that are not differentiable."""
-    ctx.set_materialize_grads(False)
-    ctx.mark_non_differentiable(*dead)
+    """Keeps d, m, those of the first `count` inputs after them that were given, and `outputs`, for both modes (_keep); `dead` are the
+    outputs that are not differentiable."""
     ctx.d, ctx.m = inputs[0], inputs[1]
-    ctx.given = [t is not None for t in inputs[2:2 + count]]
-    kept = [t for t in inputs[2:2 + count] if t is not None] + list(outputs)
-    ctx.save_for_backward(*kept)
-    ctx.save_for_forward(*kept)
+    _keep(ctx, inputs[2:2 + count], outputs, dead)
 
 
 def _fleet_kept(ctx):
     """What _fleet_setup kept: (the d lists of eight fleet tensors, the other inputs among the `count`, the outputs)"""
-    kept = iter(ctx.saved_tensors)
-    inputs = [next(kept) if given else None for given in ctx.given]
-    return [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(ctx.d)], inputs[8 * ctx.d:], list(kept)
+    inputs, outputs = _kept(ctx)
+    return _axis_tables(inputs, ctx.d, 1)[0], inputs[8 * ctx.d:], outputs
 
 
 _FleetTimes = collections.namedtuple("_FleetTimes", "slots signs delay t tau per_pair through")
@@ -1612,24 +1588,11 @@ def _fleet_gaps(fleet, at):
     """The d gaps D_c at the pairs' times, (n, pairs, k) each: one evaluator launch per axis"""
     gaps = []
     for s in fleet:
-        pos = torch.empty(at.tau.shape, dtype=torch.float64, device=at.tau.device)
-        _trajectory_launch(capi.trajectory_eval, at.tau.device, s, at.tau, pos, None, None)
+        pos = _empty(at.tau.shape, at.tau.device)
+        _enqueue(capi.trajectory_eval, at.tau.device, *at.tau.shape, s, at.tau, pos, None, None)
         pos_first, pos_second = at.per_pair(pos)
         gaps.append(pos_first - pos_second)
     return gaps
-
-
-def _class_masks(t, missing, tests, last_only=None):
-    """The class of each time: where t equals tests[0], else tests[1], ... (None: nowhere) -- exclusive, in that priority, never where
-    missing; the last class only where last_only holds."""
-    masks, taken = [], missing
-    for at, ref in enumerate(tests):
-        mask = (t == ref) & ~taken if ref is not None else torch.zeros_like(missing)
-        if last_only is not None and at == len(tests) - 1:
-            mask = mask & last_only
-        masks.append(mask)
-        taken = taken | mask
-    return masks
 
 
 def _fleet_vjp(fleet, at, need, want_tau, g_gap):
@@ -1638,11 +1601,11 @@ def _fleet_vjp(fleet, at, need, want_tau, g_gap):
     want_tau).  An axis that needs neither is not launched."""
     tau = at.tau
     for c, s in enumerate(fleet):
-        bar = [torch.empty(tau.shape[0], dtype=torch.float64, device=tau.device) if need[8 * c + f] else None for f in range(8)]
-        tau_bar = torch.empty(tau.shape, dtype=torch.float64, device=tau.device) if want_tau else None
+        bar = _bars(need[8 * c:8 * c + 8], tau.shape[0], tau.device)
+        tau_bar = _empty(tau.shape, tau.device) if want_tau else None
         if want_tau or any(x is not None for x in bar):
             upstream = (at.signs * at.through(g_gap(c))).reshape(tau.shape).contiguous()
-            _trajectory_launch(capi.trajectory_eval_vjp, tau.device, s, tau, upstream, None, None, bar, tau_bar)
+            _enqueue(capi.trajectory_eval_vjp, tau.device, *tau.shape, s, tau, upstream, None, None, bar, tau_bar)
         yield bar, tau_bar
 
 
@@ -1650,8 +1613,8 @@ def _fleet_jvp(fleet, at, gaps, dots, tau_dot):
     """Axis by axis, the evaluator's forward launch on the n m splines at at.tau; yields the axis' share of the tangent of the squared
     distance, 2 D_c (d pos_first,c - d pos_second,c), (n, pairs, k)."""
     for c, s in enumerate(fleet):
-        pos_dot = torch.empty(at.tau.shape, dtype=torch.float64, device=at.tau.device)
-        _trajectory_launch(capi.trajectory_eval_jvp, at.tau.device, s, at.tau, dots[8 * c:8 * c + 8], tau_dot, pos_dot, None, None)
+        pos_dot = _empty(at.tau.shape, at.tau.device)
+        _enqueue(capi.trajectory_eval_jvp, at.tau.device, *at.tau.shape, s, at.tau, dots[8 * c:8 * c + 8], tau_dot, pos_dot, None, None)
         dot_first, dot_second = at.per_pair(pos_dot)
         yield (2.0 * gaps[c]) * (dot_first - dot_second)
 
@@ -1679,7 +1642,7 @@ class _TrajectoryFleetSeparation(torch.autograd.Function):
         given = lo if lo is not None else hi
         n = inputs[0].shape[0] // m
         k = given.shape[1] if given is not None else 1
-        return _fleet_forward(capi.trajectory_fleet_separation, d, m, inputs, n, k, 2, lambda addr: (addr(lo), addr(hi)))
+        return _fleet_forward(capi.trajectory_fleet_separation, d, m, inputs, n, k, 2, lo, hi)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -1768,8 +1731,7 @@ class _TrajectoryStaggeredSeparation(torch.autograd.Function):
         given = lo if lo is not None else hi
         n = start.shape[0]
         k = given.shape[1] if given is not None else 1
-        return _fleet_forward(capi.trajectory_fleet_separation_staggered, d, m, inputs, n, k, 3,
-                              lambda addr: (addr(start), addr(lo), addr(hi)))
+        return _fleet_forward(capi.trajectory_fleet_separation_staggered, d, m, inputs, n, k, 3, start, lo, hi)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -2029,48 +1991,30 @@ class _TrajectoryContact(torch.autograd.Function):
     def forward(d, *inputs):
         a, b = [_dense(t) for t in inputs[:8 * d]], [_dense(t) for t in inputs[8 * d:16 * d]]
         level, lo, hi, delay = (_dense(t) for t in inputs[16 * d:])
-        shape, device = level.shape, inputs[0].device
-        time, rate = (torch.empty(shape, dtype=torch.float64, device=device) for _ in range(2))
-        n, k = shape
-        with torch.cuda.device(device):      # as _trajectory_launch
-            addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-            capi.trajectory_contact(device.index, torch.cuda.current_stream(device).cuda_stream, n, k, d, [addr(t) for t in a],
-                                    [addr(t) for t in b], addr(level), addr(lo), addr(hi), addr(delay), addr(time), addr(rate))
+        (n, k), device = level.shape, inputs[0].device
+        time, rate = _empty((n, k), device), _empty((n, k), device)
+        _enqueue(capi.trajectory_contact, device, n, k, d, a, b, level, lo, hi, delay, time, rate)
         return time, rate
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(output[1])
         d = ctx.d = inputs[0]
-        rest = inputs[1:]
-        ctx.given = [t is not None for t in rest[:16 * d]] + [False, False, False, rest[16 * d + 3] is not None]      # neither derivative
-        kept = [t for t, given in zip(rest, ctx.given) if given] + list(output)                                       # reads the level, lo or hi
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        rest = inputs[1:]      # neither derivative reads the level, lo or hi
+        _keep(ctx, rest, output, dead=output[1:], given=[t is not None for t in rest[:16 * d]] + [False, False, False, rest[16 * d + 3] is not None])
 
     @staticmethod
     def _saved(ctx):
         """(A's and B's d lists of eight tensors; A's times, 0 where there is no contact, and B's, those minus the delay; rate; where there
         is no contact; the d gaps D_c at those times)"""
         d = ctx.d
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        time, rate = next(kept), next(kept)
-        a = [[_dense(t) for t in inputs[8 * c:8 * c + 8]] for c in range(d)]
-        b = [[_dense(t) for t in inputs[8 * (d + c):8 * (d + c) + 8]] for c in range(d)]
+        inputs, (time, rate) = _kept(ctx)
+        a, b = _axis_tables(inputs, d)
         delay = inputs[16 * d + 3]
         missing = torch.isnan(time)
         zero = torch.zeros_like(time)
         t_a = torch.where(missing, zero, time).contiguous()
         t_b = torch.where(missing, zero, time - delay if delay is not None else time).contiguous()
-        gaps = []
-        for sa, sb in zip(a, b):
-            pa, pb = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
-            _trajectory_launch(capi.trajectory_eval, t_a.device, sa, t_a, pa, None, None)
-            _trajectory_launch(capi.trajectory_eval, t_a.device, sb, t_b, pb, None, None)
-            gaps.append(pa - pb)
-        return a, b, t_a, t_b, rate, missing, gaps
+        return a, b, t_a, t_b, rate, missing, _pair_gaps(a, b, t_a, t_b)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -2081,19 +2025,19 @@ class _TrajectoryContact(torch.autograd.Function):
         a, b, t_a, t_b, rate, missing, gaps = _TrajectoryContact._saved(ctx)
         need = ctx.needs_input_grad[1:]
         w = torch.where(missing, torch.zeros_like(t_a), g_time / rate)      # an unreached level: gradient 0
-        n = t_a.shape[0]
+        n, k = t_a.shape
         bars, delay_bar = [None] * (16 * d), None
         for c in range(d):
             g_pos = ((2.0 * w) * gaps[c]).contiguous()
-            bar = [torch.empty(n, dtype=torch.float64, device=t_a.device) if need[8 * c + f] else None for f in range(8)]
+            bar = _bars(need[8 * c:8 * c + 8], n, t_a.device)
             if any(x is not None for x in bar):
-                _trajectory_launch(capi.trajectory_eval_vjp, t_a.device, a[c], t_a, -g_pos, None, None, bar, None)
+                _enqueue(capi.trajectory_eval_vjp, t_a.device, n, k, a[c], t_a, -g_pos, None, None, bar, None)
             bars[8 * c:8 * c + 8] = bar
             first = 8 * (d + c)
-            bar = [torch.empty(n, dtype=torch.float64, device=t_a.device) if need[first + f] else None for f in range(8)]
-            tau_bar = torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) if need[16 * d + 3] else None
+            bar = _bars(need[first:first + 8], n, t_a.device)
+            tau_bar = _empty(t_a.shape, t_a.device) if need[16 * d + 3] else None
             if tau_bar is not None or any(x is not None for x in bar):      # B is at time - delay
-                _trajectory_launch(capi.trajectory_eval_vjp, t_a.device, b[c], t_b, g_pos, None, None, bar, tau_bar)
+                _enqueue(capi.trajectory_eval_vjp, t_a.device, n, k, b[c], t_b, g_pos, None, None, bar, tau_bar)
             bars[first:first + 8] = bar
             if tau_bar is not None:
                 delay_bar = -tau_bar if delay_bar is None else delay_bar - tau_bar
@@ -2108,9 +2052,9 @@ class _TrajectoryContact(torch.autograd.Function):
         tau_dot_b = (-delay_dot).contiguous() if delay_dot is not None else None
         total = level_dot if level_dot is not None else torch.zeros_like(t_a)
         for c in range(d):
-            pos_a, pos_b = (torch.empty(t_a.shape, dtype=torch.float64, device=t_a.device) for _ in range(2))
-            _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, a[c], t_a, dots[8 * c:8 * c + 8], None, pos_a, None, None)
-            _trajectory_launch(capi.trajectory_eval_jvp, t_a.device, b[c], t_b, dots[8 * (d + c):8 * (d + c) + 8], tau_dot_b, pos_b, None, None)
+            pos_a, pos_b = _empty(t_a.shape, t_a.device), _empty(t_a.shape, t_a.device)
+            _enqueue(capi.trajectory_eval_jvp, t_a.device, *t_a.shape, a[c], t_a, dots[8 * c:8 * c + 8], None, pos_a, None, None)
+            _enqueue(capi.trajectory_eval_jvp, t_a.device, *t_a.shape, b[c], t_b, dots[8 * (d + c):8 * (d + c) + 8], tau_dot_b, pos_b, None, None)
             total = total - (2.0 * gaps[c]) * (pos_a - pos_b)
         return torch.where(missing, torch.full_like(t_a, float("nan")), total / rate), None
 
@@ -2210,8 +2154,7 @@ class _TrajectoryFleetContact(torch.autograd.Function):
     def forward(d, m, *inputs):
         level, lo, hi = (_dense(t) for t in inputs[8 * d:])
         level, per_pair = _fleet_level(level)
-        return _fleet_forward(capi.trajectory_fleet_contact, d, m, inputs, level.shape[0], level.shape[-1], 2,
-                              lambda addr: (addr(level), int(per_pair), addr(lo), addr(hi)))
+        return _fleet_forward(capi.trajectory_fleet_contact, d, m, inputs, level.shape[0], level.shape[-1], 2, level, int(per_pair), lo, hi)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -2267,14 +2210,8 @@ def _culled_forward(entry, d, m, inputs):
     *start, level, lo, hi = (_dense(t) for t in inputs[8 * d:])
     level, per_pair = _fleet_level(level)
     n, k = level.shape[0], level.shape[-1]
-    with torch.cuda.device(inputs[0].device):
-        work, size = _cull_workspace(n, m, k, d, inputs[0].device, bool(start))
-
-    def culled(*args):
-        entry(*args, _plain(work).data_ptr(), size)
-
-    return _fleet_forward(culled, d, m, inputs, n, k, 2 + len(start),
-                          lambda addr: (*map(addr, start), addr(level), int(per_pair), addr(lo), addr(hi)))
+    work, size = _cull_workspace(n, m, k, d, inputs[0].device, bool(start))
+    return _fleet_forward(entry, d, m, inputs, n, k, 2 + len(start), *start, level, int(per_pair), lo, hi, tail=(work, size))
 
 
 class _TrajectoryFleetContactCulled(_TrajectoryFleetContact):
@@ -2298,8 +2235,8 @@ class _TrajectoryStaggeredContact(torch.autograd.Function):
     def forward(d, m, *inputs):
         start, level, lo, hi = (_dense(t) for t in inputs[8 * d:])
         level, per_pair = _fleet_level(level)
-        return _fleet_forward(capi.trajectory_fleet_contact_staggered, d, m, inputs, level.shape[0], level.shape[-1], 3,
-                              lambda addr: (addr(start), addr(level), int(per_pair), addr(lo), addr(hi)))
+        return _fleet_forward(capi.trajectory_fleet_contact_staggered, d, m, inputs, level.shape[0], level.shape[-1], 3, start, level,
+                              int(per_pair), lo, hi)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -2504,13 +2441,9 @@ def fleet_contact_candidates(fleet, radius=None, lo=None, hi=None, *, level_sq=N
         k = level.shape[-1]
         splines = [_dense(t.detach()) if t is not None else None for table in tables for t in table]
         kept = torch.empty((n, m * (m - 1) // 2), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            addr = lambda t: t.data_ptr() if t is not None else 0      # noqa: E731
-            work, size = _cull_workspace(n, m, k, d, device, start is not None)
-            head = (device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in splines])
-            tail = (addr(level), int(per_pair), addr(lo), addr(hi), work.data_ptr(), size, kept.data_ptr())
-            entry, with_start = _with_start(capi.trajectory_fleet_contact_candidates, capi.trajectory_fleet_contact_staggered_candidates, start)
-            entry(*head, *with_start, *tail)
+        work, size = _cull_workspace(n, m, k, d, device, start is not None)
+        entry, with_start = _with_start(capi.trajectory_fleet_contact_candidates, capi.trajectory_fleet_contact_staggered_candidates, start)
+        _enqueue(entry, device, n, m, k, d, splines, *with_start, level, int(per_pair), lo, hi, work, size, kept)
     return kept != 0
 
 
@@ -2535,12 +2468,8 @@ def trajectory_fleet_reach(fleet, lo=None, hi=None, *, start=None):
         size = n * m * k
         flat = torch.empty((2, d, size + (size & 1)), dtype=torch.float64, device=device)      # every array starts on a 16-byte boundary
         box = flat[:, :, :size].unflatten(2, (n, m, k))      # a view: axis c's (n, m, k) array is contiguous
-        with torch.cuda.device(device):
-            addr = lambda t: t.data_ptr() if t is not None else 0      # noqa: E731
-            tail = (addr(lo), addr(hi), [box[0, c].data_ptr() for c in range(d)], [box[1, c].data_ptr() for c in range(d)])
-            head = (device.index, torch.cuda.current_stream(device).cuda_stream, n, m, k, d, [addr(t) for t in splines])
-            entry, with_start = _with_start(capi.trajectory_fleet_reach, capi.trajectory_fleet_reach_staggered, start)
-            entry(*head, *with_start, *tail)
+        entry, with_start = _with_start(capi.trajectory_fleet_reach, capi.trajectory_fleet_reach_staggered, start)
+        _enqueue(entry, device, n, m, k, d, splines, *with_start, lo, hi, [box[0, c] for c in range(d)], [box[1, c] for c in range(d)])
     return box[0].permute(1, 2, 3, 0), box[1].permute(1, 2, 3, 0)
 
 
@@ -2573,36 +2502,22 @@ class _TrajectoryIntegrals(torch.autograd.Function):
     inputs (the table's order) and in lo and hi, each mode one launch of its own entry."""
 
     @staticmethod
-    def _launch(entry, pos0, spline, lo, hi, shape, *rest):
-        """One rp_trajectory_integrals* launch on the current stream; rest: tensors, None or lists of them (tables)."""
-        addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-        n, k = shape
-        with torch.cuda.device(pos0.device):      # as _trajectory_launch
-            entry(pos0.device.index, torch.cuda.current_stream(pos0.device).cuda_stream, n, k, [addr(t) for t in spline], addr(lo), addr(hi),
-                  *[[addr(t) for t in a] if isinstance(a, (list, tuple)) else addr(a) for a in rest])
-
-    @staticmethod
     def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, lo, hi):
         spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
         lo, hi = _dense(lo), _dense(hi)
-        shape = lo.shape if lo is not None else hi.shape if hi is not None else (pos0.shape[0], 1)
-        outs = [torch.empty(shape, dtype=torch.float64, device=pos0.device) for _ in range(4)]
-        _TrajectoryIntegrals._launch(capi.trajectory_integrals, pos0, spline, lo, hi, shape, outs)
+        n, k = _query_shape(pos0.shape[0], lo, hi)
+        outs = [_empty((n, k), pos0.device) for _ in range(4)]
+        _enqueue(capi.trajectory_integrals, pos0.device, n, k, spline, lo, hi, outs)
         return tuple(outs)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None and goes to the kernel as NULL: not read
-        ctx.given = [t is not None for t in inputs]
         ctx.shape = tuple(output[0].shape)
-        kept = [t for t in inputs if t is not None]
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _keep(ctx, inputs)
 
     @staticmethod
     def _inputs(ctx):
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
+        inputs, _ = _kept(ctx)
         return [_dense(t) for t in inputs[:8]], _dense(inputs[8]), _dense(inputs[9])
 
     @staticmethod
@@ -2611,19 +2526,25 @@ class _TrajectoryIntegrals(torch.autograd.Function):
         if all(x is None for x in g):
             return (None,) * 10
         spline, lo, hi = _TrajectoryIntegrals._inputs(ctx)
-        need, (n, k), dev = ctx.needs_input_grad, ctx.shape, spline[0].device
-        bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(8)]
-        lo_bar, hi_bar = (torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (8, 9))
-        _TrajectoryIntegrals._launch(capi.trajectory_integrals_vjp, spline[0], spline, lo, hi, (n, k), [_dense(x) for x in g], bars, lo_bar, hi_bar)
-        return tuple(bars) + (lo_bar, hi_bar)
+        return _integrals_vjp(spline, lo, hi, ctx.shape, g, ctx.needs_input_grad)
 
     @staticmethod
     def jvp(ctx, *tangents):
         spline, lo, hi = _TrajectoryIntegrals._inputs(ctx)
         dots = [_dense(t) for t in tangents]
-        outs = [torch.empty(ctx.shape, dtype=torch.float64, device=spline[0].device) for _ in range(4)]
-        _TrajectoryIntegrals._launch(capi.trajectory_integrals_jvp, spline[0], spline, lo, hi, ctx.shape, dots[:8], dots[8], dots[9], outs)
+        outs = [_empty(ctx.shape, spline[0].device) for _ in range(4)]
+        _enqueue(capi.trajectory_integrals_jvp, spline[0].device, *ctx.shape, spline, lo, hi, dots[:8], dots[8], dots[9], outs)
         return tuple(outs)
+
+
+def _integrals_vjp(spline, lo, hi, shape, g, need):
+    """The one rp_trajectory_integrals_vjp launch of _TrajectoryIntegrals.backward and _IntegralsVJP.forward: the eight bars, lo_bar and
+    hi_bar that `need` names, None for the others."""
+    (n, k), dev = shape, spline[0].device
+    bars = _bars(need[:8], n, dev)
+    lo_bar, hi_bar = _bars(need[8:10], (n, k), dev)
+    _enqueue(capi.trajectory_integrals_vjp, dev, n, k, spline, lo, hi, [_dense(x) for x in g], bars, lo_bar, hi_bar)
+    return tuple(bars) + (lo_bar, hi_bar)
 
 
 class _TrajectoryIntegrals2(_TrajectoryIntegrals):
@@ -2632,11 +2553,7 @@ class _TrajectoryIntegrals2(_TrajectoryIntegrals):
 
     @staticmethod
     def backward(ctx, *g):
-        if all(x is None for x in g):
-            return (None,) * 10
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        return _IntegralsVJP.apply(*inputs, *g, tuple(ctx.needs_input_grad[:10]), ctx.shape)
+        return _backward2(ctx, _IntegralsVJP, g, ctx.shape)
 
 
 class _IntegralsVJP(torch.autograd.Function):
@@ -2650,19 +2567,12 @@ class _IntegralsVJP(torch.autograd.Function):
     @staticmethod
     def forward(pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1, lo, hi, g0, g1, g2, g3, need, shape):
         spline = [_dense(t) for t in (pos0, pos1, pos2, vel0, vel2, vel1, duration0, duration1)]
-        (n, k), dev = shape, pos0.device
-        bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(8)]
-        lo_bar, hi_bar = (torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (8, 9))
-        _TrajectoryIntegrals._launch(capi.trajectory_integrals_vjp, spline[0], spline, _dense(lo), _dense(hi), (n, k),
-                                     [_dense(x) for x in (g0, g1, g2, g3)], bars, lo_bar, hi_bar)
-        return tuple(bars) + (lo_bar, hi_bar)
+        return _integrals_vjp(spline, _dense(lo), _dense(hi), shape, (g0, g1, g2, g3), need)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)      # a bar nothing downstream uses arrives as None and goes to the kernels as NULL: not read
-        ctx.given = [t is not None for t in inputs[:14]]
         ctx.shape = tuple(inputs[15])
-        ctx.save_for_backward(*[t for t in inputs[:14] if t is not None])
+        _keep(ctx, inputs[:14], forward=False)      # (a bar nothing downstream uses arrives as None too)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -2670,20 +2580,18 @@ class _IntegralsVJP(torch.autograd.Function):
         out = [None] * 16
         if all(x is None for x in u):
             return tuple(out)
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
+        inputs, _ = _kept(ctx)
         spline, lo, hi, g = [_dense(t) for t in inputs[:8]], _dense(inputs[8]), _dense(inputs[9]), [_dense(t) for t in inputs[10:14]]
         need, (n, k), dev = ctx.needs_input_grad, ctx.shape, spline[0].device
         dots, lo_dot, hi_dot = [_dense(x) for x in u[:8]], _dense(u[8]), _dense(u[9])
         if any(need[10:14]):
-            outs = [torch.empty((n, k), dtype=torch.float64, device=dev) if need[10 + c] else None for c in range(4)]
-            _TrajectoryIntegrals._launch(capi.trajectory_integrals_jvp, spline[0], spline, lo, hi, (n, k), dots, lo_dot, hi_dot, outs)
+            outs = _bars(need[10:14], (n, k), dev)
+            _enqueue(capi.trajectory_integrals_jvp, dev, n, k, spline, lo, hi, dots, lo_dot, hi_dot, outs)
             out[10:14] = outs
         if any(need[:10]) and any(x is not None for x in g):
-            bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(8)]
-            lo_bar, hi_bar = (torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (8, 9))
-            _TrajectoryIntegrals._launch(capi.trajectory_integrals_hvp, spline[0], spline, lo, hi, (n, k), g, dots, lo_dot, hi_dot, bars, lo_bar,
-                                         hi_bar)
+            bars = _bars(need[:8], n, dev)
+            lo_bar, hi_bar = _bars(need[8:10], (n, k), dev)
+            _enqueue(capi.trajectory_integrals_hvp, dev, n, k, spline, lo, hi, g, dots, lo_dot, hi_dot, bars, lo_bar, hi_bar)
             out[:10] = bars + [lo_bar, hi_bar]
         return tuple(out)
 
@@ -2740,38 +2648,22 @@ class _TrajectoryTracking(torch.autograd.Function):
     entry."""
 
     @staticmethod
-    def _launch(entry, a, b, lo, hi, delay, shape, *rest):
-        """One rp_trajectory_tracking* call on the current stream; rest: tensors, None or lists of them (tables)."""
-        addr = lambda t: _plain(t).data_ptr() if t is not None else 0      # noqa: E731
-        n, k = shape
-        device = a[0].device
-        with torch.cuda.device(device):      # as _trajectory_launch
-            entry(device.index, torch.cuda.current_stream(device).cuda_stream, n, k, [addr(t) for t in a], [addr(t) for t in b], addr(lo), addr(hi),
-                  addr(delay), *[[addr(t) for t in x] if isinstance(x, (list, tuple)) else addr(x) for x in rest])
-
-    @staticmethod
     def forward(*inputs):
         a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
         lo, hi, delay = (_dense(t) for t in inputs[16:19])
-        given = lo if lo is not None else hi if hi is not None else delay
-        shape = tuple(given.shape) if given is not None else (inputs[0].shape[0], 1)
-        outs = [torch.empty(shape, dtype=torch.float64, device=inputs[0].device) for _ in range(3)]
-        _TrajectoryTracking._launch(capi.trajectory_tracking, a, b, lo, hi, delay, shape, outs)
+        n, k = _query_shape(inputs[0].shape[0], lo, hi, delay)
+        outs = [_empty((n, k), inputs[0].device) for _ in range(3)]
+        _enqueue(capi.trajectory_tracking, inputs[0].device, n, k, a, b, lo, hi, delay, outs)
         return tuple(outs)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None and goes to the kernel as NULL: not read
-        ctx.given = [t is not None for t in inputs]
         ctx.shape = tuple(output[0].shape)
-        kept = [t for t in inputs if t is not None]
-        ctx.save_for_backward(*kept)
-        ctx.save_for_forward(*kept)
+        _keep(ctx, inputs)
 
     @staticmethod
     def _inputs(ctx):
-        kept = iter(ctx.saved_tensors)
-        inputs = [_dense(next(kept)) if given else None for given in ctx.given]
+        inputs = [_dense(t) for t in _kept(ctx)[0]]
         return inputs[:8], inputs[8:16], inputs[16], inputs[17], inputs[18]
 
     @staticmethod
@@ -2779,23 +2671,27 @@ class _TrajectoryTracking(torch.autograd.Function):
     def backward(ctx, *g):
         if all(x is None for x in g):
             return (None,) * 19
-        a, b, lo, hi, delay = _TrajectoryTracking._inputs(ctx)
-        need, (n, k), dev = ctx.needs_input_grad, ctx.shape, a[0].device
-        bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(16)]
-        lo_bar, hi_bar, delay_bar = (torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (16, 17, 18))
-        if any(need[:19]):
-            _TrajectoryTracking._launch(capi.trajectory_tracking_vjp, a, b, lo, hi, delay, (n, k), [_dense(x) for x in g], bars[:8], bars[8:],
-                                        lo_bar, hi_bar, delay_bar)
-        return tuple(bars) + (lo_bar, hi_bar, delay_bar)
+        return _tracking_vjp(*_TrajectoryTracking._inputs(ctx), ctx.shape, g, ctx.needs_input_grad)
 
     @staticmethod
     def jvp(ctx, *tangents):
         a, b, lo, hi, delay = _TrajectoryTracking._inputs(ctx)
         dots = [_dense(t) for t in tangents]
-        outs = [torch.empty(ctx.shape, dtype=torch.float64, device=a[0].device) for _ in range(3)]
-        _TrajectoryTracking._launch(capi.trajectory_tracking_jvp, a, b, lo, hi, delay, ctx.shape, dots[:8], dots[8:16], dots[16], dots[17],
-                                    dots[18], outs)
+        outs = [_empty(ctx.shape, a[0].device) for _ in range(3)]
+        _enqueue(capi.trajectory_tracking_jvp, a[0].device, *ctx.shape, a, b, lo, hi, delay, dots[:8], dots[8:16], dots[16], dots[17], dots[18],
+                 outs)
         return tuple(outs)
+
+
+def _tracking_vjp(a, b, lo, hi, delay, shape, g, need):
+    """The one rp_trajectory_tracking_vjp call of _TrajectoryTracking.backward and _TrackingVJP.forward: the sixteen bars, lo_bar, hi_bar
+    and delay_bar that `need` names, None for the others."""
+    (n, k), dev = shape, a[0].device
+    bars = _bars(need[:16], n, dev)
+    per_query = _bars(need[16:19], (n, k), dev)
+    if any(need[:19]):
+        _enqueue(capi.trajectory_tracking_vjp, dev, n, k, a, b, lo, hi, delay, [_dense(x) for x in g], bars[:8], bars[8:], *per_query)
+    return tuple(bars) + tuple(per_query)
 
 
 class _TrajectoryTracking2(_TrajectoryTracking):
@@ -2804,11 +2700,7 @@ class _TrajectoryTracking2(_TrajectoryTracking):
 
     @staticmethod
     def backward(ctx, *g):
-        if all(x is None for x in g):
-            return (None,) * 19
-        kept = iter(ctx.saved_tensors)
-        inputs = [next(kept) if given else None for given in ctx.given]
-        return _TrackingVJP.apply(*inputs, *g, tuple(ctx.needs_input_grad[:19]), ctx.shape)
+        return _backward2(ctx, _TrackingVJP, g, ctx.shape)
 
 
 class _TrackingVJP(torch.autograd.Function):
@@ -2825,20 +2717,12 @@ class _TrackingVJP(torch.autograd.Function):
         need, shape = inputs[22], inputs[23]
         a, b = [_dense(t) for t in inputs[:8]], [_dense(t) for t in inputs[8:16]]
         lo, hi, delay = (_dense(t) for t in inputs[16:19])
-        (n, k), dev = shape, inputs[0].device
-        bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(16)]
-        lo_bar, hi_bar, delay_bar = (torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (16, 17, 18))
-        if any(need[:19]):
-            _TrajectoryTracking._launch(capi.trajectory_tracking_vjp, a, b, lo, hi, delay, (n, k), [_dense(x) for x in inputs[19:22]], bars[:8],
-                                        bars[8:], lo_bar, hi_bar, delay_bar)
-        return tuple(bars) + (lo_bar, hi_bar, delay_bar)
+        return _tracking_vjp(a, b, lo, hi, delay, shape, inputs[19:22], need)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        ctx.set_materialize_grads(False)      # a bar nothing downstream uses arrives as None and goes to the kernels as NULL: not read
-        ctx.given = [t is not None for t in inputs[:22]]
         ctx.shape = tuple(inputs[23])
-        ctx.save_for_backward(*[t for t in inputs[:22] if t is not None])
+        _keep(ctx, inputs[:22], forward=False)      # (a bar nothing downstream uses arrives as None too)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -2846,21 +2730,19 @@ class _TrackingVJP(torch.autograd.Function):
         out = [None] * 24
         if all(x is None for x in u):
             return tuple(out)
-        kept = iter(ctx.saved_tensors)
-        inputs = [_dense(next(kept)) if given else None for given in ctx.given]
+        inputs = [_dense(t) for t in _kept(ctx)[0]]
         a, b, (lo, hi, delay), g = inputs[:8], inputs[8:16], inputs[16:19], inputs[19:22]
         need, (n, k), dev = ctx.needs_input_grad, ctx.shape, a[0].device
         dots = [_dense(x) for x in u]
         if any(need[19:22]):
-            outs = [torch.empty((n, k), dtype=torch.float64, device=dev) if need[19 + c] else None for c in range(3)]
-            _TrajectoryTracking._launch(capi.trajectory_tracking_jvp, a, b, lo, hi, delay, (n, k), dots[:8], dots[8:16], dots[16], dots[17],
-                                        dots[18], outs)
+            outs = _bars(need[19:22], (n, k), dev)
+            _enqueue(capi.trajectory_tracking_jvp, dev, n, k, a, b, lo, hi, delay, dots[:8], dots[8:16], dots[16], dots[17], dots[18], outs)
             out[19:22] = outs
         if any(need[:19]) and any(x is not None for x in g):
-            bars = [torch.empty(n, dtype=torch.float64, device=dev) if need[f] else None for f in range(16)]
-            per_query = [torch.empty((n, k), dtype=torch.float64, device=dev) if need[f] else None for f in (16, 17, 18)]
-            _TrajectoryTracking._launch(capi.trajectory_tracking_hvp, a, b, lo, hi, delay, (n, k), g, dots[:8], dots[8:16], dots[16], dots[17],
-                                        dots[18], bars[:8], bars[8:], *per_query)
+            bars = _bars(need[:16], n, dev)
+            per_query = _bars(need[16:19], (n, k), dev)
+            _enqueue(capi.trajectory_tracking_hvp, dev, n, k, a, b, lo, hi, delay, g, dots[:8], dots[8:16], dots[16], dots[17], dots[18],
+                     bars[:8], bars[8:], *per_query)
             out[:19] = bars + per_query
         return tuple(out)
 
