@@ -85,7 +85,9 @@ typedef struct rp_batch rp_batch; /* opaque, owned by the caller between create 
  *      rp_trajectory_fleet_contact_candidates (the fleet's position boxes, and the fleet's first contacts with a broad phase that skips
  *      the pairs whose boxes prove them apart; new entries only, the revision stays); rp_trajectory_fleet_reach_staggered,
  *      rp_trajectory_fleet_contact_staggered_culled(_workspace) and rp_trajectory_fleet_contact_staggered_candidates (that broad phase
- *      with a start time per vehicle: a query is out when it is refused or box-far; new entries only, the revision stays) */
+ *      with a start time per vehicle: a query is out when it is refused or box-far; new entries only, the revision stays);
+ *      rp_trajectory_cross_separation and rp_trajectory_cross_contact (the two fleet queries for every vehicle of one fleet against every
+ *      vehicle of another; new entries only, the revision stays) */
 #define RP_ABI_VERSION 7
 
 typedef enum {
@@ -788,6 +790,37 @@ RP_API int rp_trajectory_fleet_separation(int device, void *stream, size_t n, si
 RP_API int rp_trajectory_fleet_contact(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,
                                        const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
                                        double *d_rate);
+
+/* ---- the vehicles of one fleet against the vehicles of another, in one launch (new entries only, the revision
+ * stays) ----
+ * n scenes; in each, m_a vehicles of fleet A and m_b of fleet B, 1 <= m_a, m_b <= 32768, all on one clock.  d_fleet_a and d_fleet_b: one
+ * table of 8 d pointers each, axis-major, in rp_trajectory_separation's order; A's arrays hold n m_a doubles, vehicle v of scene s at
+ * s m_a + v, B's n m_b, at s m_b + v.  pairs = m_a m_b, pair r = (i, j) = (r / m_b, r % m_b), vehicle i of A against vehicle j of B,
+ * row-major: an n x pairs x k output is n x m_a x m_b x k.  No pair of two vehicles of the same fleet is looked at.  d_lo, d_hi: n x k
+ * doubles, the windows of scene s for all its pairs (NULL: -inf, +inf), read as single values, no alignment rule.
+ * rp_trajectory_cross_separation: d_value and d_time, n x pairs x k, either may be NULL but not both.  rp_trajectory_cross_contact:
+ * d_level_sq, required, in rp_trajectory_fleet_contact's two layouts (level_per_pair == 0: n x k, single values, no alignment rule; 1:
+ * n x pairs x k, 16-byte aligned -- (r_i + r_j)^2 for vehicles and obstacles of different sizes); d_time, n x pairs x k, required;
+ * d_rate, the same shape, may be NULL.
+ * Output [s, (i, j), q] is, bit for bit, what rp_trajectory_separation returns in value and time (rp_trajectory_contact in time and rate)
+ * for A = vehicle i of scene s of fleet A, B = vehicle j of scene s of fleet B, the window [lo, hi][s, q], that query's level and
+ * d_delay == NULL.  That entry's NaN rule carries over: a vehicle of A under it makes exactly its row of m_b pairs NaN, a vehicle of B
+ * exactly its column of m_a pairs; so do its domain -- the common one, which ends with the shorter of the two total times: a vehicle that
+ * stands still (an obstacle) needs durations that cover the window -- its candidates and its earliest-among-equals.  No pair-expanded
+ * array is read or written.
+ * Derivatives need no entry of their own (section 34): the fleet entries' formulas, a vehicle of A summing over its row and a vehicle of B
+ * over its column, one rp_trajectory_eval and one rp_trajectory_eval_vjp or _jvp launch per axis and fleet.  There is no batch entry.
+ * Entries [3] and [4] of any axis of either table may be NULL (zeros); m_a or m_b of 0 or above 32768, d outside 1..3, a NULL table, both
+ * outputs NULL (separation), a NULL level or time (contact), a level_per_pair other than 0 or 1, a misaligned output, a misaligned
+ * per-pair level, n or k of 0, k >= 2^31, an n x pairs x k that does not fit give RP_ERR_INVALID before any device call.  Asynchronous
+ * on `stream`; never throws.  Pointwise: a query's bits depend on its two vehicles' 16 d numbers, its level and its scene's window ends
+ * only. */
+RP_API int rp_trajectory_cross_separation(int device, void *stream, size_t n, size_t m_a, size_t m_b, size_t k, int d,
+                                          const double *const *d_fleet_a, const double *const *d_fleet_b, const double *d_lo,
+                                          const double *d_hi, double *d_value, double *d_time);
+RP_API int rp_trajectory_cross_contact(int device, void *stream, size_t n, size_t m_a, size_t m_b, size_t k, int d,
+                                       const double *const *d_fleet_a, const double *const *d_fleet_b, const double *d_level_sq,
+                                       int level_per_pair, const double *d_lo, const double *d_hi, double *d_time, double *d_rate);
 
 /* ---- the two fleet queries with a start time per vehicle (new entries only, the revision stays) ----
  * d_start, required: n x m doubles, vehicle v of scene s at s m + v, read as single values, no alignment rule.  Vehicle v runs its spline

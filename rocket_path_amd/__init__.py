@@ -18,7 +18,8 @@ def __getattr__(name):
                 "trajectory_meeting", "min_time_meeting", "trajectory_separation", "synchronize_axes", "min_time_separation",
                 "trajectory_contact", "min_time_contact", "fleet_pairs", "trajectory_fleet_separation", "min_time_fleet_separation",
                 "trajectory_fleet_contact", "min_time_fleet_contact", "fleet_first_contact", "fleet_contact_candidates",
-                "trajectory_fleet_reach"):
+                "trajectory_fleet_reach", "cross_pairs", "static_fleet", "trajectory_cross_separation", "trajectory_cross_contact",
+                "min_time_cross_separation", "min_time_cross_contact"):
         from . import autograd
         return getattr(autograd, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -61,6 +61,11 @@ contact and the pair that makes it, in plain torch.
 start= on those four (section 28) gives every vehicle a start time of its own on the scene's clock: pair (i, j) is the pair call with the
 delay start_j - start_i over the window shifted by start_i, bit for bit, in one rp_trajectory_fleet_separation_staggered or
 rp_trajectory_fleet_contact_staggered launch, differentiable in start through the same slot table; start=None is the call without it.
+trajectory_cross_separation and trajectory_cross_contact (section 34) are the two pair calls for every vehicle of one fleet against every
+vehicle of another, m_a m_b pairs row-major (cross_pairs), in one rp_trajectory_cross_separation or rp_trajectory_cross_contact launch, bit
+for bit the pair call's; a vehicle of A owns a row of the output and a vehicle of B a column, so the derivatives are the fleet calls' with
+a reshape or permute and a sum where those have the slot table; static_fleet makes the splines of obstacles that stand still;
+min_time_cross_separation and min_time_cross_contact compose them with the solves.
 """
 import collections
 import ctypes
@@ -1483,6 +1488,7 @@ def min_time_separation(pos_a, pos_b, lo=None, hi=None, delay=None, *, vel_a=Non
 
 # ---- the closest approach of every pair of a fleet ----
 FLEET_MOST = 256      # vehicles per scene (csrc/fleet_index.h)
+CROSS_MOST = 32768    # vehicles per scene and fleet of the cross queries (csrc/fleet_index.h)
 
 
 def _check_fleet_size(m, who):
@@ -1535,9 +1541,10 @@ def _fleet_forward(entry, d, m, inputs, n, k, outputs, *middle, tail=()):
     """One launch of a fleet entry on the current stream: the fleet's 8 d tensors (inputs[:8 d]; axis-major, each axis in the table's
     order, each n m values with vehicle v of scene s at s m + v), `middle`, then `outputs` fresh (n, pairs, k) tensors, which it returns,
     then `tail`."""
-    fleet = [_dense(t) for t in inputs[:8 * d]]
-    out = tuple(_empty((n, m * (m - 1) // 2, k), inputs[0].device) for _ in range(outputs))
-    _enqueue(entry, inputs[0].device, n, m, k, d, fleet, *middle, *out, *tail)
+    sizes, pairs = (m, m[0] * m[1]) if isinstance(m, tuple) else ((m,), m * (m - 1) // 2)      # (m_a, m_b): a cross entry, two tables
+    fleets = [[_dense(t) for t in inputs[8 * d * v:8 * d * (v + 1)]] for v in range(len(sizes))]
+    out = tuple(_empty((n, pairs, k), inputs[0].device) for _ in range(outputs))
+    _enqueue(entry, inputs[0].device, n, *sizes, k, d, *fleets, *middle, *out, *tail)
     return out
 
 
@@ -1842,8 +1849,8 @@ def _check_fleet_arguments(n, m, device, start, queries, who):
     return checked
 
 
-def _check_fleet_problem(pos, vel, synchronize, who):
-    """pos and vel of a fleet pipeline, shapes and types; returns (n, m, d)."""
+def _check_fleet_problem(pos, vel, synchronize, who, size=_check_fleet_size):
+    """pos and vel of a fleet pipeline, shapes and types; returns (n, m, d).  size: the check of m."""
     if synchronize and vel is not None:
         raise ValueError(who + ": synchronize=True needs rest-to-rest vehicles; pass synchronize=False with end velocities")
     if not isinstance(pos, (list, tuple)) or len(pos) != 3:
@@ -1855,7 +1862,7 @@ def _check_fleet_problem(pos, vel, synchronize, who):
         if t.dim() != 3 or t.shape != pos[0].shape or not 1 <= t.shape[2] <= 3:
             raise ValueError("%s: every tensor must have one shape (n, m, d) with d in 1..3, got %s" % (who, tuple(t.shape)))
     n, m, d = pos[0].shape
-    _check_fleet_size(int(m), who)
+    size(int(m), who)
     return n, int(m), d
 
 
@@ -1875,28 +1882,29 @@ def _solve_fleet(pos, vel, synchronize, gap_tol, max_iter, params):
     return spline, tuple(t.reshape(n, m, d) for t in solution)
 
 
-def _check_fleet(fleet, who):
+def _check_fleet(fleet, who, name="fleet", size=_check_fleet_size):
     """A fleet as trajectory_fleet_separation takes it: six or eight float64 tensors (n, m, d): shapes and types (the devices come after
-    the windows' shapes: _check_fleet_devices).  Returns (n, m, d, the d splines as lists of eight (n m,) tensors in the table's order)."""
-    _check_spline_arg("fleet", fleet, who)
+    the windows' shapes: _check_fleet_devices).  Returns (n, m, d, the d splines as lists of eight (n m,) tensors in the table's order).
+    name: what the messages call it; size: the check of m."""
+    _check_spline_arg(name, fleet, who)
     pos0 = fleet[0]
-    _check_is_tensor("fleet: pos0", pos0, who)
+    _check_is_tensor(name + ": pos0", pos0, who)
     if pos0.dim() != 3:
-        raise ValueError("%s: fleet: pos0 must have shape (n, m, d), got %s" % (who, tuple(pos0.shape)))
+        raise ValueError("%s: %s: pos0 must have shape (n, m, d), got %s" % (who, name, tuple(pos0.shape)))
     n, m, d = pos0.shape
     if n == 0:
         raise ValueError(who + ": empty batch")
-    _check_fleet_size(int(m), who)
+    size(int(m), who)
     if not 1 <= d <= 3:
-        raise ValueError("%s: fleet has %d axes; one, two or three are supported" % (who, d))
+        raise ValueError("%s: %s has %d axes; one, two or three are supported" % (who, name, d))
     names = ("pos0", "pos1", "pos2", "vel1", "duration0", "duration1", "vel0", "vel2")
-    for name, t in zip(names, fleet):
-        if t is None and name in ("vel0", "vel2"):
+    for field, t in zip(names, fleet):
+        if t is None and field in ("vel0", "vel2"):
             continue
-        _check_is_tensor("fleet: " + name, t, who)
+        _check_is_tensor(name + ": " + field, t, who)
         if t.shape != pos0.shape:
-            raise ValueError("%s: fleet: %s has shape %s, pos0 %s" % (who, name, tuple(t.shape), tuple(pos0.shape)))
-        _check_is_float64("fleet: " + name, t, who)
+            raise ValueError("%s: %s: %s has shape %s, pos0 %s" % (who, name, field, tuple(t.shape), tuple(pos0.shape)))
+        _check_is_float64(name + ": " + field, t, who)
     vel0, vel2 = fleet[6:] if len(fleet) == 8 else (None, None)
     table = list(fleet[:3]) + [vel0, vel2] + list(fleet[3:6])
     return n, int(m), d, [[t[:, :, c].reshape(n * m) if t is not None else None for t in table] for c in range(d)]
@@ -2494,6 +2502,376 @@ def fleet_first_contact(t_contact):
     one_hot = index == pair.unsqueeze(1)
     t_first = torch.where(one_hot, t_contact, torch.zeros_like(t_contact)).sum(dim=1)
     return torch.where(any_finite, t_first, torch.full_like(t_first, float("nan"))), pair
+
+
+# ---- the vehicles of one fleet against the vehicles of another ----
+def _check_cross_size(m, who):
+    if isinstance(m, bool) or not isinstance(m, int):
+        raise TypeError("%s: m_a and m_b must be ints, got %s" % (who, type(m).__name__))
+    if not 1 <= m <= CROSS_MOST:
+        raise ValueError("%s: a fleet holds 1..%d vehicles per scene, got %d" % (who, CROSS_MOST, m))
+
+
+def cross_pairs(m_a, m_b, device=None):
+    """The pairs (i, j) of m_a vehicles of fleet A against m_b of fleet B (1..32768 each) in the order of trajectory_cross_separation's
+    outputs -- row-major, pair r = (r // m_b, r % m_b): a (2, m_a m_b) int64 tensor on `device`, row 0 the vehicle of A, row 1 that of B."""
+    _check_cross_size(m_a, "cross_pairs")
+    _check_cross_size(m_b, "cross_pairs")
+    r = torch.arange(m_a * m_b, dtype=torch.int64, device=device)
+    return torch.stack((r // m_b, r % m_b))
+
+
+def static_fleet(points, duration=1.0):
+    """The spline tensors of vehicles that stand still: points (n, m, d) -> the six tensors (pos0, pos1, pos2, vel1, duration0, duration1)
+    of a fleet, with pos0 = pos1 = pos2 = points, all velocities 0 and both durations duration / 2 (they must be positive, or the NaN
+    rule bites: duration must be finite and > 0).  Keep-out spheres as fleet B of trajectory_cross_contact.  The common domain of a
+    pair ends at the smaller of its two vehicles' total times: an obstacle's duration must cover the window, or the queries are clamped
+    to the obstacle's life.  Differentiable in points by composition."""
+    who = "static_fleet"
+    _check_is_tensor("points", points, who)
+    if points.dim() != 3:
+        raise ValueError("%s: points must have shape (n, m, d), got %s" % (who, tuple(points.shape)))
+    _check_is_float64("points", points, who)
+    duration = float(duration)
+    if not (0.0 < duration < float("inf")):
+        raise ValueError("%s: duration must be finite and positive, got %r" % (who, duration))
+    half = torch.full(points.shape, 0.5 * duration, dtype=torch.float64, device=points.device)
+    return [points, points, points, torch.zeros_like(half), half, half.clone()]
+
+
+# What the two cross Functions share.  A vehicle of A owns a row of the (n, m_a, m_b, k) outputs and a vehicle of B a column: a side is the
+# view of the pairs' arrays in which its vehicles' partners are contiguous, with the names _fleet_vjp and _route_end_bars read from
+# _fleet_times -- tau, signs (+1 for A, the pair's first vehicle; -1 for B), through -- so every sum over partners is a reshape or permute
+# and a sum.  back: a side's (n m, partners k) array as (n, pairs, k); spread: a value per vehicle, (n m,), as (n, pairs, 1).
+_CrossSide = collections.namedtuple("_CrossSide", "tau signs through back spread")
+
+
+def _cross_sides(m, t):
+    """The two sides at the pairs' times t, (n, pairs, k) and contiguous, of m = (m_a, m_b) vehicles"""
+    (m_a, m_b), (n, pairs, k) = m, t.shape
+    one = torch.ones((1, 1, 1, 1), dtype=torch.float64, device=t.device)
+    square = lambda x: x.reshape(n, m_a, m_b, -1)      # noqa: E731
+    across = lambda x: square(x).permute(0, 2, 1, 3)      # noqa: E731
+    side_a = _CrossSide(t.reshape(n * m_a, m_b * k).contiguous(), one, square, lambda x: x.reshape(n, pairs, k),
+                        lambda x: x.reshape(n, m_a, 1, 1).expand(n, m_a, m_b, 1).reshape(n, pairs, 1))
+    side_b = _CrossSide(across(t).reshape(n * m_b, m_a * k).contiguous(), -one, across,
+                        lambda x: x.reshape(n, m_b, m_a, k).permute(0, 2, 1, 3).reshape(n, pairs, k),
+                        lambda x: x.reshape(n, 1, m_b, 1).expand(n, m_a, m_b, 1).reshape(n, pairs, 1))
+    return side_a, side_b
+
+
+def _cross_setup(ctx, inputs, count, dead, outputs):
+    """_fleet_setup for d, m_a, m_b in front: ctx.m is (m_a, m_b)"""
+    ctx.d, ctx.m = inputs[0], (inputs[1], inputs[2])
+    _keep(ctx, inputs[3:3 + count], outputs, dead)
+
+
+def _cross_kept(ctx):
+    """What _cross_setup kept: (A's and B's d lists of eight tensors, the other inputs among the `count`, the outputs)"""
+    inputs, outputs = _kept(ctx)
+    fleet_a, fleet_b = _axis_tables(inputs, ctx.d)
+    return fleet_a, fleet_b, inputs[16 * ctx.d:], outputs
+
+
+def _cross_gaps(fleets, sides):
+    """The d gaps D_c at the pairs' times, (n, pairs, k) each: per axis one evaluator launch on A's n m_a splines and one on B's n m_b"""
+    gaps = []
+    for s_a, s_b in zip(*fleets):
+        pos = []
+        for s, side in zip((s_a, s_b), sides):
+            out = _empty(side.tau.shape, side.tau.device)
+            _enqueue(capi.trajectory_eval, side.tau.device, *side.tau.shape, s, side.tau, out, None, None)
+            pos.append(side.back(out))
+        gaps.append(pos[0] - pos[1])
+    return gaps
+
+
+def _cross_jvp(fleets, sides, gaps, dots, tau_dots):
+    """Axis by axis, the evaluator's forward launch on each fleet's splines at its side's times; yields the axis' share of the tangent of
+    the squared distance, 2 D_c (d pos_A,c - d pos_B,c), (n, pairs, k).  dots: A's 8 d tangents, then B's."""
+    d = len(fleets[0])
+    for c in range(d):
+        pos_dot = []
+        for v, side in enumerate(sides):
+            out = _empty(side.tau.shape, side.tau.device)
+            first = 8 * (v * d + c)
+            _enqueue(capi.trajectory_eval_jvp, side.tau.device, *side.tau.shape, fleets[v][c], side.tau, dots[first:first + 8], tau_dots[v], out,
+                     None, None)
+            pos_dot.append(side.back(out))
+        yield (2.0 * gaps[c]) * (pos_dot[0] - pos_dot[1])
+
+
+def _cross_vjp(fleets, sides, need, want_tau, g_gap):
+    """_fleet_vjp on both sides, axis by axis, A's launch before B's: yields (A's eight bars, B's, the pair's tau_bar shares (A's, B's) as
+    (n, pairs, k), None unless want_tau)"""
+    d = len(fleets[0])
+    both = zip(_fleet_vjp(fleets[0], sides[0], need[:8 * d], want_tau, g_gap), _fleet_vjp(fleets[1], sides[1], need[8 * d:16 * d], want_tau, g_gap))
+    for (bar_a, tau_a), (bar_b, tau_b) in both:
+        yield bar_a, bar_b, ((sides[0].back(tau_a), sides[1].back(tau_b)) if want_tau else None)
+
+
+class _TrajectoryCrossSeparation(torch.autograd.Function):
+    """(sep_sq, t_closest), (n, pairs, k) each, of every vehicle of fleet A against every vehicle of fleet B over the scenes' windows.  Inputs:
+    d, m_a, m_b, A's 8 d tensors, B's 8 d, lo, hi (n, k).  _TrajectoryFleetSeparation's derivatives with a row per vehicle of A and a column
+    per vehicle of B where it has the slot table.  The time is not differentiable."""
+
+    @staticmethod
+    def forward(d, m_a, m_b, *inputs):
+        lo, hi = (_dense(t) for t in inputs[16 * d:])
+        given = lo if lo is not None else hi
+        n = inputs[0].shape[0] // m_a
+        k = given.shape[1] if given is not None else 1
+        return _fleet_forward(capi.trajectory_cross_separation, d, (m_a, m_b), inputs, n, k, 2, lo, hi)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _cross_setup(ctx, inputs, 16 * inputs[0] + 2, output[1:], output)
+
+    @staticmethod
+    def _saved(ctx):
+        """(the two fleets' d lists of eight tensors; the two sides; where the value is NaN, (n, pairs, k); the d gaps D_c; the class masks
+        LO, HI, [END of A's axis c], [END of B's], exclusive and in that priority)"""
+        d = ctx.d
+        fleet_a, fleet_b, (lo, hi), (value, time) = _cross_kept(ctx)
+        missing = torch.isnan(value) | torch.isnan(time)
+        t = torch.where(missing, torch.zeros_like(time), time)
+        sides = _cross_sides(ctx.m, t)
+        tests = [lo.unsqueeze(1) if lo is not None else None, hi.unsqueeze(1) if hi is not None else None]
+        tests += [side.spread(s[6] + s[7]) for fleet, side in zip((fleet_a, fleet_b), sides) for s in fleet]
+        masks = _class_masks(t, missing, tests)
+        return (fleet_a, fleet_b), sides, missing, _cross_gaps((fleet_a, fleet_b), sides), (masks[0], masks[1], masks[2:2 + d], masks[2 + d:])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_value, _g_time):
+        d = ctx.d
+        if g_value is None:
+            return (None,) * (16 * d + 5)
+        fleets, sides, missing, gaps, (is_lo, is_hi, end_a, end_b) = _TrajectoryCrossSeparation._saved(ctx)
+        g = torch.where(missing, torch.zeros_like(g_value), g_value)      # a NaN value: gradient 0
+        need = ctx.needs_input_grad[3:]
+        want_time = any(need[8 * c + 6] or need[8 * c + 7] for c in range(2 * d)) or any(need[16 * d:])
+        # (a bad vehicle's gap is NaN: not into its partners)
+        g_gap = lambda c: torch.where(missing, torch.zeros_like(g), (2.0 * g) * gaps[c])      # noqa: E731
+        bars_a, bars_b, time_bar = [], [], None
+        for bar_a, bar_b, shares in _cross_vjp(fleets, sides, need, want_time, g_gap):
+            bars_a += bar_a
+            bars_b += bar_b
+            if want_time:      # the pair's: its two vehicles', added in _TrajectorySeparation's order
+                for share in shares:
+                    time_bar = share if time_bar is None else time_bar + share
+        lo_bar = hi_bar = None
+        if want_time:
+            routed = lambda mask: torch.where(mask, time_bar, torch.zeros_like(time_bar))      # noqa: E731
+            _route_end_bars(bars_a, need[:8 * d], sides[0], routed, end_a, end_b)
+            _route_end_bars(bars_b, need[8 * d:16 * d], sides[1], routed, end_a, end_b)
+            if need[16 * d]:
+                lo_bar = routed(is_lo).sum(dim=1)
+            if need[16 * d + 1]:
+                hi_bar = routed(is_hi).sum(dim=1)
+        return (None, None, None) + tuple(bars_a) + tuple(bars_b) + (lo_bar, hi_bar)
+
+    @staticmethod
+    def jvp(ctx, _t_d, _t_a, _t_b, *tangents):
+        d = ctx.d
+        fleets, sides, missing, gaps, (is_lo, is_hi, end_a, end_b) = _TrajectoryCrossSeparation._saved(ctx)
+        dots = [_dense(t) for t in tangents[:16 * d]]
+        zero = torch.zeros(missing.shape, dtype=torch.float64, device=missing.device)
+        wide = lambda t: t.unsqueeze(1) if t is not None else zero      # noqa: E731
+        time_dot = torch.where(is_lo, wide(tangents[16 * d]), zero)
+        time_dot = torch.where(is_hi, wide(tangents[16 * d + 1]), time_dot)
+        for v, ends in enumerate((end_a, end_b)):
+            for c in range(d):
+                total = None
+                for t in (dots[8 * (v * d + c) + 6], dots[8 * (v * d + c) + 7]):
+                    if t is not None:
+                        total = t if total is None else total + t
+                if total is not None:
+                    time_dot = torch.where(ends[c], sides[v].spread(total), time_dot)
+        tau_dots = [side.through(time_dot).reshape(side.tau.shape).contiguous() for side in sides]
+        value_dot = zero
+        for share in _cross_jvp(fleets, sides, gaps, dots, tau_dots):
+            value_dot = value_dot + share
+        return torch.where(missing, torch.full_like(zero, float("nan")), value_dot), None
+
+
+class _TrajectoryCrossContact(torch.autograd.Function):
+    """(time, rate), (n, pairs, k) each, of the first time in the scene's window at which the squared distance of a vehicle of A and one of B
+    is at the level.  Inputs: d, m_a, m_b, A's 8 d tensors, B's 8 d, level_sq -- (n, k) or (n, pairs, k) --, lo, hi (n, k).
+    _TrajectoryFleetContact's implicit-function formula with rows and columns for the slot table.  lo and hi only
+    choose the branch.  rate is for the backward and is not differentiable."""
+
+    @staticmethod
+    def forward(d, m_a, m_b, *inputs):
+        level, lo, hi = (_dense(t) for t in inputs[16 * d:])
+        level, per_pair = _fleet_level(level)
+        return _fleet_forward(capi.trajectory_cross_contact, d, (m_a, m_b), inputs, level.shape[0], level.shape[-1], 2, level, int(per_pair),
+                              lo, hi)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        d = inputs[0]
+        ctx.per_pair = inputs[3 + 16 * d].dim() == 3
+        _cross_setup(ctx, inputs, 16 * d, output[1:], output)      # neither derivative reads the level, lo or hi
+
+    @staticmethod
+    def _saved(ctx):
+        """(the two fleets' d lists of eight tensors; the two sides; rate; where there is no contact, (n, pairs, k); the d gaps D_c)"""
+        fleet_a, fleet_b, _, (time, rate) = _cross_kept(ctx)
+        missing = torch.isnan(time)
+        sides = _cross_sides(ctx.m, torch.where(missing, torch.zeros_like(time), time))
+        return (fleet_a, fleet_b), sides, rate, missing, _cross_gaps((fleet_a, fleet_b), sides)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_time, _g_rate):
+        d = ctx.d
+        if g_time is None:
+            return (None,) * (16 * d + 6)
+        fleets, sides, rate, missing, gaps = _TrajectoryCrossContact._saved(ctx)
+        need = ctx.needs_input_grad[3:]
+        zero = torch.zeros_like(rate)
+        w = torch.where(missing, zero, g_time / rate)      # an unreached level: gradient 0
+        # (a bad vehicle's gap is NaN: not into its partners)
+        g_gap = lambda c: torch.where(missing, zero, -((2.0 * w) * gaps[c]))      # noqa: E731
+        bars_a, bars_b = [], []
+        for bar_a, bar_b, _ in _cross_vjp(fleets, sides, need, False, g_gap):
+            bars_a += bar_a
+            bars_b += bar_b
+        level_bar = _level_bar(ctx, w) if need[16 * d] else None
+        return (None, None, None) + tuple(bars_a) + tuple(bars_b) + (level_bar, None, None)
+
+    @staticmethod
+    def jvp(ctx, _t_d, _t_a, _t_b, *tangents):
+        d = ctx.d
+        fleets, sides, rate, missing, gaps = _TrajectoryCrossContact._saved(ctx)
+        dots = [_dense(t) for t in tangents[:16 * d]]
+        total = _level_dot(ctx, tangents[16 * d], rate)
+        for share in _cross_jvp(fleets, sides, gaps, dots, (None, None)):
+            total = total - share
+        return torch.where(missing, torch.full_like(rate, float("nan")), total / rate), None
+
+
+def _check_cross(fleet_a, fleet_b, who):
+    """Two fleets as trajectory_cross_separation takes them, shapes and types: (n, m_a, m_b, d, A's d splines, B's)"""
+    n, m_a, d, tables_a = _check_fleet(fleet_a, who, "fleet_a", _check_cross_size)
+    n_b, m_b, d_b, tables_b = _check_fleet(fleet_b, who, "fleet_b", _check_cross_size)
+    if n_b != n or d_b != d:
+        raise ValueError("%s: fleet_a has %d scenes of %d axes, fleet_b %d of %d: the two fleets share their scenes and their axes"
+                         % (who, n, d, n_b, d_b))
+    return n, m_a, m_b, d, tables_a, tables_b
+
+
+def _check_cross_devices(fleet_a, fleet_b, who):
+    _check_fleet_devices(fleet_a, who)
+    _check_fleet_devices(fleet_b, who)
+    if fleet_b[0].device != fleet_a[0].device:
+        raise TypeError("%s: fleet_b is on %s; it must be on fleet_a's device %s" % (who, fleet_b[0].device, fleet_a[0].device))
+
+
+def _check_cross_queries(n, m_a, m_b, device, radius, level_sq, lo, hi, who):
+    """_check_fleet_queries for the m_a m_b pairs of two fleets; a four-dimensional level (n, m_a, m_b, k) is the per-pair one's view."""
+    given = radius if radius is not None else level_sq
+    if isinstance(given, torch.Tensor) and given.dim() == 4:
+        if tuple(given.shape[:3]) != (n, m_a, m_b) or given.shape[3] == 0:
+            raise ValueError("%s: a four-dimensional %s must have shape (%d, %d, %d, k) -- one per vehicle of A and of B -- with k >= 1, got %s"
+                             % (who, "radius" if radius is not None else "level_sq", n, m_a, m_b, tuple(given.shape)))
+        given = given.reshape(n, m_a * m_b, given.shape[3])
+        radius, level_sq = (given, None) if radius is not None else (None, given)
+    name, level = _check_fleet_level(n, m_a * m_b, radius, level_sq, who)
+    lo, hi = _check_fleet_windows(n, device, lo, hi, who)
+    for other, t in (("lo", lo), ("hi", hi)):
+        if t is not None and t.shape[1] != level.shape[-1]:
+            raise ValueError("%s: %s has %d queries per scene, %s %d" % (who, name, level.shape[-1], other, t.shape[1]))
+    if level.device != device:
+        raise TypeError("%s: %s is on %s; it must be on the fleets' device %s" % (who, name, level.device, device))
+    return level, lo, hi
+
+
+def trajectory_cross_separation(fleet_a, fleet_b, lo=None, hi=None):
+    """trajectory_separation for every vehicle of one fleet against every vehicle of another, in one launch: n scenes, in each m_a vehicles
+    of fleet A and m_b of fleet B (1..32768 each) that move in d = 1, 2 or 3 axes, all on one clock -- your vehicles against the other
+    team's, or against obstacles (static_fleet).  fleet_a, fleet_b: each a sequence of six tensors (pos0, pos1, pos2, vel1, duration0,
+    duration1), or of eight with (vel0, vel2) appended, (n, m_a, d) and (n, m_b, d), float64 on one ROCm device.  lo, hi: exactly
+    trajectory_fleet_separation's.  Returns (sep_sq, t_closest), (n, pairs, k) each, pairs = m_a m_b in cross_pairs(m_a, m_b)'s order,
+    row-major -- reshape to (n, m_a, m_b, k): [s, (i, j), q] is bit for bit what trajectory_separation gives for vehicle i of A and vehicle
+    j of B of scene s, the window [lo, hi][s, q] and no delay -- its NaN rule (a bad vehicle of A makes exactly its row NaN, one of B its
+    column), domain, candidates and earliest-among-equals.  No pair within a fleet is looked at.
+
+    One rp_trajectory_cross_separation launch on the current stream; no pair-expanded tensor is made.  sep_sq is differentiable to first
+    order in all tensors of both fleets, lo and hi, in both modes: per axis and fleet one rp_trajectory_eval launch and one
+    rp_trajectory_eval_vjp (reverse) or rp_trajectory_eval_jvp (forward) launch on the fleet's splines at the returned times (DESIGN.md
+    section 34); a vehicle's sum over its partners is a reshape or permute and a sum, so a gradient is the same bits in every run; a double
+    backward raises torch's once_differentiable error.  A NaN value has gradient 0 (forward mode: NaN).  The time is not differentiable.
+    Does not synchronise the host."""
+    who = "trajectory_cross_separation"
+    n, m_a, m_b, d, tables_a, tables_b = _check_cross(fleet_a, fleet_b, who)
+    lo, hi = _check_fleet_windows(n, fleet_a[0].device, lo, hi, who)
+    _check_cross_devices(fleet_a, fleet_b, who)
+    return _TrajectoryCrossSeparation.apply(d, m_a, m_b, *[t for table in tables_a + tables_b for t in table], lo, hi)
+
+
+def trajectory_cross_contact(fleet_a, fleet_b, radius=None, lo=None, hi=None, *, level_sq=None):
+    """trajectory_contact for every vehicle of one fleet against every vehicle of another, in one launch: the first time in a scene's
+    windows [lo, hi] at which vehicle i of A and vehicle j of B come within `radius` of each other.  fleet_a, fleet_b, lo, hi: exactly
+    trajectory_cross_separation's.  radius: (n, k), or (k,) for the same in every scene -- one radius for all pairs of a scene --, or
+    (n, pairs, k) or (n, m_a, m_b, k) -- one per pair; the four-dimensional form is a view of the three-dimensional one, so
+    (r_a[:, :, None, None] + r_b[:, None, :, None]).expand(n, m_a, m_b, k) is the call for vehicles and obstacles of different sizes.  The
+    level is radius * radius, formed in torch, so the radius gets its gradient by the chain rule.  level_sq= may be given instead of
+    radius (giving both, or neither, is a TypeError).  Returns t_contact, (n, pairs, k), pairs = m_a m_b in cross_pairs(m_a, m_b)'s order:
+    [s, (i, j), q] is bit for bit what trajectory_contact gives for those two vehicles, the window [lo, hi][s, q], that query's level and
+    no delay -- NaN where the pair does not reach the level in the window, and its NaN rule (rows and columns, as
+    trajectory_cross_separation).  fleet_first_contact takes these times as they are: its index is then into cross_pairs(m_a, m_b).
+
+    One rp_trajectory_cross_contact launch on the current stream.  Differentiable to first order in all tensors of both fleets and the
+    level, in both modes, by trajectory_fleet_contact's formula with trajectory_cross_separation's launches and sums (DESIGN.md section
+    34); lo and hi get no gradient; an unreached level has gradient 0 (forward mode: NaN).  Does not synchronise the host."""
+    who = "trajectory_cross_contact"
+    if (radius is None) == (level_sq is None):
+        raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
+    n, m_a, m_b, d, tables_a, tables_b = _check_cross(fleet_a, fleet_b, who)
+    level, lo, hi = _check_cross_queries(n, m_a, m_b, fleet_a[0].device, radius, level_sq, lo, hi, who)
+    _check_cross_devices(fleet_a, fleet_b, who)
+    return _TrajectoryCrossContact.apply(d, m_a, m_b, *[t for table in tables_a + tables_b for t in table], level, lo, hi)[0]
+
+
+def _check_cross_problem(pos_a, pos_b, vel_a, vel_b, synchronize, who):
+    """The two fleets of a cross pipeline, shapes and types: (n, m_a, m_b, d)"""
+    n, m_a, d = _check_fleet_problem(pos_a, vel_a, synchronize, who, _check_cross_size)
+    n_b, m_b, d_b = _check_fleet_problem(pos_b, vel_b, synchronize, who, _check_cross_size)
+    if n_b != n or d_b != d:
+        raise ValueError("%s: pos_a has %d scenes of %d axes, pos_b %d of %d: the two fleets share their scenes and their axes"
+                         % (who, n, d, n_b, d_b))
+    return n, m_a, m_b, d
+
+
+def min_time_cross_separation(pos_a, pos_b, lo=None, hi=None, *, vel_a=None, vel_b=None, synchronize=True, gap_tol=1e-8, max_iter=200,
+                              params=None):
+    """min_time_solve of both fleets' axes, then trajectory_cross_separation of the solutions: min_time_fleet_separation's composition
+    for two fleets.  pos_a, pos_b: (pos0, pos1, pos2), (n, m_a, d) and (n, m_b, d) each: the n (m_a + m_b) d axis problems are solved;
+    vel_a, vel_b: (vel0, vel2) (None: rest to rest); synchronize (the default): each vehicle's axes are stretched to its slowest first.
+    Returns (sep_sq, t_closest, solution_a, solution_b), the solutions as min_time_fleet_separation returns its.  Plain composition."""
+    who = "min_time_cross_separation"
+    n, m_a, m_b, d = _check_cross_problem(pos_a, pos_b, vel_a, vel_b, synchronize, who)
+    lo, hi = _check_fleet_windows(n, pos_a[0].device, lo, hi, who)      # before the solves: a bad query costs none
+    spline_a, solution_a = _solve_fleet(pos_a, vel_a, synchronize, gap_tol, max_iter, params)
+    spline_b, solution_b = _solve_fleet(pos_b, vel_b, synchronize, gap_tol, max_iter, params)
+    return tuple(trajectory_cross_separation(spline_a, spline_b, lo, hi)) + (solution_a, solution_b)
+
+
+def min_time_cross_contact(pos_a, pos_b, radius=None, lo=None, hi=None, *, level_sq=None, vel_a=None, vel_b=None, synchronize=True,
+                           gap_tol=1e-8, max_iter=200, params=None):
+    """min_time_solve of both fleets' axes, then trajectory_cross_contact of the solutions: min_time_cross_separation's composition with
+    trajectory_cross_contact's radius (or level_sq=), lo and hi.  Returns (t_contact, solution_a, solution_b)."""
+    who = "min_time_cross_contact"
+    if (radius is None) == (level_sq is None):
+        raise TypeError(who + ": give either radius or level_sq=, not %s" % ("both" if radius is not None else "neither"))
+    n, m_a, m_b, d = _check_cross_problem(pos_a, pos_b, vel_a, vel_b, synchronize, who)
+    # before the solves: a bad query costs none
+    level, lo, hi = _check_cross_queries(n, m_a, m_b, pos_a[0].device, radius, level_sq, lo, hi, who)
+    spline_a, solution_a = _solve_fleet(pos_a, vel_a, synchronize, gap_tol, max_iter, params)
+    spline_b, solution_b = _solve_fleet(pos_b, vel_b, synchronize, gap_tol, max_iter, params)
+    return trajectory_cross_contact(spline_a, spline_b, None, lo, hi, level_sq=level), solution_a, solution_b
 
 
 # ---- how much: integrals over a window ----

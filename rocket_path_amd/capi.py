@@ -124,6 +124,11 @@ SIGNATURES = {
                                                       ctypes.POINTER(_vp), _vp, _vp, _vp, _vp]),
     "rp_trajectory_fleet_contact": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
                                                    ctypes.POINTER(_vp), _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "rp_trajectory_cross_separation": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                                      ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _vp, _vp]),
+    "rp_trajectory_cross_contact": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                                   ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, ctypes.c_int, _vp, _vp, _vp,
+                                                   _vp]),
     "rp_trajectory_fleet_separation_staggered": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
                                                                 ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp]),
     "rp_trajectory_fleet_contact_staggered": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
@@ -388,6 +393,40 @@ def trajectory_fleet_contact(device, stream, n, m, k, d, fleet, d_level_sq, leve
     d, m = _fleet_sizes("trajectory_fleet_contact", d, m)
     check(load_library().rp_trajectory_fleet_contact(int(device), vp(stream), int(n), m, int(k), d, axes_table(fleet, d), vp(d_level_sq),
                                                      int(level_per_pair), vp(d_lo), vp(d_hi), vp(d_time), vp(d_rate)))
+
+
+def _cross_sizes(who, d, m_a, m_b):
+    """(d, m_a, m_b) as ints, refused here where the C entry would refuse them"""
+    d, m_a, m_b = int(d), int(m_a), int(m_b)
+    if not 1 <= d <= 3:
+        raise ValueError("%s: d must be 1, 2 or 3, got %d" % (who, d))
+    if not (1 <= m_a <= 32768 and 1 <= m_b <= 32768):
+        raise ValueError("%s: m_a and m_b must be 1..32768 vehicles per scene, got %d and %d" % (who, m_a, m_b))
+    return d, m_a, m_b
+
+
+def trajectory_cross_separation(device, stream, n, m_a, m_b, k, d, fleet_a, fleet_b, d_lo=None, d_hi=None, d_value=None, d_time=None):
+    """rp_trajectory_cross_separation: trajectory_separation's two outputs, bit for bit with no delay, for every vehicle i of fleet A
+    (`m_a` of them, 1..32768) against every vehicle j of fleet B (`m_b`) of `n` scenes of `d` axes (1..3) on one clock; pair (i, j) at
+    i m_b + j.  `fleet_a`, `fleet_b`: 8 d addresses each, axis-major, each axis as for trajectory_eval, every array n m_a (n m_b) values
+    with vehicle v of scene s at s m_a + v (s m_b + v).  d_lo, d_hi: (n, k), the scene's windows for all its pairs (None / 0: -inf, +inf).
+    d_value, d_time: (n, m_a m_b, k) (None / 0: not wanted; not both)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m_a, m_b = _cross_sizes("trajectory_cross_separation", d, m_a, m_b)
+    check(load_library().rp_trajectory_cross_separation(int(device), vp(stream), int(n), m_a, m_b, int(k), d, axes_table(fleet_a, d),
+                                                        axes_table(fleet_b, d), vp(d_lo), vp(d_hi), vp(d_value), vp(d_time)))
+
+
+def trajectory_cross_contact(device, stream, n, m_a, m_b, k, d, fleet_a, fleet_b, d_level_sq, level_per_pair=0, d_lo=None, d_hi=None,
+                             d_time=None, d_rate=None):
+    """rp_trajectory_cross_contact: trajectory_contact's two outputs, bit for bit with no delay, for the pairs, fleets and windows of
+    trajectory_cross_separation.  d_level_sq (required), squared distance: (n, k), one level for all pairs of a scene (level_per_pair 0),
+    or (n, m_a m_b, k), 16-byte aligned (level_per_pair 1).  d_time (required), d_rate (None / 0: not wanted): (n, m_a m_b, k)."""
+    vp = lambda a: ctypes.c_void_p(a) if a else None      # noqa: E731
+    d, m_a, m_b = _cross_sizes("trajectory_cross_contact", d, m_a, m_b)
+    check(load_library().rp_trajectory_cross_contact(int(device), vp(stream), int(n), m_a, m_b, int(k), d, axes_table(fleet_a, d),
+                                                     axes_table(fleet_b, d), vp(d_level_sq), int(level_per_pair), vp(d_lo), vp(d_hi),
+                                                     vp(d_time), vp(d_rate)))
 
 
 def trajectory_fleet_separation_staggered(device, stream, n, m, k, d, fleet, d_start, d_lo=None, d_hi=None, d_value=None, d_time=None,

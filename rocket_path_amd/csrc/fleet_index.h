@@ -28,4 +28,18 @@ RP_FLEET_INLINE void fleet_pair(unsigned r, unsigned m, unsigned &i, unsigned &j
     j = first + 1u + r;
 }
 
+// The pairs across two fleets of m_a and m_b vehicles: every vehicle i of A against every vehicle j of B, row-major --
+// pair r is (r / m_b, r % m_b), so n x pairs x k is n x m_a x m_b x k.  32,768 a side: 2^30 pairs, and a pair index plus a trip's 128 places
+// stays inside 32 bits.
+constexpr unsigned kCrossMost = 32768;
+
+RP_FLEET_INLINE unsigned cross_pair_count(unsigned m_a, unsigned m_b) { return m_a * m_b; }
+
+// pair r < cross_pair_count(m_a, m_b) of 1 <= m_a, m_b <= kCrossMost vehicles
+RP_FLEET_INLINE void cross_pair(unsigned r, unsigned m_b, unsigned &i, unsigned &j)
+{
+    i = r / m_b;
+    j = r - i * m_b;
+}
+
 }  // namespace rp

@@ -221,6 +221,14 @@ hipError_t launch_fleet_separation(size_t n, size_t m, size_t k, int d, const do
 // all pairs of a scene) or n x m (m - 1) / 2 x k (1); d_time required, d_rate may be null; both n x m (m - 1) / 2 x k
 hipError_t launch_fleet_contact(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_level_sq, int level_per_pair,
                                 const double *d_lo, const double *d_hi, double *d_time, double *d_rate, hipStream_t stream);
+// the same two queries for every vehicle of fleet A (m_a of them, 1..32768) against every vehicle of fleet B (m_b) of n scenes on one clock
+// (DESIGN.md section 34): d_fleet_a holds 8 d pointers to arrays of n m_a values, d_fleet_b to n m_b; the windows, the level's two layouts
+// and the optional outputs as in the two fleet launches; the outputs n x m_a m_b x k, pair (i, j) at i m_b + j
+hipError_t launch_cross_separation(size_t n, size_t m_a, size_t m_b, size_t k, int d, const double *const *d_fleet_a, const double *const *d_fleet_b,
+                                   const double *d_lo, const double *d_hi, double *d_value, double *d_time, hipStream_t stream);
+hipError_t launch_cross_contact(size_t n, size_t m_a, size_t m_b, size_t k, int d, const double *const *d_fleet_a, const double *const *d_fleet_b,
+                                const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
+                                double *d_rate, hipStream_t stream);
 // the two fleet queries with a start time per vehicle, d_start n x m (required) on the scene's clock, on which d_lo, d_hi and d_time are;
 // d_time_local is the same time on the clock of the pair's first vehicle (any output may be null, not all)
 hipError_t launch_fleet_separation_staggered(size_t n, size_t m, size_t k, int d, const double *const *d_fleet, const double *d_start,

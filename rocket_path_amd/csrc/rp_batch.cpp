@@ -1574,6 +1574,57 @@ int rp_trajectory_fleet_contact(int device, void *stream, size_t n, size_t m, si
     return RP_OK;
 }
 
+// What the two cross entries check, in check_fleet's order: the device, m_a and m_b, d, level_per_pair (null: the entry has none), the two
+// tables of 8 d pointers, the entry's own required arrays, that n x pairs fits, and check_queries of the n x pairs x k arrays.
+static int check_cross(const char *who, int device, size_t n, size_t m_a, size_t m_b, size_t k, int d, const int *level_per_pair,
+                       const double *const *d_fleet_a, const double *const *d_fleet_b, std::initializer_list<Required> required,
+                       std::initializer_list<const void *> per_query, bool any_output)
+{
+    if (device < 0) return fail(RP_ERR_INVALID, "%s: device %d", who, device);
+    if (m_a < 1 || m_a > 32768 || m_b < 1 || m_b > 32768)
+        return fail(RP_ERR_INVALID, "%s: m_a and m_b must be 1..32768 vehicles per scene, got %zu and %zu", who, m_a, m_b);
+    if (d < 1 || d > 3) return fail(RP_ERR_INVALID, "%s: d must be 1, 2 or 3, got %d", who, d);
+    if (level_per_pair && *level_per_pair != 0 && *level_per_pair != 1)
+        return fail(RP_ERR_INVALID, "%s: level_per_pair must be 0 (n x k) or 1 (n x pairs x k), got %d", who, *level_per_pair);
+    if (!d_fleet_a) return fail(RP_ERR_INVALID, "%s: d_fleet_a is null", who);
+    if (!d_fleet_b) return fail(RP_ERR_INVALID, "%s: d_fleet_b is null", who);
+    for (int x = 0; x < d; ++x) {
+        int st = check_spline(who, "d_fleet_a", d_fleet_a + 8 * x);
+        if (st == RP_OK) st = check_spline(who, "d_fleet_b", d_fleet_b + 8 * x);
+        if (st != RP_OK) return st;
+    }
+    for (const Required &r : required)
+        if (!r.given) return fail(RP_ERR_INVALID, "%s: %s is null", who, r.name);
+    const size_t pairs = m_a * m_b;
+    if (n > SIZE_MAX / sizeof(double) / pairs) return fail(RP_ERR_INVALID, "%s: n x pairs does not fit", who);
+    return check_queries(who, n == 0 ? 0 : n * pairs, k, nullptr, nullptr, per_query, any_output);
+}
+
+// the two fleet queries for every vehicle of fleet A against every vehicle of fleet B: two tables of 8 d pointers, to
+// n m_a and n m_b values each; windows, level layouts and outputs as in the fleet entries, the outputs n x m_a m_b x k
+int rp_trajectory_cross_separation(int device, void *stream, size_t n, size_t m_a, size_t m_b, size_t k, int d, const double *const *d_fleet_a,
+                                   const double *const *d_fleet_b, const double *d_lo, const double *d_hi, double *d_value, double *d_time)
+{
+    const int st = check_cross(__func__, device, n, m_a, m_b, k, d, nullptr, d_fleet_a, d_fleet_b, {}, {d_value, d_time}, d_value || d_time);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_cross_separation(n, m_a, m_b, k, d, d_fleet_a, d_fleet_b, d_lo, d_hi, d_value, d_time, (hipStream_t)stream));
+    return RP_OK;
+}
+
+int rp_trajectory_cross_contact(int device, void *stream, size_t n, size_t m_a, size_t m_b, size_t k, int d, const double *const *d_fleet_a,
+                                const double *const *d_fleet_b, const double *d_level_sq, int level_per_pair, const double *d_lo,
+                                const double *d_hi, double *d_time, double *d_rate)
+{
+    const int st = check_cross(__func__, device, n, m_a, m_b, k, d, &level_per_pair, d_fleet_a, d_fleet_b,
+                               {{"d_level_sq", d_level_sq}, {"d_time", d_time}}, {level_per_pair ? d_level_sq : nullptr, d_time, d_rate}, true);
+    if (st != RP_OK) return st;
+    RP_HIP(hipSetDevice(device));
+    RP_HIP(rp::launch_cross_contact(n, m_a, m_b, k, d, d_fleet_a, d_fleet_b, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate,
+                                    (hipStream_t)stream));
+    return RP_OK;
+}
+
 // the two fleet entries with a start time per vehicle (n x m, read as single values): the refusals of the entries they extend, a start that is
 // required, and three outputs of which any may be left out but not all
 int rp_trajectory_fleet_separation_staggered(int device, void *stream, size_t n, size_t m, size_t k, int d, const double *const *d_fleet,

@@ -17,6 +17,7 @@
 //   the closest approach of a fleet's pairs    k_fleet                                          section 26
 //   the first contact of a fleet's pairs       k_encounter                                      section 27
 //   ... both with a start time per vehicle     k_stagger, k_rendezvous                          section 28
+//   ... both for one fleet against another     k_versus, k_intercept                            section 34
 //   plot data on the reference's fixed grid    k_sample, k_sample_records
 // The entries are include/rp_batch.h's rp_trajectory_*, rp_batch_trajectory_device, rp_batch_crossing_device, rp_batch_extrema_device,
 // rp_batch_integrals_device and rp_batch_sample*; the launchers are at the end of the file.
@@ -2589,6 +2590,58 @@ k_fleet(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, const 
     });
 }
 
+// ---- the closest approach of every vehicle of one fleet to every vehicle of another (rp_trajectory_cross_separation) ----
+// n scenes of m_a vehicles of fleet A and m_b of fleet B on one clock: A's arrays hold n m_a values, vehicle v of scene s at s m_a + v, B's
+// n m_b, at s m_b + v.  The launch's problems are the n m_a m_b (scene, pair) combinations in output order, pair r = (r / m_b, r % m_b)
+// (fleet_index.h): k_fleet with two tables and a rectangle where it has one table and a triangle.  The scene is not kept in LDS, the windows
+// are n x k and read at s k + the column, and every query is separation_query with a delay of 0.0: k_separation's bits for the gathered pair
+// with a null delay.  pairs <= 2^30, so r_first + a place stays inside 32 bits.
+template <int D> struct CrossSplines { FromArrays a[D], b[D]; };      // a cross entry's tables: fleet A's D splines and fleet B's
+
+// stage_fleet_pair's decode for the rectangle: one 64-bit division for the trip's first scene, 32-bit ones from there
+template <int D>
+__device__ __forceinline__ void stage_cross_pair(SepLds<D> &L, int q, const CrossSplines<D> &in, unsigned m_a, unsigned m_b, unsigned pairs, size_t p)
+{
+    const size_t p_first = p - (size_t)q, s_first = p_first / pairs;
+    const unsigned r = (unsigned)(p_first - s_first * pairs) + (unsigned)q;      // < pairs + kTrajProblems
+    const size_t s = s_first + r / pairs;
+    unsigned i, j;
+    cross_pair(r % pairs, m_b, i, j);
+    stage_vehicles(L, q, in.a, s * m_a + i, in.b, s * m_b + j);
+}
+
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
+k_versus(CrossSplines<D> in, size_t problems, unsigned m_a, unsigned m_b, size_t k, int P, const double *__restrict__ lo,
+         const double *__restrict__ hi, double *__restrict__ value, double *__restrict__ time)
+{
+    __shared__ SepLds<D> L;
+    const unsigned pairs = cross_pair_count(m_a, m_b);
+    auto stage_problem = [&](int q, size_t p) { stage_cross_pair(L, q, in, m_a, m_b, pairs, p); };
+    for_each_trip(problems, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k, s_first = p_first / pairs;
+        const unsigned r_first = (unsigned)(p_first - s_first * pairs);
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            const double inf = __builtin_inf();
+            const size_t sa = s_first + (r_first + (unsigned)qa) / pairs, sb = s_first + (r_first + (unsigned)qb) / pairs;
+            const size_t wa = sa * k + (e - (size_t)qa * k);                            // the scene's row, the query's column
+            const size_t wb = two ? sb * k + (e + 1 - (size_t)qb * k) : wa;
+            const double la = lo ? lo[wa] : -inf, lb = lo ? lo[wb] : -inf, ha = hi ? hi[wa] : inf, hb = hi ? hi[wb] : inf;
+            double va = 0.0, vb = 0.0, ta = 0.0, tb = 0.0;
+#pragma nounroll
+            for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_separation: each query's searches have their own trip counts
+                double v, t;
+                int trips = 0;
+                separation_query(L, half ? qb : qa, half ? lb : la, half ? hb : ha, 0.0, v, t, trips);
+                va = half ? va : v; ta = half ? ta : t;
+                vb = half ? v : vb; tb = half ? t : tb;
+            }
+            if (value) store_pair(value, e_first + e, va, vb, two);
+            if (time) store_pair(time, e_first + e, ta, tb, two);
+        });
+    });
+}
+
 // ---- when two vehicles moving in D axes first come within a distance (rp_trajectory_contact) ----
 // The inverse of section 24's squared distance f, as the meeting is the gap's.  The splines, the NaN rule, the domain, the clamped window
 // [a, b], the knots, the unsorted walk of 2 D + 1 pieces and each piece's quintic g = f' / 2 with its sign-changing roots r0[0..4] are
@@ -2773,6 +2826,44 @@ k_encounter(FleetSplines<D> in, size_t problems, unsigned m, size_t k, int P, co
             // one load_pair for both layouts (the per-scene one is its single-value form, where the window ends are): with a branch around
             // two forms D = 1 spills a register at the four-wave step (section 27)
             load_pair(level, level_per_pair ? e_first + e : wa, two && level_per_pair, pa, pb);
+            if (!level_per_pair) pb = level[wb];
+#pragma nounroll
+            for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_contact: each query's searches have their own trip counts
+                double t, r;
+                int trips = 0;
+                contact_query<D>(L, half ? qb : qa, half ? pb : pa, half ? lb : la, half ? hb : ha, 0.0, t, r, trips);
+                ta = half ? ta : t; ra = half ? ra : r;
+                tb = half ? t : tb; rb = half ? r : rb;
+            }
+            store_pair(time, e_first + e, ta, tb, two);
+            if (rate) store_pair(rate, e_first + e, ra, rb, two);
+        });
+    });
+}
+
+// ---- the first contact of every vehicle of one fleet with every vehicle of another (rp_trajectory_cross_contact) ----
+// k_versus' staging and scene arithmetic around contact_query, as k_encounter is k_fleet's: the level per scene (level_per_pair 0: n x k, read
+// where the window ends are) or per pair (1: n x pairs x k, in the outputs' layout), through k_encounter's single load_pair.  Every query is
+// contact_query with a delay of 0.0: k_contact's bits for the gathered pair with a null delay.
+template <int D>
+__global__ void __launch_bounds__(kTrajBlock) __attribute__((amdgpu_waves_per_eu(D == 3 ? 2 : 4, 8)))
+k_intercept(CrossSplines<D> in, size_t problems, unsigned m_a, unsigned m_b, size_t k, int P, const double *__restrict__ level, int level_per_pair,
+            const double *__restrict__ lo, const double *__restrict__ hi, double *__restrict__ time, double *__restrict__ rate)
+{
+    __shared__ SepLds<D> L;
+    const unsigned pairs = cross_pair_count(m_a, m_b);
+    auto stage_problem = [&](int q, size_t p) { stage_cross_pair(L, q, in, m_a, m_b, pairs, p); };
+    for_each_trip(problems, P, stage_problem, [&](size_t p_first, int here) {
+        const size_t e_first = p_first * k, s_first = p_first / pairs;
+        const unsigned r_first = (unsigned)(p_first - s_first * pairs);
+        stream_pairs(here, k, [&](size_t e, int qa, int qb, bool two) {
+            const double inf = __builtin_inf();
+            const size_t sa = s_first + (r_first + (unsigned)qa) / pairs, sb = s_first + (r_first + (unsigned)qb) / pairs;
+            const size_t wa = sa * k + (e - (size_t)qa * k);                            // the scene's row, the query's column
+            const size_t wb = two ? sb * k + (e + 1 - (size_t)qb * k) : wa;
+            const double la = lo ? lo[wa] : -inf, lb = lo ? lo[wb] : -inf, ha = hi ? hi[wa] : inf, hb = hi ? hi[wb] : inf;
+            double pa, pb, ta = 0.0, tb = 0.0, ra = 0.0, rb = 0.0;
+            load_pair(level, level_per_pair ? e_first + e : wa, two && level_per_pair, pa, pb);      // one form for both layouts, as k_encounter
             if (!level_per_pair) pb = level[wb];
 #pragma nounroll
             for (int half = 0; half < (two ? 2 : 1); ++half) {      // as k_contact: each query's searches have their own trip counts
@@ -3385,6 +3476,24 @@ template <class Launch> hipError_t launch_on_fleet(size_t n, size_t m, size_t k,
     return launch_on_pairs(problems, k, d, [&](auto axes, dim3 grid, dim3 block, int P) { launch(axes, problems, grid, block, P); });
 }
 
+template <int D> CrossSplines<D> cross_splines(const double *const *d_fleet_a, const double *const *d_fleet_b)
+{
+    CrossSplines<D> in;
+    for (int x = 0; x < D; ++x) {
+        in.a[x] = FromArrays{table_of<8>(d_fleet_a + 8 * x)};
+        in.b[x] = FromArrays{table_of<8>(d_fleet_b + 8 * x)};
+    }
+    return in;
+}
+
+// The same over the n m_a m_b (scene, pair) problems of n scenes of two fleets: launch(axes, problems, grid, block, P).
+template <class Launch> hipError_t launch_on_cross(size_t n, size_t m_a, size_t m_b, size_t k, int d, Launch launch)
+{
+    if (m_a < 1 || m_a > kCrossMost || m_b < 1 || m_b > kCrossMost) return hipErrorInvalidValue;
+    const size_t problems = n * cross_pair_count((unsigned)m_a, (unsigned)m_b);
+    return launch_on_pairs(problems, k, d, [&](auto axes, dim3 grid, dim3 block, int P) { launch(axes, problems, grid, block, P); });
+}
+
 }  // namespace
 
 hipError_t launch_trajectory_eval(size_t n, size_t k, const double *const d_spline[8], const double *d_tau, double *d_pos, double *d_vel,
@@ -3635,6 +3744,28 @@ hipError_t launch_fleet_contact(size_t n, size_t m, size_t k, int d, const doubl
         constexpr int D = decltype(axes)::value;
         hipLaunchKernelGGL(k_encounter<D>, grid, block, 0, stream, fleet_splines<D>(d_fleet), problems, (unsigned)m, k, P, d_level_sq,
                            level_per_pair, d_lo, d_hi, d_time, d_rate);
+    });
+}
+
+hipError_t launch_cross_separation(size_t n, size_t m_a, size_t m_b, size_t k, int d, const double *const *d_fleet_a, const double *const *d_fleet_b,
+                                   const double *d_lo, const double *d_hi, double *d_value, double *d_time, hipStream_t stream)
+{
+    return launch_on_cross(n, m_a, m_b, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
+        constexpr int D = decltype(axes)::value;
+        hipLaunchKernelGGL(k_versus<D>, grid, block, 0, stream, cross_splines<D>(d_fleet_a, d_fleet_b), problems, (unsigned)m_a, (unsigned)m_b, k, P,
+                           d_lo, d_hi, d_value, d_time);
+    });
+}
+
+hipError_t launch_cross_contact(size_t n, size_t m_a, size_t m_b, size_t k, int d, const double *const *d_fleet_a, const double *const *d_fleet_b,
+                                const double *d_level_sq, int level_per_pair, const double *d_lo, const double *d_hi, double *d_time,
+                                double *d_rate, hipStream_t stream)
+{
+    if (!d_level_sq || !d_time) return hipErrorInvalidValue;
+    return launch_on_cross(n, m_a, m_b, k, d, [&](auto axes, size_t problems, dim3 grid, dim3 block, int P) {
+        constexpr int D = decltype(axes)::value;
+        hipLaunchKernelGGL(k_intercept<D>, grid, block, 0, stream, cross_splines<D>(d_fleet_a, d_fleet_b), problems, (unsigned)m_a, (unsigned)m_b, k,
+                           P, d_level_sq, level_per_pair, d_lo, d_hi, d_time, d_rate);
     });
 }
 
